@@ -1,9 +1,21 @@
 #!/usr/bin/env python3
 """Benchmark of the fluid time step (BASELINE.json metric: steps/s + Mcells/s, 2D 1024^2 CNN plume & 3D Jacobi, 1-8 GPUs).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--no-graph] [--no-cpu-baseline] [--no-also]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--no-graph] [--full] [--dump-outputs DIR]
+                  [--no-cpu-baseline] [--no-also]
 
 A "step" is one pass of `simulate` over one synthetic plume state that is already resident in HBM.
+
+Plain run and --full.  A plain run does what the headline needs and no more: it builds and develops the state, warms up, times
+EXACTLY K steps and prints the contract fields (`metric`, `value`, `unit`, `n_gpus`, `steps`, `warmup`, `ms_per_step`,
+`higher_is_better`, `dtype`, ...) with `config`.  Everything else described below -- the other configurations (`also`), the CPU
+baselines, the reference-shaped calls (`dropin`), the per-kernel HIP-event profile and roofline blocks, the C++ driver leg at N = 1
+with its middle-rank model, at N > 1 the communicator probe and statistics, and the side file -- runs with `--full` only.
+
+--dump-outputs DIR  after the timed steps, writes what the timed path's last step left in the state the caller holds (U, p,
+density; at N > 1 rank 0's owned planes of the leg that sets `value`) as DIR/<name>.npy, float32, flattened; an array of more
+than DUMP_SAMPLE elements as the elements at a fixed, seeded set of flat indices (sample_outputs), < 64 MB in all.  The inputs are
+synthetic and seeded, so two builds run with the same arguments can be compared output for output.
 
 Launch.  With WORLD_SIZE in the environment (the driver's `python -m torch.distributed.run ... bench.py --gpus N`) this
 process is one rank.  Without it, `--gpus N` (N > 1) re-executes itself under `torch.distributed.run` with N ranks on
@@ -131,6 +143,8 @@ N1_HEADLINE = "plume3d_256_jacobi"   # N = 1: the metric's own 3D configuration;
 BASELINE_CONFIGS = ["plume2d_128_jacobi", "plume2d_1024_cnn", "rt2d_2048_jacobi", "plume3d_256_cnn", "plume3d_slab_jacobi"]
 BF16_MODES = ("bf16x6", "bf16x3")
 JOB_DOG = []                 # the N > 1 job's watchdog timer (main)
+DUMP_SAMPLE = 1 << 22        # --dump-outputs: elements kept per array at most (three arrays of 16 MiB)
+OUTPUT_KEYS = ("U", "p", "density")   # what `simulate` / a slab driver's step updates in the caller's state
 
 
 class Fallback:
@@ -350,9 +364,32 @@ def recorded_traffic(name):
     return (d.get("bytes_per_launch") if d else None), (d or {}).get("source"), d
 
 
-def run_workload(name, steps, warmup, use_graph, world, rank, dev, schedule="deep_first", dropin=False):
-    """Develop the state, warm up, time `steps` steps (barrier + synchronize on both sides, max over ranks), then profile
-    the dominant kernel class with HIP events.  Returns the JSON-able result dict (without cpu_baseline)."""
+def sample_outputs(st, zs=slice(None)):
+    """--dump-outputs: {name: float32 numpy array} of the state's OUTPUT_KEYS (planes `zs`), flattened; an array of more than
+    DUMP_SAMPLE elements as the elements at sorted flat indices drawn with a fixed seed (the same for every build and run)"""
+    import numpy as np
+    import torch
+    got = {}
+    for k in OUTPUT_KEYS:
+        flat = st[k][:, :, zs].contiguous().view(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            idx = np.unique(np.random.default_rng(20240).integers(0, flat.numel(), DUMP_SAMPLE))
+            flat = flat.index_select(0, torch.from_numpy(idx).to(flat.device))
+        got[k] = flat.float().cpu().numpy()
+    return got
+
+
+def write_outputs(dump_dir, got):
+    os.makedirs(dump_dir, exist_ok=True)
+    import numpy as np
+    for k, v in got.items():
+        np.save(os.path.join(dump_dir, k + ".npy"), v)
+
+
+def run_workload(name, steps, warmup, use_graph, world, rank, dev, schedule="deep_first", dropin=False, full=True, dump=False):
+    """Develop the state, warm up, time `steps` steps (barrier + synchronize on both sides, max over ranks), then (`full`) profile
+    the dominant kernel class with HIP events.  Returns the JSON-able result dict (without cpu_baseline); `dump`: with the
+    sample_outputs() of the state after the timed steps under "_outputs"."""
     import torch
     import torch.distributed as dist
     from fluidnet_cxx_amd import FluidNet, simulate
@@ -439,6 +476,37 @@ def run_workload(name, steps, warmup, use_graph, world, rank, dev, schedule="dee
     ms = elapsed / steps * 1e3
     mcells = cells * world * steps / elapsed / 1e6
     finite = bool(torch.isfinite(bd["U"]).all()) and bool(torch.isfinite(bd["p"]).all())
+    outputs = sample_outputs(bd, layout.owned_slice if slab else slice(None)) if dump and rank == 0 else None
+    if w["method"] == "jacobi":
+        step_bytes = STEP_BYTES[is3d](w["iters"]) * cells
+    else:
+        step_bytes = (STEP_BYTES[is3d](0) - (44 if not is3d else 60) + 104) * cells   # advection + CNN glue (SURVEY 8d)
+    if slab:
+        run_workload.slab_state = (bd, m)
+    res = dict(metric="fluid time-step throughput, Mcells/s = cells*steps/s/1e6 (steps/s alongside)", value=mcells,
+               unit="Mcells/s", steps_per_s=steps / elapsed, n_gpus=world, steps=steps, warmup=warmup, ms_per_step=ms,
+               higher_is_better=True, scaling="weak", vs_baseline=None,
+               dtype=f"f32 ({w['precision']} products: opt-in mode)" if w.get("precision") in BF16_MODES else "f32", data="synthetic",
+               config=dict(workload=name, grid_per_gpu=[layout.owned if slab else w["D"], w["res"], w["res"]],
+                           global_grid=[layout.D_global if slab else w["D"], w["res"], w["res"]], batch=w.get("batch", 1),
+                           cells_per_gpu=cells, method=w["method"], jacobi_iters=w["iters"], precision=w.get("precision", "fp32"),
+                           parallelism=("1 GPU" if world == 1 else
+                                        f"{world} z-slabs, neighbour P2P ghost exchange (RCCL send/recv), halo 6, 6 sweeps per exchange, "
+                                        f"schedule {schedule}"),
+                           launch="hip-graph replay" if graph_used else "eager",
+                           developed_steps=develop,
+                           developed_with=("jacobi projection (physical plume), then timed with the CNN" if w["method"] == "convnet"
+                                           else "the timed step itself"),
+                           max_cfl_after_development=umax,
+                           static_flags=static_desc,
+                           state_finite_after_timing=finite,
+                           weights="seeded (pretrained blob absent from the reference)" if net else None),
+               samples_per_s=(w["batch"] * steps / elapsed) if w.get("batch", 1) > 1 else None,
+               step_hbm_frac=step_bytes / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS)
+    if outputs is not None:
+        res["_outputs"] = outputs
+    if not full:
+        return res
 
     # ---- the reference's own call pattern on the same state (single GPU): `simulate(mconf, batch_dict, net, method)` with four
     # arguments, eager -- plume.py:237; workspace and static inputs are the layer's business (_simulate.py) -- and the same step
@@ -531,10 +599,6 @@ def run_workload(name, steps, warmup, use_graph, world, rank, dev, schedule="dee
                     algorithmic=f"{mfma_flops_per_cell(is3d):.0f} direct-convolution FLOP/cell in the MFMA conv launches x {cells} cells per step")
     else:
         roof = jacobi_roofline(name, w, cells, prof_steps, times["jacobi"], traffic, traffic_src, traffic_detail, replay_ms)
-    if w["method"] == "jacobi":
-        step_bytes = STEP_BYTES[is3d](w["iters"]) * cells
-    else:
-        step_bytes = (STEP_BYTES[is3d](0) - (44 if not is3d else 60) + 104) * cells   # advection + CNN glue (SURVEY 8d)
     advect = None
     if is3d and times.get("advect", (0, 0))[1] > 0:
         adv_ms = times["advect"][0] / prof_steps
@@ -543,39 +607,19 @@ def run_workload(name, steps, warmup, use_graph, world, rank, dev, schedule="dee
                       frac_of_model=(120.0 * cells / (adv_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if adv_ms > 0 else None,
                       valu_issue_frac=rec.get("valu_issue_frac"), valu_source=rec.get("valu_source"),
                       note="issue-bound (~1 190 VALU instructions per cell); valu_issue_frac = SQ_INSTS_VALU x 4 cycles / (1024 SIMDs x GRBM_GUI_ACTIVE), recorded PMC pass")
-    if slab:
-        run_workload.slab_state = (bd, m)
-    return dict(advect=advect, metric="fluid time-step throughput, Mcells/s = cells*steps/s/1e6 (steps/s alongside)", value=mcells,
-                unit="Mcells/s", steps_per_s=steps / elapsed, n_gpus=world, steps=steps, warmup=warmup, ms_per_step=ms,
-                higher_is_better=True, scaling="weak", vs_baseline=None,
-                dtype=f"f32 ({w['precision']} products: opt-in mode)" if w.get("precision") in BF16_MODES else "f32", data="synthetic",
-                config=dict(workload=name, grid_per_gpu=[layout.owned if slab else w["D"], w["res"], w["res"]],
-                            global_grid=[layout.D_global if slab else w["D"], w["res"], w["res"]], batch=w.get("batch", 1),
-                            cells_per_gpu=cells, method=w["method"], jacobi_iters=w["iters"], precision=w.get("precision", "fp32"),
-                            parallelism=("1 GPU" if world == 1 else
-                                         f"{world} z-slabs, neighbour P2P ghost exchange (RCCL send/recv), halo 6, 6 sweeps per exchange, "
-                                         f"schedule {schedule}"),
-                            launch="hip-graph replay" if graph_used else "eager",
-                            developed_steps=develop,
-                            developed_with=("jacobi projection (physical plume), then timed with the CNN" if w["method"] == "convnet"
-                                            else "the timed step itself"),
-                            max_cfl_after_development=umax,
-                            static_flags=static_desc,
-                            state_finite_after_timing=finite,
-                            weights="seeded (pretrained blob absent from the reference)" if net else None),
-                samples_per_s=(w["batch"] * steps / elapsed) if w.get("batch", 1) > 1 else None,
-                step_hbm_frac=step_bytes / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                kernel_ms_per_step={k: v[0] / prof_steps for k, v in times.items() if v[1] > 0},
-                roofline=roof, dropin=drop)
+    res.update(advect=advect, kernel_ms_per_step={k: v[0] / prof_steps for k, v in times.items() if v[1] > 0}, roofline=roof, dropin=drop)
+    return res
 
 
-def run_native_slab(steps, warmup, world, rank, dev, bd, m, res, D, schedule="deep_first", transport="rccl", capture=None):
+def run_native_slab(steps, warmup, world, rank, dev, bd, m, res, D, schedule="deep_first", transport="rccl", capture=None, full=True,
+                    dump=False):
     """The SAME per-GPU slab step through the C++ z-slab driver (fnx_slab_step: launches, RCCL ncclSend/ncclRecv and their
     overlap issued from C++, csrc/fnx_slab.hip), continuing from the state the Python-driver run developed; same bits as the
     Python driver (tests/test_slab.py).  At N > 1 it also returns `comm`: a one-off probe of the communicator (ghost exchanges
     of 6 MiB and of 4 KiB with each neighbour: bandwidth and latency of the link as this job sees it), and from a few extra
     steps with the driver's statistics on, the bytes posted per neighbour and step, the number of exchanges, and the time the
-    compute stream stood waiting for posted exchanges (HIP events around each stream wait)."""
+    compute stream stood waiting for posted exchanges (HIP events around each stream wait).  Without `full` only the timed steps
+    (no probe, statistics, roofline or middle-rank model); `dump`: sample_outputs() of rank 0's owned planes under "_outputs"."""
     import torch
     import torch.distributed as dist
     from fluidnet_cxx_amd._ext import ext
@@ -592,7 +636,7 @@ def run_native_slab(steps, warmup, world, rank, dev, bd, m, res, D, schedule="de
         torch.cuda.synchronize()
 
     comm_info = None
-    if world > 1:
+    if world > 1 and full:
         big, small, reps = 6 << 20, 4096, 20
         scratch = torch.zeros(4 * big, dtype=torch.uint8, device=dev)
         ms_big = ext.slab_comm_probe(comm, big, reps, scratch)
@@ -647,6 +691,8 @@ def run_native_slab(steps, warmup, world, rank, dev, bd, m, res, D, schedule="de
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    outputs = sample_outputs(bd, layout.owned_slice) if dump and rank == 0 else None
+    if world > 1 and full:
         # a few more steps with the driver's statistics on (event pairs around each wait: outside the timed region)
         n_stat = 5
         sim._drv.stats_enable(True)
@@ -662,24 +708,25 @@ def run_native_slab(steps, warmup, world, rank, dev, bd, m, res, D, schedule="de
     # the dominant kernel through THIS driver: HIP-event pairs around the solver's launches over a few eager steps (outside the timed
     # region: events cannot be recorded inside a replayed graph).  Partial edge / deep launches of the sweep blocks are in the mean.
     roof = None
-    try:
-        ext.profile_enable(True)
-        n_prof = 3
-        for _ in range(n_prof):
-            sim.step(bd)
-        torch.cuda.synchronize()
-        jac = ext.profile_read(PROF["jacobi"])
-        ext.profile_enable(False)
-        tr, tsrc, tdet = recorded_traffic("plume3d_slab_jacobi")
-        roof = jacobi_roofline("plume3d_slab_jacobi", WORKLOADS["plume3d_slab_jacobi"], res * res * layout.owned, n_prof, jac,
-                               tr if world == 1 else None, tsrc if world == 1 else None, tdet if world == 1 else None)
-        if world > 1:
-            roof["note"] = "mean over the deep and the (shorter) edge launches of the sweep blocks of this rank"
-    except Exception as e:  # noqa: BLE001
-        roof = None
-        sys.stderr.write(f"bench: no roofline from the native leg ({e})\n")
+    if full:
+        try:
+            ext.profile_enable(True)
+            n_prof = 3
+            for _ in range(n_prof):
+                sim.step(bd)
+            torch.cuda.synchronize()
+            jac = ext.profile_read(PROF["jacobi"])
+            ext.profile_enable(False)
+            tr, tsrc, tdet = recorded_traffic("plume3d_slab_jacobi")
+            roof = jacobi_roofline("plume3d_slab_jacobi", WORKLOADS["plume3d_slab_jacobi"], res * res * layout.owned, n_prof, jac,
+                                   tr if world == 1 else None, tsrc if world == 1 else None, tdet if world == 1 else None)
+            if world > 1:
+                roof["note"] = "mean over the deep and the (shorter) edge launches of the sweep blocks of this rank"
+        except Exception as e:  # noqa: BLE001
+            roof = None
+            sys.stderr.write(f"bench: no roofline from the native leg ({e})\n")
     model = None
-    if world == 1 and hasattr(ext, "slab_comm_link_model"):
+    if world == 1 and full and hasattr(ext, "slab_comm_link_model"):
         # One GPU rehearses a MIDDLE rank (rank 1 of 3: 64 owned + 2 x 6 ghost planes) through the same C++ driver with the C ABI's
         # link-model communicator: every ghost exchange occupies the communication stream for latency + bytes / bandwidth and
         # fills the ghost planes from the slab's own edge planes.  A model of N >= 3, not a measurement of it.
@@ -733,6 +780,8 @@ def run_native_slab(steps, warmup, world, rank, dev, bd, m, res, D, schedule="de
         out["middle_rank_model"] = model
     if roof:
         out["roofline"] = roof
+    if outputs is not None:
+        out["_outputs"] = outputs
     return out, comm_info
 
 
@@ -800,6 +849,28 @@ def _roof(rf, long=False):
     return e
 
 
+LEGS = ("native_driver", "native_driver_peer", "native_driver_rccl", "native_driver_rccl_graph", "native_driver_rccl_eager", "python_driver",
+        "comm", "comm_peer", "comm_rccl")
+
+
+def headline(out):
+    """the part of the printed line a plain run prints: the contract fields, `config` (the headline workload) and, at N > 1, the
+    drivers' legs"""
+    line = {k: out[k] for k in ("metric",)}
+    line.update(value=_r(out["value"], 6), unit=out["unit"], n_gpus=out["n_gpus"], steps=out["steps"], warmup=out["warmup"],
+                ms_per_step=_r(out["ms_per_step"], 6), higher_is_better=True, scaling="weak", vs_baseline=None, dtype=out.get("dtype", "f32"),
+                data="synthetic", steps_per_s=_r(out["steps_per_s"], 6))
+    c = out["config"]
+    line["config"] = {k: c.get(k) for k in ("workload", "grid_per_gpu", "global_grid", "method", "jacobi_iters", "parallelism",
+                                            "launch", "driver", "developed_steps", "world_size", "backend") if c.get(k) is not None}
+    line["config"]["state_finite"] = c.get("state_finite_after_timing")
+    for k in LEGS:
+        if isinstance(out.get(k), dict):
+            line[k] = {kk: (_r(vv) if isinstance(vv, float) else vv) for kk, vv in out[k].items()
+                       if kk != "middle_rank_model" and not kk.startswith("_")}
+    return line
+
+
 def compact(out):
     """(the one printed line, the side file's content).  The line (4 kB budget).  The driver's parser keeps the contract fields and
     `config` / `roofline` / `cpu_baseline` whole, so what answers "what fraction of which roof, on the metric's configurations, and what
@@ -812,10 +883,7 @@ def compact(out):
     Beside them: `configs` -- one row per BASELINE.json configuration; `other` -- the remaining workloads; kernel times; at N > 1 the
     drivers' numbers and `comm`."""
     name = out["config"]["workload"]
-    line = {k: out[k] for k in ("metric",)}
-    line.update(value=_r(out["value"], 6), unit=out["unit"], n_gpus=out["n_gpus"], steps=out["steps"], warmup=out["warmup"],
-                ms_per_step=_r(out["ms_per_step"], 6), higher_is_better=True, scaling="weak", vs_baseline=None, dtype=out.get("dtype", "f32"),
-                data="synthetic", steps_per_s=_r(out["steps_per_s"], 6))
+    line = headline(out)
     every = {name: out}
     every.update(out.get("also", {}))
     rows = {k: (_short(v) if "error" not in v else dict(error=v["error"][:100])) for k, v in every.items()}
@@ -823,11 +891,7 @@ def compact(out):
     if cfgs:
         line["configs"] = cfgs
         line["util_of"] = "P: PMC bytes/HBM peak, C: compulsory bytes/HBM peak, M: issued FLOPs/fp32 MFMA peak"
-    c = out["config"]
-    line["config"] = {k: c.get(k) for k in ("workload", "grid_per_gpu", "global_grid", "method", "jacobi_iters", "parallelism",
-                                            "launch", "driver", "developed_steps", "world_size", "backend") if c.get(k) is not None}
     line["config"]["static_flags"] = "tuned: flags+BCs promised static; dropin: detected by simulate()"
-    line["config"]["state_finite"] = c.get("state_finite_after_timing")
     line["config"]["weights"] = "seeded (pretrained blob absent from the reference)"
     line["roofline"] = _roof(out["roofline"], long=True)
     hbm = every.get("plume3d_hbm_jacobi")
@@ -866,10 +930,6 @@ def compact(out):
         line["advect"] = dict(ms=_r(ad["ms_per_step"]), frac_of_120B_model=_r(ad["frac_of_model"], 3), valu_issue_frac=_r(ad.get("valu_issue_frac"), 3))
     if "cpu_baseline" in out:
         line["cpu_baseline"] = {kk: (_r(vv) if isinstance(vv, float) else vv) for kk, vv in out["cpu_baseline"].items()}
-    for k in ("native_driver", "native_driver_peer", "native_driver_rccl", "native_driver_rccl_graph", "native_driver_rccl_eager", "python_driver",
-              "comm", "comm_peer", "comm_rccl"):
-        if isinstance(out.get(k), dict):
-            line[k] = {kk: (_r(vv) if isinstance(vv, float) else vv) for kk, vv in out[k].items() if kk != "middle_rank_model"}
     mm = out.get("native_driver", {}).get("middle_rank_model")
     if mm:                                   # (short form: the sentence that says what it is stays in the side file)
         line["middle_rank_model"] = {kk.replace("modelled_efficiency", "eff"): _r(vv, 3) for kk, vv in mm.items() if kk != "what" and not kk.startswith("ms_at_")}
@@ -917,6 +977,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default=None)
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of HIP-graph replay of the step")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the other configurations, CPU baselines, reference-shaped calls, per-kernel and roofline "
+                         "figures, the C++ driver leg at N = 1, the communicator probe at N > 1 and the side file (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state the last timed step left (U, p, density) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--schedule", default="deep_first", choices=["deep_first", "deep_beside", "edge_first", "last_pass"],
                     help="N > 1: how the slab driver orders a sweep block around its ghost exchange (slab.py)")
@@ -997,7 +1062,8 @@ def main():
         if rehearse:
             raise RuntimeError("skipped in the one-GPU rehearsal (gloo carries no GPU send / recv)")
         out = run_workload(name, a.steps, a.warmup, not a.no_graph, world, rank, dev, a.schedule,
-                           dropin=not a.no_dropin and (a.workload is not None or name in DROPIN))
+                           dropin=a.full and not a.no_dropin and (a.workload is not None or name in DROPIN), full=a.full,
+                           dump=a.dump_outputs is not None)
     except Exception as e:  # noqa: BLE001
         if world == 1:
             raise
@@ -1019,7 +1085,7 @@ def main():
                                  algorithmic=f"16 B/cell/sweep x {w0['iters']} sweeps x {cells0} owned cells per step"))
     out["config"]["world_size"] = dist.get_world_size() if world > 1 else 1
     out["config"]["backend"] = ("gloo (REHEARSAL: all ranks on one GPU, timings meaningless)" if rehearse else "nccl (RCCL)") if world > 1 else None
-    if world == 1 and a.workload is None and not a.no_also:
+    if a.full and world == 1 and a.workload is None and not a.no_also:
         # the other configurations the metric / north star name (single-GPU by definition), measured in the same run
         out["also"] = {}
         for other in ALSO:
@@ -1032,25 +1098,35 @@ def main():
             except Exception as e:  # noqa: BLE001  (an "also" line must not take the headline down)
                 out["also"][other] = dict(error=f"{type(e).__name__}: {e}")
             torch.cuda.empty_cache()
-    if rank == 0 and not a.no_cpu_baseline and world == 1:       # the host baseline is reported with the single-GPU line only
+    if a.full and rank == 0 and not a.no_cpu_baseline and world == 1:       # the host baseline is reported with the single-GPU line only
         out["cpu_baseline"] = cpu_baseline(WORKLOADS[name])
-    if rank == 0 and not a.no_cpu_baseline and world == 1 and a.workload is None and not a.no_also:
+    if a.full and rank == 0 and not a.no_cpu_baseline and world == 1 and a.workload is None and not a.no_also:
         out["cpu_baseline_cnn"] = cpu_baseline(WORKLOADS["plume2d_1024_cnn"], budget_s=6.0)
     done = []
+    dump = a.dump_outputs is not None
 
     def emit():
         for t in JOB_DOG:
             t.cancel()                       # (one line only: the job's watchdog must not add its own behind this one)
         if rank == 0 and not done:
             done.append(1)
+            got = take_outputs()
             try:
-                line, detail = compact(out)
+                line, detail = compact(out) if a.full else (headline(out), None)
             except Exception as e:  # noqa: BLE001  (whatever a leg left behind: the job still prints its line)
                 line = dict(metric=out.get("metric"), value=out.get("value"), unit=out.get("unit"), n_gpus=out.get("n_gpus"), steps=out.get("steps"),
                             warmup=out.get("warmup"), ms_per_step=out.get("ms_per_step"), higher_is_better=True, scaling="weak", vs_baseline=None,
                             dtype="f32", data="synthetic", config=dict(workload=out.get("config", {}).get("workload")),
                             error=f"compact(): {type(e).__name__}: {e}"[:300])
                 detail = dict(error=line["error"])
+            if dump:
+                if got is not None:
+                    write_outputs(a.dump_outputs, got)
+                else:
+                    line["dump_outputs"] = "not written: the leg that set `value` kept no outputs"
+            if not a.full:
+                FALLBACK.publish(json.dumps(line, separators=(",", ":")))        # (a plain run writes no side file)
+                return
             try:
                 os.makedirs(os.path.join(REPO, "gpurun_out"), exist_ok=True)
                 with open(os.path.join(REPO, "gpurun_out", "bench_detail.json"), "w") as f:
@@ -1058,6 +1134,15 @@ def main():
             except OSError as e:
                 line["detail_file"] = f"not written ({e})"
             FALLBACK.publish(json.dumps(line, separators=(",", ":")))
+
+    def take_outputs():
+        """--dump-outputs: the sample_outputs() of the leg whose time is `value` (every leg's are taken out of `out`)"""
+        nd = out.get("native_driver")
+        src = nd if isinstance(nd, dict) and (out["config"].get("driver") or "").startswith("native") else out
+        got = src.get("_outputs")
+        for d in [out] + [out[k] for k in LEGS if isinstance(out.get(k), dict)]:
+            d.pop("_outputs", None)
+        return got
 
     def arm_fallback(before):
         """the line as it stands, with the legs run so far, in the monitor's hands (rank 0, N > 1)"""
@@ -1067,7 +1152,7 @@ def main():
         snap = copy.deepcopy(out)
         try:
             finish()
-            line, _ = compact(out)
+            line = compact(out)[0] if a.full else headline(out)
             line["fallback"] = f"printed by the monitor process: rank 0 ended during the leg '{before}'; the legs before it are in this line"
             FALLBACK.arm(json.dumps(line, separators=(",", ":")))
         except Exception as e:  # noqa: BLE001
@@ -1116,7 +1201,7 @@ def main():
     # the z-slab workload through the C++ driver: the headline at N > 1; at N = 1 a row beside the headline (+ the middle-rank model)
     slab_name = name if WORKLOADS[name].get("slab") else ("plume3d_slab_jacobi" if "plume3d_slab_jacobi" in out.get("also", {})
                                                            and "error" not in out["also"]["plume3d_slab_jacobi"] else None)
-    if slab_name and not a.no_native:
+    if slab_name and not a.no_native and (a.full or world > 1):      # (at N = 1 the Python driver's time is the headline)
         # the same step through the C++ driver.  It has never met more than one GPU before the driver's multi-GPU run, so
         # it runs under a watchdog: if it is not through in time the Python-driver line is printed without it and the job ends
         import threading
@@ -1135,7 +1220,8 @@ def main():
             if rehearse:
                 raise RuntimeError("skipped in the one-GPU rehearsal (RCCL refuses two ranks on one device)")
             out["native_driver"], comm_info = run_native_slab(a.steps, a.warmup, world, rank, dev, bd_s, m_s, WORKLOADS[slab_name]["res"],
-                                                              WORKLOADS[slab_name]["D"], a.schedule)
+                                                              WORKLOADS[slab_name]["D"], a.schedule, full=a.full,
+                                                              dump=dump and world > 1)
             if comm_info:
                 out["comm"] = comm_info
         except Exception as e:  # noqa: BLE001
@@ -1157,7 +1243,7 @@ def main():
                 os.kill(os.getpid(), 9)                    # (tests: a rank dies the way a GPU fault kills it -- no Python runs)
             try:
                 ndp, comm_p = run_native_slab(a.steps, a.warmup, world, rank, dev, bd_s, m_s, WORKLOADS[slab_name]["res"], WORKLOADS[slab_name]["D"],
-                                              a.peer_schedule, transport="peer")
+                                              a.peer_schedule, transport="peer", full=a.full, dump=dump)
                 out["native_driver_peer"] = ndp
                 if comm_p:
                     out["comm_peer"] = comm_p
@@ -1188,7 +1274,7 @@ def main():
             arm_fallback("C++ driver over RCCL captured in a HIP graph")
             try:
                 ndg, _ = run_native_slab(a.steps, a.warmup, world, rank, dev, bd_s, m_s, WORKLOADS[slab_name]["res"], WORKLOADS[slab_name]["D"],
-                                         a.schedule, capture=True)
+                                         a.schedule, capture=True, full=a.full, dump=dump)
                 out["native_driver_rccl_graph"] = ndg
             except Exception as e:  # noqa: BLE001
                 out["native_driver_rccl_graph"] = dict(error=f"{type(e).__name__}: {e}"[:200])

@@ -404,7 +404,7 @@ def test_bench_eight_rank_rehearsal_on_one_gpu(tmp_path):
     import json
     import subprocess
     env = dict(os.environ, PYTHONPATH=REPO)
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "2", "--rehearse-one-gpu", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "2", "--rehearse-one-gpu", "--no-cpu-baseline", "--full"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=str(tmp_path))
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.returncode, r.stdout[-2000:], r.stderr[-3000:])

@@ -4,11 +4,11 @@
 cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 for w in "$@"; do
-rm -rf gpurun_out/prof_span
-timeout 600 rocprofv3 --kernel-trace --output-format csv -d gpurun_out/prof_span -o t -- python bench.py --workload $w --no-cpu-baseline --no-dropin --steps ${STEPS:-30} --warmup 5 > gpurun_out/prof_span_bench.json 2>/dev/null
-python - "$w" <<'PY'
+tmp=$(mktemp -d)
+timeout 600 rocprofv3 --kernel-trace --output-format csv -d $tmp/trace -o t -- python bench.py --full --workload $w --no-cpu-baseline --no-dropin --steps ${STEPS:-30} --warmup 5 > $tmp/bench.json 2>/dev/null
+python - "$w" "$tmp" <<'PY'
 import csv, glob, sys, json, collections
-f = glob.glob('gpurun_out/prof_span/**/*kernel_trace.csv', recursive=True)[0]
+f = glob.glob(sys.argv[2] + '/trace/**/*kernel_trace.csv', recursive=True)[0]
 rows = list(csv.DictReader(open(f)))
 rows.sort(key=lambda r: int(r['Start_Timestamp']))
 # steps start with the first advection kernel; take the timed region = the 30 steps before the profiling steps (eager); find all starts
@@ -17,7 +17,7 @@ for mark in ('pack_div_kernel', 'stage3d_kernel', 'stage2d_div_kernel'):      # 
     idx = [i for i, r in enumerate(rows) if mark in r['Kernel_Name']]
     if idx:
         break
-ms = json.loads(open('gpurun_out/prof_span_bench.json').read().strip().split('\n')[-1])['ms_per_step']
+ms = json.loads(open(sys.argv[2] + '/bench.json').read().strip().split('\n')[-1])['ms_per_step']
 # the run's CNN steps: 5 warm-up (the graph is captured in them) + STEPS timed (replayed) + up to 10 eager ones for the HIP-event profile
 import os
 nst = int(os.environ.get("STEPS", "30"))
@@ -36,4 +36,5 @@ print(f"== {sys.argv[1]}: bench {ms:.4f} ms/step under the profiler; step-to-ste
 for k, v in per.most_common(8):
     print(f"   {v/n:9.1f} us  {k}")
 PY
+rm -rf $tmp
 done

@@ -6,7 +6,8 @@
 set -u
 tag=$1
 mkdir -p gpurun_out/prof_$tag
-timeout 1500 python bench.py --steps 20 --warmup 5 > gpurun_out/prof_$tag/bench_default.log 2>&1
+dst=$_                                   # (the folder the line above made)
+timeout 1500 python bench.py --full --steps 20 --warmup 5 > $dst/bench_default.log 2>&1
 grep "^{\"metric\"" gpurun_out/prof_$tag/bench_default.log | tail -1 > gpurun_out/prof_$tag/bench_default.json
 cp gpurun_out/bench_detail.json gpurun_out/prof_$tag/bench_detail.json
 timeout 300 tools/gpu_profile.sh $tag plume3d_slab_jacobi --steps 20 --warmup 3 --no-native

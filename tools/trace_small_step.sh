@@ -1,7 +1,7 @@
 cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 for w in plume2d_128_jacobi plume2d_1024_jacobi; do
-python bench.py --workload $w --no-cpu-baseline --steps 200 --warmup 20 | cut -c1-700 | tr "," "\n" | grep -i "ms_per_step\|\"jacobi\"\|advect\|stage"
+python bench.py --full --workload $w --no-cpu-baseline --steps 200 --warmup 20 | cut -c1-700 | tr "," "\n" | grep -i "ms_per_step\|\"jacobi\"\|advect\|stage"
 rm -rf gpurun_out/t128
 timeout 300 rocprofv3 --kernel-trace --output-format csv -d gpurun_out/t128 -o t -- python bench.py --workload $w --no-cpu-baseline --steps 3 --warmup 1 --no-graph > /dev/null 2>&1
 python - <<'PY'
