@@ -650,11 +650,7 @@ void launch_sl_mac(const GridDims& g, bool is3d, bool quirks, float dt, const fl
 // z-marching tile kernels (fnx_advect_march.h): the planes of the compute window are cut into chunks so that the
 // launch is a whole number of rounds of resident workgroups (3 per CU); a chunk re-reads 2 lead-in planes.
 static void tile_launch_geometry(const GridDims& g, int& ntx, int& nty, int& zchunk, unsigned& G) {
-  static const int slots = [] {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    return 3 * cus;
-  }();
+  const int slots = 3 * cu_count();
   ntx = (g.W + 63) / 64; nty = (g.H + ATR - 1) / ATR;
   const long ntiles = (long)ntx * nty * g.B;
   long nzc = (2l * slots + ntiles - 1) / ntiles;          // two rounds of workgroups

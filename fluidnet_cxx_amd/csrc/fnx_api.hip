@@ -930,10 +930,10 @@ int fnx_simulate_step(const FnxGrid* g, const FnxStepParams* prm, const FnxState
     // simulate.py:136-142: p, U = net(cat(p, U, flags, density)) -- the net only reads U and flags (model.py:104-126),
     // so the concatenation is not materialised: U is projected in place.
     if (tail_bytes < fnx::fluidnet_ws_bytes(d, g->is3D)) return fail(FNX_EWORKSPACE, "simulate_step: workspace too small for the CNN");
-    if (prm->precision_mode < FNX_PRECISION_FP32 || prm->precision_mode > FNX_PRECISION_FP32_F2)
-      return fail(FNX_EINVAL, "simulate_step: unknown precision_mode %d", prm->precision_mode);
+    const int mode = fnx::net_mode(prm->precision_mode);
+    if (mode < 0) return fail(FNX_EINVAL, "simulate_step: unknown precision_mode %d", prm->precision_mode);
     // without flags_stick the tail of the net's forward and the step's last setConstVals are one pass (fluidnet_core)
-    if (int rc = fnx::fluidnet_core(g, st->net, st->flags, prm->normalize_threshold, prm->precision_mode, st->p, st->U, tail, stream,
+    if (int rc = fnx::fluidnet_core(g, st->net, st->flags, prm->normalize_threshold, mode, st->p, st->U, tail, stream,
                                     stick ? nullptr : st)) return rc;
     if (!stick) { HIP_OK(hipGetLastError()); return FNX_OK; }
     if (int rc = stick_pass()) return rc;                                       // simulate.py:165-166

@@ -19,8 +19,8 @@ constexpr ConvLayer LAYERS[N_LAYERS] = {
     // final 1x1
     {8, 1, 1, 0}};
 
-inline int layer_taps(const ConvLayer& L, bool is3d) { return L.k * L.k * (is3d ? L.k : 1); }
-inline size_t layer_weight_floats(const ConvLayer& L, bool is3d) { return (size_t)L.cout * L.cin * layer_taps(L, is3d); }
+constexpr int layer_taps(const ConvLayer& L, bool is3d) { return L.k * L.k * (is3d ? L.k : 1); }
+constexpr size_t layer_weight_floats(const ConvLayer& L, bool is3d) { return (size_t)L.cout * L.cin * layer_taps(L, is3d); }
 
 size_t scalenet_weight_floats(bool is3d);
 size_t scalenet_packed_bytes(bool is3d);
@@ -62,6 +62,9 @@ void launch_pack_div(const GridDims& g, bool is3d, const float* U, const float* 
 struct FnxGrid;
 struct FnxState;
 namespace fnx {
+// precision_mode (FNX_PRECISION_*) as the CNN launchers dispatch on it: FNX_PRECISION_FP32_F4 names what FNX_PRECISION_FP32 runs and
+// becomes it; -1: no such mode.  The C ABI entry points map it once; everything below them takes the mapped value.
+int net_mode(int precision_mode);
 // bcs != nullptr: the fused step's form -- the last setConstVals of the step (simulate.py:168) is part of the pass behind the
 // net (bcs supplies density, the BC arrays, bc_class and density_bc_applied; p_out must not be the workspace)
 int fluidnet_core(const FnxGrid* g, const void* packed, const float* flags, float thr, int precision_mode, float* p_out, float* U,

@@ -1,9 +1,9 @@
 // MultiScale pressure-net forward (lib/multi_scale_net.py:118-127, lib/model.py:76-227) for gfx950.
 //
 // The 32/64/128-channel 3x3(x3) layers (95 % of the FLOPs) run as implicit GEMM on the matrix cores in exact fp32
-// (conv3_mfma_kernel, 32x32x2 MFMA); the 5x5(x5) layers 3->32 and 32->8 on the 16x16x4 MFMA (conv5_mfma16_kernel);
-// the remaining thin layers (2->32 and 32->1 3x3, the final 1x1) are bandwidth-shaped and use a direct kernel
-// (a strip of output pixels x CO_T output channels per thread, weights through the scalar cache).
+// (conv3_mfma_kernel, 32x32x2 MFMA); the 5x5(x5) layers 3->32 and 32->8 on the 16x16x4 MFMA (conv5_mfma16_kernel, the 32->8
+// layer with the final 1x1 in its epilogue); the remaining thin layers (2->32 and 32->1 3x3) are bandwidth-shaped and use direct
+// kernels (conv_direct_kernel, conv3_to1_kernel).  Which kernel family runs a layer and where its weights sit: PLAN.
 #include "fnx_cnn.h"
 #include <assert.h>
 #include <stdlib.h>
@@ -13,61 +13,100 @@
 
 namespace fnx {
 // (every error return sets the thread's message: the Python layer raises fnx_last_error(), which would otherwise be an earlier call's text)
-inline int launch_status() {
+inline int launch_status(bool is3d) {
   const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? FNX_OK : set_error(FNX_EHIP, "HIP error in a CNN launch: %s (a grid the net cannot take -- 3D: D a multiple of 4?)", hipGetErrorString(e));
+  return e == hipSuccess ? FNX_OK : set_error(FNX_EHIP, "HIP error in a CNN launch: %s%s", hipGetErrorString(e),
+                                              is3d ? " (a grid the net cannot take -- D a multiple of 4?)" : "");
 }
 
 
 namespace {
 
 inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-inline int co_tile(int cout) { return cout >= 16 ? 16 : cout; }
+constexpr int co_tile(int cout) { return cout >= 16 ? 16 : cout; }
+constexpr int pad_to(int v, int m) { return (v + m - 1) / m * m; }
 
-struct PackedLayer { size_t w_off, b_off; };   // float offsets into the packed buffer
+// ---------------------------------------------------------------------------------------------------
+// The plan of a layer: the kernel family that runs it and where each of its images sits in the packed buffer.  scalenet_pack,
+// launch_conv and the towers' tail fusion take both from PLAN and derive neither.
+// ---------------------------------------------------------------------------------------------------
+enum class Family {
+  DIRECT,   // conv_direct_kernel, packed [Cout/CO_T][Cin][taps][CO_T]: the 2->32 3x3(x3) layer; the final 1x1 only runs fused (PAIR)
+  TO1,      // conv3_to1_kernel: 3x3(x3) to one channel, the half- and quarter-resolution towers' last layers
+  PAIR,     // conv5_mfma16_kernel PAIR: 5x5(x5) 32->8 with the next layer (1x1, 8->1) in its epilogue
+  KPACK,    // conv5_mfma16_kernel with K packed over (tap, channel): 5x5(x5) 3->32
+  MFMA,     // 3x3(x3), Cin % 16 == 0, Cout % 32 == 0: bf16 pieces, F(4x4), F(2x2) or implicit GEMM (launch_conv)
+};
+struct LayerPlan {
+  Family fam;
+  bool wide;        // MFMA with Cout % 64 == 0: also has the bf16 and F(4x4) images
+  // float offsets into the packed buffer
+  size_t taps;      // the family's tap image (MFMA: [taps][Cin][Cout], the implicit GEMM's A operand)
+  size_t wino2;     // MFMA: G g G^T as [dz][16][Cin][Cout] (read by the pack kernels only)
+  size_t wino3;     // MFMA: the same values stage-contiguous (conv3_wino3_kernel)
+  size_t wbf;       // wide: G g G^T cut into three bf16 pieces in conv3_wbf_kernel's operand layout (1.5x the fp32 image)
+  size_t wino4;     // wide: the nine taps in conv3_wino4_kernel's lane order ([Cin/4][Cout/64][9][4][4][16] per z tap)
+  size_t bias;
+};
+struct NetPlan { LayerPlan layer[N_LAYERS]; };
 
-// 5x5(x5) layers (Cin 3 or 32, Cout 32 or 8) run on v_mfma_f32_16x16x4_f32: Cin is padded to a multiple of 4 (one
-// k-step) and Cout to a multiple of 16 (one M block) with zero weights.
-inline bool mfma16_layer(const ConvLayer& L) { return L.k == 5 && (L.cin % 8 == 0 || L.cin <= 4) && L.cout <= 32; }
-inline int pad_to(int v, int m) { return (v + m - 1) / m * m; }
-// Cout <= 8 (and a Cin the 8-channel stage fits): two x-adjacent pixels share one 16-row M block (conv5_mfma16_kernel PAIR)
-inline bool pair_layer(int cin, int cout) { return cout <= 8 && cin % 8 == 0; }
-inline bool mfma_layer(const ConvLayer& L) { return L.k == 3 && L.cin % 16 == 0 && L.cout % 32 == 0; }
-// the 3x3(x3) MFMA layers also run in the Winograd domain (conv3_wino3_kernel): their transformed weights G g G^T
-// ([dz][16][Cin][Cout], then the same values in the kernel's stage-contiguous order) follow the [tap][Cin][Cout] image
-inline bool wino_layer(const ConvLayer& L, bool is3d) { (void)is3d; return mfma_layer(L); }
-// FNX_PRECISION_BF16X6 (conv3_wbf_kernel): the wino layers with 64 output channels per workgroup; their transformed weights
-// cut into three bf16 pieces, in the kernel's MFMA operand layout (1.5x the fp32 image), follow the two fp32 images
-inline bool wbf_layer(const ConvLayer& L, bool is3d) { return wino_layer(L, is3d) && L.cin % 16 == 0 && L.cout % 64 == 0; }
-// FNX_PRECISION_FP32 (3D) / _FP32_F4 (conv3_wino4_kernel, fnx_cnn_wino4.h): the wino layers with 64 output channels per workgroup; their nine
-// taps in the kernel's lane order ([Cin/4][Cout/64][9][4][4][16], 9 Cin Cout floats: G g G^T is formed in registers) follow the bf16 image
-inline bool wino4_layer_(const ConvLayer& L, bool is3d) { (void)is3d; return L.k == 3 && L.cin % 16 == 0 && L.cout % 64 == 0; }
-inline size_t wino4_offset(const ConvLayer& L, bool is3d) {      // floats from the layer's w_off to its F(4x4) image
-  const size_t nwino = (size_t)16 * (is3d ? 3 : 1) * L.cin * L.cout;
-  return layer_weight_floats(L, is3d) + 2 * nwino + (wbf_layer(L, is3d) ? nwino * 3 / 2 : 0);
+constexpr Family family_of(const ConvLayer& L) {
+  if (L.k == 3 && L.cin % 16 == 0 && L.cout % 32 == 0) return Family::MFMA;
+  if (L.k == 3 && L.cout == 1 && L.cin % 4 == 0) return Family::TO1;
+  if (L.k == 5 && L.cout == 8 && L.cin % 8 == 0) return Family::PAIR;
+  if (L.k == 5 && L.cin == 3 && L.cout > 16 && L.cout <= 32) return Family::KPACK;
+  return Family::DIRECT;
 }
-inline size_t packed_weight_floats(const ConvLayer& L, bool is3d) {
-  if (wino_layer(L, is3d))
-    return layer_weight_floats(L, is3d) + 2 * (size_t)16 * (is3d ? 3 : 1) * L.cin * L.cout +
-           (wbf_layer(L, is3d) ? (size_t)16 * (is3d ? 3 : 1) * L.cin * L.cout * 3 / 2 : 0) +
-           (wino4_layer_(L, is3d) ? (size_t)(is3d ? 27 : 9) * L.cin * L.cout : 0);
-  if (mfma16_layer(L) && pair_layer(L.cin, L.cout)) return (size_t)(is3d ? 5 : 1) * 30 * pad_to(L.cin, 4) * 16;
-  if (mfma16_layer(L)) return (size_t)layer_taps(L, is3d) * pad_to(L.cin, 4) * pad_to(L.cout, 16);
-  return layer_weight_floats(L, is3d);
-}
-
-PackedLayer packed_layer(int l, bool is3d) {
-  size_t off = 0;
-  PackedLayer r{0, 0};
-  for (int i = 0; i <= l; ++i) {
-    r.w_off = off;
-    off += packed_weight_floats(LAYERS[i], is3d);
-    r.b_off = off;
-    off += LAYERS[i].cout;
-    off = (off + 63) & ~(size_t)63;
+// what the launchers assume of the table: a PAIR layer is followed by the 1x1 8->1 (no ReLU) it fuses, and a DIRECT layer that
+// launches on its own is 3x3(x3) with whole 16-channel output groups
+constexpr bool plan_ok() {
+  for (int l = 0; l < N_LAYERS; ++l) {
+    const ConvLayer& L = LAYERS[l];
+    if (family_of(L) == Family::PAIR &&
+        !(l + 1 < N_LAYERS && LAYERS[l + 1].k == 1 && LAYERS[l + 1].cin == 8 && LAYERS[l + 1].cout == 1 && !LAYERS[l + 1].relu))
+      return false;
+    if (family_of(L) == Family::DIRECT && !(L.k == 3 && L.cout % 16 == 0) && !(l > 0 && family_of(LAYERS[l - 1]) == Family::PAIR))
+      return false;
   }
-  return r;
+  return true;
 }
+static_assert(plan_ok(), "LAYERS holds a layer no launcher takes");
+
+constexpr NetPlan make_plan(bool is3d) {
+  NetPlan P{};
+  size_t off = 0;
+  for (int l = 0; l < N_LAYERS; ++l) {
+    const ConvLayer& L = LAYERS[l];
+    LayerPlan& p = P.layer[l];
+    p.fam = family_of(L);
+    p.taps = off;
+    const size_t kd = is3d ? L.k : 1, nw = layer_weight_floats(L, is3d);
+    switch (p.fam) {
+      case Family::MFMA: {
+        const size_t nwino = 16 * kd * L.cin * L.cout;
+        p.wide = L.cout % 64 == 0;
+        p.wino2 = off + nw;
+        p.wino3 = p.wino2 + nwino;
+        off = p.wino3 + nwino;
+        if (p.wide) {
+          p.wbf = off;
+          p.wino4 = p.wbf + nwino * 3 / 2;
+          off = p.wino4 + 9 * kd * L.cin * L.cout;
+        }
+        break;
+      }
+      case Family::PAIR: off += kd * 30 * pad_to(L.cin, 4) * 16; break;    // [dz][r][wx 0..5][Cin padded to 4][16]
+      // [taps][Cin padded to 4][Cout padded to 16], of which the packed-K image [dz][(25 Cin) padded to 4][Cout padded to 32] uses the front
+      case Family::KPACK: off += (size_t)layer_taps(L, is3d) * pad_to(L.cin, 4) * pad_to(L.cout, 16); break;
+      default: off += nw;
+    }
+    p.bias = off;
+    off = (off + L.cout + 63) & ~(size_t)63;
+  }
+  return P;
+}
+constexpr NetPlan PLAN[2] = {make_plan(false), make_plan(true)};
+inline const LayerPlan* plan(bool is3d) { return PLAN[is3d].layer; }
 
 // blob: (Cout,Cin,taps) -> packed [taps][Cin][Cout]   (implicit-GEMM layers: the A operand of the MFMA reads 32
 // consecutive output channels per lane half)
@@ -83,24 +122,9 @@ __global__ void pack_layer_mfma_kernel(const float* __restrict__ w, const float*
   for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < cout; q += gridDim.x * blockDim.x) pb[q] = bias[q];
 }
 
-// blob: (Cout,Cin,taps) -> packed [taps][Cin padded to 4][Cout padded to 16], zeros in the padding
-__global__ void pack_layer_mfma16_kernel(const float* __restrict__ w, const float* __restrict__ bias,
-                                         float* __restrict__ pw, float* __restrict__ pb, int cin, int cout, int taps,
-                                         int cin_pad, int cout_pad) {
-  const int n = taps * cin_pad * cout_pad;
-  for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < n; q += gridDim.x * blockDim.x) {
-    const int co = q % cout_pad;
-    const int r = q / cout_pad;
-    const int ci = r % cin_pad, t = r / cin_pad;
-    pw[q] = (co < cout && ci < cin) ? w[((size_t)co * cin + ci) * taps + t] : 0.f;
-  }
-  for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < cout; q += gridDim.x * blockDim.x) pb[q] = bias[q];
-}
-
 // Cin of 2 or 3 (the first layer of a scale): the MFMA K runs over (tap, channel) pairs of a z plane, k = tap * Cin + channel,
 // padded to a multiple of 4 -- 13 / 19 K-groups of four per plane instead of 25 with one or two empty channels each
-// (conv5_mfma16_kernel<4, 2, ., false, KPC>).  0: the layer does not take that form.
-inline int kpack_cin(int cin, int cout) { return (cin == 2 || cin == 3) && cout > 16 && cout <= 32 ? cin : 0; }   // (Cout padded to 32: MB = 2)
+// (Family::KPACK: conv5_mfma16_kernel<4, 2, ., false, KPC = Cin>, Cout padded to 32).
 // blob: (Cout,Cin 2|3,taps 5x5[x5]) -> packed [dz][k = (r*5+s)*Cin + ci, padded to 4][Cout padded to 32], zeros in the padding
 __global__ void pack_layer_kpack_kernel(const float* __restrict__ w, const float* __restrict__ bias, float* __restrict__ pw,
                                         float* __restrict__ pb, int cin, int cout, int kd, int cout_pad) {
@@ -156,7 +180,7 @@ struct ConvArgs {
   const float* tail_w; const float* tail_b;
 };
 
-// Thin layers (Cin 2-3 or Cout 1-8): direct convolution.  A thread owns a vertical strip of RY output pixels x CO_T
+// Thin layers (the 2->32 3x3(x3) layer: KS 3, CO_T 16): direct convolution.  A thread owns a vertical strip of RY output pixels x CO_T
 // output channels, so each input row it loads (coalesced along x across the wave) feeds up to KS output rows:
 // (RY+KS-1)*KS loads per RY*KS*KS taps instead of one load per tap.
 template <int KS, int CO_T, bool IS3D, int RY>
@@ -219,14 +243,12 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(ConvArgs a) {
   }
 }
 
-template <int KS, bool IS3D>
-void launch_conv_k(const ConvArgs& a, hipStream_t s) {
-  constexpr int RY = (KS == 1) ? 1 : 4;
+// Family::DIRECT (3x3(x3), Cout a multiple of 16: plan_ok), and the MFMA layers beyond what the MFMA kernels can address
+void launch_conv_direct(const ConvArgs& a, bool is3d, hipStream_t s) {
+  constexpr int RY = 4;
   const dim3 grid((a.W + 63) / 64, (a.H + 4 * RY - 1) / (4 * RY), a.B * a.groups * a.D), block(64, 4);
-  const int cot = co_tile(a.cout);
-  if (cot == 16) conv_direct_kernel<KS, 16, IS3D, RY><<<grid, block, 0, s>>>(a);
-  else if (cot == 8) conv_direct_kernel<KS, 8, IS3D, RY><<<grid, block, 0, s>>>(a);
-  else conv_direct_kernel<KS, 1, IS3D, RY><<<grid, block, 0, s>>>(a);
+  if (is3d) conv_direct_kernel<3, 16, true, RY><<<grid, block, 0, s>>>(a);
+  else conv_direct_kernel<3, 16, false, RY><<<grid, block, 0, s>>>(a);
 }
 
 // 3x3(x3) convolution to ONE output channel (the towers' last layers, 32 -> 1, at half and quarter resolution).  In the strip
@@ -526,9 +548,6 @@ __global__ __launch_bounds__(256, WPS) void conv3_mfma_kernel(ConvArgs a) {
 #ifndef W3_ABL
 #define W3_ABL 0
 #endif
-#ifndef W3_HDMA
-#define W3_HDMA 1
-#endif
 constexpr int WCOLS = 34;                              // halo tile row: 32 pixels + halo
 constexpr int W3C = 4;                                 // input channels per stage of conv3_wino3_kernel
 inline int wino3_rw(int cout) { return cout % 64 == 0 ? 64 : 32; }   // its output channels per workgroup
@@ -549,7 +568,7 @@ __global__ __launch_bounds__(128 * NCG * NPG, 2) void conv3_wino3_kernel(ConvArg
   static_assert(NWI % NWV == 0 && UPT <= 4, "stage shape");
   // HDMA (the 8-wave variant: one workgroup per CU has the LDS): the halo tile goes global -> LDS by DMA into a ring of four copies;
   // the 4-wave variants (two workgroups per CU, 80 KB each) take it through registers into two
-  constexpr bool HDMA = W3_HDMA && NCG * NPG == 4;
+  constexpr bool HDMA = NCG * NPG == 4;
   constexpr int RAWN = HDMA ? NLD * NT : NEL;            // (DMA: the lanes of the last instruction beyond the tile land in the padding)
   __shared__ __attribute__((aligned(16))) float raw0[RAWN];
   __shared__ __attribute__((aligned(16))) float raw1[RAWN];
@@ -1010,7 +1029,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // PAIR (Cout <= 8): the 16 rows of the M block are (dx, cout) for TWO x-adjacent output pixels, the 16 columns are pixel
 // pairs, and k runs over a 6-wide window per tap row (weights zero where the tap falls outside an output's 5): 30
 // k-positions per row-plane instead of 2 x 25 half-empty ones -- 0.6x the MFMAs of the plain mapping for 32->8.
-// KPC (2 or 3 = Cin; 0: off): K packed over (tap, channel), see kpack_cin.
+// KPC (2 or 3 = Cin; 0: off): K packed over (tap, channel), see pack_layer_kpack_kernel.
 template <int CHS, int MB, bool IS3D, bool PAIR, int KPC = 0>
 __global__ __launch_bounds__(256, 2) void conv5_mfma16_kernel(ConvArgs a, int cin_pad) {
   constexpr int KS = 5, PAD = 2, PR = 2;
@@ -1227,25 +1246,15 @@ __global__ __launch_bounds__(256, 2) void conv5_mfma16_kernel(ConvArgs a, int ci
   }
 }
 
-void launch_conv_mfma16(const ConvArgs& a, bool is3d, hipStream_t s) {
+// Family::PAIR (Cout 8, the 1x1 tail in the epilogue) or Family::KPACK (Cin 3)
+void launch_conv_mfma16(const ConvArgs& a, bool is3d, bool pair, hipStream_t s) {
   const dim3 grid((a.W + 63) / 64, (a.H + 7) / 8, a.B * a.D);
   const int cin_pad = pad_to(a.cin, 4);
-  if (pair_layer(a.cin, a.cout)) {
+  if (pair) {
     if (is3d) conv5_mfma16_kernel<4, 1, true, true><<<grid, 256, 0, s>>>(a, cin_pad);
     else conv5_mfma16_kernel<4, 1, false, true><<<grid, 256, 0, s>>>(a, cin_pad);
-  } else if (a.cin % 8 == 0 && a.cout <= 16) {
-    if (is3d) conv5_mfma16_kernel<8, 1, true, false><<<grid, 256, 0, s>>>(a, cin_pad);
-    else conv5_mfma16_kernel<8, 1, false, false><<<grid, 256, 0, s>>>(a, cin_pad);
-  } else if (kpack_cin(a.cin, a.cout) == 3) {
-    if (is3d) conv5_mfma16_kernel<4, 2, true, false, 3><<<grid, 256, 0, s>>>(a, cin_pad);
-    else conv5_mfma16_kernel<4, 2, false, false, 3><<<grid, 256, 0, s>>>(a, cin_pad);
-  } else if (kpack_cin(a.cin, a.cout) == 2) {
-    if (is3d) conv5_mfma16_kernel<4, 2, true, false, 2><<<grid, 256, 0, s>>>(a, cin_pad);
-    else conv5_mfma16_kernel<4, 2, false, false, 2><<<grid, 256, 0, s>>>(a, cin_pad);
-  } else {
-    if (is3d) conv5_mfma16_kernel<4, 2, true, false><<<grid, 256, 0, s>>>(a, cin_pad);
-    else conv5_mfma16_kernel<4, 2, false, false><<<grid, 256, 0, s>>>(a, cin_pad);
-  }
+  } else if (is3d) conv5_mfma16_kernel<4, 2, true, false, 3><<<grid, 256, 0, s>>>(a, cin_pad);
+  else conv5_mfma16_kernel<4, 2, false, false, 3><<<grid, 256, 0, s>>>(a, cin_pad);
 }
 
 template <int CB, int PR, int CH = MF_CHUNK, int WPS = 2>
@@ -1271,7 +1280,7 @@ void launch_conv_mfma(const ConvArgs& a, bool is3d, hipStream_t s) {
 
 // Winograd F(2x2,3x3) for the 3x3(x3) MFMA layers, when the launch fills the chip (one persistent workgroup per CU slot);
 // false: nothing launched (small grid), the caller uses the direct kernel
-bool launch_conv_wino(const ConvArgs& a, bool is3d, const float* wt, hipStream_t s) {
+bool launch_conv_wino(const ConvArgs& a, bool is3d, const float* w3, hipStream_t s) {
   if (a.cin % (4 * W3C) != 0 || a.cout % 32 != 0) return false;
   if (a.D != 1 && !is3d) return false;
   if ((size_t)16 * a.D * a.H * a.W * 4 >= 0xfffffff0u) return false;   // the epilogue's 32-bit offsets span a wave's 16 output channels
@@ -1282,11 +1291,9 @@ bool launch_conv_wino(const ConvArgs& a, bool is3d, const float* wt, hipStream_t
   if (ncg == 2 && (long)((a.W + 31) / 32) * ((a.H + 7) / 8) * a.B * a.D * (a.cout / 64) >= 512) npg = 2;   // 8 waves
   if (ncg == 1) npg = 2;
   assert(wino3_rw(a.cout) == 32 * ncg);
-  const float* w3 = wt + (size_t)16 * (is3d ? 3 : 1) * a.cin * a.cout;   // the stage-contiguous image follows [dz][16][Cin][Cout]
   const int ntx = (a.W + 31) / 32, nty = (a.H + 4 * npg - 1) / (4 * npg);
   const long nt = (long)ntx * nty * a.B * a.D * (a.cout / (32 * ncg));
-  static const int ncu = [] { int d = 0; hipDeviceProp_t pr; hipGetDevice(&d); hipGetDeviceProperties(&pr, d); return pr.multiProcessorCount; }();
-  const int slots = ncu * (ncg * npg == 4 ? 1 : 2);      // 8-wave workgroups fill a CU's registers; two 4-wave ones fit
+  const int slots = cu_count() * (ncg * npg == 4 ? 1 : 2);      // 8-wave workgroups fill a CU's registers; two 4-wave ones fit
   if (nt < (npg * ncg == 4 ? 512 : 1024) || nt > 0x7fffffffl) return false;
   const int nwg = (int)(nt < slots ? nt : slots);
   if (is3d) {
@@ -1299,66 +1306,60 @@ bool launch_conv_wino(const ConvArgs& a, bool is3d, const float* wt, hipStream_t
   return true;
 }
 
-// mode: FNX_PRECISION_* (FP32_DIRECT: no Winograd, every layer a direct sum over its taps; BF16X6: conv3_wbf_kernel where it applies)
-// tail: the packed layer of a following 1x1 convolution to one channel that the launch applies in its epilogue (y then has one
-// channel); only for the PAIR 5x5 layer (fuses_tail)
-inline bool fuses_tail(const ConvLayer& L, const ConvLayer& next) {
-  return mfma16_layer(L) && pair_layer(L.cin, L.cout) && L.cout == 8 && next.k == 1 && next.cin == L.cout && next.cout == 1 && !next.relu;
-}
-void launch_conv(const ConvLayer& L, bool is3d, int mode, const float* packed, const PackedLayer& pl, const float* x, float* y,
-                 int B, int D, int H, int W, hipStream_t s, const PackedLayer* tail = nullptr) {
-  ConvArgs a{x, y, packed + pl.w_off, packed + pl.b_off, B, L.cin, L.cout, D, H, W, L.relu, L.cout / co_tile(L.cout),
-             tail ? packed + tail->w_off : nullptr, tail ? packed + tail->b_off : nullptr};
-  // (the MFMA kernels address a stage of 8 channel volumes through one 32-bit buffer range: 2^27 cells per sample at
-  // most; beyond that -- 137 GB per 128-channel activation -- the direct kernel below still works)
-  const bool direct = mode == FNX_PRECISION_FP32_DIRECT;
-  if ((mode == FNX_PRECISION_BF16X6 || mode == FNX_PRECISION_BF16X3) && wbf_layer(L, is3d)) {
-    ProfScope ps(FNX_PROF_CONV_BF16, s);
-    const size_t nwino = (size_t)16 * (is3d ? 3 : 1) * L.cin * L.cout;
-    const int nprod = mode == FNX_PRECISION_BF16X3 ? 3 : 6;
-    if (launch_conv_wbf(a, is3d, (const unsigned*)(packed + pl.w_off + layer_weight_floats(L, is3d) + 2 * nwino), s, nprod)) {
-      // six (three) bf16 MFMA products per Winograd-domain multiply (16 per 2x2 outputs and z tap)
-      prof_add_work(FNX_PROF_CONV_BF16, (double)B * D * H * W * 2.0 * L.cin * L.cout * 4.0 * (is3d ? 3 : 1) * (double)nprod);
+// Layer l of the net from x into y.  mode: FNX_PRECISION_* as net_mode leaves it (FP32_DIRECT: no Winograd, every layer a direct sum over
+// its taps; BF16X6 / BF16X3: conv3_wbf_kernel where it applies).  A PAIR layer also applies layer l + 1 (y then has one channel).
+void launch_conv(int l, bool is3d, int mode, const float* packed, const float* x, float* y, int B, int D, int H, int W, hipStream_t s) {
+  const ConvLayer& L = LAYERS[l];
+  const LayerPlan& P = plan(is3d)[l];
+  const LayerPlan* tail = P.fam == Family::PAIR ? &plan(is3d)[l + 1] : nullptr;
+  ConvArgs a{x, y, packed + P.taps, packed + P.bias, B, L.cin, L.cout, D, H, W, L.relu, L.cout / co_tile(L.cout),
+             tail ? packed + tail->taps : nullptr, tail ? packed + tail->bias : nullptr};
+  switch (P.fam) {
+    case Family::MFMA: {
+      if ((mode == FNX_PRECISION_BF16X6 || mode == FNX_PRECISION_BF16X3) && P.wide) {
+        ProfScope ps(FNX_PROF_CONV_BF16, s);
+        const int nprod = mode == FNX_PRECISION_BF16X3 ? 3 : 6;
+        if (launch_conv_wbf(a, is3d, (const unsigned*)(packed + P.wbf), s, nprod)) {
+          // six (three) bf16 MFMA products per Winograd-domain multiply (16 per 2x2 outputs and z tap)
+          prof_add_work(FNX_PROF_CONV_BF16, (double)B * D * H * W * 2.0 * L.cin * L.cout * 4.0 * (is3d ? 3 : 1) * (double)nprod);
+          return;
+        }
+      }
+      // (the MFMA kernels address a stage of 8 channel volumes through one 32-bit buffer range: 2^27 cells per sample at
+      // most; beyond that -- 137 GB per 128-channel activation -- the direct kernel still works)
+      if ((size_t)MF_CHUNK * D * H * W * 4 >= 0xf0000000ull) break;
+      ProfScope ps(FNX_PROF_CONV_MFMA, s);
+      const double px = (double)B * D * H * W, mac = 2.0 * L.cin * L.cout;
+      // F(4x4): the default (256^3 CNN step 92.2 -> 81.0 ms; 1024^2 2.29 -> 2.14 ms: replayed graphs, alternating runs on one box)
+      if (mode == FNX_PRECISION_FP32 && P.wide && launch_conv_wino4(a, packed + P.wino4, is3d, s)) {
+        prof_add_work(FNX_PROF_CONV_MFMA, px * mac * 2.25 * (is3d ? 3 : 1));  // 36 multiplies per 4x4 outputs (per z tap)
+        return;
+      }
+      if (mode != FNX_PRECISION_FP32_DIRECT && launch_conv_wino(a, is3d, packed + P.wino3, s)) {
+        prof_add_work(FNX_PROF_CONV_MFMA, px * mac * 4.0 * (is3d ? 3 : 1));   // 16 multiplies per 2x2 outputs (per z tap)
+        return;
+      }
+      launch_conv_mfma(a, is3d, s);
+      prof_add_work(FNX_PROF_CONV_MFMA, px * mac * layer_taps(L, is3d));
       return;
     }
-  }
-  if (mfma_layer(L) && (size_t)MF_CHUNK * D * H * W * 4 < 0xf0000000ull) {
-    ProfScope ps(FNX_PROF_CONV_MFMA, s);
-    const double px = (double)B * D * H * W, mac = 2.0 * L.cin * L.cout;
-    // F(4x4): the default (256^3 CNN step 92.2 -> 81.0 ms; 1024^2 2.29 -> 2.14 ms: replayed graphs, alternating runs on one box)
-    if ((mode == FNX_PRECISION_FP32_F4 || mode == FNX_PRECISION_FP32) && wino4_layer_(L, is3d) &&
-        launch_conv_wino4(a, packed + pl.w_off + wino4_offset(L, is3d), is3d, s)) {
-      prof_add_work(FNX_PROF_CONV_MFMA, px * mac * 2.25 * (is3d ? 3 : 1));  // 36 multiplies per 4x4 outputs (per z tap)
+    case Family::PAIR:
+    case Family::KPACK: {
+      ProfScope ps(FNX_PROF_CONV_MFMA16, s);
+      launch_conv_mfma16(a, is3d, P.fam == Family::PAIR, s);
+      prof_add_work(FNX_PROF_CONV_MFMA16, (double)B * D * H * W * 2.0 * L.cin * L.cout * layer_taps(L, is3d));
       return;
     }
-    if (!direct && wino_layer(L, is3d) && launch_conv_wino(a, is3d, packed + pl.w_off + layer_weight_floats(L, is3d), s)) {
-      prof_add_work(FNX_PROF_CONV_MFMA, px * mac * 4.0 * (is3d ? 3 : 1));   // 16 multiplies per 2x2 outputs (per z tap)
+    case Family::TO1: {
+      ProfScope ps(FNX_PROF_CONV_DIRECT, s);
+      const dim3 grid((W + 63) / 64, (H + 3) / 4, B * D), block(64, 4);
+      if (is3d) conv3_to1_kernel<true><<<grid, block, 0, s>>>(a); else conv3_to1_kernel<false><<<grid, block, 0, s>>>(a);
       return;
     }
-    launch_conv_mfma(a, is3d, s);
-    prof_add_work(FNX_PROF_CONV_MFMA, px * mac * layer_taps(L, is3d));
-    return;
-  }
-  if (mfma16_layer(L)) {
-    ProfScope ps(FNX_PROF_CONV_MFMA16, s); launch_conv_mfma16(a, is3d, s);
-    prof_add_work(FNX_PROF_CONV_MFMA16, (double)B * D * H * W * 2.0 * L.cin * L.cout * layer_taps(L, is3d));
-    return;
+    case Family::DIRECT: break;
   }
   ProfScope ps(FNX_PROF_CONV_DIRECT, s);
-  if (L.k == 3 && L.cout == 1 && L.cin % 4 == 0) {          // the towers' last layers: input channels split over the block's waves
-    const dim3 grid((W + 63) / 64, (H + 3) / 4, B * D), block(64, 4);
-    if (is3d) conv3_to1_kernel<true><<<grid, block, 0, s>>>(a); else conv3_to1_kernel<false><<<grid, block, 0, s>>>(a);
-    return;
-  }
-  if (is3d) {
-    if (L.k == 3) launch_conv_k<3, true>(a, s);
-    else if (L.k == 5) launch_conv_k<5, true>(a, s);
-    else launch_conv_k<1, true>(a, s);
-  } else {
-    if (L.k == 3) launch_conv_k<3, false>(a, s);
-    else if (L.k == 5) launch_conv_k<5, false>(a, s);
-    else launch_conv_k<1, false>(a, s);
-  }
+  launch_conv_direct(a, is3d, s);
 }
 
 // torch upsample_{bi,tri}linear(align_corners=False): src = scale*(dst+0.5)-0.5, clamped at 0
@@ -1449,8 +1450,7 @@ size_t scalenet_weight_floats(bool is3d) {
 }
 
 size_t scalenet_packed_bytes(bool is3d) {
-  const PackedLayer last = packed_layer(N_LAYERS - 1, is3d);
-  return al256((last.b_off + LAYERS[N_LAYERS - 1].cout + 64) * sizeof(float));
+  return al256((plan(is3d)[N_LAYERS - 1].bias + LAYERS[N_LAYERS - 1].cout + 64) * sizeof(float));
 }
 
 void scalenet_pack(bool is3d, const float* blob, void* packed, hipStream_t s) {
@@ -1458,36 +1458,30 @@ void scalenet_pack(bool is3d, const float* blob, void* packed, hipStream_t s) {
   float* pk = (float*)packed;
   for (int l = 0; l < N_LAYERS; ++l) {
     const ConvLayer& L = LAYERS[l];
-    const PackedLayer pl = packed_layer(l, is3d);
-    const size_t nw = layer_weight_floats(L, is3d);
-    if (mfma_layer(L)) {
-      pack_layer_mfma_kernel<<<64, 256, 0, s>>>(blob + off, blob + off + nw, pk + pl.w_off, pk + pl.b_off, L.cin, L.cout,
-                                                layer_taps(L, is3d));
-      if (wino_layer(L, is3d)) {
+    const LayerPlan& P = plan(is3d)[l];
+    const float *w = blob + off, *bias = blob + off + layer_weight_floats(L, is3d);
+    switch (P.fam) {
+      case Family::MFMA: {
         const int kd = is3d ? 3 : 1;
-        float* w2 = pk + pl.w_off + nw;                         // [dz][16][Cin][Cout]
-        float* w3 = w2 + (size_t)16 * kd * L.cin * L.cout;      // stage-contiguous     (conv3_wino3_kernel)
-        pack_layer_wino_kernel<<<64, 256, 0, s>>>(blob + off, w2, L.cin, L.cout, kd);
-        repack_wino3_kernel<<<64, 256, 0, s>>>(w2, w3, L.cin, L.cout, kd, wino3_rw(L.cout));
-        if (wbf_layer(L, is3d))                                 // FNX_PRECISION_BF16X6: three bf16 pieces, MFMA operand layout
-          pack_wbf_kernel<<<256, 256, 0, s>>>(w2, (unsigned*)(w3 + (size_t)16 * kd * L.cin * L.cout), L.cin, L.cout, kd);
-        if (wino4_layer_(L, is3d))                              // FNX_PRECISION_FP32_F4: the taps in lane order, stage-contiguous
-          pack_layer_wino4g_kernel<<<64, 256, 0, s>>>(blob + off, pk + pl.w_off + wino4_offset(L, is3d), L.cin, L.cout, is3d ? 3 : 1);
+        pack_layer_mfma_kernel<<<64, 256, 0, s>>>(w, bias, pk + P.taps, pk + P.bias, L.cin, L.cout, layer_taps(L, is3d));
+        pack_layer_wino_kernel<<<64, 256, 0, s>>>(w, pk + P.wino2, L.cin, L.cout, kd);
+        repack_wino3_kernel<<<64, 256, 0, s>>>(pk + P.wino2, pk + P.wino3, L.cin, L.cout, kd, wino3_rw(L.cout));
+        if (P.wide) {
+          pack_wbf_kernel<<<256, 256, 0, s>>>(pk + P.wino2, (unsigned*)(pk + P.wbf), L.cin, L.cout, kd);
+          pack_layer_wino4g_kernel<<<64, 256, 0, s>>>(w, pk + P.wino4, L.cin, L.cout, kd);
+        }
+        break;
       }
+      case Family::PAIR:
+        pack_layer_pair_kernel<<<64, 256, 0, s>>>(w, bias, pk + P.taps, pk + P.bias, L.cin, L.cout, is3d ? 5 : 1, pad_to(L.cin, 4));
+        break;
+      case Family::KPACK:
+        pack_layer_kpack_kernel<<<64, 256, 0, s>>>(w, bias, pk + P.taps, pk + P.bias, L.cin, L.cout, is3d ? 5 : 1, pad_to(L.cout, 16));
+        break;
+      default:
+        pack_layer_kernel<<<64, 256, 0, s>>>(w, bias, pk + P.taps, pk + P.bias, L.cin, L.cout, layer_taps(L, is3d), co_tile(L.cout));
     }
-    else if (mfma16_layer(L) && pair_layer(L.cin, L.cout))
-      pack_layer_pair_kernel<<<64, 256, 0, s>>>(blob + off, blob + off + nw, pk + pl.w_off, pk + pl.b_off, L.cin, L.cout,
-                                                is3d ? 5 : 1, pad_to(L.cin, 4));
-    else if (mfma16_layer(L) && kpack_cin(L.cin, L.cout))
-      pack_layer_kpack_kernel<<<64, 256, 0, s>>>(blob + off, blob + off + nw, pk + pl.w_off, pk + pl.b_off, L.cin, L.cout,
-                                                 is3d ? 5 : 1, pad_to(L.cout, 16));
-    else if (mfma16_layer(L))
-      pack_layer_mfma16_kernel<<<64, 256, 0, s>>>(blob + off, blob + off + nw, pk + pl.w_off, pk + pl.b_off, L.cin, L.cout,
-                                                  layer_taps(L, is3d), pad_to(L.cin, 4), pad_to(L.cout, 16));
-    else
-      pack_layer_kernel<<<64, 256, 0, s>>>(blob + off, blob + off + nw, pk + pl.w_off, pk + pl.b_off, L.cin, L.cout,
-                                           layer_taps(L, is3d), co_tile(L.cout));
-    off += nw + L.cout;
+    off += layer_weight_floats(L, is3d) + L.cout;
   }
 }
 
@@ -1530,10 +1524,9 @@ void multiscale_forward_crop(const GridDims& g, bool is3d, const void* packed, c
     const float* cur = in;
     for (int l = 0; l < n; ++l) {
       // the last 5x5 layer takes the final 1x1 into its epilogue (multi_scale_net.py:116): one launch, no 8-channel tensor
-      const bool fuse = l + 2 == n && fuses_tail(LAYERS[l0 + l], LAYERS[l0 + l + 1]);
+      const bool fuse = plan(is3d)[l0 + l].fam == Family::PAIR;
       float* dst = (l == n - 1 || fuse) ? out : ((l & 1) ? bufB : bufA);
-      const PackedLayer tl = fuse ? packed_layer(l0 + l + 1, is3d) : PackedLayer{0, 0};
-      launch_conv(LAYERS[l0 + l], is3d, mode, pk, packed_layer(l0 + l, is3d), cur, dst, g.B, D, H, W, s, fuse ? &tl : nullptr);
+      launch_conv(l0 + l, is3d, mode, pk, cur, dst, g.B, D, H, W, s);
       if (fuse) break;
       cur = dst;
     }
@@ -1788,6 +1781,13 @@ size_t fluidnet_ws_bytes(const GridDims& g, bool is3d) {
 
 #include "../../include/fluidnet_hip.h"
 
+namespace fnx {
+int net_mode(int precision_mode) {
+  if (precision_mode < FNX_PRECISION_FP32 || precision_mode > FNX_PRECISION_FP32_F2) return -1;
+  return precision_mode == FNX_PRECISION_FP32_F4 ? FNX_PRECISION_FP32 : precision_mode;
+}
+}  // namespace fnx
+
 // FluidNet.forward after the channel split (model.py:120-227), U in place: U holds UDiv on entry and the
 // projected velocity on exit.  ws needs fluidnet_ws_bytes() minus the flags copy.
 namespace fnx {
@@ -1823,7 +1823,7 @@ int fluidnet_core(const FnxGrid* g, const void* packed, const float* flags, floa
     launch_post_projection(d, g->is3D, pnet, U, bcs->density, flags, ubc ? bcs->UBC : nullptr, ubc ? bcs->UBCInvMask : nullptr,
                            rbc ? bcs->densityBC : nullptr, rbc ? bcs->densityBCInvMask : nullptr, s, bcs->bc_class,
                            bcs->density_bc_applied != 0, scale, p_out);          // model.py:213-226, simulate.py:168
-    return fnx::launch_status();
+    return fnx::launch_status(g->is3D);
   }
   if (int rc = fnx_velocity_divergence(g, U, flags, div, stream)) return rc;     // model.py:125-126
   launch_scale_std(d, nc, U, thr, partial, scale, s);                            // model.py:129-144
@@ -1832,7 +1832,7 @@ int fluidnet_core(const FnxGrid* g, const void* packed, const float* flags, floa
   if (int rc = fnx_velocity_update(g, p_out, U, flags, stream)) return rc;       // model.py:213-218
   launch_unscale(d, nc, scale, p_out, U, s);                                     // model.py:221-223
   if (int rc = fnx_set_wall_bcs(g, U, flags, stream)) return rc;                 // model.py:226
-  return fnx::launch_status();
+  return fnx::launch_status(g->is3D);
 }
 }  // namespace fnx
 
@@ -1848,49 +1848,54 @@ size_t fnx_scalenet_packed_bytes(int is3D) { return fnx::scalenet_packed_bytes(i
 int fnx_scalenet_pack(int is3D, const float* weights_blob, void* packed, void* stream) {
   if (!weights_blob || !packed) return fnx::set_error(FNX_EINVAL, "%s: null argument", __func__);
   fnx::scalenet_pack(is3D != 0, weights_blob, packed, (hipStream_t)stream);
-  return fnx::launch_status();
+  return fnx::launch_status(is3D != 0);
 }
 
-static bool bad_precision(int m) { return m < FNX_PRECISION_FP32 || m > FNX_PRECISION_FP32_F2; }
+// The checks the three CNN entry points share, before any device call: null arguments (`args`), the precision mode (*mode: as the
+// launchers dispatch on it, net_mode), the net's smallest grid and the workspace (fluidnet_forward's or multiscale_forward's).
+static int check_net_call(const char* fn, const FnxGrid* g, bool args, int precision_mode, int* mode, bool fluidnet, size_t ws_bytes) {
+  if (!g || !args) return fnx::set_error(FNX_EINVAL, "%s: null argument", fn);
+  *mode = fnx::net_mode(precision_mode);
+  if (*mode < 0)
+    return fnx::set_error(FNX_EINVAL, "%s: unknown precision_mode %d (FNX_PRECISION_FP32, _FP32_DIRECT, _BF16X6, _BF16X3, _FP32_F4 or "
+                          "_FP32_F2)", fn, precision_mode);
+  if (g->H < 4 || g->W < 4 || (g->is3D && g->D < 4))
+    return fnx::set_error(FNX_EINVAL, "%s: the three-scale net needs at least 4 cells per axis (D %d, H %d, W %d)", fn, g->D, g->H, g->W);
+  const GridDims d = make_dims(g->B, g->D, g->H, g->W, g->z_offset, g->D_global);
+  if (ws_bytes < (fluidnet ? fnx::fluidnet_ws_bytes(d, g->is3D) : fnx::multiscale_ws_bytes(d, g->is3D)))
+    return fnx::set_error(FNX_EWORKSPACE, "%s: workspace of %zu bytes is too small", fn, ws_bytes);
+  return FNX_OK;
+}
 
 int fnx_multiscale_forward(const FnxGrid* g, const void* packed, const float* x, float* p, int precision_mode, void* ws,
                            size_t ws_bytes, void* stream) {
-  if (!g || !packed || !x || !p || !ws) return fnx::set_error(FNX_EINVAL, "%s: null argument", __func__);
-  if (bad_precision(precision_mode)) return fnx::set_error(FNX_EINVAL, "unknown precision_mode %d (FNX_PRECISION_FP32, _FP32_DIRECT, _BF16X6 or _BF16X3)", precision_mode);
-  if (g->H < 4 || g->W < 4 || (g->is3D && g->D < 4))
-    return fnx::set_error(FNX_EINVAL, "%s: the three-scale net needs at least 4 cells per axis (D %d, H %d, W %d)", __func__, g->D, g->H, g->W);
+  int mode;
+  if (int rc = check_net_call(__func__, g, packed && x && p && ws, precision_mode, &mode, false, ws_bytes)) return rc;
   const GridDims d = make_dims(g->B, g->D, g->H, g->W, g->z_offset, g->D_global);
-  if (ws_bytes < fnx::multiscale_ws_bytes(d, g->is3D)) return fnx::set_error(FNX_EWORKSPACE, "%s: workspace of %zu bytes is too small", __func__, ws_bytes);
-  fnx::multiscale_forward(d, g->is3D, packed, x, p, precision_mode, ws, (hipStream_t)stream);
-  return fnx::launch_status();
+  fnx::multiscale_forward(d, g->is3D, packed, x, p, mode, ws, (hipStream_t)stream);
+  return fnx::launch_status(g->is3D);
 }
 
 int fnx_multiscale_forward_crop(const FnxGrid* g, const void* packed, const float* x, float* p, int precision_mode,
                                 const int trim[4], void* ws, size_t ws_bytes, void* stream) {
-  if (!g || !packed || !x || !p || !ws || !trim) return fnx::set_error(FNX_EINVAL, "%s: null argument", __func__);
-  if (bad_precision(precision_mode)) return fnx::set_error(FNX_EINVAL, "unknown precision_mode %d (FNX_PRECISION_FP32, _FP32_DIRECT, _BF16X6 or _BF16X3)", precision_mode);
+  int mode;
+  if (int rc = check_net_call(__func__, g, packed && x && p && ws && trim, precision_mode, &mode, false, ws_bytes)) return rc;
   if (!g->is3D && (trim[0] | trim[1] | trim[2] | trim[3])) return fnx::set_error(FNX_EINVAL, "multiscale_forward_crop: z windows need a 3D grid");
   for (int a = 0; a < 4; ++a)
     if (trim[a] < 0 || trim[a] % 4) return fnx::set_error(FNX_EINVAL, "multiscale_forward_crop: trim[%d] = %d must be a non-negative multiple of 4", a, trim[a]);
   if (trim[2] > trim[0] || trim[3] > trim[1]) return fnx::set_error(FNX_EINVAL, "multiscale_forward_crop: the half-resolution window must contain the full-resolution one");
   if ((trim[0] | trim[1] | trim[2] | trim[3]) && (g->D % 4 || g->D - trim[0] - trim[1] < 4))
     return fnx::set_error(FNX_EINVAL, "multiscale_forward_crop: D = %d must be a multiple of 4 and leave at least 4 planes (trims %d + %d)", g->D, trim[0], trim[1]);
-  if (g->H < 4 || g->W < 4 || (g->is3D && g->D < 4))
-    return fnx::set_error(FNX_EINVAL, "%s: the three-scale net needs at least 4 cells per axis (D %d, H %d, W %d)", __func__, g->D, g->H, g->W);
   const GridDims d = make_dims(g->B, g->D, g->H, g->W, g->z_offset, g->D_global);
-  if (ws_bytes < fnx::multiscale_ws_bytes(d, g->is3D)) return fnx::set_error(FNX_EWORKSPACE, "%s: workspace of %zu bytes is too small", __func__, ws_bytes);
-  fnx::multiscale_forward_crop(d, g->is3D, packed, x, p, precision_mode, ws, (hipStream_t)stream, trim);
-  return fnx::launch_status();
+  fnx::multiscale_forward_crop(d, g->is3D, packed, x, p, mode, ws, (hipStream_t)stream, trim);
+  return fnx::launch_status(g->is3D);
 }
 
 int fnx_fluidnet_forward(const FnxGrid* g, const void* packed, const float* input, float thr, float* p_out,
                          float* U_out, int precision_mode, void* ws, size_t ws_bytes, void* stream) {
-  if (!g || !packed || !input || !p_out || !U_out || !ws) return fnx::set_error(FNX_EINVAL, "%s: null argument", __func__);
-  if (bad_precision(precision_mode)) return fnx::set_error(FNX_EINVAL, "unknown precision_mode %d (FNX_PRECISION_FP32, _FP32_DIRECT, _BF16X6 or _BF16X3)", precision_mode);
-  if (g->H < 4 || g->W < 4 || (g->is3D && g->D < 4))
-    return fnx::set_error(FNX_EINVAL, "%s: the three-scale net needs at least 4 cells per axis (D %d, H %d, W %d)", __func__, g->D, g->H, g->W);
+  int mode;
+  if (int rc = check_net_call(__func__, g, packed && input && p_out && U_out && ws, precision_mode, &mode, true, ws_bytes)) return rc;
   const GridDims d = make_dims(g->B, g->D, g->H, g->W, g->z_offset, g->D_global);
-  if (ws_bytes < fnx::fluidnet_ws_bytes(d, g->is3D)) return fnx::set_error(FNX_EWORKSPACE, "%s: workspace of %zu bytes is too small", __func__, ws_bytes);
   hipStream_t s = (hipStream_t)stream;
   const int nc = g->is3D ? 3 : 2;
   const size_t full = (size_t)g->B * d.DHW;
@@ -1898,11 +1903,7 @@ int fnx_fluidnet_forward(const FnxGrid* g, const void* packed, const float* inpu
   void* rest = (char*)ws + ((full * 4 + 255) & ~(size_t)255);
   // model.py:104-119: split the channels
   fnx::launch_gather_input(d, nc, input, U_out, flags, s);
-  return fnx::fluidnet_core(g, packed, flags, thr, precision_mode, p_out, U_out, rest, stream);
+  return fnx::fluidnet_core(g, packed, flags, thr, mode, p_out, U_out, rest, stream);
 }
-
-#ifdef W4_TIMELINE
-int fnx_debug_w4_timeline(unsigned long long* out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(fnx::w4_tl), sizeof(fnx::w4_tl)); }
-#endif
 
 }  // extern "C"

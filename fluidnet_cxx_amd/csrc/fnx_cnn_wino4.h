@@ -30,15 +30,6 @@
 //
 // Numerics: the transforms are not exact in binary (G has 1/6, 1/24; B^T and A^T multiply by 2, 4, 5, 8): measured 2x the error of
 // F(2x2) against an fp64 evaluation of the net, 0.07 of the tests' 1e-5 |ref|max (tools/wino_f4_error_probe.py).
-#ifndef W4_V16
-#define W4_V16 1
-#endif
-#ifndef W4_NWG
-#define W4_NWG 256      // workgroups of a launch: one per CU (99 KB of LDS each)
-#endif
-#ifndef W4_NT
-#define W4_NT 2         // cache policy: 2 = output stores non-temporal (3 % faster; non-temporal halo DMA measured 5 % slower: removed)
-#endif
 constexpr int W4C = 4;                       // input channels per stage
 constexpr int W4_RAW = 4 * 18 * 34;          // 2448 floats of a stage's halo tile (4 bytes per lane: any W)
 constexpr int W4_RAW16 = 4 * 18 * 10;        // 720 pieces of 16 bytes: rows of 40 floats, columns x0 - 4 .. x0 + 35 (W % 4 == 0)
@@ -384,7 +375,7 @@ __global__ __launch_bounds__(512, 2) void conv3_wino4_kernel(ConvArgs a, const f
       float* row = yo + (size_t)yy * a.W + px;
       if (px + 3 < a.W && ((a.W & 3) == 0)) {
         const w4f4 v = {Tm[aa][0], Tm[aa][1], Tm[aa][2], Tm[aa][3]};
-        if (W4_NT & 2) __builtin_nontemporal_store(v, (w4f4*)row); else *(w4f4*)row = v;
+        __builtin_nontemporal_store(v, (w4f4*)row);      // (3 % faster; a non-temporal halo DMA measured 5 % slower)
       }
       else {
 #pragma unroll
@@ -402,9 +393,10 @@ bool launch_conv_wino4(const ConvArgs& a, const float* wt4, bool is3d, hipStream
   if ((size_t)W4C * a.D * a.H * a.W * 4 >= 0xfffffff0u) return false;
   const int ntx = (a.W + 31) / 32, nty = (a.H + 15) / 16;
   const long nt = (long)ntx * nty * a.D * a.B * (a.cout / 64);
-  if (nt < 256 || nt > 0x7fffffffl) return false;        // a launch that does not fill the chip stays on the F(2x2) / direct kernels
-  const bool v16 = (a.W & 3) == 0 && W4_V16;
-  const unsigned nwg = (unsigned)(nt < W4_NWG ? nt : W4_NWG);        // persistent: one workgroup per CU walks the tiles
+  const int ncu = cu_count();
+  if (nt < ncu || nt > 0x7fffffffl) return false;        // a launch that does not fill the chip stays on the F(2x2) / direct kernels
+  const bool v16 = (a.W & 3) == 0;
+  const unsigned nwg = (unsigned)(nt < ncu ? nt : ncu);  // persistent: one workgroup per CU (99 KB of LDS each) walks the tiles
   const int nti = (int)nt;
   if (is3d) { if (v16) conv3_wino4_kernel<true, true><<<nwg, 512, 0, s>>>(a, wt4, ntx, nty, nti); else conv3_wino4_kernel<true, false><<<nwg, 512, 0, s>>>(a, wt4, ntx, nty, nti); }
   else { if (v16) conv3_wino4_kernel<false, true><<<nwg, 512, 0, s>>>(a, wt4, ntx, nty, nti); else conv3_wino4_kernel<false, false><<<nwg, 512, 0, s>>>(a, wt4, ntx, nty, nti); }

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include <atomic>
 
 #define FNX_FLUID 1.0f
 #define FNX_OBST 2.0f
@@ -32,6 +33,21 @@ __host__ __device__ inline GridDims make_dims(int B, int D, int H, int W, int zo
   d.zoff = zoff; d.Dglob = Dglob > 0 ? Dglob : D;
   d.K0 = 0; d.KN = D;
   return d;
+}
+
+// compute units of the current device, asked once per device ordinal (256, the MI355X's, where the runtime cannot tell): what the
+// persistent and one-round launches size their grids by
+inline int cu_count() {
+  constexpr int NDEV = 64;
+  static std::atomic<int> cache[NDEV];               // 0: not asked yet
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= NDEV) return 256;
+  int n = cache[dev].load(std::memory_order_relaxed);
+  if (n == 0) {
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    cache[dev].store(n, std::memory_order_relaxed);
+  }
+  return n;
 }
 
 // per-sample field views: pointer to channel 0 of sample b; channel stride = DHW

@@ -904,11 +904,7 @@ int jacobi_max_sweeps_per_launch(const GridDims& g, bool is3d, int total) {
   // Small grids are launch-latency bound (a launch costs ~5 us + ~0.35 us per sweep whatever the halo does to the work, as
   // long as every tile has a CU to itself): the fewest launches whose tiles all run at once, the sweeps dealt evenly.
   if (total > KMAX_2D) {
-    static const long cus = [] {
-      int dev = 0, n = 256;
-      if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-      return (long)n;
-    }();
+    const long cus = cu_count();
     int kcap = 0;
     for (int K = KDEEP_2D; K > KMAX_2D; --K) if (tiles_2d(g, K) <= cus) { kcap = K; break; }
     if (kcap) {
@@ -953,9 +949,7 @@ bool jacobi3d_quad_ok(const GridDims& g) { return g.H % 4 == 0 && Z2R == 4 && Z2
 // may a two-sweep launch of these plane ranges mirror its output (launch_jacobi3d_x2's `mirror`)?  One resident set of waves, both
 // arrays in the same layout, not the from-zero pass
 bool jacobi3d_mirror_ok(const GridDims& g, int np, bool two_ranges, bool from_zero, int lay) {
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  const long slots = (long)(Z2WPS * 4 / Z2NW) * cus;
+  const long slots = (long)(Z2WPS * 4 / Z2NW) * cu_count();
   const long ntiles = (long)((g.W + 59) / 60) * ((g.H + Z2NW * Z2R - 1) / (Z2NW * Z2R)) * g.B;
   return !from_zero && (lay == 0 || lay == 3) && np >= 1 && ntiles * (two_ranges ? 2 : 1) <= slots && (size_t)(np + 4) * g.HW < 0x3fffffffu;
 }
@@ -964,11 +958,7 @@ bool jacobi3d_mirror_ok(const GridDims& g, int np, bool two_ranges, bool from_ze
 void launch_jacobi3d_x2(const GridDims& g, const unsigned char* mask, const float* div, const float* p_in, float* p_out,
                         hipStream_t s, int kb, int ke, bool from_zero, int kb2, int lay, const JacobiMirror* mirror) {
   if (ke <= kb) { kb = 0; ke = g.D; kb2 = -1; }
-  static const int slots = [] {                          // resident waves: Z2WPS per SIMD (<= 128 VGPRs each)
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    return (Z2WPS * 4 / Z2NW) * cus;
-  }();
+  const int slots = (Z2WPS * 4 / Z2NW) * cu_count();      // resident waves: Z2WPS per SIMD (<= 128 VGPRs each)
   // Smallest plane chunk.  Every (tile, chunk) wave is resident at once, so a launch lasts (chunk + 2 lead-in steps) x
   // the per-step time of one wave, whatever the occupancy: small plane ranges (the slab driver's edge parts, small
   // grids) are cut as finely as the wave slots allow (measured 20 -> 14 us for 14 planes of 512^2).

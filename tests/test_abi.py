@@ -120,6 +120,35 @@ def test_cpu_tensors_fail_loudly(built):
         fluid.velocityDivergence(U[0], flags)
 
 
+class _FnxGrid(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int) for n in ("B", "D", "H", "W", "is3D", "ref_quirks", "z_offset", "D_global", "k_begin", "k_end")]
+
+
+def test_cnn_entry_points_reject_an_unknown_precision_mode(built):
+    """The three CNN entry points check the precision mode before they touch the device, and their message names all six modes."""
+    lib = ctypes.CDLL(built.LIB)
+    lib.fnx_last_error.restype = ctypes.c_char_p
+    vp, sz = ctypes.c_void_p, ctypes.c_size_t
+    lib.fnx_multiscale_forward.argtypes = [ctypes.POINTER(_FnxGrid), vp, vp, vp, ctypes.c_int, vp, sz, vp]
+    lib.fnx_multiscale_forward_crop.argtypes = [ctypes.POINTER(_FnxGrid), vp, vp, vp, ctypes.c_int, vp, vp, sz, vp]
+    lib.fnx_fluidnet_forward.argtypes = [ctypes.POINTER(_FnxGrid), vp, vp, ctypes.c_float, vp, vp, ctypes.c_int, vp, sz, vp]
+    hdr = open(os.path.join(REPO, "include", "fluidnet_hip.h")).read()
+    einval = int(re.search(r"FNX_EINVAL = (\d+)", hdr).group(1))
+    g = _FnxGrid(B=1, D=1, H=16, W=16)
+    buf = ctypes.create_string_buffer(64)                       # host memory: nothing may read it
+    trim = (ctypes.c_int * 4)(0, 0, 0, 0)
+    a = ctypes.cast(buf, vp)
+    for mode in (-1, 6, 99):
+        calls = {"fnx_multiscale_forward": lambda: lib.fnx_multiscale_forward(ctypes.byref(g), a, a, a, mode, a, 0, None),
+                 "fnx_multiscale_forward_crop": lambda: lib.fnx_multiscale_forward_crop(ctypes.byref(g), a, a, a, mode,
+                                                                                        ctypes.cast(trim, vp), a, 0, None),
+                 "fnx_fluidnet_forward": lambda: lib.fnx_fluidnet_forward(ctypes.byref(g), a, a, 1e-3, a, a, mode, a, 0, None)}
+        for name, call in calls.items():
+            assert call() == einval, (name, mode)
+            msg = lib.fnx_last_error().decode()
+            assert f"precision_mode {mode}" in msg and "_FP32_F2" in msg and "_FP32_F4" in msg, (name, msg)
+
+
 def test_weights_deterministic_and_param_count():
     from fluidnet_cxx_amd.weights import make_scalenet_weights, scalenet_layers
     w1, w2 = make_scalenet_weights(0), make_scalenet_weights(0)
