@@ -519,13 +519,15 @@ int fnx_scalenet_pack(int is3D, const float* weights_blob, void* packed, void* s
  *                              FNX_PRECISION_FP32
  *   FNX_PRECISION_BF16X3       FNX_PRECISION_BF16X6 with only the three products that involve no low piece (ah*bh + ah*bm + am*bh): half
  *                              the bf16 MFMAs and two thirds of the operand traffic; what is dropped is below 2^-15 of a product.  Its own
- *                              label and its own tolerance: 1e-4 |ref|max against oracle and goldens in the tests (measured ~1e-5:
- *                              profiles/r05).  SURVEY.md section 7's "accurate bf16" mode; the reference's own convolutions run on
+ *                              label and its own tolerance: 1e-4 |ref|max against oracle and goldens in the tests (measured 2-3e-5 on
+ *                              the bias-dominated benchmark weights, 8-9.2e-5 on weights whose every layer reaches the output:
+ *                              tests/test_cnn_fp64_gpu.py).  SURVEY.md section 7's "accurate bf16" mode; the reference's own convolutions run on
  *                              torch.nn.Conv2d, whose CUDA default admits TF32 (lib/multi_scale_net.py:21-127)
  *   FNX_PRECISION_FP32_F4      (round 6) the 64- and 128-output-channel 3x3(x3) layers in the Winograd F(4x4,3x3) domain (conv3_wino4_kernel: 36
  *                              multiplies per 16 outputs instead of F(2x2)'s 64; 3D: in (y, x), the z taps as stages): exact-fp32 MFMAs,
- *                              the transforms round more (multipliers 4, 5, 8, 1/6, 1/24) -- measured 2x F(2x2)'s error, 0.07 of the
- *                              tests' 1e-5 |ref|max.  What FNX_PRECISION_FP32 runs since round 6 (256^3 CNN step 92.2 -> 81.0 ms,
+ *                              the transforms round more (multipliers 4, 5, 8, 1/6, 1/24) -- measured 2-3x F(2x2)'s error: up to 4.8e-6
+ *                              |ref|max (3D) against a float64 model when every layer reaches the output (tests/test_cnn_fp64_gpu.py),
+ *                              within the tests' 1e-5.  What FNX_PRECISION_FP32 runs since round 6 (256^3 CNN step 92.2 -> 81.0 ms,
  *                              1024^2 2.29 -> 2.14 ms)
  *   FNX_PRECISION_FP32_F2      F(2x2,3x3) for every Winograd layer: the default of rounds 2-5 (kept for A/B timing) */
 enum { FNX_PRECISION_FP32 = 0, FNX_PRECISION_FP32_DIRECT = 1, FNX_PRECISION_BF16X6 = 2, FNX_PRECISION_BF16X3 = 3, FNX_PRECISION_FP32_F4 = 4,

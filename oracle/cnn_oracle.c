@@ -34,10 +34,11 @@ static const Layer T2[6] = { {3, 32, 5, 1}, {32, 64, 3, 1}, {64, 128, 3, 1}, {12
 static const Layer T1[6] = { {3, 32, 5, 1}, {32, 64, 3, 1}, {64, 128, 3, 1}, {128, 64, 3, 1}, {64, 32, 3, 0}, {32, 8, 5, 0} };
 static const Layer TF[1] = { {8, 1, 1, 0} };
 
-/* Direct cross-correlation, zero padding k/2, NC(D)HW, double accumulation. */
+/* Direct cross-correlation, zero padding k/2, NC(D)HW, double accumulation.  A 3D layer has k z taps whatever D is: on a single
+ * plane (the quarter-resolution tower of a 4..7-plane grid) only the middle one meets data. */
 static void conv_nd(const float* x, float* y, const float* w, const float* bias, int B, int cin, int cout,
-                    int D, int H, int W, int k, int relu) {
-  const int kd = D > 1 ? k : 1, pad = k / 2, pd = D > 1 ? pad : 0;
+                    int D, int H, int W, int k, int relu, int is3D) {
+  const int kd = is3D ? k : 1, pad = k / 2, pd = is3D ? pad : 0;
   const size_t plane = (size_t)H * W, vol = plane * D;
 #pragma omp parallel for collapse(3) schedule(static)
   for (int b = 0; b < B; ++b)
@@ -133,7 +134,7 @@ static const float* run_tower(const Layer* T, int n, const float* wts, float** b
     size_t kk = (size_t)T[l].k * T[l].k * (is3D ? T[l].k : 1);
     const float* w = wts; const float* bias = wts + (size_t)T[l].cout * T[l].cin * kk;
     float* o = (float*)malloc((size_t)B * T[l].cout * D * H * W * sizeof(float));
-    conv_nd(cur, o, w, bias, B, T[l].cin, T[l].cout, D, H, W, T[l].k, T[l].relu);
+    conv_nd(cur, o, w, bias, B, T[l].cin, T[l].cout, D, H, W, T[l].k, T[l].relu, is3D);
     if (cur != in) free(cur);
     cur = o;
     wts += layer_floats(&T[l], is3D);
