@@ -20,14 +20,23 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # reference's ATen arithmetic depends on it.  The CNN unit is tolerance-checked and may fuse.
 HIP_UNITS = {
     "fnx_stencils.hip": ["-ffp-contract=off"],
-    "fnx_advect.hip": ["-ffp-contract=off"],
+    "fnx_advect.hip": ["-ffp-contract=off", "-Rpass-analysis=kernel-resource-usage"],
     "fnx_jacobi.hip": ["-ffp-contract=off"],
     "fnx_step.hip": ["-ffp-contract=off"],
     "fnx_api.hip": ["-ffp-contract=off"],
-    # (resource-usage remarks: build_lib checks that conv3_wbf_kernel has no scratch -- its asynchronous LDS reads rely on it)
+    # (resource-usage remarks: build_lib checks the kernels of SCRATCH_FREE)
     "fnx_cnn.hip": ["-Rpass-analysis=kernel-resource-usage"],
     "fnx_slab.hip": [],
     "fnx_peer.hip": [],
+}
+# unit -> (kernels that must use no scratch and spill no VGPR, why).  hipcc's resource-usage remarks are checked after each compile.
+SCRATCH_FREE = {
+    "fnx_cnn.hip": (["conv3_wbf_kernel"], "fnx_cnn_bf16x6.h: the results of its inline-asm LDS reads are only valid behind an explicit "
+                                          "wait; a spill copies them before it"),
+    "fnx_advect.hip": (["advect3d_fwd_tile_kernel", "advect3d_bwd_tile_kernel", "advect3d_bwd_scalar_tile_kernel",
+                        "advect3d_bwd_vel_tile_kernel"],
+                       "fnx_advect_march.h: the 3D advection marches run at 2-3 waves per SIMD with every VGPR in use; a reload from "
+                       "scratch is an s_waitcnt vmcnt(0) that also waits for the plane in flight and the stores"),
 }
 # -fno-slp-vectorize: hipcc otherwise packs adjacent scalar f32 adds into v_pk_add_f32 + v_pk_mov shuffles, measured
 # 1.6x slower per op than plain VALU on gfx950 (tools/ubench/dpp_bench.hip).
@@ -77,18 +86,23 @@ def build_lib(force=False, verbose=False):
         if p.returncode != 0:
             failed = True
             sys.stderr.write(f"--- {unit} ---\n{out.decode()}\n")
-        elif unit == "fnx_cnn.hip":
-            bad, seen = _scratch_users(out.decode(), "conv3_wbf_kernel")
-            if seen == 0:      # no remark matched (renamed kernel, another hipcc's remark format): the check must not pass unseen
+        elif unit in SCRATCH_FREE:
+            kernels, why = SCRATCH_FREE[unit]
+            spills = False
+            for kernel in kernels:
+                bad, seen = _scratch_users(out.decode(), kernel)
+                if seen == 0:  # no remark matched (renamed kernel, another hipcc's remark format): the check must not pass unseen
+                    msg = (f"no kernel-resource-usage remark for {kernel} was found in hipcc's output -- the no-scratch check could "
+                           "not run (fluidnet_cxx_amd/build.py:_scratch_users)")
+                elif bad:
+                    msg = f"{kernel} must not spill ({why}): {bad}"
+                else:
+                    continue
+                spills = True
+                sys.stderr.write(f"{unit}: {msg}\n")
+            if spills:
                 failed = True
-                os.remove(os.path.join(HERE, "build", "fnx_cnn.o"))
-                sys.stderr.write("fnx_cnn.hip: no kernel-resource-usage remark for conv3_wbf_kernel was found in hipcc's output -- the "
-                                 "no-scratch check could not run (fluidnet_cxx_amd/build.py:_scratch_users)\n")
-            elif bad:
-                failed = True
-                os.remove(os.path.join(HERE, "build", "fnx_cnn.o"))
-                sys.stderr.write("fnx_cnn.hip: conv3_wbf_kernel must not spill (fnx_cnn_bf16x6.h: the results of its inline-asm LDS reads are "
-                                 f"only valid behind an explicit wait; a spill copies them before it): {bad}\n")
+                os.remove(os.path.join(HERE, "build", unit.replace(".hip", ".o")))
         elif verbose and out:
             print(out.decode())
     if failed:

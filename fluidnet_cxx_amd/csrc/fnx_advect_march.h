@@ -119,7 +119,22 @@ struct ATile {
     const int kc = k < 0 ? 0 : (k > g.D - 1 ? g.D - 1 : k);
     return (unsigned)(kc - k0) * hw * 4u;
   }
+  // byte offset of my cell of row j inside a plane (clamped into the grid for the lanes that store nothing): the per-lane part of
+  // every per-cell global load and store, the plane's wave-uniform base (aat) the rest.  32 bits suffice: the tile plan needs
+  // (KN + 2) * HW < 2^30 (advect_tile_plan), so even twice the offset (the float2 clamp bounds) stays below 2^32.  Opaque to the
+  // optimiser at each step: otherwise it builds one 64-bit address per field and row, hoists those out of the march, and at 2-3
+  // waves per SIMD spills them to scratch (round 6: 24 VGPRs in the backward march, every reload an s_waitcnt vmcnt(0) that also
+  // waited for the plane in flight and the stores before it).
+  __device__ __forceinline__ unsigned rowoff(const GridDims& g, int j) const {
+    unsigned o = (unsigned)((j < g.H ? j : g.H - 1) * g.W + (x < g.W ? x : g.W - 1)) * 4u;
+    asm volatile("" : "+v"(o));
+    return o;
+  }
 };
+
+// the element at `boff` bytes (rowoff) past a wave-uniform base
+template <class T> __device__ __forceinline__ T& aat(T* base, unsigned boff) { return *(T*)((char*)base + boff); }
+template <class T> __device__ __forceinline__ const T& aat(const T* base, unsigned boff) { return *(const T*)((const char*)base + boff); }
 
 // blockIdx.x -> (tile, z chunk), renumbered like the Jacobi march (XCD q gets a band of neighbouring tiles).
 __device__ __forceinline__ bool atile_setup(ATile& m, const GridDims& g, int ntx, int nty, int zchunk) {
@@ -394,6 +409,10 @@ __global__ __launch_bounds__(64 * ATNW, FNX_AT_WPS_FWD) void advect3d_fwd_tile_k
   auto body = [&](int k, unsigned fbm, unsigned fbc, unsigned fbp, const float (&rM)[NF][AFSZ], const float (&rC)[NF][AFSZ],
                   const float (&rP)[NF][AFSZ], auto pre_store) __attribute__((always_inline)) {
     const int kg = k + g.zoff;
+    unsigned ob[ATRPW];
+    const size_t pk1 = sb1 + (size_t)k * g.HW, pk3 = sb3 + (size_t)k * g.HW;
+#pragma unroll
+    for (int r = 0; r < ATRPW; ++r) ob[r] = m.rowoff(g, m.j0 + ATRPW * w + r);
     if constexpr (DO_S) {
       if (k == m.k_lo) {                                   // first step of the chunk: planes k-1 and k
         box_plane(rM, fbm, bxmn[0], bxmx[0], bxan[0]);
@@ -409,7 +428,7 @@ __global__ __launch_bounds__(64 * ATNW, FNX_AT_WPS_FWD) void advect3d_fwd_tile_k
         lo = lo != lo ? INFINITY : lo; hi = hi != hi ? -INFINITY : hi;                    // members, but every one a NaN
         // stored right away (nothing here waits for a store before the next step's wait for its plane)
         const int j = m.j0 + ATRPW * w + r;
-        if (xin && j < g.H) box[sb1 + (size_t)k * g.HW + (size_t)j * g.W + i] = make_float2(any ? lo : __builtin_nanf(""), hi);
+        if (xin && j < g.H) aat(box + pk1, 2 * ob[r]) = make_float2(any ? lo : __builtin_nanf(""), hi);
         bxmn[0][r] = bxmn[1][r]; bxmx[0][r] = bxmx[1][r];
         bxmn[1][r] = bpmn[r]; bxmx[1][r] = bpmx[r];
       }
@@ -496,15 +515,14 @@ __global__ __launch_bounds__(64 * ATNW, FNX_AT_WPS_FWD) void advect3d_fwd_tile_k
     for (int r = 0; r < ATRPW; ++r) {
       const int j = m.j0 + ATRPW * w + r;
       if (xin && j < g.H) {
-        const size_t o = (size_t)k * g.HW + (size_t)j * g.W + i;
         if constexpr (DO_S) {
-          rho_fwd[sb1 + o] = o_rho[r];
-          cell_out[sb1 + o] = o_cell[r];
+          aat(rho_fwd + pk1, ob[r]) = o_rho[r];
+          aat(cell_out + pk1, ob[r]) = o_cell[r];
         }
         if constexpr (DO_V) {
-          U_fwd[sb3 + o] = o_u[r][0];
-          U_fwd[sb3 + g.DHW + o] = o_u[r][1];
-          U_fwd[sb3 + 2 * (size_t)g.DHW + o] = o_u[r][2];
+          aat(U_fwd + pk3, ob[r]) = o_u[r][0];
+          aat(U_fwd + pk3 + g.DHW, ob[r]) = o_u[r][1];
+          aat(U_fwd + pk3 + 2 * (size_t)g.DHW, ob[r]) = o_u[r][2];
         }
       }
       // lanes the neighbourhood path does not cover (|displacement| >= 1 cell, trace into a non-fluid cell) go to the fix-up
@@ -762,13 +780,13 @@ __global__ __launch_bounds__(64 * ATNW, FNX_AT_WPS_B) void advect3d_bwd_tile_ker
     // the density part's traced cells (per-cell global operands; clamped addresses for the lanes that store nothing) are asked for
     // first and arrive behind the velocity part; what hangs off them -- the clamp bounds -- and rho are fetched at the top of the
     // density part and arrive behind its traces and samples.  (Two registers live across the velocity part, which needs all 256.)
-    int cell[ATRPW];
-    auto own = [&](int r) __attribute__((always_inline)) {
-      const int j = m.j0 + ATRPW * w + r;
-      return (size_t)k * g.HW + (size_t)(j < g.H ? j : g.H - 1) * g.W + (xin ? i : g.W - 1);
-    };
+    int cell[ATRPW]; unsigned ob[ATRPW];
+    const size_t pk1 = sb1 + (size_t)k * g.HW, pk3 = sb3 + (size_t)k * g.HW;
 #pragma unroll
-    for (int r = 0; r < ATRPW; ++r) cell[r] = cell_in[sb1 + own(r)];
+    for (int r = 0; r < ATRPW; ++r) {
+      ob[r] = m.rowoff(g, m.j0 + ATRPW * w + r);
+      cell[r] = aat(cell_in + pk1, ob[r]);
+    }
     float o_u[ATRPW][3]; unsigned long long wv[ATRPW];
     // ================= velocity: sl_mac_bwd_clamp_cell_flat (advect3d_bwd_vel_tile_kernel's body) =================
 #pragma unroll
@@ -833,7 +851,7 @@ __global__ __launch_bounds__(64 * ATNW, FNX_AT_WPS_B) void advect3d_bwd_tile_ker
     for (int r = 0; r < ATRPW; ++r) {
       inslab[r] = (cell[r] >= g.HW) & (cell[r] < g.HW + g.DHW);
       bb[r] = box[sb1 + (size_t)(inslab[r] ? cell[r] - g.HW : 0)];
-      src[r] = rho[sb1 + own(r)];
+      src[r] = aat(rho + pk1, ob[r]);
     }
     float o_d[ATRPW]; unsigned long long ws[ATRPW];
 #pragma unroll
@@ -871,11 +889,10 @@ __global__ __launch_bounds__(64 * ATNW, FNX_AT_WPS_B) void advect3d_bwd_tile_ker
     for (int r = 0; r < ATRPW; ++r) {
       const int j = m.j0 + ATRPW * w + r;
       if (xin && j < g.H) {
-        const size_t o = (size_t)k * g.HW + (size_t)j * g.W + i;
-        rho_dst[sb1 + o] = o_d[r];
-        U_dst[sb3 + o] = o_u[r][0];
-        U_dst[sb3 + g.DHW + o] = o_u[r][1];
-        U_dst[sb3 + 2 * (size_t)g.DHW + o] = o_u[r][2];
+        aat(rho_dst + pk1, ob[r]) = o_d[r];
+        aat(U_dst + pk3, ob[r]) = o_u[r][0];
+        aat(U_dst + pk3 + g.DHW, ob[r]) = o_u[r][1];
+        aat(U_dst + pk3 + 2 * (size_t)g.DHW, ob[r]) = o_u[r][2];
       }
       if (lane == 0 && j < g.H) { const size_t wi = m.word(g, k, j); fix_s[wi] = ws[r]; fix_v[wi] = wv[r]; }
     }
