@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The reference's `pytorch/plume.py` main loop on this backend -- what a driver looks like after the switch.
 
-    python examples/plume.py [--res 128] [--iters 200] [--out-iter 50] [--method jacobi] [--folder out] [--restart]
+    python examples/plume.py [--res 128] [--iters 200] [--out-iter 50] [--method jacobi|pcg] [--folder out] [--restart]
 
 Same structure as the reference driver (plume.py:66-178 setup, :231-424 loop): build the batch, `createPlumeBCs`, optional
 restart from `<folder>/restart.pth`, echo the configuration as YAML, then `simulate()` per iteration and, every `out-iter`
@@ -22,7 +22,7 @@ def main(argv=None):
     ap.add_argument("--res", type=int, default=128)
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--out-iter", type=int, default=50)
-    ap.add_argument("--method", default="jacobi", choices=["jacobi"])      # 'convnet' needs a trained FluidNet state dict
+    ap.add_argument("--method", default="jacobi", choices=["jacobi", "pcg"])      # 'convnet' needs a trained FluidNet state dict
     ap.add_argument("--folder", default="plume_out")
     ap.add_argument("--restart", action="store_true")
     a = ap.parse_args(argv)
@@ -31,6 +31,8 @@ def main(argv=None):
     simConf = dict(dt=0.1, maccormackStrength=0.6, sampleOutsideFluid=False, buoyancyScale=0.25, gravityScale=0, viscosity=0,
                    correctScalar=False, gravityVec=dict(x=0.0, y=-1.0, z=0.0), operatingDensity=0.0, pTol=0.0, jacobiIter=28,
                    simMethod=a.method, resX=a.res, resY=a.res, maxIter=a.iters, outputFolder=a.folder)
+    if a.method == "pcg":                                 # the converged solve (fluid.solveLinearSystemPCG)
+        simConf.update(pcgTol=1e-5, pcgIter=50)
     os.makedirs(a.folder, exist_ok=True)
     resX = resY = a.res
     # plume.py:131-163

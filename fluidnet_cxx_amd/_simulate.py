@@ -22,7 +22,11 @@ Explicit control, as before: `workspace` (a uint8 tensor of ext.step_workspace_b
 bit set (FnxStepParams.static_flags): 1 = flags unchanged since the previous call on that workspace (the 3D Jacobi reuses its
 obstacle mask), 2 = the four BC arrays unchanged (the BC stages then go by a 1-byte class map kept in the workspace), 4 = that
 map was already built by an earlier call with bit 2 -- e.g. 0 for the first step, 3 for the second, 7 from the third on.
+8 = ('pcg') the workspace holds the multigrid hierarchy of these flags, built by an earlier call (used only together with 1; the
+automatic mode records it only after a call has succeeded).
 `static_flags=None` (the default) with no `workspace` is the automatic mode above; with a caller's workspace it means 0.
+sim_method 'pcg' (no reference counterpart) projects with the converged solve of fluid.solveLinearSystemPCG: mconf['pcgTol']
+(default 1e-5) and mconf['pcgIter'] (default 50); the wall BCs and periodic patches as for 'jacobi'.
 `geom` (an `ext.Geom`, 3D only) selects the reference-quirk mode / a z-slab view for this call; it is per call, the
 extension keeps no state.
 """
@@ -67,9 +71,10 @@ class _AutoStep:
         self.flags_id = self.bc_id = None     # identities at the previous call
         self.mask_id = None                   # flags identity the kept 3D obstacle mask was built from
         self.cls_id = None                    # BC identity the kept class map was built from
+        self.mg_id = None                     # flags identity the kept PCG hierarchy was built from (set after a successful call)
         self.held = None                      # the five tensors themselves: alive -> their addresses cannot be reused
 
-    def static_bits(self, batch_dict, flags, is3D, jacobi):
+    def static_bits(self, batch_dict, flags, is3D, jacobi, pcg=False):
         fid = _ident(flags)
         bcs = [batch_dict.get(k) for k in _BC_KEYS]
         bid = None if any(_ident(t) is None for t in bcs) else tuple(_ident(t) for t in bcs)
@@ -83,11 +88,19 @@ class _AutoStep:
             self.cls_id = bid
         else:
             self.cls_id = None
+        if pcg and (bits & 1) and self.mg_id == fid:
+            bits |= 8                         # the kept hierarchy is that of these flags
+        if pcg:
+            self.mg_id = None                 # until the call has succeeded (built_hierarchy)
         if is3D and jacobi:
             self.mask_id = fid                # this call leaves the mask of these flags behind (built now, or reused)
         self.flags_id, self.bc_id = fid, bid
         self.held = (flags, bcs)
         return bits
+
+    def built_hierarchy(self, flags):
+        """a 'pcg' step on this workspace has succeeded: it holds the multigrid hierarchy of these flags"""
+        self.mg_id = _ident(flags)
 
 
 def _auto_step(flags, is3D):
@@ -122,7 +135,7 @@ def release_workspaces():
 
 def simulate(mconf, batch_dict, net, sim_method, output_div=False, fused=True, workspace=None, static_flags=None,
              geom=None):
-    assert sim_method in ("convnet", "jacobi"), "Simulation method not supported. Choose either convnet or jacobi."
+    assert sim_method in ("convnet", "jacobi", "pcg"), "Simulation method not supported. Choose convnet, jacobi or pcg."
     dt = float(mconf["dt"])
     maccormackStrength = mconf["maccormackStrength"]
     sampleOutsideFluid = mconf["sampleOutsideFluid"]
@@ -149,11 +162,13 @@ def simulate(mconf, batch_dict, net, sim_method, output_div=False, fused=True, w
         gvec = _gravity(mconf, 1.0)[0] if want_gvec else [0.0, 0.0, 0.0]
         density = batch_dict["density"] if has_density else None
         packed = net.packed_for(U.device) if (sim_method == "convnet") else None
+        auto = None
         if workspace is None and static_flags is None and flags.is_cuda and geom is None:
             # the reference's four-argument call: the layer's own workspace, static inputs detected (module docstring)
             auto = _auto_step(flags, is3D)
             if auto is not None:
-                workspace, static_flags = auto.workspace, auto.static_bits(batch_dict, flags, is3D, sim_method == "jacobi")
+                workspace, static_flags = auto.workspace, auto.static_bits(batch_dict, flags, is3D, sim_method == "jacobi",
+                                                                           sim_method == "pcg")
         if static_flags is None:
             static_flags = 0
         ext.simulate_step_(p, U, flags, density, batch_dict.get("UBC"), batch_dict.get("UBCInvMask"),
@@ -165,7 +180,10 @@ def simulate(mconf, batch_dict, net, sim_method, output_div=False, fused=True, w
                            getattr(net, "precision_mode", "fp32") if sim_method == "convnet" else "fp32",
                            float(viscosity), float(gravityScale) if gravityScale > 0 else 0.0,
                            bool(mconf.get("correctScalar", False)) and has_density, periodic,
-                           batch_dict.get("flags_stick") if sim_method == "convnet" else None)
+                           batch_dict.get("flags_stick") if sim_method == "convnet" else None,
+                           pcg_tol=float(mconf.get("pcgTol", 1e-5)), pcg_iter=int(mconf.get("pcgIter", 50)))
+        if auto is not None and sim_method == "pcg":
+            auto.built_hierarchy(flags)
         if not has_density:
             batch_dict["density"] = torch.zeros_like(flags)     # simulate.py:82-83
         return
@@ -224,8 +242,12 @@ def simulate(mconf, batch_dict, net, sim_method, output_div=False, fused=True, w
     else:
         div = fluid.velocityDivergence(U, flags, geom=geom)
         is3D = U.size(2) > 1
-        p, residual = fluid.solveLinearSystemJacobi(flags=flags, div=div, is_3d=is3D, p_tol=mconf["pTol"],
-                                                    max_iter=mconf["jacobiIter"], geom=geom)
+        if sim_method == "pcg":
+            p, residual = fluid.solveLinearSystemPCG(flags=flags, div=div, is_3d=is3D, p_tol=mconf.get("pcgTol", 1e-5),
+                                                     max_iter=mconf.get("pcgIter", 50), geom=geom)
+        else:
+            p, residual = fluid.solveLinearSystemJacobi(flags=flags, div=div, is_3d=is3D, p_tol=mconf["pTol"],
+                                                        max_iter=mconf["jacobiIter"], geom=geom)
         fluid.velocityUpdate(pressure=p, U=U, flags=flags, geom=geom)
         U = wall_bcs(U)
     setConstVals(batch_dict, p, U, flags, density)

@@ -22,6 +22,7 @@ HIP_UNITS = {
     "fnx_stencils.hip": ["-ffp-contract=off"],
     "fnx_advect.hip": ["-ffp-contract=off", "-Rpass-analysis=kernel-resource-usage"],
     "fnx_jacobi.hip": ["-ffp-contract=off"],
+    "fnx_pcg.hip": [],
     "fnx_step.hip": ["-ffp-contract=off"],
     "fnx_api.hip": ["-ffp-contract=off"],
     # (resource-usage remarks: build_lib checks the kernels of SCRATCH_FREE)

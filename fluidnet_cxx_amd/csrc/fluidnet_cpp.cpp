@@ -1,4 +1,5 @@
 #include <memory>
+#include <optional>
 // torch cpp-extension `fluidnet_cpp` for MI355X: the reference's three pybind entry points
 // (pytorch/lib/fluid/cpp/fluids_init.cpp:1009-1014) with identical names and positional signatures, bound
 // to the C ABI of libfluidnet_hip.so, plus the operators the reference implements in Python
@@ -164,6 +165,51 @@ std::vector<Tensor> solve_linear_system(Tensor flags, Tensor div, const bool is3
                                                            residual.data_ptr<float>(), p_tol, max_iter, &iters, ws.ptr, ws.bytes,
                                                            cur_stream(flags)));
   return {p, residual};
+}
+
+// ---- the converged solve (fnx_pcg, ABI 20; no reference counterpart) -------------------------------------
+// returns (p, residual, iterations per sample); the count needs a host synchronisation, so it is only read where the solve synchronises
+// anyway (p_tol > 0 or verbose) and is None otherwise: with p_tol <= 0 the call only enqueues (capturable in a HIP graph)
+std::tuple<Tensor, Tensor, std::optional<std::vector<int>>> solve_linear_system_pcg(Tensor flags, Tensor div, const bool is3D, const float p_tol,
+                                                                      const int max_iter, const bool verbose, const Geom* geom) {
+  FnxGrid g = grid_of(flags, is3D, geom);
+  check_scalar(div, g, "div");
+  TORCH_CHECK(max_iter >= 1, "At least 1 iteration is needed (maxIter < 1)");
+  c10::hip::HIPGuard guard(flags.get_device());
+  Tensor p = at::empty_like(flags);
+  Tensor residual = at::zeros({}, flags.options());
+  const size_t bytes = fnx_pcg_workspace_bytes(&g);
+  TORCH_CHECK(bytes > 0, fnx_last_error());
+  Tensor ws = at::empty({(int64_t)bytes}, flags.options().dtype(at::kByte));
+  std::vector<int> iters(g.B, 0);
+  const bool count = p_tol > 0.f || verbose;
+  check_status((verbose ? fnx_pcg_verbose : fnx_pcg)(&g, flags.data_ptr<float>(), div.data_ptr<float>(), p.data_ptr<float>(),
+                                                     residual.data_ptr<float>(), p_tol, max_iter, count ? iters.data() : nullptr,
+                                                     ws.data_ptr(), bytes, cur_stream(flags)));
+  if (!count) return {p, residual, std::nullopt};
+  return {p, residual, iters};
+}
+
+Tensor poisson_apply(Tensor flags, Tensor p, const bool is3D, const Geom* geom) {
+  FnxGrid g = grid_of(flags, is3D, geom);
+  check_scalar(p, g, "p");
+  c10::hip::HIPGuard guard(flags.get_device());
+  Tensor Ap = at::empty_like(p);
+  check_status(fnx_poisson_apply(&g, flags.data_ptr<float>(), p.data_ptr<float>(), Ap.data_ptr<float>(), cur_stream(flags)));
+  return Ap;
+}
+
+Tensor pcg_precondition(Tensor flags, Tensor r, const bool is3D, const Geom* geom) {
+  FnxGrid g = grid_of(flags, is3D, geom);
+  check_scalar(r, g, "r");
+  c10::hip::HIPGuard guard(flags.get_device());
+  Tensor z = at::empty_like(r);
+  const size_t bytes = fnx_pcg_workspace_bytes(&g);
+  TORCH_CHECK(bytes > 0, fnx_last_error());
+  Tensor ws = at::empty({(int64_t)bytes}, flags.options().dtype(at::kByte));
+  check_status(fnx_pcg_precondition(&g, flags.data_ptr<float>(), r.data_ptr<float>(), z.data_ptr<float>(), ws.data_ptr(), bytes,
+                                    cur_stream(flags)));
+  return z;
 }
 
 // ---- operators the reference writes in Python -------------------------------------------------------
@@ -410,19 +456,21 @@ void simulate_step_(Tensor p, Tensor U, Tensor flags, c10::optional<Tensor> dens
                     std::vector<double> gravity_vec, double operating_density, double p_tol, int jacobi_iter,
                     const std::string method, double normalize_threshold, c10::optional<Tensor> workspace,
                     int static_flags, const Geom* geom, const std::string& precision_mode, double viscosity,
-                    double gravity_scale, bool correct_scalar, int periodic, c10::optional<Tensor> flags_stick) {
+                    double gravity_scale, bool correct_scalar, int periodic, c10::optional<Tensor> flags_stick, double pcg_tol,
+                    int pcg_iter) {
   check_field(U, "U");
   FnxGrid g = grid_of(flags, U.size(1) == 3, geom);
   check_vel(U, g, "U"); check_scalar(p, g, "p");
   TORCH_CHECK(viscosity >= 0, "Viscosity must be positive");
-  TORCH_CHECK(method == "jacobi" || method == "convnet", "Simulation method not supported. Choose either convnet or jacobi.");
+  TORCH_CHECK(method == "jacobi" || method == "convnet" || method == "pcg", "Simulation method not supported. Choose convnet, jacobi or pcg.");
   TORCH_CHECK(gravity_vec.size() == 3, "gravityVec needs x, y, z");
   FnxStepParams prm{};
   prm.dt = (float)dt; prm.maccormack_strength = (float)maccormack_strength; prm.sample_outside_fluid = sample_outside_fluid;
   prm.buoyancy_scale = (float)buoyancy_scale;
   for (int a = 0; a < 3; ++a) prm.gravity_vec[a] = (float)gravity_vec[a];
   prm.operating_density = (float)operating_density; prm.p_tol = (float)p_tol; prm.jacobi_iter = jacobi_iter;
-  prm.method = method == "convnet" ? 1 : 0; prm.normalize_threshold = (float)normalize_threshold;
+  prm.method = method == "convnet" ? 1 : (method == "pcg" ? 2 : 0); prm.normalize_threshold = (float)normalize_threshold;
+  prm.pcg_tol = (float)pcg_tol; prm.pcg_iter = pcg_iter;
   prm.precision_mode = precision_of(precision_mode);
   prm.viscosity = (float)viscosity; prm.gravity_scale = (float)gravity_scale; prm.correct_scalar = correct_scalar ? 1 : 0;
   prm.periodic = periodic;
@@ -527,7 +575,7 @@ struct PySlab {
             c10::optional<Tensor> densityBC, c10::optional<Tensor> densityBCInvMask, double dt, double maccormack_strength,
             bool sample_outside_fluid, double buoyancy_scale, std::vector<double> gravity_vec, double operating_density,
             double p_tol, int jacobi_iter, Tensor workspace, c10::optional<Tensor> net, const std::string& precision_mode,
-            double normalize_threshold) {
+            double normalize_threshold, const std::string& method) {
     check_field(U, "U");
     Geom none;
     FnxGrid g = grid_of(flags, true, &none);
@@ -547,6 +595,8 @@ struct PySlab {
       TORCH_CHECK(net->is_cuda() && net->is_contiguous(), "net: the packed weights (scalenet_pack) on the GPU");
       prm.method = 1; prm.precision_mode = precision_of(precision_mode); prm.normalize_threshold = (float)normalize_threshold;
     }
+    TORCH_CHECK(method == "auto" || method == "jacobi" || method == "convnet" || method == "pcg", "unknown z-slab step method '", method, "'");
+    if (method == "pcg") prm.method = 2;           // refused by fnx_slab_step (single-domain only)
     auto opt = [&](c10::optional<Tensor>& t, bool vel, const char* name) -> float* {
       if (!t.has_value() || !t->defined()) return nullptr;
       if (vel) check_vel(*t, g, name); else check_scalar(*t, g, name);
@@ -742,6 +792,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("plan") = "auto", NoGil());
   m.def("solve_linear_system", &solve_linear_system, "Solve Linear System using Jacobi's method", py::arg("flags"),
         py::arg("div"), py::arg("is3D"), py::arg("p_tol"), py::arg("max_iter"), py::arg("verbose"), GEOM, NoGil());
+  m.def("solve_linear_system_pcg", &solve_linear_system_pcg, "Converged pressure solve: multigrid-preconditioned CG (fnx_pcg); "
+        "returns (p, residual, iterations per sample or None when p_tol <= 0)", py::arg("flags"), py::arg("div"), py::arg("is3D"), py::arg("p_tol") = 1e-5,
+        py::arg("max_iter") = 50, py::arg("verbose") = false, GEOM, NoGil());
+  m.def("poisson_apply", &poisson_apply, "A p, the operator of the pressure solve (fnx_poisson_apply)", py::arg("flags"), py::arg("p"),
+        py::arg("is3D"), GEOM, NoGil());
+  m.def("pcg_precondition", &pcg_precondition, "z = M^-1 r, one V-cycle of the PCG preconditioner (fnx_pcg_precondition)", py::arg("flags"),
+        py::arg("r"), py::arg("is3D"), GEOM, NoGil());
   // operators the reference implements in Python
   m.def("velocity_divergence", &velocity_divergence, py::arg("U"), py::arg("flags"), GEOM, NoGil());
   m.def("velocity_update_", &velocity_update_, py::arg("pressure"), py::arg("U"), py::arg("flags"), GEOM, NoGil());
@@ -772,7 +829,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("operating_density"), py::arg("p_tol"), py::arg("jacobi_iter"), py::arg("method"),
         py::arg("normalize_threshold"), py::arg("workspace") = py::none(), py::arg("static_flags") = 0, GEOM,
         py::arg("precision_mode") = "fp32", py::arg("viscosity") = 0.0, py::arg("gravity_scale") = 0.0,
-        py::arg("correct_scalar") = false, py::arg("periodic") = 0, py::arg("flags_stick") = py::none(), NoGil());
+        py::arg("correct_scalar") = false, py::arg("periodic") = 0, py::arg("flags_stick") = py::none(), py::arg("pcg_tol") = 1e-5,
+        py::arg("pcg_iter") = 50, NoGil());
   m.def("step_workspace_bytes", &step_workspace_bytes);
   m.def("jacobi_sweeps_", &jacobi_sweeps_, py::arg("flags"), py::arg("div"), py::arg("p"), py::arg("is3D"), py::arg("nsweeps"),
         py::arg("workspace") = py::none(), py::arg("reuse_mask") = false, GEOM, py::arg("from_zero") = false, NoGil());
@@ -866,7 +924,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            py::arg("densityBC"), py::arg("densityBCInvMask"), py::arg("dt"), py::arg("maccormack_strength"),
            py::arg("sample_outside_fluid"), py::arg("buoyancy_scale"), py::arg("gravity_vec"), py::arg("operating_density"),
            py::arg("p_tol"), py::arg("jacobi_iter"), py::arg("workspace"), py::arg("net") = py::none(), py::arg("precision_mode") = "fp32",
-           py::arg("normalize_threshold") = 1e-5, NoGil());
+           py::arg("normalize_threshold") = 1e-5, py::arg("method") = "auto", NoGil());
   m.def("device_name", []() { const char* n = fnx_device_name(); return std::string(n ? n : ""); });
   m.def("abi_version", &fnx_abi_version);
   m.def("profile_enable", [](bool on, bool runs) { fnx_profile_enable(on ? (runs ? 2 : 1) : 0); }, py::arg("on"), py::arg("runs") = false);

@@ -87,17 +87,23 @@ bool carve_jacobi(const FnxGrid* g, void* ws, size_t ws_bytes, JacobiWs* out, si
   *need = c.off;
   return c.ok();
 }
+// PCG: the multigrid hierarchy (kept between steps by fnx_simulate_step), then the solver's vectors
+size_t ws_pcg_kept(const FnxGrid* g) { return al(fnx::pcg_kept_bytes(dims(g), g->is3D)); }
+size_t ws_pcg(const FnxGrid* g) { return ws_pcg_kept(g) + al(fnx::pcg_scratch_bytes(dims(g), g->is3D)); }
 size_t ws_step(const FnxGrid* g) {
   const size_t nc = g->is3D ? 3 : 2;
   // 2D: the fused advection launches keep both forward fields at once
   size_t adv = ws_advect_scalar_fields(g) + ws_advect_vel_fields(g) + ws_advect_fix(g);
   size_t solve = ws_jacobi(g);
   size_t cnn = fnx::fluidnet_ws_bytes(dims(g), g->is3D);
+  size_t pcg = al(fnx::pcg_scratch_bytes(dims(g), g->is3D));
   size_t tail = adv > solve ? adv : solve;
   if (cnn > tail) tail = cnn;
+  if (pcg > tail) tail = pcg;
   return al(ncell(g) * 4) /*rho2*/ + al(ncell(g) * 4 * nc) /*U2*/ + al(ncell(g) * 4) /*div*/ +
          ws_mask(g) /*Jacobi obstacle mask, kept between steps*/ +
          al(ncell(g)) /*BC class map, kept between steps*/ +
+         ws_pcg_kept(g) /*PCG multigrid hierarchy, kept between steps*/ +
          (g->is3D ? 0 : al(ncell(g) * 4 * nc)) /*2D: the viscous velocity that is advected (FnxStepParams.viscosity)*/ + tail;
 }
 
@@ -616,6 +622,70 @@ int fnx_residual(const FnxGrid* g, const float* a, const float* b, float* sumsq,
   return FNX_OK;
 }
 
+size_t fnx_pcg_workspace_bytes(const FnxGrid* g) {
+  if (check_grid(g) != FNX_OK) return 0;
+  return ws_pcg(g);
+}
+
+namespace {
+int check_pcg_grid(const FnxGrid* g, const char* who) {
+  if (int rc = check_grid(g)) return rc;
+  if (g->k_begin != 0 || g->k_end != 0 || g->z_offset != 0 || g->D_global != 0)
+    return fail(FNX_EINVAL, "%s: no compute window or z-slab view (the solve is single-domain)", who);
+  return FNX_OK;
+}
+
+int pcg_entry(const FnxGrid* g, const float* flags, const float* div, float* p, float* residual, float p_tol, int max_iter,
+              int* iters_done, void* ws, size_t ws_bytes, void* stream, bool verbose) {
+  if (int rc = check_pcg_grid(g, "pcg")) return rc;
+  if (!flags || !div || !p) return fail(FNX_EINVAL, "pcg: NULL tensor");
+  if (div == p) return fail(FNX_EINVAL, "pcg: p must not alias div");
+  if (max_iter < 1) return fail(FNX_EINVAL, "At least 1 iteration is needed (maxIter < 1)");
+  if (!ws || ws_bytes < ws_pcg(g)) return fail(FNX_EWORKSPACE, "pcg: workspace too small (%zu < %zu)", ws_bytes, ws_pcg(g));
+  hipStream_t s = (hipStream_t)stream;
+  const GridDims d = dims(g);
+  char* kept = (char*)ws;
+  fnx::launch_pcg_build(d, g->is3D, quirks(g), flags, kept, s);
+  HIP_OK(hipGetLastError());
+  if (int rc = fnx::pcg_solve(d, g->is3D, kept, kept + ws_pcg_kept(g), div, p, residual, p_tol, max_iter, iters_done, verbose, s)) return rc;
+  HIP_OK(hipGetLastError());
+  return FNX_OK;
+}
+}  // namespace
+
+int fnx_pcg(const FnxGrid* g, const float* flags, const float* div, float* p, float* residual, float p_tol, int max_iter,
+            int* iters_done, void* ws, size_t ws_bytes, void* stream) {
+  return pcg_entry(g, flags, div, p, residual, p_tol, max_iter, iters_done, ws, ws_bytes, stream, false);
+}
+
+int fnx_pcg_verbose(const FnxGrid* g, const float* flags, const float* div, float* p, float* residual, float p_tol, int max_iter,
+                    int* iters_done, void* ws, size_t ws_bytes, void* stream) {
+  return pcg_entry(g, flags, div, p, residual, p_tol, max_iter, iters_done, ws, ws_bytes, stream, true);
+}
+
+int fnx_poisson_apply(const FnxGrid* g, const float* flags, const float* p, float* Ap, void* stream) {
+  if (int rc = check_pcg_grid(g, "poisson_apply")) return rc;
+  if (!flags || !p || !Ap) return fail(FNX_EINVAL, "poisson_apply: NULL tensor");
+  if (p == Ap) return fail(FNX_EINVAL, "poisson_apply: Ap must not alias p");
+  fnx::launch_poisson_apply(dims(g), g->is3D, quirks(g), flags, p, Ap, (hipStream_t)stream);
+  HIP_OK(hipGetLastError());
+  return FNX_OK;
+}
+
+int fnx_pcg_precondition(const FnxGrid* g, const float* flags, const float* r, float* z, void* ws, size_t ws_bytes, void* stream) {
+  if (int rc = check_pcg_grid(g, "pcg_precondition")) return rc;
+  if (!flags || !r || !z) return fail(FNX_EINVAL, "pcg_precondition: NULL tensor");
+  if (r == z) return fail(FNX_EINVAL, "pcg_precondition: z must not alias r");
+  if (!ws || ws_bytes < ws_pcg(g)) return fail(FNX_EWORKSPACE, "pcg_precondition: workspace too small (%zu < %zu)", ws_bytes, ws_pcg(g));
+  hipStream_t s = (hipStream_t)stream;
+  const GridDims d = dims(g);
+  char* kept = (char*)ws;
+  fnx::launch_pcg_build(d, g->is3D, quirks(g), flags, kept, s);
+  fnx::launch_pcg_precondition(d, g->is3D, kept, kept + ws_pcg_kept(g), r, z, s);
+  HIP_OK(hipGetLastError());
+  return FNX_OK;
+}
+
 int fnx_velocity_update(const FnxGrid* g, const float* p, float* U, const float* flags, void* stream) {
   if (int rc = check_grid(g)) return rc;
   if (!p || !U || !flags) return fail(FNX_EINVAL, "velocity_update: NULL tensor");
@@ -797,7 +867,7 @@ int fnx_pre_projection(const FnxGrid* g, const FnxStepParams* prm, const FnxStat
   }
   // simulate.py:119-130: setWallBcs and the periodic patches in the Jacobi branch only; with 'flags_stick' the convnet branch
   // runs setWallBcsStick between the stages and the second setConstVals, which are then the caller's (fnx_simulate_step)
-  const bool wall = prm->method == 0;
+  const bool wall = prm->method != 1;
   const bool periodic = wall && (prm->periodic & 1);
   const bool second_bcs = !(prm->method == 1 && st->flags_stick);
   fnx::ProfScope ps(FNX_PROF_STAGE, (hipStream_t)stream);
@@ -847,7 +917,10 @@ int fnx_simulate_step(const FnxGrid* g, const FnxStepParams* prm, const FnxState
                       void* stream) {
   if (int rc = check_grid(g)) return rc;
   if (!prm || !st || !st->p || !st->U || !st->flags) return fail(FNX_EINVAL, "simulate_step: NULL state");
-  if (prm->method != 0 && prm->method != 1) return fail(FNX_EINVAL, "Simulation method not supported. Choose either convnet or jacobi.");
+  if (prm->method < 0 || prm->method > 2) return fail(FNX_EINVAL, "Simulation method not supported. Choose convnet, jacobi or pcg.");
+  if (prm->method == 2 && prm->pcg_iter < 1) return fail(FNX_EINVAL, "At least 1 iteration of the solver is needed (pcg_iter < 1)");
+  if (prm->method == 2 && (g->k_begin != 0 || g->k_end != 0 || g->z_offset != 0 || g->D_global != 0))
+    return fail(FNX_EINVAL, "simulate_step: the PCG solve takes no compute window or z-slab view (single domain only)");
   if (prm->method == 1 && !st->net) return fail(FNX_EINVAL, "simulate_step: convnet method needs packed weights");
   hipStream_t s = (hipStream_t)stream;
   const size_t n = ncell(g), nc = g->is3D ? 3 : 2;
@@ -857,6 +930,7 @@ int fnx_simulate_step(const FnxGrid* g, const FnxStepParams* prm, const FnxState
   float* div = (float*)c.take(n * 4);
   unsigned char* kept_mask = g->is3D ? (unsigned char*)c.take(ws_mask(g)) : nullptr;
   unsigned char* kept_cls = (unsigned char*)c.take(n);
+  void* kept_pcg = c.take(ws_pcg_kept(g));
   float* orig = g->is3D ? nullptr : (float*)c.take(n * 4 * nc);        // 2D: the viscous velocity (prm->viscosity > 0)
   void* tail = c.take(0);
   const size_t tail_bytes = ws_bytes > c.off ? ws_bytes - c.off : 0;
@@ -867,7 +941,7 @@ int fnx_simulate_step(const FnxGrid* g, const FnxStepParams* prm, const FnxState
   if (viscous && g->is3D) return fail(FNX_EINVAL, "simulate_step: viscosity is 2D only (reference viscosity.py:5)");
   const bool stick = prm->method == 1 && st->flags_stick != nullptr;           // simulate.py:129-130, :165-166
   if (stick && g->is3D) return fail(FNX_EINVAL, "simulate_step: flags_stick is 2D only (set_wall_bcs_stick.py:85-86)");
-  const bool periodic = prm->method == 0 && (prm->periodic & 1);
+  const bool periodic = prm->method != 1 && (prm->periodic & 1);
   // simulate.py:66-93: advect density then velocity (both by the OLD U; the velocity advected is the viscous one)
   if (viscous) {
     if (int rc = fnx_add_viscosity(g, prm->dt, st->U, orig, st->flags, prm->viscosity, stream)) return rc;
@@ -899,7 +973,7 @@ int fnx_simulate_step(const FnxGrid* g, const FnxStepParams* prm, const FnxState
   stc.density_bc_applied = 1;                  // by the pre-projection stage below, with these BC arrays
   st = &stc;
   // simulate.py:96-133 (+ :144 divergence) in one pass: BCs, buoyancy, gravity, wall BCs (+ periodic patches), BCs, -div
-  if (int rc = fnx_pre_projection(g, prm, st, U2, has_rho ? rho2 : nullptr, prm->method == 0 ? div : nullptr, stream)) return rc;
+  if (int rc = fnx_pre_projection(g, prm, st, U2, has_rho ? rho2 : nullptr, prm->method != 1 ? div : nullptr, stream)) return rc;
   const GridDims d = dims(g);
   float* rho = has_rho ? st->density : nullptr;
   // setWallBcsStick is out of place: st->U -> U2 (free since the staging pass) and back
@@ -908,9 +982,17 @@ int fnx_simulate_step(const FnxGrid* g, const FnxStepParams* prm, const FnxState
     HIP_OK(hipMemcpyAsync(st->U, U2, n * 4 * nc, hipMemcpyDeviceToDevice, s));
     return FNX_OK;
   };
-  if (prm->method == 0) {
+  if (prm->method != 1) {
     // simulate.py:144-168
-    if (int rc = jacobi_solve(g, st->flags, div, st->p, nullptr, prm->p_tol, prm->jacobi_iter, nullptr, tail, tail_bytes, kept_mask, (prm->static_flags & 1) != 0, stream, 0)) return rc;
+    if (prm->method == 0) {
+      if (int rc = jacobi_solve(g, st->flags, div, st->p, nullptr, prm->p_tol, prm->jacobi_iter, nullptr, tail, tail_bytes, kept_mask, (prm->static_flags & 1) != 0, stream, 0)) return rc;
+    } else {
+      // the hierarchy is only trusted when the caller says both that flags are unchanged (bit 0) and that this workspace holds
+      // the hierarchy of these flags (bit 3)
+      if ((prm->static_flags & 9) != 9) fnx::launch_pcg_build(d, g->is3D, quirks(g), st->flags, kept_pcg, s);
+      if (tail_bytes < fnx::pcg_scratch_bytes(d, g->is3D)) return fail(FNX_EWORKSPACE, "simulate_step: workspace too small for the PCG solve");
+      if (int rc = fnx::pcg_solve(d, g->is3D, kept_pcg, tail, div, st->p, nullptr, prm->pcg_tol, prm->pcg_iter, nullptr, false, s)) return rc;
+    }
     if (!periodic) return fnx_post_projection(g, st, stream);
     // simulate.py:157-164: the patches read the field as it was before setWallBcs; their source row / column (border cells,
     // which velocityUpdate leaves alone) is saved ahead of the in-place pass.  The solve is through with the tail.

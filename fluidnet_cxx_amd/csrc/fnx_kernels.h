@@ -118,4 +118,15 @@ void launch_residual(int B, size_t per_sample, size_t first, size_t count, const
                      float* sumsq, float* res, hipStream_t s);
 void launch_residual_root(int B, const float* sumsq, float* res, hipStream_t s);   // res = max_b sqrt(sumsq[b])
 
+// Multigrid-preconditioned CG (fnx_pcg.hip).  `kept`: the hierarchy built from flags (pcg_kept_bytes, reusable while flags do not
+// change); `scratch`: vectors, partial sums and per-sample scalars (pcg_scratch_bytes).
+size_t pcg_kept_bytes(const GridDims& g, bool is3d);
+size_t pcg_scratch_bytes(const GridDims& g, bool is3d);
+void launch_pcg_build(const GridDims& g, bool is3d, bool quirks, const float* flags, void* kept, hipStream_t s);
+void launch_poisson_apply(const GridDims& g, bool is3d, bool quirks, const float* flags, const float* x, float* y, hipStream_t s);
+void launch_pcg_precondition(const GridDims& g, bool is3d, const void* kept, void* scratch, const float* r, float* z, hipStream_t s);
+// returns FNX_OK or an FNX_E* code (set_error); synchronises only for tol > 0, iters_done != null or verbose
+int pcg_solve(const GridDims& g, bool is3d, const void* kept, void* scratch, const float* div, float* p, float* residual, float tol,
+              int max_iter, int* iters_done, bool verbose, hipStream_t s);
+
 }  // namespace fnx

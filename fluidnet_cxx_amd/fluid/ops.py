@@ -92,6 +92,17 @@ def solveLinearSystemJacobi(flags, div, is_3d=False, p_tol=1e-5, max_iter=1000, 
     return p, res
 
 
+def solveLinearSystemPCG(flags, div, is_3d=False, p_tol=1e-5, max_iter=50, verbose=False, *, geom=None):
+    """The converged pressure solve (no reference counterpart): the pressure the Jacobi solve tends to with infinitely many sweeps, by
+    multigrid-preconditioned conjugate gradients (fnx_pcg).  Stops per sample at ||div - A p|| <= p_tol ||div|| (div projected onto
+    mean zero over the fluid cells of a closed domain, p then has mean zero there); p_tol <= 0 runs exactly max_iter iterations.
+    Returns (p, residual) like solveLinearSystemJacobi, residual the largest relative residual of the batch (0-dim tensor)."""
+    _check5(div, flags)
+    assert flags.size(1) == 1, "flags is not scalar"
+    p, res, _ = ext.solve_linear_system_pcg(flags, div, bool(is_3d), float(p_tol), int(max_iter), bool(verbose), geom)
+    return p, res
+
+
 # ---- autograd: the reference's operators are chains of differentiable ATen ops, and its training graph goes through
 # velocityUpdate -> setWallBcs -> velocityDivergence (model.py:190-227, fluid_net_train.py:366).  Here each operator is one
 # native launch, so its adjoint is one too (fnx_velocity_divergence_backward, fnx_velocity_update_backward; setWallBcs is

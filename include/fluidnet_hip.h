@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define FNX_ABI_VERSION 19
+#define FNX_ABI_VERSION 20
 
 enum {
   FNX_OK = 0,
@@ -185,6 +185,34 @@ int fnx_jacobi_pass_mirror(const FnxGrid* g, const float* flags, const float* di
                            int k_end, int k_begin2, int layout, const FnxPlaneMirror* mirror, void* ws, size_t ws_bytes,
                            int reuse_mask, void* stream);
 
+/* ---- Converged pressure solve (ABI 20; the reference has none: its README names PCG as what FluidNet replaces) ----
+ * The system is the fixed point of fnx_jacobi, in the same semantics (FnxGrid.ref_quirks included): on an ACTIVE cell (neither
+ * border nor TypeObstacle)  (denom - n_obs) p_i - sum_{active nbr j} p_j = div_i,  denom 4 (2D) / 6 (3D), n_obs the obstacle
+ * neighbours (Neumann: the Jacobi substitutes p_i; with ref_quirks in 3D the z obstacle neighbours count 0 instead),
+ * a non-obstacle border neighbour 0 (Dirichlet); every other cell gets p = 0.  A is symmetric positive semi-definite.  A sample none
+ * of whose active cells touches a Dirichlet cell (every closed box) is singular: div is projected onto mean zero over the active
+ * cells, and p is returned with active-cell mean zero (velocityUpdate ignores constants).  Several closed fluid components (a pocket
+ * sealed inside obstacles) keep one null vector each of which only the global mean is removed: such a solve may stop at max_iter
+ * without converging (finite output, residual above p_tol).
+ * Method: conjugate gradients from p = 0, preconditioned by one symmetric V-cycle of an aggregation multigrid (2:1 in every axis,
+ * Galerkin coarse operators built from flags on the device, damped Jacobi 2 + 2, coarse correction x 1.8).  Per sample it stops at
+ * ||r||_2 <= p_tol ||b||_2 (b: the projected div) and is frozen from then on.  residual: DEVICE float, max over the batch of that
+ * relative residual from the recurrence (may be NULL); iters_done: HOST int[B] or NULL.  p_tol <= 0 runs exactly max_iter
+ * iterations without a host synchronisation (capturable in a HIP graph); p_tol > 0 reads one device flag every 4 iterations.
+ * Dot products: fp64 partial sums added in a fixed order, no atomics -- the same bits run to run.  No compute window, no z-slab view. */
+size_t fnx_pcg_workspace_bytes(const FnxGrid* g);
+int fnx_pcg(const FnxGrid* g, const float* flags, const float* div, float* p, float* residual, float p_tol, int max_iter,
+            int* iters_done, void* ws, size_t ws_bytes, void* stream);
+/* The same with one line per iteration on stdout ("PCG iteration N: residual R") and the termination reason: one host
+ * synchronisation per iteration. */
+int fnx_pcg_verbose(const FnxGrid* g, const float* flags, const float* div, float* p, float* residual, float p_tol, int max_iter,
+                    int* iters_done, void* ws, size_t ws_bytes, void* stream);
+/* Ap = A p (the operator above; p is read on active cells only, Ap is 0 elsewhere).  No workspace. */
+int fnx_poisson_apply(const FnxGrid* g, const float* flags, const float* p, float* Ap, void* stream);
+/* z = M^-1 r, one V-cycle of the preconditioner (a fixed symmetric linear map; r is read on active cells only, z is 0 elsewhere).
+ * ws: fnx_pcg_workspace_bytes. */
+int fnx_pcg_precondition(const FnxGrid* g, const float* flags, const float* r, float* z, void* ws, size_t ws_bytes, void* stream);
+
 /* velocityUpdate (in place on U), lib/fluid/velocity_update.py:6-162 */
 int fnx_velocity_update(const FnxGrid* g, const float* p, float* U, const float* flags, void* stream);
 
@@ -252,7 +280,8 @@ typedef struct FnxStepParams {
   float operating_density;    /* mconf['operatingDensity'] */
   float p_tol;                /* mconf['pTol'] */
   int   jacobi_iter;          /* mconf['jacobiIter'] */
-  int   method;               /* 0 = 'jacobi', 1 = 'convnet' */
+  int   method;               /* 0 = 'jacobi', 1 = 'convnet', 2 = 'pcg' (ABI 20: fnx_pcg with pcg_tol / pcg_iter below; the wall BCs
+                                 and periodic patches as for method 0) */
   float normalize_threshold;  /* mconf['normalizeInputThreshold'] (convnet) */
   int   precision_mode;       /* convnet: FNX_PRECISION_FP32 (0, the default), _FP32_DIRECT, _BF16X6 or _BF16X3, see fnx_multiscale_forward */
   int   static_flags;         /* promises about the previous fnx_simulate_step on this workspace (no reference key; every
@@ -260,7 +289,14 @@ typedef struct FnxStepParams {
                                  bit 0: `flags` is unchanged -> the 3D Jacobi solver reuses the obstacle mask it left there;
                                  bit 1: UBC / UBCInvMask / densityBC / densityBCInvMask are unchanged -> the BC stages use a
                                         1-byte-per-cell class map kept in the workspace (see FnxState.bc_class);
-                                 bit 2: that class map was already built by an earlier call with bit 1 set */
+                                 bit 2: that class map was already built by an earlier call with bit 1 set;
+                                 bit 3 (method 2): the PCG multigrid hierarchy in this workspace was built by an earlier call for
+                                        these flags AND this FnxGrid.ref_quirks (the hierarchy depends on both) -- reused only
+                                        together with bit 0.
+                                 The step workspace (fnx_workspace_bytes FNX_OP_STEP) holds that hierarchy for every method:
+                                 ~2 bytes per cell + 16 bytes per coarse cell (~4.3 B per cell in 3D, ~2.7 in 2D), kept between
+                                 steps; the PCG vectors (~26 B per cell) share the scratch tail with the advection and the CNN,
+                                 whose needs are larger, so they add nothing there */
   /* Optional stages of lib/simulate.py (all off when zero; fnx_slab_step refuses them): */
   float viscosity;            /* mconf['viscosity'] > 0 (2D only, like addViscosity): the velocity advected is
                                  addViscosity(U.clone()), advected by U (simulate.py:66-69, :85-93) */
@@ -271,6 +307,9 @@ typedef struct FnxStepParams {
   int   periodic;             /* bit 0: mconf has BOTH 'periodic-x' and 'periodic-y'; bit 1 / bit 2: their values.  Method 0
                                  only (simulate.py:121-128, :157-164): U[:,1,:,:,1] = U_temp[:,1,:,:,W-1],
                                  U[:,0,:,1] = U_temp[:,0,:,H-1] after each setWallBcs, U_temp the field before it */
+  /* ABI 20, method 2 (mconf['pcgTol'], mconf['pcgIter']): */
+  float pcg_tol;              /* relative residual ||b - A p|| / ||b|| to stop at; <= 0 runs exactly pcg_iter iterations, no host sync */
+  int   pcg_iter;             /* at most that many CG iterations (>= 1) */
 } FnxStepParams;
 
 typedef struct FnxState {
@@ -472,6 +511,7 @@ void fnx_slab_destroy(FnxSlab* s);
  * bits on every rank; one host synchronisation), FNX_SLAB_NET_MARGIN + 1 ghost planes of U exchanged once, the net evaluated on
  * owned +- FNX_SLAB_NET_MARGIN planes, velocityUpdate / un-normalise / setWallBcs / setConstVals on the owned planes: p and U
  * within the CNN tolerance (1e-5 |ref|max) of the single-domain step, density bit for bit.
+ * prm->method 2 (PCG) is refused with FNX_EINVAL: its dot products would need an all-reduce per iteration (single domain only).
  * Jacobi:  prm->p_tol > 0 runs the reference's convergence test (fluids_init.cpp:961-979): one sweep per ghost exchange,
  * the squared differences over the owned planes all-reduced over the ranks, one host sync per sweep (as in fnx_jacobi);
  * every rank's part reproducible (fnx_residual).  The bit-for-bit statement above holds for p_tol == 0; with p_tol > 0 every
