@@ -1,6 +1,7 @@
 """fluidnet_cxx_amd: MI355X-native fluid time-step behind fluidnet_cxx's operator surface.
 
     from fluidnet_cxx_amd import fluid, simulate, FluidNet     # mirrors the reference's `lib`
+    from fluidnet_cxx_amd import FluidNetTrain                 # the same net with a native backward pass (2D)
 
 Importing the operator modules loads the native extension; there is no CPU fallback.
 """
@@ -18,4 +19,6 @@ def __getattr__(name):
         return importlib.import_module(".output", __name__)
     if name in ("FluidNet", "MultiScaleNet"):
         return getattr(importlib.import_module(".model", __name__), name)
+    if name == "FluidNetTrain":
+        return importlib.import_module(".train", __name__).FluidNetTrain
     raise AttributeError(name)

@@ -448,6 +448,127 @@ std::vector<Tensor> fluidnet_forward(Tensor packed, Tensor input, double normali
   return {p, U};
 }
 
+// ---- training of the 2D net (fnx_cnn_train.hip) -----------------------------------------------------------
+Tensor scalenet_pack_t(Tensor blob) {
+  TORCH_CHECK(blob.is_cuda() && blob.scalar_type() == at::kFloat && blob.is_contiguous(), "weights blob must be a contiguous float32 GPU tensor");
+  TORCH_CHECK((size_t)blob.numel() == fnx_scalenet_weight_floats(0), "weights blob has ", blob.numel(), " floats, expected ",
+              fnx_scalenet_weight_floats(0));
+  c10::hip::HIPGuard guard(blob.get_device());
+  Tensor packed = at::zeros({(int64_t)fnx_scalenet_packed_t_bytes()}, blob.options().dtype(at::kByte));
+  check_status(fnx_scalenet_pack_t(blob.data_ptr<float>(), packed.data_ptr(), cur_stream(blob)));
+  return packed;
+}
+
+// the two weight images look alike and differ in size: a swapped pair must not reach the device
+static void check_packed(const Tensor& t, size_t bytes, const char* what, const Tensor& like) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.get_device() == like.get_device() && (size_t)t.nbytes() == bytes, what, " must be the ",
+              bytes, "-byte image from scalenet_pack", bytes == fnx_scalenet_packed_t_bytes() ? "_t" : "", " on the input's device (got ",
+              t.nbytes(), " bytes)");
+}
+static FnxGrid grid2d(int64_t B, int64_t H, int64_t W) {
+  FnxGrid g{}; g.B = (int)B; g.D = 1; g.H = (int)H; g.W = (int)W;
+  return g;
+}
+// a (B,C,H,W) or (B,C,1,H,W) tensor of the 2D net; anything deeper is 3D, which the training entry points refuse
+static FnxGrid grid_of_net_tensor(const Tensor& x, const char* what) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.is_contiguous(), what, " must be a contiguous float32 GPU tensor");
+  TORCH_CHECK(x.dim() == 4 || x.dim() == 5, what, " must be (B,C,H,W) or (B,C,D,H,W)");
+  FnxGrid g = grid2d(x.size(0), x.size(x.dim() - 2), x.size(x.dim() - 1));
+  if (x.dim() == 5 && x.size(2) > 1) { g.D = (int)x.size(2); g.is3D = 1; }
+  return g;
+}
+
+std::vector<py::tuple> multiscale_tape_layout(int64_t B, int64_t H, int64_t W) {
+  const FnxGrid g = grid2d(B, H, W);
+  std::vector<FnxTapeEntry> e(fnx_multiscale_tape_entries());
+  if (fnx_multiscale_tape_layout(&g, e.data()) == 0) check_status(FNX_EINVAL);
+  std::vector<py::tuple> out;
+  for (const FnxTapeEntry& t : e) out.push_back(py::make_tuple(std::string(t.name), (int64_t)t.offset, t.C, t.H, t.W));
+  return out;
+}
+
+std::vector<Tensor> multiscale_forward_train(Tensor packed, Tensor x, const std::string& precision_mode) {
+  const FnxGrid g = grid_of_net_tensor(x, "x");
+  TORCH_CHECK(x.size(1) == 2, "x must have 2 channels");
+  check_packed(packed, fnx_scalenet_packed_bytes(0), "packed", x);
+  c10::hip::HIPGuard guard(x.get_device());
+  std::vector<int64_t> osz = x.sizes().vec(); osz[1] = 1;
+  Tensor p = at::empty(osz, x.options());
+  const size_t floats = g.is3D ? 1 : fnx_multiscale_tape_layout(&g, nullptr);
+  if (!g.is3D && floats == 0) check_status(FNX_EINVAL);
+  Tensor tape = at::empty({(int64_t)floats}, x.options());
+  check_status(fnx_multiscale_forward_train(&g, packed.data_ptr(), x.data_ptr<float>(), p.data_ptr<float>(), tape.data_ptr<float>(),
+                                            precision_of(precision_mode), cur_stream(x)));
+  return {p, tape};
+}
+
+static Tensor multiscale_backward_impl(Tensor packed_t, Tensor grad_p, Tensor tape, const std::string& precision_mode, bool plain) {
+  const FnxGrid g = grid_of_net_tensor(grad_p, "grad_p");
+  check_packed(packed_t, fnx_scalenet_packed_t_bytes(), "packed_t", grad_p);
+  TORCH_CHECK(grad_p.size(1) == 1, "grad_p must have 1 channel");
+  TORCH_CHECK(tape.is_cuda() && tape.scalar_type() == at::kFloat && tape.is_contiguous(), "tape must be a contiguous float32 GPU tensor");
+  TORCH_CHECK(g.is3D || (size_t)tape.numel() == fnx_multiscale_tape_layout(&g, nullptr), "tape has ", tape.numel(), " floats, not the layout of this grid");
+  c10::hip::HIPGuard guard(grad_p.get_device());
+  Tensor grad = at::empty({(int64_t)fnx_scalenet_weight_floats(0)}, grad_p.options());
+  const size_t bytes = g.is3D ? 1 : fnx_multiscale_backward_ws_bytes(&g);
+  Tensor ws = at::empty({(int64_t)bytes}, grad_p.options().dtype(at::kByte));
+  check_status((plain ? fnx_multiscale_backward_plain : fnx_multiscale_backward)(
+      &g, packed_t.data_ptr(), grad_p.data_ptr<float>(), tape.data_ptr<float>(), grad.data_ptr<float>(), precision_of(precision_mode),
+      ws.data_ptr(), bytes, cur_stream(grad_p)));
+  return grad;
+}
+Tensor multiscale_backward(Tensor packed_t, Tensor grad_p, Tensor tape, const std::string& precision_mode) {
+  return multiscale_backward_impl(packed_t, grad_p, tape, precision_mode, false);
+}
+// the plain weight-gradient kernel for every layer (fnx_multiscale_backward_plain): a cross-check, not a training path
+Tensor multiscale_backward_plain(Tensor packed_t, Tensor grad_p, Tensor tape, const std::string& precision_mode) {
+  return multiscale_backward_impl(packed_t, grad_p, tape, precision_mode, true);
+}
+
+// -> p, U, tape, s (B), flags (B,1,1,H,W)
+std::vector<Tensor> fluidnet_forward_train(Tensor packed, Tensor input, double normalize_threshold, const std::string& precision_mode) {
+  check_field(input, "input");
+  TORCH_CHECK(input.size(1) == 5 || input.size(1) == 6, "input must have 5 (2D) or 6 (3D) channels [p, U, flags, density]");
+  FnxGrid g = grid2d(input.size(0), input.size(3), input.size(4));
+  g.D = (int)input.size(2); g.is3D = input.size(1) == 6;
+  check_packed(packed, fnx_scalenet_packed_bytes(0), "packed", input);
+  c10::hip::HIPGuard guard(input.get_device());
+  const bool ok2d = !g.is3D && g.D == 1;
+  Tensor p = at::empty({g.B, 1, g.D, g.H, g.W}, input.options());
+  Tensor U = at::empty({g.B, g.is3D ? 3 : 2, g.D, g.H, g.W}, input.options());
+  Tensor flags = at::empty({g.B, 1, g.D, g.H, g.W}, input.options());
+  Tensor scale = at::empty({g.B}, input.options());
+  const size_t floats = ok2d ? fnx_multiscale_tape_layout(&g, nullptr) : 1, bytes = ok2d ? fnx_fluidnet_train_ws_bytes(&g) : 1;
+  if (ok2d && floats == 0) check_status(FNX_EINVAL);
+  Tensor tape = at::empty({(int64_t)floats}, input.options());
+  Tensor ws = at::empty({(int64_t)bytes}, input.options().dtype(at::kByte));
+  check_status(fnx_fluidnet_forward_train(&g, packed.data_ptr(), input.data_ptr<float>(), (float)normalize_threshold, p.data_ptr<float>(),
+                                          U.data_ptr<float>(), flags.data_ptr<float>(), scale.data_ptr<float>(), tape.data_ptr<float>(),
+                                          precision_of(precision_mode), ws.data_ptr(), bytes, cur_stream(input)));
+  return {p, U, tape, scale, flags};
+}
+
+Tensor fluidnet_backward(Tensor packed_t, Tensor flags, Tensor scale, Tensor grad_p, Tensor grad_U, Tensor tape,
+                         const std::string& precision_mode) {
+  check_field(grad_p, "grad_p"); check_field(grad_U, "grad_U"); check_field(flags, "flags");
+  TORCH_CHECK(grad_p.size(1) == 1 && grad_U.size(1) == 2 && flags.size(1) == 1 && grad_p.size(2) == 1, "fluidnet_backward is 2D: grad_p (B,1,1,H,W), grad_U (B,2,1,H,W)");
+  TORCH_CHECK(grad_U.size(0) == grad_p.size(0) && grad_U.size(3) == grad_p.size(3) && grad_U.size(4) == grad_p.size(4) &&
+              flags.sizes() == grad_p.sizes(), "grad_p, grad_U and flags must share their grid");
+  const FnxGrid g = grid2d(grad_p.size(0), grad_p.size(3), grad_p.size(4));
+  check_packed(packed_t, fnx_scalenet_packed_t_bytes(), "packed_t", grad_p);
+  TORCH_CHECK(scale.is_cuda() && scale.scalar_type() == at::kFloat && scale.is_contiguous() && scale.numel() == g.B, "scale must hold B floats on the GPU");
+  TORCH_CHECK(tape.is_cuda() && tape.scalar_type() == at::kFloat && tape.is_contiguous() &&
+              (size_t)tape.numel() == fnx_multiscale_tape_layout(&g, nullptr), "tape is not the layout of this grid");
+  c10::hip::HIPGuard guard(grad_p.get_device());
+  Tensor grad = at::empty({(int64_t)fnx_scalenet_weight_floats(0)}, grad_p.options());
+  const size_t bytes = fnx_fluidnet_train_ws_bytes(&g);
+  Tensor ws = at::empty({(int64_t)bytes}, grad_p.options().dtype(at::kByte));
+  check_status(fnx_fluidnet_backward(&g, packed_t.data_ptr(), flags.data_ptr<float>(), scale.data_ptr<float>(), grad_p.data_ptr<float>(),
+                                     grad_U.data_ptr<float>(), tape.data_ptr<float>(), grad.data_ptr<float>(), precision_of(precision_mode),
+                                     ws.data_ptr(), bytes, cur_stream(grad_p)));
+  return grad;
+}
+
 // one whole step of lib/simulate.py:28-171, in place on p, U, density
 void simulate_step_(Tensor p, Tensor U, Tensor flags, c10::optional<Tensor> density, c10::optional<Tensor> UBC,
                     c10::optional<Tensor> UBCInvMask, c10::optional<Tensor> densityBC,
@@ -926,6 +1047,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            py::arg("p_tol"), py::arg("jacobi_iter"), py::arg("workspace"), py::arg("net") = py::none(), py::arg("precision_mode") = "fp32",
            py::arg("normalize_threshold") = 1e-5, py::arg("method") = "auto", NoGil());
   m.def("device_name", []() { const char* n = fnx_device_name(); return std::string(n ? n : ""); });
+  m.def("scalenet_pack_t", &scalenet_pack_t, py::arg("blob"), NoGil());
+  m.def("multiscale_tape_layout", &multiscale_tape_layout, py::arg("B"), py::arg("H"), py::arg("W"));
+  m.def("multiscale_forward_train", &multiscale_forward_train, py::arg("packed"), py::arg("x"), py::arg("precision_mode") = "fp32", NoGil());
+  m.def("multiscale_backward", &multiscale_backward, py::arg("packed_t"), py::arg("grad_p"), py::arg("tape"),
+        py::arg("precision_mode") = "fp32", NoGil());
+  m.def("multiscale_backward_plain", &multiscale_backward_plain, py::arg("packed_t"), py::arg("grad_p"), py::arg("tape"),
+        py::arg("precision_mode") = "fp32", NoGil());
+  m.def("fluidnet_forward_train", &fluidnet_forward_train, py::arg("packed"), py::arg("input"), py::arg("normalize_threshold"),
+        py::arg("precision_mode") = "fp32", NoGil());
+  m.def("fluidnet_backward", &fluidnet_backward, py::arg("packed_t"), py::arg("flags"), py::arg("scale"), py::arg("grad_p"),
+        py::arg("grad_U"), py::arg("tape"), py::arg("precision_mode") = "fp32", NoGil());
   m.def("abi_version", &fnx_abi_version);
   m.def("profile_enable", [](bool on, bool runs) { fnx_profile_enable(on ? (runs ? 2 : 1) : 0); }, py::arg("on"), py::arg("runs") = false);
   m.def("roctx_enable", [](bool on) { check_status(fnx_roctx_enable(on ? 1 : 0)); });

@@ -1306,6 +1306,42 @@ bool launch_conv_wino(const ConvArgs& a, bool is3d, const float* w3, hipStream_t
   return true;
 }
 
+// A Family::MFMA layer (3x3(x3), Cin % 16 == 0, Cout % 32 == 0) by the mode rule: the bf16 pieces, F(4x4), F(2x2) or the implicit GEMM.
+// a.w / a.bias: the tap image [taps][Cin][Cout] and the bias; wbf, wino4 (wide layers) and wino3: the other images of the same weights.
+// false: nothing launched (an activation beyond the MFMA kernels' 32-bit ranges).  Also runs the input-gradient convolutions of the
+// training backward on transposed images (conv_mfma_images).
+bool launch_conv_mfma_family(const ConvArgs& a, bool is3d, int mode, bool wide, const float* wbf, const float* wino4, const float* wino3,
+                             hipStream_t s) {
+  const int B = a.B, D = a.D, H = a.H, W = a.W;
+  const int taps = is3d ? 27 : 9;
+  if ((mode == FNX_PRECISION_BF16X6 || mode == FNX_PRECISION_BF16X3) && wide) {
+    ProfScope ps(FNX_PROF_CONV_BF16, s);
+    const int nprod = mode == FNX_PRECISION_BF16X3 ? 3 : 6;
+    if (launch_conv_wbf(a, is3d, (const unsigned*)wbf, s, nprod)) {
+      // six (three) bf16 MFMA products per Winograd-domain multiply (16 per 2x2 outputs and z tap)
+      prof_add_work(FNX_PROF_CONV_BF16, (double)B * D * H * W * 2.0 * a.cin * a.cout * 4.0 * (is3d ? 3 : 1) * (double)nprod);
+      return true;
+    }
+  }
+  // (the MFMA kernels address a stage of 8 channel volumes through one 32-bit buffer range: 2^27 cells per sample at
+  // most; beyond that -- 137 GB per 128-channel activation -- the direct kernel still works)
+  if ((size_t)MF_CHUNK * D * H * W * 4 >= 0xf0000000ull) return false;
+  ProfScope ps(FNX_PROF_CONV_MFMA, s);
+  const double px = (double)B * D * H * W, mac = 2.0 * a.cin * a.cout;
+  // F(4x4): the default (256^3 CNN step 92.2 -> 81.0 ms; 1024^2 2.29 -> 2.14 ms: replayed graphs, alternating runs on one box)
+  if (mode == FNX_PRECISION_FP32 && wide && launch_conv_wino4(a, wino4, is3d, s)) {
+    prof_add_work(FNX_PROF_CONV_MFMA, px * mac * 2.25 * (is3d ? 3 : 1));  // 36 multiplies per 4x4 outputs (per z tap)
+    return true;
+  }
+  if (mode != FNX_PRECISION_FP32_DIRECT && launch_conv_wino(a, is3d, wino3, s)) {
+    prof_add_work(FNX_PROF_CONV_MFMA, px * mac * 4.0 * (is3d ? 3 : 1));   // 16 multiplies per 2x2 outputs (per z tap)
+    return true;
+  }
+  launch_conv_mfma(a, is3d, s);
+  prof_add_work(FNX_PROF_CONV_MFMA, px * mac * taps);
+  return true;
+}
+
 // Layer l of the net from x into y.  mode: FNX_PRECISION_* as net_mode leaves it (FP32_DIRECT: no Winograd, every layer a direct sum over
 // its taps; BF16X6 / BF16X3: conv3_wbf_kernel where it applies).  A PAIR layer also applies layer l + 1 (y then has one channel).
 void launch_conv(int l, bool is3d, int mode, const float* packed, const float* x, float* y, int B, int D, int H, int W, hipStream_t s) {
@@ -1315,34 +1351,9 @@ void launch_conv(int l, bool is3d, int mode, const float* packed, const float* x
   ConvArgs a{x, y, packed + P.taps, packed + P.bias, B, L.cin, L.cout, D, H, W, L.relu, L.cout / co_tile(L.cout),
              tail ? packed + tail->taps : nullptr, tail ? packed + tail->bias : nullptr};
   switch (P.fam) {
-    case Family::MFMA: {
-      if ((mode == FNX_PRECISION_BF16X6 || mode == FNX_PRECISION_BF16X3) && P.wide) {
-        ProfScope ps(FNX_PROF_CONV_BF16, s);
-        const int nprod = mode == FNX_PRECISION_BF16X3 ? 3 : 6;
-        if (launch_conv_wbf(a, is3d, (const unsigned*)(packed + P.wbf), s, nprod)) {
-          // six (three) bf16 MFMA products per Winograd-domain multiply (16 per 2x2 outputs and z tap)
-          prof_add_work(FNX_PROF_CONV_BF16, (double)B * D * H * W * 2.0 * L.cin * L.cout * 4.0 * (is3d ? 3 : 1) * (double)nprod);
-          return;
-        }
-      }
-      // (the MFMA kernels address a stage of 8 channel volumes through one 32-bit buffer range: 2^27 cells per sample at
-      // most; beyond that -- 137 GB per 128-channel activation -- the direct kernel still works)
-      if ((size_t)MF_CHUNK * D * H * W * 4 >= 0xf0000000ull) break;
-      ProfScope ps(FNX_PROF_CONV_MFMA, s);
-      const double px = (double)B * D * H * W, mac = 2.0 * L.cin * L.cout;
-      // F(4x4): the default (256^3 CNN step 92.2 -> 81.0 ms; 1024^2 2.29 -> 2.14 ms: replayed graphs, alternating runs on one box)
-      if (mode == FNX_PRECISION_FP32 && P.wide && launch_conv_wino4(a, packed + P.wino4, is3d, s)) {
-        prof_add_work(FNX_PROF_CONV_MFMA, px * mac * 2.25 * (is3d ? 3 : 1));  // 36 multiplies per 4x4 outputs (per z tap)
-        return;
-      }
-      if (mode != FNX_PRECISION_FP32_DIRECT && launch_conv_wino(a, is3d, packed + P.wino3, s)) {
-        prof_add_work(FNX_PROF_CONV_MFMA, px * mac * 4.0 * (is3d ? 3 : 1));   // 16 multiplies per 2x2 outputs (per z tap)
-        return;
-      }
-      launch_conv_mfma(a, is3d, s);
-      prof_add_work(FNX_PROF_CONV_MFMA, px * mac * layer_taps(L, is3d));
-      return;
-    }
+    case Family::MFMA:
+      if (launch_conv_mfma_family(a, is3d, mode, P.wide, packed + P.wbf, packed + P.wino4, packed + P.wino3, s)) return;
+      break;
     case Family::PAIR:
     case Family::KPACK: {
       ProfScope ps(FNX_PROF_CONV_MFMA16, s);
@@ -1360,18 +1371,6 @@ void launch_conv(int l, bool is3d, int mode, const float* packed, const float* x
   }
   ProfScope ps(FNX_PROF_CONV_DIRECT, s);
   launch_conv_direct(a, is3d, s);
-}
-
-// torch upsample_{bi,tri}linear(align_corners=False): src = scale*(dst+0.5)-0.5, clamped at 0
-__device__ __forceinline__ void src_index(int dst, int in, int out, int& i0, int& i1, float& l0, float& l1) {
-  const float scale = (float)in / (float)out;
-  float sidx = scale * ((float)dst + 0.5f) - 0.5f;
-  if (sidx < 0.f) sidx = 0.f;
-  i0 = (int)sidx;
-  if (i0 > in - 1) i0 = in - 1;
-  i1 = i0 + (i0 < in - 1 ? 1 : 0);
-  l1 = sidx - (float)i0;
-  l0 = 1.f - l1;
 }
 
 // x (B,C,Di,Hi,Wi) -> channels [c_off, c_off+C) of y (B,Ctot,Do,Ho,Wo)
@@ -1442,6 +1441,41 @@ inline Sizes sizes(const GridDims& g, bool is3d) {
 }
 
 }  // namespace
+
+// ---- what the training unit (fnx_cnn_train.hip) uses of the launchers above ----
+void conv_layer(int l, int mode, const float* packed, const float* x, float* y, int B, int H, int W, hipStream_t s) {
+  launch_conv(l, false, mode, packed, x, y, B, 1, H, W, s);
+}
+void packed_offsets(int l, size_t* taps, size_t* bias) { *taps = plan(false)[l].taps; *bias = plan(false)[l].bias; }
+void resize2d(const float* x0, int C0, int H0, int W0, const float* x1, int C1, int H1, int W1, float* y, int B, int Ho, int Wo,
+              hipStream_t s) {
+  launch_resize2(RSrc{x0, C0, 1, H0, W0, ZWin{1, 0, 1, 0}}, RSrc{x1, C1, 1, H1, W1, ZWin{1, 0, 1, 0}}, y, B, 1, Ho, Wo, s);
+}
+MfmaImages mfma_images(int cin, int cout, size_t off) {       // make_plan's Family::MFMA case, 2D
+  MfmaImages im{};
+  const size_t nw = (size_t)9 * cin * cout, nwino = (size_t)16 * cin * cout;
+  im.wide = cout % 64 == 0;
+  im.taps = off; im.wino2 = off + nw; im.wino3 = im.wino2 + nwino;
+  off = im.wino3 + nwino;
+  if (im.wide) { im.wbf = off; im.wino4 = im.wbf + nwino * 3 / 2; off = im.wino4 + nw; }
+  im.bias = off;
+  im.end = (off + cout + 63) & ~(size_t)63;
+  return im;
+}
+void pack_mfma_images(const float* w, const float* bias, int cin, int cout, float* base, const MfmaImages& im, hipStream_t s) {
+  pack_layer_mfma_kernel<<<64, 256, 0, s>>>(w, bias, base + im.taps, base + im.bias, cin, cout, 9);
+  pack_layer_wino_kernel<<<64, 256, 0, s>>>(w, base + im.wino2, cin, cout, 1);
+  repack_wino3_kernel<<<64, 256, 0, s>>>(base + im.wino2, base + im.wino3, cin, cout, 1, wino3_rw(cout));
+  if (im.wide) {
+    pack_wbf_kernel<<<256, 256, 0, s>>>(base + im.wino2, (unsigned*)(base + im.wbf), cin, cout, 1);
+    pack_layer_wino4g_kernel<<<64, 256, 0, s>>>(w, base + im.wino4, cin, cout, 1);
+  }
+}
+bool conv_mfma_images(const MfmaImages& im, const float* base, int cin, int cout, int relu, int mode, const float* x, float* y, int B,
+                      int H, int W, hipStream_t s) {
+  const ConvArgs a{x, y, base + im.taps, base + im.bias, B, cin, cout, 1, H, W, relu, cout / co_tile(cout), nullptr, nullptr};
+  return launch_conv_mfma_family(a, false, mode, im.wide, base + im.wbf, base + im.wino4, base + im.wino3, s);
+}
 
 size_t scalenet_weight_floats(bool is3d) {
   size_t n = 0;

@@ -1,0 +1,196 @@
+"""Training of the 2D pressure net on the native backend (reference pytorch/fluid_net_train.py:270-285, 356-375).
+
+`FluidNetTrain(mconf, dropout=False)` is a torch.nn.Module with the reference FluidNet's parameter names and shapes
+(`multiScale.convN_4.encode.0.weight` ...), so state_dict() / load_state_dict() exchange checkpoints with `FluidNet` and with the
+reference, and torch.optim.* / zero_grad() work on it.  forward(input_) returns (p, U) attached to ONE autograd function whose
+backward is the native backward pass (fnx_fluidnet_backward); `net.multiScale(x)` is differentiable in the same way.  Under
+torch.no_grad() or .eval() both run the inference launches.  Gradients come from the kernels: torch only carries the tensors.
+
+Scope: the 2D ScaleNet configuration `FluidNet` accepts, precision modes fp32 / fp32_f4 / fp32_f2 / fp32_direct, gradients with respect to
+the parameters.  3D, the bf16 modes, dropout and a gradient with respect to input_ raise.
+"""
+from collections import OrderedDict
+
+import torch
+
+from ._ext import ext
+from .model import _UNUSED_PREFIXES
+from .weights import make_scalenet_weights, scalenet_layers
+
+_TRAIN_MODES = ("fp32", "fp32_f4", "fp32_f2", "fp32_direct")
+
+
+def _no_input_grad(t, what):
+    if t.requires_grad:
+        raise RuntimeError(f"fluidnet_cxx_amd.FluidNetTrain: {what}.requires_grad is set, but the native backward pass gives gradients "
+                           "with respect to the parameters only (the training data is a leaf without grad in the reference too)")
+
+
+def _split(blob, shapes):
+    """the gradient blob (the layout of model.blob_from_state_dict) as one view per parameter"""
+    grads, off = [], 0
+    for shp in shapes:
+        grads.append(blob[off:off + shp.numel()].view(shp))
+        off += shp.numel()
+    return grads
+
+
+class _MultiScaleFn(torch.autograd.Function):
+    """x (B,2,H,W) or (B,2,1,H,W) -> p; the parameters ride along so that autograd routes their gradients"""
+
+    @staticmethod
+    def forward(ctx, x, owner, *params):
+        packed, ctx.packed_t = owner._packed(x.device)
+        p, ctx.tape = ext.multiscale_forward_train(packed, x, owner.precision_mode)
+        ctx.mode, ctx.shapes = owner.precision_mode, [q.shape for q in params]
+        return p
+
+    @staticmethod
+    def backward(ctx, gp):
+        blob = ext.multiscale_backward(ctx.packed_t, gp.contiguous(), ctx.tape, ctx.mode)
+        return (None, None) + tuple(_split(blob, ctx.shapes))
+
+
+class _FluidNetFn(torch.autograd.Function):
+    """input_ (B,5,1,H,W) -> (p, U)   (model.py:76-227 around the taped net)"""
+
+    @staticmethod
+    def forward(ctx, input_, owner, *params):
+        packed, ctx.packed_t = owner._packed(input_.device)
+        p, U, ctx.tape, ctx.scale, ctx.flags = ext.fluidnet_forward_train(packed, input_, owner.threshold, owner.precision_mode)
+        ctx.mode, ctx.shapes = owner.precision_mode, [q.shape for q in params]
+        return p, U
+
+    @staticmethod
+    def backward(ctx, gp, gU):
+        # a loss that leaves out one of the two outputs delivers None for it
+        gp = ctx.flags.new_zeros(ctx.flags.shape) if gp is None else gp.contiguous()
+        gU = ctx.flags.new_zeros((ctx.flags.size(0), 2) + tuple(ctx.flags.shape[2:])) if gU is None else gU.contiguous()
+        blob = ext.fluidnet_backward(ctx.packed_t, ctx.flags, ctx.scale, gp, gU, ctx.tape, ctx.mode)
+        return (None, None) + tuple(_split(blob, ctx.shapes))
+
+
+class _Conv(torch.nn.Module):
+    """the parameters of one convolution, under the names torch.nn.Conv2d gives them"""
+
+    def __init__(self, weight, bias):
+        super().__init__()
+        self.weight = torch.nn.Parameter(torch.from_numpy(weight).clone())
+        self.bias = torch.nn.Parameter(torch.from_numpy(bias).clone())
+
+
+class _Holder(torch.nn.Module):
+    pass
+
+
+class _MultiScaleTrain(torch.nn.Module):
+    """x (B,2,H,W) -> p (B,1,H,W)   (multi_scale_net.py:118-127), differentiable with respect to the parameters"""
+
+    def __init__(self, precision_mode):
+        super().__init__()
+        self.precision_mode = precision_mode
+        w = make_scalenet_weights(0, ndim=2)
+        for L in scalenet_layers(2, 2):
+            parts = L["name"].split(".")[1:]             # convN_4, encode, 0  |  final
+            mod = self
+            for part in parts[:-1]:
+                if not hasattr(mod, part):
+                    mod.add_module(part, _Holder())
+                mod = getattr(mod, part)
+            mod.add_module(parts[-1], _Conv(w[L["name"] + ".weight"], w[L["name"] + ".bias"]))
+        self._key = None
+        self._images = None
+
+    def _ordered(self):
+        """the 34 parameters in the blob's order (scalenet_layers(): weight, bias per convolution)"""
+        named = dict(self.named_parameters())
+        return [named[L["name"].split(".", 1)[1] + sfx] for L in scalenet_layers(2, 2) for sfx in (".weight", ".bias")]
+
+    def _packed(self, device):
+        """(packed, packed_t) for the current parameter values on `device`: repacked on the device whenever a parameter was written
+        (an optimiser step, load_state_dict, .to())"""
+        params = self._ordered()
+        key = (str(device),) + tuple((p.data_ptr(), p._version) for p in params)
+        if key != self._key:
+            blob = torch.cat([p.detach().reshape(-1) for p in params]).to(device=device, dtype=torch.float32).contiguous()
+            self._images = (ext.scalenet_pack(blob, False), ext.scalenet_pack_t(blob))
+            self._key = key
+        return self._images
+
+    def forward(self, x):
+        x = x.contiguous()
+        if not (self.training and torch.is_grad_enabled()):
+            return ext.multiscale_forward(self._packed(x.device)[0], x, self.precision_mode, [])
+        _no_input_grad(x, "x")
+        return _MultiScaleFn.apply(x, self, *self._ordered())
+
+
+class FluidNetTrain(torch.nn.Module):
+    """input_ (B,5,1,H,W) = [p, U, flags, density] -> (p, U), differentiable with respect to the net's parameters.
+
+    What replaces `lib.FluidNet` in the reference's fluid_net_train.py; constructed, loaded and called the same way."""
+
+    def __init__(self, mconf, dropout=False):
+        super().__init__()
+        if dropout:
+            raise ValueError("fluidnet_cxx_amd.FluidNetTrain: dropout=True is not supported (the reference's drivers build the ScaleNet "
+                             "path with dropout=False)")
+        if mconf.get("model", "ScaleNet") != "ScaleNet":
+            raise ValueError("fluidnet_cxx_amd.FluidNetTrain: only the ScaleNet variant is accelerated")
+        ic = mconf.get("inputChannels", {"div": True, "pDiv": False, "UDiv": False})
+        if not (ic.get("div", False) and not ic.get("pDiv", False) and not ic.get("UDiv", False)):
+            raise ValueError("fluidnet_cxx_amd.FluidNetTrain: inputChannels must be {div} (convModel_mconf.pth)")
+        if not (mconf.get("normalizeInput", True) and mconf.get("normalizeInputChan", "UDiv") == "UDiv"):
+            raise ValueError("fluidnet_cxx_amd.FluidNetTrain: normalizeInput on 'UDiv' is the supported configuration")
+        if mconf.get("is3D", False):
+            raise ValueError("fluidnet_cxx_amd.FluidNetTrain: training is 2D only (is3D=True)")
+        self.precision_mode = str(mconf.get("precisionMode", "fp32"))
+        if self.precision_mode not in _TRAIN_MODES:
+            raise ValueError(f"fluidnet_cxx_amd.FluidNetTrain: training runs in fp32 arithmetic only (precisionMode one of {_TRAIN_MODES}), "
+                             f"not '{self.precision_mode}'")
+        self.mconf = mconf
+        self.is3D = False
+        self.inDims = mconf.get("inputDim", 2)
+        self.threshold = float(mconf.get("normalizeInputThreshold", 1e-5))
+        self.multiScale = _MultiScaleTrain(self.precision_mode)
+        self._extra = OrderedDict()          # the reference's unused parameters (conv1.* ...), kept for state_dict()
+
+    def _packed(self, device):
+        return self.multiScale._packed(device)
+
+    @property
+    def packed(self):
+        return self._packed(next(self.parameters()).device)[0]
+
+    def packed_for(self, device):
+        """The packed weight blob on `device` (what fnx_simulate_step takes as FnxState.net): simulate(..., net, 'convnet') and the
+        z-slab driver ask a net for it, as they ask FluidNet."""
+        return self._packed(device)[0]
+
+    def state_dict(self, *args, destination=None, prefix="", keep_vars=False):
+        if args:                                  # the deprecated positional form (destination, prefix, keep_vars)
+            destination = args[0]
+            prefix = args[1] if len(args) > 1 else prefix
+            keep_vars = args[2] if len(args) > 2 else keep_vars
+        # (a parent module passes its own `destination` and ignores the return value: the kept keys go into that dict)
+        sd = super().state_dict(destination=destination, prefix=prefix, keep_vars=keep_vars)
+        for k, v in self._extra.items():
+            sd[prefix + k] = v
+        return sd
+
+    def load_state_dict(self, state_dict, strict=True, **kwargs):
+        """Like FluidNet.load_state_dict: every multiScale.* parameter must be present with the right shape; the reference FluidNet's
+        parameters that the ScaleNet forward never reads are accepted and kept."""
+        extra = OrderedDict((k, v) for k, v in state_dict.items() if k.startswith(_UNUSED_PREFIXES))
+        own = OrderedDict((k, torch.as_tensor(v)) for k, v in state_dict.items() if not k.startswith(_UNUSED_PREFIXES))
+        res = super().load_state_dict(own, strict=strict, **kwargs)
+        self._extra = extra
+        return res
+
+    def forward(self, input_):
+        input_ = input_.contiguous()
+        if not (self.training and torch.is_grad_enabled()):
+            p, U = ext.fluidnet_forward(self._packed(input_.device)[0], input_, self.threshold, self.precision_mode)
+            return p, U
+        _no_input_grad(input_, "input_")
+        return _FluidNetFn.apply(input_, self, *self.multiScale._ordered())

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define FNX_ABI_VERSION 20
+#define FNX_ABI_VERSION 21
 
 enum {
   FNX_OK = 0,
@@ -587,6 +587,56 @@ int fnx_multiscale_forward_crop(const FnxGrid* g, const void* packed, const floa
 /* input: (B,5|6,D,H,W) = [p, U, flags, density] -> p_out (B,1,..), U_out (B,2|3,..) */
 int fnx_fluidnet_forward(const FnxGrid* g, const void* packed, const float* input, float normalize_threshold,
                          float* p_out, float* U_out, int precision_mode, void* ws, size_t ws_bytes, void* stream);
+
+/* Training of the 2D net (ABI 21): gradients of a scalar loss of p (or of FluidNet.forward's (p, U)) with respect to the 34 parameter
+ * tensors, fp32 arithmetic only.  Every entry point checks, before it touches the device: a 2D grid (is3D = 0, D = 1) and a precision mode
+ * among FNX_PRECISION_FP32, _FP32_F4, _FP32_F2 and _FP32_DIRECT (the bf16 modes and 3D are FNX_EINVAL with their own fnx_last_error text).
+ * No gradient with respect to the input, no dropout, no compute window.  No atomics: two calls on the same inputs give the same bits.
+ *
+ * The training forward writes every layer's input into one caller-provided buffer, the tape: the three concatenated tower inputs
+ * ("xq" (B,2,H/4,W/4), "in2" (B,3,H/2,W/2), "in1" (B,3,H,W)) and the output "y<l>" of each of the first 16 convolutions AFTER its ReLU,
+ * including the 8-channel "y15" that the inference forward's fused tail never writes -- about 420 floats per full-resolution pixel.
+ * The derivative of a ReLU layer is (saved output > 0), torch's rule.  fnx_multiscale_tape_layout returns the tape's size in floats
+ * (0 on error) and, if `entries` is not NULL, fills fnx_multiscale_tape_entries() of them in tape order; the layout is a function
+ * of (B, H, W) alone.  p of the training forward is bit-identical to fnx_multiscale_forward's in the same mode. */
+typedef struct FnxTapeEntry {
+  char name[8];
+  size_t offset;     /* floats from the start of the tape; the tensor is a contiguous (B,C,H,W) */
+  int C, H, W;
+} FnxTapeEntry;
+int fnx_multiscale_tape_entries(void);
+size_t fnx_multiscale_tape_layout(const FnxGrid* g, FnxTapeEntry* entries);
+/* packed_t: what the backward reads of the weights -- the blob itself and, for the 3x3 layers between 32, 64 and 128 channels, the
+ * images of the transposed, tap-flipped weight with zero bias (ten layers), so that their input gradients run through the forward's own launchers
+ * by the same mode rule.  Repack it with fnx_scalenet_pack whenever the weights change; both run on the device. */
+size_t fnx_scalenet_packed_t_bytes(void);
+int fnx_scalenet_pack_t(const float* weights_blob, void* packed_t, void* stream);
+size_t fnx_multiscale_backward_ws_bytes(const FnxGrid* g);
+/* x (B,2,1,H,W) -> p (B,1,1,H,W) and the tape (fnx_multiscale_tape_layout floats).  No workspace. */
+int fnx_multiscale_forward_train(const FnxGrid* g, const void* packed, const float* x, float* p, float* tape, int precision_mode,
+                                 void* stream);
+/* grad_p (B,1,1,H,W) and the tape of the forward -> grad_blob (fnx_scalenet_weight_floats(0) floats) in the layout of weights_blob:
+ * per conv the weight gradient (Cout,Cin,kh,kw) then the bias gradient.  grad_p and the tape are not modified.  The weight gradients of the
+ * 3x3 layers between 32, 64 and 128 channels (95 % of the FLOPs) run on the matrix cores in exact fp32 (v_mfma_f32_32x32x2_f32, a GEMM
+ * over K = B H W split across workgroups, partials added in a fixed order).  precision_mode picks the launcher of the input-gradient
+ * convolutions. */
+int fnx_multiscale_backward(const FnxGrid* g, const void* packed_t, const float* grad_p, const float* tape, float* grad_blob,
+                            int precision_mode, void* ws, size_t ws_bytes, void* stream);
+/* The same call with the plain weight-gradient kernel of the thin layers for every layer: a cross-check of the MFMA kernel for tests and
+ * A/B timing (7x slower), not something a training loop calls. */
+int fnx_multiscale_backward_plain(const FnxGrid* g, const void* packed_t, const float* grad_p, const float* tape, float* grad_blob,
+                                  int precision_mode, void* ws, size_t ws_bytes, void* stream);
+/* FluidNet.forward for training and its backward (one workspace size for both).  The forward is fnx_fluidnet_forward with the taped
+ * net; it also returns the flags channel as a contiguous (B,1,1,H,W) tensor and the per-sample scale s (B floats), which the backward
+ * takes back.  Behind the net the forward is velocityUpdate(p, UDiv / s), p s, UDiv s, setWallBcs (model.py:213-226), so the
+ * gradient that reaches the net's output is   g_net = s grad_p + velocity_update_backward_p(s setWallBcs(grad_U)). */
+size_t fnx_fluidnet_train_ws_bytes(const FnxGrid* g);
+int fnx_fluidnet_forward_train(const FnxGrid* g, const void* packed, const float* input, float normalize_threshold, float* p_out,
+                               float* U_out, float* flags_out, float* scale_out, float* tape, int precision_mode, void* ws, size_t ws_bytes,
+                               void* stream);
+int fnx_fluidnet_backward(const FnxGrid* g, const void* packed_t, const float* flags, const float* scale, const float* grad_p,
+                          const float* grad_U, const float* tape, float* grad_blob, int precision_mode, void* ws, size_t ws_bytes,
+                          void* stream);
 
 /* Optional timing of the dominant kernels with HIP events on the launch stream (used by bench.py for the roofline
  * figures).  While enabled, every launch of the tagged kernel class is bracketed by an event pair (up to 16384 pairs,
