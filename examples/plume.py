@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The reference's `pytorch/plume.py` main loop on this backend -- what a driver looks like after the switch.
 
-    python examples/plume.py [--res 128] [--iters 200] [--out-iter 50] [--method jacobi|pcg] [--folder out] [--restart]
+    python examples/plume.py [--res 128] [--iters 200] [--out-iter 50] [--method jacobi|pcg] [--vorticity AMP] [--folder out] [--restart]
 
 Same structure as the reference driver (plume.py:66-178 setup, :231-424 loop): build the batch, `createPlumeBCs`, optional
 restart from `<folder>/restart.pth`, echo the configuration as YAML, then `simulate()` per iteration and, every `out-iter`
@@ -23,6 +23,8 @@ def main(argv=None):
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--out-iter", type=int, default=50)
     ap.add_argument("--method", default="jacobi", choices=["jacobi", "pcg"])      # 'convnet' needs a trained FluidNet state dict
+    ap.add_argument("--vorticity", type=float, default=0.0, metavar="AMP",
+                    help="vorticity confinement amplitude (mconf['vorticityConfinementAmp'], no reference key; 0 = off)")
     ap.add_argument("--folder", default="plume_out")
     ap.add_argument("--restart", action="store_true")
     a = ap.parse_args(argv)
@@ -33,6 +35,8 @@ def main(argv=None):
                    simMethod=a.method, resX=a.res, resY=a.res, maxIter=a.iters, outputFolder=a.folder)
     if a.method == "pcg":                                 # the converged solve (fluid.solveLinearSystemPCG)
         simConf.update(pcgTol=1e-5, pcgIter=50)
+    if a.vorticity > 0:                                   # puts back the small-scale rotation the advection smooths away
+        simConf.update(vorticityConfinementAmp=a.vorticity)
     os.makedirs(a.folder, exist_ok=True)
     resX = resY = a.res
     # plume.py:131-163

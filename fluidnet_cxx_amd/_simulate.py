@@ -27,6 +27,8 @@ automatic mode records it only after a call has succeeded).
 `static_flags=None` (the default) with no `workspace` is the automatic mode above; with a caller's workspace it means 0.
 sim_method 'pcg' (no reference counterpart) projects with the converged solve of fluid.solveLinearSystemPCG: mconf['pcgTol']
 (default 1e-5) and mconf['pcgIter'] (default 50); the wall BCs and periodic patches as for 'jacobi'.
+mconf['vorticityConfinementAmp'] > 0 (no reference key either) adds fluid.addVorticityConfinement with that amplitude after
+addGravity and before setWallBcs, for every method; whole grids only (a compute window or z-slab `geom` raises).
 `geom` (an `ext.Geom`, 3D only) selects the reference-quirk mode / a z-slab view for this call; it is per call, the
 extension keeps no state.
 """
@@ -143,6 +145,7 @@ def simulate(mconf, batch_dict, net, sim_method, output_div=False, fused=True, w
     gravityScale = mconf.get("gravityScale", 0)
     viscosity = mconf.get("viscosity", 0)
     assert viscosity >= 0, "Viscosity must be positive"
+    vorticityAmp = mconf.get("vorticityConfinementAmp", 0)      # no reference key: fluid.addVorticityConfinement after addGravity
     p, U, flags = batch_dict["p"], batch_dict["U"], batch_dict["flags"]
     has_density = "density" in batch_dict
 
@@ -181,7 +184,8 @@ def simulate(mconf, batch_dict, net, sim_method, output_div=False, fused=True, w
                            float(viscosity), float(gravityScale) if gravityScale > 0 else 0.0,
                            bool(mconf.get("correctScalar", False)) and has_density, periodic,
                            batch_dict.get("flags_stick") if sim_method == "convnet" else None,
-                           pcg_tol=float(mconf.get("pcgTol", 1e-5)), pcg_iter=int(mconf.get("pcgIter", 50)))
+                           pcg_tol=float(mconf.get("pcgTol", 1e-5)), pcg_iter=int(mconf.get("pcgIter", 50)),
+                           vorticity_confinement=float(vorticityAmp) if vorticityAmp > 0 else 0.0)
         if auto is not None and sim_method == "pcg":
             auto.built_hierarchy(flags)
         if not has_density:
@@ -214,6 +218,8 @@ def simulate(mconf, batch_dict, net, sim_method, output_div=False, fused=True, w
         gvec, _ = _gravity(mconf, 1.0)
         gravity = (torch.tensor(gvec, dtype=torch.float32) * (-gravityScale)).tolist()
         U = fluid.addGravity(U, flags, gravity, dt, geom=geom)
+    if vorticityAmp > 0:                                        # a body force like the two above; the projection removes its divergence
+        U = fluid.addVorticityConfinement(U, flags, vorticityAmp, geom=geom)
     if output_div:
         return
     periodic = "periodic-x" in mconf and "periodic-y" in mconf

@@ -24,6 +24,7 @@ HIP_UNITS = {
     "fnx_jacobi.hip": ["-ffp-contract=off"],
     "fnx_pcg.hip": [],
     "fnx_step.hip": ["-ffp-contract=off"],
+    "fnx_vorticity.hip": ["-ffp-contract=off", "-Rpass-analysis=kernel-resource-usage"],
     "fnx_api.hip": ["-ffp-contract=off"],
     # (resource-usage remarks: build_lib checks the kernels of SCRATCH_FREE)
     "fnx_cnn.hip": ["-Rpass-analysis=kernel-resource-usage"],
@@ -41,6 +42,9 @@ SCRATCH_FREE = {
                         "advect3d_bwd_vel_tile_kernel"],
                        "fnx_advect_march.h: the 3D advection marches run at 2-3 waves per SIMD with every VGPR in use; a reload from "
                        "scratch is an s_waitcnt vmcnt(0) that also waits for the plane in flight and the stores"),
+    "fnx_vorticity.hip": (["vorticity_confinement_kernel"],
+                          "its z-march keeps three planes of c and n, two of the curl and three of F_z in registers between the barriers; "
+                          "a spill puts a scratch round trip into every step of the march"),
 }
 # -fno-slp-vectorize: hipcc otherwise packs adjacent scalar f32 adds into v_pk_add_f32 + v_pk_mov shuffles, measured
 # 1.6x slower per op than plain VALU on gfx950 (tools/ubench/dpp_bench.hip).

@@ -256,6 +256,32 @@ void add_gravity_(Tensor U, Tensor flags, std::vector<double> gravity, double dt
   wrote(U);
 }
 
+// vorticity confinement (fnx_add_vorticity_confinement), in place on U like addGravity: the operator itself is out of place
+void add_vorticity_confinement_(Tensor U, Tensor flags, double strength, const Geom* geom) {
+  check_field(U, "U");
+  FnxGrid g = grid_of(flags, U.size(1) == 3, geom);
+  check_vel(U, g, "U");
+  TORCH_CHECK(g.k_begin == 0 && g.k_end == 0 && g.z_offset == 0 && g.D_global == 0,
+              "addVorticityConfinement: no compute window or z-slab view (whole grids only)");
+  c10::hip::HIPGuard guard(flags.get_device());
+  Tensor old = U.clone();
+  check_status(fnx_add_vorticity_confinement(&g, old.data_ptr<float>(), U.data_ptr<float>(), flags.data_ptr<float>(), (float)strength,
+                                             cur_stream(U)));
+  wrote(U);
+}
+
+// the same out of place, as the C ABI has it: U is left alone, the confined field is returned
+Tensor add_vorticity_confinement(Tensor U, Tensor flags, double strength, const Geom* geom) {
+  check_field(U, "U");
+  FnxGrid g = grid_of(flags, U.size(1) == 3, geom);
+  check_vel(U, g, "U");
+  c10::hip::HIPGuard guard(flags.get_device());
+  Tensor out = at::empty_like(U);
+  check_status(fnx_add_vorticity_confinement(&g, U.data_ptr<float>(), out.data_ptr<float>(), flags.data_ptr<float>(), (float)strength,
+                                             cur_stream(U)));
+  return out;
+}
+
 // correctScalar (cpp/advection.py:9-12), in place on src
 void correct_scalar_(double dt, Tensor src, Tensor div, Tensor flags) {
   check_field(src, "src"); check_field(flags, "flags");
@@ -578,7 +604,7 @@ void simulate_step_(Tensor p, Tensor U, Tensor flags, c10::optional<Tensor> dens
                     const std::string method, double normalize_threshold, c10::optional<Tensor> workspace,
                     int static_flags, const Geom* geom, const std::string& precision_mode, double viscosity,
                     double gravity_scale, bool correct_scalar, int periodic, c10::optional<Tensor> flags_stick, double pcg_tol,
-                    int pcg_iter) {
+                    int pcg_iter, double vorticity_confinement) {
   check_field(U, "U");
   FnxGrid g = grid_of(flags, U.size(1) == 3, geom);
   check_vel(U, g, "U"); check_scalar(p, g, "p");
@@ -595,6 +621,7 @@ void simulate_step_(Tensor p, Tensor U, Tensor flags, c10::optional<Tensor> dens
   prm.precision_mode = precision_of(precision_mode);
   prm.viscosity = (float)viscosity; prm.gravity_scale = (float)gravity_scale; prm.correct_scalar = correct_scalar ? 1 : 0;
   prm.periodic = periodic;
+  prm.vorticity_confinement = (float)vorticity_confinement;
   auto opt = [&](c10::optional<Tensor>& t, bool vel, const char* name) -> float* {
     if (!t.has_value() || !t->defined()) return nullptr;
     if (vel) check_vel(*t, g, name); else check_scalar(*t, g, name);
@@ -928,6 +955,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("correct_scalar_", &correct_scalar_, py::arg("dt"), py::arg("src"), py::arg("div"), py::arg("flags"), NoGil());
   m.def("add_gravity_", &add_gravity_, py::arg("U"), py::arg("flags"), py::arg("gravity"), py::arg("dt"), GEOM, NoGil());
   m.def("add_viscosity_", &add_viscosity_, NoGil());
+  m.def("add_vorticity_confinement", &add_vorticity_confinement, py::arg("U"), py::arg("flags"), py::arg("strength"), GEOM, NoGil());
+  m.def("add_vorticity_confinement_", &add_vorticity_confinement_, py::arg("U"), py::arg("flags"), py::arg("strength"), GEOM, NoGil());
   m.def("set_wall_bcs_", &set_wall_bcs_, py::arg("U"), py::arg("flags"), GEOM, NoGil());
   m.def("set_wall_bcs_stick_", &set_wall_bcs_stick_, NoGil());
   m.def("set_const_vals_", &set_const_vals_, NoGil());
@@ -951,7 +980,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("normalize_threshold"), py::arg("workspace") = py::none(), py::arg("static_flags") = 0, GEOM,
         py::arg("precision_mode") = "fp32", py::arg("viscosity") = 0.0, py::arg("gravity_scale") = 0.0,
         py::arg("correct_scalar") = false, py::arg("periodic") = 0, py::arg("flags_stick") = py::none(), py::arg("pcg_tol") = 1e-5,
-        py::arg("pcg_iter") = 50, NoGil());
+        py::arg("pcg_iter") = 50, py::arg("vorticity_confinement") = 0.0, NoGil());
   m.def("step_workspace_bytes", &step_workspace_bytes);
   m.def("jacobi_sweeps_", &jacobi_sweeps_, py::arg("flags"), py::arg("div"), py::arg("p"), py::arg("is3D"), py::arg("nsweeps"),
         py::arg("workspace") = py::none(), py::arg("reuse_mask") = false, GEOM, py::arg("from_zero") = false, NoGil());

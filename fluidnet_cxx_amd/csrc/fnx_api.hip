@@ -724,6 +724,20 @@ int fnx_add_viscosity(const FnxGrid* g, float dt, const float* U_in, float* U_ou
   return FNX_OK;
 }
 
+int fnx_add_vorticity_confinement(const FnxGrid* g, const float* U_in, float* U_out, const float* flags, float amp, void* stream) {
+  if (!U_in || !U_out || !flags) return fail(FNX_EINVAL, "add_vorticity_confinement: NULL tensor");
+  if (U_in == U_out) return fail(FNX_EINVAL, "add_vorticity_confinement: U_out must not alias U_in (a cell reads U_in three cells around it)");
+  if (int rc = check_grid(g)) return rc;
+  if (g->k_begin != 0 || g->k_end != 0 || g->z_offset != 0 || g->D_global != 0)
+    return fail(FNX_EINVAL, "add_vorticity_confinement: no compute window or z-slab view (whole grids only)");
+  if (!(amp == amp)) return fail(FNX_EINVAL, "add_vorticity_confinement: the amplitude is NaN");
+  hipStream_t s = (hipStream_t)stream;
+  if (amp == 0.f) HIP_OK(hipMemcpyAsync(U_out, U_in, ncell(g) * 4 * (g->is3D ? 3 : 2), hipMemcpyDeviceToDevice, s));
+  else fnx::launch_vorticity_confinement(dims(g), g->is3D, U_in, flags, U_out, amp, s);
+  HIP_OK(hipGetLastError());
+  return FNX_OK;
+}
+
 int fnx_add_buoyancy(const FnxGrid* g, float* U, const float* flags, const float* density, const float gravity[3],
                      float rho_star, float dt, void* stream) {
   if (int rc = check_grid(g)) return rc;
@@ -870,7 +884,33 @@ int fnx_pre_projection(const FnxGrid* g, const FnxStepParams* prm, const FnxStat
   const bool wall = prm->method != 1;
   const bool periodic = wall && (prm->periodic & 1);
   const bool second_bcs = !(prm->method == 1 && st->flags_stick);
+  const bool confine = prm->vorticity_confinement > 0.f;
+  if (confine && (g->k_begin != 0 || g->k_end != 0 || g->z_offset != 0 || g->D_global != 0))
+    return fail(FNX_EINVAL, "pre_projection: vorticity confinement takes no compute window or z-slab view (single domain only)");
   fnx::ProfScope ps(FNX_PROF_STAGE, (hipStream_t)stream);
+  if (confine) {
+    // The stage cut in two around the confinement, which reads the field three cells around a cell and so cannot join the
+    // radius-1 recompute: (1) setConstVals, addBuoyancy, addGravity: U_adv -> st->U; (2) confinement: st->U -> U_adv;
+    // (3) setWallBcs (+ periodic patches), setConstVals, divergence: U_adv -> st->U.  The density is through with (1) but for
+    // its second setConstVals.
+    hipStream_t s = (hipStream_t)stream;
+    const GridDims d = dims(g);
+    float* U_scr = const_cast<float*>(U_adv);
+    const float* ubc_ = ubc ? st->UBC : nullptr; const float* ubm_ = ubc ? st->UBCInvMask : nullptr;
+    fnx::launch_pre_projection(d, g->is3D, quirks(g), U_adv, rho_adv, st->flags, ubc_, ubm_, rbc ? st->densityBC : nullptr,
+                               rbc ? st->densityBCInvMask : nullptr, st->U, st->density, nullptr, buoy, sx, sy, sz,
+                               prm->operating_density, false, s, st->bc_class, grav ? gv : nullptr, false, 0);
+    fnx::launch_vorticity_confinement(d, g->is3D, st->U, st->flags, U_scr, prm->vorticity_confinement, s);
+    fnx::launch_pre_projection(d, g->is3D, quirks(g), U_scr, nullptr, st->flags, ubc_, ubm_, nullptr, nullptr, st->U, nullptr,
+                               periodic ? nullptr : div, false, 0.f, 0.f, 0.f, 0.f, wall, s, st->bc_class, nullptr, second_bcs,
+                               d.K0 + d.KN, false);
+    if (periodic)
+      fnx::launch_periodic_pre(d, g->is3D, U_scr, ubc_, ubm_, st->U, (prm->periodic & 2) != 0, (prm->periodic & 4) != 0, s, true);
+    if (periodic && div) fnx::launch_divergence(d, g->is3D, st->U, st->flags, div, s);
+    if (has_rho && rbc && second_bcs) fnx::launch_set_const_vals(ncell(g), st->density, st->densityBC, st->densityBCInvMask, s);
+    HIP_OK(hipGetLastError());
+    return FNX_OK;
+  }
   // One fused pass writes the staged fields and the divergence (each cell re-derives the staged component of its +1 neighbours),
   // unless the periodic patches have to go between the stages and the divergence: then staging, patches, a divergence pass.
   const bool split = periodic;
@@ -921,6 +961,8 @@ int fnx_simulate_step(const FnxGrid* g, const FnxStepParams* prm, const FnxState
   if (prm->method == 2 && prm->pcg_iter < 1) return fail(FNX_EINVAL, "At least 1 iteration of the solver is needed (pcg_iter < 1)");
   if (prm->method == 2 && (g->k_begin != 0 || g->k_end != 0 || g->z_offset != 0 || g->D_global != 0))
     return fail(FNX_EINVAL, "simulate_step: the PCG solve takes no compute window or z-slab view (single domain only)");
+  if (prm->vorticity_confinement > 0.f && (g->k_begin != 0 || g->k_end != 0 || g->z_offset != 0 || g->D_global != 0))
+    return fail(FNX_EINVAL, "simulate_step: vorticity confinement takes no compute window or z-slab view (single domain only)");
   if (prm->method == 1 && !st->net) return fail(FNX_EINVAL, "simulate_step: convnet method needs packed weights");
   hipStream_t s = (hipStream_t)stream;
   const size_t n = ncell(g), nc = g->is3D ? 3 : 2;
@@ -938,6 +980,7 @@ int fnx_simulate_step(const FnxGrid* g, const FnxStepParams* prm, const FnxState
   const bool has_rho = st->density != nullptr;
   const bool viscous = prm->viscosity > 0.f;
   if (prm->viscosity < 0.f) return fail(FNX_EINVAL, "Viscosity must be positive");
+  if (prm->vorticity_confinement != prm->vorticity_confinement) return fail(FNX_EINVAL, "simulate_step: vorticity_confinement is NaN");
   if (viscous && g->is3D) return fail(FNX_EINVAL, "simulate_step: viscosity is 2D only (reference viscosity.py:5)");
   const bool stick = prm->method == 1 && st->flags_stick != nullptr;           // simulate.py:129-130, :165-166
   if (stick && g->is3D) return fail(FNX_EINVAL, "simulate_step: flags_stick is 2D only (set_wall_bcs_stick.py:85-86)");

@@ -71,14 +71,15 @@ void launch_pre_projection(const GridDims& g, bool is3d, bool quirks, const floa
                            const float* rhoBCInvMask, float* U, float* rho, float* div, bool buoyancy, float sx,
                            float sy, float sz, float rho_star, bool wall_bcs, hipStream_t s,
                            const unsigned char* cls = nullptr, const float* gravity = nullptr, bool second_bcs = true,
-                           int div_k_end = 0);
+                           int div_k_end = 0, bool first_bcs = true);
+// first_bcs = false leaves out the setConstVals of simulate.py:96 (U_adv is a field that has been through it already);
 // gravity: 3 host floats (gravity * dt) or null; second_bcs = false leaves out the setConstVals of simulate.py:133; 3D with `div`:
 // the divergence of the staged field is written for the planes [g.K0, div_k_end) of the staged range (the staged value of a cell's
 // +1 neighbours is re-derived in the same pass; their advected inputs must be valid)
 // periodic patches of the Jacobi branch (simulate.py:121-128, :157-164); `save`: periodic_save_bytes(g), mode 0 = save the
 // source row / column before the post-projection pass, 1 = write the destinations after it
 void launch_periodic_pre(const GridDims& g, bool is3d, const float* U_adv, const float* UBC, const float* UBCInvMask, float* U,
-                         bool px, bool py, hipStream_t s);
+                         bool px, bool py, hipStream_t s, bool staged = false);   // staged: U_adv is the field ahead of setWallBcs itself
 size_t periodic_save_bytes(const GridDims& g);
 void launch_periodic_post(const GridDims& g, bool is3d, float* U, float* save, const float* UBC, const float* UBCInvMask,
                           bool px, bool py, int mode, hipStream_t s);
@@ -90,6 +91,11 @@ void launch_post_projection(const GridDims& g, bool is3d, const float* p, float*
 // p_scaled = p * s out of it); p_scaled must not alias p (a cell reads p of its -1 neighbours)
 void launch_bc_classify(const GridDims& g, bool is3d, const float* UBC, const float* UBCInvMask, const float* rhoBC,
                         const float* rhoBCInvMask, unsigned char* cls, hipStream_t s);
+
+// vorticity confinement (fnx_vorticity.hip): U_out = U_in + the confinement force of U_in scaled by amp; whole grids only (no
+// compute window, no z-slab view); U_out must not alias U_in
+void launch_vorticity_confinement(const GridDims& g, bool is3d, const float* U_in, const float* flags, float* U_out, float amp,
+                                  hipStream_t s);
 
 // Jacobi (fnx_jacobi.hip)
 // 2D: `nsweeps` sweeps (1..jacobi_max_sweeps_per_launch) from p_in into p_out; from_zero: p_in is all zeros and is not read

@@ -40,11 +40,14 @@ __device__ __forceinline__ bool gravity_applies(float fc, float fm) {
 // The stage sequence of component `a` of one 3D cell: u its advected value, (um, uc) its velocity-BC entry, fc / fm the flags of
 // the cell and of its -1 neighbour along a (the cell's own where that neighbour does not exist), r0 / r1 their densities with
 // the BC entries (rm0, rc0) / (rm1, rc1), kg = k + zoff the cell's global plane, k its local one.
-template <bool QUIRKS, bool WALL>
+// BC1 = false leaves out the first setConstVals (simulate.py:96): the input is a field that has been through it already -- the second
+// launch of a stage cut in two around the vorticity confinement (fnx_pre_projection).  The default instantiations are the kernels
+// of the uncut stage, unchanged.
+template <bool QUIRKS, bool WALL, bool BC1 = true>
 __device__ __forceinline__ float stage_eval3d(int a, float v, bool ubc, float um, float uc, float fc, float fm, bool border, bool buoy,
                                               float r0, float r1, bool rbc, float rm0, float rc0, float rm1, float rc1, float s_a,
                                               float rho_star, bool grav, float g_a, bool bc2, int kg, int k) {
-  if (ubc) { const float t = v * um; v = t + uc; }                                         // simulate.py:96
+  if (ubc && BC1) { const float t = v * um; v = t + uc; }                                         // simulate.py:96
   if (buoy && !border && fc == FNX_FLUID && fm == FNX_FLUID) {                              // source_terms.py
     float q0 = r0, q1 = r1;
     if (rbc) { float t = q0 * rm0; q0 = t + rc0; t = q1 * rm1; q1 = t + rc1; }
@@ -72,7 +75,7 @@ __device__ __forceinline__ float stage_eval3d(int a, float v, bool ubc, float um
 // neighbouring thread loads as its own -- instead of a second pass reading the staged field back (round 1 measured the fused
 // form slower, 0.67 against 0.59 ms at 256^3: that was the branchy kernel with 54 dependent loads; in the straight-line form
 // the divergence pass's 75 us at 512x512x64 become ~15).
-template <bool QUIRKS, bool WALL, bool DIV>
+template <bool QUIRKS, bool WALL, bool DIV, bool BC1 = true>
 __global__ __launch_bounds__(BX* BY) void stage3d_kernel(GridDims g, StepPtrs P, int buoy, float sx, float sy, float sz,
                                                          float rho_star, int kdiv) {
   const int i = blockIdx.x * BX + threadIdx.x, j = blockIdx.y * BY + threadIdx.y;
@@ -143,7 +146,7 @@ __global__ __launch_bounds__(BX* BY) void stage3d_kernel(GridDims g, StepPtrs P,
   float un[3];
 #pragma unroll
   for (int a = 0; a < 3; ++a)
-    un[a] = stage_eval3d<QUIRKS, WALL>(a, u[a], ubc, um[a], uc[a], fc, fm[a], border, by, r0, r1[a], rb, rm0, rc0, rm1[a], rc1[a], sa[a],
+    un[a] = stage_eval3d<QUIRKS, WALL, BC1>(a, u[a], ubc, um[a], uc[a], fc, fm[a], border, by, r0, r1[a], rb, rm0, rc0, rm1[a], rc1[a], sa[a],
                                        rho_star, gr, ga[a], P.bc2 != 0, k + g.zoff, k);
   float rnew = r0;
   if (has_rho && rbc) {
@@ -161,7 +164,7 @@ __global__ __launch_bounds__(BX* BY) void stage3d_kernel(GridDims g, StepPtrs P,
 #pragma unroll
       for (int a = 0; a < 3; ++a) {
         const bool bp = is_border<true>(g, i + (a == 0), j + (a == 1), k + (a == 2));
-        vp[a] = stage_eval3d<QUIRKS, WALL>(a, up[a], ubc, ump[a], ucp[a], fp[a], fc, bp, by, rp[a], r0, rb, rmp[a], rcp[a], rm0, rc0, sa[a],
+        vp[a] = stage_eval3d<QUIRKS, WALL, BC1>(a, up[a], ubc, ump[a], ucp[a], fp[a], fc, bp, by, rp[a], r0, rb, rmp[a], rcp[a], rm0, rc0, sa[a],
                                            rho_star, gr, ga[a], P.bc2 != 0, k + (a == 2) + g.zoff, k + (a == 2));
       }
       d = ((un[0] - vp[0]) + un[1]) - vp[1];
@@ -177,11 +180,11 @@ __global__ __launch_bounds__(BX* BY) void stage3d_kernel(GridDims g, StepPtrs P,
 // density at the cell and its four neighbours, four advected velocity values and, unless the whole wave is in identity
 // BC cells, their BC entries -- are issued up front (clamped indices where a neighbour does not exist; such values are
 // never used) and the stage conditions become selects.
-template <bool WALL>
+template <bool WALL, bool BC1 = true>
 __device__ __forceinline__ float stage_eval2d(int a, float u, bool ubc, float um, float uc, float fc, float fm, bool border,
                                               bool buoy, float r0, float r1, bool rbc, float rm0, float rc0, float rm1,
                                               float rc1, float s_a, float rho_star, bool grav, float g_a, bool bc2) {
-  if (ubc) { const float t = u * um; u = t + uc; }                                           // simulate.py:96
+  if (ubc && BC1) { const float t = u * um; u = t + uc; }                                           // simulate.py:96
   if (buoy && !border && fc == FNX_FLUID && fm == FNX_FLUID) {                               // source_terms.py
     if (rbc) { float t = r0 * rm0; r0 = t + rc0; t = r1 * rm1; r1 = t + rc1; }
     u = u + s_a * ((0.5f * (r0 + r1)) - rho_star);
@@ -195,7 +198,7 @@ __device__ __forceinline__ float stage_eval2d(int a, float u, bool ubc, float um
   return u;
 }
 
-template <bool WALL>
+template <bool WALL, bool BC1 = true>
 __global__ __launch_bounds__(BX* BY) void stage2d_div_kernel(GridDims g, StepPtrs P, int buoy_, float sx, float sy,
                                                              float rho_star) {
   const int i = blockIdx.x * BX + threadIdx.x, j = blockIdx.y * BY + threadIdx.y;
@@ -235,16 +238,16 @@ __global__ __launch_bounds__(BX* BY) void stage2d_div_kernel(GridDims g, StepPtr
   }
   // ---- the four staged values
   const bool border = is_border<false>(g, i, j, 0);
-  const float v0 = stage_eval2d<WALL>(0, u0, ubc, m0, c0, F00, Fm0, border, buoy, R00, Rm0, rbc, rm00, rc00, rmm0, rcm0, sx, rho_star, grav, P.gx, bc2);
-  const float v1 = stage_eval2d<WALL>(1, u1, ubc, m1, c1, F00, F0m, border, buoy, R00, R0m, rbc, rm00, rc00, rm0m, rc0m, sy, rho_star, grav, P.gy, bc2);
+  const float v0 = stage_eval2d<WALL, BC1>(0, u0, ubc, m0, c0, F00, Fm0, border, buoy, R00, Rm0, rbc, rm00, rc00, rmm0, rcm0, sx, rho_star, grav, P.gx, bc2);
+  const float v1 = stage_eval2d<WALL, BC1>(1, u1, ubc, m1, c1, F00, F0m, border, buoy, R00, R0m, rbc, rm00, rc00, rm0m, rc0m, sy, rho_star, grav, P.gy, bc2);
   float rnew = R00;
   if (rbc) { float t = rnew * rm00; rnew = t + rc00; if (bc2) { t = rnew * rm00; rnew = t + rc00; } }    // simulate.py:96, :133
   float d = 0.f;
   if (P.div) {
     if (!border) {
-      const float v0p = stage_eval2d<WALL>(0, u0p, ubc, m0p, c0p, Fp0, F00, is_border<false>(g, i + 1, j, 0), buoy, Rp0, R00, rbc,
+      const float v0p = stage_eval2d<WALL, BC1>(0, u0p, ubc, m0p, c0p, Fp0, F00, is_border<false>(g, i + 1, j, 0), buoy, Rp0, R00, rbc,
                                            rmp0, rcp0, rm00, rc00, sx, rho_star, grav, P.gx, bc2);
-      const float v1p = stage_eval2d<WALL>(1, u1p, ubc, m1p, c1p, F0p, F00, is_border<false>(g, i, j + 1, 0), buoy, R0p, R00, rbc,
+      const float v1p = stage_eval2d<WALL, BC1>(1, u1p, ubc, m1p, c1p, F0p, F00, is_border<false>(g, i, j + 1, 0), buoy, R0p, R00, rbc,
                                            rm0p, rc0p, rm00, rc00, sy, rho_star, grav, P.gy, bc2);
       d = ((v0 - v0p) + v1) - v1p;
     }
@@ -378,7 +381,7 @@ __global__ __launch_bounds__(256) void bc_classify_kernel(size_t n, size_t dhw, 
 // cell, then the second setConstVals at the destination.
 __global__ __launch_bounds__(256) void periodic_pre_kernel(GridDims g, int nc, const float* __restrict__ U_adv,
                                                            const float* __restrict__ UBC, const float* __restrict__ UBCInvMask,
-                                                           float* __restrict__ U, int px, int py) {
+                                                           float* __restrict__ U, int px, int py, int staged) {
   const int t = blockIdx.x * 256 + threadIdx.x;
   const int bk = blockIdx.y, b = bk / g.KN, k = g.K0 + (bk - b * g.KN);
   if (t >= g.H + g.W) return;
@@ -389,7 +392,11 @@ __global__ __launch_bounds__(256) void periodic_pre_kernel(GridDims g, int nc, c
   const size_t src = base + (xp ? (size_t)t * g.W + (g.W - 1) : (size_t)(g.H - 1) * g.W + (t - g.H));
   const size_t dst = base + (xp ? (size_t)t * g.W + 1 : (size_t)g.W + (t - g.H));
   float v = U_adv[src];
-  if (UBC) { float q = v * UBCInvMask[src]; v = q + UBC[src]; q = v * UBCInvMask[dst]; v = q + UBC[dst]; }
+  if (UBC) {
+    float q;
+    if (!staged) { q = v * UBCInvMask[src]; v = q + UBC[src]; }       // (staged: U_adv already is the field ahead of setWallBcs)
+    q = v * UBCInvMask[dst]; v = q + UBC[dst];
+  }
   U[dst] = v;
 }
 
@@ -424,10 +431,25 @@ void launch_pre_projection(const GridDims& g, bool is3d, bool quirks, const floa
                            const float* flags, const float* UBC, const float* UBCInvMask, const float* rhoBC,
                            const float* rhoBCInvMask, float* U, float* rho, float* div, bool buoyancy, float sx,
                            float sy, float sz, float rho_star, bool wall_bcs, hipStream_t s, const unsigned char* cls,
-                           const float* gravity, bool second_bcs, int div_k_end) {
+                           const float* gravity, bool second_bcs, int div_k_end, bool first_bcs) {
   StepPtrs P{U_adv, rho_adv, flags, UBC, UBCInvMask, rhoBC, rhoBCInvMask, U, rho, div, cls,
              gravity ? 1 : 0, gravity ? gravity[0] : 0.f, gravity ? gravity[1] : 0.f, gravity ? gravity[2] : 0.f, second_bcs ? 1 : 0};
   const dim3 grid = cell_grid(g), block(BX, BY);
+  if (!first_bcs) {
+    // the staged input has its buoyancy and gravity behind it (the caller passes neither; QUIRKS only concerns the buoyancy)
+    const int kd = div ? div_k_end : 0;
+    if (!is3d) {
+      if (wall_bcs) stage2d_div_kernel<true, false><<<grid, block, 0, s>>>(g, P, 0, 0.f, 0.f, rho_star);
+      else stage2d_div_kernel<false, false><<<grid, block, 0, s>>>(g, P, 0, 0.f, 0.f, rho_star);
+    } else if (div) {
+      if (wall_bcs) stage3d_kernel<false, true, true, false><<<grid, block, 0, s>>>(g, P, 0, 0.f, 0.f, 0.f, rho_star, kd);
+      else stage3d_kernel<false, false, true, false><<<grid, block, 0, s>>>(g, P, 0, 0.f, 0.f, 0.f, rho_star, kd);
+    } else {
+      if (wall_bcs) stage3d_kernel<false, true, false, false><<<grid, block, 0, s>>>(g, P, 0, 0.f, 0.f, 0.f, rho_star, kd);
+      else stage3d_kernel<false, false, false, false><<<grid, block, 0, s>>>(g, P, 0, 0.f, 0.f, 0.f, rho_star, kd);
+    }
+    return;
+  }
   if (!is3d) {
     if (wall_bcs) stage2d_div_kernel<true><<<grid, block, 0, s>>>(g, P, buoyancy, sx, sy, rho_star);
     else stage2d_div_kernel<false><<<grid, block, 0, s>>>(g, P, buoyancy, sx, sy, rho_star);
@@ -463,9 +485,9 @@ void launch_post_projection(const GridDims& g, bool is3d, const float* p, float*
 }
 
 void launch_periodic_pre(const GridDims& g, bool is3d, const float* U_adv, const float* UBC, const float* UBCInvMask, float* U,
-                         bool px, bool py, hipStream_t s) {
+                         bool px, bool py, hipStream_t s, bool staged) {
   const dim3 grid((g.H + g.W + 255) / 256, g.B * g.KN);
-  periodic_pre_kernel<<<grid, 256, 0, s>>>(g, is3d ? 3 : 2, U_adv, UBC, UBCInvMask, U, px, py);
+  periodic_pre_kernel<<<grid, 256, 0, s>>>(g, is3d ? 3 : 2, U_adv, UBC, UBCInvMask, U, px, py, staged ? 1 : 0);
 }
 
 size_t periodic_save_bytes(const GridDims& g) { return (size_t)g.B * g.KN * (g.H + g.W) * sizeof(float); }

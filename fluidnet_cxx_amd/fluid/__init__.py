@@ -14,11 +14,11 @@ CellType = IntEnum("CellType", dict(TypeNone=0, TypeFluid=1, TypeObstacle=2, Typ
                                     TypeOpen=32, TypeStick=128, TypeReserved=256))
 Geom = _ext.Geom     # per-call 3D geometry options (ref_quirks, z-slab view, compute window); no reference counterpart
 from .ops import (advectScalar, advectVelocity, correctScalar, solveLinearSystemJacobi, solveLinearSystemPCG, velocityDivergence,
-                  velocityUpdate, addBuoyancy, addGravity, addViscosity, setWallBcs, setWallBcsStick, flagsToOccupancy, setConstVals,
+                  velocityUpdate, addBuoyancy, addGravity, addViscosity, addVorticityConfinement, setWallBcs, setWallBcsStick, flagsToOccupancy, setConstVals,
                   getDx, getCentered)
 from .init_conditions import emptyDomain, createPlumeBCs, createRayleighTaylorBCs
 from .geometry_utils import createCylinder, createBox2D
 
 __all__ = ["CellType", "Geom", "advectScalar", "advectVelocity", "correctScalar", "solveLinearSystemJacobi", "solveLinearSystemPCG",
-           "velocityDivergence", "velocityUpdate", "addBuoyancy", "addGravity", "addViscosity", "setWallBcs", "setWallBcsStick", "flagsToOccupancy", "setConstVals",
+           "velocityDivergence", "velocityUpdate", "addBuoyancy", "addGravity", "addViscosity", "addVorticityConfinement", "setWallBcs", "setWallBcsStick", "flagsToOccupancy", "setConstVals",
            "getDx", "getCentered", "emptyDomain", "createPlumeBCs", "createRayleighTaylorBCs", "createCylinder", "createBox2D"]

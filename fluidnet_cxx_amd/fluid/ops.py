@@ -210,6 +210,16 @@ def addViscosity(dt, U, flags, viscosity):
     ext.add_viscosity_(float(dt), U, flags, float(viscosity))
 
 
+def addVorticityConfinement(U, flags, strength, *, geom=None):
+    """Vorticity confinement (no runnable reference counterpart; include/fluidnet_hip.h: fnx_add_vorticity_confinement) -- in place
+    on U, returns U.  F = (grad|w| / |grad|w||) x w * strength from the curl w of the cell-centred velocity, averaged onto the MAC
+    faces addGravity writes.  Whole grids only: a compute window or z-slab view through `geom` raises.  strength 0 leaves U alone."""
+    _check5(U, flags)
+    assert flags.size(1) == 1, "flags is not scalar"
+    ext.add_vorticity_confinement_(U, flags, float(strength), geom)
+    return U
+
+
 def setWallBcs(U, flags, *, geom=None):
     """lib/fluid/set_wall_bcs.py:4-86 -- in place on U, returns U (differentiable w.r.t. U)."""
     _check5(U, flags)

@@ -23,6 +23,12 @@ import torch
 import torch.distributed as dist
 
 
+def _refuse_vorticity(mconf):
+    # the confinement reads U three planes either side of a plane: single-domain only (fnx_slab_step refuses it too)
+    if float(mconf.get("vorticityConfinementAmp", 0) or 0) > 0:
+        raise ValueError("the z-slab drivers do not run vorticity confinement (mconf['vorticityConfinementAmp'] > 0 is single-domain only)")
+
+
 class SlabLayout:
     """Index arithmetic of one rank's slab."""
 
@@ -251,6 +257,7 @@ class SlabSimulator:
         pass over U and one 4-byte all-reduce(MAX) on the control path."""
         assert schedule in ("last_pass", "edge_first", "deep_first", "deep_beside")
         assert method in ("jacobi", "convnet")
+        _refuse_vorticity(mconf)
         self.method, self.net = method, net
         if method == "convnet" and layout.world > 1:
             assert net is not None, "method 'convnet' needs the net (a FluidNet, or any x -> p callable for the CPU operator sets)"
@@ -827,6 +834,7 @@ class NativeSlabSimulator:
         layout.halo >= 49 (a multiple of 4) and owned planes a multiple of 4 (include/fluidnet_hip.h)."""
         from ._ext import ext
         assert method in ("jacobi", "convnet") and (method == "jacobi" or net is not None)
+        _refuse_vorticity(mconf)
         self.ext, self.l, self.cfg, self.comm = ext, layout, mconf, comm
         self.method, self.net = method, net
         # direct_sends "auto" | "never" | "always": where the communicator offers them (peer-store, link model) a sweep block's last edge

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define FNX_ABI_VERSION 21
+#define FNX_ABI_VERSION 22
 
 enum {
   FNX_OK = 0,
@@ -231,6 +231,20 @@ int fnx_correct_scalar(const FnxGrid* g, float dt, float* src, const float* div,
 int fnx_add_viscosity(const FnxGrid* g, float dt, const float* U_in, float* U_out, const float* flags,
                       float viscosity, void* stream);
 
+/* Vorticity confinement (ABI 22; no runnable reference counterpart -- the reference tree only keeps its per-cell statement as
+ * dead code): U_out = U_in + the confinement force of U_in.  fp32, uncontracted, in this order, every field below being 0
+ * outside the interior cells (1 <= i <= W-2, 1 <= j <= H-2, in 3D 1 <= k <= D-2):
+ *   c_a = 0.5 (U_a(cell) + U_a(cell + e_a))                                  centred velocity (c_z = 0 in 2D)
+ *   w   = curl c by central differences, w_z = 0.5 (d_x c_y - d_y c_x) ...   with d_a f = f(cell + e_a) - f(cell - e_a)
+ *   n   = norm(w);  norm(v) = sqrt((v_x v_x + v_y v_y) + v_z v_z) if that sum > 1e-6, else 0
+ *   g_a = 0.5 d_a n;  m = norm(g);  g = g / m if m > 1e-6 else 0;  F = (g x w) * amp
+ *   U_a(cell) += 0.5 (F_a(cell - e_a) + F_a(cell))   on the interior cells and components addGravity writes (cell fluid or
+ *                                                    empty, -e_a neighbour fluid, or empty under a fluid cell)
+ * Every other value is copied.  A component depends on U_in within three cells in every axis, so U_out must be a distinct
+ * buffer.  Whole grids only (no compute window, no z-slab view).  amp == 0 copies U_in. */
+int fnx_add_vorticity_confinement(const FnxGrid* g, const float* U_in, float* U_out, const float* flags, float amp,
+                                  void* stream);
+
 /* setWallBcs (in place on U), lib/fluid/set_wall_bcs.py:4-86 */
 int fnx_set_wall_bcs(const FnxGrid* g, float* U, const float* flags, void* stream);
 
@@ -310,6 +324,9 @@ typedef struct FnxStepParams {
   /* ABI 20, method 2 (mconf['pcgTol'], mconf['pcgIter']): */
   float pcg_tol;              /* relative residual ||b - A p|| / ||b|| to stop at; <= 0 runs exactly pcg_iter iterations, no host sync */
   int   pcg_iter;             /* at most that many CG iterations (>= 1) */
+  /* ABI 22 (mconf['vorticityConfinementAmp']; off when <= 0; single domain only, fnx_slab_step refuses it): */
+  float vorticity_confinement; /* fnx_add_vorticity_confinement with this amplitude after addGravity and before setWallBcs, for
+                                 every method.  With it off the step launches what it launched before ABI 22. */
 } FnxStepParams;
 
 typedef struct FnxState {
@@ -347,7 +364,11 @@ int fnx_simulate_step(const FnxGrid* g, const FnxStepParams* prm, const FnxState
  *         setConstVals [not with st->flags_stick in method 1: the caller runs setWallBcsStick first], velocityDivergence
  *         [div != NULL])
  *   post: simulate.py:154-168        velocityUpdate(st->p), setWallBcs, setConstVals, in place on st->U / st->density (no
- *         periodic patches: fnx_simulate_step wraps it with them) */
+ *         periodic patches: fnx_simulate_step wraps it with them)
+ * With prm->vorticity_confinement > 0 the pre stage is cut in two around the confinement (stages up to addGravity -> st->U,
+ * confinement st->U -> U_adv, the remaining stages U_adv -> st->U): U_adv is then OVERWRITTEN (it is scratch of the caller's
+ * in every use the library makes of it), the density's second setConstVals is a pass of its own, and the grid must be whole (no
+ * compute window, no z-slab view). */
 int fnx_pre_projection(const FnxGrid* g, const FnxStepParams* prm, const FnxState* st, const float* U_adv,
                        const float* rho_adv, float* div, void* stream);
 int fnx_post_projection(const FnxGrid* g, const FnxState* st, void* stream);
