@@ -74,7 +74,7 @@ size_t ws_advect_fix(const FnxGrid* g) { return al(4 * 8 * (size_t)g->B * g->D *
 // the stand-alone operators take the tile kernels too (ABI 19): their fields + the bitmaps
 size_t ws_advect_scalar(const FnxGrid* g) { return ws_advect_scalar_fields(g) + ws_advect_fix(g); }
 size_t ws_advect_vel(const FnxGrid* g) { return ws_advect_vel_fields(g) + ws_advect_fix(g); }
-size_t ws_mask(const FnxGrid* g) { return g->is3D ? al(fnx::jacobi3d_mask_bytes(dims(g))) : 0; }   // 3D solver: neighbour-mask bytes, twice (rows / row groups)
+size_t ws_mask(const FnxGrid* g) { return g->is3D ? al(fnx::jacobi3d_mask_bytes(dims(g))) : 0; }   // 3D solver: neighbour-mask bytes, twice (rows / row groups), and the planes-alike bits
 // Jacobi workspace: ping-pong pressure, the residual's fixed-order partial sums, one result float, the 3D neighbour mask
 size_t ws_jacobi(const FnxGrid* g) { return al(ncell(g) * 4) + al(fnx::residual_scratch_bytes(g->B)) + al(4) + ws_mask(g); }
 struct JacobiWs { float* tmp; double* partials; float* res; unsigned char* mask; };

@@ -346,6 +346,43 @@ __global__ __launch_bounds__(256) void jacobi3d_maskq_kernel(GridDims g, const u
   maskq[(bk * Hq + q) * g.W + i] = w;
 }
 
+// "Plane k's mask equals plane k-1's" per tile of the two-sweep march, one bit per plane packed along z:
+// same[(b * nyt + by) * nxt + bx][k >> 5] bit (k & 31), set when the three values the march's ldm(k) returns -- the own word at the
+// clamped column x = bx*60-2+lane, byte 3 of the row group below, byte 0 of the one above (0 where that group does not exist) -- equal
+// those of plane k-1 in every lane.  Bit 0 of plane 0 and the bits of planes >= D stay 0.  One wave per (tile, word): a domain whose
+// obstacles are extruded in z (or absent) has every bit set but those next to the z walls, and the march then keeps the mask registers
+// it holds instead of loading them again.
+__global__ __launch_bounds__(64) void jacobi3d_masksame_kernel(GridDims g, const unsigned* __restrict__ maskq,
+                                                               unsigned* __restrict__ same, int nxt, int nyt, int kwords) {
+  const int lane = threadIdx.x;
+  const int bx = blockIdx.x % nxt, by = blockIdx.x / nxt, kw = blockIdx.y, b = blockIdx.z;
+  const int x = bx * 60 - 2 + lane;
+  const int xc = x < 0 ? 0 : (x > g.W - 1 ? g.W - 1 : x);
+  const int HqM = (g.H + 3) >> 2;
+  const size_t HqW = (size_t)HqM * g.W;
+  const bool has_m = by > 0, has_p = by + 1 < HqM;
+  const unsigned* col = maskq + (size_t)b * g.D * HqW + xc;
+  auto ld = [&](int k, unsigned& own, unsigned& lo, unsigned& hi) {
+    const unsigned* pl = col + (size_t)k * HqW;
+    own = pl[(size_t)by * g.W];
+    lo = has_m ? pl[(size_t)(by - 1) * g.W] >> 24 : 0u;
+    hi = has_p ? pl[(size_t)(by + 1) * g.W] & 0xffu : 0u;
+  };
+  const int kfirst = kw * 32;
+  unsigned po = 0, pl = 0, ph = 0, bits = 0;
+  if (kfirst > 0) ld(kfirst - 1, po, pl, ph);
+  for (int q = 0; q < 32; ++q) {
+    const int k = kfirst + q;
+    if (k >= g.D) break;
+    unsigned o, l, h;
+    ld(k, o, l, h);
+    const bool differs = (o != po) | (l != pl) | (h != ph);
+    if (k > 0 && __builtin_amdgcn_ballot_w64(differs) == 0) bits |= 1u << q;
+    po = o; pl = l; ph = h;
+  }
+  if (lane == 0) same[((size_t)(b * nyt + by) * nxt + bx) * kwords + kw] = bits;
+}
+
 // first sweep from p = 0: ((((((0+0)+0)+0)+0)+0)+div)/6 == div/6 on 'cont' cells.  Writes the planes [kb, ke) of every
 // sample only (`first` = kb*HW, `count` = (ke-kb)*HW cells per sample; `per` = cells per sample).
 __global__ __launch_bounds__(256) void jacobi3d_first_kernel(int B, size_t per, size_t first, size_t count,
@@ -541,6 +578,7 @@ __device__ __forceinline__ BufRsrc make_rsrc(const void* p, unsigned bytes) {
 struct MirrorArgs { float* out[2][2]; const unsigned* sel[2]; int k[2]; int n; unsigned long long bstride; unsigned long long* clock; };
 template <bool ZERO, bool SPLIT, int LAY, bool MIR = false>
 __global__ __launch_bounds__(64 * Z2NW, Z2WPS) void jacobi3d_march2_kernel(GridDims g, const unsigned* __restrict__ maskq,
+                                                                      const unsigned* __restrict__ msame,
                                                                       const float* __restrict__ div,
                                                                       const float* __restrict__ p_in,
                                                                       float* __restrict__ p_out, int nxt, int nyt,
@@ -638,6 +676,12 @@ __global__ __launch_bounds__(64 * Z2NW, Z2WPS) void jacobi3d_march2_kernel(GridD
     m.hi = has_p ? (unsigned)__builtin_amdgcn_raw_buffer_load_b8(r_m, xoff, po + mq_p, 0) : 0u;
     return m;
   };
+  // "plane k's mask equals plane k-1's" bits of this tile (jacobi3d_masksame_kernel) for the planes the steps after the first load the
+  // mask of, [k_lo + 1, k_hi + 1]: two words from a wave-uniform address, i.e. scalar loads; planes past them simply load
+  const int skw = (g.D + 31) >> 5, sw0 = (k_lo + 1) >> 5;
+  const unsigned* srow = msame + (size_t)tile * skw;
+  const unsigned long long sbits = (unsigned long long)(sw0 < skw ? srow[sw0] : 0u) |
+                                   ((unsigned long long)(sw0 + 1 < skw ? srow[sw0 + 1] : 0u) << 32);
   auto ldf = [&](const BufRsrc& r, unsigned cell) {
     return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, xoff, cell * 4u, 0));
   };
@@ -739,7 +783,11 @@ __global__ __launch_bounds__(64 * Z2NW, Z2WPS) void jacobi3d_march2_kernel(GridD
     load_p0(P0[SN], p2);
 #pragma unroll
     for (int rr = 0; rr < R1; ++rr) AD[SP][rr] = ldf(r_d, p1 + rowb[rr + 1]);
-    AM[SP] = ldm(t + 1);
+    // (the mask of a plane that equals the one held -- every plane but those at the z walls where obstacles are extruded in z or
+    // absent -- is copied, not loaded: 3 of the step's 13 vector-memory instructions; the first step of a segment always loads)
+    const unsigned sq = (unsigned)(t + 1 - 32 * sw0);
+    if (t >= k_lo && sq < 64u && ((sbits >> sq) & 1ull)) AM[SP] = AM[SC];
+    else AM[SP] = ldm(t + 1);
     // ---- sweep 1 on plane t, rows j0-1 .. j0+4
     const unsigned ob = AM[SC].own | ((AM[SC].lo | AM[SC].hi) & 0xffu);
     // no cell of these rows has an obstacle neighbour (0) / only x neighbours (1) / any (2)
@@ -933,7 +981,14 @@ void launch_jacobi(const GridDims& g, const float* flags, const float* div, cons
 // 3D fast path (mask precomputed by launch_jacobi3d_mask)
 // the mask allocation: B*D*H*W neighbour-mask bytes, then (256-B aligned) the same bytes in row groups of four
 static size_t maskq_offset(const GridDims& g) { return (((size_t)g.B * g.DHW) + 255) & ~(size_t)255; }
-size_t jacobi3d_mask_bytes(const GridDims& g) { return maskq_offset(g) + (size_t)g.B * g.D * ((g.H + 3) / 4) * g.W * 4; }
+// ... then (256-B aligned) one "same as the plane below" bit per (sample, tile of the two-sweep march, plane), 32 planes to a word
+static size_t masksame_offset(const GridDims& g) {
+  return (maskq_offset(g) + (size_t)g.B * g.D * ((g.H + 3) / 4) * g.W * 4 + 255) & ~(size_t)255;
+}
+size_t jacobi3d_mask_bytes(const GridDims& g) {
+  const size_t tiles = (size_t)((g.W + 59) / 60) * ((g.H + Z2NW * Z2R - 1) / (Z2NW * Z2R)) * g.B;
+  return masksame_offset(g) + tiles * ((g.D + 31) / 32) * 4;
+}
 
 void launch_jacobi3d_mask(const GridDims& g, bool quirks, const float* flags, unsigned char* mask, hipStream_t s) {
   const dim3 grid((g.W + 63) / 64, (g.H + 3) / 4, g.B * g.D), block(64, 4);
@@ -941,6 +996,9 @@ void launch_jacobi3d_mask(const GridDims& g, bool quirks, const float* flags, un
   else jacobi3d_mask_kernel<false><<<grid, block, 0, s>>>(g, flags, mask);
   const dim3 gridq((g.W + 63) / 64, ((g.H + 3) / 4 + 3) / 4, g.B * g.D);
   jacobi3d_maskq_kernel<<<gridq, block, 0, s>>>(g, mask, (unsigned*)(mask + maskq_offset(g)));
+  const int nxt = (g.W + 59) / 60, nyt = (g.H + Z2NW * Z2R - 1) / (Z2NW * Z2R), kwords = (g.D + 31) / 32;
+  jacobi3d_masksame_kernel<<<dim3(nxt * nyt, kwords, g.B), 64, 0, s>>>(g, (const unsigned*)(mask + maskq_offset(g)),
+                                                                         (unsigned*)(mask + masksame_offset(g)), nxt, nyt, kwords);
 }
 
 // can the two-sweep passes of this grid hand each other p in the row-quad layout (`lay` of launch_jacobi3d_x2)?
@@ -990,16 +1048,17 @@ void launch_jacobi3d_x2(const GridDims& g, const unsigned char* mask, const floa
   }
   const dim3 grid((unsigned)G), block(64, Z2NW);
   const unsigned* maskq = (const unsigned*)(mask + maskq_offset(g));
+  const unsigned* msame = (const unsigned*)(mask + masksame_offset(g));
   if (mirror) {                                            // (jacobi3d_mirror_ok has been checked: resident set, not from zero, lay 0 or 3)
     MirrorArgs m{};
     for (int r = 0; r < 2; ++r) { m.out[r][0] = mirror->out[r][0]; m.out[r][1] = mirror->out[r][1]; m.sel[r] = mirror->sel[r]; }
     m.k[0] = mirror->k[0]; m.k[1] = mirror->k[1]; m.n = mirror->n;
     m.bstride = mirror->bstride; m.clock = mirror->clock;
-    if (lay == 3) jacobi3d_march2_kernel<false, false, 3, true><<<grid, block, 0, s>>>(g, maskq, div, p_in, p_out, nxt, nyt, zchunk, kb, ke, kb2, m);
-    else jacobi3d_march2_kernel<false, false, 0, true><<<grid, block, 0, s>>>(g, maskq, div, p_in, p_out, nxt, nyt, zchunk, kb, ke, kb2, m);
+    if (lay == 3) jacobi3d_march2_kernel<false, false, 3, true><<<grid, block, 0, s>>>(g, maskq, msame, div, p_in, p_out, nxt, nyt, zchunk, kb, ke, kb2, m);
+    else jacobi3d_march2_kernel<false, false, 0, true><<<grid, block, 0, s>>>(g, maskq, msame, div, p_in, p_out, nxt, nyt, zchunk, kb, ke, kb2, m);
     return;
   }
-#define J3Q(Z, S, L) jacobi3d_march2_kernel<Z, S, L><<<grid, block, 0, s>>>(g, maskq, div, p_in, p_out, nxt, nyt, zchunk, kb, ke, kb2)
+#define J3Q(Z, S, L) jacobi3d_march2_kernel<Z, S, L><<<grid, block, 0, s>>>(g, maskq, msame, div, p_in, p_out, nxt, nyt, zchunk, kb, ke, kb2)
 #define J3Q_S(Z, L) do { if (zchunk > 0) J3Q(Z, false, L); else J3Q(Z, true, L); } while (0)
   if (from_zero) lay &= 2;                                 // no input: its layout does not matter
   if (lay == 0) { if (from_zero) J3Q_S(true, 0); else J3Q_S(false, 0); }

@@ -103,7 +103,7 @@ void launch_jacobi(const GridDims& g, const float* flags, const float* div, cons
                    bool from_zero, hipStream_t s);
 int  jacobi_max_sweeps_per_launch(const GridDims& g, bool is3d, int total_sweeps);   // total_sweeps: what the solve still has to run
 // 3D: flags -> 7-bit neighbour mask (once per solve), then z-marching passes of two sweeps (one for an odd remainder)
-size_t jacobi3d_mask_bytes(const GridDims& g);   // bytes of the `mask` allocation of the 3D launches below (byte mask + the same bytes in row groups of four)
+size_t jacobi3d_mask_bytes(const GridDims& g);   // bytes of the `mask` allocation of the 3D launches below (byte mask + the same bytes in row groups of four + one "same as the plane below" bit per tile and plane of the two-sweep march)
 void launch_jacobi3d_mask(const GridDims& g, bool quirks, const float* flags, unsigned char* mask, hipStream_t s);
 // kb/ke: restrict the OUTPUT to planes [kb, ke) (0,0 = all planes); inputs are read from kb-1 (kb-2 for x2) on
 void launch_jacobi3d(const GridDims& g, const unsigned char* mask, const float* div, const float* p_in, float* p_out,
