@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
 """The reference's `pytorch/plume.py` main loop on this backend -- what a driver looks like after the switch.
 
-    python examples/plume.py [--res 128] [--iters 200] [--out-iter 50] [--method jacobi|pcg] [--vorticity AMP] [--folder out] [--restart]
+    python examples/plume.py [--res 128] [--iters 200] [--out-iter 50] [--method jacobi|pcg|convnet] [--weights CKPT] [--vorticity AMP]
+                             [--folder out] [--restart]
 
 Same structure as the reference driver (plume.py:66-178 setup, :231-424 loop): build the batch, `createPlumeBCs`, optional
 restart from `<folder>/restart.pth`, echo the configuration as YAML, then `simulate()` per iteration and, every `out-iter`
 iterations, the PNG panels, the VTK cell data and the restart file.  Only the import line differs from a reference-side
-driver: `lib` -> `fluidnet_cxx_amd`."""
+driver: `lib` -> `fluidnet_cxx_amd`.  `--method convnet --weights CKPT` projects with a trained net: CKPT is what examples/train.py
+writes ({'state_dict', 'mconf', ...}), loaded the way the reference driver loads convModel_lastEpoch_best.pth (plume.py:119-123)."""
 import argparse
 import os
 import sys
@@ -14,7 +16,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from fluidnet_cxx_amd import fluid, simulate, output, load_restart      # noqa: E402   (reference: `import lib, lib.fluid as fluid`)
+from fluidnet_cxx_amd import fluid, simulate, output, load_restart, FluidNet      # noqa: E402   (reference: `import lib, lib.fluid as fluid`)
 
 
 def main(argv=None):
@@ -22,12 +24,15 @@ def main(argv=None):
     ap.add_argument("--res", type=int, default=128)
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--out-iter", type=int, default=50)
-    ap.add_argument("--method", default="jacobi", choices=["jacobi", "pcg"])      # 'convnet' needs a trained FluidNet state dict
+    ap.add_argument("--method", default="jacobi", choices=["jacobi", "pcg", "convnet"])
+    ap.add_argument("--weights", default=None, metavar="CKPT", help="checkpoint of examples/train.py (needed by --method convnet)")
     ap.add_argument("--vorticity", type=float, default=0.0, metavar="AMP",
                     help="vorticity confinement amplitude (mconf['vorticityConfinementAmp'], no reference key; 0 = off)")
     ap.add_argument("--folder", default="plume_out")
     ap.add_argument("--restart", action="store_true")
     a = ap.parse_args(argv)
+    if (a.method == "convnet") != (a.weights is not None):
+        ap.error("--method convnet needs --weights CKPT, and --weights is only read by --method convnet")
     cuda = torch.device("cuda")
     # plumeConfig.yaml:29-76 (the keys simulate() reads)
     simConf = dict(dt=0.1, maccormackStrength=0.6, sampleOutsideFluid=False, buoyancyScale=0.25, gravityScale=0, viscosity=0,
@@ -37,6 +42,15 @@ def main(argv=None):
         simConf.update(pcgTol=1e-5, pcgIter=50)
     if a.vorticity > 0:                                   # puts back the small-scale rotation the advection smooths away
         simConf.update(vorticityConfinementAmp=a.vorticity)
+    net = None
+    if a.method == "convnet":                             # plume.py:119-123
+        state = torch.load(a.weights, map_location="cpu", weights_only=False)
+        mconf = state["mconf"]
+        net = FluidNet(mconf, dropout=False)
+        net = net.cuda()
+        net.load_state_dict(state["state_dict"])
+        net.eval()
+        simConf.update(normalizeInputThreshold=mconf.get("normalizeInputThreshold", 1e-5))
     os.makedirs(a.folder, exist_ok=True)
     resX = resY = a.res
     # plume.py:131-163
@@ -55,7 +69,7 @@ def main(argv=None):
         print("Restarting from checkpoint at it = " + str(it))
     output.echo_config(os.path.join(a.folder, "plumeConfig.yaml"), simConf)      # plume.py:176-178
     while it < a.iters:                                   # plume.py:231-424
-        simulate(simConf, batch_dict, None, a.method)
+        simulate(simConf, batch_dict, net, a.method)
         if it % a.out_iter == 0:
             print("It = " + str(it))
             output.save_state(a.folder, it, batch_dict)

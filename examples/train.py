@@ -1,0 +1,72 @@
+#!/usr/bin/env python3
+"""Train the 2D pressure net on one GPU, with nothing downloaded -- what the reference's `pytorch/fluid_net_train.py` does with a
+Mantaflow data set, on scenes generated while training (fluidnet_cxx_amd/training.py).
+
+    python examples/train.py [--res 128] [--batch 64] [--iters 1000] [--seed 0] [--out convModel.pth] [--lr 5e-5] [--eval-every 50]
+                             [--no-long-term] [--resume CKPT] [--report FILE]
+
+Writes a checkpoint {'state_dict', 'optimizer', 'mconf', 'it', ...} that `FluidNet.load_state_dict` takes and
+`examples/plume.py --method convnet --weights` runs.  With --report the loss curve, the held-out ratio divL2(net's U) / divL2(U before
+the projection) and the number of Jacobi sweeps that reach the same held-out divL2 on the same scenes go to FILE as text."""
+import argparse
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from fluidnet_cxx_amd.training import MCONF_DEFAULTS, evaluate, jacobi_divL2, jacobi_sweeps_to_reach, lambdas_of, train      # noqa: E402
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--res", type=int, default=128)
+    ap.add_argument("--batch", type=int, default=64)             # trainConfig.yaml: batchSize
+    ap.add_argument("--iters", type=int, default=1000)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--out", default="convModel.pth")
+    ap.add_argument("--lr", type=float, default=MCONF_DEFAULTS["lr"])
+    ap.add_argument("--eval-every", type=int, default=50)
+    ap.add_argument("--no-long-term", action="store_true", help="divLongTermLambda = 0 (the reference's default is 1)")
+    ap.add_argument("--resume", default=None, metavar="CKPT")
+    ap.add_argument("--report", default=None, metavar="FILE")
+    a = ap.parse_args(argv)
+    mconf = dict(MCONF_DEFAULTS, lr=a.lr)
+    if a.no_long_term:
+        mconf["divLongTermLambda"] = 0.0
+    tconf = dict(res=a.res, batch=a.batch, iters=a.iters, seed=a.seed, evalEvery=a.eval_every)
+    t0 = time.time()
+    run = train(mconf, tconf, torch.device("cuda"), out=a.out, resume=a.resume, log=print)
+    torch.cuda.synchronize()
+    seconds = time.time() - t0
+    lam = lambdas_of(mconf)
+    ev = evaluate(run["net"], run["held_out"], lam)
+    ratio = ev["divL2_out"] / ev["divL2_in"]
+    sweeps = jacobi_sweeps_to_reach(run["held_out"], ev["divL2_out"])
+    lines = [f"examples/train.py --res {a.res} --batch {a.batch} --iters {a.iters} --seed {a.seed} --lr {a.lr:g}"
+             f"{' --no-long-term' if a.no_long_term else ''}: {seconds:.1f} s wall ({seconds / max(a.iters, 1) * 1e3:.1f} ms per iteration, "
+             "sampler, evaluation and checkpoint included)",
+             f"held-out ({len(run['held_out'])} batches of another seed): loss {ev['loss']:.4e}, divL2 of the net's U {ev['divL2_out']:.4e}, "
+             f"divL2 of U before the projection {ev['divL2_in']:.4e}, ratio {ratio:.4e}",
+             f"Jacobi sweeps that reach the same held-out divL2 on the same scenes: {sweeps}"
+             + ("" if sweeps is None else f" (divL2 {jacobi_divL2(run['held_out'], sweeps):.4e}; {max(sweeps - 1, 1)} sweeps: "
+                                          f"{jacobi_divL2(run['held_out'], max(sweeps - 1, 1)):.4e})"),
+             "it  loss  long-term  lr  [held-out loss  divL2 out / in]"]
+    for r in run["history"]:
+        if "val" in r or r["it"] % max(a.eval_every // 5, 1) == 0:
+            lt = "-" if r["lt"] is None else f"{r['lt']:.4e}"
+            val = f"  {r['val']:.4e}  {r['val_divL2_out'] / r['val_divL2_in']:.4e}" if "val" in r else ""
+            lines.append(f"{r['it'] + 1:6d}  {r['loss']:.4e}  {lt}  {r['lr']:.3e}{val}")
+    text = "\n".join(lines)
+    print(text)
+    print(f"checkpoint: {a.out}")
+    if a.report:
+        os.makedirs(os.path.dirname(os.path.abspath(a.report)), exist_ok=True)
+        with open(a.report, "w") as f:
+            f.write(text + "\n")
+    return run
+
+
+if __name__ == "__main__":
+    main()

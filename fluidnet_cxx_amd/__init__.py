@@ -2,6 +2,7 @@
 
     from fluidnet_cxx_amd import fluid, simulate, FluidNet     # mirrors the reference's `lib`
     from fluidnet_cxx_amd import FluidNetTrain                 # the same net with a native backward pass (2D)
+    from fluidnet_cxx_amd.training import train, SceneSampler  # the training loop on scenes generated on the device (2D)
 
 Importing the operator modules loads the native extension; there is no CPU fallback.
 """

@@ -595,6 +595,76 @@ Tensor fluidnet_backward(Tensor packed_t, Tensor flags, Tensor scale, Tensor gra
   return grad;
 }
 
+// ---- training scenes and the training loss (ABI 23; 2D, the C ABI refuses everything else before it touches the device) ----------
+static Tensor check_scene_ids(const Tensor& ids) {
+  TORCH_CHECK(ids.is_cuda() && ids.scalar_type() == at::kInt && ids.dim() == 1 && ids.is_contiguous() && ids.numel() >= 1,
+              "scene_ids must be a contiguous int32 GPU tensor (B)");
+  return ids;
+}
+// -> flags (B,1,depth,H,W)
+Tensor scene_obstacles(Tensor scene_ids, int64_t H, int64_t W, int64_t seed, int n_min, int n_max, double centre_min, double centre_max,
+                       double size_min, double size_max, int64_t depth) {
+  check_scene_ids(scene_ids);
+  FnxGrid g = grid2d(scene_ids.numel(), H, W);
+  g.D = (int)depth; g.is3D = depth > 1;
+  FnxSceneParams prm{};
+  prm.seed = (unsigned)seed; prm.n_min = n_min; prm.n_max = n_max;
+  prm.centre_min = (float)centre_min; prm.centre_max = (float)centre_max; prm.size_min = (float)size_min; prm.size_max = (float)size_max;
+  c10::hip::HIPGuard guard(scene_ids.get_device());
+  TORCH_CHECK(depth >= 1 && H >= 1 && W >= 1, "scene_obstacles: depth, H and W must be positive");
+  Tensor flags = at::empty({g.B, 1, depth, H, W}, scene_ids.options().dtype(at::kFloat));
+  check_status(fnx_scene_obstacles(&g, &prm, scene_ids.data_ptr<int>(), flags.data_ptr<float>(), cur_stream(scene_ids)));
+  return flags;
+}
+// -> U (B,2,depth,H,W), density (B,1,depth,H,W) or None
+std::vector<Tensor> scene_turbulence(Tensor scene_ids, int64_t H, int64_t W, int64_t seed, int octaves, double wavelength, double amplitude,
+                                     double density_scale, bool with_density, int64_t depth) {
+  check_scene_ids(scene_ids);
+  FnxGrid g = grid2d(scene_ids.numel(), H, W);
+  g.D = (int)depth; g.is3D = depth > 1;
+  FnxSceneParams prm{};
+  prm.seed = (unsigned)seed; prm.octaves = octaves; prm.wavelength = (float)wavelength; prm.amplitude = (float)amplitude;
+  prm.density_scale = (float)density_scale;
+  c10::hip::HIPGuard guard(scene_ids.get_device());
+  TORCH_CHECK(depth >= 1 && H >= 1 && W >= 1, "scene_turbulence: depth, H and W must be positive");
+  Tensor U = at::empty({g.B, 2, depth, H, W}, scene_ids.options().dtype(at::kFloat));
+  Tensor rho = with_density ? at::empty({g.B, 1, depth, H, W}, U.options()) : Tensor();
+  check_status(fnx_scene_turbulence(&g, &prm, scene_ids.data_ptr<int>(), U.data_ptr<float>(), with_density ? rho.data_ptr<float>() : nullptr,
+                                    cur_stream(scene_ids)));
+  return {U, rho};
+}
+// fluid_net_train.py:276-285 -> [terms (5: pL2, divL2, pL1, divL1 unweighted, total) or None, grad_p or None, grad_U or None];
+// upstream: a one-element GPU tensor (the gradient of what the total feeds) or None for the terms alone
+std::vector<Tensor> train_loss(Tensor out_p, Tensor out_U, Tensor flags, c10::optional<Tensor> target_p, std::vector<double> lambdas,
+                               c10::optional<Tensor> upstream, bool terms) {
+  check_field(out_U, "out_U");
+  TORCH_CHECK(lambdas.size() == 4, "lambdas must be (pL2, divL2, pL1, divL1)");
+  FnxGrid g = grid_of(flags, out_U.size(1) == 3, nullptr);
+  check_scalar(out_p, g, "out_p");
+  TORCH_CHECK(out_U.size(0) == g.B && out_U.size(2) == g.D && out_U.size(3) == g.H && out_U.size(4) == g.W, "Size mismatch");
+  const bool has_t = target_p.has_value() && target_p->defined();
+  if (has_t) check_scalar(*target_p, g, "target_p");
+  const bool grads = upstream.has_value() && upstream->defined();
+  if (grads)
+    TORCH_CHECK(upstream->is_cuda() && upstream->scalar_type() == at::kFloat && upstream->numel() == 1 && upstream->get_device() == out_p.get_device(),
+                "upstream must be one float32 on the GPU");
+  c10::hip::HIPGuard guard(out_p.get_device());
+  const float lam[4] = {(float)lambdas[0], (float)lambdas[1], (float)lambdas[2], (float)lambdas[3]};
+  Tensor t, gp, gU, ws;
+  size_t bytes = 0;
+  if (terms) {
+    t = at::empty({5}, out_p.options());
+    bytes = (!g.is3D && g.D == 1) ? fnx_train_loss_ws_bytes(&g) : 0;
+    ws = at::empty({(int64_t)(bytes ? bytes : 1)}, out_p.options().dtype(at::kByte));
+  }
+  if (grads) { gp = at::empty_like(out_p); gU = at::empty_like(out_U); }
+  check_status(fnx_train_loss(&g, out_p.data_ptr<float>(), out_U.data_ptr<float>(), flags.data_ptr<float>(),
+                              has_t ? target_p->data_ptr<float>() : nullptr, lam, grads ? upstream->data_ptr<float>() : nullptr,
+                              terms ? t.data_ptr<float>() : nullptr, grads ? gp.data_ptr<float>() : nullptr,
+                              grads ? gU.data_ptr<float>() : nullptr, terms ? ws.data_ptr() : nullptr, bytes, cur_stream(out_p)));
+  return {t, gp, gU};
+}
+
 // one whole step of lib/simulate.py:28-171, in place on p, U, density
 void simulate_step_(Tensor p, Tensor U, Tensor flags, c10::optional<Tensor> density, c10::optional<Tensor> UBC,
                     c10::optional<Tensor> UBCInvMask, c10::optional<Tensor> densityBC,
@@ -1087,6 +1157,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("precision_mode") = "fp32", NoGil());
   m.def("fluidnet_backward", &fluidnet_backward, py::arg("packed_t"), py::arg("flags"), py::arg("scale"), py::arg("grad_p"),
         py::arg("grad_U"), py::arg("tape"), py::arg("precision_mode") = "fp32", NoGil());
+  m.def("scene_obstacles", &scene_obstacles, py::arg("scene_ids"), py::arg("H"), py::arg("W"), py::arg("seed"), py::arg("n_min"), py::arg("n_max"),
+        py::arg("centre_min"), py::arg("centre_max"), py::arg("size_min"), py::arg("size_max"), py::arg("depth") = 1, NoGil());
+  m.def("scene_turbulence", &scene_turbulence, py::arg("scene_ids"), py::arg("H"), py::arg("W"), py::arg("seed"), py::arg("octaves"),
+        py::arg("wavelength"), py::arg("amplitude"), py::arg("density_scale"), py::arg("with_density") = true, py::arg("depth") = 1, NoGil());
+  m.def("train_loss", &train_loss, py::arg("out_p"), py::arg("out_U"), py::arg("flags"), py::arg("target_p"), py::arg("lambdas"),
+        py::arg("upstream") = py::none(), py::arg("terms") = true, NoGil());
   m.def("abi_version", &fnx_abi_version);
   m.def("profile_enable", [](bool on, bool runs) { fnx_profile_enable(on ? (runs ? 2 : 1) : 0); }, py::arg("on"), py::arg("runs") = false);
   m.def("roctx_enable", [](bool on) { check_status(fnx_roctx_enable(on ? 1 : 0)); });

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define FNX_ABI_VERSION 22
+#define FNX_ABI_VERSION 23
 
 enum {
   FNX_OK = 0,
@@ -658,6 +658,56 @@ int fnx_fluidnet_forward_train(const FnxGrid* g, const void* packed, const float
 int fnx_fluidnet_backward(const FnxGrid* g, const void* packed_t, const float* flags, const float* scale, const float* grad_p,
                           const float* grad_U, const float* tape, float* grad_blob, int precision_mode, void* ws, size_t ws_bytes,
                           void* stream);
+
+/* ---- Training scenes and the training loss (ABI 23; the reference trains on a pre-computed Mantaflow data set and composes its loss
+ * from ATen operators, fluid_net_train.py:276-285).  2D only, like the training entry points above; every entry point checks before it
+ * touches the device: null arguments, a 2D grid, H and W of at least 4 (and at most 32768, B at most 65535), and what is said per call.
+ *
+ * Randomness is counter based, without state or atomics: a 32-bit word is
+ *   hash(seed, scene, stream, counter) = mix(mix(mix(mix(seed + 0x9e3779b9) ^ scene) ^ stream) ^ counter)
+ *   mix(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16      (the "lowbias32" finaliser)
+ * and a uniform float is (hash >> 8) * 2^-24.  The bits of a scene depend on (seed, scene id, H, W) and the parameters only: not on the
+ * batch slot, the batch size or the launch geometry.  Arithmetic: integer operations, fp32 add / subtract / multiply / compare and
+ * int <-> float conversion, uncontracted, in the order tests/scene_reference.py states in numpy -- the kernels are bit-identical to it. */
+#define FNX_SCENE_MAX_PRIMITIVES 16   /* the cap on n_max */
+#define FNX_SCENE_MAX_OCTAVES 8
+typedef struct FnxSceneParams {
+  unsigned seed;
+  /* obstacles: n_min .. n_max primitives per scene (0 <= n_min <= n_max <= FNX_SCENE_MAX_PRIMITIVES), each a disc or an axis-aligned box
+   * by one hash bit; the centre is the grid centre ((W - 1) / 2, (H - 1) / 2) + an offset drawn per axis in [centre_min, centre_max] *
+   * min(H, W); the radius (disc) or the two half extents (box) are drawn in [size_min, size_max] * min(H, W).  A cell centre (i, j)
+   * is inside on squared distances: dx^2 + dy^2 <= r^2, resp. dx^2 <= a^2 and dy^2 <= b^2. */
+  int n_min, n_max;
+  float centre_min, centre_max;
+  float size_min, size_max;
+  /* turbulence: psi(node) = amplitude * sum_{o < octaves} 2^-o noise_o(node / (wavelength 2^-o)); noise_o is value noise on the integer
+   * lattice (values 2 uniform - 1 from stream 16 + o, blended with the smoothstep t t (3 - 2 t)); 1 <= octaves <= FNX_SCENE_MAX_OCTAVES,
+   * wavelength (cells) >= 2^(octaves - 1).  density = clamp(density_scale * the same sum on the streams 32 + o at the cell, 0, 1). */
+  int octaves;
+  float wavelength, amplitude, density_scale;
+} FnxSceneParams;
+/* scene_ids: B DEVICE ints.  flags (B,1,1,H,W) = emptyDomain (border ring TypeObstacle, interior TypeFluid) united with the scene's
+ * primitives.  Refuses n_max above the cap and inverted ranges. */
+int fnx_scene_obstacles(const FnxGrid* g, const FnxSceneParams* prm, const int* scene_ids, float* flags, void* stream);
+/* U (B,2,1,H,W) = the discrete curl of psi on the grid nodes: U0(i,j) = psi(i,j+1) - psi(i,j), U1(i,j) = -(psi(i+1,j) - psi(i,j)):
+ * divergence-free up to the rounding of the four differences, before any boundary condition.  density (B,1,1,H,W) may be NULL. */
+int fnx_scene_turbulence(const FnxGrid* g, const FnxSceneParams* prm, const int* scene_ids, float* U, float* density, void* stream);
+
+/* The loss of fluid_net_train.py:276-285 and its gradient.  div = fnx_velocity_divergence(out_U, flags), bit for bit (0 on the border
+ * ring and in obstacles), N = B H W:
+ *   terms[0..3] = mean (out_p - target_p)^2, mean div^2, mean |out_p - target_p|, mean |div|      (nn.MSELoss / nn.L1Loss, unweighted)
+ *   terms[4]    = lambdas . terms[0..3]                                   lambdas = (pL2, divL2, pL1, divL1), 4 HOST floats
+ *   grad_p      = upstream (2 pL2 (out_p - target_p) + pL1 sign(out_p - target_p)) / N;  exactly 0 when both pressure lambdas are 0
+ *   grad_U      = the stencil of fnx_velocity_divergence_backward on upstream (2 divL2 div + divL1 sign(div)) / N, formed per face from
+ *                 the face's two cells (div is never stored); sign(0) = 0, torch's subgradient
+ * upstream: 1 DEVICE float (the gradient of whatever the total feeds).  target_p may be NULL when both pressure lambdas are 0 (the two
+ * pressure terms are then 0); with one of them set a NULL target is refused.  terms (5 DEVICE floats) may be NULL (gradients only: ws
+ * unused), or grad_p, grad_U and upstream may all be NULL (terms only).  The sums are fp64 partials per workgroup in ws
+ * (fnx_train_loss_ws_bytes) added in index order by a second, one-workgroup launch: two calls give the same bits. */
+size_t fnx_train_loss_ws_bytes(const FnxGrid* g);
+int fnx_train_loss(const FnxGrid* g, const float* out_p, const float* out_U, const float* flags, const float* target_p,
+                   const float lambdas[4], const float* upstream, float* terms, float* grad_p, float* grad_U, void* ws, size_t ws_bytes,
+                   void* stream);
 
 /* Optional timing of the dominant kernels with HIP events on the launch stream (used by bench.py for the roofline
  * figures).  While enabled, every launch of the tagged kernel class is bracketed by an event pair (up to 16384 pairs,
