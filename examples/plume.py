@@ -2,13 +2,16 @@
 """The reference's `pytorch/plume.py` main loop on this backend -- what a driver looks like after the switch.
 
     python examples/plume.py [--res 128] [--iters 200] [--out-iter 50] [--method jacobi|pcg|convnet] [--weights CKPT] [--vorticity AMP]
-                             [--folder out] [--restart]
+                             [--depth N] [--render] [--folder out] [--restart]
 
 Same structure as the reference driver (plume.py:66-178 setup, :231-424 loop): build the batch, `createPlumeBCs`, optional
 restart from `<folder>/restart.pth`, echo the configuration as YAML, then `simulate()` per iteration and, every `out-iter`
 iterations, the PNG panels, the VTK cell data and the restart file.  Only the import line differs from a reference-side
 driver: `lib` -> `fluidnet_cxx_amd`.  `--method convnet --weights CKPT` projects with a trained net: CKPT is what examples/train.py
-writes ({'state_dict', 'mconf', ...}), loaded the way the reference driver loads convModel_lastEpoch_best.pth (plume.py:119-123)."""
+writes ({'state_dict', 'mconf', ...}), loaded the way the reference driver loads convModel_lastEpoch_best.pth (plume.py:119-123).
+`--depth N` (N > 1) runs the 3D plume on a N x res x res grid (jacobi, pcg and --vorticity as in 2D; there are no 3D weights, so not
+convnet); `--render` adds volume renderings of the density (output.save_render: from the front, lit from above, and from the side)
+to every output event."""
 import argparse
 import os
 import sys
@@ -19,7 +22,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from fluidnet_cxx_amd import fluid, simulate, output, load_restart, FluidNet      # noqa: E402   (reference: `import lib, lib.fluid as fluid`)
 
 
-def main(argv=None):
+RENDER_VIEWS = (("-z", "-y"), ("+x", "-y"))               # (view, light): from the front and from the side, lit from above
+
+
+def parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--res", type=int, default=128)
     ap.add_argument("--iters", type=int, default=200)
@@ -28,11 +34,27 @@ def main(argv=None):
     ap.add_argument("--weights", default=None, metavar="CKPT", help="checkpoint of examples/train.py (needed by --method convnet)")
     ap.add_argument("--vorticity", type=float, default=0.0, metavar="AMP",
                     help="vorticity confinement amplitude (mconf['vorticityConfinementAmp'], no reference key; 0 = off)")
+    ap.add_argument("--depth", type=int, default=1, metavar="N", help="cells along z; 1 (default) is the 2D plume, N > 1 the 3D one")
+    ap.add_argument("--render", action="store_true", help="write volume renderings (render_<view>_<it>.png) with every output event")
     ap.add_argument("--folder", default="plume_out")
     ap.add_argument("--restart", action="store_true")
+    return ap
+
+
+def parse_args(argv=None):
+    ap = parser()
     a = ap.parse_args(argv)
+    if a.depth < 1 or a.depth == 2:
+        ap.error("--depth must be 1 (2D) or at least 3")
+    if a.method == "convnet" and a.depth > 1:
+        ap.error("--method convnet with --depth > 1: no 3D weights can be trained here (examples/train.py trains the 2D net only)")
     if (a.method == "convnet") != (a.weights is not None):
         ap.error("--method convnet needs --weights CKPT, and --weights is only read by --method convnet")
+    return a
+
+
+def main(argv=None):
+    a = parse_args(argv)
     cuda = torch.device("cuda")
     # plumeConfig.yaml:29-76 (the keys simulate() reads)
     simConf = dict(dt=0.1, maccormackStrength=0.6, sampleOutsideFluid=False, buoyancyScale=0.25, gravityScale=0, viscosity=0,
@@ -53,11 +75,12 @@ def main(argv=None):
         simConf.update(normalizeInputThreshold=mconf.get("normalizeInputThreshold", 1e-5))
     os.makedirs(a.folder, exist_ok=True)
     resX = resY = a.res
+    resZ = a.depth
     # plume.py:131-163
-    p = torch.zeros(1, 1, 1, resY, resX, dtype=torch.float, device=cuda)
-    U = torch.zeros(1, 2, 1, resY, resX, dtype=torch.float, device=cuda)
-    flags = torch.zeros(1, 1, 1, resY, resX, dtype=torch.float, device=cuda)
-    density = torch.zeros(1, 1, 1, resY, resX, dtype=torch.float, device=cuda)
+    p = torch.zeros(1, 1, resZ, resY, resX, dtype=torch.float, device=cuda)
+    U = torch.zeros(1, 3 if resZ > 1 else 2, resZ, resY, resX, dtype=torch.float, device=cuda)
+    flags = torch.zeros(1, 1, resZ, resY, resX, dtype=torch.float, device=cuda)
+    density = torch.zeros(1, 1, resZ, resY, resX, dtype=torch.float, device=cuda)
     fluid.emptyDomain(flags)
     batch_dict = dict(p=p, U=U, flags=flags, density=density)
     fluid.createPlumeBCs(batch_dict, 0.1, 2, 0.145)
@@ -72,7 +95,7 @@ def main(argv=None):
         simulate(simConf, batch_dict, net, a.method)
         if it % a.out_iter == 0:
             print("It = " + str(it))
-            output.save_state(a.folder, it, batch_dict)
+            output.save_state(a.folder, it, batch_dict, render=RENDER_VIEWS if a.render else None)
         it += 1
     return batch_dict, it
 

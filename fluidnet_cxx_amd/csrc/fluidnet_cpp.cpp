@@ -282,6 +282,32 @@ Tensor add_vorticity_confinement(Tensor U, Tensor flags, double strength, const 
   return out;
 }
 
+// volume rendering (fnx_render_volume): density (B,1,D,H,W) + flags -> image (B,2,R,Cc); directions 0..5 = +x -x +y -y +z -z.
+// 1 - ambient is formed here, once, in fp32 (the kernels and tests/render_reference.py take it as given)
+Tensor render_volume(Tensor density, Tensor flags, int view_dir, int light_dir, double k_view, double k_light, double ambient,
+                     double albedo_smoke, double albedo_obstacle, int bnd) {
+  check_field(density, "density");
+  FnxGrid g = grid_of(flags, flags.size(2) > 1, nullptr);
+  check_scalar(density, g, "density");
+  TORCH_CHECK(density.get_device() == flags.get_device(), "density and flags are on different devices");
+  FnxRenderParams prm{};
+  prm.view_dir = view_dir; prm.light_dir = light_dir;
+  prm.k_view = (float)k_view; prm.k_light = (float)k_light;
+  prm.ambient = (float)ambient; prm.one_minus_ambient = 1.f - prm.ambient;
+  prm.albedo_smoke = (float)albedo_smoke; prm.albedo_obstacle = (float)albedo_obstacle;
+  prm.bnd = bnd;
+  TORCH_CHECK(view_dir >= 0 && view_dir <= 5 && light_dir >= 0 && light_dir <= 5, "renderVolume: direction outside 0..5");
+  c10::hip::HIPGuard guard(flags.get_device());
+  const int va = view_dir >> 1;
+  const int64_t R = va == 2 ? g.H : g.D, Cc = va == 0 ? g.H : g.W;
+  Tensor image = at::empty({(int64_t)g.B, 2, R, Cc}, density.options());
+  const size_t bytes = fnx_render_volume_ws_bytes(&g, &prm);
+  Tensor ws = at::empty({(int64_t)(bytes ? bytes : 1)}, density.options().dtype(at::kByte));
+  check_status(fnx_render_volume(&g, density.data_ptr<float>(), flags.data_ptr<float>(), &prm, image.data_ptr<float>(),
+                                 bytes ? ws.data_ptr() : nullptr, bytes, cur_stream(density)));
+  return image;
+}
+
 // correctScalar (cpp/advection.py:9-12), in place on src
 void correct_scalar_(double dt, Tensor src, Tensor div, Tensor flags) {
   check_field(src, "src"); check_field(flags, "flags");
@@ -1027,6 +1053,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("add_viscosity_", &add_viscosity_, NoGil());
   m.def("add_vorticity_confinement", &add_vorticity_confinement, py::arg("U"), py::arg("flags"), py::arg("strength"), GEOM, NoGil());
   m.def("add_vorticity_confinement_", &add_vorticity_confinement_, py::arg("U"), py::arg("flags"), py::arg("strength"), GEOM, NoGil());
+  m.def("render_volume", &render_volume, "density + flags -> (B,2,R,Cc) radiance / transmittance image (fnx_render_volume)", py::arg("density"),
+        py::arg("flags"), py::arg("view_dir"), py::arg("light_dir"), py::arg("k_view"), py::arg("k_light"), py::arg("ambient") = 0.25,
+        py::arg("albedo_smoke") = 1.0, py::arg("albedo_obstacle") = 0.5, py::arg("bnd") = 1, NoGil());
   m.def("set_wall_bcs_", &set_wall_bcs_, py::arg("U"), py::arg("flags"), GEOM, NoGil());
   m.def("set_wall_bcs_stick_", &set_wall_bcs_stick_, NoGil());
   m.def("set_const_vals_", &set_const_vals_, NoGil());

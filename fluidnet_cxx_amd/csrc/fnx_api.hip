@@ -738,6 +738,41 @@ int fnx_add_vorticity_confinement(const FnxGrid* g, const float* U_in, float* U_
   return FNX_OK;
 }
 
+namespace {
+int check_render(const FnxGrid* g, const FnxRenderParams* prm) {
+  if (!prm) return fail(FNX_EINVAL, "render_volume: NULL parameters");
+  if (int rc = check_grid(g)) return rc;
+  if (g->k_begin != 0 || g->k_end != 0 || g->z_offset != 0 || g->D_global != 0)
+    return fail(FNX_EINVAL, "render_volume: no compute window or z-slab view (whole grids only)");
+  if (prm->view_dir < 0 || prm->view_dir > 5 || prm->light_dir < 0 || prm->light_dir > 5)
+    return fail(FNX_EINVAL, "render_volume: direction outside 0..5 (view_dir=%d light_dir=%d)", prm->view_dir, prm->light_dir);
+  if (prm->bnd < 0) return fail(FNX_EINVAL, "render_volume: bnd < 0 (%d)", prm->bnd);
+  const float k[2] = {prm->k_view, prm->k_light};
+  for (float v : k)
+    if (!(v >= 0.f) || !(v - v == 0.f))
+      return fail(FNX_EINVAL, "render_volume: absorption must be finite and not negative (k_view=%g k_light=%g)", prm->k_view, prm->k_light);
+  return FNX_OK;
+}
+}  // namespace
+
+size_t fnx_render_volume_ws_bytes(const FnxGrid* g, const FnxRenderParams* prm) {
+  if (check_render(g, prm) != FNX_OK) return 0;
+  return prm->view_dir == prm->light_dir ? 0 : al(ncell(g) * 4);
+}
+
+int fnx_render_volume(const FnxGrid* g, const float* density, const float* flags, const FnxRenderParams* prm, float* image,
+                      void* ws, size_t ws_bytes, void* stream) {
+  if (!density || !flags || !image) return fail(FNX_EINVAL, "render_volume: NULL tensor");
+  if (int rc = check_render(g, prm)) return rc;
+  const size_t need = prm->view_dir == prm->light_dir ? 0 : al(ncell(g) * 4);
+  if (need && (!ws || ws_bytes < need)) return fail(FNX_EINVAL, "render_volume: workspace too small (%zu < %zu)", ws ? ws_bytes : (size_t)0, need);
+  const fnx::RenderConsts c = {prm->k_view, prm->k_light, prm->ambient, prm->one_minus_ambient, prm->albedo_smoke, prm->albedo_obstacle,
+                               prm->bnd};
+  fnx::launch_render_volume(dims(g), prm->view_dir, prm->light_dir, c, density, flags, (float*)ws, image, (hipStream_t)stream);
+  HIP_OK(hipGetLastError());
+  return FNX_OK;
+}
+
 int fnx_add_buoyancy(const FnxGrid* g, float* U, const float* flags, const float* density, const float gravity[3],
                      float rho_star, float dt, void* stream) {
   if (int rc = check_grid(g)) return rc;

@@ -97,6 +97,12 @@ void launch_bc_classify(const GridDims& g, bool is3d, const float* UBC, const fl
 void launch_vorticity_confinement(const GridDims& g, bool is3d, const float* U_in, const float* flags, float* U_out, float amp,
                                   hipStream_t s);
 
+// volume rendering (fnx_render.hip): density + flags -> image (B, 2, R, Cc), channel 0 radiance, channel 1 transmittance.  Directions
+// 0..5 = +x -x +y -y +z -z (the way rays / light travel).  Lws: B*D*H*W floats, unused (may be NULL) when view_dir == light_dir.
+struct RenderConsts { float k_view, k_light, ambient, one_minus_ambient, albedo_smoke, albedo_obstacle; int bnd; };
+void launch_render_volume(const GridDims& g, int view_dir, int light_dir, const RenderConsts& c, const float* density, const float* flags,
+                          float* Lws, float* image, hipStream_t s);
+
 // Jacobi (fnx_jacobi.hip)
 // 2D: `nsweeps` sweeps (1..jacobi_max_sweeps_per_launch) from p_in into p_out; from_zero: p_in is all zeros and is not read
 void launch_jacobi(const GridDims& g, const float* flags, const float* div, const float* p_in, float* p_out, int nsweeps,

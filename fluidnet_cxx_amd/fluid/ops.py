@@ -220,6 +220,32 @@ def addVorticityConfinement(U, flags, strength, *, geom=None):
     return U
 
 
+RENDER_DIRECTIONS = ("+x", "-x", "+y", "-y", "+z", "-z")     # the way rays / light travel; the codes of FnxRenderParams
+
+
+def renderVolume(density, flags, view="-z", light="-y", *, absorption=None, light_absorption=None, ambient=0.25, albedo_smoke=1.0,
+                 albedo_obstacle=0.5, bnd=1):
+    """Volume rendering (no reference counterpart; include/fluidnet_hip.h: fnx_render_volume): density (B,1,D,H,W) with the obstacles
+    of flags -> (B,2,R,Cc) float32, channel 0 the radiance towards the viewer, channel 1 the transmittance left for a background.
+    Orthographic along `view`, single scattering with self-shadowing from `light`; both are one of '+x' '-x' '+y' '-y' '+z' '-z', the
+    way the rays or the light TRAVEL (x = W, y = H, z = D), and independent of each other.  Rows and columns are the two axes the
+    view does not travel along, in (z, y, x) order, index 0 = coordinate 0.  `absorption` / `light_absorption`: extinction per cell
+    of density 1 along the view / the light (default 16 / cells along that axis).  Cells within `bnd` of a domain face count as empty
+    (emptyDomain's wall would hide everything).  Neither input is written."""
+    _check5(density, flags)
+    assert flags.size(1) == 1, "flags is not scalar"
+    assert density.shape == flags.shape, "size mismatch"
+    assert density.dtype == torch.float32 and flags.dtype == torch.float32, "density and flags must be float32"
+    assert density.is_cuda and flags.is_cuda, "density and flags must be on the GPU"
+    assert view in RENDER_DIRECTIONS and light in RENDER_DIRECTIONS, "view / light must be one of " + " ".join(RENDER_DIRECTIONS)
+    assert int(bnd) >= 0, "bnd < 0"
+    v, l = RENDER_DIRECTIONS.index(view), RENDER_DIRECTIONS.index(light)
+    cells = lambda d: density.size(4 - (d >> 1))                          # noqa: E731   (x: W, y: H, z: D)
+    k_view = 16.0 / cells(v) if absorption is None else float(absorption)
+    k_light = 16.0 / cells(l) if light_absorption is None else float(light_absorption)
+    return ext.render_volume(density, flags, v, l, k_view, k_light, float(ambient), float(albedo_smoke), float(albedo_obstacle), int(bnd))
+
+
 def setWallBcs(U, flags, *, geom=None):
     """lib/fluid/set_wall_bcs.py:4-86 -- in place on U, returns U (differentiable w.r.t. U)."""
     _check5(U, flags)

@@ -231,14 +231,34 @@ def save_png(folder, it, batch_dict, window=None, plane=None):
     return write_png(os.path.join(folder, "output_{0:05}.png".format(it)), canvas)
 
 
-def save_state(folder, it, batch_dict, window=None, vtk=True, png=True, restart=True):
-    """One output event of the driver loop (plume.py:238-424): PNG, VTK and the restart file."""
+def render_image(batch_dict, view="-z", light="-y", background=1.0, **kw):
+    """Volume rendering of sample 0 (fluid.renderVolume: orthographic along `view`, self-shadowed by `light`, both one of '+x' ...
+    '-z') over a uniform background: radiance + transmittance * background, clipped to [0, 1], as (R, Cc, 3) uint8 grey with row 0
+    at the bottom like `colorize`.  2D states render too (views along x or y give a single row).  **kw goes to renderVolume."""
+    img = fluid.renderVolume(batch_dict["density"][0:1].contiguous(), batch_dict["flags"][0:1].contiguous(), view, light, **kw)
+    a = img[0].cpu().numpy()
+    grey = np.clip(a[0] + a[1] * np.float32(background), 0.0, 1.0)
+    g8 = (grey * 255.0 + 0.5).astype(np.uint8)
+    return np.ascontiguousarray(np.repeat(g8[::-1, :, None], 3, axis=2))
+
+
+def save_render(folder, it, batch_dict, views=(("-z", "-y"),), **kw):
+    """`<folder>/render_<view>_<it:05>.png` per (view, light) pair of `views`; returns the file names."""
+    return [write_png(os.path.join(folder, "render_{0}_{1:05}.png".format(view, it)), render_image(batch_dict, view, light, **kw))
+            for view, light in views]
+
+
+def save_state(folder, it, batch_dict, window=None, vtk=True, png=True, restart=True, render=None):
+    """One output event of the driver loop (plume.py:238-424): PNG, VTK and the restart file.  `render`: (view, light) pairs for
+    `save_render` (default: no rendering, and the files and the returned list are what they were without the keyword)."""
     from .state_io import save_restart
     files = []
     if png:
         files.append(save_png(folder, it, batch_dict, window))
     if vtk:
         files.append(save_vtk(folder, it, batch_dict, window))
+    if render:
+        files += save_render(folder, it, batch_dict, render)
     if restart:
         rf = os.path.join(folder, "restart.pth")
         save_restart(rf, batch_dict, it)

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define FNX_ABI_VERSION 23
+#define FNX_ABI_VERSION 24
 
 enum {
   FNX_OK = 0,
@@ -244,6 +244,32 @@ int fnx_add_viscosity(const FnxGrid* g, float dt, const float* U_in, float* U_ou
  * buffer.  Whole grids only (no compute window, no z-slab view).  amp == 0 copies U_in. */
 int fnx_add_vorticity_confinement(const FnxGrid* g, const float* U_in, float* U_out, const float* flags, float amp,
                                   void* stream);
+
+/* Volume rendering (ABI 24; no reference counterpart): a density grid with its obstacles -> an image.  Axis-aligned and orthographic,
+ * single scattering with self-shadowing from an axis-aligned light.  Axes x = W, y = H, z = D; a direction is the way rays or light
+ * TRAVEL, 0..5 = +x -x +y -y +z -z; view_dir and light_dir are independent (equal: a headlight, opposite: backlit).
+ * Per cell, fp32 add / subtract / multiply / compare in exactly this order (tests/render_reference.py is the same in numpy):
+ *   rho = min(max(density, 0), 1);  obs = flags == FNX_TYPE_OBSTACLE
+ *   a cell within bnd cells of a domain face is empty in both passes (not an obstacle, rho = 0); a 2D grid (D == 1) has no z faces
+ *   light pass along light_dir, Lin = 1 before the first cell:  L[cell] = Lin;  Lin = obs ? 0 : Lin * (1 - min(k_light * rho, 1))
+ *   view pass along view_dir, T = 1, C = 0:                     s = ambient + one_minus_ambient * L[cell]
+ *     obs:   C = C + T * (albedo_obstacle * s);  T = 0
+ *     else:  a = min(k_view * rho, 1);  C = C + (T * a) * (albedo_smoke * s);  T = T * (1 - a)
+ * image: (B, 2, R, Cc) floats, channel 0 = C (radiance), channel 1 = T (what is left of the background).  Rows and columns are the two
+ * axes the view does not travel along, in (z, y, x) order -- view along z: (y, x), along y: (z, x), along x: (z, y) -- index 0 is
+ * coordinate 0, nothing is mirrored for the negative directions.
+ * ws: fnx_render_volume_ws_bytes() bytes (L, one float per cell); 0 when view_dir == light_dir, which runs as one march with no L in
+ * memory.  density and flags are only read.  Everything is launched on `stream`, nothing synchronises.  Whole grids only (no compute
+ * window, no z-slab view). */
+typedef struct FnxRenderParams {
+  int view_dir, light_dir;      /* 0..5: +x -x +y -y +z -z */
+  float k_view, k_light;        /* absorption per cell of rho = 1 */
+  float ambient, one_minus_ambient, albedo_smoke, albedo_obstacle;
+  int bnd;
+} FnxRenderParams;
+size_t fnx_render_volume_ws_bytes(const FnxGrid* g, const FnxRenderParams* prm);   /* 0 also for a grid or params that are refused */
+int fnx_render_volume(const FnxGrid* g, const float* density, const float* flags, const FnxRenderParams* prm, float* image,
+                      void* ws, size_t ws_bytes, void* stream);
 
 /* setWallBcs (in place on U), lib/fluid/set_wall_bcs.py:4-86 */
 int fnx_set_wall_bcs(const FnxGrid* g, float* U, const float* flags, void* stream);
