@@ -621,6 +621,141 @@ Tensor fluidnet_backward(Tensor packed_t, Tensor flags, Tensor scale, Tensor gra
   return grad;
 }
 
+// ---- training of the 3D net (fnx_cnn_train3d.hip) ---------------------------------------------------------
+Tensor scalenet3d_pack_t(Tensor blob) {
+  TORCH_CHECK(blob.is_cuda() && blob.scalar_type() == at::kFloat && blob.is_contiguous(), "weights blob must be a contiguous float32 GPU tensor");
+  TORCH_CHECK((size_t)blob.numel() == fnx_scalenet_weight_floats(1), "weights blob has ", blob.numel(), " floats, expected ",
+              fnx_scalenet_weight_floats(1), " (the 3D net)");
+  c10::hip::HIPGuard guard(blob.get_device());
+  Tensor packed = at::zeros({(int64_t)fnx_scalenet3d_packed_t_bytes()}, blob.options().dtype(at::kByte));
+  check_status(fnx_scalenet3d_pack_t(blob.data_ptr<float>(), packed.data_ptr(), cur_stream(blob)));
+  return packed;
+}
+
+static void check_image3d(const Tensor& t, const char* what, const Tensor& like) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.get_device() == like.get_device(), what, " must be a contiguous weight image on the input's device");
+}
+static FnxGrid grid3d(int64_t B, int64_t D, int64_t H, int64_t W) {
+  FnxGrid g{}; g.B = (int)B; g.D = (int)D; g.H = (int)H; g.W = (int)W; g.is3D = 1;
+  return g;
+}
+// a (B,C,D,H,W) tensor of the 3D net; a (B,C,H,W) one or a single plane is 2D, which the C ABI refuses ("3D only")
+static FnxGrid grid_of_net3d_tensor(const Tensor& x, const char* what) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.is_contiguous(), what, " must be a contiguous float32 GPU tensor");
+  TORCH_CHECK(x.dim() == 4 || x.dim() == 5, what, " must be (B,C,D,H,W)");
+  if (x.dim() == 4) { FnxGrid g = grid2d(x.size(0), x.size(2), x.size(3)); return g; }
+  FnxGrid g = grid3d(x.size(0), x.size(2), x.size(3), x.size(4));
+  if (g.D == 1) g.is3D = 0;
+  return g;
+}
+
+std::vector<py::tuple> multiscale3d_tape_layout(int64_t B, int64_t D, int64_t H, int64_t W) {
+  const FnxGrid g = grid3d(B, D, H, W);
+  std::vector<FnxTapeEntry3D> e(fnx_multiscale_tape_entries());
+  if (fnx_multiscale3d_tape_layout(&g, e.data()) == 0) check_status(FNX_EINVAL);
+  std::vector<py::tuple> out;
+  for (const FnxTapeEntry3D& t : e) out.push_back(py::make_tuple(std::string(t.name), (int64_t)t.offset, t.C, t.D, t.H, t.W));
+  return out;
+}
+
+// gd (B,1,Do,Ho,Wo) -> gs (B,1,Di,Hi,Wi): fnx_trilinear_upsample_backward
+Tensor trilinear_upsample_backward(Tensor gd, std::vector<int64_t> size) {
+  TORCH_CHECK(gd.is_cuda() && gd.scalar_type() == at::kFloat && gd.is_contiguous() && gd.dim() == 5 && gd.size(1) == 1,
+              "grad_dst must be a contiguous float32 GPU tensor (B,1,Do,Ho,Wo)");
+  TORCH_CHECK(size.size() == 3 && size[0] >= 1 && size[1] >= 1 && size[2] >= 1, "size: the source's (Di,Hi,Wi)");
+  c10::hip::HIPGuard guard(gd.get_device());
+  Tensor gs = at::empty({gd.size(0), 1, size[0], size[1], size[2]}, gd.options());
+  check_status(fnx_trilinear_upsample_backward((int)gd.size(0), (int)size[0], (int)size[1], (int)size[2], (int)gd.size(2), (int)gd.size(3),
+                                               (int)gd.size(4), gd.data_ptr<float>(), gs.data_ptr<float>(), cur_stream(gd)));
+  return gs;
+}
+
+std::vector<Tensor> multiscale3d_forward_train(Tensor packed, Tensor x, const std::string& precision_mode) {
+  const FnxGrid g = grid_of_net3d_tensor(x, "x");
+  TORCH_CHECK(x.size(1) == 2, "x must have 2 channels");
+  check_image3d(packed, "packed", x);
+  c10::hip::HIPGuard guard(x.get_device());
+  std::vector<int64_t> osz = x.sizes().vec(); osz[1] = 1;
+  Tensor p = at::empty(osz, x.options());
+  // (a grid the C ABI refuses gets a token tape: the call below raises before it reads anything)
+  const bool ok = g.is3D && g.D >= 4 && g.H >= 4 && g.W >= 4;
+  const size_t floats = ok ? fnx_multiscale3d_tape_layout(&g, nullptr) : 0;
+  Tensor tape = at::empty({(int64_t)(floats ? floats : 1)}, x.options());
+  check_status(fnx_multiscale3d_forward_train(&g, packed.data_ptr(), (size_t)packed.nbytes(), x.data_ptr<float>(), p.data_ptr<float>(),
+                                              tape.data_ptr<float>(), precision_of(precision_mode), cur_stream(x)));
+  return {p, tape};
+}
+
+static Tensor multiscale3d_backward_impl(Tensor packed_t, Tensor grad_p, Tensor tape, const std::string& precision_mode, bool plain) {
+  const FnxGrid g = grid_of_net3d_tensor(grad_p, "grad_p");
+  check_image3d(packed_t, "packed3d_t", grad_p);
+  TORCH_CHECK(grad_p.size(1) == 1, "grad_p must have 1 channel");
+  TORCH_CHECK(tape.is_cuda() && tape.scalar_type() == at::kFloat && tape.is_contiguous(), "tape must be a contiguous float32 GPU tensor");
+  const bool ok = g.is3D && g.D >= 4 && g.H >= 4 && g.W >= 4;
+  const size_t floats = ok ? fnx_multiscale3d_tape_layout(&g, nullptr) : 0;
+  TORCH_CHECK(!floats || (size_t)tape.numel() == floats, "tape has ", tape.numel(), " floats, not the layout of this grid");
+  c10::hip::HIPGuard guard(grad_p.get_device());
+  Tensor grad = at::empty({(int64_t)fnx_scalenet_weight_floats(1)}, grad_p.options());
+  const size_t bytes = floats ? fnx_multiscale3d_backward_ws_bytes(&g) : 1;
+  Tensor ws = at::empty({(int64_t)bytes}, grad_p.options().dtype(at::kByte));
+  check_status((plain ? fnx_multiscale3d_backward_plain : fnx_multiscale3d_backward)(
+      &g, packed_t.data_ptr(), (size_t)packed_t.nbytes(), grad_p.data_ptr<float>(), tape.data_ptr<float>(), grad.data_ptr<float>(),
+      precision_of(precision_mode), ws.data_ptr(), bytes, cur_stream(grad_p)));
+  return grad;
+}
+Tensor multiscale3d_backward(Tensor packed_t, Tensor grad_p, Tensor tape, const std::string& precision_mode) {
+  return multiscale3d_backward_impl(packed_t, grad_p, tape, precision_mode, false);
+}
+// the plain weight-gradient kernel for every layer (fnx_multiscale3d_backward_plain): a cross-check, not a training path
+Tensor multiscale3d_backward_plain(Tensor packed_t, Tensor grad_p, Tensor tape, const std::string& precision_mode) {
+  return multiscale3d_backward_impl(packed_t, grad_p, tape, precision_mode, true);
+}
+
+// -> p, U, tape, s (B), flags (B,1,D,H,W)
+std::vector<Tensor> fluidnet3d_forward_train(Tensor packed, Tensor input, double normalize_threshold, const std::string& precision_mode) {
+  check_field(input, "input");
+  TORCH_CHECK(input.size(1) == 5 || input.size(1) == 6, "input must have 6 channels [p, Ux, Uy, Uz, flags, density] (5: a 2D input, which is refused)");
+  FnxGrid g = grid3d(input.size(0), input.size(2), input.size(3), input.size(4));
+  g.is3D = input.size(1) == 6;
+  check_image3d(packed, "packed", input);
+  c10::hip::HIPGuard guard(input.get_device());
+  const bool ok = g.is3D && g.D >= 4 && g.H >= 4 && g.W >= 4;
+  Tensor p = at::empty({g.B, 1, g.D, g.H, g.W}, input.options());
+  Tensor U = at::empty({g.B, g.is3D ? 3 : 2, g.D, g.H, g.W}, input.options());
+  Tensor flags = at::empty({g.B, 1, g.D, g.H, g.W}, input.options());
+  Tensor scale = at::empty({g.B}, input.options());
+  const size_t floats = ok ? fnx_multiscale3d_tape_layout(&g, nullptr) : 0, bytes = floats ? fnx_fluidnet3d_train_ws_bytes(&g) : 1;
+  Tensor tape = at::empty({(int64_t)(floats ? floats : 1)}, input.options());
+  Tensor ws = at::empty({(int64_t)bytes}, input.options().dtype(at::kByte));
+  check_status(fnx_fluidnet3d_forward_train(&g, packed.data_ptr(), (size_t)packed.nbytes(), input.data_ptr<float>(), (float)normalize_threshold,
+                                            p.data_ptr<float>(), U.data_ptr<float>(), flags.data_ptr<float>(), scale.data_ptr<float>(),
+                                            tape.data_ptr<float>(), precision_of(precision_mode), ws.data_ptr(), bytes, cur_stream(input)));
+  return {p, U, tape, scale, flags};
+}
+
+Tensor fluidnet3d_backward(Tensor packed_t, Tensor flags, Tensor scale, Tensor grad_p, Tensor grad_U, Tensor tape,
+                           const std::string& precision_mode) {
+  check_field(grad_p, "grad_p"); check_field(grad_U, "grad_U"); check_field(flags, "flags");
+  TORCH_CHECK(grad_p.size(1) == 1 && grad_U.size(1) == 3 && flags.size(1) == 1, "fluidnet3d_backward: grad_p (B,1,D,H,W), grad_U (B,3,D,H,W), flags (B,1,D,H,W)");
+  TORCH_CHECK(grad_U.size(0) == grad_p.size(0) && grad_U.size(2) == grad_p.size(2) && grad_U.size(3) == grad_p.size(3) &&
+              grad_U.size(4) == grad_p.size(4) && flags.sizes() == grad_p.sizes(), "grad_p, grad_U and flags must share their grid");
+  const FnxGrid g = grid3d(grad_p.size(0), grad_p.size(2), grad_p.size(3), grad_p.size(4));
+  check_image3d(packed_t, "packed3d_t", grad_p);
+  TORCH_CHECK(scale.is_cuda() && scale.scalar_type() == at::kFloat && scale.is_contiguous() && scale.numel() == g.B, "scale must hold B floats on the GPU");
+  const bool ok = g.D >= 4 && g.H >= 4 && g.W >= 4;
+  const size_t floats = ok ? fnx_multiscale3d_tape_layout(&g, nullptr) : 0;
+  TORCH_CHECK(tape.is_cuda() && tape.scalar_type() == at::kFloat && tape.is_contiguous() && (!floats || (size_t)tape.numel() == floats),
+              "tape is not the layout of this grid");
+  c10::hip::HIPGuard guard(grad_p.get_device());
+  Tensor grad = at::empty({(int64_t)fnx_scalenet_weight_floats(1)}, grad_p.options());
+  const size_t bytes = floats ? fnx_fluidnet3d_train_ws_bytes(&g) : 1;
+  Tensor ws = at::empty({(int64_t)bytes}, grad_p.options().dtype(at::kByte));
+  check_status(fnx_fluidnet3d_backward(&g, packed_t.data_ptr(), (size_t)packed_t.nbytes(), flags.data_ptr<float>(), scale.data_ptr<float>(),
+                                       grad_p.data_ptr<float>(), grad_U.data_ptr<float>(), tape.data_ptr<float>(), grad.data_ptr<float>(),
+                                       precision_of(precision_mode), ws.data_ptr(), bytes, cur_stream(grad_p)));
+  return grad;
+}
+
 // ---- training scenes and the training loss (ABI 23; 2D, the C ABI refuses everything else before it touches the device) ----------
 static Tensor check_scene_ids(const Tensor& ids) {
   TORCH_CHECK(ids.is_cuda() && ids.scalar_type() == at::kInt && ids.dim() == 1 && ids.is_contiguous() && ids.numel() >= 1,
@@ -1190,6 +1325,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("centre_min"), py::arg("centre_max"), py::arg("size_min"), py::arg("size_max"), py::arg("depth") = 1, NoGil());
   m.def("scene_turbulence", &scene_turbulence, py::arg("scene_ids"), py::arg("H"), py::arg("W"), py::arg("seed"), py::arg("octaves"),
         py::arg("wavelength"), py::arg("amplitude"), py::arg("density_scale"), py::arg("with_density") = true, py::arg("depth") = 1, NoGil());
+  m.def("scalenet3d_pack_t", &scalenet3d_pack_t, py::arg("blob"), NoGil());
+  m.def("multiscale3d_tape_layout", &multiscale3d_tape_layout, py::arg("B"), py::arg("D"), py::arg("H"), py::arg("W"));
+  m.def("trilinear_upsample_backward", &trilinear_upsample_backward, py::arg("grad_dst"), py::arg("size"), NoGil());
+  m.def("multiscale3d_forward_train", &multiscale3d_forward_train, py::arg("packed"), py::arg("x"), py::arg("precision_mode") = "fp32", NoGil());
+  m.def("multiscale3d_backward", &multiscale3d_backward, py::arg("packed_t"), py::arg("grad_p"), py::arg("tape"),
+        py::arg("precision_mode") = "fp32", NoGil());
+  m.def("multiscale3d_backward_plain", &multiscale3d_backward_plain, py::arg("packed_t"), py::arg("grad_p"), py::arg("tape"),
+        py::arg("precision_mode") = "fp32", NoGil());
+  m.def("fluidnet3d_forward_train", &fluidnet3d_forward_train, py::arg("packed"), py::arg("input"), py::arg("normalize_threshold"),
+        py::arg("precision_mode") = "fp32", NoGil());
+  m.def("fluidnet3d_backward", &fluidnet3d_backward, py::arg("packed_t"), py::arg("flags"), py::arg("scale"), py::arg("grad_p"),
+        py::arg("grad_U"), py::arg("tape"), py::arg("precision_mode") = "fp32", NoGil());
   m.def("train_loss", &train_loss, py::arg("out_p"), py::arg("out_U"), py::arg("flags"), py::arg("target_p"), py::arg("lambdas"),
         py::arg("upstream") = py::none(), py::arg("terms") = true, NoGil());
   m.def("abi_version", &fnx_abi_version);

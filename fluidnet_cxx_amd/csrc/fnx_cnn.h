@@ -112,6 +112,36 @@ bool multiscale_backward(int B, int H, int W, const void* packed_t, const float*
 // g_net = scale[b] * grad_p + velocity_update_backward_p(scale[b] * setWallBcs(grad_U))   (the adjoint of model.py:213-226)
 void launch_scale_mul(size_t n1, int nc, int B, const float* scale, const float* a, const float* addend, float* out, hipStream_t s);
 
+
+// ---- training in 3D (fnx_cnn_train3d.hip: fp32 modes) ------------------------------------------------------------------------------
+// The 3D versions of the hooks above: layer l of the 3D net (launch_conv with is3d), the 3D plan's offsets, the net's tower sizes
+// (q, h: {D, H, W} at quarter and half resolution, the reference's int(n * 0.25) / int(n * 0.5)), the two-source trilinear resampling,
+// and the images of a 3x3x3 Family::MFMA weight (27 taps, the Winograd images with kd = 3) as scalenet_pack(is3d = true) writes them.
+void conv_layer3d(int l, int mode, const float* packed, const float* x, float* y, int B, int D, int H, int W, hipStream_t s);
+void packed_offsets3d(int l, size_t* taps, size_t* bias);
+void net_sizes3d(int D, int H, int W, int q[3], int h[3]);
+void resize3d(const float* x0, int C0, int D0, int H0, int W0, const float* x1, int C1, int D1, int H1, int W1, float* y, int B, int Do,
+              int Ho, int Wo, hipStream_t s);
+MfmaImages mfma_images3d(int cin, int cout, size_t off);
+void pack_mfma_images3d(const float* w, const float* bias, int cin, int cout, float* base, const MfmaImages& im, hipStream_t s);
+bool conv_mfma_images3d(const MfmaImages& im, const float* base, int cin, int cout, int relu, int mode, const float* x, float* y, int B,
+                        int D, int H, int W, hipStream_t s);
+
+// The tape of the 3D training forward: the 2D tape's 19 entries as (B,C,D,H,W) tensors; a function of (B,D,H,W) alone.
+struct TapeEntry3d { const char* name; size_t off; int C, D, H, W; };
+struct TapeLayout3d { TapeEntry3d e[N_TAPE]; size_t floats; };
+TapeLayout3d tape_layout3d(int B, int D, int H, int W);
+// gd (B,1,Do,Ho,Wo) -> gs (B,1,Di,Hi,Wi): the adjoint of resize_kernel's trilinear resampling of one channel from (Di,Hi,Wi) to (Do,Ho,Wo)
+void launch_resize3d_adjoint(const float* gd, float* gs, int B, int Di, int Hi, int Wi, int Do, int Ho, int Wo, hipStream_t s);
+// packed3d_t: the 3D blob followed by the images of the ten transposed, tap-flipped 3x3x3 weights between 32, 64 and 128 channels
+size_t scalenet3d_packed_t_bytes();
+void scalenet3d_pack_t(const float* blob, void* packed_t, hipStream_t s);
+size_t multiscale3d_backward_ws_bytes(int B, int D, int H, int W);
+// x (B,2,D,H,W) -> p (B,1,D,H,W) bit-identical to multiscale_forward(is3d) in the same mode, and every layer's input in `tape`
+void multiscale3d_forward_train(int B, int D, int H, int W, const void* packed, const float* x, float* p, float* tape, int mode, hipStream_t s);
+// as multiscale_backward, for the 3D net
+bool multiscale3d_backward(int B, int D, int H, int W, const void* packed_t, const float* grad_p, const float* tape, float* grad_blob,
+                           int mode, void* ws, hipStream_t s, bool wgrad_mfma = true);
 }  // namespace fnx
 
 struct FnxGrid;

@@ -35,38 +35,57 @@ def _split(blob, shapes):
     return grads
 
 
+class _Api:
+    """what differs between the 2D and the 3D net: the extension's entry points and the number of velocity components (only the
+    dimension is state, so a module that holds one copies and pickles as before)"""
+
+    def __init__(self, ndim):
+        self.ndim, self.nc = ndim, ndim
+
+    def _fn(self, name):
+        return getattr(ext, name.replace("#", "" if self.ndim == 2 else "3d"))
+
+    def pack(self, blob):
+        return ext.scalenet_pack(blob, self.ndim == 3), self._fn("scalenet#_pack_t")(blob)
+
+    multiscale_forward_train = property(lambda self: self._fn("multiscale#_forward_train"))
+    multiscale_backward = property(lambda self: self._fn("multiscale#_backward"))
+    fluidnet_forward_train = property(lambda self: self._fn("fluidnet#_forward_train"))
+    fluidnet_backward = property(lambda self: self._fn("fluidnet#_backward"))
+
+
 class _MultiScaleFn(torch.autograd.Function):
-    """x (B,2,H,W) or (B,2,1,H,W) -> p; the parameters ride along so that autograd routes their gradients"""
+    """x (B,2,H,W), (B,2,1,H,W) or, for the 3D net, (B,2,D,H,W) -> p; the parameters ride along so that autograd routes their gradients"""
 
     @staticmethod
     def forward(ctx, x, owner, *params):
         packed, ctx.packed_t = owner._packed(x.device)
-        p, ctx.tape = ext.multiscale_forward_train(packed, x, owner.precision_mode)
-        ctx.mode, ctx.shapes = owner.precision_mode, [q.shape for q in params]
+        p, ctx.tape = owner._api.multiscale_forward_train(packed, x, owner.precision_mode)
+        ctx.mode, ctx.shapes, ctx.api = owner.precision_mode, [q.shape for q in params], owner._api
         return p
 
     @staticmethod
     def backward(ctx, gp):
-        blob = ext.multiscale_backward(ctx.packed_t, gp.contiguous(), ctx.tape, ctx.mode)
+        blob = ctx.api.multiscale_backward(ctx.packed_t, gp.contiguous(), ctx.tape, ctx.mode)
         return (None, None) + tuple(_split(blob, ctx.shapes))
 
 
 class _FluidNetFn(torch.autograd.Function):
-    """input_ (B,5,1,H,W) -> (p, U)   (model.py:76-227 around the taped net)"""
+    """input_ (B,5,1,H,W) or, for the 3D net, (B,6,D,H,W) -> (p, U)   (model.py:76-227 around the taped net)"""
 
     @staticmethod
     def forward(ctx, input_, owner, *params):
         packed, ctx.packed_t = owner._packed(input_.device)
-        p, U, ctx.tape, ctx.scale, ctx.flags = ext.fluidnet_forward_train(packed, input_, owner.threshold, owner.precision_mode)
-        ctx.mode, ctx.shapes = owner.precision_mode, [q.shape for q in params]
+        p, U, ctx.tape, ctx.scale, ctx.flags = owner._api.fluidnet_forward_train(packed, input_, owner.threshold, owner.precision_mode)
+        ctx.mode, ctx.shapes, ctx.api = owner.precision_mode, [q.shape for q in params], owner._api
         return p, U
 
     @staticmethod
     def backward(ctx, gp, gU):
         # a loss that leaves out one of the two outputs delivers None for it
         gp = ctx.flags.new_zeros(ctx.flags.shape) if gp is None else gp.contiguous()
-        gU = ctx.flags.new_zeros((ctx.flags.size(0), 2) + tuple(ctx.flags.shape[2:])) if gU is None else gU.contiguous()
-        blob = ext.fluidnet_backward(ctx.packed_t, ctx.flags, ctx.scale, gp, gU, ctx.tape, ctx.mode)
+        gU = ctx.flags.new_zeros((ctx.flags.size(0), ctx.api.nc) + tuple(ctx.flags.shape[2:])) if gU is None else gU.contiguous()
+        blob = ctx.api.fluidnet_backward(ctx.packed_t, ctx.flags, ctx.scale, gp, gU, ctx.tape, ctx.mode)
         return (None, None) + tuple(_split(blob, ctx.shapes))
 
 
@@ -84,13 +103,15 @@ class _Holder(torch.nn.Module):
 
 
 class _MultiScaleTrain(torch.nn.Module):
-    """x (B,2,H,W) -> p (B,1,H,W)   (multi_scale_net.py:118-127), differentiable with respect to the parameters"""
+    """x (B,2,H,W) -> p (B,1,H,W), or (B,2,D,H,W) -> (B,1,D,H,W) with ndim = 3   (multi_scale_net.py:118-127), differentiable with
+    respect to the parameters"""
 
-    def __init__(self, precision_mode):
+    def __init__(self, precision_mode, ndim=2):
         super().__init__()
         self.precision_mode = precision_mode
-        w = make_scalenet_weights(0, ndim=2)
-        for L in scalenet_layers(2, 2):
+        self._api = _Api(ndim)
+        w = make_scalenet_weights(0, ndim=ndim)
+        for L in scalenet_layers(2, ndim):
             parts = L["name"].split(".")[1:]             # convN_4, encode, 0  |  final
             mod = self
             for part in parts[:-1]:
@@ -104,7 +125,7 @@ class _MultiScaleTrain(torch.nn.Module):
     def _ordered(self):
         """the 34 parameters in the blob's order (scalenet_layers(): weight, bias per convolution)"""
         named = dict(self.named_parameters())
-        return [named[L["name"].split(".", 1)[1] + sfx] for L in scalenet_layers(2, 2) for sfx in (".weight", ".bias")]
+        return [named[L["name"].split(".", 1)[1] + sfx] for L in scalenet_layers(2, self._api.ndim) for sfx in (".weight", ".bias")]
 
     def _packed(self, device):
         """(packed, packed_t) for the current parameter values on `device`: repacked on the device whenever a parameter was written
@@ -113,7 +134,7 @@ class _MultiScaleTrain(torch.nn.Module):
         key = (str(device),) + tuple((p.data_ptr(), p._version) for p in params)
         if key != self._key:
             blob = torch.cat([p.detach().reshape(-1) for p in params]).to(device=device, dtype=torch.float32).contiguous()
-            self._images = (ext.scalenet_pack(blob, False), ext.scalenet_pack_t(blob))
+            self._images = self._api.pack(blob)
             self._key = key
         return self._images
 
@@ -125,34 +146,39 @@ class _MultiScaleTrain(torch.nn.Module):
         return _MultiScaleFn.apply(x, self, *self._ordered())
 
 
-class FluidNetTrain(torch.nn.Module):
-    """input_ (B,5,1,H,W) = [p, U, flags, density] -> (p, U), differentiable with respect to the net's parameters.
+class _FluidNetTrainBase(torch.nn.Module):
+    """What FluidNetTrain (2D) and FluidNetTrain3D share: everything but the dimension, which a subclass states in _NDIM, and its
+    check of mconf['is3D'] (_check_dim)."""
 
-    What replaces `lib.FluidNet` in the reference's fluid_net_train.py; constructed, loaded and called the same way."""
+    _NDIM = 2
+
+    def _check_dim(self, mconf):
+        raise NotImplementedError
 
     def __init__(self, mconf, dropout=False):
         super().__init__()
+        name = f"fluidnet_cxx_amd.{type(self).__name__}"
         if dropout:
-            raise ValueError("fluidnet_cxx_amd.FluidNetTrain: dropout=True is not supported (the reference's drivers build the ScaleNet "
+            raise ValueError(f"{name}: dropout=True is not supported (the reference's drivers build the ScaleNet "
                              "path with dropout=False)")
         if mconf.get("model", "ScaleNet") != "ScaleNet":
-            raise ValueError("fluidnet_cxx_amd.FluidNetTrain: only the ScaleNet variant is accelerated")
+            raise ValueError(f"{name}: only the ScaleNet variant is accelerated")
         ic = mconf.get("inputChannels", {"div": True, "pDiv": False, "UDiv": False})
         if not (ic.get("div", False) and not ic.get("pDiv", False) and not ic.get("UDiv", False)):
-            raise ValueError("fluidnet_cxx_amd.FluidNetTrain: inputChannels must be {div} (convModel_mconf.pth)")
+            raise ValueError(f"{name}: inputChannels must be {{div}} (convModel_mconf.pth)")
         if not (mconf.get("normalizeInput", True) and mconf.get("normalizeInputChan", "UDiv") == "UDiv"):
-            raise ValueError("fluidnet_cxx_amd.FluidNetTrain: normalizeInput on 'UDiv' is the supported configuration")
-        if mconf.get("is3D", False):
-            raise ValueError("fluidnet_cxx_amd.FluidNetTrain: training is 2D only (is3D=True)")
+            raise ValueError(f"{name}: normalizeInput on 'UDiv' is the supported configuration")
+        self._check_dim(mconf)
         self.precision_mode = str(mconf.get("precisionMode", "fp32"))
         if self.precision_mode not in _TRAIN_MODES:
-            raise ValueError(f"fluidnet_cxx_amd.FluidNetTrain: training runs in fp32 arithmetic only (precisionMode one of {_TRAIN_MODES}), "
+            raise ValueError(f"{name}: training runs in fp32 arithmetic only (precisionMode one of {_TRAIN_MODES}), "
                              f"not '{self.precision_mode}'")
         self.mconf = mconf
-        self.is3D = False
-        self.inDims = mconf.get("inputDim", 2)
+        self.is3D = self._NDIM == 3
+        self.inDims = mconf.get("inputDim", self._NDIM)
         self.threshold = float(mconf.get("normalizeInputThreshold", 1e-5))
-        self.multiScale = _MultiScaleTrain(self.precision_mode)
+        self.multiScale = _MultiScaleTrain(self.precision_mode, self._NDIM)
+        self._api = self.multiScale._api
         self._extra = OrderedDict()          # the reference's unused parameters (conv1.* ...), kept for state_dict()
 
     def _packed(self, device):
@@ -194,3 +220,13 @@ class FluidNetTrain(torch.nn.Module):
             return p, U
         _no_input_grad(input_, "input_")
         return _FluidNetFn.apply(input_, self, *self.multiScale._ordered())
+
+
+class FluidNetTrain(_FluidNetTrainBase):
+    """input_ (B,5,1,H,W) = [p, U, flags, density] -> (p, U), differentiable with respect to the net's parameters.
+
+    What replaces `lib.FluidNet` in the reference's fluid_net_train.py; constructed, loaded and called the same way."""
+
+    def _check_dim(self, mconf):
+        if mconf.get("is3D", False):
+            raise ValueError("fluidnet_cxx_amd.FluidNetTrain: training is 2D only (is3D=True; FluidNetTrain3D trains the 3D net)")

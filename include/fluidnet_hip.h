@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define FNX_ABI_VERSION 24
+#define FNX_ABI_VERSION 25
 
 enum {
   FNX_OK = 0,
@@ -684,6 +684,59 @@ int fnx_fluidnet_forward_train(const FnxGrid* g, const void* packed, const float
 int fnx_fluidnet_backward(const FnxGrid* g, const void* packed_t, const float* flags, const float* scale, const float* grad_p,
                           const float* grad_U, const float* tape, float* grad_blob, int precision_mode, void* ws, size_t ws_bytes,
                           void* stream);
+
+/* Training of the 3D net (ABI 25): the same gradients for the Conv3d net, under names of their own next to the 2D entry points above,
+ * which keep refusing 3D.  Every entry point checks, before it touches the device and each with its own fnx_last_error text: null
+ * arguments; a 3D grid (is3D = 1, D >= 4: "3D only"); H and W of at least 4; a precision mode among FNX_PRECISION_FP32, _FP32_F4, _FP32_F2
+ * and _FP32_DIRECT ("fp32 arithmetic only"); a whole domain (no compute window k_begin / k_end, no z-slab view z_offset / D_global); at most
+ * 2^26 cells per sample and 65535 planes B * D; and the size of the weight image it is given -- `packed` is fnx_scalenet_pack(1, ..)'s
+ * fnx_scalenet_packed_bytes(1) bytes, `packed3d_t` fnx_scalenet3d_pack_t's fnx_scalenet3d_packed_t_bytes() bytes; the two look alike, and
+ * a swapped pair is told apart by its size.  No gradient with respect to the input, no dropout.  No atomics: two calls on the same inputs
+ * give the same bits.
+ *
+ * The tape holds the 2D tape's entries as contiguous (B,C,D,H,W) tensors: "xq" at int(n * 0.25) per axis, "in2" at int(n * 0.5), "in1"
+ * at full resolution and the outputs "y0" .. "y15" after their ReLU -- 331 floats per full-resolution voxel, 324 per half- and 131 per
+ * quarter-resolution voxel (373.5 per full-resolution voxel in all, 1.49 KB).  fnx_multiscale3d_tape_layout returns its size in floats (0 on error) and fills
+ * fnx_multiscale_tape_entries() entries; the layout is a function of (B, D, H, W) alone.  p of the training forward is bit-identical to
+ * fnx_multiscale_forward's on the 3D grid in the same mode. */
+typedef struct FnxTapeEntry3D {
+  char name[8];
+  size_t offset;     /* floats from the start of the tape; the tensor is a contiguous (B,C,D,H,W) */
+  int C, D, H, W;
+} FnxTapeEntry3D;
+size_t fnx_multiscale3d_tape_layout(const FnxGrid* g, FnxTapeEntry3D* entries);
+/* The adjoint of the net's trilinear resampling (align_corners = False, sample positions in float32) of one channel on its own, as
+ * the backward applies it at the two tower joints: grad_dst (B,1,Do,Ho,Wo) -> grad_src (B,1,Di,Hi,Wi), every source voxel the sum of
+ * its destinations in a fixed x, y, z order.  Exposed so that a test can hold it against the transposed interpolation matrices. */
+int fnx_trilinear_upsample_backward(int B, int Di, int Hi, int Wi, int Do, int Ho, int Wo, const float* grad_dst, float* grad_src,
+                                    void* stream);
+/* packed3d_t: the 3D blob itself and, for the ten 3x3x3 layers between 32, 64 and 128 channels, the images of the transposed, tap-flipped
+ * weight with zero bias, packed on the device by the forward's own pack kernels.  weights_blob: fnx_scalenet_weight_floats(1) floats. */
+size_t fnx_scalenet3d_packed_t_bytes(void);
+int fnx_scalenet3d_pack_t(const float* weights_blob, void* packed_t, void* stream);
+size_t fnx_multiscale3d_backward_ws_bytes(const FnxGrid* g);
+/* x (B,2,D,H,W) -> p (B,1,D,H,W) and the tape (fnx_multiscale3d_tape_layout floats).  No workspace. */
+int fnx_multiscale3d_forward_train(const FnxGrid* g, const void* packed, size_t packed_bytes, const float* x, float* p, float* tape,
+                                   int precision_mode, void* stream);
+/* grad_p (B,1,D,H,W) and the tape of the forward -> grad_blob (fnx_scalenet_weight_floats(1) floats) in the layout of weights_blob: per
+ * conv the weight gradient (Cout,Cin,kd,kh,kw) then the bias gradient.  grad_p and the tape are not modified.  The weight gradients of
+ * the 3x3x3 layers between 32, 64 and 128 channels run on the matrix cores in exact fp32 (v_mfma_f32_32x32x2_f32), one workgroup per
+ * (32 x 32 channel block, z tap, split of the pixel tiles), partials added in a fixed order in fp64. */
+int fnx_multiscale3d_backward(const FnxGrid* g, const void* packed_t, size_t packed_t_bytes, const float* grad_p, const float* tape,
+                              float* grad_blob, int precision_mode, void* ws, size_t ws_bytes, void* stream);
+/* The same call with the plain fp64 weight-gradient kernel of the thin layers for every layer: a cross-check for tests and A/B timing. */
+int fnx_multiscale3d_backward_plain(const FnxGrid* g, const void* packed_t, size_t packed_t_bytes, const float* grad_p, const float* tape,
+                                    float* grad_blob, int precision_mode, void* ws, size_t ws_bytes, void* stream);
+/* FluidNet.forward for training on a 3D grid and its backward (one workspace size for both): fnx_fluidnet_forward with the taped net;
+ * input (B,6,D,H,W) = [p, Ux, Uy, Uz, flags, density]; flags_out (B,1,D,H,W) and scale_out (B) go back into the backward, where
+ * g_net = s grad_p + velocity_update_backward_p(s setWallBcs(grad_U)), grad_U (B,3,D,H,W). */
+size_t fnx_fluidnet3d_train_ws_bytes(const FnxGrid* g);
+int fnx_fluidnet3d_forward_train(const FnxGrid* g, const void* packed, size_t packed_bytes, const float* input, float normalize_threshold,
+                                 float* p_out, float* U_out, float* flags_out, float* scale_out, float* tape, int precision_mode, void* ws,
+                                 size_t ws_bytes, void* stream);
+int fnx_fluidnet3d_backward(const FnxGrid* g, const void* packed_t, size_t packed_t_bytes, const float* flags, const float* scale,
+                            const float* grad_p, const float* grad_U, const float* tape, float* grad_blob, int precision_mode, void* ws,
+                            size_t ws_bytes, void* stream);
 
 /* ---- Training scenes and the training loss (ABI 23; the reference trains on a pre-computed Mantaflow data set and composes its loss
  * from ATen operators, fluid_net_train.py:276-285).  2D only, like the training entry points above; every entry point checks before it
