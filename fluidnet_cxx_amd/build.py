@@ -31,7 +31,6 @@ HIP_UNITS = {
     # (resource-usage remarks: build_lib checks the kernels of SCRATCH_FREE)
     "fnx_cnn.hip": ["-Rpass-analysis=kernel-resource-usage"],
     "fnx_cnn_train.hip": ["-Rpass-analysis=kernel-resource-usage"],
-    "fnx_cnn_train3d.hip": ["-Rpass-analysis=kernel-resource-usage"],
     "fnx_slab.hip": [],
     "fnx_peer.hip": [],
 }
@@ -39,11 +38,10 @@ HIP_UNITS = {
 SCRATCH_FREE = {
     "fnx_cnn.hip": (["conv3_wbf_kernel"], "fnx_cnn_bf16x6.h: the results of its inline-asm LDS reads are only valid behind an explicit "
                                           "wait; a spill copies them before it"),
-    "fnx_cnn_train.hip": (["wgrad3_mfma_kernel"], "its nine 32x32 accumulators (144 VGPRs) live across the whole pixel march at two workgroups "
-                                                  "per CU; a spill puts scratch traffic between the MFMAs"),
-    "fnx_cnn_train3d.hip": (["wgrad_dz_mfma_kernel", "wgrad3d_small_kernel"],
-                            "the MFMA kernel's nine 32x32 accumulators (144 VGPRs) live across the whole pixel march at two workgroups per "
-                            "CU, and the plain kernel slices a 5x5x5 layer by dz so that its 25 fp64 accumulators stay in registers"),
+    "fnx_cnn_train.hip": (["wgrad_mfma_kernel", "wgrad_small_kernel"],
+                          "the MFMA kernel's nine 32x32 accumulators (144 VGPRs) live across the whole pixel march at two workgroups per "
+                          "CU; a spill puts scratch traffic between the MFMAs.  The plain kernel slices a 5x5x5 layer by dz so that its "
+                          "25 fp64 accumulators stay in registers"),
     "fnx_advect.hip": (["advect3d_fwd_tile_kernel", "advect3d_bwd_tile_kernel", "advect3d_bwd_scalar_tile_kernel",
                         "advect3d_bwd_vel_tile_kernel"],
                        "fnx_advect_march.h: the 3D advection marches run at 2-3 waves per SIMD with every VGPR in use; a reload from "

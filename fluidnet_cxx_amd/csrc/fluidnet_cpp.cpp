@@ -621,7 +621,7 @@ Tensor fluidnet_backward(Tensor packed_t, Tensor flags, Tensor scale, Tensor gra
   return grad;
 }
 
-// ---- training of the 3D net (fnx_cnn_train3d.hip) ---------------------------------------------------------
+// ---- training of the 3D net (fnx_cnn_train.hip) -----------------------------------------------------------
 Tensor scalenet3d_pack_t(Tensor blob) {
   TORCH_CHECK(blob.is_cuda() && blob.scalar_type() == at::kFloat && blob.is_contiguous(), "weights blob must be a contiguous float32 GPU tensor");
   TORCH_CHECK((size_t)blob.numel() == fnx_scalenet_weight_floats(1), "weights blob has ", blob.numel(), " floats, expected ",

@@ -58,7 +58,7 @@ void launch_scale_from_sums(int nranks, int B, double n, float thr, const float*
 void launch_pack_div(const GridDims& g, bool is3d, const float* U, const float* flags, const float* scale, float* x, hipStream_t s);
 
 
-// ---- training (fnx_cnn_train.hip: 2D, fp32 modes) ---------------------------------------------------------------------------------
+// ---- training (fnx_cnn_train.hip: 2D and 3D, fp32 modes) --------------------------------------------------------------------------
 // torch upsample_{bi,tri}linear(align_corners=False): src = scale*(dst+0.5)-0.5, clamped at 0
 __device__ __forceinline__ void src_index(int dst, int in, int out, int& i0, int& i1, float& l0, float& l1) {
   const float scale = (float)in / (float)out;
@@ -72,76 +72,54 @@ __device__ __forceinline__ void src_index(int dst, int in, int out, int& i0, int
 }
 
 
-// what the training unit uses of the forward's launchers (fnx_cnn.hip)
-// layer l of the 2D net from x into y, exactly the launch the inference forward makes (launch_conv)
-void conv_layer(int l, int mode, const float* packed, const float* x, float* y, int B, int H, int W, hipStream_t s);
-// float offsets of layer l's tap image and bias in the packed buffer (2D)
-void packed_offsets(int l, size_t* taps, size_t* bias);
-// the resampling of multi_scale_net.py:119-125 in 2D: x0 (B,C0,H0,W0) and, if C1 > 0, x1 (B,C1,H1,W1) -> channels [0, C0 + C1) of y (B,.,Ho,Wo)
-void resize2d(const float* x0, int C0, int H0, int W0, const float* x1, int C1, int H1, int W1, float* y, int B, int Ho, int Wo,
-              hipStream_t s);
-// The images of one 2D Family::MFMA weight (3x3, Cin % 16 == 0, Cout % 32 == 0) at float offset `off` of a buffer: what scalenet_pack
+// what the training unit uses of the forward's launchers (fnx_cnn.hip).  These hooks, and tape_layout, multiscale_forward_train,
+// multiscale_backward and its workspace size below, take `is3d` and a grid {D, H, W}; 2D is D = 1 (one plane in every tensor).
+// layer l of the net from x into y, exactly the launch the inference forward makes (launch_conv)
+void conv_layer(int l, bool is3d, int mode, const float* packed, const float* x, float* y, int B, int D, int H, int W, hipStream_t s);
+// float offsets of layer l's tap image and bias in the packed buffer
+void packed_offsets(int l, bool is3d, size_t* taps, size_t* bias);
+// the net's tower sizes: q, h = {D, H, W} at quarter and half resolution, the reference's int(n * 0.25) / int(n * 0.5) (D stays 1 in 2D)
+void net_sizes(bool is3d, int D, int H, int W, int q[3], int h[3]);
+// the resampling of multi_scale_net.py:119-125: x0 (B,C0,D0,H0,W0) and, if C1 > 0, x1 (B,C1,D1,H1,W1) -> channels [0, C0 + C1) of
+// y (B,.,Do,Ho,Wo)
+void resize(const float* x0, int C0, int D0, int H0, int W0, const float* x1, int C1, int D1, int H1, int W1, float* y, int B, int Do,
+            int Ho, int Wo, hipStream_t s);
+// The images of one Family::MFMA weight (3x3(x3), Cin % 16 == 0, Cout % 32 == 0) at float offset `off` of a buffer: what scalenet_pack
 // writes for such a layer, for any weight tensor -- the backward's transposed, tap-flipped weights go through the forward's launchers.
 struct MfmaImages { size_t taps, wino2, wino3, wbf, wino4, bias, end; bool wide; };
-MfmaImages mfma_images(int cin, int cout, size_t off);
-// w (Cout,Cin,3,3), bias (Cout) -> the images at base + im.*
-void pack_mfma_images(const float* w, const float* bias, int cin, int cout, float* base, const MfmaImages& im, hipStream_t s);
-// y = conv3x3(x, the packed weight) [+ ReLU] by launch_conv's mode rule; false: nothing launched (H * W beyond the MFMA kernels' range)
-bool conv_mfma_images(const MfmaImages& im, const float* base, int cin, int cout, int relu, int mode, const float* x, float* y, int B,
-                      int H, int W, hipStream_t s);
+MfmaImages mfma_images(bool is3d, int cin, int cout, size_t off);
+// w (Cout,Cin,(3,)3,3), bias (Cout) -> the images at base + im.*
+void pack_mfma_images(bool is3d, const float* w, const float* bias, int cin, int cout, float* base, const MfmaImages& im, hipStream_t s);
+// y = conv3x3(x3)(x, the packed weight) [+ ReLU] by launch_conv's mode rule; false: nothing launched (D * H * W beyond the MFMA kernels'
+// range)
+bool conv_mfma_images(bool is3d, const MfmaImages& im, const float* base, int cin, int cout, int relu, int mode, const float* x, float* y,
+                      int B, int D, int H, int W, hipStream_t s);
 
-// One entry of the tape of the training forward: a (B,C,H,W) tensor at float offset `off`.  The layout is a function of (B,H,W) alone.
+// One entry of the tape of the training forward: a (B,C,D,H,W) tensor at float offset `off`.  The layout is a function of the
+// dimension and (B,D,H,W) alone.
 constexpr int N_TAPE = 19;   // xq, y0..y3, in2, y4..y9, in1, y10..y15   (y_l: the output of LAYERS[l], after its ReLU)
-struct TapeEntry { const char* name; size_t off; int C, H, W; };
+struct TapeEntry { const char* name; size_t off; int C, D, H, W; };
 struct TapeLayout { TapeEntry e[N_TAPE]; size_t floats; };
-TapeLayout tape_layout(int B, int H, int W);
+TapeLayout tape_layout(bool is3d, int B, int D, int H, int W);
 inline int tape_input_index(int tower) { return tower == 0 ? 0 : (tower == 1 ? 5 : 12); }   // xq, in2, in1
 inline int tape_output_index(int l) { return l < 4 ? 1 + l : (l < 10 ? 2 + l : 3 + l); }    // y_l, l = 0..15
 
-// packed_t: the blob itself followed by the images of the ten transposed, tap-flipped 3x3 weights between 32, 64 and 128 channels
-size_t scalenet_packed_t_bytes();
-void scalenet_pack_t(const float* blob, void* packed_t, hipStream_t s);
-size_t multiscale_backward_ws_bytes(int B, int H, int W);
-// x (B,2,H,W) -> p (B,1,H,W) bit-identical to multiscale_forward in the same mode, and every layer's input in `tape`
-void multiscale_forward_train(int B, int H, int W, const void* packed, const float* x, float* p, float* tape, int mode, hipStream_t s);
-// grad_p (B,1,H,W), the tape of the forward -> grad_blob in the blob's own layout (per layer: weight gradient, bias gradient).
+// packed_t: the blob itself followed by the images of the ten transposed, tap-flipped 3x3(x3) weights between 32, 64 and 128 channels
+size_t scalenet_packed_t_bytes(bool is3d);
+void scalenet_pack_t(bool is3d, const float* blob, void* packed_t, hipStream_t s);
+size_t multiscale_backward_ws_bytes(bool is3d, int B, int D, int H, int W);
+// x (B,2,D,H,W) -> p (B,1,D,H,W) bit-identical to multiscale_forward in the same mode, and every layer's input in `tape`
+void multiscale_forward_train(bool is3d, int B, int D, int H, int W, const void* packed, const float* x, float* p, float* tape, int mode,
+                              hipStream_t s);
+// grad_p (B,1,D,H,W), the tape of the forward -> grad_blob in the blob's own layout (per layer: weight gradient, bias gradient).
 // No atomics; every sum in a fixed order.  wgrad_mfma = false: the plain weight-gradient kernel for every layer (cross-checks).
 // false: an input-gradient convolution was not launched (see conv_mfma_images).
-bool multiscale_backward(int B, int H, int W, const void* packed_t, const float* grad_p, const float* tape, float* grad_blob, int mode,
-                         void* ws, hipStream_t s, bool wgrad_mfma = true);
+bool multiscale_backward(bool is3d, int B, int D, int H, int W, const void* packed_t, const float* grad_p, const float* tape,
+                         float* grad_blob, int mode, void* ws, hipStream_t s, bool wgrad_mfma = true);
+// gd (B,1,Do,Ho,Wo) -> gs (B,1,Di,Hi,Wi): the adjoint of resize_kernel's resampling of one channel from (Di,Hi,Wi) to (Do,Ho,Wo)
+void launch_resize3d_adjoint(const float* gd, float* gs, int B, int Di, int Hi, int Wi, int Do, int Ho, int Wo, hipStream_t s);
 // g_net = scale[b] * grad_p + velocity_update_backward_p(scale[b] * setWallBcs(grad_U))   (the adjoint of model.py:213-226)
 void launch_scale_mul(size_t n1, int nc, int B, const float* scale, const float* a, const float* addend, float* out, hipStream_t s);
-
-
-// ---- training in 3D (fnx_cnn_train3d.hip: fp32 modes) ------------------------------------------------------------------------------
-// The 3D versions of the hooks above: layer l of the 3D net (launch_conv with is3d), the 3D plan's offsets, the net's tower sizes
-// (q, h: {D, H, W} at quarter and half resolution, the reference's int(n * 0.25) / int(n * 0.5)), the two-source trilinear resampling,
-// and the images of a 3x3x3 Family::MFMA weight (27 taps, the Winograd images with kd = 3) as scalenet_pack(is3d = true) writes them.
-void conv_layer3d(int l, int mode, const float* packed, const float* x, float* y, int B, int D, int H, int W, hipStream_t s);
-void packed_offsets3d(int l, size_t* taps, size_t* bias);
-void net_sizes3d(int D, int H, int W, int q[3], int h[3]);
-void resize3d(const float* x0, int C0, int D0, int H0, int W0, const float* x1, int C1, int D1, int H1, int W1, float* y, int B, int Do,
-              int Ho, int Wo, hipStream_t s);
-MfmaImages mfma_images3d(int cin, int cout, size_t off);
-void pack_mfma_images3d(const float* w, const float* bias, int cin, int cout, float* base, const MfmaImages& im, hipStream_t s);
-bool conv_mfma_images3d(const MfmaImages& im, const float* base, int cin, int cout, int relu, int mode, const float* x, float* y, int B,
-                        int D, int H, int W, hipStream_t s);
-
-// The tape of the 3D training forward: the 2D tape's 19 entries as (B,C,D,H,W) tensors; a function of (B,D,H,W) alone.
-struct TapeEntry3d { const char* name; size_t off; int C, D, H, W; };
-struct TapeLayout3d { TapeEntry3d e[N_TAPE]; size_t floats; };
-TapeLayout3d tape_layout3d(int B, int D, int H, int W);
-// gd (B,1,Do,Ho,Wo) -> gs (B,1,Di,Hi,Wi): the adjoint of resize_kernel's trilinear resampling of one channel from (Di,Hi,Wi) to (Do,Ho,Wo)
-void launch_resize3d_adjoint(const float* gd, float* gs, int B, int Di, int Hi, int Wi, int Do, int Ho, int Wo, hipStream_t s);
-// packed3d_t: the 3D blob followed by the images of the ten transposed, tap-flipped 3x3x3 weights between 32, 64 and 128 channels
-size_t scalenet3d_packed_t_bytes();
-void scalenet3d_pack_t(const float* blob, void* packed_t, hipStream_t s);
-size_t multiscale3d_backward_ws_bytes(int B, int D, int H, int W);
-// x (B,2,D,H,W) -> p (B,1,D,H,W) bit-identical to multiscale_forward(is3d) in the same mode, and every layer's input in `tape`
-void multiscale3d_forward_train(int B, int D, int H, int W, const void* packed, const float* x, float* p, float* tape, int mode, hipStream_t s);
-// as multiscale_backward, for the 3D net
-bool multiscale3d_backward(int B, int D, int H, int W, const void* packed_t, const float* grad_p, const float* tape, float* grad_blob,
-                           int mode, void* ws, hipStream_t s, bool wgrad_mfma = true);
 }  // namespace fnx
 
 struct FnxGrid;

@@ -1442,58 +1442,23 @@ inline Sizes sizes(const GridDims& g, bool is3d) {
 
 }  // namespace
 
-// ---- what the training unit (fnx_cnn_train.hip) uses of the launchers above ----
-void conv_layer(int l, int mode, const float* packed, const float* x, float* y, int B, int H, int W, hipStream_t s) {
-  launch_conv(l, false, mode, packed, x, y, B, 1, H, W, s);
+// ---- what the training unit (fnx_cnn_train.hip) uses of the launchers above; 2D is D = 1 ----
+void conv_layer(int l, bool is3d, int mode, const float* packed, const float* x, float* y, int B, int D, int H, int W, hipStream_t s) {
+  launch_conv(l, is3d, mode, packed, x, y, B, D, H, W, s);
 }
-void packed_offsets(int l, size_t* taps, size_t* bias) { *taps = plan(false)[l].taps; *bias = plan(false)[l].bias; }
-void resize2d(const float* x0, int C0, int H0, int W0, const float* x1, int C1, int H1, int W1, float* y, int B, int Ho, int Wo,
-              hipStream_t s) {
-  launch_resize2(RSrc{x0, C0, 1, H0, W0, ZWin{1, 0, 1, 0}}, RSrc{x1, C1, 1, H1, W1, ZWin{1, 0, 1, 0}}, y, B, 1, Ho, Wo, s);
-}
-MfmaImages mfma_images(int cin, int cout, size_t off) {       // make_plan's Family::MFMA case, 2D
-  MfmaImages im{};
-  const size_t nw = (size_t)9 * cin * cout, nwino = (size_t)16 * cin * cout;
-  im.wide = cout % 64 == 0;
-  im.taps = off; im.wino2 = off + nw; im.wino3 = im.wino2 + nwino;
-  off = im.wino3 + nwino;
-  if (im.wide) { im.wbf = off; im.wino4 = im.wbf + nwino * 3 / 2; off = im.wino4 + nw; }
-  im.bias = off;
-  im.end = (off + cout + 63) & ~(size_t)63;
-  return im;
-}
-void pack_mfma_images(const float* w, const float* bias, int cin, int cout, float* base, const MfmaImages& im, hipStream_t s) {
-  pack_layer_mfma_kernel<<<64, 256, 0, s>>>(w, bias, base + im.taps, base + im.bias, cin, cout, 9);
-  pack_layer_wino_kernel<<<64, 256, 0, s>>>(w, base + im.wino2, cin, cout, 1);
-  repack_wino3_kernel<<<64, 256, 0, s>>>(base + im.wino2, base + im.wino3, cin, cout, 1, wino3_rw(cout));
-  if (im.wide) {
-    pack_wbf_kernel<<<256, 256, 0, s>>>(base + im.wino2, (unsigned*)(base + im.wbf), cin, cout, 1);
-    pack_layer_wino4g_kernel<<<64, 256, 0, s>>>(w, base + im.wino4, cin, cout, 1);
-  }
-}
-bool conv_mfma_images(const MfmaImages& im, const float* base, int cin, int cout, int relu, int mode, const float* x, float* y, int B,
-                      int H, int W, hipStream_t s) {
-  const ConvArgs a{x, y, base + im.taps, base + im.bias, B, cin, cout, 1, H, W, relu, cout / co_tile(cout), nullptr, nullptr};
-  return launch_conv_mfma_family(a, false, mode, im.wide, base + im.wbf, base + im.wino4, base + im.wino3, s);
-}
-
-// ---- the same hooks for the 3D net (fnx_cnn_train3d.hip) ----
-void conv_layer3d(int l, int mode, const float* packed, const float* x, float* y, int B, int D, int H, int W, hipStream_t s) {
-  launch_conv(l, true, mode, packed, x, y, B, D, H, W, s);
-}
-void packed_offsets3d(int l, size_t* taps, size_t* bias) { *taps = plan(true)[l].taps; *bias = plan(true)[l].bias; }
-void net_sizes3d(int D, int H, int W, int q[3], int h[3]) {
-  const Sizes z = sizes(make_dims(1, D, H, W), true);
+void packed_offsets(int l, bool is3d, size_t* taps, size_t* bias) { *taps = plan(is3d)[l].taps; *bias = plan(is3d)[l].bias; }
+void net_sizes(bool is3d, int D, int H, int W, int q[3], int h[3]) {
+  const Sizes z = sizes(make_dims(1, D, H, W), is3d);
   q[0] = z.Dq; q[1] = z.Hq; q[2] = z.Wq;
   h[0] = z.Dh; h[1] = z.Hh; h[2] = z.Wh;
 }
-void resize3d(const float* x0, int C0, int D0, int H0, int W0, const float* x1, int C1, int D1, int H1, int W1, float* y, int B, int Do,
-              int Ho, int Wo, hipStream_t s) {
+void resize(const float* x0, int C0, int D0, int H0, int W0, const float* x1, int C1, int D1, int H1, int W1, float* y, int B, int Do,
+            int Ho, int Wo, hipStream_t s) {
   launch_resize2(RSrc{x0, C0, D0, H0, W0, ZWin{D0, 0, Do, 0}}, RSrc{x1, C1, D1, H1, W1, ZWin{D1, 0, Do, 0}}, y, B, Do, Ho, Wo, s);
 }
-MfmaImages mfma_images3d(int cin, int cout, size_t off) {     // make_plan's Family::MFMA case, 3D (kd = 3)
+MfmaImages mfma_images(bool is3d, int cin, int cout, size_t off) {       // make_plan's Family::MFMA case (kd = 3 in 3D)
   MfmaImages im{};
-  const size_t nw = (size_t)27 * cin * cout, nwino = (size_t)16 * 3 * cin * cout;
+  const size_t kd = is3d ? 3 : 1, nw = 9 * kd * cin * cout, nwino = 16 * kd * cin * cout;
   im.wide = cout % 64 == 0;
   im.taps = off; im.wino2 = off + nw; im.wino3 = im.wino2 + nwino;
   off = im.wino3 + nwino;
@@ -1502,19 +1467,20 @@ MfmaImages mfma_images3d(int cin, int cout, size_t off) {     // make_plan's Fam
   im.end = (off + cout + 63) & ~(size_t)63;
   return im;
 }
-void pack_mfma_images3d(const float* w, const float* bias, int cin, int cout, float* base, const MfmaImages& im, hipStream_t s) {
-  pack_layer_mfma_kernel<<<64, 256, 0, s>>>(w, bias, base + im.taps, base + im.bias, cin, cout, 27);
-  pack_layer_wino_kernel<<<64, 256, 0, s>>>(w, base + im.wino2, cin, cout, 3);
-  repack_wino3_kernel<<<64, 256, 0, s>>>(base + im.wino2, base + im.wino3, cin, cout, 3, wino3_rw(cout));
+void pack_mfma_images(bool is3d, const float* w, const float* bias, int cin, int cout, float* base, const MfmaImages& im, hipStream_t s) {
+  const int kd = is3d ? 3 : 1;
+  pack_layer_mfma_kernel<<<64, 256, 0, s>>>(w, bias, base + im.taps, base + im.bias, cin, cout, 9 * kd);
+  pack_layer_wino_kernel<<<64, 256, 0, s>>>(w, base + im.wino2, cin, cout, kd);
+  repack_wino3_kernel<<<64, 256, 0, s>>>(base + im.wino2, base + im.wino3, cin, cout, kd, wino3_rw(cout));
   if (im.wide) {
-    pack_wbf_kernel<<<256, 256, 0, s>>>(base + im.wino2, (unsigned*)(base + im.wbf), cin, cout, 3);
-    pack_layer_wino4g_kernel<<<64, 256, 0, s>>>(w, base + im.wino4, cin, cout, 3);
+    pack_wbf_kernel<<<256, 256, 0, s>>>(base + im.wino2, (unsigned*)(base + im.wbf), cin, cout, kd);
+    pack_layer_wino4g_kernel<<<64, 256, 0, s>>>(w, base + im.wino4, cin, cout, kd);
   }
 }
-bool conv_mfma_images3d(const MfmaImages& im, const float* base, int cin, int cout, int relu, int mode, const float* x, float* y, int B,
-                        int D, int H, int W, hipStream_t s) {
+bool conv_mfma_images(bool is3d, const MfmaImages& im, const float* base, int cin, int cout, int relu, int mode, const float* x, float* y,
+                      int B, int D, int H, int W, hipStream_t s) {
   const ConvArgs a{x, y, base + im.taps, base + im.bias, B, cin, cout, D, H, W, relu, cout / co_tile(cout), nullptr, nullptr};
-  return launch_conv_mfma_family(a, true, mode, im.wide, base + im.wbf, base + im.wino4, base + im.wino3, s);
+  return launch_conv_mfma_family(a, is3d, mode, im.wide, base + im.wbf, base + im.wino4, base + im.wino3, s);
 }
 
 size_t scalenet_weight_floats(bool is3d) {
