@@ -2,15 +2,15 @@
 """The reference's `pytorch/plume.py` main loop on this backend -- what a driver looks like after the switch.
 
     python examples/plume.py [--res 128] [--iters 200] [--out-iter 50] [--method jacobi|pcg|convnet] [--weights CKPT] [--vorticity AMP]
-                             [--depth N] [--render] [--folder out] [--restart]
+                             [--depth N] [--weights3d CKPT] [--render] [--folder out] [--restart]
 
 Same structure as the reference driver (plume.py:66-178 setup, :231-424 loop): build the batch, `createPlumeBCs`, optional
 restart from `<folder>/restart.pth`, echo the configuration as YAML, then `simulate()` per iteration and, every `out-iter`
 iterations, the PNG panels, the VTK cell data and the restart file.  Only the import line differs from a reference-side
 driver: `lib` -> `fluidnet_cxx_amd`.  `--method convnet --weights CKPT` projects with a trained net: CKPT is what examples/train.py
 writes ({'state_dict', 'mconf', ...}), loaded the way the reference driver loads convModel_lastEpoch_best.pth (plume.py:119-123).
-`--depth N` (N > 1) runs the 3D plume on a N x res x res grid (jacobi, pcg and --vorticity as in 2D; there are no 3D weights, so not
-convnet); `--render` adds volume renderings of the density (output.save_render: from the front, lit from above, and from the side)
+`--depth N` (N > 1) runs the 3D plume on a N x res x res grid (jacobi, pcg and --vorticity as in 2D); there `--method convnet` takes
+`--weights3d CKPT`, a checkpoint of `examples/train.py --depth N` (the 3D net; a 2D checkpoint given by --weights is refused).  `--render` adds volume renderings of the density (output.save_render: from the front, lit from above, and from the side)
 to every output event."""
 import argparse
 import os
@@ -34,6 +34,8 @@ def parser():
     ap.add_argument("--weights", default=None, metavar="CKPT", help="checkpoint of examples/train.py (needed by --method convnet)")
     ap.add_argument("--vorticity", type=float, default=0.0, metavar="AMP",
                     help="vorticity confinement amplitude (mconf['vorticityConfinementAmp'], no reference key; 0 = off)")
+    ap.add_argument("--weights3d", default=None, metavar="CKPT",
+                    help="checkpoint of examples/train.py --depth N (needed by --method convnet with --depth > 1)")
     ap.add_argument("--depth", type=int, default=1, metavar="N", help="cells along z; 1 (default) is the 2D plume, N > 1 the 3D one")
     ap.add_argument("--render", action="store_true", help="write volume renderings (render_<view>_<it>.png) with every output event")
     ap.add_argument("--folder", default="plume_out")
@@ -46,8 +48,17 @@ def parse_args(argv=None):
     a = ap.parse_args(argv)
     if a.depth < 1 or a.depth == 2:
         ap.error("--depth must be 1 (2D) or at least 3")
-    if a.method == "convnet" and a.depth > 1:
-        ap.error("--method convnet with --depth > 1: no 3D weights can be trained here (examples/train.py trains the 2D net only)")
+    if a.depth > 1:
+        if a.weights is not None:
+            ap.error("--weights with --depth > 1: no 3D weights can be trained here by the 2D trainer this checkpoint comes from; "
+                     "train the 3D net with examples/train.py --depth N and pass its checkpoint as --weights3d CKPT")
+        if (a.method == "convnet") != (a.weights3d is not None):
+            ap.error("--method convnet with --depth > 1 needs --weights3d CKPT, and --weights3d is only read by --method convnet")
+        if a.method == "convnet" and a.depth < 4:
+            ap.error("--method convnet needs --depth of at least 4 (the net's three scales)")
+        return a
+    if a.weights3d is not None:
+        ap.error("--weights3d is a 3D checkpoint: it needs --depth N (N > 1)")
     if (a.method == "convnet") != (a.weights is not None):
         ap.error("--method convnet needs --weights CKPT, and --weights is only read by --method convnet")
     return a
@@ -66,8 +77,9 @@ def main(argv=None):
         simConf.update(vorticityConfinementAmp=a.vorticity)
     net = None
     if a.method == "convnet":                             # plume.py:119-123
-        state = torch.load(a.weights, map_location="cpu", weights_only=False)
+        state = torch.load(a.weights3d if a.depth > 1 else a.weights, map_location="cpu", weights_only=False)
         mconf = state["mconf"]
+        assert bool(mconf.get("is3D", False)) == (a.depth > 1), "the checkpoint's net has another dimension than the grid"
         net = FluidNet(mconf, dropout=False)
         net = net.cuda()
         net.load_state_dict(state["state_dict"])

@@ -1,13 +1,16 @@
 #!/usr/bin/env python3
-"""Train the 2D pressure net on one GPU, with nothing downloaded -- what the reference's `pytorch/fluid_net_train.py` does with a
-Mantaflow data set, on scenes generated while training (fluidnet_cxx_amd/training.py).
+"""Train the 2D or the 3D pressure net on one GPU, with nothing downloaded -- what the reference's `pytorch/fluid_net_train.py` does with a
+Mantaflow data set, on scenes generated while training (fluidnet_cxx_amd/training.py; with --depth fluidnet_cxx_amd/training3d.py).
 
     python examples/train.py [--res 128] [--batch 64] [--iters 1000] [--seed 0] [--out convModel.pth] [--lr 5e-5] [--eval-every 50]
-                             [--no-long-term] [--resume CKPT] [--report FILE]
+                             [--no-long-term] [--resume CKPT] [--report FILE] [--depth N]
 
 Writes a checkpoint {'state_dict', 'optimizer', 'mconf', 'it', ...} that `FluidNet.load_state_dict` takes and
 `examples/plume.py --method convnet --weights` runs.  With --report the loss curve, the held-out ratio divL2(net's U) / divL2(U before
-the projection) and the number of Jacobi sweeps that reach the same held-out divL2 on the same scenes go to FILE as text."""
+the projection) and the number of Jacobi sweeps that reach the same held-out divL2 on the same scenes go to FILE as text.
+
+`--depth N` (N >= 4) trains the 3D net on a N x res x res grid instead (the defaults become --res 64 --batch 4); its checkpoint goes to
+`examples/plume.py --depth N --method convnet --weights3d`.  The report then has no Jacobi line."""
 import argparse
 import os
 import sys
@@ -19,10 +22,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from fluidnet_cxx_amd.training import MCONF_DEFAULTS, evaluate, jacobi_divL2, jacobi_sweeps_to_reach, lambdas_of, train      # noqa: E402
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--res", type=int, default=128)
-    ap.add_argument("--batch", type=int, default=64)             # trainConfig.yaml: batchSize
+    ap.add_argument("--res", type=int, default=None, help="cells along x and y (default 128; 64 with --depth)")
+    ap.add_argument("--batch", type=int, default=None, help="default 64 (trainConfig.yaml: batchSize); 4 with --depth")
     ap.add_argument("--iters", type=int, default=1000)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default="convModel.pth")
@@ -31,24 +34,42 @@ def main(argv=None):
     ap.add_argument("--no-long-term", action="store_true", help="divLongTermLambda = 0 (the reference's default is 1)")
     ap.add_argument("--resume", default=None, metavar="CKPT")
     ap.add_argument("--report", default=None, metavar="FILE")
+    ap.add_argument("--depth", type=int, default=None, metavar="N", help="train the 3D net on N x res x res cells (N >= 4)")
     a = ap.parse_args(argv)
-    mconf = dict(MCONF_DEFAULTS, lr=a.lr)
+    if a.depth is not None and a.depth < 4:
+        ap.error("--depth must be at least 4 (the net's three scales need 4 planes); without --depth the 2D net is trained")
+    is3d = a.depth is not None
+    a.res = a.res if a.res is not None else (64 if is3d else 128)
+    a.batch = a.batch if a.batch is not None else (4 if is3d else 64)
+    return a
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    is3d = a.depth is not None
+    if is3d:
+        from fluidnet_cxx_amd.training3d import MCONF3D_DEFAULTS, evaluate3d, train3d
+    mconf = dict(MCONF3D_DEFAULTS if is3d else MCONF_DEFAULTS, lr=a.lr)
     if a.no_long_term:
         mconf["divLongTermLambda"] = 0.0
     tconf = dict(res=a.res, batch=a.batch, iters=a.iters, seed=a.seed, evalEvery=a.eval_every)
     t0 = time.time()
-    run = train(mconf, tconf, torch.device("cuda"), out=a.out, resume=a.resume, log=print)
+    if is3d:
+        run = train3d(mconf, dict(tconf, D=a.depth), torch.device("cuda"), out=a.out, resume=a.resume, log=print)
+    else:
+        run = train(mconf, tconf, torch.device("cuda"), out=a.out, resume=a.resume, log=print)
     torch.cuda.synchronize()
     seconds = time.time() - t0
     lam = lambdas_of(mconf)
-    ev = evaluate(run["net"], run["held_out"], lam)
+    ev = (evaluate3d if is3d else evaluate)(run["net"], run["held_out"], lam)
     ratio = ev["divL2_out"] / ev["divL2_in"]
-    sweeps = jacobi_sweeps_to_reach(run["held_out"], ev["divL2_out"])
-    lines = [f"examples/train.py --res {a.res} --batch {a.batch} --iters {a.iters} --seed {a.seed} --lr {a.lr:g}"
+    sweeps = None if is3d else jacobi_sweeps_to_reach(run["held_out"], ev["divL2_out"])
+    lines = [f"examples/train.py{f' --depth {a.depth}' if is3d else ''} --res {a.res} --batch {a.batch} --iters {a.iters} --seed {a.seed} --lr {a.lr:g}"
              f"{' --no-long-term' if a.no_long_term else ''}: {seconds:.1f} s wall ({seconds / max(a.iters, 1) * 1e3:.1f} ms per iteration, "
              "sampler, evaluation and checkpoint included)",
              f"held-out ({len(run['held_out'])} batches of another seed): loss {ev['loss']:.4e}, divL2 of the net's U {ev['divL2_out']:.4e}, "
              f"divL2 of U before the projection {ev['divL2_in']:.4e}, ratio {ratio:.4e}",
+             "Jacobi sweeps that reach the same held-out divL2: not searched in 3D" if is3d else
              f"Jacobi sweeps that reach the same held-out divL2 on the same scenes: {sweeps}"
              + ("" if sweeps is None else f" (divL2 {jacobi_divL2(run['held_out'], sweeps):.4e}; {max(sweeps - 1, 1)} sweeps: "
                                           f"{jacobi_divL2(run['held_out'], max(sweeps - 1, 1)):.4e})"),

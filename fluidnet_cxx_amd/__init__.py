@@ -4,6 +4,7 @@
     from fluidnet_cxx_amd import FluidNetTrain                 # the same net with a native backward pass (2D)
     from fluidnet_cxx_amd import FluidNetTrain3D               # ... and its Conv3d counterpart (3D grids)
     from fluidnet_cxx_amd.training import train, SceneSampler  # the training loop on scenes generated on the device (2D)
+    from fluidnet_cxx_amd.training3d import train3d, SceneSampler3D   # ... and in 3D
 
 Importing the operator modules loads the native extension; there is no CPU fallback.
 """

@@ -826,6 +826,73 @@ std::vector<Tensor> train_loss(Tensor out_p, Tensor out_U, Tensor flags, c10::op
   return {t, gp, gU};
 }
 
+// ---- the same in 3D (ABI 26; entry points of their own, the C ABI refuses a 2D grid before it touches the device) ----------------
+static FnxGrid scene_grid3d(int64_t B, int64_t D, int64_t H, int64_t W, const char* fn) {
+  TORCH_CHECK(D >= 1 && H >= 1 && W >= 1, fn, ": D, H and W must be positive");
+  FnxGrid g = grid2d(B, H, W);
+  g.D = (int)D; g.is3D = D > 1;
+  return g;
+}
+// -> flags (B,1,D,H,W)
+Tensor scene_obstacles3d(Tensor scene_ids, int64_t D, int64_t H, int64_t W, int64_t seed, int n_min, int n_max, double centre_min,
+                         double centre_max, double size_min, double size_max) {
+  check_scene_ids(scene_ids);
+  const FnxGrid g = scene_grid3d(scene_ids.numel(), D, H, W, "scene_obstacles3d");
+  FnxSceneParams prm{};
+  prm.seed = (unsigned)seed; prm.n_min = n_min; prm.n_max = n_max;
+  prm.centre_min = (float)centre_min; prm.centre_max = (float)centre_max; prm.size_min = (float)size_min; prm.size_max = (float)size_max;
+  c10::hip::HIPGuard guard(scene_ids.get_device());
+  Tensor flags = at::empty({g.B, 1, D, H, W}, scene_ids.options().dtype(at::kFloat));
+  check_status(fnx_scene_obstacles3d(&g, &prm, scene_ids.data_ptr<int>(), flags.data_ptr<float>(), cur_stream(scene_ids)));
+  return flags;
+}
+// -> U (B,3,D,H,W), density (B,1,D,H,W) or None
+std::vector<Tensor> scene_turbulence3d(Tensor scene_ids, int64_t D, int64_t H, int64_t W, int64_t seed, int octaves, double wavelength,
+                                       double amplitude, double density_scale, bool with_density) {
+  check_scene_ids(scene_ids);
+  const FnxGrid g = scene_grid3d(scene_ids.numel(), D, H, W, "scene_turbulence3d");
+  FnxSceneParams prm{};
+  prm.seed = (unsigned)seed; prm.octaves = octaves; prm.wavelength = (float)wavelength; prm.amplitude = (float)amplitude;
+  prm.density_scale = (float)density_scale;
+  c10::hip::HIPGuard guard(scene_ids.get_device());
+  Tensor U = at::empty({g.B, 3, D, H, W}, scene_ids.options().dtype(at::kFloat));
+  Tensor rho = with_density ? at::empty({g.B, 1, D, H, W}, U.options()) : Tensor();
+  check_status(fnx_scene_turbulence3d(&g, &prm, scene_ids.data_ptr<int>(), U.data_ptr<float>(), with_density ? rho.data_ptr<float>() : nullptr,
+                                      cur_stream(scene_ids)));
+  return {U, rho};
+}
+// train_loss for out_p (B,1,D,H,W), out_U (B,3,D,H,W)
+std::vector<Tensor> train_loss3d(Tensor out_p, Tensor out_U, Tensor flags, c10::optional<Tensor> target_p, std::vector<double> lambdas,
+                                 c10::optional<Tensor> upstream, bool terms) {
+  check_field(out_U, "out_U");
+  TORCH_CHECK(lambdas.size() == 4, "lambdas must be (pL2, divL2, pL1, divL1)");
+  TORCH_CHECK(out_U.size(1) == 2 || out_U.size(1) == 3, "out_U must have 2 or 3 channels");
+  FnxGrid g = grid_of(flags, out_U.size(1) == 3, nullptr);
+  check_scalar(out_p, g, "out_p");
+  TORCH_CHECK(out_U.size(0) == g.B && out_U.size(2) == g.D && out_U.size(3) == g.H && out_U.size(4) == g.W, "Size mismatch");
+  const bool has_t = target_p.has_value() && target_p->defined();
+  if (has_t) check_scalar(*target_p, g, "target_p");
+  const bool grads = upstream.has_value() && upstream->defined();
+  if (grads)
+    TORCH_CHECK(upstream->is_cuda() && upstream->scalar_type() == at::kFloat && upstream->numel() == 1 && upstream->get_device() == out_p.get_device(),
+                "upstream must be one float32 on the GPU");
+  c10::hip::HIPGuard guard(out_p.get_device());
+  const float lam[4] = {(float)lambdas[0], (float)lambdas[1], (float)lambdas[2], (float)lambdas[3]};
+  Tensor t, gp, gU, ws;
+  size_t bytes = 0;
+  if (terms) {
+    t = at::empty({5}, out_p.options());
+    bytes = fnx_train_loss3d_ws_bytes(&g);             // 0 for a grid the call below refuses
+    ws = at::empty({(int64_t)(bytes ? bytes : 1)}, out_p.options().dtype(at::kByte));
+  }
+  if (grads) { gp = at::empty_like(out_p); gU = at::empty_like(out_U); }
+  check_status(fnx_train_loss3d(&g, out_p.data_ptr<float>(), out_U.data_ptr<float>(), flags.data_ptr<float>(),
+                                has_t ? target_p->data_ptr<float>() : nullptr, lam, grads ? upstream->data_ptr<float>() : nullptr,
+                                terms ? t.data_ptr<float>() : nullptr, grads ? gp.data_ptr<float>() : nullptr,
+                                grads ? gU.data_ptr<float>() : nullptr, terms ? ws.data_ptr() : nullptr, bytes, cur_stream(out_p)));
+  return {t, gp, gU};
+}
+
 // one whole step of lib/simulate.py:28-171, in place on p, U, density
 void simulate_step_(Tensor p, Tensor U, Tensor flags, c10::optional<Tensor> density, c10::optional<Tensor> UBC,
                     c10::optional<Tensor> UBCInvMask, c10::optional<Tensor> densityBC,
@@ -1338,6 +1405,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fluidnet3d_backward", &fluidnet3d_backward, py::arg("packed_t"), py::arg("flags"), py::arg("scale"), py::arg("grad_p"),
         py::arg("grad_U"), py::arg("tape"), py::arg("precision_mode") = "fp32", NoGil());
   m.def("train_loss", &train_loss, py::arg("out_p"), py::arg("out_U"), py::arg("flags"), py::arg("target_p"), py::arg("lambdas"),
+        py::arg("upstream") = py::none(), py::arg("terms") = true, NoGil());
+  m.def("scene_obstacles3d", &scene_obstacles3d, py::arg("scene_ids"), py::arg("D"), py::arg("H"), py::arg("W"), py::arg("seed"), py::arg("n_min"),
+        py::arg("n_max"), py::arg("centre_min"), py::arg("centre_max"), py::arg("size_min"), py::arg("size_max"), NoGil());
+  m.def("scene_turbulence3d", &scene_turbulence3d, py::arg("scene_ids"), py::arg("D"), py::arg("H"), py::arg("W"), py::arg("seed"), py::arg("octaves"),
+        py::arg("wavelength"), py::arg("amplitude"), py::arg("density_scale"), py::arg("with_density") = true, NoGil());
+  m.def("train_loss3d", &train_loss3d, py::arg("out_p"), py::arg("out_U"), py::arg("flags"), py::arg("target_p"), py::arg("lambdas"),
         py::arg("upstream") = py::none(), py::arg("terms") = true, NoGil());
   m.def("abi_version", &fnx_abi_version);
   m.def("profile_enable", [](bool on, bool runs) { fnx_profile_enable(on ? (runs ? 2 : 1) : 0); }, py::arg("on"), py::arg("runs") = false);

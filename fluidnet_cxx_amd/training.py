@@ -13,9 +13,12 @@ torch carries the tensors (allocation, copies, concatenation, the optimiser); th
 Every random choice comes from the counter-based hash of the scene kernels (include/fluidnet_hip.h), evaluated on the host for the
 per-call choices: torch's global generator is never used, and one seed gives the same batches and the same trained bits.
 
-2D only, like FluidNetTrain: a 3D grid is refused before the device is touched.
+2D only, like FluidNetTrain: a 3D grid is refused before the device is touched.  fluidnet_cxx_amd/training3d.py is the 3D counterpart;
+the bodies that do not depend on the dimension stand here once, in private bases (_SceneSamplerBase, _train, _evaluate, _loss_fn) that
+both modules use -- the precedent is train._FluidNetTrainBase -- and a `_Dim` record says what does depend on it.
 """
 import copy
+
 
 import torch
 
@@ -66,28 +69,50 @@ def host_normal(seed, scene, stream, counter):
     return sum(host_uniform(seed, scene, stream, counter + k) for k in range(12)) - 6.0
 
 
+def lambdas_of(mconf):
+    return [float(mconf.get(k, 0.0)) for k in ("pL2Lambda", "divL2Lambda", "pL1Lambda", "divL1Lambda")]
+
+
 def _refuse_3d(what, *sizes):
     if any(int(s) != 1 for s in sizes):
         raise ValueError(f"fluidnet_cxx_amd.training.{what}: training is 2D only (depth {[int(s) for s in sizes]})")
 
 
-# ---- the loss -------------------------------------------------------------------------------------------------------------------------
-class _LossFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, out_p, out_U, flags, target_p, lambdas):
-        out_p, out_U = out_p.contiguous(), out_U.contiguous()
-        terms5 = ext.train_loss(out_p, out_U, flags, target_p, lambdas, None, True)[0]
-        ctx.save_for_backward(out_p, out_U, flags, target_p)
-        ctx.lambdas = lambdas
-        total, terms = terms5[4].clone(), terms5[:4].clone()
-        ctx.mark_non_differentiable(terms)
-        return total, terms
+# ---- what depends on the dimension ----------------------------------------------------------------------------------------------------
+class _Dim:
+    """what the loop needs to know about the dimension: `nU` velocity channels (data = [p, U (nU), flags, density]), the net's class, the
+    sampler's constructor (mconf, B, dims, seed, device, scene, sceneLength, stride), the differentiable loss and the loss kernel's binding"""
 
-    @staticmethod
-    def backward(ctx, g_total, _g_terms):
-        out_p, out_U, flags, target_p = ctx.saved_tensors
-        _, gp, gU = ext.train_loss(out_p, out_U, flags, target_p, ctx.lambdas, g_total.contiguous().reshape(1), False)
-        return gp, gU, None, None, None
+    def __init__(self, nU, net, sampler, loss, raw_loss):
+        self.nU, self.net, self.sampler, self.loss, self.raw_loss = nU, net, sampler, loss, raw_loss
+        self.iU, self.iflags, self.irho = slice(1, 1 + nU), slice(1 + nU, 2 + nU), slice(2 + nU, 3 + nU)
+
+
+# ---- the loss -------------------------------------------------------------------------------------------------------------------------
+def _loss_fn(raw_loss):
+    """the autograd function around one loss kernel binding (ext.train_loss / ext.train_loss3d)"""
+
+    class _LossFn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, out_p, out_U, flags, target_p, lambdas):
+            out_p, out_U = out_p.contiguous(), out_U.contiguous()
+            terms5 = raw_loss(out_p, out_U, flags, target_p, lambdas, None, True)[0]
+            ctx.save_for_backward(out_p, out_U, flags, target_p)
+            ctx.lambdas = lambdas
+            total, terms = terms5[4].clone(), terms5[:4].clone()
+            ctx.mark_non_differentiable(terms)
+            return total, terms
+
+        @staticmethod
+        def backward(ctx, g_total, _g_terms):
+            out_p, out_U, flags, target_p = ctx.saved_tensors
+            _, gp, gU = raw_loss(out_p, out_U, flags, target_p, ctx.lambdas, g_total.contiguous().reshape(1), False)
+            return gp, gU, None, None, None
+
+    return _LossFn
+
+
+_LossFn = _loss_fn(ext.train_loss)
 
 
 def fluidnet_loss(out_p, out_U, flags, target_p, lambdas):
@@ -103,30 +128,18 @@ def fluidnet_loss(out_p, out_U, flags, target_p, lambdas):
     return _LossFn.apply(out_p, out_U, flags.contiguous(), target_p, lam)
 
 
-def lambdas_of(mconf):
-    return [float(mconf.get(k, 0.0)) for k in ("pL2Lambda", "divL2Lambda", "pL1Lambda", "divL1Lambda")]
-
-
 # ---- the sampler ----------------------------------------------------------------------------------------------------------------------
-class SceneSampler:
-    """B scenes of H x W cells advancing in lock step.  Scene b has an age (solver steps since it was drawn); once it reaches
-    `sceneLength` the slot is redrawn under the next unused scene id.  Ages start staggered (slot b at b sceneLength // B), so a batch
-    mixes young and old scenes.
+class _SceneSamplerBase:
+    """B scenes advancing in lock step.  A subclass gives `_IS3D`, `draw(ids)` -> (flags, U, density) from its scene kernels and
+    `_gravity(h)` -> (axis, sign) from one hash word."""
 
-    A redraw: obstacles, turbulence and density from the scene kernels, setWallBcs, one 'pcg' projection.
-    next(): `stride` full 'pcg' steps; then the stages of one more step up to the projection on the operator path (advection, buoyancy,
-    setWallBcs) -> data; the 'pcg' projection -> target.  Per call, from the hash on the host: the gravity direction (+-x / +-y), with
-    probability trainBuoyancyProb a buoyancy scale trainBuoyancyScale + n, and the time step dt (0.2028 + |n| timeScaleSigma), n the
-    host_normal variate (fluid_net_train.py:296-339).  `last_choice` holds them for the caller (the trainer's rollout uses the same)."""
+    _IS3D = False
 
-    def __init__(self, mconf, B, H, W, seed, device="cuda", scene=None, sceneLength=32, stride=2, depth=1):
-        _refuse_3d("SceneSampler", depth)
-        if mconf.get("is3D", False):
-            raise ValueError("fluidnet_cxx_amd.training.SceneSampler: training is 2D only (is3D=True)")
-        self.mconf = dict(MCONF_DEFAULTS, **mconf)
-        self.B, self.H, self.W, self.seed = int(B), int(H), int(W), int(seed) & 0xffffffff
+    def _init(self, mconf, B, seed, device, scene_defaults, scene, sceneLength, stride):
+        self.mconf = mconf
+        self.B, self.seed = int(B), int(seed) & 0xffffffff
         self.device = torch.device(device)
-        self.scene = dict(SCENE_DEFAULTS, **(scene or {}))
+        self.scene = dict(scene_defaults, **(scene or {}))
         self.sceneLength, self.stride = int(sceneLength), int(stride)
         assert self.B >= 1 and self.sceneLength >= 1 and self.stride >= 0
         self.age = [(b * self.sceneLength) // self.B for b in range(self.B)]
@@ -138,19 +151,9 @@ class SceneSampler:
         self.bd = {}
         self._redraw(list(range(self.B)), keep_age=True)
 
-    # -- scenes
-    def draw(self, ids):
-        """(flags, U, density) of the scenes `ids`, as the kernels give them (no boundary condition applied)"""
-        s = self.scene
-        t = torch.tensor([int(i) for i in ids], dtype=torch.int32, device=self.device)
-        flags = ext.scene_obstacles(t, self.H, self.W, self.seed, s["n_min"], s["n_max"], s["centre_min"], s["centre_max"], s["size_min"],
-                                    s["size_max"])
-        U, rho = ext.scene_turbulence(t, self.H, self.W, self.seed, s["octaves"], s["wavelength"], s["amplitude"], s["density_scale"], True)
-        return flags, U, rho
-
     def _project(self, U, flags):
         div = fluid.velocityDivergence(U, flags)
-        p, _ = fluid.solveLinearSystemPCG(flags, div, False, self.mconf["pcgTol"], self.mconf["pcgIter"])
+        p, _ = fluid.solveLinearSystemPCG(flags, div, self._IS3D, self.mconf["pcgTol"], self.mconf["pcgIter"])
         fluid.velocityUpdate(p, U, flags)
         fluid.setWallBcs(U, flags)
         return p
@@ -189,8 +192,7 @@ class SceneSampler:
         buoyancy = float(m["buoyancyScale"])
         if host_uniform(s, call, _STREAM_SAMPLER, 0) < m["trainBuoyancyProb"]:
             buoyancy = float(m["trainBuoyancyScale"]) + host_normal(s, call, _STREAM_SAMPLER, 16)
-        h = host_hash(s, call, _STREAM_SAMPLER, 1)
-        axis, sign = ("x", "y")[h & 1], float(((h >> 1) & 1) * 2 - 1)
+        axis, sign = self._gravity(host_hash(s, call, _STREAM_SAMPLER, 1))
         gvec = dict(x=0.0, y=0.0, z=0.0)
         gvec[axis] = sign
         dt = float(m["dt"])
@@ -244,6 +246,42 @@ class SceneSampler:
         self.bd = {k: v.to(self.device).contiguous() for k, v in sd["fields"].items()}
 
 
+class SceneSampler(_SceneSamplerBase):
+    """B scenes of H x W cells advancing in lock step.  Scene b has an age (solver steps since it was drawn); once it reaches
+    `sceneLength` the slot is redrawn under the next unused scene id.  Ages start staggered (slot b at b sceneLength // B), so a batch
+    mixes young and old scenes.
+
+    A redraw: obstacles, turbulence and density from the scene kernels, setWallBcs, one 'pcg' projection.
+    next(): `stride` full 'pcg' steps; then the stages of one more step up to the projection on the operator path (advection, buoyancy,
+    setWallBcs) -> data; the 'pcg' projection -> target.  Per call, from the hash on the host: the gravity direction (+-x / +-y), with
+    probability trainBuoyancyProb a buoyancy scale trainBuoyancyScale + n, and the time step dt (0.2028 + |n| timeScaleSigma), n the
+    host_normal variate (fluid_net_train.py:296-339).  `last_choice` holds them for the caller (the trainer's rollout uses the same)."""
+
+    def __init__(self, mconf, B, H, W, seed, device="cuda", scene=None, sceneLength=32, stride=2, depth=1):
+        _refuse_3d("SceneSampler", depth)
+        if mconf.get("is3D", False):
+            raise ValueError("fluidnet_cxx_amd.training.SceneSampler: training is 2D only (is3D=True)")
+        self.H, self.W = int(H), int(W)
+        self._init(dict(MCONF_DEFAULTS, **mconf), B, seed, device, SCENE_DEFAULTS, scene, sceneLength, stride)
+
+    # -- scenes
+    def draw(self, ids):
+        """(flags, U, density) of the scenes `ids`, as the kernels give them (no boundary condition applied)"""
+        s = self.scene
+        t = torch.tensor([int(i) for i in ids], dtype=torch.int32, device=self.device)
+        flags = ext.scene_obstacles(t, self.H, self.W, self.seed, s["n_min"], s["n_max"], s["centre_min"], s["centre_max"], s["size_min"],
+                                    s["size_max"])
+        U, rho = ext.scene_turbulence(t, self.H, self.W, self.seed, s["octaves"], s["wavelength"], s["amplitude"], s["density_scale"], True)
+        return flags, U, rho
+
+    def _gravity(self, h):
+        return ("x", "y")[h & 1], float(((h >> 1) & 1) * 2 - 1)
+
+
+_DIM = _Dim(2, FluidNetTrain, lambda mconf, B, dims, *rest: SceneSampler(mconf, B, dims[0], dims[1], *rest), fluidnet_loss,
+            ext.train_loss)
+
+
 # ---- the trainer ----------------------------------------------------------------------------------------------------------------------
 def kaiming_init(net, seed):
     """fluid_net_train.py:170-187: kaiming_uniform_ on every convolution weight (the biases are left as constructed), from a generator of
@@ -258,21 +296,106 @@ def kaiming_init(net, seed):
     return net
 
 
-def evaluate(net, batches, lambdas):
-    """held-out figures under no_grad, averaged over `batches` [(data, target)]: the loss, divL2 of the net's U and divL2 of the U it was
-    given (before the projection)"""
+def _evaluate(dim, net, batches, lambdas):
     tot = []
     with torch.no_grad():
         for data, target in batches:
-            flags = data[:, 3:4].contiguous()
+            flags = data[:, dim.iflags].contiguous()
             tp = target[:, 0:1].contiguous() if (lambdas[0] or lambdas[2]) else None
             p, U = net(data)
-            t_out = ext.train_loss(p, U, flags, tp, lambdas, None, True)[0]
-            t_in = ext.train_loss(p, data[:, 1:3].contiguous(), flags, None, [0.0, 1.0, 0.0, 0.0], None, True)[0]
+            t_out = dim.raw_loss(p, U, flags, tp, lambdas, None, True)[0]
+            t_in = dim.raw_loss(p, data[:, dim.iU].contiguous(), flags, None, [0.0, 1.0, 0.0, 0.0], None, True)[0]
             tot.append((t_out, t_in))
     host = [(a.cpu().tolist(), b.cpu().tolist()) for a, b in tot]
     n = float(len(host))
     return dict(loss=sum(a[4] for a, _ in host) / n, divL2_out=sum(a[1] for a, _ in host) / n, divL2_in=sum(b[1] for _, b in host) / n)
+
+
+def _train(dim, mconf, tconf, dims, device, out, resume, log):
+    """the body of train() / train3d(): `dims` = (H, W) resp. (D, H, W), the configurations complete"""
+    dev = torch.device(device)
+    B, seed, iters = int(tconf["batch"]), int(tconf["seed"]), int(tconf["iters"])
+    lam = lambdas_of(mconf)
+    lt_lambda = float(mconf["divLongTermLambda"])
+    say = log if log is not None else (lambda *_: None)
+
+    net = dim.net(mconf)
+    kaiming_init(net, seed)
+    net.to(dev).train()
+    opt = torch.optim.Adam(net.parameters(), lr=float(mconf["lr"]))
+    sched = torch.optim.lr_scheduler.ReduceLROnPlateau(opt, mode="min", factor=0.6, patience=10, threshold=3e-4, threshold_mode="rel")
+    sampler = dim.sampler(mconf, B, dims, seed, dev, tconf.get("scene"), tconf["sceneLength"], tconf["stride"])
+    held = dim.sampler(mconf, B, dims, seed ^ 0x5eed5eed, dev, tconf.get("scene"), tconf["sceneLength"], tconf["stride"])
+    held_out = [held.next() for _ in range(int(tconf["evalBatches"]))]
+    it0, history = 0, []
+    if resume is not None:
+        ck = torch.load(resume, map_location="cpu", weights_only=False) if isinstance(resume, str) else resume
+        net.load_state_dict(ck["state_dict"])
+        opt.load_state_dict(ck["optimizer"])
+        sched.load_state_dict(ck["scheduler"])
+        sampler.load_state_dict(ck["sampler"])
+        it0, history = int(ck["it"]), list(ck.get("history", []))
+
+    def checkpoint(it):
+        ck = dict(state_dict={k: v.detach().cpu().clone() for k, v in net.state_dict().items()}, optimizer=copy.deepcopy(opt.state_dict()),
+                  mconf=mconf, it=it, scheduler=copy.deepcopy(sched.state_dict()), sampler=sampler.state_dict(), tconf=tconf,
+                  history=list(history))
+        if out:
+            torch.save(ck, out)
+        return ck
+
+    one = torch.ones((), device=dev)
+    lt_weight = torch.full((), lt_lambda, device=dev)
+    pending = []                                          # (it, total, long-term total or None, lr): read back in one go
+    for it in range(it0, iters):
+        data, target = sampler.next()
+        opt.zero_grad()
+        flags = data[:, dim.iflags].contiguous()
+        target_p = target[:, 0:1].contiguous() if (lam[0] or lam[2]) else None
+        out_p, out_U = net(data)
+        total, _ = dim.loss(out_p, out_U, flags, target_p, lam)
+        roots, weights, total_lt = [total], [one], None
+        if lt_lambda > 0:
+            # fluid_net_train.py:341-375: some steps into the future with the net as it is (no gradient), then the divergence the net
+            # leaves there.  The sampler's choices of this call (time step, buoyancy, gravity direction) hold for the rollout too.
+            steps = mconf["longTermDivNumSteps"]
+            n = int(steps[1] if host_uniform(seed, it, _STREAM_TRAINER, 0) > mconf["longTermDivProbability"] else steps[0])
+            bd = dict(p=out_p.detach().clone(), U=out_U.detach().clone(), flags=flags, density=data[:, dim.irho].contiguous())
+            conf = sampler.sim_conf(sampler.last_choice)
+            with torch.no_grad():
+                for _ in range(n):
+                    simulate(conf, bd, net, "convnet")
+            data_lt = torch.cat((bd["p"], bd["U"], flags, bd["density"]), 1)
+            p_lt, U_lt = net(data_lt)
+            total_lt, _ = dim.loss(p_lt, U_lt, flags, None, [0.0, 1.0, 0.0, 0.0])
+            roots.append(total_lt)
+            weights.append(lt_weight)
+        torch.autograd.backward(roots, weights)
+        opt.step()
+        pending.append((it, total.detach(), None if total_lt is None else total_lt.detach(), opt.param_groups[0]["lr"]))
+        done = it + 1
+        evaluating = tconf["evalEvery"] and done % int(tconf["evalEvery"]) == 0
+        saving = tconf["saveEvery"] and done % int(tconf["saveEvery"]) == 0 and done != iters
+        if evaluating or saving or done == iters:
+            for i, a, b, lr in pending:
+                history.append(dict(it=i, loss=float(a), lt=None if b is None else float(b), lr=lr))
+            pending = []
+        if evaluating:
+            ev = _evaluate(dim, net, held_out, lam)
+            sched.step(ev["loss"])
+            history[-1].update(val=ev["loss"], val_divL2_out=ev["divL2_out"], val_divL2_in=ev["divL2_in"])
+            say(f"it {done:6d}  loss {history[-1]['loss']:.4e}  long-term {history[-1]['lt']}  held-out {ev['loss']:.4e}  "
+                f"divL2 out/in {ev['divL2_out'] / max(ev['divL2_in'], 1e-300):.4e}  lr {opt.param_groups[0]['lr']:.3e}")
+        if saving:
+            checkpoint(done)
+    ck = checkpoint(iters)
+    return dict(net=net, checkpoint=ck, history=history, held_out=held_out, sampler=sampler)
+
+
+def evaluate(net, batches, lambdas):
+    """held-out figures under no_grad, averaged over `batches` [(data, target)]: the loss, divL2 of the net's U and divL2 of the U it was
+    given (before the projection)"""
+    return _evaluate(_DIM, net, batches, lambdas)
 
 
 def jacobi_divL2(batches, sweeps):
@@ -312,81 +435,5 @@ def train(mconf=None, tconf=None, device="cuda", out=None, resume=None, log=None
     if mconf.get("is3D", False):
         raise ValueError("fluidnet_cxx_amd.training.train: training is 2D only (is3D=True)")
     _refuse_3d("train", tconf.get("D", 1))
-    dev = torch.device(device)
     H, W = int(tconf.get("H", tconf["res"])), int(tconf.get("W", tconf["res"]))
-    B, seed, iters = int(tconf["batch"]), int(tconf["seed"]), int(tconf["iters"])
-    lam = lambdas_of(mconf)
-    lt_lambda = float(mconf["divLongTermLambda"])
-    say = log if log is not None else (lambda *_: None)
-
-    net = FluidNetTrain(mconf)
-    kaiming_init(net, seed)
-    net.to(dev).train()
-    opt = torch.optim.Adam(net.parameters(), lr=float(mconf["lr"]))
-    sched = torch.optim.lr_scheduler.ReduceLROnPlateau(opt, mode="min", factor=0.6, patience=10, threshold=3e-4, threshold_mode="rel")
-    sampler = SceneSampler(mconf, B, H, W, seed, dev, tconf.get("scene"), tconf["sceneLength"], tconf["stride"])
-    held = SceneSampler(mconf, B, H, W, seed ^ 0x5eed5eed, dev, tconf.get("scene"), tconf["sceneLength"], tconf["stride"])
-    held_out = [held.next() for _ in range(int(tconf["evalBatches"]))]
-    it0, history = 0, []
-    if resume is not None:
-        ck = torch.load(resume, map_location="cpu", weights_only=False) if isinstance(resume, str) else resume
-        net.load_state_dict(ck["state_dict"])
-        opt.load_state_dict(ck["optimizer"])
-        sched.load_state_dict(ck["scheduler"])
-        sampler.load_state_dict(ck["sampler"])
-        it0, history = int(ck["it"]), list(ck.get("history", []))
-
-    def checkpoint(it):
-        ck = dict(state_dict={k: v.detach().cpu().clone() for k, v in net.state_dict().items()}, optimizer=copy.deepcopy(opt.state_dict()),
-                  mconf=mconf, it=it, scheduler=copy.deepcopy(sched.state_dict()), sampler=sampler.state_dict(), tconf=tconf,
-                  history=list(history))
-        if out:
-            torch.save(ck, out)
-        return ck
-
-    one = torch.ones((), device=dev)
-    lt_weight = torch.full((), lt_lambda, device=dev)
-    pending = []                                          # (it, total, long-term total or None, lr): read back in one go
-    for it in range(it0, iters):
-        data, target = sampler.next()
-        opt.zero_grad()
-        flags = data[:, 3:4].contiguous()
-        target_p = target[:, 0:1].contiguous() if (lam[0] or lam[2]) else None
-        out_p, out_U = net(data)
-        total, _ = fluidnet_loss(out_p, out_U, flags, target_p, lam)
-        roots, weights, total_lt = [total], [one], None
-        if lt_lambda > 0:
-            # fluid_net_train.py:341-375: some steps into the future with the net as it is (no gradient), then the divergence the net
-            # leaves there.  The sampler's choices of this call (time step, buoyancy, gravity direction) hold for the rollout too.
-            steps = mconf["longTermDivNumSteps"]
-            n = int(steps[1] if host_uniform(seed, it, _STREAM_TRAINER, 0) > mconf["longTermDivProbability"] else steps[0])
-            bd = dict(p=out_p.detach().clone(), U=out_U.detach().clone(), flags=flags, density=data[:, 4:5].contiguous())
-            conf = sampler.sim_conf(sampler.last_choice)
-            with torch.no_grad():
-                for _ in range(n):
-                    simulate(conf, bd, net, "convnet")
-            data_lt = torch.cat((bd["p"], bd["U"], flags, bd["density"]), 1)
-            p_lt, U_lt = net(data_lt)
-            total_lt, _ = fluidnet_loss(p_lt, U_lt, flags, None, [0.0, 1.0, 0.0, 0.0])
-            roots.append(total_lt)
-            weights.append(lt_weight)
-        torch.autograd.backward(roots, weights)
-        opt.step()
-        pending.append((it, total.detach(), None if total_lt is None else total_lt.detach(), opt.param_groups[0]["lr"]))
-        done = it + 1
-        evaluating = tconf["evalEvery"] and done % int(tconf["evalEvery"]) == 0
-        saving = tconf["saveEvery"] and done % int(tconf["saveEvery"]) == 0 and done != iters
-        if evaluating or saving or done == iters:
-            for i, a, b, lr in pending:
-                history.append(dict(it=i, loss=float(a), lt=None if b is None else float(b), lr=lr))
-            pending = []
-        if evaluating:
-            ev = evaluate(net, held_out, lam)
-            sched.step(ev["loss"])
-            history[-1].update(val=ev["loss"], val_divL2_out=ev["divL2_out"], val_divL2_in=ev["divL2_in"])
-            say(f"it {done:6d}  loss {history[-1]['loss']:.4e}  long-term {history[-1]['lt']}  held-out {ev['loss']:.4e}  "
-                f"divL2 out/in {ev['divL2_out'] / max(ev['divL2_in'], 1e-300):.4e}  lr {opt.param_groups[0]['lr']:.3e}")
-        if saving:
-            checkpoint(done)
-    ck = checkpoint(iters)
-    return dict(net=net, checkpoint=ck, history=history, held_out=held_out, sampler=sampler)
+    return _train(_DIM, mconf, tconf, (H, W), device, out, resume, log)

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define FNX_ABI_VERSION 25
+#define FNX_ABI_VERSION 26
 
 enum {
   FNX_OK = 0,
@@ -787,6 +787,42 @@ size_t fnx_train_loss_ws_bytes(const FnxGrid* g);
 int fnx_train_loss(const FnxGrid* g, const float* out_p, const float* out_U, const float* flags, const float* target_p,
                    const float lambdas[4], const float* upstream, float* terms, float* grad_p, float* grad_U, void* ws, size_t ws_bytes,
                    void* stream);
+
+/* ---- Training scenes and the training loss in 3D (ABI 26; the reference has no 3D training at all).  The counterparts of the four
+ * entry points above under names of their own, as fnx_fluidnet3d_* stand next to fnx_fluidnet_*: the 2D names keep refusing a 3D grid.
+ * Every entry point checks before it touches the device, each case with its own text: a null argument ("null argument"); a 2D grid,
+ * is3D = 0 or D < 4, since the net's three scales need 4 planes ("3D only"); H or W below 4 ("at least 4 cells per axis"); an axis above
+ * 32768, B * D above 65535 or D * H * W of 2^31 and more (the range is stated); the parameter caps and inverted ranges of the 2D calls.
+ *
+ * The hash is the one above.  A lattice value at the integer point (lx, ly, lz) of octave o of a noise with the stream base s0 is
+ *   hash(seed, scene, stream = (lz << 8) | (s0 + o), counter = ly * 65536 + lx)
+ * -- the plane goes into the stream word above its low byte -- which is injective for lx, ly < 65536 and lz < 2^24, and the accepted
+ * grids stay inside that.  Stream bases: 80 = the obstacle primitives, 96 + o = psi_x, 112 + o = psi_y, 128 + o = psi_z, 144 + o = the
+ * density (the 2D kernels use 0, 16 + o, 32 + o; the samplers 64 and 65).  A scene's bits depend on (seed, scene id, D, H, W) and the
+ * parameters only.  Arithmetic as in 2D; tests/scene_reference_3d.py is the numpy statement and the kernels are bit-identical to it.
+ *
+ * Obstacles: flags (B,1,D,H,W) = a border shell one cell wide (TypeObstacle) united with n_min .. n_max primitives, each a ball or an
+ * axis-aligned box by one hash bit.  Primitive t draws at the counters 16 t + d of stream 80: d = 0 ball / box (the top bit),
+ * d = 1, 2, 3 the centre's offset along x, y, z in [centre_min, centre_max] * m from the grid centre ((W-1)/2, (H-1)/2, (D-1)/2),
+ * d = 4, 5, 6 the radius (d = 4) resp. the half extents along x, y, z in [size_min, size_max] * m, with m = min(D, H, W); the number of
+ * primitives is drawn at counter 0xffff0000.  Inside on squared distances: (dx^2 + dy^2) + dz^2 <= a^2, resp. dx^2 <= a^2 and
+ * dy^2 <= b^2 and dz^2 <= c^2. */
+int fnx_scene_obstacles3d(const FnxGrid* g, const FnxSceneParams* prm, const int* scene_ids, float* flags, void* stream);
+/* U (B,3,D,H,W) = the discrete curl of a vector potential whose component psi_a sits on the cell edges along axis a; psi_a(i,j,k) =
+ * amplitude * the 2D sum over octaves with a trilinear smoothstep blend (along x, then y, then z) at the integer point (i,j,k):
+ *   U0(i,j,k) = (psi_z(i,j+1,k) - psi_z(i,j,k)) - (psi_y(i,j,k+1) - psi_y(i,j,k))
+ *   U1(i,j,k) = (psi_x(i,j,k+1) - psi_x(i,j,k)) - (psi_z(i+1,j,k) - psi_z(i,j,k))
+ *   U2(i,j,k) = (psi_y(i+1,j,k) - psi_y(i,j,k)) - (psi_x(i,j+1,k) - psi_x(i,j,k))
+ * so the MAC divergence cancels term by term, up to the rounding of the differences, before any boundary condition.  density
+ * (B,1,D,H,W), = clamp(density_scale * the same sum on the streams 144 + o at the cell, 0, 1), may be NULL. */
+int fnx_scene_turbulence3d(const FnxGrid* g, const FnxSceneParams* prm, const int* scene_ids, float* U, float* density, void* stream);
+/* fnx_train_loss for out_p (B,1,D,H,W) and out_U (B,3,D,H,W), N = B D H W: div has the bits of fnx_velocity_divergence on the 3D grid,
+ * grad_U is the stencil of fnx_velocity_divergence_backward formed per face; everything else as said there (the workspace is one fp64
+ * quadruple per workgroup of 64 x 4 cells of a plane; fnx_train_loss3d_ws_bytes gives 0 for a grid that is refused). */
+size_t fnx_train_loss3d_ws_bytes(const FnxGrid* g);
+int fnx_train_loss3d(const FnxGrid* g, const float* out_p, const float* out_U, const float* flags, const float* target_p,
+                     const float lambdas[4], const float* upstream, float* terms, float* grad_p, float* grad_U, void* ws, size_t ws_bytes,
+                     void* stream);
 
 /* Optional timing of the dominant kernels with HIP events on the launch stream (used by bench.py for the roofline
  * figures).  While enabled, every launch of the tagged kernel class is bracketed by an event pair (up to 16384 pairs,

@@ -3,12 +3,14 @@
 
     python tools/train_time.py [--res 128] [--batches 64,16] [--warmup 3] [--iters 10] [--out profiles/r12/train_time.txt]
     python tools/train_time.py --trace-only --batches 16 --iters 3          # the loop alone, for rocprofv3 --kernel-trace --stats -- ...
+    python tools/train_time.py --depth 64 --res 64 --batches 4 [--no-long-term]      # the 3D loop (fluidnet_cxx_amd/training3d.py)
 
 The loop is train()'s iteration with device events between its stages, back to back after a warm-up, no host synchronisation inside an
 iteration: sampler (next(): redraw, `stride` pcg steps, the operator-path step and its projection), forward (FluidNetTrain, the repack
 of the weights the optimiser wrote included -- it is timed once more on its own), loss kernel (fnx_train_loss, terms), rollout (the
 no-grad convnet steps and the second forward + loss), backward (both roots: the loss kernel's gradient, fnx_fluidnet_backward, autograd's
-accumulation), optimiser (Adam).  The sampler's own stages are timed in a second pass.  Nothing is asserted: the figures are a record."""
+accumulation), optimiser (Adam).  The sampler's own stages are timed in a second pass, the redraw split into its scene kernels and the
+wall BCs + pcg projection next to them.  Nothing is asserted: the figures are a record."""
 import argparse
 import os
 import sys
@@ -24,12 +26,21 @@ from fluidnet_cxx_amd.training import (MCONF_DEFAULTS, SceneSampler, fluidnet_lo
 STAGES = ["sampler", "forward", "loss kernel", "rollout", "backward", "optimiser"]
 
 
-def run(res, B, warmup, iters, dev, record=True):
-    mconf = dict(MCONF_DEFAULTS)
+def run(res, B, warmup, iters, dev, record=True, depth=None, long_term=True):
     seed = 0
-    net = kaiming_init(FluidNetTrain(mconf), seed).to(dev).train()
+    if depth is None:
+        mconf = dict(MCONF_DEFAULTS)
+        net = kaiming_init(FluidNetTrain(mconf), seed).to(dev).train()
+        sampler = SceneSampler(mconf, B, res, res, seed, dev)
+        loss_fn, raw_loss, nU = fluidnet_loss, ext.train_loss, 2
+    else:
+        from fluidnet_cxx_amd import FluidNetTrain3D
+        from fluidnet_cxx_amd.training3d import MCONF3D_DEFAULTS, SceneSampler3D, fluidnet_loss3d
+        mconf = dict(MCONF3D_DEFAULTS)
+        net = kaiming_init(FluidNetTrain3D(mconf), seed).to(dev).train()
+        sampler = SceneSampler3D(mconf, B, depth, res, res, seed, dev)
+        loss_fn, raw_loss, nU = fluidnet_loss3d, ext.train_loss3d, 3
     opt = torch.optim.Adam(net.parameters(), lr=mconf["lr"])
-    sampler = SceneSampler(mconf, B, res, res, seed, dev)
     lam = lambdas_of(mconf)
     one, ltw = torch.ones((), device=dev), torch.full((), float(mconf["divLongTermLambda"]), device=dev)
     marks, steps_taken = [], []
@@ -39,22 +50,26 @@ def run(res, B, warmup, iters, dev, record=True):
         data, target = sampler.next()
         ev[1].record()
         opt.zero_grad()
-        flags = data[:, 3:4].contiguous()
+        flags = data[:, 1 + nU:2 + nU].contiguous()
         out_p, out_U = net(data)
         ev[2].record()
-        total, _ = fluidnet_loss(out_p, out_U, flags, None, lam)
+        total, _ = loss_fn(out_p, out_U, flags, None, lam)
         ev[3].record()
         n = int(mconf["longTermDivNumSteps"][1] if host_uniform(seed, it, _STREAM_TRAINER, 0) > mconf["longTermDivProbability"]
-                else mconf["longTermDivNumSteps"][0])
-        bd = dict(p=out_p.detach().clone(), U=out_U.detach().clone(), flags=flags, density=data[:, 4:5].contiguous())
-        conf = sampler.sim_conf(sampler.last_choice)
-        with torch.no_grad():
-            for _ in range(n):
-                simulate(conf, bd, net, "convnet")
-        p_lt, U_lt = net(torch.cat((bd["p"], bd["U"], flags, bd["density"]), 1))
-        total_lt, _ = fluidnet_loss(p_lt, U_lt, flags, None, [0.0, 1.0, 0.0, 0.0])
+                else mconf["longTermDivNumSteps"][0]) if long_term else 0
+        roots, weights = [total], [one]
+        if long_term:
+            bd = dict(p=out_p.detach().clone(), U=out_U.detach().clone(), flags=flags, density=data[:, 2 + nU:3 + nU].contiguous())
+            conf = sampler.sim_conf(sampler.last_choice)
+            with torch.no_grad():
+                for _ in range(n):
+                    simulate(conf, bd, net, "convnet")
+            p_lt, U_lt = net(torch.cat((bd["p"], bd["U"], flags, bd["density"]), 1))
+            total_lt, _ = loss_fn(p_lt, U_lt, flags, None, [0.0, 1.0, 0.0, 0.0])
+            roots.append(total_lt)
+            weights.append(ltw)
         ev[4].record()
-        torch.autograd.backward([total, total_lt], [one, ltw])
+        torch.autograd.backward(roots, weights)
         ev[5].record()
         opt.step()
         ev[6].record()
@@ -72,25 +87,32 @@ def run(res, B, warmup, iters, dev, record=True):
     a.record()
     for _ in range(10):
         blob = torch.cat([p.detach().reshape(-1) for p in params]).contiguous()
-        ext.scalenet_pack(blob, False)
-        ext.scalenet_pack_t(blob)
+        ext.scalenet_pack(blob, depth is not None)
+        (ext.scalenet_pack_t if depth is None else ext.scalenet3d_pack_t)(blob)
     b.record()
     torch.cuda.synchronize()
     repack = a.elapsed_time(b) / 10
     # the loss kernel with its gradient in one call (terms and both gradients)
     a.record()
     for _ in range(20):
-        ext.train_loss(out_p.detach(), out_U.detach(), flags, None, lam, one.reshape(1), True)
+        raw_loss(out_p.detach(), out_U.detach(), flags, None, lam, one.reshape(1), True)
     b.record()
     torch.cuda.synchronize()
     fused_loss = a.elapsed_time(b) / 20
     # the sampler's stages
-    names = ["redraw (all slots)", f"{sampler.stride} pcg steps", "advection + buoyancy + wall BCs", "pcg projection"]
-    evs = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
+    names = ["redraw (all slots)", f"{sampler.stride} pcg steps", "advection + buoyancy + wall BCs", "pcg projection",
+             "of the redraw: the scene kernels", "of the redraw: wall BCs + pcg projection"]
+    evs = [torch.cuda.Event(enable_timing=True) for _ in range(7)]
     reps = 5
-    acc = [0.0] * 4
+    acc = [0.0] * 6
     for _ in range(reps):
         conf = sampler.sim_conf(sampler.choices(0))
+        evs[4].record()
+        fl0, U0, _ = sampler.draw(list(range(B)))
+        evs[5].record()
+        fluid.setWallBcs(U0, fl0)
+        sampler._project(U0, fl0)
+        evs[6].record()
         evs[0].record()
         sampler._redraw(list(range(B)))
         evs[1].record()
@@ -104,10 +126,12 @@ def run(res, B, warmup, iters, dev, record=True):
         fluid.setWallBcs(U2, fl)
         evs[3].record()
         sampler._project(U2, fl)
-        evs[4].record()
+        last = torch.cuda.Event(enable_timing=True)
+        last.record()
         torch.cuda.synchronize()
-        for i in range(4):
-            acc[i] += evs[i].elapsed_time(evs[i + 1]) / reps
+        spans = [(evs[0], evs[1]), (evs[1], evs[2]), (evs[2], evs[3]), (evs[3], last), (evs[4], evs[5]), (evs[5], evs[6])]
+        for i, (a0, a1) in enumerate(spans):
+            acc[i] += a0.elapsed_time(a1) / reps
     return dict(res=res, B=B, per=per, whole=whole, repack=repack, fused_loss=fused_loss, rollout_steps=sum(steps_taken) / len(steps_taken),
                 sampler=list(zip(names, acc)), scene_length=sampler.sceneLength, stride=sampler.stride)
 
@@ -120,11 +144,15 @@ def main(argv=None):
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--out", default=None)
     ap.add_argument("--trace-only", action="store_true")
+    ap.add_argument("--depth", type=int, default=None, metavar="N", help="time the 3D loop on N x res x res cells")
+    ap.add_argument("--no-long-term", action="store_true", help="leave the long-term rollout out of the iteration")
     a = ap.parse_args(argv)
     dev = torch.device("cuda")
-    lines = [f"training iteration at {a.res}^2 on {ext.device_name()}: device events, {a.iters} back-to-back iterations after {a.warmup} of warm-up; ms"]
+    grid = f"{a.res}^2" if a.depth is None else f"{a.depth} x {a.res} x {a.res}"
+    lines = [f"training iteration at {grid}{' without the long-term term' if a.no_long_term else ''} on {ext.device_name()}: device events, "
+             f"{a.iters} back-to-back iterations after {a.warmup} of warm-up; ms"]
     for B in [int(b) for b in a.batches.split(",")]:
-        r = run(a.res, B, a.warmup, a.iters, dev, record=not a.trace_only)
+        r = run(a.res, B, a.warmup, a.iters, dev, record=not a.trace_only, depth=a.depth, long_term=not a.no_long_term)
         if r is None:
             continue
         lines.append(f"B = {B}: iteration {r['whole']:.3f} ms (rollout steps per iteration {r['rollout_steps']:.1f})")
