@@ -26,7 +26,6 @@ HIP_UNITS = {
     "fnx_step.hip": ["-ffp-contract=off"],
     "fnx_vorticity.hip": ["-ffp-contract=off", "-Rpass-analysis=kernel-resource-usage"],
     "fnx_scenes.hip": ["-ffp-contract=off", "-Rpass-analysis=kernel-resource-usage"],
-    "fnx_scenes3d.hip": ["-ffp-contract=off", "-Rpass-analysis=kernel-resource-usage"],
     "fnx_render.hip": ["-ffp-contract=off", "-Rpass-analysis=kernel-resource-usage"],
     "fnx_api.hip": ["-ffp-contract=off"],
     # (resource-usage remarks: build_lib checks the kernels of SCRATCH_FREE)
@@ -51,11 +50,9 @@ SCRATCH_FREE = {
                           "its z-march keeps three planes of c and n, two of the curl and three of F_z in registers between the barriers; "
                           "a spill puts a scratch round trip into every step of the march"),
     "fnx_scenes.hip": (["scene_obstacles_kernel", "scene_turbulence_kernel", "train_loss_kernel", "train_loss_finish_kernel"],
-                       "they are streaming kernels with a handful of live values per thread; scratch there would mean the octave loop "
-                       "or the fp64 partial sums were turned into arrays in memory"),
-    "fnx_scenes3d.hip": (["scene_obstacles3d_kernel", "scene_turbulence3d_kernel", "train_loss3d_kernel", "train_loss_finish_kernel"],
-                         "the 3D counterparts of the above: the turbulence thread's nine potential values and the loss's fp64 partial "
-                         "sums are a handful of registers; scratch would mean they were turned into arrays in memory"),
+                       "they are streaming kernels with a handful of live values per thread in either dimension (the 3D turbulence "
+                       "thread's nine potential values, the loss's fp64 partial sums); scratch there would mean the octave loop, the "
+                       "per-axis arrays or the partial sums were turned into arrays in memory"),
     "fnx_render.hip": (["render_march_kernel", "render_march_x_kernel"],
                        "a column's running light, transmittance and radiance live in registers for the whole march; scratch there "
                        "would put a memory round trip between every two cells of a serial chain"),

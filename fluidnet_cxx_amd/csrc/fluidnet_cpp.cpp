@@ -500,161 +500,62 @@ std::vector<Tensor> fluidnet_forward(Tensor packed, Tensor input, double normali
   return {p, U};
 }
 
-// ---- training of the 2D net (fnx_cnn_train.hip) -----------------------------------------------------------
-Tensor scalenet_pack_t(Tensor blob) {
-  TORCH_CHECK(blob.is_cuda() && blob.scalar_type() == at::kFloat && blob.is_contiguous(), "weights blob must be a contiguous float32 GPU tensor");
-  TORCH_CHECK((size_t)blob.numel() == fnx_scalenet_weight_floats(0), "weights blob has ", blob.numel(), " floats, expected ",
-              fnx_scalenet_weight_floats(0));
-  c10::hip::HIPGuard guard(blob.get_device());
-  Tensor packed = at::zeros({(int64_t)fnx_scalenet_packed_t_bytes()}, blob.options().dtype(at::kByte));
-  check_status(fnx_scalenet_pack_t(blob.data_ptr<float>(), packed.data_ptr(), cur_stream(blob)));
-  return packed;
-}
-
-// the two weight images look alike and differ in size: a swapped pair must not reach the device
-static void check_packed(const Tensor& t, size_t bytes, const char* what, const Tensor& like) {
-  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.get_device() == like.get_device() && (size_t)t.nbytes() == bytes, what, " must be the ",
-              bytes, "-byte image from scalenet_pack", bytes == fnx_scalenet_packed_t_bytes() ? "_t" : "", " on the input's device (got ",
-              t.nbytes(), " bytes)");
-}
-static FnxGrid grid2d(int64_t B, int64_t H, int64_t W) {
-  FnxGrid g{}; g.B = (int)B; g.D = 1; g.H = (int)H; g.W = (int)W;
+// ---- training: the CNN's backward pass (fnx_cnn_train.hip), the scenes and the loss (fnx_scenes.hip) -------------------------------
+// Every operation is one body that takes the dimension; the module registers it under its 2D and its 3D name.  A body builds the grid
+// it is given, of either dimension, and the C ABI of its own dimension refuses the other ("2D only", "3D only") before it touches the
+// device: a refused grid gets a token tape and workspace, so the C ABI's text is what is raised.
+static FnxGrid make_grid(int64_t B, int64_t D, int64_t H, int64_t W, bool is3D) {
+  FnxGrid g{}; g.B = (int)B; g.D = (int)D; g.H = (int)H; g.W = (int)W; g.is3D = is3D;
   return g;
 }
-// a (B,C,H,W) or (B,C,1,H,W) tensor of the 2D net; anything deeper is 3D, which the training entry points refuse
+// a (B,C,H,W) or (B,C,D,H,W) tensor of the net: 3D if it has more than one plane
 static FnxGrid grid_of_net_tensor(const Tensor& x, const char* what) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.is_contiguous(), what, " must be a contiguous float32 GPU tensor");
   TORCH_CHECK(x.dim() == 4 || x.dim() == 5, what, " must be (B,C,H,W) or (B,C,D,H,W)");
-  FnxGrid g = grid2d(x.size(0), x.size(x.dim() - 2), x.size(x.dim() - 1));
-  if (x.dim() == 5 && x.size(2) > 1) { g.D = (int)x.size(2); g.is3D = 1; }
-  return g;
+  const int64_t D = x.dim() == 5 ? x.size(2) : 1;
+  return make_grid(x.size(0), D, x.size(x.dim() - 2), x.size(x.dim() - 1), D > 1);
 }
-
-std::vector<py::tuple> multiscale_tape_layout(int64_t B, int64_t H, int64_t W) {
-  const FnxGrid g = grid2d(B, H, W);
-  std::vector<FnxTapeEntry> e(fnx_multiscale_tape_entries());
-  if (fnx_multiscale_tape_layout(&g, e.data()) == 0) check_status(FNX_EINVAL);
-  std::vector<py::tuple> out;
-  for (const FnxTapeEntry& t : e) out.push_back(py::make_tuple(std::string(t.name), (int64_t)t.offset, t.C, t.H, t.W));
-  return out;
+// the size queries of a dimension: 0 for a grid it refuses
+static size_t tape_floats(bool is3d, const FnxGrid& g) {
+  return is3d ? fnx_multiscale3d_tape_layout(&g, nullptr) : fnx_multiscale_tape_layout(&g, nullptr);
 }
-
-std::vector<Tensor> multiscale_forward_train(Tensor packed, Tensor x, const std::string& precision_mode) {
-  const FnxGrid g = grid_of_net_tensor(x, "x");
-  TORCH_CHECK(x.size(1) == 2, "x must have 2 channels");
-  check_packed(packed, fnx_scalenet_packed_bytes(0), "packed", x);
-  c10::hip::HIPGuard guard(x.get_device());
-  std::vector<int64_t> osz = x.sizes().vec(); osz[1] = 1;
-  Tensor p = at::empty(osz, x.options());
-  const size_t floats = g.is3D ? 1 : fnx_multiscale_tape_layout(&g, nullptr);
-  if (!g.is3D && floats == 0) check_status(FNX_EINVAL);
-  Tensor tape = at::empty({(int64_t)floats}, x.options());
-  check_status(fnx_multiscale_forward_train(&g, packed.data_ptr(), x.data_ptr<float>(), p.data_ptr<float>(), tape.data_ptr<float>(),
-                                            precision_of(precision_mode), cur_stream(x)));
-  return {p, tape};
-}
-
-static Tensor multiscale_backward_impl(Tensor packed_t, Tensor grad_p, Tensor tape, const std::string& precision_mode, bool plain) {
-  const FnxGrid g = grid_of_net_tensor(grad_p, "grad_p");
-  check_packed(packed_t, fnx_scalenet_packed_t_bytes(), "packed_t", grad_p);
-  TORCH_CHECK(grad_p.size(1) == 1, "grad_p must have 1 channel");
+static void check_tape(const Tensor& tape, size_t floats) {
   TORCH_CHECK(tape.is_cuda() && tape.scalar_type() == at::kFloat && tape.is_contiguous(), "tape must be a contiguous float32 GPU tensor");
-  TORCH_CHECK(g.is3D || (size_t)tape.numel() == fnx_multiscale_tape_layout(&g, nullptr), "tape has ", tape.numel(), " floats, not the layout of this grid");
-  c10::hip::HIPGuard guard(grad_p.get_device());
-  Tensor grad = at::empty({(int64_t)fnx_scalenet_weight_floats(0)}, grad_p.options());
-  const size_t bytes = g.is3D ? 1 : fnx_multiscale_backward_ws_bytes(&g);
-  Tensor ws = at::empty({(int64_t)bytes}, grad_p.options().dtype(at::kByte));
-  check_status((plain ? fnx_multiscale_backward_plain : fnx_multiscale_backward)(
-      &g, packed_t.data_ptr(), grad_p.data_ptr<float>(), tape.data_ptr<float>(), grad.data_ptr<float>(), precision_of(precision_mode),
-      ws.data_ptr(), bytes, cur_stream(grad_p)));
-  return grad;
+  TORCH_CHECK(!floats || (size_t)tape.numel() == floats, "tape has ", tape.numel(), " floats, not the layout of this grid");
 }
-Tensor multiscale_backward(Tensor packed_t, Tensor grad_p, Tensor tape, const std::string& precision_mode) {
-  return multiscale_backward_impl(packed_t, grad_p, tape, precision_mode, false);
-}
-// the plain weight-gradient kernel for every layer (fnx_multiscale_backward_plain): a cross-check, not a training path
-Tensor multiscale_backward_plain(Tensor packed_t, Tensor grad_p, Tensor tape, const std::string& precision_mode) {
-  return multiscale_backward_impl(packed_t, grad_p, tape, precision_mode, true);
+// The forward's weight image and the backward's look alike and differ in size: a swapped pair must not reach the device.  The 3D entry
+// points of the C ABI take the image's size and refuse a wrong one themselves; the 2D ones take no size, so it is checked here.
+static void check_image(bool is3d, const Tensor& t, bool transposed, const Tensor& like) {
+  const char* what = !transposed ? "packed" : is3d ? "packed3d_t" : "packed_t";
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.get_device() == like.get_device(), what, " must be a contiguous weight image on the input's device");
+  if (is3d) return;
+  const size_t bytes = transposed ? fnx_scalenet_packed_t_bytes() : fnx_scalenet_packed_bytes(0);
+  TORCH_CHECK((size_t)t.nbytes() == bytes, what, " must be the ", bytes, "-byte image from scalenet_pack", transposed ? "_t" : "", " (got ",
+              t.nbytes(), " bytes)");
 }
 
-// -> p, U, tape, s (B), flags (B,1,1,H,W)
-std::vector<Tensor> fluidnet_forward_train(Tensor packed, Tensor input, double normalize_threshold, const std::string& precision_mode) {
-  check_field(input, "input");
-  TORCH_CHECK(input.size(1) == 5 || input.size(1) == 6, "input must have 5 (2D) or 6 (3D) channels [p, U, flags, density]");
-  FnxGrid g = grid2d(input.size(0), input.size(3), input.size(4));
-  g.D = (int)input.size(2); g.is3D = input.size(1) == 6;
-  check_packed(packed, fnx_scalenet_packed_bytes(0), "packed", input);
-  c10::hip::HIPGuard guard(input.get_device());
-  const bool ok2d = !g.is3D && g.D == 1;
-  Tensor p = at::empty({g.B, 1, g.D, g.H, g.W}, input.options());
-  Tensor U = at::empty({g.B, g.is3D ? 3 : 2, g.D, g.H, g.W}, input.options());
-  Tensor flags = at::empty({g.B, 1, g.D, g.H, g.W}, input.options());
-  Tensor scale = at::empty({g.B}, input.options());
-  const size_t floats = ok2d ? fnx_multiscale_tape_layout(&g, nullptr) : 1, bytes = ok2d ? fnx_fluidnet_train_ws_bytes(&g) : 1;
-  if (ok2d && floats == 0) check_status(FNX_EINVAL);
-  Tensor tape = at::empty({(int64_t)floats}, input.options());
-  Tensor ws = at::empty({(int64_t)bytes}, input.options().dtype(at::kByte));
-  check_status(fnx_fluidnet_forward_train(&g, packed.data_ptr(), input.data_ptr<float>(), (float)normalize_threshold, p.data_ptr<float>(),
-                                          U.data_ptr<float>(), flags.data_ptr<float>(), scale.data_ptr<float>(), tape.data_ptr<float>(),
-                                          precision_of(precision_mode), ws.data_ptr(), bytes, cur_stream(input)));
-  return {p, U, tape, scale, flags};
-}
-
-Tensor fluidnet_backward(Tensor packed_t, Tensor flags, Tensor scale, Tensor grad_p, Tensor grad_U, Tensor tape,
-                         const std::string& precision_mode) {
-  check_field(grad_p, "grad_p"); check_field(grad_U, "grad_U"); check_field(flags, "flags");
-  TORCH_CHECK(grad_p.size(1) == 1 && grad_U.size(1) == 2 && flags.size(1) == 1 && grad_p.size(2) == 1, "fluidnet_backward is 2D: grad_p (B,1,1,H,W), grad_U (B,2,1,H,W)");
-  TORCH_CHECK(grad_U.size(0) == grad_p.size(0) && grad_U.size(3) == grad_p.size(3) && grad_U.size(4) == grad_p.size(4) &&
-              flags.sizes() == grad_p.sizes(), "grad_p, grad_U and flags must share their grid");
-  const FnxGrid g = grid2d(grad_p.size(0), grad_p.size(3), grad_p.size(4));
-  check_packed(packed_t, fnx_scalenet_packed_t_bytes(), "packed_t", grad_p);
-  TORCH_CHECK(scale.is_cuda() && scale.scalar_type() == at::kFloat && scale.is_contiguous() && scale.numel() == g.B, "scale must hold B floats on the GPU");
-  TORCH_CHECK(tape.is_cuda() && tape.scalar_type() == at::kFloat && tape.is_contiguous() &&
-              (size_t)tape.numel() == fnx_multiscale_tape_layout(&g, nullptr), "tape is not the layout of this grid");
-  c10::hip::HIPGuard guard(grad_p.get_device());
-  Tensor grad = at::empty({(int64_t)fnx_scalenet_weight_floats(0)}, grad_p.options());
-  const size_t bytes = fnx_fluidnet_train_ws_bytes(&g);
-  Tensor ws = at::empty({(int64_t)bytes}, grad_p.options().dtype(at::kByte));
-  check_status(fnx_fluidnet_backward(&g, packed_t.data_ptr(), flags.data_ptr<float>(), scale.data_ptr<float>(), grad_p.data_ptr<float>(),
-                                     grad_U.data_ptr<float>(), tape.data_ptr<float>(), grad.data_ptr<float>(), precision_of(precision_mode),
-                                     ws.data_ptr(), bytes, cur_stream(grad_p)));
-  return grad;
-}
-
-// ---- training of the 3D net (fnx_cnn_train.hip) -----------------------------------------------------------
-Tensor scalenet3d_pack_t(Tensor blob) {
+Tensor scalenet_pack_t(bool is3d, Tensor blob) {
   TORCH_CHECK(blob.is_cuda() && blob.scalar_type() == at::kFloat && blob.is_contiguous(), "weights blob must be a contiguous float32 GPU tensor");
-  TORCH_CHECK((size_t)blob.numel() == fnx_scalenet_weight_floats(1), "weights blob has ", blob.numel(), " floats, expected ",
-              fnx_scalenet_weight_floats(1), " (the 3D net)");
+  TORCH_CHECK((size_t)blob.numel() == fnx_scalenet_weight_floats(is3d), "weights blob has ", blob.numel(), " floats, expected ",
+              fnx_scalenet_weight_floats(is3d), is3d ? " (the 3D net)" : "");
   c10::hip::HIPGuard guard(blob.get_device());
-  Tensor packed = at::zeros({(int64_t)fnx_scalenet3d_packed_t_bytes()}, blob.options().dtype(at::kByte));
-  check_status(fnx_scalenet3d_pack_t(blob.data_ptr<float>(), packed.data_ptr(), cur_stream(blob)));
+  const size_t bytes = is3d ? fnx_scalenet3d_packed_t_bytes() : fnx_scalenet_packed_t_bytes();
+  Tensor packed = at::zeros({(int64_t)bytes}, blob.options().dtype(at::kByte));
+  check_status((is3d ? fnx_scalenet3d_pack_t : fnx_scalenet_pack_t)(blob.data_ptr<float>(), packed.data_ptr(), cur_stream(blob)));
   return packed;
 }
 
-static void check_image3d(const Tensor& t, const char* what, const Tensor& like) {
-  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.get_device() == like.get_device(), what, " must be a contiguous weight image on the input's device");
-}
-static FnxGrid grid3d(int64_t B, int64_t D, int64_t H, int64_t W) {
-  FnxGrid g{}; g.B = (int)B; g.D = (int)D; g.H = (int)H; g.W = (int)W; g.is3D = 1;
-  return g;
-}
-// a (B,C,D,H,W) tensor of the 3D net; a (B,C,H,W) one or a single plane is 2D, which the C ABI refuses ("3D only")
-static FnxGrid grid_of_net3d_tensor(const Tensor& x, const char* what) {
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.is_contiguous(), what, " must be a contiguous float32 GPU tensor");
-  TORCH_CHECK(x.dim() == 4 || x.dim() == 5, what, " must be (B,C,D,H,W)");
-  if (x.dim() == 4) { FnxGrid g = grid2d(x.size(0), x.size(2), x.size(3)); return g; }
-  FnxGrid g = grid3d(x.size(0), x.size(2), x.size(3), x.size(4));
-  if (g.D == 1) g.is3D = 0;
-  return g;
-}
-
-std::vector<py::tuple> multiscale3d_tape_layout(int64_t B, int64_t D, int64_t H, int64_t W) {
-  const FnxGrid g = grid3d(B, D, H, W);
-  std::vector<FnxTapeEntry3D> e(fnx_multiscale_tape_entries());
-  if (fnx_multiscale3d_tape_layout(&g, e.data()) == 0) check_status(FNX_EINVAL);
+// -> (name, offset, C, H, W) per tape entry in 2D, (name, offset, C, D, H, W) in 3D
+std::vector<py::tuple> multiscale_tape_layout(bool is3d, int64_t B, int64_t D, int64_t H, int64_t W) {
+  const FnxGrid g = make_grid(B, D, H, W, is3d);
+  const size_t n = fnx_multiscale_tape_entries();
+  std::vector<FnxTapeEntry> e2(n);
+  std::vector<FnxTapeEntry3D> e3(n);
+  if ((is3d ? fnx_multiscale3d_tape_layout(&g, e3.data()) : fnx_multiscale_tape_layout(&g, e2.data())) == 0) check_status(FNX_EINVAL);
   std::vector<py::tuple> out;
-  for (const FnxTapeEntry3D& t : e) out.push_back(py::make_tuple(std::string(t.name), (int64_t)t.offset, t.C, t.D, t.H, t.W));
+  for (size_t q = 0; q < n; ++q)
+    out.push_back(is3d ? py::make_tuple(std::string(e3[q].name), (int64_t)e3[q].offset, e3[q].C, e3[q].D, e3[q].H, e3[q].W)
+                       : py::make_tuple(std::string(e2[q].name), (int64_t)e2[q].offset, e2[q].C, e2[q].H, e2[q].W));
   return out;
 }
 
@@ -670,200 +571,141 @@ Tensor trilinear_upsample_backward(Tensor gd, std::vector<int64_t> size) {
   return gs;
 }
 
-std::vector<Tensor> multiscale3d_forward_train(Tensor packed, Tensor x, const std::string& precision_mode) {
-  const FnxGrid g = grid_of_net3d_tensor(x, "x");
+// x (B,2,[D,]H,W) -> p, tape
+std::vector<Tensor> multiscale_forward_train(bool is3d, Tensor packed, Tensor x, const std::string& precision_mode) {
+  const FnxGrid g = grid_of_net_tensor(x, "x");
   TORCH_CHECK(x.size(1) == 2, "x must have 2 channels");
-  check_image3d(packed, "packed", x);
+  check_image(is3d, packed, false, x);
   c10::hip::HIPGuard guard(x.get_device());
   std::vector<int64_t> osz = x.sizes().vec(); osz[1] = 1;
   Tensor p = at::empty(osz, x.options());
-  // (a grid the C ABI refuses gets a token tape: the call below raises before it reads anything)
-  const bool ok = g.is3D && g.D >= 4 && g.H >= 4 && g.W >= 4;
-  const size_t floats = ok ? fnx_multiscale3d_tape_layout(&g, nullptr) : 0;
+  const size_t floats = tape_floats(is3d, g);
   Tensor tape = at::empty({(int64_t)(floats ? floats : 1)}, x.options());
-  check_status(fnx_multiscale3d_forward_train(&g, packed.data_ptr(), (size_t)packed.nbytes(), x.data_ptr<float>(), p.data_ptr<float>(),
-                                              tape.data_ptr<float>(), precision_of(precision_mode), cur_stream(x)));
+  const int mode = precision_of(precision_mode);
+  check_status(is3d ? fnx_multiscale3d_forward_train(&g, packed.data_ptr(), (size_t)packed.nbytes(), x.data_ptr<float>(), p.data_ptr<float>(),
+                                                     tape.data_ptr<float>(), mode, cur_stream(x))
+                    : fnx_multiscale_forward_train(&g, packed.data_ptr(), x.data_ptr<float>(), p.data_ptr<float>(), tape.data_ptr<float>(), mode,
+                                                   cur_stream(x)));
   return {p, tape};
 }
 
-static Tensor multiscale3d_backward_impl(Tensor packed_t, Tensor grad_p, Tensor tape, const std::string& precision_mode, bool plain) {
-  const FnxGrid g = grid_of_net3d_tensor(grad_p, "grad_p");
-  check_image3d(packed_t, "packed3d_t", grad_p);
+// plain: the plain weight-gradient kernel for every layer (fnx_multiscale*_backward_plain), a cross-check and not a training path
+static Tensor multiscale_backward_impl(bool is3d, bool plain, Tensor packed_t, Tensor grad_p, Tensor tape, const std::string& precision_mode) {
+  const FnxGrid g = grid_of_net_tensor(grad_p, "grad_p");
+  check_image(is3d, packed_t, true, grad_p);
   TORCH_CHECK(grad_p.size(1) == 1, "grad_p must have 1 channel");
-  TORCH_CHECK(tape.is_cuda() && tape.scalar_type() == at::kFloat && tape.is_contiguous(), "tape must be a contiguous float32 GPU tensor");
-  const bool ok = g.is3D && g.D >= 4 && g.H >= 4 && g.W >= 4;
-  const size_t floats = ok ? fnx_multiscale3d_tape_layout(&g, nullptr) : 0;
-  TORCH_CHECK(!floats || (size_t)tape.numel() == floats, "tape has ", tape.numel(), " floats, not the layout of this grid");
+  const size_t floats = tape_floats(is3d, g);
+  check_tape(tape, floats);
   c10::hip::HIPGuard guard(grad_p.get_device());
-  Tensor grad = at::empty({(int64_t)fnx_scalenet_weight_floats(1)}, grad_p.options());
-  const size_t bytes = floats ? fnx_multiscale3d_backward_ws_bytes(&g) : 1;
+  Tensor grad = at::empty({(int64_t)fnx_scalenet_weight_floats(is3d)}, grad_p.options());
+  const size_t bytes = !floats ? 1 : is3d ? fnx_multiscale3d_backward_ws_bytes(&g) : fnx_multiscale_backward_ws_bytes(&g);
   Tensor ws = at::empty({(int64_t)bytes}, grad_p.options().dtype(at::kByte));
-  check_status((plain ? fnx_multiscale3d_backward_plain : fnx_multiscale3d_backward)(
-      &g, packed_t.data_ptr(), (size_t)packed_t.nbytes(), grad_p.data_ptr<float>(), tape.data_ptr<float>(), grad.data_ptr<float>(),
-      precision_of(precision_mode), ws.data_ptr(), bytes, cur_stream(grad_p)));
+  const int mode = precision_of(precision_mode);
+  check_status(is3d ? (plain ? fnx_multiscale3d_backward_plain : fnx_multiscale3d_backward)(
+                          &g, packed_t.data_ptr(), (size_t)packed_t.nbytes(), grad_p.data_ptr<float>(), tape.data_ptr<float>(),
+                          grad.data_ptr<float>(), mode, ws.data_ptr(), bytes, cur_stream(grad_p))
+                    : (plain ? fnx_multiscale_backward_plain : fnx_multiscale_backward)(
+                          &g, packed_t.data_ptr(), grad_p.data_ptr<float>(), tape.data_ptr<float>(), grad.data_ptr<float>(), mode, ws.data_ptr(),
+                          bytes, cur_stream(grad_p)));
   return grad;
 }
-Tensor multiscale3d_backward(Tensor packed_t, Tensor grad_p, Tensor tape, const std::string& precision_mode) {
-  return multiscale3d_backward_impl(packed_t, grad_p, tape, precision_mode, false);
+Tensor multiscale_backward(bool is3d, Tensor packed_t, Tensor grad_p, Tensor tape, const std::string& precision_mode) {
+  return multiscale_backward_impl(is3d, false, packed_t, grad_p, tape, precision_mode);
 }
-// the plain weight-gradient kernel for every layer (fnx_multiscale3d_backward_plain): a cross-check, not a training path
-Tensor multiscale3d_backward_plain(Tensor packed_t, Tensor grad_p, Tensor tape, const std::string& precision_mode) {
-  return multiscale3d_backward_impl(packed_t, grad_p, tape, precision_mode, true);
+Tensor multiscale_backward_plain(bool is3d, Tensor packed_t, Tensor grad_p, Tensor tape, const std::string& precision_mode) {
+  return multiscale_backward_impl(is3d, true, packed_t, grad_p, tape, precision_mode);
 }
 
-// -> p, U, tape, s (B), flags (B,1,D,H,W)
-std::vector<Tensor> fluidnet3d_forward_train(Tensor packed, Tensor input, double normalize_threshold, const std::string& precision_mode) {
+// input (B,5|6,D,H,W) = [p, U, flags, density] -> p, U, tape, s (B), flags (B,1,D,H,W)
+std::vector<Tensor> fluidnet_forward_train(bool is3d, Tensor packed, Tensor input, double normalize_threshold, const std::string& precision_mode) {
   check_field(input, "input");
-  TORCH_CHECK(input.size(1) == 5 || input.size(1) == 6, "input must have 6 channels [p, Ux, Uy, Uz, flags, density] (5: a 2D input, which is refused)");
-  FnxGrid g = grid3d(input.size(0), input.size(2), input.size(3), input.size(4));
-  g.is3D = input.size(1) == 6;
-  check_image3d(packed, "packed", input);
+  TORCH_CHECK(input.size(1) == 5 || input.size(1) == 6, "input must have 5 (2D) or 6 (3D) channels [p, U, flags, density]");
+  const FnxGrid g = make_grid(input.size(0), input.size(2), input.size(3), input.size(4), input.size(1) == 6);
+  check_image(is3d, packed, false, input);
   c10::hip::HIPGuard guard(input.get_device());
-  const bool ok = g.is3D && g.D >= 4 && g.H >= 4 && g.W >= 4;
   Tensor p = at::empty({g.B, 1, g.D, g.H, g.W}, input.options());
   Tensor U = at::empty({g.B, g.is3D ? 3 : 2, g.D, g.H, g.W}, input.options());
   Tensor flags = at::empty({g.B, 1, g.D, g.H, g.W}, input.options());
   Tensor scale = at::empty({g.B}, input.options());
-  const size_t floats = ok ? fnx_multiscale3d_tape_layout(&g, nullptr) : 0, bytes = floats ? fnx_fluidnet3d_train_ws_bytes(&g) : 1;
+  const size_t floats = tape_floats(is3d, g);
+  const size_t bytes = !floats ? 1 : is3d ? fnx_fluidnet3d_train_ws_bytes(&g) : fnx_fluidnet_train_ws_bytes(&g);
   Tensor tape = at::empty({(int64_t)(floats ? floats : 1)}, input.options());
   Tensor ws = at::empty({(int64_t)bytes}, input.options().dtype(at::kByte));
-  check_status(fnx_fluidnet3d_forward_train(&g, packed.data_ptr(), (size_t)packed.nbytes(), input.data_ptr<float>(), (float)normalize_threshold,
-                                            p.data_ptr<float>(), U.data_ptr<float>(), flags.data_ptr<float>(), scale.data_ptr<float>(),
-                                            tape.data_ptr<float>(), precision_of(precision_mode), ws.data_ptr(), bytes, cur_stream(input)));
+  const int mode = precision_of(precision_mode);
+  const float thr = (float)normalize_threshold;
+  check_status(is3d ? fnx_fluidnet3d_forward_train(&g, packed.data_ptr(), (size_t)packed.nbytes(), input.data_ptr<float>(), thr, p.data_ptr<float>(),
+                                                   U.data_ptr<float>(), flags.data_ptr<float>(), scale.data_ptr<float>(), tape.data_ptr<float>(),
+                                                   mode, ws.data_ptr(), bytes, cur_stream(input))
+                    : fnx_fluidnet_forward_train(&g, packed.data_ptr(), input.data_ptr<float>(), thr, p.data_ptr<float>(), U.data_ptr<float>(),
+                                                 flags.data_ptr<float>(), scale.data_ptr<float>(), tape.data_ptr<float>(), mode, ws.data_ptr(),
+                                                 bytes, cur_stream(input)));
   return {p, U, tape, scale, flags};
 }
 
-Tensor fluidnet3d_backward(Tensor packed_t, Tensor flags, Tensor scale, Tensor grad_p, Tensor grad_U, Tensor tape,
-                           const std::string& precision_mode) {
+// grad_p (B,1,D,H,W), grad_U (B,2|3,D,H,W), flags (B,1,D,H,W) and scale (B) of the forward -> the gradient in the blob's layout
+Tensor fluidnet_backward(bool is3d, Tensor packed_t, Tensor flags, Tensor scale, Tensor grad_p, Tensor grad_U, Tensor tape,
+                         const std::string& precision_mode) {
   check_field(grad_p, "grad_p"); check_field(grad_U, "grad_U"); check_field(flags, "flags");
-  TORCH_CHECK(grad_p.size(1) == 1 && grad_U.size(1) == 3 && flags.size(1) == 1, "fluidnet3d_backward: grad_p (B,1,D,H,W), grad_U (B,3,D,H,W), flags (B,1,D,H,W)");
+  TORCH_CHECK(grad_p.size(1) == 1 && grad_U.size(1) == (is3d ? 3 : 2) && flags.size(1) == 1, "grad_p and flags must have 1 channel, grad_U ",
+              is3d ? 3 : 2);
   TORCH_CHECK(grad_U.size(0) == grad_p.size(0) && grad_U.size(2) == grad_p.size(2) && grad_U.size(3) == grad_p.size(3) &&
               grad_U.size(4) == grad_p.size(4) && flags.sizes() == grad_p.sizes(), "grad_p, grad_U and flags must share their grid");
-  const FnxGrid g = grid3d(grad_p.size(0), grad_p.size(2), grad_p.size(3), grad_p.size(4));
-  check_image3d(packed_t, "packed3d_t", grad_p);
+  const FnxGrid g = make_grid(grad_p.size(0), grad_p.size(2), grad_p.size(3), grad_p.size(4), is3d);
+  check_image(is3d, packed_t, true, grad_p);
   TORCH_CHECK(scale.is_cuda() && scale.scalar_type() == at::kFloat && scale.is_contiguous() && scale.numel() == g.B, "scale must hold B floats on the GPU");
-  const bool ok = g.D >= 4 && g.H >= 4 && g.W >= 4;
-  const size_t floats = ok ? fnx_multiscale3d_tape_layout(&g, nullptr) : 0;
-  TORCH_CHECK(tape.is_cuda() && tape.scalar_type() == at::kFloat && tape.is_contiguous() && (!floats || (size_t)tape.numel() == floats),
-              "tape is not the layout of this grid");
+  const size_t floats = tape_floats(is3d, g);
+  check_tape(tape, floats);
   c10::hip::HIPGuard guard(grad_p.get_device());
-  Tensor grad = at::empty({(int64_t)fnx_scalenet_weight_floats(1)}, grad_p.options());
-  const size_t bytes = floats ? fnx_fluidnet3d_train_ws_bytes(&g) : 1;
+  Tensor grad = at::empty({(int64_t)fnx_scalenet_weight_floats(is3d)}, grad_p.options());
+  const size_t bytes = !floats ? 1 : is3d ? fnx_fluidnet3d_train_ws_bytes(&g) : fnx_fluidnet_train_ws_bytes(&g);
   Tensor ws = at::empty({(int64_t)bytes}, grad_p.options().dtype(at::kByte));
-  check_status(fnx_fluidnet3d_backward(&g, packed_t.data_ptr(), (size_t)packed_t.nbytes(), flags.data_ptr<float>(), scale.data_ptr<float>(),
-                                       grad_p.data_ptr<float>(), grad_U.data_ptr<float>(), tape.data_ptr<float>(), grad.data_ptr<float>(),
-                                       precision_of(precision_mode), ws.data_ptr(), bytes, cur_stream(grad_p)));
+  const int mode = precision_of(precision_mode);
+  check_status(is3d ? fnx_fluidnet3d_backward(&g, packed_t.data_ptr(), (size_t)packed_t.nbytes(), flags.data_ptr<float>(), scale.data_ptr<float>(),
+                                              grad_p.data_ptr<float>(), grad_U.data_ptr<float>(), tape.data_ptr<float>(), grad.data_ptr<float>(),
+                                              mode, ws.data_ptr(), bytes, cur_stream(grad_p))
+                    : fnx_fluidnet_backward(&g, packed_t.data_ptr(), flags.data_ptr<float>(), scale.data_ptr<float>(), grad_p.data_ptr<float>(),
+                                            grad_U.data_ptr<float>(), tape.data_ptr<float>(), grad.data_ptr<float>(), mode, ws.data_ptr(), bytes,
+                                            cur_stream(grad_p)));
   return grad;
 }
 
-// ---- training scenes and the training loss (ABI 23; 2D, the C ABI refuses everything else before it touches the device) ----------
-static Tensor check_scene_ids(const Tensor& ids) {
+// the grid of B scenes: 3D if it has more than one plane, whichever name was called
+static FnxGrid scene_grid(const Tensor& ids, int64_t D, int64_t H, int64_t W) {
   TORCH_CHECK(ids.is_cuda() && ids.scalar_type() == at::kInt && ids.dim() == 1 && ids.is_contiguous() && ids.numel() >= 1,
               "scene_ids must be a contiguous int32 GPU tensor (B)");
-  return ids;
-}
-// -> flags (B,1,depth,H,W)
-Tensor scene_obstacles(Tensor scene_ids, int64_t H, int64_t W, int64_t seed, int n_min, int n_max, double centre_min, double centre_max,
-                       double size_min, double size_max, int64_t depth) {
-  check_scene_ids(scene_ids);
-  FnxGrid g = grid2d(scene_ids.numel(), H, W);
-  g.D = (int)depth; g.is3D = depth > 1;
-  FnxSceneParams prm{};
-  prm.seed = (unsigned)seed; prm.n_min = n_min; prm.n_max = n_max;
-  prm.centre_min = (float)centre_min; prm.centre_max = (float)centre_max; prm.size_min = (float)size_min; prm.size_max = (float)size_max;
-  c10::hip::HIPGuard guard(scene_ids.get_device());
-  TORCH_CHECK(depth >= 1 && H >= 1 && W >= 1, "scene_obstacles: depth, H and W must be positive");
-  Tensor flags = at::empty({g.B, 1, depth, H, W}, scene_ids.options().dtype(at::kFloat));
-  check_status(fnx_scene_obstacles(&g, &prm, scene_ids.data_ptr<int>(), flags.data_ptr<float>(), cur_stream(scene_ids)));
-  return flags;
-}
-// -> U (B,2,depth,H,W), density (B,1,depth,H,W) or None
-std::vector<Tensor> scene_turbulence(Tensor scene_ids, int64_t H, int64_t W, int64_t seed, int octaves, double wavelength, double amplitude,
-                                     double density_scale, bool with_density, int64_t depth) {
-  check_scene_ids(scene_ids);
-  FnxGrid g = grid2d(scene_ids.numel(), H, W);
-  g.D = (int)depth; g.is3D = depth > 1;
-  FnxSceneParams prm{};
-  prm.seed = (unsigned)seed; prm.octaves = octaves; prm.wavelength = (float)wavelength; prm.amplitude = (float)amplitude;
-  prm.density_scale = (float)density_scale;
-  c10::hip::HIPGuard guard(scene_ids.get_device());
-  TORCH_CHECK(depth >= 1 && H >= 1 && W >= 1, "scene_turbulence: depth, H and W must be positive");
-  Tensor U = at::empty({g.B, 2, depth, H, W}, scene_ids.options().dtype(at::kFloat));
-  Tensor rho = with_density ? at::empty({g.B, 1, depth, H, W}, U.options()) : Tensor();
-  check_status(fnx_scene_turbulence(&g, &prm, scene_ids.data_ptr<int>(), U.data_ptr<float>(), with_density ? rho.data_ptr<float>() : nullptr,
-                                    cur_stream(scene_ids)));
-  return {U, rho};
-}
-// fluid_net_train.py:276-285 -> [terms (5: pL2, divL2, pL1, divL1 unweighted, total) or None, grad_p or None, grad_U or None];
-// upstream: a one-element GPU tensor (the gradient of what the total feeds) or None for the terms alone
-std::vector<Tensor> train_loss(Tensor out_p, Tensor out_U, Tensor flags, c10::optional<Tensor> target_p, std::vector<double> lambdas,
-                               c10::optional<Tensor> upstream, bool terms) {
-  check_field(out_U, "out_U");
-  TORCH_CHECK(lambdas.size() == 4, "lambdas must be (pL2, divL2, pL1, divL1)");
-  FnxGrid g = grid_of(flags, out_U.size(1) == 3, nullptr);
-  check_scalar(out_p, g, "out_p");
-  TORCH_CHECK(out_U.size(0) == g.B && out_U.size(2) == g.D && out_U.size(3) == g.H && out_U.size(4) == g.W, "Size mismatch");
-  const bool has_t = target_p.has_value() && target_p->defined();
-  if (has_t) check_scalar(*target_p, g, "target_p");
-  const bool grads = upstream.has_value() && upstream->defined();
-  if (grads)
-    TORCH_CHECK(upstream->is_cuda() && upstream->scalar_type() == at::kFloat && upstream->numel() == 1 && upstream->get_device() == out_p.get_device(),
-                "upstream must be one float32 on the GPU");
-  c10::hip::HIPGuard guard(out_p.get_device());
-  const float lam[4] = {(float)lambdas[0], (float)lambdas[1], (float)lambdas[2], (float)lambdas[3]};
-  Tensor t, gp, gU, ws;
-  size_t bytes = 0;
-  if (terms) {
-    t = at::empty({5}, out_p.options());
-    bytes = (!g.is3D && g.D == 1) ? fnx_train_loss_ws_bytes(&g) : 0;
-    ws = at::empty({(int64_t)(bytes ? bytes : 1)}, out_p.options().dtype(at::kByte));
-  }
-  if (grads) { gp = at::empty_like(out_p); gU = at::empty_like(out_U); }
-  check_status(fnx_train_loss(&g, out_p.data_ptr<float>(), out_U.data_ptr<float>(), flags.data_ptr<float>(),
-                              has_t ? target_p->data_ptr<float>() : nullptr, lam, grads ? upstream->data_ptr<float>() : nullptr,
-                              terms ? t.data_ptr<float>() : nullptr, grads ? gp.data_ptr<float>() : nullptr,
-                              grads ? gU.data_ptr<float>() : nullptr, terms ? ws.data_ptr() : nullptr, bytes, cur_stream(out_p)));
-  return {t, gp, gU};
-}
-
-// ---- the same in 3D (ABI 26; entry points of their own, the C ABI refuses a 2D grid before it touches the device) ----------------
-static FnxGrid scene_grid3d(int64_t B, int64_t D, int64_t H, int64_t W, const char* fn) {
-  TORCH_CHECK(D >= 1 && H >= 1 && W >= 1, fn, ": D, H and W must be positive");
-  FnxGrid g = grid2d(B, H, W);
-  g.D = (int)D; g.is3D = D > 1;
-  return g;
+  TORCH_CHECK(D >= 1 && H >= 1 && W >= 1, "the scenes' depth, H and W must be positive");
+  return make_grid(ids.numel(), D, H, W, D > 1);
 }
 // -> flags (B,1,D,H,W)
-Tensor scene_obstacles3d(Tensor scene_ids, int64_t D, int64_t H, int64_t W, int64_t seed, int n_min, int n_max, double centre_min,
-                         double centre_max, double size_min, double size_max) {
-  check_scene_ids(scene_ids);
-  const FnxGrid g = scene_grid3d(scene_ids.numel(), D, H, W, "scene_obstacles3d");
+Tensor scene_obstacles(bool is3d, Tensor scene_ids, int64_t D, int64_t H, int64_t W, int64_t seed, int n_min, int n_max, double centre_min,
+                       double centre_max, double size_min, double size_max) {
+  const FnxGrid g = scene_grid(scene_ids, D, H, W);
   FnxSceneParams prm{};
   prm.seed = (unsigned)seed; prm.n_min = n_min; prm.n_max = n_max;
   prm.centre_min = (float)centre_min; prm.centre_max = (float)centre_max; prm.size_min = (float)size_min; prm.size_max = (float)size_max;
   c10::hip::HIPGuard guard(scene_ids.get_device());
   Tensor flags = at::empty({g.B, 1, D, H, W}, scene_ids.options().dtype(at::kFloat));
-  check_status(fnx_scene_obstacles3d(&g, &prm, scene_ids.data_ptr<int>(), flags.data_ptr<float>(), cur_stream(scene_ids)));
+  check_status((is3d ? fnx_scene_obstacles3d : fnx_scene_obstacles)(&g, &prm, scene_ids.data_ptr<int>(), flags.data_ptr<float>(), cur_stream(scene_ids)));
   return flags;
 }
-// -> U (B,3,D,H,W), density (B,1,D,H,W) or None
-std::vector<Tensor> scene_turbulence3d(Tensor scene_ids, int64_t D, int64_t H, int64_t W, int64_t seed, int octaves, double wavelength,
-                                       double amplitude, double density_scale, bool with_density) {
-  check_scene_ids(scene_ids);
-  const FnxGrid g = scene_grid3d(scene_ids.numel(), D, H, W, "scene_turbulence3d");
+// -> U (B,2|3,D,H,W), density (B,1,D,H,W) or None
+std::vector<Tensor> scene_turbulence(bool is3d, Tensor scene_ids, int64_t D, int64_t H, int64_t W, int64_t seed, int octaves, double wavelength,
+                                     double amplitude, double density_scale, bool with_density) {
+  const FnxGrid g = scene_grid(scene_ids, D, H, W);
   FnxSceneParams prm{};
   prm.seed = (unsigned)seed; prm.octaves = octaves; prm.wavelength = (float)wavelength; prm.amplitude = (float)amplitude;
   prm.density_scale = (float)density_scale;
   c10::hip::HIPGuard guard(scene_ids.get_device());
-  Tensor U = at::empty({g.B, 3, D, H, W}, scene_ids.options().dtype(at::kFloat));
+  Tensor U = at::empty({g.B, is3d ? 3 : 2, D, H, W}, scene_ids.options().dtype(at::kFloat));
   Tensor rho = with_density ? at::empty({g.B, 1, D, H, W}, U.options()) : Tensor();
-  check_status(fnx_scene_turbulence3d(&g, &prm, scene_ids.data_ptr<int>(), U.data_ptr<float>(), with_density ? rho.data_ptr<float>() : nullptr,
-                                      cur_stream(scene_ids)));
+  check_status((is3d ? fnx_scene_turbulence3d : fnx_scene_turbulence)(&g, &prm, scene_ids.data_ptr<int>(), U.data_ptr<float>(),
+                                                                     with_density ? rho.data_ptr<float>() : nullptr, cur_stream(scene_ids)));
   return {U, rho};
 }
-// train_loss for out_p (B,1,D,H,W), out_U (B,3,D,H,W)
-std::vector<Tensor> train_loss3d(Tensor out_p, Tensor out_U, Tensor flags, c10::optional<Tensor> target_p, std::vector<double> lambdas,
-                                 c10::optional<Tensor> upstream, bool terms) {
+// fluid_net_train.py:276-285 for out_p (B,1,D,H,W), out_U (B,2|3,D,H,W) -> [terms (5: pL2, divL2, pL1, divL1 unweighted, total) or None,
+// grad_p or None, grad_U or None]; upstream: a one-element GPU tensor (the gradient of what the total feeds) or None for the terms alone
+std::vector<Tensor> train_loss(bool is3d, Tensor out_p, Tensor out_U, Tensor flags, c10::optional<Tensor> target_p, std::vector<double> lambdas,
+                               c10::optional<Tensor> upstream, bool terms) {
   check_field(out_U, "out_U");
   TORCH_CHECK(lambdas.size() == 4, "lambdas must be (pL2, divL2, pL1, divL1)");
   TORCH_CHECK(out_U.size(1) == 2 || out_U.size(1) == 3, "out_U must have 2 or 3 channels");
@@ -882,14 +724,14 @@ std::vector<Tensor> train_loss3d(Tensor out_p, Tensor out_U, Tensor flags, c10::
   size_t bytes = 0;
   if (terms) {
     t = at::empty({5}, out_p.options());
-    bytes = fnx_train_loss3d_ws_bytes(&g);             // 0 for a grid the call below refuses
+    bytes = (is3d ? fnx_train_loss3d_ws_bytes : fnx_train_loss_ws_bytes)(&g);       // 0 for a grid the call below refuses
     ws = at::empty({(int64_t)(bytes ? bytes : 1)}, out_p.options().dtype(at::kByte));
   }
   if (grads) { gp = at::empty_like(out_p); gU = at::empty_like(out_U); }
-  check_status(fnx_train_loss3d(&g, out_p.data_ptr<float>(), out_U.data_ptr<float>(), flags.data_ptr<float>(),
-                                has_t ? target_p->data_ptr<float>() : nullptr, lam, grads ? upstream->data_ptr<float>() : nullptr,
-                                terms ? t.data_ptr<float>() : nullptr, grads ? gp.data_ptr<float>() : nullptr,
-                                grads ? gU.data_ptr<float>() : nullptr, terms ? ws.data_ptr() : nullptr, bytes, cur_stream(out_p)));
+  check_status((is3d ? fnx_train_loss3d : fnx_train_loss)(
+      &g, out_p.data_ptr<float>(), out_U.data_ptr<float>(), flags.data_ptr<float>(), has_t ? target_p->data_ptr<float>() : nullptr, lam,
+      grads ? upstream->data_ptr<float>() : nullptr, terms ? t.data_ptr<float>() : nullptr, grads ? gp.data_ptr<float>() : nullptr,
+      grads ? gU.data_ptr<float>() : nullptr, terms ? ws.data_ptr() : nullptr, bytes, cur_stream(out_p)));
   return {t, gp, gU};
 }
 
@@ -1208,6 +1050,12 @@ int64_t step_workspace_bytes(int B, int D, int H, int W, bool is3D) {
 
 }  // namespace
 
+// a training operation's one body with its dimension bound: what the module registers under the operation's 2D and 3D name
+template <class R, class... A>
+static auto in_dim(bool is3d, R (*body)(bool, A...)) {
+  return [=](A... a) { return body(is3d, std::forward<A>(a)...); };
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // Every compute entry point releases the GIL while it checks, allocates and enqueues: arguments are
   // converted before the guard is taken and results after it is dropped; nothing inside touches Python objects.
@@ -1377,41 +1225,45 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            py::arg("p_tol"), py::arg("jacobi_iter"), py::arg("workspace"), py::arg("net") = py::none(), py::arg("precision_mode") = "fp32",
            py::arg("normalize_threshold") = 1e-5, py::arg("method") = "auto", NoGil());
   m.def("device_name", []() { const char* n = fnx_device_name(); return std::string(n ? n : ""); });
-  m.def("scalenet_pack_t", &scalenet_pack_t, py::arg("blob"), NoGil());
-  m.def("multiscale_tape_layout", &multiscale_tape_layout, py::arg("B"), py::arg("H"), py::arg("W"));
-  m.def("multiscale_forward_train", &multiscale_forward_train, py::arg("packed"), py::arg("x"), py::arg("precision_mode") = "fp32", NoGil());
-  m.def("multiscale_backward", &multiscale_backward, py::arg("packed_t"), py::arg("grad_p"), py::arg("tape"),
-        py::arg("precision_mode") = "fp32", NoGil());
-  m.def("multiscale_backward_plain", &multiscale_backward_plain, py::arg("packed_t"), py::arg("grad_p"), py::arg("tape"),
-        py::arg("precision_mode") = "fp32", NoGil());
-  m.def("fluidnet_forward_train", &fluidnet_forward_train, py::arg("packed"), py::arg("input"), py::arg("normalize_threshold"),
-        py::arg("precision_mode") = "fp32", NoGil());
-  m.def("fluidnet_backward", &fluidnet_backward, py::arg("packed_t"), py::arg("flags"), py::arg("scale"), py::arg("grad_p"),
-        py::arg("grad_U"), py::arg("tape"), py::arg("precision_mode") = "fp32", NoGil());
-  m.def("scene_obstacles", &scene_obstacles, py::arg("scene_ids"), py::arg("H"), py::arg("W"), py::arg("seed"), py::arg("n_min"), py::arg("n_max"),
-        py::arg("centre_min"), py::arg("centre_max"), py::arg("size_min"), py::arg("size_max"), py::arg("depth") = 1, NoGil());
-  m.def("scene_turbulence", &scene_turbulence, py::arg("scene_ids"), py::arg("H"), py::arg("W"), py::arg("seed"), py::arg("octaves"),
-        py::arg("wavelength"), py::arg("amplitude"), py::arg("density_scale"), py::arg("with_density") = true, py::arg("depth") = 1, NoGil());
-  m.def("scalenet3d_pack_t", &scalenet3d_pack_t, py::arg("blob"), NoGil());
-  m.def("multiscale3d_tape_layout", &multiscale3d_tape_layout, py::arg("B"), py::arg("D"), py::arg("H"), py::arg("W"));
   m.def("trilinear_upsample_backward", &trilinear_upsample_backward, py::arg("grad_dst"), py::arg("size"), NoGil());
-  m.def("multiscale3d_forward_train", &multiscale3d_forward_train, py::arg("packed"), py::arg("x"), py::arg("precision_mode") = "fp32", NoGil());
-  m.def("multiscale3d_backward", &multiscale3d_backward, py::arg("packed_t"), py::arg("grad_p"), py::arg("tape"),
-        py::arg("precision_mode") = "fp32", NoGil());
-  m.def("multiscale3d_backward_plain", &multiscale3d_backward_plain, py::arg("packed_t"), py::arg("grad_p"), py::arg("tape"),
-        py::arg("precision_mode") = "fp32", NoGil());
-  m.def("fluidnet3d_forward_train", &fluidnet3d_forward_train, py::arg("packed"), py::arg("input"), py::arg("normalize_threshold"),
-        py::arg("precision_mode") = "fp32", NoGil());
-  m.def("fluidnet3d_backward", &fluidnet3d_backward, py::arg("packed_t"), py::arg("flags"), py::arg("scale"), py::arg("grad_p"),
-        py::arg("grad_U"), py::arg("tape"), py::arg("precision_mode") = "fp32", NoGil());
-  m.def("train_loss", &train_loss, py::arg("out_p"), py::arg("out_U"), py::arg("flags"), py::arg("target_p"), py::arg("lambdas"),
-        py::arg("upstream") = py::none(), py::arg("terms") = true, NoGil());
-  m.def("scene_obstacles3d", &scene_obstacles3d, py::arg("scene_ids"), py::arg("D"), py::arg("H"), py::arg("W"), py::arg("seed"), py::arg("n_min"),
-        py::arg("n_max"), py::arg("centre_min"), py::arg("centre_max"), py::arg("size_min"), py::arg("size_max"), NoGil());
-  m.def("scene_turbulence3d", &scene_turbulence3d, py::arg("scene_ids"), py::arg("D"), py::arg("H"), py::arg("W"), py::arg("seed"), py::arg("octaves"),
-        py::arg("wavelength"), py::arg("amplitude"), py::arg("density_scale"), py::arg("with_density") = true, NoGil());
-  m.def("train_loss3d", &train_loss3d, py::arg("out_p"), py::arg("out_U"), py::arg("flags"), py::arg("target_p"), py::arg("lambdas"),
-        py::arg("upstream") = py::none(), py::arg("terms") = true, NoGil());
+  m.def("multiscale_tape_layout", [](int64_t B, int64_t H, int64_t W) { return multiscale_tape_layout(false, B, 1, H, W); }, py::arg("B"),
+        py::arg("H"), py::arg("W"));
+  m.def("multiscale3d_tape_layout", in_dim(true, &multiscale_tape_layout), py::arg("B"), py::arg("D"), py::arg("H"), py::arg("W"));
+  m.def("scene_obstacles",
+        [](Tensor ids, int64_t H, int64_t W, int64_t seed, int n_min, int n_max, double centre_min, double centre_max, double size_min,
+           double size_max, int64_t depth) {
+          return scene_obstacles(false, ids, depth, H, W, seed, n_min, n_max, centre_min, centre_max, size_min, size_max);
+        },
+        py::arg("scene_ids"), py::arg("H"), py::arg("W"), py::arg("seed"), py::arg("n_min"), py::arg("n_max"), py::arg("centre_min"),
+        py::arg("centre_max"), py::arg("size_min"), py::arg("size_max"), py::arg("depth") = 1, NoGil());
+  m.def("scene_obstacles3d", in_dim(true, &scene_obstacles), py::arg("scene_ids"), py::arg("D"), py::arg("H"), py::arg("W"), py::arg("seed"),
+        py::arg("n_min"), py::arg("n_max"), py::arg("centre_min"), py::arg("centre_max"), py::arg("size_min"), py::arg("size_max"), NoGil());
+  m.def("scene_turbulence",
+        [](Tensor ids, int64_t H, int64_t W, int64_t seed, int octaves, double wavelength, double amplitude, double density_scale,
+           bool with_density, int64_t depth) {
+          return scene_turbulence(false, ids, depth, H, W, seed, octaves, wavelength, amplitude, density_scale, with_density);
+        },
+        py::arg("scene_ids"), py::arg("H"), py::arg("W"), py::arg("seed"), py::arg("octaves"), py::arg("wavelength"), py::arg("amplitude"),
+        py::arg("density_scale"), py::arg("with_density") = true, py::arg("depth") = 1, NoGil());
+  m.def("scene_turbulence3d", in_dim(true, &scene_turbulence), py::arg("scene_ids"), py::arg("D"), py::arg("H"), py::arg("W"), py::arg("seed"),
+        py::arg("octaves"), py::arg("wavelength"), py::arg("amplitude"), py::arg("density_scale"), py::arg("with_density") = true, NoGil());
+  // the operations whose two names differ in the dimension alone: "<net>_..." in 2D, "<net>3d_..." in 3D
+  for (const bool is3d : {false, true}) {
+    const std::string d = is3d ? "3d" : "";
+    m.def(("scalenet" + d + "_pack_t").c_str(), in_dim(is3d, &scalenet_pack_t), py::arg("blob"), NoGil());
+    m.def(("multiscale" + d + "_forward_train").c_str(), in_dim(is3d, &multiscale_forward_train), py::arg("packed"), py::arg("x"),
+          py::arg("precision_mode") = "fp32", NoGil());
+    m.def(("multiscale" + d + "_backward").c_str(), in_dim(is3d, &multiscale_backward), py::arg("packed_t"), py::arg("grad_p"), py::arg("tape"),
+          py::arg("precision_mode") = "fp32", NoGil());
+    m.def(("multiscale" + d + "_backward_plain").c_str(), in_dim(is3d, &multiscale_backward_plain), py::arg("packed_t"), py::arg("grad_p"),
+          py::arg("tape"), py::arg("precision_mode") = "fp32", NoGil());
+    m.def(("fluidnet" + d + "_forward_train").c_str(), in_dim(is3d, &fluidnet_forward_train), py::arg("packed"), py::arg("input"),
+          py::arg("normalize_threshold"), py::arg("precision_mode") = "fp32", NoGil());
+    m.def(("fluidnet" + d + "_backward").c_str(), in_dim(is3d, &fluidnet_backward), py::arg("packed_t"), py::arg("flags"), py::arg("scale"),
+          py::arg("grad_p"), py::arg("grad_U"), py::arg("tape"), py::arg("precision_mode") = "fp32", NoGil());
+    m.def(is3d ? "train_loss3d" : "train_loss", in_dim(is3d, &train_loss), py::arg("out_p"), py::arg("out_U"), py::arg("flags"),
+          py::arg("target_p"), py::arg("lambdas"), py::arg("upstream") = py::none(), py::arg("terms") = true, NoGil());
+  }
   m.def("abi_version", &fnx_abi_version);
   m.def("profile_enable", [](bool on, bool runs) { fnx_profile_enable(on ? (runs ? 2 : 1) : 0); }, py::arg("on"), py::arg("runs") = false);
   m.def("roctx_enable", [](bool on) { check_status(fnx_roctx_enable(on ? 1 : 0)); });

@@ -40,6 +40,7 @@ def test_scratch_free_lists():
     kernels, _ = build.SCRATCH_FREE[UNIT]
     assert kernels == [MFMA, PLAIN]
     assert "fnx_cnn_train3d.hip" not in build.HIP_UNITS and "fnx_cnn_train3d.hip" not in build.SCRATCH_FREE
+    assert "fnx_scenes3d.hip" not in build.HIP_UNITS and "fnx_scenes3d.hip" not in build.SCRATCH_FREE
 
 
 def test_wgrad_mfma_kernel_uses_no_scratch(remarks):

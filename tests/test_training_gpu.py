@@ -124,6 +124,29 @@ def test_loss_against_float64(dev, ext, oracle, lam):
         ext.train_loss(p.detach(), U.detach(), flags, None, [1.0, 1.0, 0.0, 0.0], None, True)
 
 
+@pytest.mark.parametrize("shape", [(3, 6, 70), (3, 5, 6, 70)], ids=["2d", "3d"])
+def test_the_three_loss_kernels_agree_bit_for_bit(dev, ext, shape):
+    """The terms-only, the gradients-only and the combined call are three instantiations of one kernel template per dimension: the five
+    terms of a terms-only call are those of the combined call, the gradients of a gradients-only call are those of the combined call.
+    (B,[D,]H,W) crosses the 64 x 4 workgroup in x and y and has more than one plane and sample."""
+    B, dims = shape[0], (1,) * (4 - len(shape)) + tuple(shape[1:])
+    s = random_state(B, *dims, 0.5, seed=29, boxes=True)
+    s["flags"][:, :, dims[0] // 2, 2:4, 30:68] = 2.0                     # obstacle cells inside the border, across the workgroup's edge
+    loss = ext.train_loss3d if len(shape) == 4 else ext.train_loss
+    p, U, flags = T(s["p"], dev), T(s["U"], dev), T(s["flags"], dev)
+    t = T(np.random.default_rng(31).standard_normal(s["p"].shape).astype(np.float32), dev)
+    up = torch.full((1,), 0.75, device=dev)
+    for target, lam in ((t, [1.0, 1.0, 0.5, 0.5]), (None, [0.0, 1.0, 0.0, 0.5])):
+        terms_only = loss(p, U, flags, target, lam, None, True)
+        grads_only = loss(p, U, flags, target, lam, up, False)
+        both = loss(p, U, flags, target, lam, up, True)
+        assert terms_only[1] is None and terms_only[2] is None and grads_only[0] is None
+        assert np.all(both[0].cpu().numpy()[[1, 3, 4]] > 0) and np.any(both[2].cpu().numpy())
+        assert_bitexact(terms_only[0].cpu().numpy(), both[0].cpu().numpy(), f"terms {shape} {lam}")
+        assert_bitexact(grads_only[1].cpu().numpy(), both[1].cpu().numpy(), f"grad_p {shape} {lam}")
+        assert_bitexact(grads_only[2].cpu().numpy(), both[2].cpu().numpy(), f"grad_U {shape} {lam}")
+
+
 # ---- the sampler ------------------------------------------------------------------------------------------------------------------------
 def _sampler(dev, seed=3, B=6, H=64, W=64, **kw):
     from fluidnet_cxx_amd.training import SceneSampler
