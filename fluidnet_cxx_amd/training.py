@@ -43,7 +43,7 @@ TCONF_DEFAULTS = dict(res=128, batch=64, iters=1000, seed=0, sceneLength=32, str
 _STREAM_SAMPLER, _STREAM_TRAINER = 64, 65      # host-side streams of the hash (the kernels use 0, 16 + octave and 32 + octave)
 
 
-# ---- the hash on the host (include/fluidnet_hip.h; tests/scene_reference.py is the numpy statement) ----------------------------------
+# ---- the hash on the host (include/fluidnet_hip.h; tests/scene_reference.py is the numpy statement, 2D and 3D) -----------------------
 def _mix32(x):
     x &= 0xffffffff
     x ^= x >> 16

@@ -1,5 +1,5 @@
 """The native training path of the 3D pressure net against torch's float64 autograd over the float64 model of the net
-(tests/cnn_grad_reference_3d.py), on weights under which every layer shows in the output (propagating_weights(3)).
+(tests/cnn_grad_reference.py), on weights under which every layer shows in the output (propagating_weights(3)).
 
 As in 2D (tests/test_cnn_train_gpu.py) the float64 model takes its ReLU decisions from the implementation under test (the tape's saved
 outputs > 0), and the tolerance rule is that test's, with its constants: per shape, e32 = the worst-tensor error of torch float32 on the
@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 import torch
 
-import cnn_grad_reference_3d as G
+import cnn_grad_reference as G
 from cnn_reference import _axis_weights, net_input, propagating_weights
 from util import assert_bitexact, assert_close_rel
 
@@ -140,16 +140,16 @@ def test_training_forward(dev, ext, images, weights, case, native, shape, mode):
 @pytest.mark.parametrize("shape,mode", CASES, ids=CASE_IDS)
 def test_backward_vs_masked_fp64(case, native, shape, mode):
     n = native(shape, mode)
-    got = G.split_blob(n["grad"].cpu().numpy())
+    got = G.split_blob(n["grad"].cpu().numpy(), 3)
     _check_zero_taps(got, shape, f"{_id(shape)} {mode}")
     _check_grads(got, n["g64"], case(shape)[2], f"{_id(shape)} {mode}", own=case(shape)[3])
 
 
-@pytest.mark.parametrize("shape", G.GPU_SHAPES, ids=_id)
+@pytest.mark.parametrize("shape", G.GPU_SHAPES[3], ids=_id)
 def test_plain_weight_gradient_kernel_agrees(ext, images, case, native, shape):
     """multiscale3d_backward_plain: the thin layers' kernel for every layer -- the same bound, and an independent check of the MFMA kernel"""
     n = native(shape, "fp32")
-    got = G.split_blob(ext.multiscale3d_backward_plain(images[1], n["gt"], n["tape"], "fp32").cpu().numpy())
+    got = G.split_blob(ext.multiscale3d_backward_plain(images[1], n["gt"], n["tape"], "fp32").cpu().numpy(), 3)
     _check_zero_taps(got, shape, f"{_id(shape)} fp32 plain")
     _check_grads(got, n["g64"], case(shape)[2], f"{_id(shape)} fp32 plain", own=case(shape)[3])
 
@@ -180,8 +180,8 @@ def big(dev, ext, images):
     x, wp = G.case_inputs(BIG)
     xt, gt = torch.from_numpy(x).to(dev), torch.from_numpy(wp).to(dev)
     p, tape = ext.multiscale3d_forward_train(images[0], xt, "fp32_direct")
-    grads = {m: G.split_blob(ext.multiscale3d_backward(images[1], gt, tape, m).cpu().numpy()) for m in ("fp32_direct", "fp32", "fp32_f2")}
-    grads["plain"] = G.split_blob(ext.multiscale3d_backward_plain(images[1], gt, tape, "fp32_direct").cpu().numpy())
+    grads = {m: G.split_blob(ext.multiscale3d_backward(images[1], gt, tape, m).cpu().numpy(), 3) for m in ("fp32_direct", "fp32", "fp32_f2")}
+    grads["plain"] = G.split_blob(ext.multiscale3d_backward_plain(images[1], gt, tape, "fp32_direct").cpu().numpy(), 3)
     return dict(xt=xt, grads=grads)
 
 

@@ -11,6 +11,7 @@ import torch
 
 from fluidnet_cxx_amd import build
 from fluidnet_cxx_amd.weights import make_scalenet_weights, scalenet_layers
+from util import TRAIN_BANNED, FnxGrid as _FnxGrid
 
 MCONF = dict(model="ScaleNet", inputChannels=dict(div=True, pDiv=False, UDiv=False), normalizeInput=True,
              normalizeInputChan="UDiv", normalizeInputThreshold=1e-5, is3D=True, inputDim=3)
@@ -25,10 +26,6 @@ SYMBOLS = ["fnx_multiscale3d_tape_layout", "fnx_scalenet3d_packed_t_bytes", "fnx
 def built():
     build.build_all()
     return build
-
-
-class _FnxGrid(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int) for n in ("B", "D", "H", "W", "is3D", "ref_quirks", "z_offset", "D_global", "k_begin", "k_end")]
 
 
 class _Entry(ctypes.Structure):
@@ -220,7 +217,6 @@ def test_out_of_scope_configurations_raise(built):
 
 def test_train3d_py_has_no_torch_arithmetic():
     """as tests/test_cnn_train_host.py states it for train.py: the gradients come from the kernels"""
-    banned = re.compile(r"torch\.where\(|F\.conv|functional\.conv|interpolate\(|torch\.nn\.functional|\.conv[123]d\(|\.backward\(|autograd\.grad\(")
     txt = open(os.path.join(os.path.dirname(build.HERE), "fluidnet_cxx_amd", "train3d.py")).read()
     code = "\n".join(l.split("#")[0] for l in txt.splitlines())
-    assert not banned.search(code), banned.search(code).group(0)
+    assert not TRAIN_BANNED.search(code), TRAIN_BANNED.search(code).group(0)

@@ -10,6 +10,7 @@ import torch
 
 from fluidnet_cxx_amd import build
 from fluidnet_cxx_amd.weights import make_scalenet_weights, scalenet_layers
+from util import TRAIN_BANNED, FnxGrid as _FnxGrid
 
 MCONF = dict(model="ScaleNet", inputChannels=dict(div=True, pDiv=False, UDiv=False), normalizeInput=True,
              normalizeInputChan="UDiv", normalizeInputThreshold=1e-5, is3D=False, inputDim=2)
@@ -115,14 +116,9 @@ def test_out_of_scope_configurations_raise(built):
 
 def test_train_py_has_no_torch_arithmetic():
     """as tests/test_abi.py states it for the operator surface: the gradients come from the kernels"""
-    banned = re.compile(r"torch\.where\(|F\.conv|functional\.conv|interpolate\(|torch\.nn\.functional|\.conv[123]d\(|\.backward\(|autograd\.grad\(")
     txt = open(os.path.join(os.path.dirname(build.HERE), "fluidnet_cxx_amd", "train.py")).read()
     code = "\n".join(l.split("#")[0] for l in txt.splitlines())
-    assert not banned.search(code), banned.search(code).group(0)
-
-
-class _FnxGrid(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int) for n in ("B", "D", "H", "W", "is3D", "ref_quirks", "z_offset", "D_global", "k_begin", "k_end")]
+    assert not TRAIN_BANNED.search(code), TRAIN_BANNED.search(code).group(0)
 
 
 def test_training_entry_points_check_before_the_device(built):

@@ -1,11 +1,11 @@
 """The 3D scene kernels (fnx_scene_obstacles3d, fnx_scene_turbulence3d) on the GPU against their numpy statement
-(tests/scene_reference_3d.py): the same bits, at shapes that cross a workgroup edge in every direction (the block is 64 x 4 cells of
+(tests/scene_reference.py): the same bits, at shapes that cross a workgroup edge in every direction (the block is 64 x 4 cells of
 one plane, z comes from the grid) and at each end of every parameter's range, and independent of the batch slot."""
 import numpy as np
 import pytest
 import torch
 
-import scene_reference_3d as S3
+import scene_reference as S3
 from util import assert_bitexact
 
 pytestmark = pytest.mark.gpu
@@ -51,18 +51,18 @@ def _gpu(ext, dev, ids, D, H, W, prm, seed=SEED, with_density=True):
 def test_kernels_have_the_bits_of_the_numpy_model(ext, dev, shape, name):
     D, H, W = shape
     B = len(IDS)
-    prm = dict(S3.DEFAULTS, **PARAMS[name])
+    prm = dict(S3.DEFAULTS[3], **PARAMS[name])
     flags, U, rho = _gpu(ext, dev, IDS, D, H, W, prm)
     assert flags.shape == (B, 1, D, H, W) and U.shape == (B, 3, D, H, W) and rho.shape == (B, 1, D, H, W)
-    assert_bitexact(flags, S3.obstacles(SEED, IDS, D, H, W, **prm), f"flags {shape} {name}")
-    wantU, wantrho = S3.turbulence(SEED, IDS, D, H, W, **prm)
+    assert_bitexact(flags, S3.obstacles(SEED, IDS, shape, **prm), f"flags {shape} {name}")
+    wantU, wantrho = S3.turbulence(SEED, IDS, shape, **prm)
     assert_bitexact(U, wantU, f"U {shape} {name}")
     assert_bitexact(rho, wantrho, f"density {shape} {name}")
 
 
 def test_a_scene_does_not_depend_on_its_slot(ext, dev):
     k, (D, H, W) = 1000003, (9, 7, 33)
-    prm = dict(S3.DEFAULTS)
+    prm = dict(S3.DEFAULTS[3])
     one = _gpu(ext, dev, [k], D, H, W, prm)
     five = _gpu(ext, dev, [4, 9, 2, k, 77], D, H, W, prm)
     for a, b, what in zip(one, five, ("flags", "U", "density")):
@@ -74,7 +74,7 @@ def test_a_scene_does_not_depend_on_its_slot(ext, dev):
 
 def test_refusals_reach_python(ext, dev):
     t = torch.zeros(2, dtype=torch.int32, device=dev)
-    d = S3.DEFAULTS
+    d = S3.DEFAULTS[3]
     with pytest.raises(RuntimeError, match="3D only"):
         ext.scene_obstacles3d(t, 1, 16, 16, 0, 0, 4, -0.3, 0.3, 0.03, 0.12)
     with pytest.raises(RuntimeError, match="3D only"):

@@ -48,18 +48,18 @@ def _gpu(ext, dev, ids, H, W, prm, seed=SEED, with_density=True):
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))
 def test_kernels_have_the_bits_of_the_numpy_model(ext, dev, shape, name):
     B, H, W = shape
-    prm = dict(SR.DEFAULTS, **PARAMS[name])
+    prm = dict(SR.DEFAULTS[2], **PARAMS[name])
     flags, U, rho = _gpu(ext, dev, IDS[B], H, W, prm)
     assert flags.shape == (B, 1, 1, H, W) and U.shape == (B, 2, 1, H, W) and rho.shape == (B, 1, 1, H, W)
-    assert_bitexact(flags, SR.obstacles(SEED, IDS[B], H, W, **prm), f"flags {shape} {name}")
-    wantU, wantrho = SR.turbulence(SEED, IDS[B], H, W, **prm)
+    assert_bitexact(flags, SR.obstacles(SEED, IDS[B], (H, W), **prm), f"flags {shape} {name}")
+    wantU, wantrho = SR.turbulence(SEED, IDS[B], (H, W), **prm)
     assert_bitexact(U, wantU, f"U {shape} {name}")
     assert_bitexact(rho, wantrho, f"density {shape} {name}")
 
 
 def test_a_scene_does_not_depend_on_its_slot(ext, dev):
     k, (H, W) = 1000003, (37, 53)
-    prm = dict(SR.DEFAULTS)
+    prm = dict(SR.DEFAULTS[2])
     one = _gpu(ext, dev, [k], H, W, prm)
     five = _gpu(ext, dev, [4, 9, 2, k, 77], H, W, prm)
     for a, b, what in zip(one, five, ("flags", "U", "density")):
@@ -71,7 +71,7 @@ def test_a_scene_does_not_depend_on_its_slot(ext, dev):
 
 def test_refusals_reach_python(ext, dev):
     t = torch.zeros(2, dtype=torch.int32, device=dev)
-    d = SR.DEFAULTS
+    d = SR.DEFAULTS[2]
     with pytest.raises(RuntimeError, match="2D only"):
         ext.scene_obstacles(t, 16, 16, 0, 0, 4, -0.3, 0.3, 0.03, 0.12, depth=8)
     with pytest.raises(RuntimeError, match="2D only"):

@@ -7,9 +7,9 @@ SEED = 20240
 
 
 def _scene(ids, H=64, W=64, seed=SEED, **over):
-    prm = dict(SR.DEFAULTS, **over)
-    flags = SR.obstacles(seed, ids, H, W, **prm)
-    U, rho = SR.turbulence(seed, ids, H, W, **prm)
+    prm = dict(SR.DEFAULTS[2], **over)
+    flags = SR.obstacles(seed, ids, (H, W), **prm)
+    U, rho = SR.turbulence(seed, ids, (H, W), **prm)
     return flags, U, rho
 
 
@@ -54,7 +54,7 @@ def test_same_seed_and_scene_same_arrays_distinct_scenes_distinct_arrays():
     for i in range(len(ids)):
         for j in range(i + 1, len(ids)):
             assert not np.array_equal(U[i], U[j]) and not np.array_equal(rho[i], rho[j]), (i, j)
-    withprims = [i for i, s in enumerate(ids) if SR.primitives(SEED, s, 64, 64, **SR.DEFAULTS)]
+    withprims = [i for i, s in enumerate(ids) if SR.primitives(SEED, s, (64, 64), **SR.DEFAULTS[2])]
     assert len(withprims) >= 4
     assert len({flags[i].tobytes() for i in withprims}) == len(withprims)
     other = _scene([3, 11, 4], seed=SEED + 1)
@@ -63,20 +63,20 @@ def test_same_seed_and_scene_same_arrays_distinct_scenes_distinct_arrays():
 
 def test_flags_hold_fluid_and_obstacle_inside_an_intact_ring():
     for H, W in ((64, 64), (37, 53), (128, 96)):
-        flags = SR.obstacles(SEED, range(16), H, W, **SR.DEFAULTS)
+        flags = SR.obstacles(SEED, range(16), (H, W), **SR.DEFAULTS[2])
         assert flags.dtype == np.float32 and set(np.unique(flags)) <= {1.0, 2.0}
         f = flags[:, 0, 0]
         assert (f[:, 0, :] == 2).all() and (f[:, -1, :] == 2).all() and (f[:, :, 0] == 2).all() and (f[:, :, -1] == 2).all()
 
 
 def test_fluid_fraction_stays_inside_its_bounds():
-    """SR.DEFAULTS at 64 x 64: at most four primitives, each inside a box of half extent 0.12 * 64 = 7.68 cells, which covers at most
+    """SR.DEFAULTS[2] at 64 x 64: at most four primitives, each inside a box of half extent 0.12 * 64 = 7.68 cells, which covers at most
     15 x 15 = 225 cell centres, so at least 62 * 62 - 4 * 225 = 2944 of the 4096 cells stay fluid (0.718); a scene without primitives
     has the 62 * 62 interior cells (0.9385) and nothing has more.  Over 64 scene ids the count of primitives is uniform on 0 .. 4, so
     the mean lies strictly below the upper bound: at most 0.93 would need fewer than ~40 covered cells per scene on average, while one
     smallest primitive alone (half extent 0.03 * 64 = 1.92: a disc of 9 cells or more) comes with four in five scenes -- asserted
     loosely as mean <= 0.93."""
-    flags = SR.obstacles(SEED, range(64), 64, 64, **SR.DEFAULTS)
+    flags = SR.obstacles(SEED, range(64), (64, 64), **SR.DEFAULTS[2])
     frac = (flags[:, 0, 0] == 1.0).mean(axis=(1, 2))
     print("fluid fraction over 64 scenes: min %.4f mean %.4f max %.4f" % (frac.min(), frac.mean(), frac.max()))
     assert frac.min() >= 2944 / 4096 and frac.max() <= 3844 / 4096
@@ -100,4 +100,4 @@ def test_density_lies_in_the_unit_interval():
     _, _, rho = _scene(range(8))
     assert rho.dtype == np.float32 and rho.min() >= 0.0 and rho.max() <= 1.0
     assert (rho == 0).any() and (rho > 0.2).any()
-    assert SR.turbulence(SEED, [1], 16, 16, with_density=False, **SR.DEFAULTS)[1] is None
+    assert SR.turbulence(SEED, [1], (16, 16), with_density=False, **SR.DEFAULTS[2])[1] is None

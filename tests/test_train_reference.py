@@ -14,7 +14,7 @@ B, H, W = 3, 37, 53
 
 
 def _case():
-    flags = SR.obstacles(5, [2, 9, 31], H, W, **dict(SR.DEFAULTS, n_min=2, n_max=4))
+    flags = SR.obstacles(5, [2, 9, 31], (H, W), **dict(SR.DEFAULTS[2], n_min=2, n_max=4))
     rng = np.random.default_rng(3)
     U = rng.standard_normal((B, 2, 1, H, W)).astype(np.float32)
     p = rng.standard_normal((B, 1, 1, H, W)).astype(np.float32)

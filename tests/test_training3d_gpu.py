@@ -1,4 +1,4 @@
-"""The 3D training loop on the GPU: the loss kernel against a float64 model (tests/train_reference_3d.py), its composition with
+"""The 3D training loop on the GPU: the loss kernel against a float64 model (tests/train_reference.py), its composition with
 FluidNetTrain3D, the online sampler, a short Adam run against a CPU model of the same loop, the long-term term, reproducibility and
 resume, and the use of the checkpoint."""
 import os
@@ -10,8 +10,8 @@ import pytest
 import torch
 
 import poisson_reference as PR
-import scene_reference_3d as S3
-import train_reference_3d as T3
+import scene_reference as S3
+import train_reference as T3
 from util import assert_bitexact, random_state
 
 pytestmark = pytest.mark.gpu
@@ -20,10 +20,10 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FACTOR = 8.0                                                 # the suite's rule (tests/test_training_gpu.py)
 LAMBDAS = {"reference": (0.0, 1.0, 0.0, 0.0), "all_terms": (1.0, 1.0, 0.5, 0.5)}     # those of tests/test_training_gpu.py
 # scene parameters scaled to the 16-cell grids of these tests
-SCENE = dict(S3.DEFAULTS, wavelength=8.0, octaves=2)
+SCENE = dict(S3.DEFAULTS[3], wavelength=8.0, octaves=2)
 # the short training run: K Adam iterations at rate LR on 16^3, B = 2 (see test_training_lowers_the_held_out_divergence)
 K, LR = 24, 3e-4
-CPU_BEGIN, CPU_END = 9.209268e-02, 1.678031e-03      # the CPU model's held-out divL2 before and after (see the test's docstring)
+CPU_BEGIN, CPU_END = 9.209267e-02, 1.686494e-03      # the CPU model's held-out divL2 before and after (see the test's docstring)
 
 
 @pytest.fixture(scope="module")
@@ -48,23 +48,6 @@ def _mconf(**kw):
 
 
 # ---- the loss ---------------------------------------------------------------------------------------------------------------------------
-def _loss_model(p, U, flags, t, lam, dtype):
-    """the loss and its gradients in torch on the CPU in `dtype`: value (the four terms and the total), grad_p, grad_U.  The gradient
-    with respect to U is the adjoint of the divergence (pinned to the oracle's by tests/test_train_reference_3d.py) applied to dL/d div,
-    as the kernel forms it."""
-    cast = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dtype)
-    p, U, flags, t = cast(p), cast(U), cast(flags), cast(t)
-    N = p.numel()
-    d = T3.divergence(U, flags)
-    e = p - t
-    total, terms = T3.loss_terms(p, U, flags, t, lam)
-    g_div = (2.0 * lam[1] * d + lam[3] * torch.sign(d)) / N
-    gU = T3.divergence_adjoint(g_div, flags)
-    gp = (2.0 * lam[0] * e + lam[2] * torch.sign(e)) / N
-    vals = np.array([float(v) for v in terms] + [float(total)], np.float64)
-    return vals, gp.double().numpy(), gU.double().numpy()
-
-
 @pytest.fixture(scope="module")
 def loss_case():
     """(B,D,H,W) = (2, 6, 10, 70) of util.random_state(boxes=True).  make_flags places its boxes from 12 cells per axis on only, so at
@@ -85,8 +68,8 @@ def test_loss_against_float64(dev, ext, loss_case, lam):
     B, _, D, H, W = s["p"].shape
     lams = LAMBDAS[lam]
     use_t = lams[0] != 0 or lams[2] != 0
-    v64, gp64, gU64 = _loss_model(s["p"], s["U"], s["flags"], t, lams, torch.float64)
-    v32, gp32, gU32 = _loss_model(s["p"], s["U"], s["flags"], t, lams, torch.float32)
+    v64, gp64, gU64 = T3.loss_and_gradients(s["p"], s["U"], s["flags"], t, lams, torch.float64)
+    v32, gp32, gU32 = T3.loss_and_gradients(s["p"], s["U"], s["flags"], t, lams, torch.float32)
     p = T(s["p"], dev).requires_grad_(True)
     U = T(s["U"], dev).requires_grad_(True)
     flags = T(s["flags"], dev)
@@ -164,7 +147,7 @@ def test_loss_against_float64(dev, ext, loss_case, lam):
 def test_loss_composes_with_the_training_net(dev, ext):
     """fluidnet_loss3d(net(data)).backward() gives the parameter gradients of ((p * g_p).sum() + (U * g_U).sum()).backward() with
     (g_p, g_U) from ext.train_loss3d on the same outputs, bit for bit (the net's backward against float64: tests/test_cnn_train3d_gpu.py)"""
-    import cnn_grad_reference_3d as G3
+    import cnn_grad_reference as G3
     from fluidnet_cxx_amd import FluidNetTrain3D
     from fluidnet_cxx_amd.training import kaiming_init
     from fluidnet_cxx_amd.training3d import fluidnet_loss3d
@@ -198,7 +181,7 @@ def _sampler(dev, seed=SAMPLER_SEED, B=4, dims=(16, 16, 24), **kw):
 
 def test_sampler_batches(dev, ext):
     """Every scene drawn here has one fluid component (the solver does not converge on sealed pockets): checked on the
-    CPU with scene_reference_3d.obstacles and scipy.ndimage.label for the ids 0 .. 47 of seed 3 at (16, 16, 24); the three calls draw the
+    CPU with scene_reference.obstacles and scipy.ndimage.label for the ids 0 .. 47 of seed 3 at (16, 16, 24); the three calls draw the
     ids 0 .. 5."""
     from fluidnet_cxx_amd import fluid
     B, (D, H, W) = 4, (16, 16, 24)
@@ -210,7 +193,7 @@ def test_sampler_batches(dev, ext):
         d, t = data.cpu().numpy(), target.cpu().numpy()
         flags = d[:, 4:5]
         assert set(np.unique(flags)) <= {1.0, 2.0}
-        assert_bitexact(flags, S3.obstacles(SAMPLER_SEED, s.scene_id, D, H, W, **SCENE), "flags in data and of the numpy model")
+        assert_bitexact(flags, S3.obstacles(SAMPLER_SEED, s.scene_id, (D, H, W), **SCENE), "flags in data and of the numpy model")
         assert_bitexact(flags, s.bd["flags"].cpu().numpy(), "flags in data and in the scene")
         assert_bitexact(d[:, 5], t[:, 4], "density in data and target")
         assert_bitexact(t[:, 0:1], s.bd["p"].cpu().numpy(), "target p is the scene's p")
@@ -281,10 +264,10 @@ TCONF = dict(res=16, batch=2, seed=11, sceneLength=16, stride=1, evalEvery=0, ev
 def test_training_lowers_the_held_out_divergence(dev, ext):
     """K = 24 Adam iterations at rate 3e-4 on 16 x 16 x 16, B = 2, divL2 only (no long-term term), from the trainer's seeded Kaiming
     weights: the native held-out divL2 must fall by at least half of the relative fall of a CPU model of the same loop.
-    Choice of K and the rate, on the CPU alone: a float32 torch model of the loop (train_reference_3d.adam_run: the net of
-    cnn_grad_reference_3d, torch Adam) on train_reference_3d.cpu_batches (scenes of the numpy model with SCENE, the oracle's 3D
+    Choice of K and the rate, on the CPU alone: a float32 torch model of the loop (train_reference.adam_run: the net of
+    cnn_grad_reference, torch Adam) on train_reference.cpu_batches (scenes of the numpy model with SCENE, the oracle's 3D
     operators, poisson_reference; seed 11, 24 training batches, 2 held-out batches of seed 11 ^ 0x5eed5eed).  Its held-out divL2 falls
-    from 9.209268e-02 to 1.678031e-03 (x 0.018; a relative fall of 0.982, far above the quarter asked for), so the native run must lose
+    from 9.209267e-02 to 1.686494e-03 (x 0.018; a relative fall of 0.982, far above the quarter asked for), so the native run must lose
     at least 0.491 of its own.  Tried next to it: (24, 1e-3) x 0.007, (40, 1e-4) x 0.034, (40, 3e-4) x 0.010.  The factor one half is a
     margin for batches that differ from the CPU model's (the sampler advances its scenes through the solver; the CPU batches are one
     advection after the projection), not a measured tolerance.  Every scene of both seeds (ids 0 .. 47) has one fluid component."""

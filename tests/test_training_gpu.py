@@ -44,23 +44,6 @@ def _mconf(**kw):
 
 
 # ---- the loss ---------------------------------------------------------------------------------------------------------------------------
-def _loss_model(p, U, flags, t, lam, dtype):
-    """the loss and its gradients in torch on the CPU in `dtype`: value (5 numbers: the four terms and the total), grad_p, grad_U.  The
-    gradient with respect to U is the adjoint of the divergence (pinned to the oracle's by tests/test_train_reference.py) applied to
-    dL/d div, as the kernel forms it."""
-    cast = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dtype)
-    p, U, flags, t = cast(p), cast(U), cast(flags), cast(t)
-    N = p.numel()
-    d = TR.divergence(U, flags)
-    e = p - t
-    total, terms = TR.loss_terms(p, U, flags, t, lam)
-    g_div = (2.0 * lam[1] * d + lam[3] * torch.sign(d)) / N
-    gU = TR.divergence_adjoint(g_div, flags)
-    gp = (2.0 * lam[0] * e + lam[2] * torch.sign(e)) / N
-    vals = np.array([float(v) for v in terms] + [float(total)], np.float64)
-    return vals, gp.double().numpy(), gU.double().numpy()
-
-
 @pytest.mark.parametrize("lam", list(LAMBDAS))
 def test_loss_against_float64(dev, ext, oracle, lam):
     from fluidnet_cxx_amd.training import fluidnet_loss
@@ -72,8 +55,8 @@ def test_loss_against_float64(dev, ext, oracle, lam):
     # the float64 model's divergence is the oracle's (in float32 on these inputs, within the rounding of its three additions)
     d64 = TR.divergence(torch.from_numpy(s["U"]).double(), torch.from_numpy(s["flags"]).double()).numpy()
     assert np.abs(d64 - oracle.velocity_divergence(s["U"], s["flags"])).max() <= 4 * 2.0 ** -24 * 3 * np.abs(s["U"]).max()
-    v64, gp64, gU64 = _loss_model(s["p"], s["U"], s["flags"], t, lams, torch.float64)
-    v32, gp32, gU32 = _loss_model(s["p"], s["U"], s["flags"], t, lams, torch.float32)
+    v64, gp64, gU64 = TR.loss_and_gradients(s["p"], s["U"], s["flags"], t, lams, torch.float64)
+    v32, gp32, gU32 = TR.loss_and_gradients(s["p"], s["U"], s["flags"], t, lams, torch.float32)
     p = T(s["p"], dev).requires_grad_(True)
     U = T(s["U"], dev).requires_grad_(True)
     flags = T(s["flags"], dev)
@@ -256,7 +239,7 @@ def test_training_against_float64(dev, ext):
     assert_bitexact(again.bd["U"].cpu().numpy(), run["sampler"].bd["U"].cpu().numpy(), "the replayed sampler's state")
     held_np = [d.cpu().numpy() for d, _ in held]
     t1 = time.time()
-    w0 = TR.kaiming_weights(tconf["seed"])
+    w0 = TR.kaiming_weights(tconf["seed"], 2)
     b64, e64, _ = TR.adam_run(w0, batches, held_np, LR, torch.float64)
     t2 = time.time()
     b32, e32, _ = TR.adam_run(w0, batches, held_np, LR, torch.float32)

@@ -1,3 +1,6 @@
+import ctypes
+import re
+
 import numpy as np
 
 PLUME_CFG = dict(dt=0.1, maccormackStrength=0.6, sampleOutsideFluid=False, buoyancyScale=0.25, gravityScale=0,
@@ -90,3 +93,12 @@ def assert_close_rel(a, b, rtol, what=""):
     scale = float(np.abs(b).max())
     d = np.abs(a - b).max()
     assert d <= rtol * scale, f"{what}: max |d| = {d:.3e} > {rtol:.1e} * |ref|max {scale:.3e} (relative {d / max(scale, 1e-300):.2e})"
+
+
+class FnxGrid(ctypes.Structure):
+    """FnxGrid of include/fluidnet_hip.h, for the tests that call the C ABI through ctypes"""
+    _fields_ = [(n, ctypes.c_int) for n in ("B", "D", "H", "W", "is3D", "ref_quirks", "z_offset", "D_global", "k_begin", "k_end")]
+
+
+# what the "no torch arithmetic" tests of train.py and train3d.py refuse in the code (comments stripped): the gradients come from the kernels
+TRAIN_BANNED = re.compile(r"torch\.where\(|F\.conv|functional\.conv|interpolate\(|torch\.nn\.functional|\.conv[123]d\(|\.backward\(|autograd\.grad\(")
