@@ -98,6 +98,10 @@ int plan_of(const std::string& plan) {
   return plan == "tiles" ? FNX_ADVECT_PLAN_TILES : (plan == "cells" ? FNX_ADVECT_PLAN_CELLS : (plan == "tiles_split" ? FNX_ADVECT_PLAN_TILES_SPLIT : FNX_ADVECT_PLAN_AUTO));
 }
 
+Tensor out_or_like(const c10::optional<Tensor>& out, const Tensor& like) {
+  return (out.has_value() && out->defined()) ? *out : at::empty_like(like);
+}
+
 Tensor advect_scalar(float dt, Tensor src, Tensor U, Tensor flags, const std::string method, int bnd,
                      const bool sample_outside_fluid, const float maccormack_strength, c10::optional<Tensor> out,
                      const Geom* geom, const std::string& plan) {
@@ -105,7 +109,7 @@ Tensor advect_scalar(float dt, Tensor src, Tensor U, Tensor flags, const std::st
   FnxGrid g = grid_of(flags, U.size(1) == 3, geom);
   check_vel(U, g, "U"); check_scalar(src, g, "src");
   c10::hip::HIPGuard guard(flags.get_device());
-  Tensor dst = (out.has_value() && out->defined()) ? *out : at::empty_like(src);
+  Tensor dst = out_or_like(out, src);
   check_scalar(dst, g, "out");
   Workspace ws(g, FNX_OP_ADVECT_SCALAR, src);
   check_status(fnx_advect_scalar_plan(&g, dt, src.data_ptr<float>(), U.data_ptr<float>(), flags.data_ptr<float>(),
@@ -120,7 +124,7 @@ Tensor advect_vel(float dt, Tensor orig, Tensor U, Tensor flags, const std::stri
   FnxGrid g = grid_of(flags, U.size(1) == 3, geom);
   check_vel(U, g, "U"); check_vel(orig, g, "orig");
   c10::hip::HIPGuard guard(flags.get_device());
-  Tensor dst = (out.has_value() && out->defined()) ? *out : at::empty_like(U);
+  Tensor dst = out_or_like(out, U);
   check_vel(dst, g, "out");
   Workspace ws(g, FNX_OP_ADVECT_VEL, U);
   check_status(fnx_advect_vel_plan(&g, dt, orig.data_ptr<float>(), U.data_ptr<float>(), flags.data_ptr<float>(),
@@ -138,8 +142,8 @@ std::vector<Tensor> advect_step(float dt, Tensor density, Tensor U, Tensor flags
   check_vel(U, g, "U"); check_scalar(density, g, "density");
   const int pl = plan_of(plan);
   c10::hip::HIPGuard guard(flags.get_device());
-  Tensor rd = (out_density.has_value() && out_density->defined()) ? *out_density : at::empty_like(density);
-  Tensor ud = (out_U.has_value() && out_U->defined()) ? *out_U : at::empty_like(U);
+  Tensor rd = out_or_like(out_density, density);
+  Tensor ud = out_or_like(out_U, U);
   check_scalar(rd, g, "out_density"); check_vel(ud, g, "out_U");
   Workspace ws(g, FNX_OP_ADVECT_STEP, U);
   check_status(fnx_advect_step_plan(&g, dt, density.data_ptr<float>(), U.data_ptr<float>(), flags.data_ptr<float>(),

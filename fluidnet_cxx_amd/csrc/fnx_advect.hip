@@ -7,6 +7,7 @@
 // within a few cells of the thread's own cell and are served by L1/L2.
 //
 // Bit-parity: see fnx_device.h.  Compiled with -ffp-contract=off.
+#include "../../include/fluidnet_hip.h"
 #include "fnx_device.h"
 #include "fnx_kernels.h"
 
@@ -592,64 +593,22 @@ __global__ __launch_bounds__(BX* BY) void advect_bwd_kernel(GridDims g, float dt
 
 inline dim3 cell_grid(const GridDims& g) { return dim3((g.W + BX - 1) / BX, (g.H + BY - 1) / BY, g.B * g.KN); }
 
-}  // namespace
-
-namespace fnx {
-
-size_t advect_fix_words(const GridDims& g) { return (size_t)g.B * g.D * g.H * ((g.W + 63) / 64); }
-
-#define DISPATCH3(IS3D, Q, SO, KERNEL, ...)                                                   \
-  do {                                                                                        \
-    if (IS3D) {                                                                               \
-      if (Q) { if (SO) KERNEL<true, true, true> __VA_ARGS__; else KERNEL<true, true, false> __VA_ARGS__; } \
-      else   { if (SO) KERNEL<true, false, true> __VA_ARGS__; else KERNEL<true, false, false> __VA_ARGS__; } \
-    } else {                                                                                  \
-      if (SO) KERNEL<false, false, true> __VA_ARGS__; else KERNEL<false, false, false> __VA_ARGS__; \
-    }                                                                                         \
-  } while (0)
-
-#define DISPATCH2(IS3D, Q, KERNEL, ...)                                                       \
-  do {                                                                                        \
-    if (IS3D) { if (Q) KERNEL<true, true> __VA_ARGS__; else KERNEL<true, false> __VA_ARGS__; } \
-    else KERNEL<false, false> __VA_ARGS__;                                                    \
-  } while (0)
-
-void launch_sl_scalar(const GridDims& g, bool is3d, bool quirks, bool sample_outside, float dt, const float* src,
-                      const float* U, const float* flags, float* dst, int* cell_out, hipStream_t s) {
-  const dim3 grid = cell_grid(g), block(BX, BY);
-  DISPATCH3(is3d, quirks, sample_outside, sl_scalar_kernel, <<<grid, block, 0, s>>>(g, dt, src, U, flags, dst, cell_out));
+// the same grid with the compute window widened by `by` planes (clipped to the array)
+inline GridDims widened(GridDims d, int by) {
+  const int a = d.K0 - by < 0 ? 0 : d.K0 - by, b = d.K0 + d.KN + by > d.D ? d.D : d.K0 + d.KN + by;
+  d.K0 = a; d.KN = b - a;
+  return d;
 }
 
-void launch_sl_scalar_bwd_clamp(const GridDims& g, bool is3d, bool quirks, bool sample_outside, float dt, float half_s,
-                                const float* src, const float* fwd, const int* cell_in, const float* U,
-                                const float* flags, const float* box, float* dst, hipStream_t s) {
-  const dim3 grid = cell_grid(g), block(BX, BY);
-  DISPATCH3(is3d, quirks, sample_outside, sl_scalar_bwd_clamp_kernel,
-            <<<grid, block, 0, s>>>(g, dt, half_s, src, fwd, cell_in, U, flags, (const float2*)box, dst));
-}
+inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 
-void launch_box_minmax(const GridDims& g, bool sample_outside, const float* src, const float* flags, float* box,
-                       hipStream_t s) {
-  const int nzc = (g.KN + BOX_ZC - 1) / BOX_ZC;
-  const dim3 grid((g.W + 61) / 62, (g.H + 4 * BOX_R - 1) / (4 * BOX_R), g.B * nzc), block(64, 4);
-  if (g.D > 1) {
-    if (sample_outside) box_minmax_kernel<true, true><<<grid, block, 0, s>>>(g, src, flags, (float2*)box, nzc);
-    else box_minmax_kernel<true, false><<<grid, block, 0, s>>>(g, src, flags, (float2*)box, nzc);
-  } else {
-    if (sample_outside) box_minmax_kernel<false, true><<<grid, block, 0, s>>>(g, src, flags, (float2*)box, nzc);
-    else box_minmax_kernel<false, false><<<grid, block, 0, s>>>(g, src, flags, (float2*)box, nzc);
-  }
-}
-
-void launch_sl_mac(const GridDims& g, bool is3d, bool quirks, float dt, const float* src, const float* U,
-                   const float* flags, float* dst, hipStream_t s) {
-  const dim3 grid = cell_grid(g), block(BX, BY);
-  DISPATCH2(is3d, quirks, sl_mac_kernel, <<<grid, block, 0, s>>>(g, dt, src, U, flags, dst));
-}
+// fix-up bitmaps of the tile kernels (fnx_advect_march.h, fnx_advect_tile2d.h): one 64-bit word per 64-cell row segment of the array,
+// four of them: forward density, forward velocity, backward density, backward velocity
+inline size_t fix_words(const GridDims& g) { return (size_t)g.B * g.D * g.H * ((g.W + 63) / 64); }
 
 // z-marching tile kernels (fnx_advect_march.h): the planes of the compute window are cut into chunks so that the
 // launch is a whole number of rounds of resident workgroups (3 per CU); a chunk re-reads 2 lead-in planes.
-static void tile_launch_geometry(const GridDims& g, int& ntx, int& nty, int& zchunk, unsigned& G) {
+void tile_launch_geometry(const GridDims& g, int& ntx, int& nty, int& zchunk, unsigned& G) {
   const int slots = 3 * cu_count();
   ntx = (g.W + 63) / 64; nty = (g.H + ATR - 1) / ATR;
   const long ntiles = (long)ntx * nty * g.B;
@@ -662,120 +621,139 @@ static void tile_launch_geometry(const GridDims& g, int& ntx, int& nty, int& zch
   G = (unsigned)(((n + 7) / 8) * 8);
 }
 
-// WHAT-dispatch of the templated tile launches: `K` is a generic lambda taking std::integral_constant<int, WHAT>
-template <class K> static void with_what(int what, K k) {
-  if (what == 3) k(AIC<3>{}); else if (what == 1) k(AIC<1>{}); else k(AIC<2>{});
+// The one dispatch of run-time choices to template arguments: `k` is a generic lambda that receives IS3D, QUIRKS, SAMPLE_OUTSIDE
+// and WHAT as AIC<> constants
+template <class K> void with_flag(bool b, K k) { if (b) k(AIC<1>{}); else k(AIC<0>{}); }
+template <class K> void with_what(int what, K k) {
+  if (what == fnx::ADVECT_BOTH) k(AIC<fnx::ADVECT_BOTH>{}); else if (what == fnx::ADVECT_RHO) k(AIC<fnx::ADVECT_RHO>{}); else k(AIC<fnx::ADVECT_VEL>{});
 }
-
-static void launch_fwd_tile(const GridDims& g, int what, bool sample_outside, float dt, const float* rho, const float* U,
-                            const float* flags, float* rho_fwd, int* cell, float* U_fwd, float* box, unsigned long long* fix_s,
-                            unsigned long long* fix_v, hipStream_t s) {
-  int ntx, nty, zchunk; unsigned G;
-  tile_launch_geometry(g, ntx, nty, zchunk, G);
-  const unsigned nfix = (unsigned)(((size_t)g.B * g.KN * g.H * ntx + 255) / 256);
-  with_what(what, [&](auto W) {
-    constexpr int WH = decltype(W)::value;
-    if (sample_outside) {
-      advect3d_fwd_tile_kernel<true, WH><<<dim3(G), 64 * ATNW, 0, s>>>(g, dt, rho, U, flags, rho_fwd, cell, U_fwd, (float2*)box, fix_s, fix_v, ntx, nty, zchunk);
-      advect3d_fwd_fix_kernel<true><<<dim3(nfix), 256, 0, s>>>(g, dt, rho, U, flags, rho_fwd, cell, U_fwd, fix_s, fix_v, ntx);
-    } else {
-      advect3d_fwd_tile_kernel<false, WH><<<dim3(G), 64 * ATNW, 0, s>>>(g, dt, rho, U, flags, rho_fwd, cell, U_fwd, (float2*)box, fix_s, fix_v, ntx, nty, zchunk);
-      advect3d_fwd_fix_kernel<false><<<dim3(nfix), 256, 0, s>>>(g, dt, rho, U, flags, rho_fwd, cell, U_fwd, fix_s, fix_v, ntx);
-    }
+template <class K> void dispatch(const fnx::AdvectPlan& p, bool sample_outside, K k) {
+  with_flag(p.is3d, [&](auto is3d) {
+    with_flag(p.quirks, [&](auto quirks) {
+      if constexpr (decltype(is3d)::value || !decltype(quirks)::value)          // quirks mode exists in 3D only
+        with_flag(sample_outside, [&](auto outside) { with_what(p.what, [&](auto what) { k(is3d, quirks, outside, what); }); });
+    });
   });
 }
 
-// which plan launch_advect_fused takes for this grid: 2 = the 2D LDS tiles, 3 = the 3D z-marching tiles, 0 = one thread per cell
+}  // namespace
+
+namespace fnx {
+
+// Which kernels an advection call runs.
 // 3D default semantics: the z-marching LDS tile kernels (fnx_advect_march.h); quirks mode and plane ranges beyond the
 // tile kernels' 32-bit offsets: one thread per cell
 // 2D: LDS tile kernels (fnx_advect_tile2d.h) on grids large enough to pay for the two fix-up launches (measured, advection per
 // step, tiles vs one thread per cell: 2048^2 105 vs 129 us, 1024^2 38.6 vs 37.2, 128^2 17.6 vs 12.6), wherever a row offset
 // fits the tiles' 32-bit buffer offsets
-int advect_tile_plan(const GridDims& g, const GridDims& gfwd, bool is3d, bool quirks, int plan) {
-  const bool want_tiles = plan == 1 || plan == 3 || (plan == 0 && (is3d || (size_t)g.HW * g.B >= ((size_t)3 << 19)));
-  if (!want_tiles) return 0;
-  if (!is3d) return (size_t)g.HW < 0x3fffffffu ? 2 : 0;
-  if (quirks) return 0;
-  return ((size_t)(gfwd.KN + 2) * gfwd.HW < 0x3fffffffu ? 1 : 0) | ((size_t)(g.KN + 2) * g.HW < 0x3fffffffu ? 4 : 0);   // bit 0: forward, bit 2: backward
-}
-
-// MacCormack self-advection of U plus advection of rho by U, both by the OLD U (simulate.py:75-93), in two launches.
-// `what`: 3 = both (one step's pair), 1 = the density only (stand-alone advectScalar: U_fwd / U_dst unused), 2 = the velocity only
-// (stand-alone advectVel with orig == U: rho / rho_fwd / cell / box / rho_dst unused).  what != 3 needs a tile plan
-// (advect_tile_plan(...) != 0 in 2D, both bits in 3D): the per-cell stand-alone launches are the callers' own.
-void launch_advect_fused(const GridDims& g, const GridDims& gfwd, bool is3d, bool quirks, bool sample_outside, float dt,
-                         float half_s, const float* rho, const float* U, const float* flags, float* rho_fwd, int* cell,
-                         float* U_fwd, float* box, float* rho_dst, float* U_dst, unsigned long long* fix, hipStream_t s, int plan,
-                         int what) {
-  // fix-up bitmaps of the tile kernels: 4 x (one 64-bit word per 64-cell row segment): fwd density, fwd velocity,
-  // bwd density, bwd velocity
-  const size_t nwords = advect_fix_words(g);
-  const dim3 block(BX, BY);
-  const bool do_s = what & 1, do_v = what & 2;
-  // forward passes and clamp bounds on `gfwd` (the compute window widened by what the backward pass reads)
-  const int tp = advect_tile_plan(g, gfwd, is3d, quirks, plan);
+AdvectPlan advect_plan(const GridDims& g, bool is3d, bool quirks, int what, bool orig_is_U, int method, int request) {
+  AdvectPlan p;
+  p.g = p.gfwd = g;
+  p.is3d = is3d; p.quirks = is3d && quirks; p.what = what;
+  p.maccormack = method == FNX_ADVECT_MACCORMACK;
+  p.fwd = p.bwd = AdvectPath::CELLS;
+  p.bwd_fused = false;
+  // one thread per cell: the pair runs advect_fwd_kernel / advect_bwd_kernel (phase-ordered velocity passes outside quirks mode), a
+  // stand-alone advection sl_scalar_kernel / sl_scalar_bwd_clamp_kernel or sl_mac_kernel / sl_mac_bwd_clamp_kernel
+  p.cells_pair = what == ADVECT_BOTH;
+  if (!p.maccormack) return p;                           // Euler: the forward pass alone, on the compute window, straight into dst
+  p.gfwd = widened(g, 2);                                // what the backward pass / clamp read at |U dt| <= 1
+  const bool want_tiles = request == FNX_ADVECT_PLAN_TILES || request == FNX_ADVECT_PLAN_TILES_SPLIT ||
+                          (request == FNX_ADVECT_PLAN_AUTO && (is3d || (size_t)g.HW * g.B >= ((size_t)3 << 19)));
+  // the tile kernels advect U by itself (every call of simulate.py:93 without viscosity); advect_vel of another field stays per cell
+  if (!want_tiles || (what == ADVECT_VEL && !orig_is_U)) return p;
+  if (!is3d) {
+    if ((size_t)g.HW < 0x3fffffffu) p.fwd = p.bwd = AdvectPath::TILES_2D;
+    return p;
+  }
+  if (p.quirks) return p;
+  const bool fwd_fits = (size_t)(p.gfwd.KN + 2) * p.gfwd.HW < 0x3fffffffu, bwd_fits = (size_t)(g.KN + 2) * g.HW < 0x3fffffffu;
+  // the pair takes the tiles for whichever pass fits (its per-cell kernels and the tile kernels exchange the same fields); a
+  // stand-alone advection takes them only when both passes fit
+  if (what != ADVECT_BOTH && !(fwd_fits && bwd_fits)) return p;
+  if (fwd_fits) p.fwd = AdvectPath::TILES_3D;
+  if (bwd_fits) p.bwd = AdvectPath::TILES_3D;
   // The 3D backward pass of the pair is ONE march for density and velocity (advect3d_bwd_tile_kernel, round 6): 761-769 against 772-775 us
   // per pair of a developed 512 x 512 x 64 plume in alternating rounds on one box (profiles/r06/b_advect_ab_alternating.txt) -- 1 %: the
   // marches are VALU-issue bound and the fused one issues 96 % of their instructions; the traffic it saves was not the bound.
   // FNX_ADVECT_PLAN_TILES_SPLIT keeps the two separate marches (what the stand-alone advections run) for A/B timing.
-  const bool bwd_fused = plan != 3;
-  if (!is3d && tp) {
-    const int ntx = (g.W + 63) / 64, nty = (g.H + T2R - 1) / T2R;
-    const dim3 grid((unsigned)(ntx * nty * g.B));
-    const unsigned nfix = (unsigned)(((size_t)g.B * g.H * ntx + 255) / 256);
-    unsigned long long *ff_s = do_s ? fix : nullptr, *ff_v = do_v ? fix + nwords : nullptr;
-    unsigned long long *fb_s = do_s ? fix + 2 * nwords : nullptr, *fb_v = do_v ? fix + 3 * nwords : nullptr;
-    with_what(what, [&](auto W) {
-      constexpr int WH = decltype(W)::value;
-      if (sample_outside) {
-        advect2d_fwd_tile_kernel<true, WH><<<grid, 64 * T2NW, 0, s>>>(g, dt, rho, U, flags, rho_fwd, cell, U_fwd, ff_s, ff_v, ntx, nty);
-        advect2d_fwd_fix_kernel<true><<<nfix, 256, 0, s>>>(g, dt, rho, U, flags, rho_fwd, cell, U_fwd, ff_s, ff_v, ntx);
-        advect2d_bwd_tile_kernel<true, WH><<<grid, 64 * T2NW, 0, s>>>(g, dt, half_s, rho, rho_fwd, cell, U, U_fwd, flags, rho_dst, U_dst, fb_s, fb_v, ntx, nty);
-        advect2d_bwd_fix_kernel<true><<<nfix, 256, 0, s>>>(g, dt, half_s, rho, rho_fwd, cell, U, U_fwd, flags, rho_dst, U_dst, fb_s, fb_v, ntx);
-      } else {
-        advect2d_fwd_tile_kernel<false, WH><<<grid, 64 * T2NW, 0, s>>>(g, dt, rho, U, flags, rho_fwd, cell, U_fwd, ff_s, ff_v, ntx, nty);
-        advect2d_fwd_fix_kernel<false><<<nfix, 256, 0, s>>>(g, dt, rho, U, flags, rho_fwd, cell, U_fwd, ff_s, ff_v, ntx);
-        advect2d_bwd_tile_kernel<false, WH><<<grid, 64 * T2NW, 0, s>>>(g, dt, half_s, rho, rho_fwd, cell, U, U_fwd, flags, rho_dst, U_dst, fb_s, fb_v, ntx, nty);
-        advect2d_bwd_fix_kernel<false><<<nfix, 256, 0, s>>>(g, dt, half_s, rho, rho_fwd, cell, U, U_fwd, flags, rho_dst, U_dst, fb_s, fb_v, ntx);
-      }
-    });
-    return;
-  }
-  // (the tile kernel also reduces the clamp bounds of the density step from the rho planes it streams)
-  if (is3d && (tp & 1)) {
-    launch_fwd_tile(gfwd, what, sample_outside, dt, rho, U, flags, rho_fwd, cell, U_fwd, box, do_s ? fix : nullptr, do_v ? fix + nwords : nullptr, s);
-  } else {
-    DISPATCH3(is3d, quirks, sample_outside, advect_fwd_kernel, <<<cell_grid(gfwd), block, 0, s>>>(gfwd, dt, rho, U, flags, rho_fwd, cell, U_fwd));
-    if (is3d) launch_box_minmax(gfwd, sample_outside, rho, flags, box, s);
-  }
-  if (is3d && (tp & 4)) {
-    int ntx, nty, zchunk; unsigned G;
-    tile_launch_geometry(g, ntx, nty, zchunk, G);
-    unsigned long long* fb_s = do_s ? fix + 2 * nwords : nullptr;
-    unsigned long long* fb_v = do_v ? fix + 3 * nwords : nullptr;
-    if (what == 3 && bwd_fused) {
-      if (sample_outside) advect3d_bwd_tile_kernel<true><<<dim3(G), 64 * ATNW, 0, s>>>(g, dt, half_s, rho, rho_fwd, cell, U, U_fwd, flags, (const float2*)box, rho_dst, U_dst, fb_s, fb_v, ntx, nty, zchunk);
-      else advect3d_bwd_tile_kernel<false><<<dim3(G), 64 * ATNW, 0, s>>>(g, dt, half_s, rho, rho_fwd, cell, U, U_fwd, flags, (const float2*)box, rho_dst, U_dst, fb_s, fb_v, ntx, nty, zchunk);
-    } else {
-    if (do_s) {
-      if (sample_outside) advect3d_bwd_scalar_tile_kernel<true><<<dim3(G), 64 * ATNW, 0, s>>>(g, dt, half_s, rho, rho_fwd, cell, U, flags, (const float2*)box, rho_dst, fb_s, ntx, nty, zchunk);
-      else advect3d_bwd_scalar_tile_kernel<false><<<dim3(G), 64 * ATNW, 0, s>>>(g, dt, half_s, rho, rho_fwd, cell, U, flags, (const float2*)box, rho_dst, fb_s, ntx, nty, zchunk);
-    }
-    if (do_v) advect3d_bwd_vel_tile_kernel<<<dim3(G), 64 * ATNW, 0, s>>>(g, dt, half_s, U, U_fwd, flags, U_dst, fb_v, ntx, nty, zchunk);
-    }
-    const unsigned nfix = (unsigned)(((size_t)g.B * g.KN * g.H * ntx + 255) / 256);
-    if (sample_outside) advect3d_bwd_fix_kernel<true><<<dim3(nfix), 256, 0, s>>>(g, dt, half_s, rho, rho_fwd, cell, U, U_fwd, flags, (const float2*)box, rho_dst, U_dst, fb_s, fb_v, ntx);
-    else advect3d_bwd_fix_kernel<false><<<dim3(nfix), 256, 0, s>>>(g, dt, half_s, rho, rho_fwd, cell, U, U_fwd, flags, (const float2*)box, rho_dst, U_dst, fb_s, fb_v, ntx);
-    return;
-  }
-  DISPATCH3(is3d, quirks, sample_outside, advect_bwd_kernel,
-            <<<cell_grid(g), block, 0, s>>>(g, dt, half_s, rho, rho_fwd, cell, U, U_fwd, flags, (const float2*)box, rho_dst, U_dst));
+  p.bwd_fused = bwd_fits && what == ADVECT_BOTH && request != FNX_ADVECT_PLAN_TILES_SPLIT;
+  return p;
 }
 
-void launch_sl_mac_bwd_clamp(const GridDims& g, bool is3d, bool quirks, float dt, float half_s, const float* orig,
-                             const float* fwd, const float* U, const float* flags, float* dst, hipStream_t s) {
-  const dim3 grid = cell_grid(g), block(BX, BY);
-  DISPATCH2(is3d, quirks, sl_mac_bwd_clamp_kernel, <<<grid, block, 0, s>>>(g, dt, half_s, orig, fwd, U, flags, dst));
+AdvectWs advect_workspace(const GridDims& g, bool is3d, int what, void* base) {
+  AdvectWs w{};
+  const size_t n = (size_t)g.B * g.DHW;
+  auto take = [&](size_t bytes) { void* r = base ? (char*)base + w.bytes : nullptr; w.bytes += al(bytes); return r; };
+  if (what & ADVECT_RHO) {
+    w.rho_fwd = (float*)take(n * 4);
+    w.cell = (int*)take(n * 4);
+    if (is3d) w.box = (float2*)take(n * 8);              // 2D: the 3x3 clamp box is walked in the backward kernel
+  }
+  if (what & ADVECT_VEL) w.U_fwd = (float*)take(n * 4 * (is3d ? 3 : 2));
+  w.fix = (unsigned long long*)take(4 * 8 * fix_words(g));
+  return w;
+}
+
+// MacCormack: forward pass(es) on p.gfwd into the workspace, backward pass fused with the correction and the clamp on p.g into dst;
+// the density and the velocity of a pair both by the OLD U (simulate.py:75-93).  Euler: the forward pass into dst.
+void launch_advect(const AdvectPlan& p, const AdvectArgs& a, const AdvectWs& w, hipStream_t s) {
+  const GridDims &g = p.g, &gf = p.gfwd;
+  const float dt = a.dt, half_s = a.half_s;
+  const dim3 block(BX, BY);
+  const bool do_s = p.what & ADVECT_RHO, do_v = p.what & ADVECT_VEL, mac = p.maccormack;
+  float* const rho_fwd = mac ? w.rho_fwd : a.rho_dst;
+  float* const U_fwd = mac ? w.U_fwd : a.U_dst;
+  const size_t nwords = fix_words(g);
+  unsigned long long *ff_s = do_s ? w.fix : nullptr, *ff_v = do_v ? w.fix + nwords : nullptr;
+  unsigned long long *fb_s = do_s ? w.fix + 2 * nwords : nullptr, *fb_v = do_v ? w.fix + 3 * nwords : nullptr;
+  dispatch(p, a.sample_outside, [&](auto is3d_, auto quirks_, auto outside_, auto what_) {
+    constexpr bool IS3D = decltype(is3d_)::value, Q = decltype(quirks_)::value, SO = decltype(outside_)::value;
+    constexpr int WH = decltype(what_)::value;
+    // ---- forward
+    if (p.fwd == AdvectPath::TILES_2D) {
+      const int ntx = (g.W + 63) / 64, nty = (g.H + T2R - 1) / T2R;
+      const unsigned nfix = (unsigned)(((size_t)g.B * g.H * ntx + 255) / 256);
+      advect2d_fwd_tile_kernel<SO, WH><<<dim3((unsigned)(ntx * nty * g.B)), 64 * T2NW, 0, s>>>(g, dt, a.rho, a.U, a.flags, rho_fwd, w.cell, U_fwd, ff_s, ff_v, ntx, nty);
+      advect2d_fwd_fix_kernel<SO><<<nfix, 256, 0, s>>>(g, dt, a.rho, a.U, a.flags, rho_fwd, w.cell, U_fwd, ff_s, ff_v, ntx);
+    } else if (p.fwd == AdvectPath::TILES_3D) {
+      // (the tile kernel also reduces the clamp bounds of the density step from the rho planes it streams)
+      int ntx, nty, zchunk; unsigned G;
+      tile_launch_geometry(gf, ntx, nty, zchunk, G);
+      const unsigned nfix = (unsigned)(((size_t)gf.B * gf.KN * gf.H * ntx + 255) / 256);
+      advect3d_fwd_tile_kernel<SO, WH><<<dim3(G), 64 * ATNW, 0, s>>>(gf, dt, a.rho, a.U, a.flags, rho_fwd, w.cell, U_fwd, w.box, ff_s, ff_v, ntx, nty, zchunk);
+      advect3d_fwd_fix_kernel<SO><<<dim3(nfix), 256, 0, s>>>(gf, dt, a.rho, a.U, a.flags, rho_fwd, w.cell, U_fwd, ff_s, ff_v, ntx);
+    } else {
+      if (p.cells_pair) advect_fwd_kernel<IS3D, Q, SO><<<cell_grid(gf), block, 0, s>>>(gf, dt, a.rho, a.U, a.flags, rho_fwd, w.cell, U_fwd);
+      if (!p.cells_pair && do_s) sl_scalar_kernel<IS3D, Q, SO><<<cell_grid(gf), block, 0, s>>>(gf, dt, a.rho, a.U, a.flags, rho_fwd, w.cell);
+      if (!p.cells_pair && do_v) sl_mac_kernel<IS3D, Q><<<cell_grid(gf), block, 0, s>>>(gf, dt, a.orig, a.U, a.flags, U_fwd);
+      if (mac && do_s && p.is3d) {                       // the clamp bounds of the density step as a field
+        const int nzc = (gf.KN + BOX_ZC - 1) / BOX_ZC;
+        const dim3 grid((gf.W + 61) / 62, (gf.H + 4 * BOX_R - 1) / (4 * BOX_R), gf.B * nzc);
+        box_minmax_kernel<IS3D, SO><<<grid, dim3(64, 4), 0, s>>>(gf, a.rho, a.flags, w.box, nzc);
+      }
+    }
+    if (!mac) return;
+    // ---- backward, correction and clamp
+    if (p.bwd == AdvectPath::TILES_2D) {
+      const int ntx = (g.W + 63) / 64, nty = (g.H + T2R - 1) / T2R;
+      const unsigned nfix = (unsigned)(((size_t)g.B * g.H * ntx + 255) / 256);
+      advect2d_bwd_tile_kernel<SO, WH><<<dim3((unsigned)(ntx * nty * g.B)), 64 * T2NW, 0, s>>>(g, dt, half_s, a.rho, rho_fwd, w.cell, a.U, U_fwd, a.flags, a.rho_dst, a.U_dst, fb_s, fb_v, ntx, nty);
+      advect2d_bwd_fix_kernel<SO><<<nfix, 256, 0, s>>>(g, dt, half_s, a.rho, rho_fwd, w.cell, a.U, U_fwd, a.flags, a.rho_dst, a.U_dst, fb_s, fb_v, ntx);
+    } else if (p.bwd == AdvectPath::TILES_3D) {
+      int ntx, nty, zchunk; unsigned G;
+      tile_launch_geometry(g, ntx, nty, zchunk, G);
+      const unsigned nfix = (unsigned)(((size_t)g.B * g.KN * g.H * ntx + 255) / 256);
+      if (p.bwd_fused) advect3d_bwd_tile_kernel<SO><<<dim3(G), 64 * ATNW, 0, s>>>(g, dt, half_s, a.rho, rho_fwd, w.cell, a.U, U_fwd, a.flags, w.box, a.rho_dst, a.U_dst, fb_s, fb_v, ntx, nty, zchunk);
+      if (!p.bwd_fused && do_s) advect3d_bwd_scalar_tile_kernel<SO><<<dim3(G), 64 * ATNW, 0, s>>>(g, dt, half_s, a.rho, rho_fwd, w.cell, a.U, a.flags, w.box, a.rho_dst, fb_s, ntx, nty, zchunk);
+      if (!p.bwd_fused && do_v) advect3d_bwd_vel_tile_kernel<<<dim3(G), 64 * ATNW, 0, s>>>(g, dt, half_s, a.U, U_fwd, a.flags, a.U_dst, fb_v, ntx, nty, zchunk);
+      advect3d_bwd_fix_kernel<SO><<<dim3(nfix), 256, 0, s>>>(g, dt, half_s, a.rho, rho_fwd, w.cell, a.U, U_fwd, a.flags, w.box, a.rho_dst, a.U_dst, fb_s, fb_v, ntx);
+    } else {
+      if (p.cells_pair) advect_bwd_kernel<IS3D, Q, SO><<<cell_grid(g), block, 0, s>>>(g, dt, half_s, a.rho, rho_fwd, w.cell, a.U, U_fwd, a.flags, w.box, a.rho_dst, a.U_dst);
+      if (!p.cells_pair && do_s) sl_scalar_bwd_clamp_kernel<IS3D, Q, SO><<<cell_grid(g), block, 0, s>>>(g, dt, half_s, a.rho, rho_fwd, w.cell, a.U, a.flags, w.box, a.rho_dst);
+      if (!p.cells_pair && do_v) sl_mac_bwd_clamp_kernel<IS3D, Q><<<cell_grid(g), block, 0, s>>>(g, dt, half_s, a.orig, U_fwd, a.U, a.flags, a.U_dst);
+    }
+  });
 }
 
 }  // namespace fnx

@@ -121,7 +121,7 @@ struct ATile {
   }
   // byte offset of my cell of row j inside a plane (clamped into the grid for the lanes that store nothing): the per-lane part of
   // every per-cell global load and store, the plane's wave-uniform base (aat) the rest.  32 bits suffice: the tile plan needs
-  // (KN + 2) * HW < 2^30 (advect_tile_plan), so even twice the offset (the float2 clamp bounds) stays below 2^32.  Opaque to the
+  // (KN + 2) * HW < 2^30 (advect_plan), so even twice the offset (the float2 clamp bounds) stays below 2^32.  Opaque to the
   // optimiser at each step: otherwise it builds one 64-bit address per field and row, hoists those out of the march, and at 2-3
   // waves per SIMD spills them to scratch (round 6: 24 VGPRs in the backward march, every reload an s_waitcnt vmcnt(0) that also
   // waited for the plane in flight and the stores before it).

@@ -50,12 +50,6 @@ inline GridDims dims(const FnxGrid* g) {
   if (g->is3D && g->k_end > g->k_begin) { d.K0 = g->k_begin; d.KN = g->k_end - g->k_begin; }
   return d;
 }
-// the same grid with the compute window widened by `by` planes (clipped to the array)
-inline GridDims widened(GridDims d, int by) {
-  const int a = d.K0 - by < 0 ? 0 : d.K0 - by, b = d.K0 + d.KN + by > d.D ? d.D : d.K0 + d.KN + by;
-  d.K0 = a; d.KN = b - a;
-  return d;
-}
 inline bool quirks(const FnxGrid* g) { return g->is3D && g->ref_quirks; }
 inline size_t ncell(const FnxGrid* g) { return (size_t)g->B * g->D * g->H * g->W; }
 inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -67,13 +61,8 @@ struct Carver {
   bool ok() const { return base != nullptr && off <= cap; }
 };
 
-size_t ws_advect_scalar_fields(const FnxGrid* g) { return al(ncell(g) * 4) + al(ncell(g) * 4) + (g->is3D ? al(ncell(g) * 8) : 0); }   // fwd, traced cell, 3D clamp bounds
-size_t ws_advect_vel_fields(const FnxGrid* g) { return al(ncell(g) * 4 * (g->is3D ? 3 : 2)); }
-// fix-up bitmaps of the tile advection kernels (fnx_advect_march.h, fnx_advect_tile2d.h): 4 x one 64-bit word per 64-cell row segment
-size_t ws_advect_fix(const FnxGrid* g) { return al(4 * 8 * (size_t)g->B * g->D * g->H * ((g->W + 63) / 64)); }
-// the stand-alone operators take the tile kernels too (ABI 19): their fields + the bitmaps
-size_t ws_advect_scalar(const FnxGrid* g) { return ws_advect_scalar_fields(g) + ws_advect_fix(g); }
-size_t ws_advect_vel(const FnxGrid* g) { return ws_advect_vel_fields(g) + ws_advect_fix(g); }
+// advection: the forward fields of `what` and the tile kernels' fix-up bitmaps (the layout is fnx::advect_workspace's)
+size_t ws_advect(const FnxGrid* g, int what) { return fnx::advect_workspace(dims(g), g->is3D, what, nullptr).bytes; }
 size_t ws_mask(const FnxGrid* g) { return g->is3D ? al(fnx::jacobi3d_mask_bytes(dims(g))) : 0; }   // 3D solver: neighbour-mask bytes, twice (rows / row groups), and the planes-alike bits
 // Jacobi workspace: ping-pong pressure, the residual's fixed-order partial sums, one result float, the 3D neighbour mask
 size_t ws_jacobi(const FnxGrid* g) { return al(ncell(g) * 4) + al(fnx::residual_scratch_bytes(g->B)) + al(4) + ws_mask(g); }
@@ -92,8 +81,7 @@ size_t ws_pcg_kept(const FnxGrid* g) { return al(fnx::pcg_kept_bytes(dims(g), g-
 size_t ws_pcg(const FnxGrid* g) { return ws_pcg_kept(g) + al(fnx::pcg_scratch_bytes(dims(g), g->is3D)); }
 size_t ws_step(const FnxGrid* g) {
   const size_t nc = g->is3D ? 3 : 2;
-  // 2D: the fused advection launches keep both forward fields at once
-  size_t adv = ws_advect_scalar_fields(g) + ws_advect_vel_fields(g) + ws_advect_fix(g);
+  size_t adv = ws_advect(g, fnx::ADVECT_BOTH);          // the fused advection launches keep both forward fields at once
   size_t solve = ws_jacobi(g);
   size_t cnn = fnx::fluidnet_ws_bytes(dims(g), g->is3D);
   size_t pcg = al(fnx::pcg_scratch_bytes(dims(g), g->is3D));
@@ -243,15 +231,33 @@ const char* fnx_device_name(void) {
 size_t fnx_workspace_bytes(const FnxGrid* g, int op) {
   if (check_grid(g) != FNX_OK) return 0;
   switch (op) {
-    case FNX_OP_ADVECT_SCALAR: return ws_advect_scalar(g);
-    case FNX_OP_ADVECT_VEL: return ws_advect_vel(g);
+    case FNX_OP_ADVECT_SCALAR: return ws_advect(g, fnx::ADVECT_RHO);
+    case FNX_OP_ADVECT_VEL: return ws_advect(g, fnx::ADVECT_VEL);
     case FNX_OP_JACOBI: return ws_jacobi(g);
     case FNX_OP_STEP: return ws_step(g);
     case FNX_OP_FLUIDNET: return fnx::fluidnet_ws_bytes(dims(g), g->is3D);
-    case FNX_OP_ADVECT_STEP: return ws_advect_scalar_fields(g) + ws_advect_vel_fields(g) + ws_advect_fix(g);
+    case FNX_OP_ADVECT_STEP: return ws_advect(g, fnx::ADVECT_BOTH);
   }
   fail(FNX_EINVAL, "unknown op %d", op);
   return 0;
+}
+
+// What the three advection entry points do after their argument checks: plan, carve, launch.  The stand-alone operators take the
+// LDS tile kernels of the pair with their part only (3D default semantics; 2D from 1.5 M cells): same bits as one thread per cell
+// (fnx_advect_march.h), ~1.5x faster in 3D.
+static int advect_run(const char* name, const FnxGrid* g, int what, int method, int plan, const fnx::AdvectArgs& a, void* ws,
+                      size_t ws_bytes, void* stream) {
+  const fnx::AdvectPlan p = fnx::advect_plan(dims(g), g->is3D, quirks(g), what, a.orig == a.U, method, plan);
+  fnx::AdvectWs w{};
+  if (p.maccormack) {                                    // Euler writes dst directly and takes no workspace
+    w = fnx::advect_workspace(p.g, g->is3D, what, ws);
+    if (!ws || w.bytes > ws_bytes) return fail(FNX_EWORKSPACE, "%s: workspace too small (%zu < %zu)", name, ws_bytes, w.bytes);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  fnx::ProfScope ps(FNX_PROF_ADVECT, s);
+  fnx::launch_advect(p, a, w, s);
+  HIP_OK(hipGetLastError());
+  return FNX_OK;
 }
 
 int fnx_advect_scalar(const FnxGrid* g, float dt, const float* src, const float* U, const float* flags, float* dst,
@@ -269,37 +275,8 @@ int fnx_advect_scalar_plan(const FnxGrid* g, float dt, const float* src, const f
   if (dst == src) return fail(FNX_EINVAL, "advect_scalar: dst must not alias src");
   if (method != FNX_ADVECT_EULER && method != FNX_ADVECT_MACCORMACK) return fail(FNX_EMETHOD, "Advection method not supported");
   if (bnd != 1) return fail(FNX_EINVAL, "advect_scalar: only boundary_width == 1 is supported (the reference's MAC sampling strips exactly one border cell)");
-  hipStream_t s = (hipStream_t)stream;
-  const GridDims d = dims(g);
-  if (method == FNX_ADVECT_EULER) {
-    fnx::launch_sl_scalar(d, g->is3D, quirks(g), sample_outside != 0, dt, src, U, flags, dst, nullptr, s);
-  } else {
-    Carver c(ws, ws_bytes);
-    float* fwd = (float*)c.take(ncell(g) * 4);
-    int* cell = (int*)c.take(ncell(g) * 4);
-    float* box = g->is3D ? (float*)c.take(ncell(g) * 8) : nullptr;
-    unsigned long long* fix = (unsigned long long*)c.take(ws_advect_fix(g));
-    if (!c.ok()) return fail(FNX_EWORKSPACE, "advect_scalar: workspace too small (%zu < %zu)", ws_bytes, c.off);
-    const GridDims dw = widened(d, 2);                  // what the backward pass / clamp read at |U dt| <= 1
-    // the LDS tile kernels of the fused pair, density part only (3D default semantics; 2D from 1.5 M cells): same bits as the
-    // per-cell launches below (fnx_advect_march.h), ~1.5x faster in 3D
-    const int tp = fnx::advect_tile_plan(d, dw, g->is3D, quirks(g), plan);
-    if (g->is3D ? tp == 5 : tp == 2) {
-      fnx::ProfScope ps(FNX_PROF_ADVECT, s);
-      fnx::launch_advect_fused(d, dw, g->is3D, false, sample_outside != 0, dt, strength * 0.5f, src, U, flags, fwd, cell, nullptr, box,
-                               dst, nullptr, fix, s, plan, 1);
-      HIP_OK(hipGetLastError());
-      return FNX_OK;
-    }
-    { fnx::ProfScope ps(FNX_PROF_ADVECT, s); fnx::launch_sl_scalar(dw, g->is3D, quirks(g), sample_outside != 0, dt, src, U, flags, fwd, cell, s); }
-    if (g->is3D) { fnx::ProfScope ps(FNX_PROF_ADVECT, s); fnx::launch_box_minmax(dw, sample_outside != 0, src, flags, box, s); }
-    else box = nullptr;                                  // 2D: the 3x3 clamp box is walked in the backward kernel
-    fnx::ProfScope ps2(FNX_PROF_ADVECT, s);
-    fnx::launch_sl_scalar_bwd_clamp(d, g->is3D, quirks(g), sample_outside != 0, dt, strength * 0.5f, src, fwd, cell, U,
-                                    flags, box, dst, s);
-  }
-  HIP_OK(hipGetLastError());
-  return FNX_OK;
+  const fnx::AdvectArgs a{dt, strength * 0.5f, sample_outside != 0, src, U, U, flags, dst, nullptr};
+  return advect_run("advect_scalar", g, fnx::ADVECT_RHO, method, plan, a, ws, ws_bytes, stream);
 }
 
 int fnx_advect_vel(const FnxGrid* g, float dt, const float* orig, const float* U, const float* flags, float* dst,
@@ -315,30 +292,8 @@ int fnx_advect_vel_plan(const FnxGrid* g, float dt, const float* orig, const flo
   if (dst == orig || dst == U) return fail(FNX_EINVAL, "advect_vel: dst must not alias orig or U");
   if (method != FNX_ADVECT_EULER && method != FNX_ADVECT_MACCORMACK) return fail(FNX_EMETHOD, "Advection method not supported");
   if (bnd != 1) return fail(FNX_EINVAL, "advect_vel: only boundary_width == 1 is supported");
-  hipStream_t s = (hipStream_t)stream;
-  const GridDims d = dims(g);
-  if (method == FNX_ADVECT_EULER) {
-    fnx::launch_sl_mac(d, g->is3D, quirks(g), dt, orig, U, flags, dst, s);
-  } else {
-    Carver c(ws, ws_bytes);
-    float* fwd = (float*)c.take(ncell(g) * 4 * (g->is3D ? 3 : 2));
-    unsigned long long* fix = (unsigned long long*)c.take(ws_advect_fix(g));
-    if (!c.ok()) return fail(FNX_EWORKSPACE, "advect_vel: workspace too small (%zu < %zu)", ws_bytes, c.off);
-    // self-advection (orig is U: every call of simulate.py:93 without viscosity): the LDS tile kernels, velocity part only
-    const int tp = orig == U ? fnx::advect_tile_plan(d, widened(d, 2), g->is3D, quirks(g), plan) : 0;
-    if (g->is3D ? tp == 5 : tp == 2) {
-      fnx::ProfScope ps(FNX_PROF_ADVECT, s);
-      fnx::launch_advect_fused(d, widened(d, 2), g->is3D, false, false, dt, strength * 0.5f, nullptr, U, flags, nullptr, nullptr, fwd,
-                               nullptr, nullptr, dst, fix, s, plan, 2);
-      HIP_OK(hipGetLastError());
-      return FNX_OK;
-    }
-    { fnx::ProfScope ps(FNX_PROF_ADVECT, s); fnx::launch_sl_mac(widened(d, 2), g->is3D, quirks(g), dt, orig, U, flags, fwd, s); }
-    fnx::ProfScope ps2(FNX_PROF_ADVECT, s);
-    fnx::launch_sl_mac_bwd_clamp(d, g->is3D, quirks(g), dt, strength * 0.5f, orig, fwd, U, flags, dst, s);
-  }
-  HIP_OK(hipGetLastError());
-  return FNX_OK;
+  const fnx::AdvectArgs a{dt, strength * 0.5f, false, nullptr, orig, U, flags, nullptr, dst};
+  return advect_run("advect_vel", g, fnx::ADVECT_VEL, method, plan, a, ws, ws_bytes, stream);
 }
 
 int fnx_advect_step(const FnxGrid* g, float dt, const float* density, const float* U, const float* flags,
@@ -354,21 +309,8 @@ int fnx_advect_step_plan(const FnxGrid* g, float dt, const float* density, const
   if (plan < FNX_ADVECT_PLAN_AUTO || plan > FNX_ADVECT_PLAN_TILES_SPLIT) return fail(FNX_EINVAL, "advect_step: unknown plan %d", plan);
   if (!density || !U || !flags || !density_dst || !U_dst) return fail(FNX_EINVAL, "advect_step: NULL tensor");
   if (density_dst == density || U_dst == U) return fail(FNX_EINVAL, "advect_step: dst must not alias the inputs");
-  hipStream_t s = (hipStream_t)stream;
-  const size_t n = ncell(g), nc = g->is3D ? 3 : 2;
-  Carver c(ws, ws_bytes);
-  float* rho_fwd = (float*)c.take(n * 4);
-  int* cell = (int*)c.take(n * 4);
-  float* box = g->is3D ? (float*)c.take(n * 8) : nullptr;
-  float* U_fwd = (float*)c.take(n * 4 * nc);
-  unsigned long long* fix = (unsigned long long*)c.take(ws_advect_fix(g));
-  if (!c.ok()) return fail(FNX_EWORKSPACE, "advect_step: workspace too small (%zu < %zu)", ws_bytes, c.off);
-  const GridDims d = dims(g);
-  fnx::ProfScope ps(FNX_PROF_ADVECT, s);
-  fnx::launch_advect_fused(d, widened(d, 2), g->is3D, quirks(g), sample_outside != 0, dt, strength * 0.5f, density, U, flags,
-                           rho_fwd, cell, U_fwd, box, density_dst, U_dst, fix, s, plan);
-  HIP_OK(hipGetLastError());
-  return FNX_OK;
+  const fnx::AdvectArgs a{dt, strength * 0.5f, sample_outside != 0, density, U, U, flags, density_dst, U_dst};
+  return advect_run("advect_step", g, fnx::ADVECT_BOTH, FNX_ADVECT_MACCORMACK, plan, a, ws, ws_bytes, stream);
 }
 
 int fnx_velocity_divergence(const FnxGrid* g, const float* U, const float* flags, float* div, void* stream) {

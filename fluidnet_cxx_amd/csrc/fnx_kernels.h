@@ -18,27 +18,30 @@ struct ProfScope {
   ~ProfScope() { prof_end(tag, s, pushed); }
 };
 
-// advection (fnx_advect.hip)
-void launch_sl_scalar(const GridDims& g, bool is3d, bool quirks, bool sample_outside, float dt, const float* src,
-                      const float* U, const float* flags, float* dst, int* cell_out, hipStream_t s);
-void launch_sl_scalar_bwd_clamp(const GridDims& g, bool is3d, bool quirks, bool sample_outside, float dt, float half_s,
-                                const float* src, const float* fwd, const int* cell_in, const float* U,
-                                const float* flags, const float* box, float* dst, hipStream_t s);
-// `fix`: 4 * advect_fix_words(g) 64-bit words (3D: the tile kernels' fix-up bitmaps; unused in 2D)
-size_t advect_fix_words(const GridDims& g);
-void launch_advect_fused(const GridDims& g, const GridDims& gfwd, bool is3d, bool quirks, bool sample_outside, float dt,
-                         float half_s, const float* rho, const float* U, const float* flags, float* rho_fwd, int* cell,
-                         float* U_fwd, float* box, float* rho_dst, float* U_dst, unsigned long long* fix, hipStream_t s,
-                         int plan = 0, int what = 3);   // plan: FNX_ADVECT_PLAN_*; what: 3 both, 1 density only, 2 velocity only (tiles only)
-// which kernels launch_advect_fused takes: 0 = one thread per cell; 2D: 2 = LDS tiles; 3D: bit 0 / bit 2 = z-marching tiles for the
-// forward / backward pass
-int advect_tile_plan(const GridDims& g, const GridDims& gfwd, bool is3d, bool quirks, int plan);
-void launch_box_minmax(const GridDims& g, bool sample_outside, const float* src, const float* flags, float* box,
-                       hipStream_t s);
-void launch_sl_mac(const GridDims& g, bool is3d, bool quirks, float dt, const float* src, const float* U,
-                   const float* flags, float* dst, hipStream_t s);
-void launch_sl_mac_bwd_clamp(const GridDims& g, bool is3d, bool quirks, float dt, float half_s, const float* orig,
-                             const float* fwd, const float* U, const float* flags, float* dst, hipStream_t s);
+// advection (fnx_advect.hip): a call is planned (advect_plan), given its workspace (advect_workspace) and launched (launch_advect)
+enum { ADVECT_RHO = 1, ADVECT_VEL = 2, ADVECT_BOTH = 3 };   // `what`: the density by U, `orig` by U, or one step's pair (orig is U)
+enum class AdvectPath { CELLS, TILES_2D, TILES_3D };        // one thread per cell; LDS tiles (2D); z-marching LDS tiles (3D)
+struct AdvectPlan {
+  GridDims g, gfwd;        // the compute window; the window of the forward pass (MacCormack: widened by what the backward pass reads)
+  bool is3d, quirks;
+  int what;
+  bool maccormack;         // false: Euler, the forward pass writes dst and nothing follows
+  AdvectPath fwd, bwd;     // 2D: both tiles or both cells; 3D: see advect_plan
+  bool bwd_fused;          // TILES_3D backward pass of a pair: one march for density and velocity instead of two
+  bool cells_pair;         // CELLS passes: the pair's fused kernels instead of the stand-alone scalar / velocity kernels
+};
+// request: FNX_ADVECT_PLAN_*; method: FNX_ADVECT_EULER / _MACCORMACK; orig_is_U: what the velocity advection advects is U itself
+AdvectPlan advect_plan(const GridDims& g, bool is3d, bool quirks, int what, bool orig_is_U, int method, int request);
+// Workspace of a MacCormack call, in this order: forward density, traced cell, 3D clamp bounds (the density's three), forward
+// velocity, the tile kernels' four fix-up bitmaps (2D and 3D); each rounded up to 256 bytes.  base == nullptr: the size only.
+struct AdvectWs { float* rho_fwd; int* cell; float2* box; float* U_fwd; unsigned long long* fix; size_t bytes; };
+AdvectWs advect_workspace(const GridDims& g, bool is3d, int what, void* base);
+struct AdvectArgs {
+  float dt, half_s; bool sample_outside;
+  const float *rho, *orig, *U, *flags;
+  float *rho_dst, *U_dst;
+};
+void launch_advect(const AdvectPlan& p, const AdvectArgs& a, const AdvectWs& ws, hipStream_t s);
 
 // stencils (fnx_stencils.hip)
 void launch_divergence(const GridDims& g, bool is3d, const float* U, const float* flags, float* div, hipStream_t s);
