@@ -63,19 +63,20 @@ struct Carver {
 
 // advection: the forward fields of `what` and the tile kernels' fix-up bitmaps (the layout is fnx::advect_workspace's)
 size_t ws_advect(const FnxGrid* g, int what) { return fnx::advect_workspace(dims(g), g->is3D, what, nullptr).bytes; }
-size_t ws_mask(const FnxGrid* g) { return g->is3D ? al(fnx::jacobi3d_mask_bytes(dims(g))) : 0; }   // 3D solver: neighbour-mask bytes, twice (rows / row groups), and the planes-alike bits
-// Jacobi workspace: ping-pong pressure, the residual's fixed-order partial sums, one result float, the 3D neighbour mask
-size_t ws_jacobi(const FnxGrid* g) { return al(ncell(g) * 4) + al(fnx::residual_scratch_bytes(g->B)) + al(4) + ws_mask(g); }
-struct JacobiWs { float* tmp; double* partials; float* res; unsigned char* mask; };
-bool carve_jacobi(const FnxGrid* g, void* ws, size_t ws_bytes, JacobiWs* out, size_t* need) {
-  Carver c(ws, ws_bytes);
+// 3D solver: the neighbour mask by rows and by row groups and the planes-alike bits (the layout is fnx::jacobi3d_mask_layout's)
+size_t ws_mask(const FnxGrid* g) { return g->is3D ? fnx::jacobi3d_mask_layout(dims(g), nullptr).bytes : 0; }
+// Jacobi workspace: ping-pong pressure, the residual's fixed-order partial sums, one result float, the 3D neighbour mask.  Returns
+// the bytes it takes; ws == nullptr: the size only.
+struct JacobiWs { float* tmp; double* partials; float* res; fnx::JacobiMaskLayout mask; };
+size_t carve_jacobi(const FnxGrid* g, void* ws, JacobiWs* out) {
+  Carver c(ws, 0);
   out->tmp = (float*)c.take(ncell(g) * 4);
   out->partials = (double*)c.take(fnx::residual_scratch_bytes(g->B));
   out->res = (float*)c.take(4);
-  out->mask = g->is3D ? (unsigned char*)c.take(ws_mask(g)) : nullptr;
-  *need = c.off;
-  return c.ok();
+  out->mask = fnx::jacobi3d_mask_layout(dims(g), g->is3D ? c.take(ws_mask(g)) : nullptr);
+  return c.off;
 }
+size_t ws_jacobi(const FnxGrid* g) { JacobiWs W; return carve_jacobi(g, nullptr, &W); }
 // PCG: the multigrid hierarchy (kept between steps by fnx_simulate_step), then the solver's vectors
 size_t ws_pcg_kept(const FnxGrid* g) { return al(fnx::pcg_kept_bytes(dims(g), g->is3D)); }
 size_t ws_pcg(const FnxGrid* g) { return ws_pcg_kept(g) + al(fnx::pcg_scratch_bytes(dims(g), g->is3D)); }
@@ -321,18 +322,42 @@ int fnx_velocity_divergence(const FnxGrid* g, const float* U, const float* flags
   return FNX_OK;
 }
 
-static int jacobi_solve(const FnxGrid* g, const float* flags, const float* div, float* p, float* residual, float p_tol,
-                        int max_iter, int* iters_done, void* ws, size_t ws_bytes, unsigned char* kept_mask, bool reuse_mask,
-                        void* stream, int verbose);
-
-int fnx_jacobi(const FnxGrid* g, const float* flags, const float* div, float* p, float* residual, float p_tol,
-               int max_iter, int* iters_done, void* ws, size_t ws_bytes, void* stream) {
-  return jacobi_solve(g, flags, div, p, residual, p_tol, max_iter, iters_done, ws, ws_bytes, nullptr, false, stream, 0);
+// Jacobi (the decisions are fnx_jacobi_plan.h's).  What every entry point does after its argument checks: carve the workspace, refusing
+// under its name, and in 3D build the neighbour mask unless the one in place is current (kept_mask: it lives there, not in the workspace)
+static int jacobi_begin(const char* name, const FnxGrid* g, const float* flags, void* ws, size_t ws_bytes, bool reuse_mask,
+                        hipStream_t s, JacobiWs* W, unsigned char* kept_mask = nullptr) {
+  const size_t need = carve_jacobi(g, ws, W);
+  if (!ws || need > ws_bytes) return fail(FNX_EWORKSPACE, "%s: workspace too small (%zu < %zu)", name, ws_bytes, need);
+  if (g->is3D && kept_mask) W->mask = fnx::jacobi3d_mask_layout(dims(g), kept_mask);
+  if (g->is3D && !reuse_mask) fnx::launch_jacobi3d_mask(dims(g), quirks(g), flags, W->mask, s);
+  return FNX_OK;
 }
 
-int fnx_jacobi_verbose(const FnxGrid* g, const float* flags, const float* div, float* p, float* residual, float p_tol,
-                       int max_iter, int* iters_done, void* ws, size_t ws_bytes, void* stream) {
-  return jacobi_solve(g, flags, div, p, residual, p_tol, max_iter, iters_done, ws, ws_bytes, nullptr, false, stream, 1);
+// the output planes [kb, ke) of a 3D pass (whole_ok: ke == 0 stands for all planes) and its second range [kb2, kb2 + ke - kb), if any
+static int check_plane_ranges(const char* name, const FnxGrid* g, int kb, int ke, int kb2, bool whole_ok) {
+  if (kb < 0 || ke > g->D || ((ke != 0 || !whole_ok) && ke <= kb)) return fail(FNX_EINVAL, "%s: bad plane range", name);
+  const int n = ke - kb;
+  if (kb2 >= 0 && (ke == 0 || kb2 + n > g->D || (kb2 < ke && kb < kb2 + n)))
+    return fail(FNX_EINVAL, "%s: bad or overlapping second plane range", name);
+  return FNX_OK;
+}
+
+// Issues the launches of a schedule, one profiler scope each: launch l reads what launch l - 1 wrote (the first: `in`, NULL = all zeros,
+// not read) and writes buf[(first + l) & 1].  Returns where the result lies.  The one place that chooses between the 2D and 3D launches.
+static const float* run_jacobi_launches(const FnxGrid* g, const fnx::JacobiSchedule& sch, const float* flags, const float* div,
+                                        const fnx::JacobiMaskLayout& mask, const float* in, float* const buf[2], int first,
+                                        hipStream_t s) {
+  const GridDims d = dims(g);
+  for (int l = 0; l < sch.n; ++l) {
+    const fnx::JacobiLaunch L = sch.at(l);
+    float* out = buf[(first + l) & 1];
+    fnx::ProfScope ps(FNX_PROF_JACOBI, s);
+    if (!g->is3D) fnx::launch_jacobi(d, flags, div, in, out, L.sweeps, in == nullptr, s);
+    else if (L.sweeps == 2) fnx::launch_jacobi3d_x2(d, mask, div, in, out, s, 0, 0, in == nullptr, -1, L.lay);
+    else fnx::launch_jacobi3d(d, mask, div, in, out, in == nullptr, s);
+    in = out;
+  }
+  return in;
 }
 
 static int jacobi_solve(const FnxGrid* g, const float* flags, const float* div, float* p, float* residual, float p_tol,
@@ -343,64 +368,32 @@ static int jacobi_solve(const FnxGrid* g, const float* flags, const float* div, 
   if (max_iter < 1) return fail(FNX_EINVAL, "At least 1 iteration is needed (maxIter < 1)");
   hipStream_t s = (hipStream_t)stream;
   const GridDims d = dims(g);
-  JacobiWs W; size_t need;
-  if (!carve_jacobi(g, ws, ws_bytes, &W, &need)) return fail(FNX_EWORKSPACE, "solve_linear_system: workspace too small (%zu < %zu)", ws_bytes, need);
-  float* tmp = W.tmp;
-  unsigned char* mask = W.mask;
-  if (g->is3D && kept_mask) mask = kept_mask;           // a slot nothing else in the step scribbles on
-  else reuse_mask = false;
-  const bool q = quirks(g);
-  if (g->is3D && !reuse_mask) fnx::launch_jacobi3d_mask(d, q, flags, mask, s);
-  auto sweep = [&](const float* in, float* out, int k, bool from_zero, int lay = 0) {
-    fnx::ProfScope ps(FNX_PROF_JACOBI, s);
-    if (g->is3D) {
-      if (k == 2) fnx::launch_jacobi3d_x2(d, mask, div, in, out, s, 0, 0, from_zero, -1, lay);
-      else fnx::launch_jacobi3d(d, mask, div, in, out, from_zero, s);
-    } else {
-      fnx::launch_jacobi(d, flags, div, in, out, k, from_zero, s);
-    }
-  };
+  JacobiWs W;                                           // kept_mask: a slot nothing else in the step scribbles on; only such a mask can be current
+  if (int rc = jacobi_begin("solve_linear_system", g, flags, ws, ws_bytes, reuse_mask && kept_mask, s, &W, kept_mask)) return rc;
+  float* const buf[2] = {p, W.tmp};
+  const int cus = cu_count();
+  const fnx::JacobiSchedule one = fnx::jacobi_schedule(d, g->is3D, 1, cus);      // the residual's sweep, the per-sweep test's
   // ||a - b||_2 per sample, max over the batch, reproducible (fixed-order fp64 partial sums, no atomics)
   const size_t per = (size_t)g->D * g->H * g->W;
   auto residual_of = [&](const float* a, const float* b, float* out) { fnx::launch_residual(g->B, per, 0, per, a, b, W.partials, nullptr, out, s); };
   const bool per_sweep = p_tol > 0.f || verbose;        // the reference's per-sweep host test / per-sweep print
   if (!per_sweep) {
-    // Sweeps per launch: 2D up to kmax (register temporal blocking); 3D pairs (the first one knows p = 0).  When the caller
-    // wants the residual ||p_n - p_(n-1)||, the last sweep runs on its own so that both iterates are in memory.
-    const int fused = residual ? max_iter - 1 : max_iter;
-    int plan[1024]; int nl = 0, left = fused;
-    const int kmax = g->is3D ? 2 : fnx::jacobi_max_sweeps_per_launch(d, false, fused);
-    while (left > 0 && nl < 1022) {
-      const int k = left < kmax ? left : kmax;
-      plan[nl++] = k; left -= k;
-    }
-    if (left > 0) return fail(FNX_EINVAL, "solve_linear_system: max_iter too large for one call (%d)", max_iter);
-    const int ntot = nl + (residual ? 1 : 0);
-    const float* in = nullptr;
-    // 3D: consecutive two-sweep passes hand each other p in the row-quad layout (fewer, wider vector-memory
-    // instructions: launch_jacobi3d_x2); the last of them writes rows
-    const bool quad = g->is3D && fnx::jacobi3d_quad_ok(d);
-    bool in_quad = false;
-    for (int l = 0; l < nl; ++l) {
-      float* out = ((ntot - 1 - l) % 2 == 0) ? p : tmp;    // the last launch writes p
-      const bool out_quad = quad && plan[l] == 2 && l + 1 < nl && plan[l + 1] == 2;
-      sweep(in, out, plan[l], l == 0, (in_quad ? 1 : 0) | (out_quad ? 2 : 0));
-      in = out; in_quad = out_quad;
-    }
+    // When the caller wants the residual ||p_n - p_(n-1)||, the last sweep runs on its own so that both iterates are in memory.
+    const fnx::JacobiSchedule sch = fnx::jacobi_schedule(d, g->is3D, residual ? max_iter - 1 : max_iter, cus);
+    if (sch.n > fnx::JACOBI_MAX_LAUNCHES) return fail(FNX_EINVAL, "solve_linear_system: max_iter too large for one call (%d)", max_iter);
+    const float* in = run_jacobi_launches(g, sch, flags, div, W.mask, nullptr, buf, fnx::jacobi_solve_first_buffer(sch, residual != nullptr), s);
     if (residual) {
-      sweep(in, p, 1, nl == 0);
+      run_jacobi_launches(g, one, flags, div, W.mask, in, buf, 0, s);
       residual_of(p, in, residual);
     }
     if (iters_done) *iters_done = max_iter;
   } else {
     // the reference's own per-sweep convergence test (fluids_init.cpp:961-979): one host read per sweep
     const float* in = nullptr;
-    float* bufs[2] = { p, tmp };
     int sweeps = 0;
     float r = 0.f;
     for (;;) {
-      float* out = bufs[sweeps & 1];
-      sweep(in, out, 1, sweeps == 0);
+      const float* out = run_jacobi_launches(g, one, flags, div, W.mask, in, buf, sweeps & 1, s);
       residual_of(out, in, W.res);
       HIP_OK(hipMemcpyAsync(&r, W.res, 4, hipMemcpyDeviceToHost, s));
       HIP_OK(hipStreamSynchronize(s));
@@ -425,6 +418,16 @@ static int jacobi_solve(const FnxGrid* g, const float* flags, const float* div, 
   return FNX_OK;
 }
 
+int fnx_jacobi(const FnxGrid* g, const float* flags, const float* div, float* p, float* residual, float p_tol,
+               int max_iter, int* iters_done, void* ws, size_t ws_bytes, void* stream) {
+  return jacobi_solve(g, flags, div, p, residual, p_tol, max_iter, iters_done, ws, ws_bytes, nullptr, false, stream, 0);
+}
+
+int fnx_jacobi_verbose(const FnxGrid* g, const float* flags, const float* div, float* p, float* residual, float p_tol,
+                       int max_iter, int* iters_done, void* ws, size_t ws_bytes, void* stream) {
+  return jacobi_solve(g, flags, div, p, residual, p_tol, max_iter, iters_done, ws, ws_bytes, nullptr, false, stream, 1);
+}
+
 int fnx_jacobi_sweeps(const FnxGrid* g, const float* flags, const float* div, float* p, int nsweeps, void* ws,
                       size_t ws_bytes, void* stream) {
   return fnx_jacobi_sweeps_ex(g, flags, div, p, nsweeps, ws, ws_bytes, 0, stream);
@@ -436,35 +439,13 @@ int fnx_jacobi_sweeps_ex(const FnxGrid* g, const float* flags, const float* div,
   if (!flags || !div || !p) return fail(FNX_EINVAL, "jacobi_sweeps: NULL tensor");
   if (nsweeps < 1) return fail(FNX_EINVAL, "At least 1 iteration is needed (maxIter < 1)");
   hipStream_t s = (hipStream_t)stream;
-  const GridDims d = dims(g);
-  JacobiWs W; size_t need;
-  if (!carve_jacobi(g, ws, ws_bytes, &W, &need)) return fail(FNX_EWORKSPACE, "jacobi_sweeps: workspace too small (%zu < %zu)", ws_bytes, need);
-  float* tmp = W.tmp;
-  unsigned char* mask = W.mask;
+  JacobiWs W;
+  if (int rc = jacobi_begin("jacobi_sweeps", g, flags, ws, ws_bytes, (reuse_mask & 1) != 0, s, &W)) return rc;
   const bool from_zero = (reuse_mask & 2) != 0;
-  if (g->is3D && !(reuse_mask & 1)) fnx::launch_jacobi3d_mask(d, quirks(g), flags, mask, s);
-  const int kmax = g->is3D ? 2 : fnx::jacobi_max_sweeps_per_launch(d, false, nsweeps);
   // ping-pong p -> tmp -> p ...; an odd number of launches ends in tmp and is copied back
-  const float* in = from_zero ? nullptr : p;
-  int done = 0;
-  const bool quad = g->is3D && fnx::jacobi3d_quad_ok(d);      // see jacobi_solve
-  bool in_quad = false;
-  for (int l = 0; done < nsweeps; ++l) {
-    const int k = nsweeps - done < kmax ? nsweeps - done : kmax;
-    float* out = (l % 2 == 0) ? tmp : p;
-    const bool out_quad = quad && k == 2 && nsweeps - done - k >= 2;        // the launch after this one is a two-sweep pass too
-    const int lay = (in_quad ? 1 : 0) | (out_quad ? 2 : 0);
-    in_quad = out_quad;
-    { fnx::ProfScope ps(FNX_PROF_JACOBI, s);
-      const bool fz = from_zero && l == 0;
-      if (g->is3D) {
-        if (k == 2) fnx::launch_jacobi3d_x2(d, mask, div, in, out, s, 0, 0, fz, -1, lay);
-        else fnx::launch_jacobi3d(d, mask, div, in, out, fz, s);
-      } else {
-        fnx::launch_jacobi(d, flags, div, in, out, k, fz, s);
-      } }
-    in = out; done += k;
-  }
+  float* const buf[2] = {p, W.tmp};
+  const fnx::JacobiSchedule sch = fnx::jacobi_schedule(dims(g), g->is3D, nsweeps, cu_count());
+  const float* in = run_jacobi_launches(g, sch, flags, div, W.mask, from_zero ? nullptr : p, buf, 1, s);
   if (in != p) HIP_OK(hipMemcpyAsync(p, in, ncell(g) * 4, hipMemcpyDeviceToDevice, s));
   HIP_OK(hipGetLastError());
   return FNX_OK;
@@ -492,23 +473,16 @@ int fnx_jacobi_pass_layout(const FnxGrid* g, const float* flags, const float* di
   if (!g->is3D) return fail(FNX_EINVAL, "jacobi_pass: 3D only (2D uses fnx_jacobi_sweeps)");
   const bool from_zero = p_in == nullptr;                 // the first pass of a solve: p = 0 everywhere, nothing to read
   if (nsweeps < 1 || nsweeps > 2) return fail(FNX_EINVAL, "jacobi_pass: nsweeps must be 1 or 2");
-  if (k_begin < 0 || k_end > g->D || (k_end != 0 && k_end <= k_begin)) return fail(FNX_EINVAL, "jacobi_pass: bad plane range");
-  if (k_begin2 >= 0) {
-    const int n = k_end - k_begin;
-    if (k_end == 0 || k_begin2 + n > g->D || (k_begin2 < k_end && k_begin < k_begin2 + n))
-      return fail(FNX_EINVAL, "jacobi_pass: bad or overlapping second plane range");
-  }
+  if (int rc = check_plane_ranges("jacobi_pass", g, k_begin, k_end, k_begin2, true)) return rc;
   hipStream_t s = (hipStream_t)stream;
   const GridDims d = dims(g);
-  JacobiWs W; size_t need;
-  if (!carve_jacobi(g, ws, ws_bytes, &W, &need)) return fail(FNX_EWORKSPACE, "jacobi_pass: workspace too small (%zu < %zu)", ws_bytes, need);
-  unsigned char* mask = W.mask;
-  if (!reuse_mask) fnx::launch_jacobi3d_mask(d, quirks(g), flags, mask, s);
+  JacobiWs W;
+  if (int rc = jacobi_begin("jacobi_pass", g, flags, ws, ws_bytes, reuse_mask != 0, s, &W)) return rc;
   fnx::ProfScope ps(FNX_PROF_JACOBI, s);
-  if (nsweeps == 2) fnx::launch_jacobi3d_x2(d, mask, div, p_in, p_out, s, k_begin, k_end, from_zero, k_begin2, layout);
+  if (nsweeps == 2) fnx::launch_jacobi3d_x2(d, W.mask, div, p_in, p_out, s, k_begin, k_end, from_zero, k_begin2, layout);
   else {
-    fnx::launch_jacobi3d(d, mask, div, p_in, p_out, from_zero, s, k_begin, k_end);
-    if (k_begin2 >= 0) fnx::launch_jacobi3d(d, mask, div, p_in, p_out, from_zero, s, k_begin2, k_begin2 + (k_end - k_begin));
+    fnx::launch_jacobi3d(d, W.mask, div, p_in, p_out, from_zero, s, k_begin, k_end);
+    if (k_begin2 >= 0) fnx::launch_jacobi3d(d, W.mask, div, p_in, p_out, from_zero, s, k_begin2, k_begin2 + (k_end - k_begin));
   }
   HIP_OK(hipGetLastError());
   return FNX_OK;
@@ -516,7 +490,7 @@ int fnx_jacobi_pass_layout(const FnxGrid* g, const float* flags, const float* di
 
 int fnx_jacobi_pass_mirror_ok(const FnxGrid* g, int planes, int two_ranges, int layout) {
   if (check_grid(g) != FNX_OK || !g->is3D || planes < 1) return 0;
-  return fnx::jacobi3d_mirror_ok(dims(g), planes, two_ranges != 0, false, layout) ? 1 : 0;
+  return fnx::jacobi3d_mirror_ok(dims(g), planes, two_ranges != 0, false, layout, cu_count()) ? 1 : 0;
 }
 
 int fnx_jacobi_pass_mirror(const FnxGrid* g, const float* flags, const float* div, const float* p_in, float* p_out, int k_begin,
@@ -524,20 +498,16 @@ int fnx_jacobi_pass_mirror(const FnxGrid* g, const float* flags, const float* di
                            int reuse_mask, void* stream) {
   if (int rc = check_grid(g)) return rc;
   if (!g->is3D || !flags || !div || !p_in || !p_out || p_in == p_out || !mirror) return fail(FNX_EINVAL, "jacobi_pass_mirror: NULL or aliased argument");
-  if (k_begin < 0 || k_end > g->D || k_end <= k_begin) return fail(FNX_EINVAL, "jacobi_pass_mirror: bad plane range");
-  const int np = k_end - k_begin;
-  if (k_begin2 >= 0 && (k_begin2 + np > g->D || (k_begin2 < k_end && k_begin < k_begin2 + np)))
-    return fail(FNX_EINVAL, "jacobi_pass_mirror: bad or overlapping second plane range");
-  if ((layout != 0 && layout != 3) || (layout == 3 && !fnx::jacobi3d_quad_ok(dims(g))) || !fnx::jacobi3d_mirror_ok(dims(g), np, k_begin2 >= 0, false, layout))
+  if (int rc = check_plane_ranges("jacobi_pass_mirror", g, k_begin, k_end, k_begin2, false)) return rc;
+  const GridDims d = dims(g);
+  if ((layout == 3 && !fnx::jacobi3d_quad_ok(d)) || !fnx::jacobi3d_mirror_ok(d, k_end - k_begin, k_begin2 >= 0, false, layout, cu_count()))
     return fail(FNX_EINVAL, "jacobi_pass_mirror: this launch cannot mirror its output (fnx_jacobi_pass_mirror_ok)");
   if (mirror->planes < 1 || !mirror->out[0][0] || (mirror->slot_select[0] && !mirror->out[0][1]) ||
       (k_begin2 >= 0 && (!mirror->out[1][0] || (mirror->slot_select[1] && !mirror->out[1][1]))))
     return fail(FNX_EINVAL, "jacobi_pass_mirror: bad mirror");
   hipStream_t s = (hipStream_t)stream;
-  const GridDims d = dims(g);
-  JacobiWs W; size_t need;
-  if (!carve_jacobi(g, ws, ws_bytes, &W, &need)) return fail(FNX_EWORKSPACE, "jacobi_pass_mirror: workspace too small (%zu < %zu)", ws_bytes, need);
-  if (!reuse_mask) fnx::launch_jacobi3d_mask(d, quirks(g), flags, W.mask, s);
+  JacobiWs W;
+  if (int rc = jacobi_begin("jacobi_pass_mirror", g, flags, ws, ws_bytes, reuse_mask != 0, s, &W)) return rc;
   fnx::ProfScope ps(FNX_PROF_JACOBI, s);
   fnx::JacobiMirror m{};
   for (int r = 0; r < 2; ++r) { m.out[r][0] = mirror->out[r][0]; m.out[r][1] = mirror->out[r][1]; m.sel[r] = mirror->slot_select[r]; }

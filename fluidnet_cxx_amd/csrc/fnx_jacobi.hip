@@ -502,8 +502,7 @@ __global__ __launch_bounds__(256) void jacobi3d_march_kernel(GridDims g, const u
 // of HBM traffic per pass the kernel moves 5.3 TB/s: it sits on the HBM bound of a 2-sweep pass, and more sweeps per
 // pass in registers would pay (R+2K)/R redundant rows.
 // ---------------------------------------------------------------------------------------------------
-constexpr int Z2R = 4, Z2NW = 1;
-constexpr int Z2WPS = 4;                   // waves per SIMD the register budget is sized for
+using fnx::Z2R; using fnx::Z2NW; using fnx::Z2WPS;   // = 4, 1, 4: fnx_jacobi_plan.h, where the host plans the launch by them
 constexpr int Z2C_DEFAULT = 16;
 
 // x / 6.0f, correctly rounded, without the v_rcp/v_div_scale expansion: q = x*zh, r = x - 6q (exact), q + r*zh with
@@ -934,41 +933,15 @@ void launch_tiles(const GridDims& g, const float* flags, const float* div, const
   launch_wg<8, 8>(g, flags, div, p_in, p_out, from_zero, K, s);
 }
 
+// The fourteen instances of the two-sweep march: (ZERO, LAY) in {(T,0), (F,0), (T,2), (F,2), (F,1), (F,3)}, each SPLIT or not, through
+// march2; the two that mirror (not SPLIT, not from zero, lay 0 or 3) are named where they are launched.
+using March2 = void (*)(GridDims, const unsigned*, const unsigned*, const float*, const float*, float*, int, int, int, int, int, int, MirrorArgs);
+template <bool ZERO, int LAY>
+March2 march2(bool split) { return split ? jacobi3d_march2_kernel<ZERO, true, LAY> : jacobi3d_march2_kernel<ZERO, false, LAY>; }
+
 }  // namespace
 
 namespace fnx {
-
-constexpr int KMAX_2D = 8, KLARGE_2D = 10, KDEEP_2D = 28;
-
-// 64 x 64 tiles with an output window of (64 - 2K)^2: how many a launch of K sweeps needs
-static long tiles_2d(const GridDims& g, int K) {
-  const int o = 64 - 2 * K;
-  return (long)((g.W + o - 1) / o) * ((g.H + o - 1) / o) * g.B;
-}
-
-int jacobi_max_sweeps_per_launch(const GridDims& g, bool is3d, int total) {
-  if (is3d || g.D != 1) return 1;
-
-  // Small grids are launch-latency bound (a launch costs ~5 us + ~0.35 us per sweep whatever the halo does to the work, as
-  // long as every tile has a CU to itself): the fewest launches whose tiles all run at once, the sweeps dealt evenly.
-  if (total > KMAX_2D) {
-    const long cus = cu_count();
-    int kcap = 0;
-    for (int K = KDEEP_2D; K > KMAX_2D; --K) if (tiles_2d(g, K) <= cus) { kcap = K; break; }
-    if (kcap) {
-      const int nl = (total + kcap - 1) / kcap;
-      return (total + nl - 1) / nl;
-    }
-  }
-  // a wave's chain per sweep is its 8 rows whatever K, so the halo (2K of the 64 columns and rows of a tile) is what limits K:
-  // 7 where launches are still short (28 sweeps = 4 launches); on large grids at most 10, the sweeps dealt evenly over the
-  // launches (measured at 2048^2 x 100 sweeps, ms per step: 13 launches of <= 8 0.584, 12 of <= 9 0.607, 10 of 10 0.574, 9 of <= 12
-  // 0.615, 8 of <= 14 0.630)
-  if ((long)g.W * g.H * g.B <= (2l << 20)) return 7;
-  const int nl = (total + KLARGE_2D - 1) / KLARGE_2D;
-  const int k = (total + nl - 1) / nl;
-  return k < 1 ? 1 : k;
-}
 
 // 2D: nsweeps in [1, jacobi_max_sweeps_per_launch] sweeps from p_in into p_out
 void launch_jacobi(const GridDims& g, const float* flags, const float* div, const float* p_in, float* p_out, int nsweeps,
@@ -978,110 +951,55 @@ void launch_jacobi(const GridDims& g, const float* flags, const float* div, cons
   jacobi_sweep_kernel<<<grid, block, 0, s>>>(g, flags, div, p_in, p_out, from_zero);
 }
 
-// 3D fast path (mask precomputed by launch_jacobi3d_mask)
-// the mask allocation: B*D*H*W neighbour-mask bytes, then (256-B aligned) the same bytes in row groups of four
-static size_t maskq_offset(const GridDims& g) { return (((size_t)g.B * g.DHW) + 255) & ~(size_t)255; }
-// ... then (256-B aligned) one "same as the plane below" bit per (sample, tile of the two-sweep march, plane), 32 planes to a word
-static size_t masksame_offset(const GridDims& g) {
-  return (maskq_offset(g) + (size_t)g.B * g.D * ((g.H + 3) / 4) * g.W * 4 + 255) & ~(size_t)255;
-}
-size_t jacobi3d_mask_bytes(const GridDims& g) {
-  const size_t tiles = (size_t)((g.W + 59) / 60) * ((g.H + Z2NW * Z2R - 1) / (Z2NW * Z2R)) * g.B;
-  return masksame_offset(g) + tiles * ((g.D + 31) / 32) * 4;
-}
-
-void launch_jacobi3d_mask(const GridDims& g, bool quirks, const float* flags, unsigned char* mask, hipStream_t s) {
+// 3D (the mask built by launch_jacobi3d_mask)
+void launch_jacobi3d_mask(const GridDims& g, bool quirks, const float* flags, const JacobiMaskLayout& m, hipStream_t s) {
   const dim3 grid((g.W + 63) / 64, (g.H + 3) / 4, g.B * g.D), block(64, 4);
-  if (quirks) jacobi3d_mask_kernel<true><<<grid, block, 0, s>>>(g, flags, mask);
-  else jacobi3d_mask_kernel<false><<<grid, block, 0, s>>>(g, flags, mask);
+  if (quirks) jacobi3d_mask_kernel<true><<<grid, block, 0, s>>>(g, flags, m.rows);
+  else jacobi3d_mask_kernel<false><<<grid, block, 0, s>>>(g, flags, m.rows);
   const dim3 gridq((g.W + 63) / 64, ((g.H + 3) / 4 + 3) / 4, g.B * g.D);
-  jacobi3d_maskq_kernel<<<gridq, block, 0, s>>>(g, mask, (unsigned*)(mask + maskq_offset(g)));
-  const int nxt = (g.W + 59) / 60, nyt = (g.H + Z2NW * Z2R - 1) / (Z2NW * Z2R), kwords = (g.D + 31) / 32;
-  jacobi3d_masksame_kernel<<<dim3(nxt * nyt, kwords, g.B), 64, 0, s>>>(g, (const unsigned*)(mask + maskq_offset(g)),
-                                                                         (unsigned*)(mask + masksame_offset(g)), nxt, nyt, kwords);
-}
-
-// can the two-sweep passes of this grid hand each other p in the row-quad layout (`lay` of launch_jacobi3d_x2)?
-bool jacobi3d_quad_ok(const GridDims& g) { return g.H % 4 == 0 && Z2R == 4 && Z2NW == 1; }
-
-// may a two-sweep launch of these plane ranges mirror its output (launch_jacobi3d_x2's `mirror`)?  One resident set of waves, both
-// arrays in the same layout, not the from-zero pass
-bool jacobi3d_mirror_ok(const GridDims& g, int np, bool two_ranges, bool from_zero, int lay) {
-  const long slots = (long)(Z2WPS * 4 / Z2NW) * cu_count();
-  const long ntiles = (long)((g.W + 59) / 60) * ((g.H + Z2NW * Z2R - 1) / (Z2NW * Z2R)) * g.B;
-  return !from_zero && (lay == 0 || lay == 3) && np >= 1 && ntiles * (two_ranges ? 2 : 1) <= slots && (size_t)(np + 4) * g.HW < 0x3fffffffu;
+  jacobi3d_maskq_kernel<<<gridq, block, 0, s>>>(g, m.rows, m.quads);
+  const Jacobi3dTiles t = jacobi3d_tiles(g);
+  jacobi3d_masksame_kernel<<<dim3(t.nxt * t.nyt, t.kwords, g.B), 64, 0, s>>>(g, m.quads, m.same, t.nxt, t.nyt, t.kwords);
 }
 
 // two sweeps in one pass: p_in = p^n, p_out = p^{n+2}.  lay: bit 0 = p_in, bit 1 = p_out in the row-quad layout
-void launch_jacobi3d_x2(const GridDims& g, const unsigned char* mask, const float* div, const float* p_in, float* p_out,
+void launch_jacobi3d_x2(const GridDims& g, const JacobiMaskLayout& mask, const float* div, const float* p_in, float* p_out,
                         hipStream_t s, int kb, int ke, bool from_zero, int kb2, int lay, const JacobiMirror* mirror) {
   if (ke <= kb) { kb = 0; ke = g.D; kb2 = -1; }
-  const int slots = (Z2WPS * 4 / Z2NW) * cu_count();      // resident waves: Z2WPS per SIMD (<= 128 VGPRs each)
-  // Smallest plane chunk.  Every (tile, chunk) wave is resident at once, so a launch lasts (chunk + 2 lead-in steps) x
-  // the per-step time of one wave, whatever the occupancy: small plane ranges (the slab driver's edge parts, small
-  // grids) are cut as finely as the wave slots allow (measured 20 -> 14 us for 14 planes of 512^2).
-  constexpr int zmin = 2;
-  const int nxt = (g.W + 59) / 60, nyt = (g.H + Z2NW * Z2R - 1) / (Z2NW * Z2R);
-  const int np = ke - kb, ntiles = nxt * nyt * g.B;
-  // as many equal plane chunks per tile as fit one resident set
-  int nzc = slots / ntiles;
-  if (kb2 >= 0) nzc /= 2;                                // two plane ranges share the resident set
-  if (nzc < 1) nzc = 1;
-  int zchunk = (np + nzc - 1) / nzc;
-  if (zchunk < zmin) zchunk = zmin;
-  if (ntiles > slots) zchunk = 0;                        // more tiles than slots: even split of the (tile, plane) space
-  if (zchunk == 0 && (size_t)(np + 4) * g.HW >= 0x3fffffffu) zchunk = 64;   // keep a segment's 32-bit offsets below 4 GB
-  if (kb2 >= 0 && (zchunk <= 0 || 2 * ntiles > slots)) {   // no room for both ranges at once: one after the other
-    launch_jacobi3d_x2(g, mask, div, p_in, p_out, s, kb, ke, from_zero, -1, lay, nullptr);
-    launch_jacobi3d_x2(g, mask, div, p_in, p_out, s, kb2, kb2 + np, from_zero, -1, lay, nullptr);
-    return;
-  }
-  long long G;
-  if (zchunk > 0) {
-    G = (long long)ntiles * ((np + zchunk - 1) / zchunk) * (kb2 >= 0 ? 2 : 1);
-    G = ((G + 7) / 8) * 8;
-  } else {
-    G = (long long)ntiles * np / 8;
-    if (G > slots) G = slots;
-    G = (G / 8) * 8;
-    if (G < 8) G = 8;
-  }
-  const dim3 grid((unsigned)G), block(64, Z2NW);
-  const unsigned* maskq = (const unsigned*)(mask + maskq_offset(g));
-  const unsigned* msame = (const unsigned*)(mask + masksame_offset(g));
-  if (mirror) {                                            // (jacobi3d_mirror_ok has been checked: resident set, not from zero, lay 0 or 3)
-    MirrorArgs m{};
+  const int np = ke - kb;
+  const Jacobi3dX2Plan p = jacobi3d_x2_plan(g, np, kb2 >= 0, from_zero, lay, cu_count());
+  const Jacobi3dTiles t = jacobi3d_tiles(g);
+  const dim3 grid((unsigned)p.G), block(64, Z2NW);
+  MirrorArgs m{};
+  if (p.serial) mirror = nullptr;                          // (jacobi3d_mirror_ok refuses such a launch: nothing asks for it)
+  if (mirror) {                                            // (it has been checked: one resident set, not from zero, lay 0 or 3)
     for (int r = 0; r < 2; ++r) { m.out[r][0] = mirror->out[r][0]; m.out[r][1] = mirror->out[r][1]; m.sel[r] = mirror->sel[r]; }
     m.k[0] = mirror->k[0]; m.k[1] = mirror->k[1]; m.n = mirror->n;
     m.bstride = mirror->bstride; m.clock = mirror->clock;
-    if (lay == 3) jacobi3d_march2_kernel<false, false, 3, true><<<grid, block, 0, s>>>(g, maskq, msame, div, p_in, p_out, nxt, nyt, zchunk, kb, ke, kb2, m);
-    else jacobi3d_march2_kernel<false, false, 0, true><<<grid, block, 0, s>>>(g, maskq, msame, div, p_in, p_out, nxt, nyt, zchunk, kb, ke, kb2, m);
-    return;
   }
-#define J3Q(Z, S, L) jacobi3d_march2_kernel<Z, S, L><<<grid, block, 0, s>>>(g, maskq, msame, div, p_in, p_out, nxt, nyt, zchunk, kb, ke, kb2)
-#define J3Q_S(Z, L) do { if (zchunk > 0) J3Q(Z, false, L); else J3Q(Z, true, L); } while (0)
-  if (from_zero) lay &= 2;                                 // no input: its layout does not matter
-  if (lay == 0) { if (from_zero) J3Q_S(true, 0); else J3Q_S(false, 0); }
-  else if (lay == 2) { if (from_zero) J3Q_S(true, 2); else J3Q_S(false, 2); }
-  else if (lay == 3) J3Q_S(false, 3);
-  else J3Q_S(false, 1);
-#undef J3Q_S
-#undef J3Q
+  for (int r = 0; r < (p.serial ? 2 : 1); ++r) {            // serial: the ranges one after the other, each alone
+    const int b0 = r == 0 ? kb : kb2, b2 = p.serial ? -1 : kb2;
+    March2 k;
+    if (mirror) k = p.lay == 3 ? jacobi3d_march2_kernel<false, false, 3, true> : jacobi3d_march2_kernel<false, false, 0, true>;
+    else if (from_zero) k = p.lay == 2 ? march2<true, 2>(p.split) : march2<true, 0>(p.split);
+    else k = p.lay == 0 ? march2<false, 0>(p.split) : p.lay == 1 ? march2<false, 1>(p.split) : p.lay == 2 ? march2<false, 2>(p.split) : march2<false, 3>(p.split);
+    k<<<grid, block, 0, s>>>(g, mask.quads, mask.same, div, p_in, p_out, t.nxt, t.nyt, p.zchunk, b0, b0 + np, b2, m);
+  }
 }
 
-void launch_jacobi3d(const GridDims& g, const unsigned char* mask, const float* div, const float* p_in, float* p_out,
+void launch_jacobi3d(const GridDims& g, const JacobiMaskLayout& mask, const float* div, const float* p_in, float* p_out,
                      bool from_zero, hipStream_t s, int kb, int ke) {
   if (ke <= kb) { kb = 0; ke = g.D; }
   if (from_zero) {
     const size_t count = (size_t)(ke - kb) * g.HW;
     size_t nb = (count + 256 * 4 - 1) / (256 * 4);
     if (nb > 4096) nb = 4096;
-    jacobi3d_first_kernel<<<(unsigned)nb, 256, 0, s>>>(g.B, (size_t)g.DHW, (size_t)kb * g.HW, count, div, mask, p_out);
+    jacobi3d_first_kernel<<<(unsigned)nb, 256, 0, s>>>(g.B, (size_t)g.DHW, (size_t)kb * g.HW, count, div, mask.rows, p_out);
     return;
   }
   const int nzc = (ke - kb + ZCHUNK - 1) / ZCHUNK;
   const dim3 grid((g.W + 63) / 64, (g.H + 4 * ZR - 1) / (4 * ZR), g.B * nzc), block(64, 4);
-  jacobi3d_march_kernel<<<grid, block, 0, s>>>(g, mask, div, p_in, p_out, nzc, kb, ke);
+  jacobi3d_march_kernel<<<grid, block, 0, s>>>(g, mask.rows, div, p_in, p_out, nzc, kb, ke);
 }
 
 size_t residual_scratch_bytes(int B) { return (size_t)B * RES_BLOCKS * sizeof(double); }

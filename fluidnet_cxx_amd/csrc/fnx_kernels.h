@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "fnx_device.h"
+#include "fnx_jacobi_plan.h"
 
 namespace fnx {
 
@@ -106,25 +107,23 @@ struct RenderConsts { float k_view, k_light, ambient, one_minus_ambient, albedo_
 void launch_render_volume(const GridDims& g, int view_dir, int light_dir, const RenderConsts& c, const float* density, const float* flags,
                           float* Lws, float* image, hipStream_t s);
 
-// Jacobi (fnx_jacobi.hip)
+// Jacobi (fnx_jacobi.hip).  What a call decides before it launches is fnx_jacobi_plan.h, pure functions: the schedule of a run of sweeps,
+// the tile geometry, mask layout, launch plan and mirror predicate of the 3D two-sweep march.  The launches:
 // 2D: `nsweeps` sweeps (1..jacobi_max_sweeps_per_launch) from p_in into p_out; from_zero: p_in is all zeros and is not read
 void launch_jacobi(const GridDims& g, const float* flags, const float* div, const float* p_in, float* p_out, int nsweeps,
                    bool from_zero, hipStream_t s);
-int  jacobi_max_sweeps_per_launch(const GridDims& g, bool is3d, int total_sweeps);   // total_sweeps: what the solve still has to run
 // 3D: flags -> 7-bit neighbour mask (once per solve), then z-marching passes of two sweeps (one for an odd remainder)
-size_t jacobi3d_mask_bytes(const GridDims& g);   // bytes of the `mask` allocation of the 3D launches below (byte mask + the same bytes in row groups of four + one "same as the plane below" bit per tile and plane of the two-sweep march)
-void launch_jacobi3d_mask(const GridDims& g, bool quirks, const float* flags, unsigned char* mask, hipStream_t s);
+void launch_jacobi3d_mask(const GridDims& g, bool quirks, const float* flags, const JacobiMaskLayout& mask, hipStream_t s);
 // kb/ke: restrict the OUTPUT to planes [kb, ke) (0,0 = all planes); inputs are read from kb-1 (kb-2 for x2) on
-void launch_jacobi3d(const GridDims& g, const unsigned char* mask, const float* div, const float* p_in, float* p_out,
+void launch_jacobi3d(const GridDims& g, const JacobiMaskLayout& mask, const float* div, const float* p_in, float* p_out,
                      bool from_zero, hipStream_t s, int kb = 0, int ke = 0);
 // mirror of a two-sweep launch's output: planes [k[r], k[r] + n) of plane range r also go to out[r][q] + sample * bstride (floats),
 // q = (*sel[r] + 1) & 1 read on the device (sel NULL: q = 0)
 struct JacobiMirror { float* out[2][2]; const unsigned* sel[2]; int k[2]; int n; unsigned long long bstride; unsigned long long* clock; };
-bool jacobi3d_mirror_ok(const GridDims& g, int np, bool two_ranges, bool from_zero, int lay);
-void launch_jacobi3d_x2(const GridDims& g, const unsigned char* mask, const float* div, const float* p_in, float* p_out,
+// plans (jacobi3d_x2_plan) and launches: once, or once per plane range when the two (kb2 >= 0: [kb2, kb2 + ke - kb)) do not fit together
+void launch_jacobi3d_x2(const GridDims& g, const JacobiMaskLayout& mask, const float* div, const float* p_in, float* p_out,
                         hipStream_t s, int kb = 0, int ke = 0, bool from_zero = false, int kb2 = -1, int lay = 0,
                         const JacobiMirror* mirror = nullptr);
-bool jacobi3d_quad_ok(const GridDims& g);   // may two-sweep passes hand each other p in the row-quad layout (lay bits 0 / 1 = p_in / p_out)?
 // Reproducible residual (no atomics): per sample b the squared differences of a[b*per_sample + first + q] - b[...] (b == null:
 // zeros), q < count, summed in a fixed order in fp64 through `partials` (residual_scratch_bytes(B)); sumsq (B floats, may be
 // null) receives the sums, res (1 float, may be null) max_b sqrt(sum)
