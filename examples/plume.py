@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """The reference's `pytorch/plume.py` main loop on this backend -- what a driver looks like after the switch.
 
-    python examples/plume.py [--res 128] [--iters 200] [--out-iter 50] [--method jacobi|pcg|convnet] [--weights CKPT] [--vorticity AMP]
-                             [--depth N] [--weights3d CKPT] [--render] [--folder out] [--restart]
+    python examples/plume.py [--res 128] [--iters 200] [--out-iter 50] [--method jacobi|pcg|convnet|hybrid] [--weights CKPT]
+                             [--pcg-warm] [--vorticity AMP] [--depth N] [--weights3d CKPT] [--render] [--folder out] [--restart]
 
 Same structure as the reference driver (plume.py:66-178 setup, :231-424 loop): build the batch, `createPlumeBCs`, optional
 restart from `<folder>/restart.pth`, echo the configuration as YAML, then `simulate()` per iteration and, every `out-iter`
@@ -11,7 +11,8 @@ driver: `lib` -> `fluidnet_cxx_amd`.  `--method convnet --weights CKPT` projects
 writes ({'state_dict', 'mconf', ...}), loaded the way the reference driver loads convModel_lastEpoch_best.pth (plume.py:119-123).
 `--depth N` (N > 1) runs the 3D plume on a N x res x res grid (jacobi, pcg and --vorticity as in 2D); there `--method convnet` takes
 `--weights3d CKPT`, a checkpoint of `examples/train.py --depth N` (the 3D net; a 2D checkpoint given by --weights is refused).  `--render` adds volume renderings of the density (output.save_render: from the front, lit from above, and from the side)
-to every output event."""
+to every output event.  `--method hybrid` takes the same checkpoints as convnet and projects with the converged solve started from the
+net's pressure; `--pcg-warm` starts the 'pcg' solve from the previous step's pressure (mconf['pcgWarmStart'])."""
 import argparse
 import os
 import sys
@@ -30,12 +31,14 @@ def parser():
     ap.add_argument("--res", type=int, default=128)
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--out-iter", type=int, default=50)
-    ap.add_argument("--method", default="jacobi", choices=["jacobi", "pcg", "convnet"])
-    ap.add_argument("--weights", default=None, metavar="CKPT", help="checkpoint of examples/train.py (needed by --method convnet)")
+    ap.add_argument("--method", default="jacobi", choices=["jacobi", "pcg", "convnet", "hybrid"])
+    ap.add_argument("--weights", default=None, metavar="CKPT", help="checkpoint of examples/train.py (needed by --method convnet and hybrid)")
+    ap.add_argument("--pcg-warm", action="store_true",
+                    help="--method pcg: start each solve from the previous step's pressure (mconf['pcgWarmStart'])")
     ap.add_argument("--vorticity", type=float, default=0.0, metavar="AMP",
                     help="vorticity confinement amplitude (mconf['vorticityConfinementAmp'], no reference key; 0 = off)")
     ap.add_argument("--weights3d", default=None, metavar="CKPT",
-                    help="checkpoint of examples/train.py --depth N (needed by --method convnet with --depth > 1)")
+                    help="checkpoint of examples/train.py --depth N (needed by --method convnet and hybrid with --depth > 1)")
     ap.add_argument("--depth", type=int, default=1, metavar="N", help="cells along z; 1 (default) is the 2D plume, N > 1 the 3D one")
     ap.add_argument("--render", action="store_true", help="write volume renderings (render_<view>_<it>.png) with every output event")
     ap.add_argument("--folder", default="plume_out")
@@ -46,21 +49,25 @@ def parser():
 def parse_args(argv=None):
     ap = parser()
     a = ap.parse_args(argv)
+    uses_net = a.method in ("convnet", "hybrid")
+    if a.pcg_warm and a.method != "pcg":
+        ap.error("--pcg-warm is only read by --method pcg")
     if a.depth < 1 or a.depth == 2:
         ap.error("--depth must be 1 (2D) or at least 3")
     if a.depth > 1:
         if a.weights is not None:
             ap.error("--weights with --depth > 1: no 3D weights can be trained here by the 2D trainer this checkpoint comes from; "
                      "train the 3D net with examples/train.py --depth N and pass its checkpoint as --weights3d CKPT")
-        if (a.method == "convnet") != (a.weights3d is not None):
-            ap.error("--method convnet with --depth > 1 needs --weights3d CKPT, and --weights3d is only read by --method convnet")
-        if a.method == "convnet" and a.depth < 4:
-            ap.error("--method convnet needs --depth of at least 4 (the net's three scales)")
+        if uses_net != (a.weights3d is not None):
+            ap.error(f"--method {a.method if uses_net else 'convnet'} with --depth > 1 needs --weights3d CKPT, and --weights3d is only read by "
+                     "--method convnet and hybrid")
+        if uses_net and a.depth < 4:
+            ap.error(f"--method {a.method} needs --depth of at least 4 (the net's three scales)")
         return a
     if a.weights3d is not None:
         ap.error("--weights3d is a 3D checkpoint: it needs --depth N (N > 1)")
-    if (a.method == "convnet") != (a.weights is not None):
-        ap.error("--method convnet needs --weights CKPT, and --weights is only read by --method convnet")
+    if uses_net != (a.weights is not None):
+        ap.error(f"--method {a.method if uses_net else 'convnet'} needs --weights CKPT, and --weights is only read by --method convnet and hybrid")
     return a
 
 
@@ -71,12 +78,12 @@ def main(argv=None):
     simConf = dict(dt=0.1, maccormackStrength=0.6, sampleOutsideFluid=False, buoyancyScale=0.25, gravityScale=0, viscosity=0,
                    correctScalar=False, gravityVec=dict(x=0.0, y=-1.0, z=0.0), operatingDensity=0.0, pTol=0.0, jacobiIter=28,
                    simMethod=a.method, resX=a.res, resY=a.res, maxIter=a.iters, outputFolder=a.folder)
-    if a.method == "pcg":                                 # the converged solve (fluid.solveLinearSystemPCG)
-        simConf.update(pcgTol=1e-5, pcgIter=50)
+    if a.method in ("pcg", "hybrid"):                     # the converged solve (fluid.solveLinearSystemPCG), cold or from a guess
+        simConf.update(pcgTol=1e-5, pcgIter=50, pcgWarmStart=bool(a.pcg_warm))
     if a.vorticity > 0:                                   # puts back the small-scale rotation the advection smooths away
         simConf.update(vorticityConfinementAmp=a.vorticity)
     net = None
-    if a.method == "convnet":                             # plume.py:119-123
+    if a.method in ("convnet", "hybrid"):                 # plume.py:119-123
         state = torch.load(a.weights3d if a.depth > 1 else a.weights, map_location="cpu", weights_only=False)
         mconf = state["mconf"]
         assert bool(mconf.get("is3D", False)) == (a.depth > 1), "the checkpoint's net has another dimension than the grid"

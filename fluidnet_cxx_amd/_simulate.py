@@ -26,7 +26,10 @@ map was already built by an earlier call with bit 2 -- e.g. 0 for the first step
 automatic mode records it only after a call has succeeded).
 `static_flags=None` (the default) with no `workspace` is the automatic mode above; with a caller's workspace it means 0.
 sim_method 'pcg' (no reference counterpart) projects with the converged solve of fluid.solveLinearSystemPCG: mconf['pcgTol']
-(default 1e-5) and mconf['pcgIter'] (default 50); the wall BCs and periodic patches as for 'jacobi'.
+(default 1e-5) and mconf['pcgIter'] (default 50); the wall BCs and periodic patches as for 'jacobi'.  mconf['pcgWarmStart'] (default
+off) starts that solve from batch_dict['p'], the previous step's pressure (a first step from p = 0 is the cold solve).
+sim_method 'hybrid' is 'pcg' started from the net's pressure: p0, _ = net(cat(p, U, flags, density)) on the U the solve projects (the
+net's velocity is discarded), then solveLinearSystemPCG(..., p0=p0) to pcgTol / pcgIter -- the net's speed-up with a checked residual.
 mconf['vorticityConfinementAmp'] > 0 (no reference key either) adds fluid.addVorticityConfinement with that amplitude after
 addGravity and before setWallBcs, for every method; whole grids only (a compute window or z-slab `geom` raises).
 `geom` (an `ext.Geom`, 3D only) selects the reference-quirk mode / a z-slab view for this call; it is per call, the
@@ -137,7 +140,10 @@ def release_workspaces():
 
 def simulate(mconf, batch_dict, net, sim_method, output_div=False, fused=True, workspace=None, static_flags=None,
              geom=None):
-    assert sim_method in ("convnet", "jacobi", "pcg"), "Simulation method not supported. Choose convnet, jacobi or pcg."
+    assert sim_method in ("convnet", "jacobi", "pcg", "hybrid"), "Simulation method not supported. Choose convnet, jacobi, pcg or hybrid."
+    uses_net = sim_method in ("convnet", "hybrid")
+    uses_pcg = sim_method in ("pcg", "hybrid")
+    pcg_warm = sim_method == "pcg" and bool(mconf.get("pcgWarmStart", False))
     dt = float(mconf["dt"])
     maccormackStrength = mconf["maccormackStrength"]
     sampleOutsideFluid = mconf["sampleOutsideFluid"]
@@ -164,14 +170,13 @@ def simulate(mconf, batch_dict, net, sim_method, output_div=False, fused=True, w
         # gravityVec is only read when buoyancy is applied (simulate.py:99-105)
         gvec = _gravity(mconf, 1.0)[0] if want_gvec else [0.0, 0.0, 0.0]
         density = batch_dict["density"] if has_density else None
-        packed = net.packed_for(U.device) if (sim_method == "convnet") else None
+        packed = net.packed_for(U.device) if uses_net else None
         auto = None
         if workspace is None and static_flags is None and flags.is_cuda and geom is None:
             # the reference's four-argument call: the layer's own workspace, static inputs detected (module docstring)
             auto = _auto_step(flags, is3D)
             if auto is not None:
-                workspace, static_flags = auto.workspace, auto.static_bits(batch_dict, flags, is3D, sim_method == "jacobi",
-                                                                           sim_method == "pcg")
+                workspace, static_flags = auto.workspace, auto.static_bits(batch_dict, flags, is3D, sim_method == "jacobi", uses_pcg)
         if static_flags is None:
             static_flags = 0
         ext.simulate_step_(p, U, flags, density, batch_dict.get("UBC"), batch_dict.get("UBCInvMask"),
@@ -180,13 +185,13 @@ def simulate(mconf, batch_dict, net, sim_method, output_div=False, fused=True, w
                            float(mconf.get("operatingDensity", 0.0)), float(mconf.get("pTol", 0.0)),
                            int(mconf.get("jacobiIter", 1)), sim_method,
                            float(mconf.get("normalizeInputThreshold", 1e-5)), workspace, int(static_flags), geom,
-                           getattr(net, "precision_mode", "fp32") if sim_method == "convnet" else "fp32",
+                           getattr(net, "precision_mode", "fp32") if uses_net else "fp32",
                            float(viscosity), float(gravityScale) if gravityScale > 0 else 0.0,
                            bool(mconf.get("correctScalar", False)) and has_density, periodic,
                            batch_dict.get("flags_stick") if sim_method == "convnet" else None,
                            pcg_tol=float(mconf.get("pcgTol", 1e-5)), pcg_iter=int(mconf.get("pcgIter", 50)),
-                           vorticity_confinement=float(vorticityAmp) if vorticityAmp > 0 else 0.0)
-        if auto is not None and sim_method == "pcg":
+                           vorticity_confinement=float(vorticityAmp) if vorticityAmp > 0 else 0.0, pcg_warm=pcg_warm)
+        if auto is not None and uses_pcg:
             auto.built_hierarchy(flags)
         if not has_density:
             batch_dict["density"] = torch.zeros_like(flags)     # simulate.py:82-83
@@ -248,9 +253,12 @@ def simulate(mconf, batch_dict, net, sim_method, output_div=False, fused=True, w
     else:
         div = fluid.velocityDivergence(U, flags, geom=geom)
         is3D = U.size(2) > 1
-        if sim_method == "pcg":
+        if uses_pcg:
+            p0 = p if pcg_warm else None
+            if sim_method == "hybrid":                           # the net's pressure of the U being projected; its velocity is not used
+                p0, _ = net(torch.cat((p, U, flags, density), 1))
             p, residual = fluid.solveLinearSystemPCG(flags=flags, div=div, is_3d=is3D, p_tol=mconf.get("pcgTol", 1e-5),
-                                                     max_iter=mconf.get("pcgIter", 50), geom=geom)
+                                                     max_iter=mconf.get("pcgIter", 50), geom=geom, p0=p0)
         else:
             p, residual = fluid.solveLinearSystemJacobi(flags=flags, div=div, is_3d=is3D, p_tol=mconf["pTol"],
                                                         max_iter=mconf["jacobiIter"], geom=geom)

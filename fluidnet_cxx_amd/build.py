@@ -22,7 +22,7 @@ HIP_UNITS = {
     "fnx_stencils.hip": ["-ffp-contract=off"],
     "fnx_advect.hip": ["-ffp-contract=off", "-Rpass-analysis=kernel-resource-usage"],
     "fnx_jacobi.hip": ["-ffp-contract=off"],
-    "fnx_pcg.hip": [],
+    "fnx_pcg.hip": ["-Rpass-analysis=kernel-resource-usage"],
     "fnx_step.hip": ["-ffp-contract=off"],
     "fnx_vorticity.hip": ["-ffp-contract=off", "-Rpass-analysis=kernel-resource-usage"],
     "fnx_scenes.hip": ["-ffp-contract=off", "-Rpass-analysis=kernel-resource-usage"],
@@ -46,6 +46,9 @@ SCRATCH_FREE = {
                         "advect3d_bwd_vel_tile_kernel"],
                        "fnx_advect_march.h: the 3D advection marches run at 2-3 waves per SIMD with every VGPR in use; a reload from "
                        "scratch is an s_waitcnt vmcnt(0) that also waits for the plane in flight and the stores"),
+    "fnx_pcg.hip": (["pcg_guess_kernel"],
+                    "a streaming kernel like pcg_dir_apply_kernel: a cell's stencil, seven loads and three fp64 partial sums; scratch there "
+                    "would mean the partial sums or the stencil were turned into arrays in memory"),
     "fnx_vorticity.hip": (["vorticity_confinement_kernel"],
                           "its z-march keeps three planes of c and n, two of the curl and three of F_z in registers between the barriers; "
                           "a spill puts a scratch round trip into every step of the march"),

@@ -173,12 +173,16 @@ std::vector<Tensor> solve_linear_system(Tensor flags, Tensor div, const bool is3
 
 // ---- the converged solve (fnx_pcg, ABI 20; no reference counterpart) -------------------------------------
 // returns (p, residual, iterations per sample); the count needs a host synchronisation, so it is only read where the solve synchronises
-// anyway (p_tol > 0 or verbose) and is None otherwise: with p_tol <= 0 the call only enqueues (capturable in a HIP graph)
+// anyway (p_tol > 0 or verbose) and is None otherwise: with p_tol <= 0 the call only enqueues (capturable in a HIP graph).
+// p0 (ABI 27, fnx_pcg_from): a starting guess; with it max_iter may be 0 (the line-searched guess is returned)
 std::tuple<Tensor, Tensor, std::optional<std::vector<int>>> solve_linear_system_pcg(Tensor flags, Tensor div, const bool is3D, const float p_tol,
-                                                                      const int max_iter, const bool verbose, const Geom* geom) {
+                                                                      const int max_iter, const bool verbose, const Geom* geom,
+                                                                      c10::optional<Tensor> p0) {
   FnxGrid g = grid_of(flags, is3D, geom);
   check_scalar(div, g, "div");
-  TORCH_CHECK(max_iter >= 1, "At least 1 iteration is needed (maxIter < 1)");
+  const bool from = p0.has_value() && p0->defined();
+  if (from) check_scalar(*p0, g, "p0");
+  TORCH_CHECK(from ? max_iter >= 0 : max_iter >= 1, from ? "max_iter must not be negative (maxIter < 0)" : "At least 1 iteration is needed (maxIter < 1)");
   c10::hip::HIPGuard guard(flags.get_device());
   Tensor p = at::empty_like(flags);
   Tensor residual = at::zeros({}, flags.options());
@@ -187,9 +191,14 @@ std::tuple<Tensor, Tensor, std::optional<std::vector<int>>> solve_linear_system_
   Tensor ws = at::empty({(int64_t)bytes}, flags.options().dtype(at::kByte));
   std::vector<int> iters(g.B, 0);
   const bool count = p_tol > 0.f || verbose;
-  check_status((verbose ? fnx_pcg_verbose : fnx_pcg)(&g, flags.data_ptr<float>(), div.data_ptr<float>(), p.data_ptr<float>(),
-                                                     residual.data_ptr<float>(), p_tol, max_iter, count ? iters.data() : nullptr,
-                                                     ws.data_ptr(), bytes, cur_stream(flags)));
+  if (from)
+    check_status((verbose ? fnx_pcg_from_verbose : fnx_pcg_from)(&g, flags.data_ptr<float>(), div.data_ptr<float>(), p0->data_ptr<float>(),
+                                                                 p.data_ptr<float>(), residual.data_ptr<float>(), p_tol, max_iter,
+                                                                 count ? iters.data() : nullptr, ws.data_ptr(), bytes, cur_stream(flags)));
+  else
+    check_status((verbose ? fnx_pcg_verbose : fnx_pcg)(&g, flags.data_ptr<float>(), div.data_ptr<float>(), p.data_ptr<float>(),
+                                                       residual.data_ptr<float>(), p_tol, max_iter, count ? iters.data() : nullptr,
+                                                       ws.data_ptr(), bytes, cur_stream(flags)));
   if (!count) return {p, residual, std::nullopt};
   return {p, residual, iters};
 }
@@ -748,19 +757,21 @@ void simulate_step_(Tensor p, Tensor U, Tensor flags, c10::optional<Tensor> dens
                     const std::string method, double normalize_threshold, c10::optional<Tensor> workspace,
                     int static_flags, const Geom* geom, const std::string& precision_mode, double viscosity,
                     double gravity_scale, bool correct_scalar, int periodic, c10::optional<Tensor> flags_stick, double pcg_tol,
-                    int pcg_iter, double vorticity_confinement) {
+                    int pcg_iter, double vorticity_confinement, bool pcg_warm) {
   check_field(U, "U");
   FnxGrid g = grid_of(flags, U.size(1) == 3, geom);
   check_vel(U, g, "U"); check_scalar(p, g, "p");
   TORCH_CHECK(viscosity >= 0, "Viscosity must be positive");
-  TORCH_CHECK(method == "jacobi" || method == "convnet" || method == "pcg", "Simulation method not supported. Choose convnet, jacobi or pcg.");
+  TORCH_CHECK(method == "jacobi" || method == "convnet" || method == "pcg" || method == "hybrid",
+              "Simulation method not supported. Choose convnet, jacobi, pcg or hybrid.");
   TORCH_CHECK(gravity_vec.size() == 3, "gravityVec needs x, y, z");
   FnxStepParams prm{};
   prm.dt = (float)dt; prm.maccormack_strength = (float)maccormack_strength; prm.sample_outside_fluid = sample_outside_fluid;
   prm.buoyancy_scale = (float)buoyancy_scale;
   for (int a = 0; a < 3; ++a) prm.gravity_vec[a] = (float)gravity_vec[a];
   prm.operating_density = (float)operating_density; prm.p_tol = (float)p_tol; prm.jacobi_iter = jacobi_iter;
-  prm.method = method == "convnet" ? 1 : (method == "pcg" ? 2 : 0); prm.normalize_threshold = (float)normalize_threshold;
+  // 'hybrid': the solve started from the net's pressure; 'pcg' with pcg_warm: from p as it stands (the previous step's)
+  prm.method = method == "convnet" ? 1 : (method == "hybrid" ? 3 : (method == "pcg" ? (pcg_warm ? 4 : 2) : 0)); prm.normalize_threshold = (float)normalize_threshold;
   prm.pcg_tol = (float)pcg_tol; prm.pcg_iter = pcg_iter;
   prm.precision_mode = precision_of(precision_mode);
   prm.viscosity = (float)viscosity; prm.gravity_scale = (float)gravity_scale; prm.correct_scalar = correct_scalar ? 1 : 0;
@@ -1091,8 +1102,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("solve_linear_system", &solve_linear_system, "Solve Linear System using Jacobi's method", py::arg("flags"),
         py::arg("div"), py::arg("is3D"), py::arg("p_tol"), py::arg("max_iter"), py::arg("verbose"), GEOM, NoGil());
   m.def("solve_linear_system_pcg", &solve_linear_system_pcg, "Converged pressure solve: multigrid-preconditioned CG (fnx_pcg); "
-        "returns (p, residual, iterations per sample or None when p_tol <= 0)", py::arg("flags"), py::arg("div"), py::arg("is3D"), py::arg("p_tol") = 1e-5,
-        py::arg("max_iter") = 50, py::arg("verbose") = false, GEOM, NoGil());
+        "returns (p, residual, iterations per sample or None when p_tol <= 0).  p0: a starting guess (fnx_pcg_from; max_iter may then be 0)",
+        py::arg("flags"), py::arg("div"), py::arg("is3D"), py::arg("p_tol") = 1e-5,
+        py::arg("max_iter") = 50, py::arg("verbose") = false, GEOM, py::arg("p0") = py::none(), NoGil());
   m.def("poisson_apply", &poisson_apply, "A p, the operator of the pressure solve (fnx_poisson_apply)", py::arg("flags"), py::arg("p"),
         py::arg("is3D"), GEOM, NoGil());
   m.def("pcg_precondition", &pcg_precondition, "z = M^-1 r, one V-cycle of the PCG preconditioner (fnx_pcg_precondition)", py::arg("flags"),
@@ -1133,7 +1145,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("normalize_threshold"), py::arg("workspace") = py::none(), py::arg("static_flags") = 0, GEOM,
         py::arg("precision_mode") = "fp32", py::arg("viscosity") = 0.0, py::arg("gravity_scale") = 0.0,
         py::arg("correct_scalar") = false, py::arg("periodic") = 0, py::arg("flags_stick") = py::none(), py::arg("pcg_tol") = 1e-5,
-        py::arg("pcg_iter") = 50, py::arg("vorticity_confinement") = 0.0, NoGil());
+        py::arg("pcg_iter") = 50, py::arg("vorticity_confinement") = 0.0, py::arg("pcg_warm") = false, NoGil());
   m.def("step_workspace_bytes", &step_workspace_bytes);
   m.def("jacobi_sweeps_", &jacobi_sweeps_, py::arg("flags"), py::arg("div"), py::arg("p"), py::arg("is3D"), py::arg("nsweeps"),
         py::arg("workspace") = py::none(), py::arg("reuse_mask") = false, GEOM, py::arg("from_zero") = false, NoGil());

@@ -547,19 +547,21 @@ int check_pcg_grid(const FnxGrid* g, const char* who) {
   return FNX_OK;
 }
 
-int pcg_entry(const FnxGrid* g, const float* flags, const float* div, float* p, float* residual, float p_tol, int max_iter,
-              int* iters_done, void* ws, size_t ws_bytes, void* stream, bool verbose) {
+// min_iter: the smallest max_iter the entry point takes (fnx_pcg 1, fnx_pcg_from 0)
+int pcg_entry(const FnxGrid* g, const float* flags, const float* div, const float* p0, float* p, float* residual, float p_tol, int max_iter,
+              int min_iter, int* iters_done, void* ws, size_t ws_bytes, void* stream, bool verbose) {
   if (int rc = check_pcg_grid(g, "pcg")) return rc;
   if (!flags || !div || !p) return fail(FNX_EINVAL, "pcg: NULL tensor");
   if (div == p) return fail(FNX_EINVAL, "pcg: p must not alias div");
-  if (max_iter < 1) return fail(FNX_EINVAL, "At least 1 iteration is needed (maxIter < 1)");
+  if (min_iter > 0 && max_iter < 1) return fail(FNX_EINVAL, "At least 1 iteration is needed (maxIter < 1)");
+  if (max_iter < 0) return fail(FNX_EINVAL, "pcg_from: max_iter must not be negative (maxIter < 0)");
   if (!ws || ws_bytes < ws_pcg(g)) return fail(FNX_EWORKSPACE, "pcg: workspace too small (%zu < %zu)", ws_bytes, ws_pcg(g));
   hipStream_t s = (hipStream_t)stream;
   const GridDims d = dims(g);
   char* kept = (char*)ws;
   fnx::launch_pcg_build(d, g->is3D, quirks(g), flags, kept, s);
   HIP_OK(hipGetLastError());
-  if (int rc = fnx::pcg_solve(d, g->is3D, kept, kept + ws_pcg_kept(g), div, p, residual, p_tol, max_iter, iters_done, verbose, s)) return rc;
+  if (int rc = fnx::pcg_solve(d, g->is3D, kept, kept + ws_pcg_kept(g), div, p0, p, residual, p_tol, max_iter, iters_done, verbose, s)) return rc;
   HIP_OK(hipGetLastError());
   return FNX_OK;
 }
@@ -567,12 +569,22 @@ int pcg_entry(const FnxGrid* g, const float* flags, const float* div, float* p, 
 
 int fnx_pcg(const FnxGrid* g, const float* flags, const float* div, float* p, float* residual, float p_tol, int max_iter,
             int* iters_done, void* ws, size_t ws_bytes, void* stream) {
-  return pcg_entry(g, flags, div, p, residual, p_tol, max_iter, iters_done, ws, ws_bytes, stream, false);
+  return pcg_entry(g, flags, div, nullptr, p, residual, p_tol, max_iter, 1, iters_done, ws, ws_bytes, stream, false);
 }
 
 int fnx_pcg_verbose(const FnxGrid* g, const float* flags, const float* div, float* p, float* residual, float p_tol, int max_iter,
                     int* iters_done, void* ws, size_t ws_bytes, void* stream) {
-  return pcg_entry(g, flags, div, p, residual, p_tol, max_iter, iters_done, ws, ws_bytes, stream, true);
+  return pcg_entry(g, flags, div, nullptr, p, residual, p_tol, max_iter, 1, iters_done, ws, ws_bytes, stream, true);
+}
+
+int fnx_pcg_from(const FnxGrid* g, const float* flags, const float* div, const float* p0, float* p, float* residual, float p_tol,
+                 int max_iter, int* iters_done, void* ws, size_t ws_bytes, void* stream) {
+  return pcg_entry(g, flags, div, p0, p, residual, p_tol, max_iter, 0, iters_done, ws, ws_bytes, stream, false);
+}
+
+int fnx_pcg_from_verbose(const FnxGrid* g, const float* flags, const float* div, const float* p0, float* p, float* residual, float p_tol,
+                         int max_iter, int* iters_done, void* ws, size_t ws_bytes, void* stream) {
+  return pcg_entry(g, flags, div, p0, p, residual, p_tol, max_iter, 0, iters_done, ws, ws_bytes, stream, true);
 }
 
 int fnx_poisson_apply(const FnxGrid* g, const float* flags, const float* p, float* Ap, void* stream) {
@@ -904,13 +916,16 @@ int fnx_simulate_step(const FnxGrid* g, const FnxStepParams* prm, const FnxState
                       void* stream) {
   if (int rc = check_grid(g)) return rc;
   if (!prm || !st || !st->p || !st->U || !st->flags) return fail(FNX_EINVAL, "simulate_step: NULL state");
-  if (prm->method < 0 || prm->method > 2) return fail(FNX_EINVAL, "Simulation method not supported. Choose convnet, jacobi or pcg.");
-  if (prm->method == 2 && prm->pcg_iter < 1) return fail(FNX_EINVAL, "At least 1 iteration of the solver is needed (pcg_iter < 1)");
-  if (prm->method == 2 && (g->k_begin != 0 || g->k_end != 0 || g->z_offset != 0 || g->D_global != 0))
+  if (prm->method < 0 || prm->method > 4) return fail(FNX_EINVAL, "Simulation method not supported. Choose convnet, jacobi, pcg or hybrid.");
+  const bool pcg = prm->method >= 2;                 // 2: cold, 3 ('hybrid'): from the net's pressure, 4: from st->p as it stands
+  if (pcg && prm->pcg_iter < 1) return fail(FNX_EINVAL, "At least 1 iteration of the solver is needed (pcg_iter < 1)");
+  if (pcg && (g->k_begin != 0 || g->k_end != 0 || g->z_offset != 0 || g->D_global != 0))
     return fail(FNX_EINVAL, "simulate_step: the PCG solve takes no compute window or z-slab view (single domain only)");
   if (prm->vorticity_confinement > 0.f && (g->k_begin != 0 || g->k_end != 0 || g->z_offset != 0 || g->D_global != 0))
     return fail(FNX_EINVAL, "simulate_step: vorticity confinement takes no compute window or z-slab view (single domain only)");
   if (prm->method == 1 && !st->net) return fail(FNX_EINVAL, "simulate_step: convnet method needs packed weights");
+  if (prm->method == 3 && !st->net) return fail(FNX_EINVAL, "simulate_step: hybrid method needs packed weights");
+  if (prm->method == 3 && fnx::net_mode(prm->precision_mode) < 0) return fail(FNX_EINVAL, "simulate_step: unknown precision_mode %d", prm->precision_mode);
   hipStream_t s = (hipStream_t)stream;
   const size_t n = ncell(g), nc = g->is3D ? 3 : 2;
   Carver c(ws, ws_bytes);
@@ -981,7 +996,15 @@ int fnx_simulate_step(const FnxGrid* g, const FnxStepParams* prm, const FnxState
       // the hierarchy of these flags (bit 3)
       if ((prm->static_flags & 9) != 9) fnx::launch_pcg_build(d, g->is3D, quirks(g), st->flags, kept_pcg, s);
       if (tail_bytes < fnx::pcg_scratch_bytes(d, g->is3D)) return fail(FNX_EWORKSPACE, "simulate_step: workspace too small for the PCG solve");
-      if (int rc = fnx::pcg_solve(d, g->is3D, kept_pcg, tail, div, st->p, nullptr, prm->pcg_tol, prm->pcg_iter, nullptr, false, s)) return rc;
+      if (prm->method == 3) {
+        // the guess: the net's un-normalised pressure of this U, written into st->p.  The net's scratch and the solve's share the
+        // tail: the net has finished (same stream) before the solve's first launch, and all the solve takes from it is st->p
+        if (tail_bytes < fnx::fluidnet_ws_bytes(d, g->is3D)) return fail(FNX_EWORKSPACE, "simulate_step: workspace too small for the CNN");
+        if (int rc = fnx::fluidnet_pressure(g, st->net, st->flags, prm->normalize_threshold, fnx::net_mode(prm->precision_mode), st->p, st->U,
+                                            tail, stream)) return rc;
+      }
+      const float* p0 = prm->method == 2 ? nullptr : st->p;
+      if (int rc = fnx::pcg_solve(d, g->is3D, kept_pcg, tail, div, p0, st->p, nullptr, prm->pcg_tol, prm->pcg_iter, nullptr, false, s)) return rc;
     }
     if (!periodic) return fnx_post_projection(g, st, stream);
     // simulate.py:157-164: the patches read the field as it was before setWallBcs; their source row / column (border cells,

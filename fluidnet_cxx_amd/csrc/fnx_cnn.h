@@ -128,6 +128,10 @@ namespace fnx {
 // precision_mode (FNX_PRECISION_*) as the CNN launchers dispatch on it: FNX_PRECISION_FP32_F4 names what FNX_PRECISION_FP32 runs and
 // becomes it; -1: no such mode.  The C ABI entry points map it once; everything below them takes the mapped value.
 int net_mode(int precision_mode);
+// the net's un-normalised pressure alone (model.py:125-175, :221-222) for the hybrid projection: p_out = scale * net(div(U) / scale, occupancy);
+// U is read only.  ws: fluidnet_ws_bytes.
+int fluidnet_pressure(const FnxGrid* g, const void* packed, const float* flags, float thr, int precision_mode, float* p_out, const float* U,
+                      void* ws, void* stream);
 // bcs != nullptr: the fused step's form -- the last setConstVals of the step (simulate.py:168) is part of the pass behind the
 // net (bcs supplies density, the BC arrays, bc_class and density_bc_applied; p_out must not be the workspace)
 int fluidnet_core(const FnxGrid* g, const void* packed, const float* flags, float thr, int precision_mode, float* p_out, float* U,

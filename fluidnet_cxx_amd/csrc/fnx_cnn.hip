@@ -1874,6 +1874,29 @@ int fluidnet_core(const FnxGrid* g, const void* packed, const float* flags, floa
   if (int rc = fnx_set_wall_bcs(g, U, flags, stream)) return rc;                 // model.py:226
   return fnx::launch_status(g->is3D);
 }
+
+// The hybrid projection's guess (fnx_simulate_step, method 3): the launches of the fused step in front of the net, the net straight
+// into p_out, and the multiply launch_unscale applies to p (nc = 0: no velocity is touched).  The same arithmetic per value as
+// fluidnet_core, so p_out holds the bits fnx_fluidnet_forward returns as p for this U.
+int fluidnet_pressure(const FnxGrid* g, const void* packed, const float* flags, float thr, int precision_mode, float* p_out, const float* U,
+                      void* ws, void* stream) {
+  const GridDims d = make_dims(g->B, g->D, g->H, g->W, g->z_offset, g->D_global);
+  hipStream_t s = (hipStream_t)stream;
+  const int nc = g->is3D ? 3 : 2;
+  const size_t full = (size_t)g->B * d.DHW;
+  char* w = (char*)ws;
+  auto take = [&](size_t bytes) { void* r = w; w += (bytes + 255) & ~(size_t)255; return r; };
+  take(full * 4);                                                                // (fluidnet_core's layout: its divergence buffer)
+  float* x = (float*)take(full * 2 * 4);
+  double* partial = (double*)take(scale_std_scratch_bytes(g->B));
+  float* scale = (float*)take(sizeof(float) * g->B);
+  void* msws = w;
+  launch_scale_std(d, nc, U, thr, partial, scale, s);                            // model.py:129-144
+  launch_pack_div(d, g->is3D, U, flags, scale, x, s);                            // model.py:125-126, :146-168
+  multiscale_forward(d, g->is3D, packed, x, p_out, precision_mode, msws, s);     // model.py:174-175
+  launch_unscale(d, 0, scale, p_out, nullptr, s);                                // model.py:221-222
+  return fnx::launch_status(g->is3D);
+}
 }  // namespace fnx
 
 // ---------------------------------------------------------------------------------------------------

@@ -139,8 +139,9 @@ size_t pcg_scratch_bytes(const GridDims& g, bool is3d);
 void launch_pcg_build(const GridDims& g, bool is3d, bool quirks, const float* flags, void* kept, hipStream_t s);
 void launch_poisson_apply(const GridDims& g, bool is3d, bool quirks, const float* flags, const float* x, float* y, hipStream_t s);
 void launch_pcg_precondition(const GridDims& g, bool is3d, const void* kept, void* scratch, const float* r, float* z, hipStream_t s);
-// returns FNX_OK or an FNX_E* code (set_error); synchronises only for tol > 0, iters_done != null or verbose
-int pcg_solve(const GridDims& g, bool is3d, const void* kept, void* scratch, const float* div, float* p, float* residual, float tol,
-              int max_iter, int* iters_done, bool verbose, hipStream_t s);
+// returns FNX_OK or an FNX_E* code (set_error); synchronises only for tol > 0, iters_done != null or verbose.  p0: a starting guess or
+// null (the cold solve, launch for launch); it may be p.  With p0, max_iter 0 returns the line-searched guess.
+int pcg_solve(const GridDims& g, bool is3d, const void* kept, void* scratch, const float* div, const float* p0, float* p, float* residual,
+              float tol, int max_iter, int* iters_done, bool verbose, hipStream_t s);
 
 }  // namespace fnx

@@ -17,6 +17,12 @@
 // sample run as ONE launch of one workgroup per sample (barriers between the phases) instead of ~6 launches per level.
 // CG: per sample, zero initial guess, alpha / beta / norms on the device, every dot product as fp64 partial sums per
 // workgroup added in a fixed order by one workgroup (no atomics): the same bits run to run.
+// Warm start (ABI 27: fnx_pcg_from, FnxStepParams.method 3 and 4): with a guess x0, d = x0 on the degrees of freedom and 0 elsewhere,
+// and the solve starts from x = a0 d, a0 = (d.b) / (d.A d) -- one steepest-descent step along d.  a0 = 0 is among the candidates, so
+// in the energy norm the start is never worse than x = 0 whatever the guess's magnitude; A d, d.b (b has mean zero there) and d.A d
+// do not see a constant added to d on a singular sample, so d needs no mean removal.  r0 = b - a0 (A d - mean(A d)) is the true fp32
+// residual, and CG goes on from it exactly as from r0 = b.  A sample whose d.A d is not > 0 or whose dot products are not finite (a
+// zero, NaN or Inf guess) is held out of that step and runs the cold solve bit for bit.  Without a guess nothing is added or changed.
 #include "fnx_device.h"
 #include "fnx_kernels.h"
 #include "../../include/fluidnet_hip.h"
@@ -61,7 +67,8 @@ struct PcgScalars {
 };
 struct PcgGlobal { float res; int all_done; };
 
-enum { FIN_INIT = 0, FIN_BNORM, FIN_RZ0, FIN_ALPHA, FIN_CHECK, FIN_BETA, FIN_XMEAN };
+enum { FIN_INIT = 0, FIN_BNORM, FIN_RZ0, FIN_ALPHA, FIN_CHECK, FIN_BETA, FIN_XMEAN, FIN_GUESS, FIN_START };
+constexpr int kHeld = 2;              // PcgScalars.done between FIN_GUESS and FIN_START: the guess was rejected, the line-search step skips the sample
 
 // ---- the operator ------------------------------------------------------------------------------------
 
@@ -409,6 +416,34 @@ __global__ __launch_bounds__(kRed) void pcg_dir_apply_kernel(LevelDev L, const f
   store_partials<2>(v, part, b, gridDim.x);
 }
 
+// the warm start's direction: d = x0 on the degrees of freedom, 0 elsewhere, and Ap = A d; sums d.b, d.Ap and Ap, b the projected
+// right-hand side pcg_rhs_kernel forms (div - mean).  Runs BEFORE pcg_rhs_kernel, which zeroes x: x0 may be x.
+__global__ __launch_bounds__(kRed) void pcg_guess_kernel(LevelDev L, const float* __restrict__ x0, const float* __restrict__ div,
+                                                         float* __restrict__ d, float* __restrict__ Ap, const PcgScalars* sc, double* part) {
+  const int b = blockIdx.y;
+  const size_t base = (size_t)b * L.N;
+  const double mean = sc[b].mean;
+  const float* xs = x0 + base;
+  const int W = L.W, HW = L.H * L.W;
+  double v[3] = {0.0, 0.0, 0.0};
+  PCG_CELL_LOOP(c, L.N) {
+    const St s = code_stencil(L.code[base + c], L.denom);
+    if (!s.dof) { d[base + c] = 0.f; Ap[base + c] = 0.f; continue; }
+    const float dc = xs[c];
+    float y = s.d * dc;                               // (a weight is only non-zero towards a degree of freedom)
+    if (s.xm != 0.f) y -= xs[c - 1];
+    if (s.xp != 0.f) y -= xs[c + 1];
+    if (s.ym != 0.f) y -= xs[c - W];
+    if (s.yp != 0.f) y -= xs[c + W];
+    if (s.zm != 0.f) y -= xs[c - HW];
+    if (s.zp != 0.f) y -= xs[c + HW];
+    d[base + c] = dc; Ap[base + c] = y;
+    const float bv = (float)((double)div[base + c] - mean);
+    v[0] += (double)dc * bv; v[1] += (double)dc * y; v[2] += (double)y;
+  }
+  store_partials<3>(v, part, b, gridDim.x);
+}
+
 // x += alpha p, r -= alpha (Ap - mean(Ap)); sum r^2
 __global__ __launch_bounds__(kRed) void pcg_update_kernel(LevelDev L, const float* __restrict__ p, const float* __restrict__ Ap,
                                                           float* __restrict__ x, float* __restrict__ r, const PcgScalars* sc, double* part) {
@@ -516,6 +551,50 @@ __global__ __launch_bounds__(kRed) void pcg_finalize_kernel(int mode, int B, int
     __syncthreads();
   }
   if (threadIdx.x == 0 && mode != FIN_INIT && mode != FIN_XMEAN) {
+    int all = 1; float mx = 0.f;
+    for (int b = 0; b < B; ++b) {
+      all &= sc[b].done;
+      const float r = sc[b].relres;
+      if (!(r <= mx)) mx = r;                                 // NaN propagates
+    }
+    gl->all_done = all; gl->res = mx;
+    if (residual) *residual = mx;
+  }
+}
+
+// the scalar part of the warm start (pcg_finalize_kernel is the cold solve's and stays as it is).  FIN_GUESS, behind FIN_INIT: alpha =
+// a0 = d.b / d.Ad and mAp, or the guess is rejected.  FIN_START, behind the line-search step's pcg_update_kernel: FIN_CHECK without the
+// iteration count; like FIN_CHECK it publishes the batch's stop flag and residual.
+__global__ __launch_bounds__(kRed) void pcg_finalize_guess_kernel(int mode, int B, int nblk, const double* part, PcgScalars* sc, PcgGlobal* gl,
+                                                                  float tol, float* residual) {
+  __shared__ double sh[kRed];
+  __shared__ double q[kNQ];
+  const int nq = mode == FIN_GUESS ? 3 : 1;
+  for (int b = 0; b < B; ++b) {
+    for (int k = 0; k < nq; ++k) {
+      const double s = sum_partials(part + ((size_t)b * kNQ + k) * nblk, nblk, sh);
+      if (threadIdx.x == 0) q[k] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      PcgScalars& S = sc[b];
+      if (mode == FIN_GUESS) {
+        const float a0 = (float)(q[0] / q[1]);
+        const float m = S.singular ? (float)(q[2] / S.n) : 0.f;
+        if (!(q[1] > 0.0) || !isfinite(q[0]) || !isfinite(q[1]) || !isfinite(a0) || !isfinite(m)) S.done = kHeld;
+        else { S.alpha = a0; S.mAp = m; }
+      } else if (S.done == kHeld) {
+        S.done = 0;                                           // rejected: x = 0, r = b, relres 1 as FIN_BNORM left them
+      } else if (!S.done) {
+        S.relres = (float)(sqrt(q[0]) / S.bnorm);
+        if (tol > 0.f && S.relres <= tol) { S.done = 1; S.converged = 1; }
+        else if (!isfinite(S.relres)) S.done = 1;
+        if (S.relres < S.best) S.best = S.relres;
+      }
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0 && mode == FIN_START) {
     int all = 1; float mx = 0.f;
     for (int b = 0; b < B; ++b) {
       all &= sc[b].done;
@@ -662,8 +741,8 @@ void launch_pcg_precondition(const GridDims& g, bool is3d, const void* kept, voi
   vcycle(level_set(h, is3d, k, sc, r, z), h.ls, is3d, g.B, nullptr, s);
 }
 
-int pcg_solve(const GridDims& g, bool is3d, const void* kept, void* scratch, const float* div, float* p, float* residual, float tol,
-              int max_iter, int* iters_done, bool verbose, hipStream_t st) {
+int pcg_solve(const GridDims& g, bool is3d, const void* kept, void* scratch, const float* div, const float* p0, float* p, float* residual,
+              float tol, int max_iter, int* iters_done, bool verbose, hipStream_t st) {
   const Hier h = make_hier(g, is3d);
   const int B = g.B, N = h.N[0], nblk = nblk_of(N);
   size_t nb;
@@ -673,19 +752,46 @@ int pcg_solve(const GridDims& g, bool is3d, const void* kept, void* scratch, con
   const LevelDev& L0 = S.lv[0];
   const dim3 rg(nblk, B);
   auto fin = [&](int mode) { pcg_finalize_kernel<<<1, kRed, 0, st>>>(mode, B, nblk, s.part, s.sc, s.gl, tol, residual); };
+  auto fin_guess = [&](int mode) { pcg_finalize_guess_kernel<<<1, kRed, 0, st>>>(mode, B, nblk, s.part, s.sc, s.gl, tol, residual); };
   // b = div projected onto the range of A where constants are null vectors; x (= p) = 0
   pcg_init_kernel<<<rg, kRed, 0, st>>>(L0, div, s.part);
   fin(FIN_INIT);
+  // the guess is read before anything writes p (p0 may be p): d -> pA (free until the first direction lands in pB), A d -> Ap
+  if (p0) {
+    pcg_guess_kernel<<<rg, kRed, 0, st>>>(L0, p0, div, s.pA, s.Ap, s.sc, s.part);
+    fin_guess(FIN_GUESS);
+  }
   pcg_rhs_kernel<<<rg, kRed, 0, st>>>(L0, div, s.sc, s.r, p, s.part);
   fin(FIN_BNORM);
   float* P[2] = {s.pA, s.pB};
   int it = 0;
   PcgGlobal hg{0.f, 0};
-  // z = M^-1 r; the first direction is z
-  vcycle(S, h.ls, is3d, B, s.sc, st);
-  pcg_rz_kernel<<<rg, kRed, 0, st>>>(L0, s.r, s.z, s.sc, s.part);
-  fin(FIN_RZ0);
-  while (it < max_iter) {
+  bool run = max_iter > 0;
+  if (p0) {
+    // x = a0 d, r = b - a0 (A d - mean(A d)): the update of a CG step, skipped by the samples FIN_GUESS holds
+    pcg_update_kernel<<<rg, kRed, 0, st>>>(L0, s.pA, s.Ap, p, s.r, s.sc, s.part);
+    fin_guess(FIN_START);
+    PCG_HIP(hipGetLastError());
+    if (verbose || tol > 0.f) {
+      std::vector<PcgScalars> hs(B);
+      PCG_HIP(hipMemcpyAsync(hs.data(), s.sc, (size_t)B * sizeof(PcgScalars), hipMemcpyDeviceToHost, st));
+      PCG_HIP(hipMemcpyAsync(&hg, s.gl, sizeof(hg), hipMemcpyDeviceToHost, st));
+      PCG_HIP(hipStreamSynchronize(st));
+      if (verbose) {
+        printf("PCG warm start: a0");
+        for (int b = 0; b < B; ++b) printf(" %g", (double)hs[b].alpha);
+        printf(", residual %g\n", (double)hg.res);
+      }
+      if (hg.all_done) run = false;             // every sample starts within p_tol (or with b = 0)
+    }
+  }
+  if (run) {
+    // z = M^-1 r; the first direction is z
+    vcycle(S, h.ls, is3d, B, s.sc, st);
+    pcg_rz_kernel<<<rg, kRed, 0, st>>>(L0, s.r, s.z, s.sc, s.part);
+    fin(FIN_RZ0);
+  }
+  while (run && it < max_iter) {
     pcg_dir_apply_kernel<<<rg, kRed, 0, st>>>(L0, s.z, P[it & 1], P[(it + 1) & 1], s.Ap, s.sc, it == 0 ? 1 : 0, s.part);
     fin(FIN_ALPHA);
     pcg_update_kernel<<<rg, kRed, 0, st>>>(L0, P[(it + 1) & 1], s.Ap, p, s.r, s.sc, s.part);

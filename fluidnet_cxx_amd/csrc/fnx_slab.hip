@@ -787,8 +787,8 @@ int fnx_slab_step(FnxSlab* s, const FnxStepParams* prm, const FnxState* st, void
 static int slab_step_body(FnxSlab* s, const FnxStepParams* prm, const FnxState* st, void* ws, size_t ws_bytes, void* vstream) {
   if (!s || !prm || !st) return fnx::set_error(FNX_EINVAL, "slab_step: NULL argument");
   if (!st->p || !st->U || !st->flags || !st->density) return fnx::set_error(FNX_EINVAL, "slab_step: the z-slab driver needs p, U, flags and a density field");
-  if (prm->method == 2)
-    return fnx::set_error(FNX_EINVAL, "slab_step: method 2 (PCG) is single-domain only (its dot products would need an all-reduce per iteration)");
+  if (prm->method >= 2 && prm->method <= 4)
+    return fnx::set_error(FNX_EINVAL, "slab_step: method %d (PCG) is single-domain only (its dot products would need an all-reduce per iteration)", prm->method);
   if (prm->method != 0 && prm->method != 1) return fnx::set_error(FNX_EINVAL, "slab_step: unknown method %d", prm->method);
   if (prm->method == 1 && (s->cfg.method != 1 || !st->net))
     return fnx::set_error(FNX_EINVAL, "slab_step: the CNN projection needs a driver created with cfg.method = 1 and st->net (the packed weights)");

@@ -92,14 +92,20 @@ def solveLinearSystemJacobi(flags, div, is_3d=False, p_tol=1e-5, max_iter=1000, 
     return p, res
 
 
-def solveLinearSystemPCG(flags, div, is_3d=False, p_tol=1e-5, max_iter=50, verbose=False, *, geom=None):
+def solveLinearSystemPCG(flags, div, is_3d=False, p_tol=1e-5, max_iter=50, verbose=False, *, geom=None, p0=None):
     """The converged pressure solve (no reference counterpart): the pressure the Jacobi solve tends to with infinitely many sweeps, by
     multigrid-preconditioned conjugate gradients (fnx_pcg).  Stops per sample at ||div - A p|| <= p_tol ||div|| (div projected onto
     mean zero over the fluid cells of a closed domain, p then has mean zero there); p_tol <= 0 runs exactly max_iter iterations.
+    `p0`: a starting guess of div's shape (fnx_pcg_from) -- a net's pressure, the previous step's.  The solve starts from a0 p0 with
+    the line-search scale a0 = (p0 . div) / (p0 . A p0), so the guess's magnitude and (on a closed domain) its mean do not matter and
+    the start is never worse than the cold one; a sample whose guess is zero or not finite runs the cold solve bit for bit.  With a
+    guess max_iter may be 0: the scaled guess is returned.
     Returns (p, residual) like solveLinearSystemJacobi, residual the largest relative residual of the batch (0-dim tensor)."""
     _check5(div, flags)
     assert flags.size(1) == 1, "flags is not scalar"
-    p, res, _ = ext.solve_linear_system_pcg(flags, div, bool(is_3d), float(p_tol), int(max_iter), bool(verbose), geom)
+    if p0 is not None:
+        _check5(p0, flags)
+    p, res, _ = ext.solve_linear_system_pcg(flags, div, bool(is_3d), float(p_tol), int(max_iter), bool(verbose), geom, p0)
     return p, res
 
 

@@ -424,6 +424,31 @@ def jacobi_sweeps_to_reach(batches, divL2, limit=4096):
     return None
 
 
+def _hybrid_iterations(dim, net, batches, tol, max_iter):
+    cold, warm = [], []
+    with torch.no_grad():
+        for data, _ in batches:
+            flags, U = data[:, dim.iflags].contiguous(), data[:, dim.iU].contiguous()
+            is3d = dim.nU == 3
+            div = fluid.velocityDivergence(U, flags)
+            p0, _ = net(data)
+            cold += ext.solve_linear_system_pcg(flags, div, is3d, float(tol), int(max_iter), False, None)[2]
+            warm += ext.solve_linear_system_pcg(flags, div, is3d, float(tol), int(max_iter), False, None, p0.contiguous())[2]
+    return cold, warm
+
+
+def hybrid_iterations(net, batches, tol=1e-5, max_iter=100):
+    """what a trained net is worth to simulate(..., 'hybrid'): for each held-out batch [(data, target)] the CG iterations of
+    solveLinearSystemPCG on div(U) to `tol` (> 0) from zero and from the net's pressure.  Returns (cold, warm), two lists with one count per sample in
+    batch order.  2D and 3D batches alike (by the number of channels of `data`)."""
+    assert tol > 0, "the iteration counts are those of a solve that stops at a tolerance"
+    batches = list(batches)
+    dim = _DIM
+    if batches and batches[0][0].size(1) == 6:
+        from .training3d import _DIM3 as dim
+    return _hybrid_iterations(dim, net, batches, tol, max_iter)
+
+
 def train(mconf=None, tconf=None, device="cuda", out=None, resume=None, log=None):
     """One training run.  mconf: the reference's modelParam keys (MCONF_DEFAULTS); tconf: TCONF_DEFAULTS (res or (H, W) via 'H', 'W';
     batch; iters; seed; sceneLength; stride; evalEvery; evalBatches; saveEvery).  `resume`: a checkpoint (path or dict) of a run with the

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define FNX_ABI_VERSION 26
+#define FNX_ABI_VERSION 27
 
 enum {
   FNX_OK = 0,
@@ -207,6 +207,22 @@ int fnx_pcg(const FnxGrid* g, const float* flags, const float* div, float* p, fl
  * synchronisation per iteration. */
 int fnx_pcg_verbose(const FnxGrid* g, const float* flags, const float* div, float* p, float* residual, float p_tol, int max_iter,
                     int* iters_done, void* ws, size_t ws_bytes, void* stream);
+/* ABI 27: the same solve from a starting guess p0 (DEVICE, the shape of p; it may BE p: it is read before p is written).
+ * p0 == NULL is fnx_pcg.  Let d = p0 on the active cells and 0 elsewhere.  The solve starts from x = a0 d with the line-search scale
+ *   a0 = (d . b) / (d . A d),
+ * b the projected div: one steepest-descent step along d.  a0 = 0 is among the candidates, so in the energy norm the start is never
+ * worse than the cold one, and a guess of the wrong magnitude (an un-normalised or under-trained net) is repaired for free.  A d,
+ * d . b and d . A d do not change when a constant is added to d on a singular sample, so d needs no mean removal (p is returned
+ * with active-cell mean zero as above).  The stopping test is unchanged, ||r|| <= p_tol ||b||, with r0 = b - a0 A d the true fp32
+ * residual; a sample that meets it at the start reports 0 iterations.  Per sample the guess is REJECTED when d . A d is not > 0 or
+ * a dot product is not finite (a zero, NaN or Inf guess): that sample runs the cold solve bit for bit, no value of the guess reaches
+ * p.  max_iter >= 0 here: 0 returns the scaled guess (zeros where it was rejected).  With p_tol > 0 the start costs one more host
+ * read of the stop flag.  Same workspace, same determinism, no compute window, no z-slab view. */
+int fnx_pcg_from(const FnxGrid* g, const float* flags, const float* div, const float* p0, float* p, float* residual, float p_tol,
+                 int max_iter, int* iters_done, void* ws, size_t ws_bytes, void* stream);
+/* The same with fnx_pcg_verbose's lines, preceded (with a guess) by one line "PCG warm start: a0 <per sample> , residual R". */
+int fnx_pcg_from_verbose(const FnxGrid* g, const float* flags, const float* div, const float* p0, float* p, float* residual, float p_tol,
+                         int max_iter, int* iters_done, void* ws, size_t ws_bytes, void* stream);
 /* Ap = A p (the operator above; p is read on active cells only, Ap is 0 elsewhere).  No workspace. */
 int fnx_poisson_apply(const FnxGrid* g, const float* flags, const float* p, float* Ap, void* stream);
 /* z = M^-1 r, one V-cycle of the preconditioner (a fixed symmetric linear map; r is read on active cells only, z is 0 elsewhere).
@@ -321,7 +337,15 @@ typedef struct FnxStepParams {
   float p_tol;                /* mconf['pTol'] */
   int   jacobi_iter;          /* mconf['jacobiIter'] */
   int   method;               /* 0 = 'jacobi', 1 = 'convnet', 2 = 'pcg' (ABI 20: fnx_pcg with pcg_tol / pcg_iter below; the wall BCs
-                                 and periodic patches as for method 0) */
+                                 and periodic patches as for method 0).
+                                 ABI 27: 3 = 'hybrid': the stages of method 2, but the solve is fnx_pcg_from started from the net's
+                                 pressure of the staged U (st->net, precision_mode and normalize_threshold as for method 1: the
+                                 un-normalised p that fnx_fluidnet_forward returns, written into st->p; the net updates no
+                                 velocity; flags_stick is ignored as by methods 0 and 2); 4 = 'pcg' started from st->p as it
+                                 stands on entry (the previous step's pressure; p = 0 gives the cold solve).  static_flags bits 0
+                                 and 3 mean for 3 and 4 what they mean for 2.  The net's scratch and the solve's vectors overlap
+                                 in the workspace tail -- the net has finished before the solve starts and the solve takes only
+                                 st->p from it -- so fnx_workspace_bytes(FNX_OP_STEP) is what it was before ABI 27 */
   float normalize_threshold;  /* mconf['normalizeInputThreshold'] (convnet) */
   int   precision_mode;       /* convnet: FNX_PRECISION_FP32 (0, the default), _FP32_DIRECT, _BF16X6 or _BF16X3, see fnx_multiscale_forward */
   int   static_flags;         /* promises about the previous fnx_simulate_step on this workspace (no reference key; every
@@ -348,7 +372,7 @@ typedef struct FnxStepParams {
                                  only (simulate.py:121-128, :157-164): U[:,1,:,:,1] = U_temp[:,1,:,:,W-1],
                                  U[:,0,:,1] = U_temp[:,0,:,H-1] after each setWallBcs, U_temp the field before it */
   /* ABI 20, method 2 (mconf['pcgTol'], mconf['pcgIter']): */
-  float pcg_tol;              /* relative residual ||b - A p|| / ||b|| to stop at; <= 0 runs exactly pcg_iter iterations, no host sync */
+  float pcg_tol;              /* (methods 2, 3, 4) relative residual ||b - A p|| / ||b|| to stop at; <= 0 runs exactly pcg_iter iterations, no host sync */
   int   pcg_iter;             /* at most that many CG iterations (>= 1) */
   /* ABI 22 (mconf['vorticityConfinementAmp']; off when <= 0; single domain only, fnx_slab_step refuses it): */
   float vorticity_confinement; /* fnx_add_vorticity_confinement with this amplitude after addGravity and before setWallBcs, for
@@ -362,7 +386,7 @@ typedef struct FnxState {
   const float* flags;
   const float* UBC; const float* UBCInvMask;                 /* may be NULL */
   const float* densityBC; const float* densityBCInvMask;     /* may be NULL */
-  const void*  net;  /* packed ScaleNet weights from fnx_scalenet_pack (method 1), else NULL */
+  const void*  net;  /* packed ScaleNet weights from fnx_scalenet_pack (methods 1 and 3), else NULL */
   /* Optional (B,1,D,H,W) bytes from fnx_bc_classify, or NULL: bit 0 = setConstVals is x*1+0 for every velocity component
    * of the cell, bit 1 = the same for the density.  The BC stages then skip the 8 BC loads of such a cell (32 of its 64-68
    * bytes) and apply t = x*1, t + 0 directly: same bits.  Only valid while the four BC arrays do not change. */
@@ -558,7 +582,8 @@ void fnx_slab_destroy(FnxSlab* s);
  * bits on every rank; one host synchronisation), FNX_SLAB_NET_MARGIN + 1 ghost planes of U exchanged once, the net evaluated on
  * owned +- FNX_SLAB_NET_MARGIN planes, velocityUpdate / un-normalise / setWallBcs / setConstVals on the owned planes: p and U
  * within the CNN tolerance (1e-5 |ref|max) of the single-domain step, density bit for bit.
- * prm->method 2 (PCG) is refused with FNX_EINVAL: its dot products would need an all-reduce per iteration (single domain only).
+ * prm->method 2, 3, 4 (PCG, cold or warm-started) are refused with FNX_EINVAL: its dot products would need an all-reduce per iteration
+ * (single domain only).
  * Jacobi:  prm->p_tol > 0 runs the reference's convergence test (fluids_init.cpp:961-979): one sweep per ghost exchange,
  * the squared differences over the owned planes all-reduced over the ranks, one host sync per sweep (as in fnx_jacobi);
  * every rank's part reproducible (fnx_residual).  The bit-for-bit statement above holds for p_tol == 0; with p_tol > 0 every
