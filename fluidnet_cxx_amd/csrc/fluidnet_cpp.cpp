@@ -748,6 +748,34 @@ std::vector<Tensor> train_loss(bool is3d, Tensor out_p, Tensor out_U, Tensor fla
   return {t, gp, gU};
 }
 
+// an optional field of a step's state: its device pointer, or nullptr for None
+static float* opt_field(const FnxGrid& g, c10::optional<Tensor>& t, bool vel, const char* name) {
+  if (!t.has_value() || !t->defined()) return nullptr;
+  if (vel) check_vel(*t, g, name); else check_scalar(*t, g, name);
+  return t->data_ptr<float>();
+}
+
+// the fields every state has; the net, the class map and flags_stick are the caller's to add
+static FnxState make_state(const FnxGrid& g, Tensor& p, Tensor& U, Tensor& flags, c10::optional<Tensor>& density,
+                           c10::optional<Tensor>& UBC, c10::optional<Tensor>& UBCInvMask,
+                           c10::optional<Tensor>& densityBC, c10::optional<Tensor>& densityBCInvMask) {
+  FnxState st{};
+  st.p = p.data_ptr<float>(); st.U = U.data_ptr<float>(); st.flags = flags.data_ptr<float>();
+  st.density = opt_field(g, density, false, "density");
+  st.UBC = opt_field(g, UBC, true, "UBC"); st.UBCInvMask = opt_field(g, UBCInvMask, true, "UBCInvMask");
+  st.densityBC = opt_field(g, densityBC, false, "densityBC"); st.densityBCInvMask = opt_field(g, densityBCInvMask, false, "densityBCInvMask");
+  return st;
+}
+
+// the parameters every caller of a step or of its stage sets (gravity_vec: x, y, z, checked by the caller); the rest start at zero
+static FnxStepParams step_params(double dt, double buoyancy_scale, const std::vector<double>& gravity_vec, double operating_density) {
+  FnxStepParams prm{};
+  prm.dt = (float)dt; prm.buoyancy_scale = (float)buoyancy_scale;
+  for (int a = 0; a < 3; ++a) prm.gravity_vec[a] = (float)gravity_vec[a];
+  prm.operating_density = (float)operating_density;
+  return prm;
+}
+
 // one whole step of lib/simulate.py:28-171, in place on p, U, density
 void simulate_step_(Tensor p, Tensor U, Tensor flags, c10::optional<Tensor> density, c10::optional<Tensor> UBC,
                     c10::optional<Tensor> UBCInvMask, c10::optional<Tensor> densityBC,
@@ -765,11 +793,9 @@ void simulate_step_(Tensor p, Tensor U, Tensor flags, c10::optional<Tensor> dens
   TORCH_CHECK(method == "jacobi" || method == "convnet" || method == "pcg" || method == "hybrid",
               "Simulation method not supported. Choose convnet, jacobi, pcg or hybrid.");
   TORCH_CHECK(gravity_vec.size() == 3, "gravityVec needs x, y, z");
-  FnxStepParams prm{};
-  prm.dt = (float)dt; prm.maccormack_strength = (float)maccormack_strength; prm.sample_outside_fluid = sample_outside_fluid;
-  prm.buoyancy_scale = (float)buoyancy_scale;
-  for (int a = 0; a < 3; ++a) prm.gravity_vec[a] = (float)gravity_vec[a];
-  prm.operating_density = (float)operating_density; prm.p_tol = (float)p_tol; prm.jacobi_iter = jacobi_iter;
+  FnxStepParams prm = step_params(dt, buoyancy_scale, gravity_vec, operating_density);
+  prm.maccormack_strength = (float)maccormack_strength; prm.sample_outside_fluid = sample_outside_fluid;
+  prm.p_tol = (float)p_tol; prm.jacobi_iter = jacobi_iter;
   // 'hybrid': the solve started from the net's pressure; 'pcg' with pcg_warm: from p as it stands (the previous step's)
   prm.method = method == "convnet" ? 1 : (method == "hybrid" ? 3 : (method == "pcg" ? (pcg_warm ? 4 : 2) : 0)); prm.normalize_threshold = (float)normalize_threshold;
   prm.pcg_tol = (float)pcg_tol; prm.pcg_iter = pcg_iter;
@@ -777,18 +803,9 @@ void simulate_step_(Tensor p, Tensor U, Tensor flags, c10::optional<Tensor> dens
   prm.viscosity = (float)viscosity; prm.gravity_scale = (float)gravity_scale; prm.correct_scalar = correct_scalar ? 1 : 0;
   prm.periodic = periodic;
   prm.vorticity_confinement = (float)vorticity_confinement;
-  auto opt = [&](c10::optional<Tensor>& t, bool vel, const char* name) -> float* {
-    if (!t.has_value() || !t->defined()) return nullptr;
-    if (vel) check_vel(*t, g, name); else check_scalar(*t, g, name);
-    return t->data_ptr<float>();
-  };
-  FnxState st{};
-  st.p = p.data_ptr<float>(); st.U = U.data_ptr<float>(); st.flags = flags.data_ptr<float>();
-  st.density = opt(density, false, "density");
-  st.UBC = opt(UBC, true, "UBC"); st.UBCInvMask = opt(UBCInvMask, true, "UBCInvMask");
-  st.densityBC = opt(densityBC, false, "densityBC"); st.densityBCInvMask = opt(densityBCInvMask, false, "densityBCInvMask");
+  FnxState st = make_state(g, p, U, flags, density, UBC, UBCInvMask, densityBC, densityBCInvMask);
   st.net = (net.has_value() && net->defined()) ? net->data_ptr() : nullptr;
-  st.flags_stick = opt(flags_stick, false, "flags_stick");
+  st.flags_stick = opt_field(g, flags_stick, false, "flags_stick");
   c10::hip::HIPGuard guard(flags.get_device());
   const size_t bytes = fnx_workspace_bytes(&g, FNX_OP_STEP);
   Tensor ws;
@@ -888,11 +905,9 @@ struct PySlab {
                 cfg.B, " x ", l[0] + l[1] + l[2], " x ", cfg.H, " x ", cfg.W, " with ghost planes)");
     TORCH_CHECK(gravity_vec.size() == 3, "gravityVec needs x, y, z");
     TORCH_CHECK(workspace.is_cuda() && workspace.is_contiguous(), "workspace must be a contiguous GPU tensor");
-    FnxStepParams prm{};
-    prm.dt = (float)dt; prm.maccormack_strength = (float)maccormack_strength; prm.sample_outside_fluid = sample_outside_fluid;
-    prm.buoyancy_scale = (float)buoyancy_scale;
-    for (int a = 0; a < 3; ++a) prm.gravity_vec[a] = (float)gravity_vec[a];
-    prm.operating_density = (float)operating_density; prm.p_tol = (float)p_tol; prm.jacobi_iter = jacobi_iter; prm.method = 0;
+    FnxStepParams prm = step_params(dt, buoyancy_scale, gravity_vec, operating_density);
+    prm.maccormack_strength = (float)maccormack_strength; prm.sample_outside_fluid = sample_outside_fluid;
+    prm.p_tol = (float)p_tol; prm.jacobi_iter = jacobi_iter; prm.method = 0;
     const bool cnn = net.has_value() && net->defined();
     if (cnn) {                                       // the CNN projection (a driver created with method = "convnet")
       TORCH_CHECK(net->is_cuda() && net->is_contiguous(), "net: the packed weights (scalenet_pack) on the GPU");
@@ -900,15 +915,8 @@ struct PySlab {
     }
     TORCH_CHECK(method == "auto" || method == "jacobi" || method == "convnet" || method == "pcg", "unknown z-slab step method '", method, "'");
     if (method == "pcg") prm.method = 2;           // refused by fnx_slab_step (single-domain only)
-    auto opt = [&](c10::optional<Tensor>& t, bool vel, const char* name) -> float* {
-      if (!t.has_value() || !t->defined()) return nullptr;
-      if (vel) check_vel(*t, g, name); else check_scalar(*t, g, name);
-      return t->data_ptr<float>();
-    };
-    FnxState st{};
-    st.p = p.data_ptr<float>(); st.U = U.data_ptr<float>(); st.flags = flags.data_ptr<float>(); st.density = density.data_ptr<float>();
-    st.UBC = opt(UBC, true, "UBC"); st.UBCInvMask = opt(UBCInvMask, true, "UBCInvMask");
-    st.densityBC = opt(densityBC, false, "densityBC"); st.densityBCInvMask = opt(densityBCInvMask, false, "densityBCInvMask");
+    c10::optional<Tensor> rho(density);
+    FnxState st = make_state(g, p, U, flags, rho, UBC, UBCInvMask, densityBC, densityBCInvMask);
     if (cnn) st.net = net->data_ptr();
     c10::hip::HIPGuard guard(flags.get_device());
     check_status(fnx_slab_step(s, &prm, &st, workspace.data_ptr(), (size_t)workspace.numel() * workspace.element_size(), cur_stream(U)));
@@ -975,24 +983,6 @@ int64_t jacobi_workspace_bytes(int B, int D, int H, int W, bool is3D) {
   return (int64_t)fnx_workspace_bytes(&g, FNX_OP_JACOBI);
 }
 
-static FnxState make_state(const FnxGrid& g, Tensor& p, Tensor& U, Tensor& flags, c10::optional<Tensor>& density,
-                           c10::optional<Tensor>& UBC, c10::optional<Tensor>& UBCInvMask,
-                           c10::optional<Tensor>& densityBC, c10::optional<Tensor>& densityBCInvMask) {
-  auto opt = [&](c10::optional<Tensor>& t, bool vel, const char* name) -> float* {
-    if (!t.has_value() || !t->defined()) return nullptr;
-    if (vel) check_vel(*t, g, name); else check_scalar(*t, g, name);
-    return t->data_ptr<float>();
-  };
-  FnxState st{};
-  st.p = p.data_ptr<float>(); st.U = U.data_ptr<float>(); st.flags = flags.data_ptr<float>();
-  st.density = opt(density, false, "density");
-  st.UBC = opt(UBC, true, "UBC"); st.UBCInvMask = opt(UBCInvMask, true, "UBCInvMask");
-  st.densityBC = opt(densityBC, false, "densityBC"); st.densityBCInvMask = opt(densityBCInvMask, false, "densityBCInvMask");
-  st.net = nullptr;
-  st.bc_class = nullptr;
-  return st;
-}
-
 static const unsigned char* bc_class_ptr(c10::optional<Tensor>& t, const Tensor& flags) {
   if (!t.has_value() || !t->defined()) return nullptr;
   TORCH_CHECK(t->scalar_type() == at::kByte && t->is_contiguous() && t->numel() == flags.numel() && t->device() == flags.device(),
@@ -1007,13 +997,8 @@ Tensor bc_classify(Tensor flags, bool is3D, c10::optional<Tensor> UBC, c10::opti
   Tensor dummy;
   c10::optional<Tensor> none;
   FnxState st{};
-  auto opt = [&](c10::optional<Tensor>& t, bool vel, const char* name) -> const float* {
-    if (!t.has_value() || !t->defined()) return nullptr;
-    if (vel) check_vel(*t, g, name); else check_scalar(*t, g, name);
-    return t->data_ptr<float>();
-  };
-  st.UBC = opt(UBC, true, "UBC"); st.UBCInvMask = opt(UBCInvMask, true, "UBCInvMask");
-  st.densityBC = opt(densityBC, false, "densityBC"); st.densityBCInvMask = opt(densityBCInvMask, false, "densityBCInvMask");
+  st.UBC = opt_field(g, UBC, true, "UBC"); st.UBCInvMask = opt_field(g, UBCInvMask, true, "UBCInvMask");
+  st.densityBC = opt_field(g, densityBC, false, "densityBC"); st.densityBCInvMask = opt_field(g, densityBCInvMask, false, "densityBCInvMask");
   c10::hip::HIPGuard guard(flags.get_device());
   Tensor cls = at::empty(flags.sizes(), flags.options().dtype(at::kByte));
   check_status(fnx_bc_classify(&g, &st, cls.data_ptr<unsigned char>(), cur_stream(flags)));
@@ -1029,10 +1014,8 @@ Tensor pre_projection_(Tensor U_adv, c10::optional<Tensor> rho_adv, Tensor p, Te
   check_field(U, "U");
   FnxGrid g = grid_of(flags, U.size(1) == 3, geom);
   check_vel(U, g, "U"); check_vel(U_adv, g, "U_adv"); check_scalar(p, g, "p");
-  FnxStepParams prm{};
-  prm.dt = (float)dt; prm.buoyancy_scale = (float)buoyancy_scale;
-  for (int a = 0; a < 3; ++a) prm.gravity_vec[a] = (float)gravity_vec[a];
-  prm.operating_density = (float)operating_density; prm.method = jacobi_method ? 0 : 1;
+  FnxStepParams prm = step_params(dt, buoyancy_scale, gravity_vec, operating_density);
+  prm.method = jacobi_method ? 0 : 1;
   FnxState st = make_state(g, p, U, flags, density, UBC, UBCInvMask, densityBC, densityBCInvMask);
   const float* ra = nullptr;
   if (rho_adv.has_value() && rho_adv->defined()) { check_scalar(*rho_adv, g, "rho_adv"); ra = rho_adv->data_ptr<float>(); }

@@ -7,6 +7,7 @@
 #include "../../include/fluidnet_hip.h"
 #include "fnx_cnn.h"
 #include "fnx_kernels.h"
+#include <algorithm>
 #include <atomic>
 #include <dlfcn.h>
 
@@ -55,10 +56,9 @@ inline size_t ncell(const FnxGrid* g) { return (size_t)g->B * g->D * g->H * g->W
 inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct Carver {
-  char* base; size_t off, cap;
-  Carver(void* p, size_t c) : base((char*)p), off(0), cap(c) {}
+  char* base; size_t off;
+  explicit Carver(void* p) : base((char*)p), off(0) {}
   void* take(size_t bytes) { void* r = base ? base + off : nullptr; off += al(bytes); return r; }
-  bool ok() const { return base != nullptr && off <= cap; }
 };
 
 // advection: the forward fields of `what` and the tile kernels' fix-up bitmaps (the layout is fnx::advect_workspace's)
@@ -69,7 +69,7 @@ size_t ws_mask(const FnxGrid* g) { return g->is3D ? fnx::jacobi3d_mask_layout(di
 // the bytes it takes; ws == nullptr: the size only.
 struct JacobiWs { float* tmp; double* partials; float* res; fnx::JacobiMaskLayout mask; };
 size_t carve_jacobi(const FnxGrid* g, void* ws, JacobiWs* out) {
-  Carver c(ws, 0);
+  Carver c(ws);
   out->tmp = (float*)c.take(ncell(g) * 4);
   out->partials = (double*)c.take(fnx::residual_scratch_bytes(g->B));
   out->res = (float*)c.take(4);
@@ -80,21 +80,20 @@ size_t ws_jacobi(const FnxGrid* g) { JacobiWs W; return carve_jacobi(g, nullptr,
 // PCG: the multigrid hierarchy (kept between steps by fnx_simulate_step), then the solver's vectors
 size_t ws_pcg_kept(const FnxGrid* g) { return al(fnx::pcg_kept_bytes(dims(g), g->is3D)); }
 size_t ws_pcg(const FnxGrid* g) { return ws_pcg_kept(g) + al(fnx::pcg_scratch_bytes(dims(g), g->is3D)); }
-size_t ws_step(const FnxGrid* g) {
-  const size_t nc = g->is3D ? 3 : 2;
-  size_t adv = ws_advect(g, fnx::ADVECT_BOTH);          // the fused advection launches keep both forward fields at once
-  size_t solve = ws_jacobi(g);
-  size_t cnn = fnx::fluidnet_ws_bytes(dims(g), g->is3D);
-  size_t pcg = al(fnx::pcg_scratch_bytes(dims(g), g->is3D));
-  size_t tail = adv > solve ? adv : solve;
-  if (cnn > tail) tail = cnn;
-  if (pcg > tail) tail = pcg;
-  return al(ncell(g) * 4) /*rho2*/ + al(ncell(g) * 4 * nc) /*U2*/ + al(ncell(g) * 4) /*div*/ +
-         ws_mask(g) /*Jacobi obstacle mask, kept between steps*/ +
-         al(ncell(g)) /*BC class map, kept between steps*/ +
-         ws_pcg_kept(g) /*PCG multigrid hierarchy, kept between steps*/ +
-         (g->is3D ? 0 : al(ncell(g) * 4 * nc)) /*2D: the viscous velocity that is advected (FnxStepParams.viscosity)*/ + tail;
+// neither a whole domain nor all of its planes: a compute window or a z-slab view
+inline bool is_view(const FnxGrid* g) { return g->k_begin != 0 || g->k_end != 0 || g->z_offset != 0 || g->D_global != 0; }
+// The step's workspace (the layout is fnx::step_layout's).  Its tail serves, one after the other, the users named here.
+fnx::StepLayout carve_step(const FnxGrid* g, void* ws) {
+  const GridDims d = dims(g);
+  const size_t advect = ws_advect(g, fnx::ADVECT_BOTH);              // the fused advection launches keep both forward fields at once
+  const size_t jacobi = ws_jacobi(g);                               // sized as the stand-alone solve (its 3D mask is the kept one)
+  const size_t net = fnx::fluidnet_ws_bytes(d, g->is3D);            // the convnet projection, the hybrid's guess
+  const size_t pcg = al(fnx::pcg_scratch_bytes(d, g->is3D));        // the PCG solve's vectors
+  const size_t periodic = fnx::periodic_save_bytes(d);              // the patches' source row and column around the post-projection pass
+  const size_t tail_need = std::max({advect, jacobi, net, pcg, periodic});
+  return fnx::step_layout(ncell(g), g->is3D ? 3 : 2, g->is3D != 0, ws_mask(g), ws_pcg_kept(g), tail_need, ws);
 }
+size_t ws_step(const FnxGrid* g) { return carve_step(g, nullptr).bytes; }
 
 }  // namespace
 
@@ -542,7 +541,7 @@ size_t fnx_pcg_workspace_bytes(const FnxGrid* g) {
 namespace {
 int check_pcg_grid(const FnxGrid* g, const char* who) {
   if (int rc = check_grid(g)) return rc;
-  if (g->k_begin != 0 || g->k_end != 0 || g->z_offset != 0 || g->D_global != 0)
+  if (is_view(g))
     return fail(FNX_EINVAL, "%s: no compute window or z-slab view (the solve is single-domain)", who);
   return FNX_OK;
 }
@@ -652,7 +651,7 @@ int fnx_add_vorticity_confinement(const FnxGrid* g, const float* U_in, float* U_
   if (!U_in || !U_out || !flags) return fail(FNX_EINVAL, "add_vorticity_confinement: NULL tensor");
   if (U_in == U_out) return fail(FNX_EINVAL, "add_vorticity_confinement: U_out must not alias U_in (a cell reads U_in three cells around it)");
   if (int rc = check_grid(g)) return rc;
-  if (g->k_begin != 0 || g->k_end != 0 || g->z_offset != 0 || g->D_global != 0)
+  if (is_view(g))
     return fail(FNX_EINVAL, "add_vorticity_confinement: no compute window or z-slab view (whole grids only)");
   if (!(amp == amp)) return fail(FNX_EINVAL, "add_vorticity_confinement: the amplitude is NaN");
   hipStream_t s = (hipStream_t)stream;
@@ -666,7 +665,7 @@ namespace {
 int check_render(const FnxGrid* g, const FnxRenderParams* prm) {
   if (!prm) return fail(FNX_EINVAL, "render_volume: NULL parameters");
   if (int rc = check_grid(g)) return rc;
-  if (g->k_begin != 0 || g->k_end != 0 || g->z_offset != 0 || g->D_global != 0)
+  if (is_view(g))
     return fail(FNX_EINVAL, "render_volume: no compute window or z-slab view (whole grids only)");
   if (prm->view_dir < 0 || prm->view_dir > 5 || prm->light_dir < 0 || prm->light_dir > 5)
     return fail(FNX_EINVAL, "render_volume: direction outside 0..5 (view_dir=%d light_dir=%d)", prm->view_dir, prm->light_dir);
@@ -815,89 +814,69 @@ int fnx_velocity_update_backward(const FnxGrid* g, const float* grad_U_out, cons
   return FNX_OK;
 }
 
+// The stage by its plan, for fnx_pre_projection and fnx_simulate_step.  One fused pass writes the staged fields and the divergence (each
+// cell re-derives the staged component of its +1 neighbours), unless the periodic patches have to go between the stages and the
+// divergence: then staging, patches, a divergence pass.  With the confinement, which reads the field three cells around a cell and so
+// cannot join the radius-1 recompute, the stage is cut in three around it.
+static int pre_projection(const FnxGrid* g, const fnx::StagePlan& sp, const FnxState* st, const float* U_adv, const float* rho_adv,
+                          float* div, void* stream) {
+  // a cell reads the advected fields of its +1 / -1 neighbours while other threads write theirs: no in-place use
+  if (U_adv == st->U || (rho_adv && rho_adv == st->density)) return fail(FNX_EINVAL, "pre_projection: the advected fields must not alias the state");
+  if (sp.confine && is_view(g))
+    return fail(FNX_EINVAL, "pre_projection: vorticity confinement takes no compute window or z-slab view (single domain only)");
+  hipStream_t s = (hipStream_t)stream;
+  fnx::ProfScope ps(FNX_PROF_STAGE, s);
+  const GridDims d = dims(g);
+  const fnx::BcPtrs bc = fnx::bc_ptrs(st);
+  // the uncut stage: every operation of the plan, the divergence in the same pass unless the patches come between
+  const fnx::StageIO io{U_adv, rho_adv, st->flags, bc, st->U, st->density, sp.periodic ? nullptr : div};
+  const fnx::StageOps all{quirks(g), true, sp.buoy, {sp.s[0], sp.s[1], sp.s[2]}, sp.rho_star, sp.grav, {sp.g[0], sp.g[1], sp.g[2]},
+                          sp.wall, sp.second_bcs, d.K0 + d.KN};
+  if (!sp.confine) {
+    // the staging covers one plane more than the divergences asked for where there is one (3D ranges): the divergence of the last
+    // plane reads the advected fields of that plane, and the callers of plane ranges expect it staged as well
+    GridDims ds = d;
+    if (g->is3D && div && ds.K0 + ds.KN < ds.D) ds.KN += 1;
+    fnx::launch_pre_projection(ds, g->is3D, io, all, s);
+    if (sp.periodic) fnx::launch_periodic_pre(ds, g->is3D, U_adv, bc.UBC, bc.UBCInvMask, st->U, sp.px, sp.py, s, false);
+  } else {
+    // (1) setConstVals, addBuoyancy, addGravity: U_adv -> st->U; the density is through with it but for its second setConstVals
+    fnx::StageIO io1 = io;
+    io1.div = nullptr;
+    fnx::StageOps upto_gravity = all;
+    upto_gravity.wall = false; upto_gravity.second_bcs = false; upto_gravity.div_k_end = 0;
+    fnx::launch_pre_projection(d, g->is3D, io1, upto_gravity, s);
+    // (2) the confinement: st->U -> U_adv, which is scratch from here on
+    float* U_scr = const_cast<float*>(U_adv);
+    fnx::launch_vorticity_confinement(d, g->is3D, st->U, st->flags, U_scr, sp.amp, s);
+    // (3) setWallBcs (+ periodic patches), setConstVals, divergence: U_adv -> st->U, the velocity alone
+    fnx::StageIO io3 = io;
+    io3.rho_adv = nullptr; io3.rho = nullptr; io3.bc.rhoBC = nullptr; io3.bc.rhoBCInvMask = nullptr;
+    fnx::StageOps from_walls = all;
+    from_walls.first_bcs = false; from_walls.buoy = false; from_walls.grav = false;
+    fnx::launch_pre_projection(d, g->is3D, io3, from_walls, s);
+    if (sp.periodic) fnx::launch_periodic_pre(d, g->is3D, U_scr, bc.UBC, bc.UBCInvMask, st->U, sp.px, sp.py, s, true);
+  }
+  if (sp.periodic && div) fnx::launch_divergence(d, g->is3D, st->U, st->flags, div, s);
+  if (sp.confine && rho_adv && bc.rhoBC && sp.second_bcs) fnx::launch_set_const_vals(ncell(g), st->density, bc.rhoBC, bc.rhoBCInvMask, s);
+  HIP_OK(hipGetLastError());
+  return FNX_OK;
+}
+
 int fnx_pre_projection(const FnxGrid* g, const FnxStepParams* prm, const FnxState* st, const float* U_adv,
                        const float* rho_adv, float* div, void* stream) {
   if (int rc = check_grid(g)) return rc;
   if (!prm || !st || !st->U || !st->flags || !U_adv) return fail(FNX_EINVAL, "pre_projection: NULL state");
   if (rho_adv && !st->density) return fail(FNX_EINVAL, "pre_projection: rho_adv given but state has no density");
-  // a cell reads the advected fields of its +1 / -1 neighbours while other threads write theirs: no in-place use
-  if (U_adv == st->U || (rho_adv && rho_adv == st->density)) return fail(FNX_EINVAL, "pre_projection: the advected fields must not alias the state");
-  const bool has_rho = rho_adv != nullptr;
-  const bool buoy = has_rho && prm->buoyancy_scale > 0.f;
-  float sx = 0.f, sy = 0.f, sz = 0.f;
-  if (buoy) {
-    const float ns = -prm->buoyancy_scale;                       // gravity.mul_(-buoyancyScale), simulate.py:101-105
-    const float gx = prm->gravity_vec[0] * ns, gy = prm->gravity_vec[1] * ns, gz = prm->gravity_vec[2] * ns;
-    sx = gx * prm->dt; sy = gy * prm->dt; sz = gz * prm->dt;     // strength = gravity * dt, source_terms.py:45
-  }
-  const bool ubc = st->UBC && st->UBCInvMask, rbc = st->densityBC && st->densityBCInvMask;
-  // simulate.py:107-114: addGravity(gravityVec * -gravityScale) after the buoyancy, inside the density branch
-  const bool grav = has_rho && prm->gravity_scale > 0.f;
-  float gv[3] = {0.f, 0.f, 0.f};
-  if (grav) {
-    const float ns = -prm->gravity_scale;
-    for (int a = 0; a < 3; ++a) gv[a] = (prm->gravity_vec[a] * ns) * prm->dt;       // force = gravity * dt, source_terms.py
-  }
-  // simulate.py:119-130: setWallBcs and the periodic patches in the Jacobi branch only; with 'flags_stick' the convnet branch
-  // runs setWallBcsStick between the stages and the second setConstVals, which are then the caller's (fnx_simulate_step)
-  const bool wall = prm->method != 1;
-  const bool periodic = wall && (prm->periodic & 1);
-  const bool second_bcs = !(prm->method == 1 && st->flags_stick);
-  const bool confine = prm->vorticity_confinement > 0.f;
-  if (confine && (g->k_begin != 0 || g->k_end != 0 || g->z_offset != 0 || g->D_global != 0))
-    return fail(FNX_EINVAL, "pre_projection: vorticity confinement takes no compute window or z-slab view (single domain only)");
-  fnx::ProfScope ps(FNX_PROF_STAGE, (hipStream_t)stream);
-  if (confine) {
-    // The stage cut in two around the confinement, which reads the field three cells around a cell and so cannot join the
-    // radius-1 recompute: (1) setConstVals, addBuoyancy, addGravity: U_adv -> st->U; (2) confinement: st->U -> U_adv;
-    // (3) setWallBcs (+ periodic patches), setConstVals, divergence: U_adv -> st->U.  The density is through with (1) but for
-    // its second setConstVals.
-    hipStream_t s = (hipStream_t)stream;
-    const GridDims d = dims(g);
-    float* U_scr = const_cast<float*>(U_adv);
-    const float* ubc_ = ubc ? st->UBC : nullptr; const float* ubm_ = ubc ? st->UBCInvMask : nullptr;
-    fnx::launch_pre_projection(d, g->is3D, quirks(g), U_adv, rho_adv, st->flags, ubc_, ubm_, rbc ? st->densityBC : nullptr,
-                               rbc ? st->densityBCInvMask : nullptr, st->U, st->density, nullptr, buoy, sx, sy, sz,
-                               prm->operating_density, false, s, st->bc_class, grav ? gv : nullptr, false, 0);
-    fnx::launch_vorticity_confinement(d, g->is3D, st->U, st->flags, U_scr, prm->vorticity_confinement, s);
-    fnx::launch_pre_projection(d, g->is3D, quirks(g), U_scr, nullptr, st->flags, ubc_, ubm_, nullptr, nullptr, st->U, nullptr,
-                               periodic ? nullptr : div, false, 0.f, 0.f, 0.f, 0.f, wall, s, st->bc_class, nullptr, second_bcs,
-                               d.K0 + d.KN, false);
-    if (periodic)
-      fnx::launch_periodic_pre(d, g->is3D, U_scr, ubc_, ubm_, st->U, (prm->periodic & 2) != 0, (prm->periodic & 4) != 0, s, true);
-    if (periodic && div) fnx::launch_divergence(d, g->is3D, st->U, st->flags, div, s);
-    if (has_rho && rbc && second_bcs) fnx::launch_set_const_vals(ncell(g), st->density, st->densityBC, st->densityBCInvMask, s);
-    HIP_OK(hipGetLastError());
-    return FNX_OK;
-  }
-  // One fused pass writes the staged fields and the divergence (each cell re-derives the staged component of its +1 neighbours),
-  // unless the periodic patches have to go between the stages and the divergence: then staging, patches, a divergence pass.
-  const bool split = periodic;
-  // the staging covers one plane more than the divergences asked for where there is one (3D ranges): the divergence of the last
-  // plane reads the advected fields of that plane, and the callers of plane ranges expect it staged as well
-  GridDims ds = dims(g);
-  const int div_k_end = ds.K0 + ds.KN;
-  if (g->is3D && div && ds.K0 + ds.KN < ds.D) ds.KN += 1;
-  fnx::launch_pre_projection(ds, g->is3D, quirks(g), U_adv, rho_adv, st->flags, ubc ? st->UBC : nullptr,
-                             ubc ? st->UBCInvMask : nullptr, rbc ? st->densityBC : nullptr,
-                             rbc ? st->densityBCInvMask : nullptr, st->U, st->density, (split && div) ? nullptr : div, buoy, sx, sy, sz,
-                             prm->operating_density, wall, (hipStream_t)stream, st->bc_class, grav ? gv : nullptr, second_bcs, div_k_end);
-  if (periodic)
-    fnx::launch_periodic_pre(ds, g->is3D, U_adv, ubc ? st->UBC : nullptr, ubc ? st->UBCInvMask : nullptr, st->U,
-                             (prm->periodic & 2) != 0, (prm->periodic & 4) != 0, (hipStream_t)stream);
-  if (split && div) fnx::launch_divergence(dims(g), g->is3D, st->U, st->flags, div, (hipStream_t)stream);
-  HIP_OK(hipGetLastError());
-  return FNX_OK;
+  return pre_projection(g, fnx::stage_plan(prm, rho_adv != nullptr, st->flags_stick != nullptr), st, U_adv, rho_adv, div, stream);
 }
 
 int fnx_post_projection(const FnxGrid* g, const FnxState* st, void* stream) {
   if (int rc = check_grid(g)) return rc;
   if (!st || !st->U || !st->flags || !st->p) return fail(FNX_EINVAL, "post_projection: NULL state");
-  const bool ubc = st->UBC && st->UBCInvMask, rbc = st->densityBC && st->densityBCInvMask;
   fnx::ProfScope ps(FNX_PROF_STAGE, (hipStream_t)stream);
-  fnx::launch_post_projection(dims(g), g->is3D, st->p, st->U, st->density, st->flags, ubc ? st->UBC : nullptr,
-                              ubc ? st->UBCInvMask : nullptr, rbc ? st->densityBC : nullptr,
-                              rbc ? st->densityBCInvMask : nullptr, (hipStream_t)stream, st->bc_class, st->density_bc_applied != 0);
+  fnx::launch_post_projection(dims(g), g->is3D, st->p, st->U, st->density, st->flags, fnx::bc_ptrs(st), (hipStream_t)stream,
+                              st->density_bc_applied != 0);
   HIP_OK(hipGetLastError());
   return FNX_OK;
 }
@@ -905,135 +884,124 @@ int fnx_post_projection(const FnxGrid* g, const FnxState* st, void* stream) {
 int fnx_bc_classify(const FnxGrid* g, const FnxState* st, unsigned char* bc_class, void* stream) {
   if (int rc = check_grid(g)) return rc;
   if (!st || !bc_class) return fail(FNX_EINVAL, "bc_classify: NULL argument");
-  const bool ubc = st->UBC && st->UBCInvMask, rbc = st->densityBC && st->densityBCInvMask;
-  fnx::launch_bc_classify(dims(g), g->is3D, ubc ? st->UBC : nullptr, ubc ? st->UBCInvMask : nullptr,
-                          rbc ? st->densityBC : nullptr, rbc ? st->densityBCInvMask : nullptr, bc_class, (hipStream_t)stream);
+  fnx::launch_bc_classify(dims(g), g->is3D, fnx::bc_ptrs(st), bc_class, (hipStream_t)stream);
   HIP_OK(hipGetLastError());
   return FNX_OK;
 }
 
+// One whole step: the argument checks, the workspace (carve_step), the plan (fnx::step_plan), then the sequence the plan names.
 int fnx_simulate_step(const FnxGrid* g, const FnxStepParams* prm, const FnxState* st, void* ws, size_t ws_bytes,
                       void* stream) {
+  using fnx::StepAdvect; using fnx::StepClassMap; using fnx::StepProjection; using fnx::StepTail;
   if (int rc = check_grid(g)) return rc;
   if (!prm || !st || !st->p || !st->U || !st->flags) return fail(FNX_EINVAL, "simulate_step: NULL state");
   if (prm->method < 0 || prm->method > 4) return fail(FNX_EINVAL, "Simulation method not supported. Choose convnet, jacobi, pcg or hybrid.");
   const bool pcg = prm->method >= 2;                 // 2: cold, 3 ('hybrid'): from the net's pressure, 4: from st->p as it stands
   if (pcg && prm->pcg_iter < 1) return fail(FNX_EINVAL, "At least 1 iteration of the solver is needed (pcg_iter < 1)");
-  if (pcg && (g->k_begin != 0 || g->k_end != 0 || g->z_offset != 0 || g->D_global != 0))
+  if (pcg && is_view(g))
     return fail(FNX_EINVAL, "simulate_step: the PCG solve takes no compute window or z-slab view (single domain only)");
-  if (prm->vorticity_confinement > 0.f && (g->k_begin != 0 || g->k_end != 0 || g->z_offset != 0 || g->D_global != 0))
+  if (prm->vorticity_confinement > 0.f && is_view(g))
     return fail(FNX_EINVAL, "simulate_step: vorticity confinement takes no compute window or z-slab view (single domain only)");
   if (prm->method == 1 && !st->net) return fail(FNX_EINVAL, "simulate_step: convnet method needs packed weights");
   if (prm->method == 3 && !st->net) return fail(FNX_EINVAL, "simulate_step: hybrid method needs packed weights");
   if (prm->method == 3 && fnx::net_mode(prm->precision_mode) < 0) return fail(FNX_EINVAL, "simulate_step: unknown precision_mode %d", prm->precision_mode);
-  hipStream_t s = (hipStream_t)stream;
-  const size_t n = ncell(g), nc = g->is3D ? 3 : 2;
-  Carver c(ws, ws_bytes);
-  float* rho2 = (float*)c.take(n * 4);
-  float* U2 = (float*)c.take(n * 4 * nc);
-  float* div = (float*)c.take(n * 4);
-  unsigned char* kept_mask = g->is3D ? (unsigned char*)c.take(ws_mask(g)) : nullptr;
-  unsigned char* kept_cls = (unsigned char*)c.take(n);
-  void* kept_pcg = c.take(ws_pcg_kept(g));
-  float* orig = g->is3D ? nullptr : (float*)c.take(n * 4 * nc);        // 2D: the viscous velocity (prm->viscosity > 0)
-  void* tail = c.take(0);
-  const size_t tail_bytes = ws_bytes > c.off ? ws_bytes - c.off : 0;
-  if (!c.ok() || ws_bytes < ws_step(g)) return fail(FNX_EWORKSPACE, "simulate_step: workspace too small (%zu < %zu)", ws_bytes, ws_step(g));
+  const fnx::StepLayout L = carve_step(g, ws);
+  if (!ws || ws_bytes < L.bytes) return fail(FNX_EWORKSPACE, "simulate_step: workspace too small (%zu < %zu)", ws_bytes, L.bytes);
   const bool has_rho = st->density != nullptr;
-  const bool viscous = prm->viscosity > 0.f;
+  const fnx::StepPlan plan = fnx::step_plan(prm, has_rho, st->flags_stick != nullptr, st->UBC || st->densityBC);
   if (prm->viscosity < 0.f) return fail(FNX_EINVAL, "Viscosity must be positive");
   if (prm->vorticity_confinement != prm->vorticity_confinement) return fail(FNX_EINVAL, "simulate_step: vorticity_confinement is NaN");
-  if (viscous && g->is3D) return fail(FNX_EINVAL, "simulate_step: viscosity is 2D only (reference viscosity.py:5)");
-  const bool stick = prm->method == 1 && st->flags_stick != nullptr;           // simulate.py:129-130, :165-166
-  if (stick && g->is3D) return fail(FNX_EINVAL, "simulate_step: flags_stick is 2D only (set_wall_bcs_stick.py:85-86)");
-  const bool periodic = prm->method != 1 && (prm->periodic & 1);
+  if (plan.viscous && g->is3D) return fail(FNX_EINVAL, "simulate_step: viscosity is 2D only (reference viscosity.py:5)");
+  if (plan.projection == StepProjection::NET_STICK && g->is3D) return fail(FNX_EINVAL, "simulate_step: flags_stick is 2D only (set_wall_bcs_stick.py:85-86)");
+  hipStream_t s = (hipStream_t)stream;
+  const GridDims d = dims(g);
+  const size_t nc = g->is3D ? 3 : 2;
+
   // simulate.py:66-93: advect density then velocity (both by the OLD U; the velocity advected is the viscous one)
-  if (viscous) {
-    if (int rc = fnx_add_viscosity(g, prm->dt, st->U, orig, st->flags, prm->viscosity, stream)) return rc;
-    if (has_rho) {
-      if (int rc = fnx_advect_scalar(g, prm->dt, st->density, st->U, st->flags, rho2, FNX_ADVECT_MACCORMACK, 1,
-                                     prm->sample_outside_fluid, prm->maccormack_strength, tail, tail_bytes, stream)) return rc;
-    }
-    if (int rc = fnx_advect_vel(g, prm->dt, orig, st->U, st->flags, U2, FNX_ADVECT_MACCORMACK, 1, prm->maccormack_strength,
-                                tail, tail_bytes, stream)) return rc;
-  } else if (has_rho) {
+  if (plan.viscous) {
+    if (int rc = fnx_add_viscosity(g, prm->dt, st->U, L.orig, st->flags, prm->viscosity, stream)) return rc;
+  }
+  if (plan.advect == StepAdvect::PAIR) {
     // forward passes of both advections in one launch, backward/clamp passes in another (same cell functions)
-    if (int rc = fnx_advect_step(g, prm->dt, st->density, st->U, st->flags, rho2, U2, prm->sample_outside_fluid,
-                                 prm->maccormack_strength, tail, tail_bytes, stream)) return rc;
-  } else {                                     // simulate.py:71-83: no 'density' key in the batch
-    if (int rc = fnx_advect_vel(g, prm->dt, st->U, st->U, st->flags, U2, FNX_ADVECT_MACCORMACK, 1,
-                                prm->maccormack_strength, tail, tail_bytes, stream)) return rc;
+    if (int rc = fnx_advect_step(g, prm->dt, st->density, st->U, st->flags, L.rho2, L.U2, prm->sample_outside_fluid,
+                                 prm->maccormack_strength, L.tail, L.tail_bytes, stream)) return rc;
+  } else {
+    if (plan.advect == StepAdvect::RHO_THEN_VEL) {
+      if (int rc = fnx_advect_scalar(g, prm->dt, st->density, st->U, st->flags, L.rho2, FNX_ADVECT_MACCORMACK, 1,
+                                     prm->sample_outside_fluid, prm->maccormack_strength, L.tail, L.tail_bytes, stream)) return rc;
+    }
+    if (int rc = fnx_advect_vel(g, prm->dt, plan.viscous ? L.orig : st->U, st->U, st->flags, L.U2, FNX_ADVECT_MACCORMACK, 1,
+                                prm->maccormack_strength, L.tail, L.tail_bytes, stream)) return rc;
   }
-  if (has_rho && prm->correct_scalar) {        // simulate.py:79-81: by the divergence of the OLD U (st->U is still untouched)
-    fnx::launch_divergence(dims(g), g->is3D, st->U, st->flags, div, s);
-    if (int rc = fnx_correct_scalar(g, prm->dt, rho2, div, st->flags, stream)) return rc;
+  if (plan.correct_scalar) {                   // simulate.py:79-81: by the divergence of the OLD U (st->U is still untouched)
+    fnx::launch_divergence(d, g->is3D, st->U, st->flags, L.div, s);
+    if (int rc = fnx_correct_scalar(g, prm->dt, L.rho2, L.div, st->flags, stream)) return rc;
   }
-  // static BC arrays (static_flags bit 1): the BC stages go by the class map kept in the workspace (built once, bit 2)
+  // static BC arrays: the BC stages go by the class map kept in the workspace
   FnxState stc = *st;
-  stc.bc_class = nullptr;
-  if ((prm->static_flags & 2) && (st->UBC || st->densityBC)) {
-    if (!(prm->static_flags & 4)) { if (int rc = fnx_bc_classify(g, st, kept_cls, stream)) return rc; }
-    stc.bc_class = kept_cls;
-  }
+  if (plan.class_map == StepClassMap::BUILD) { if (int rc = fnx_bc_classify(g, st, L.cls, stream)) return rc; }
+  stc.bc_class = plan.class_map == StepClassMap::NONE ? nullptr : L.cls;
   stc.density_bc_applied = 1;                  // by the pre-projection stage below, with these BC arrays
   st = &stc;
   // simulate.py:96-133 (+ :144 divergence) in one pass: BCs, buoyancy, gravity, wall BCs (+ periodic patches), BCs, -div
-  if (int rc = fnx_pre_projection(g, prm, st, U2, has_rho ? rho2 : nullptr, prm->method != 1 ? div : nullptr, stream)) return rc;
-  const GridDims d = dims(g);
-  float* rho = has_rho ? st->density : nullptr;
-  // setWallBcsStick is out of place: st->U -> U2 (free since the staging pass) and back
-  auto stick_pass = [&]() -> int {
-    if (int rc = fnx_set_wall_bcs_stick(g, st->U, U2, st->flags, st->flags_stick, stream)) return rc;
-    HIP_OK(hipMemcpyAsync(st->U, U2, n * 4 * nc, hipMemcpyDeviceToDevice, s));
-    return FNX_OK;
+  if (int rc = pre_projection(g, plan.stage, st, L.U2, has_rho ? L.rho2 : nullptr, plan.solve ? L.div : nullptr, stream)) return rc;
+
+  // setWallBcsStick is out of place: st->U -> U2 (free since the staging pass) and back; then the setConstVals behind it
+  auto stick_then_bcs = [&]() -> int {
+    if (int rc = fnx_set_wall_bcs_stick(g, st->U, L.U2, st->flags, st->flags_stick, stream)) return rc;
+    HIP_OK(hipMemcpyAsync(st->U, L.U2, ncell(g) * 4 * nc, hipMemcpyDeviceToDevice, s));
+    return fnx_set_const_vals(g, st->U, st->UBC, st->UBCInvMask, st->density, st->densityBC, st->densityBCInvMask, stream);
   };
-  if (prm->method != 1) {
-    // simulate.py:144-168
-    if (prm->method == 0) {
-      if (int rc = jacobi_solve(g, st->flags, div, st->p, nullptr, prm->p_tol, prm->jacobi_iter, nullptr, tail, tail_bytes, kept_mask, (prm->static_flags & 1) != 0, stream, 0)) return rc;
-    } else {
-      // the hierarchy is only trusted when the caller says both that flags are unchanged (bit 0) and that this workspace holds
-      // the hierarchy of these flags (bit 3)
-      if ((prm->static_flags & 9) != 9) fnx::launch_pcg_build(d, g->is3D, quirks(g), st->flags, kept_pcg, s);
-      if (tail_bytes < fnx::pcg_scratch_bytes(d, g->is3D)) return fail(FNX_EWORKSPACE, "simulate_step: workspace too small for the PCG solve");
-      if (prm->method == 3) {
+  switch (plan.projection) {                   // simulate.py:136-152
+    case StepProjection::JACOBI:
+      if (int rc = jacobi_solve(g, st->flags, L.div, st->p, nullptr, prm->p_tol, prm->jacobi_iter, nullptr, L.tail, L.tail_bytes, L.mask,
+                                plan.reuse_mask, stream, 0)) return rc;
+      break;
+    case StepProjection::PCG_COLD: case StepProjection::PCG_FROM_NET: case StepProjection::PCG_FROM_P: {
+      if (plan.pcg_rebuild) fnx::launch_pcg_build(d, g->is3D, quirks(g), st->flags, L.pcg_kept, s);
+      if (plan.projection == StepProjection::PCG_FROM_NET) {
         // the guess: the net's un-normalised pressure of this U, written into st->p.  The net's scratch and the solve's share the
         // tail: the net has finished (same stream) before the solve's first launch, and all the solve takes from it is st->p
-        if (tail_bytes < fnx::fluidnet_ws_bytes(d, g->is3D)) return fail(FNX_EWORKSPACE, "simulate_step: workspace too small for the CNN");
         if (int rc = fnx::fluidnet_pressure(g, st->net, st->flags, prm->normalize_threshold, fnx::net_mode(prm->precision_mode), st->p, st->U,
-                                            tail, stream)) return rc;
+                                            L.tail, stream)) return rc;
       }
-      const float* p0 = prm->method == 2 ? nullptr : st->p;
-      if (int rc = fnx::pcg_solve(d, g->is3D, kept_pcg, tail, div, p0, st->p, nullptr, prm->pcg_tol, prm->pcg_iter, nullptr, false, s)) return rc;
+      const float* p0 = plan.projection == StepProjection::PCG_COLD ? nullptr : st->p;
+      if (int rc = fnx::pcg_solve(d, g->is3D, L.pcg_kept, L.tail, L.div, p0, st->p, nullptr, prm->pcg_tol, prm->pcg_iter, nullptr, false, s)) return rc;
+      break;
     }
-    if (!periodic) return fnx_post_projection(g, st, stream);
-    // simulate.py:157-164: the patches read the field as it was before setWallBcs; their source row / column (border cells,
-    // which velocityUpdate leaves alone) is saved ahead of the in-place pass.  The solve is through with the tail.
-    if (tail_bytes < fnx::periodic_save_bytes(d)) return fail(FNX_EWORKSPACE, "simulate_step: workspace too small for the periodic patches");
-    const bool ubc = st->UBC && st->UBCInvMask;
-    const bool px = (prm->periodic & 2) != 0, py = (prm->periodic & 4) != 0;
-    fnx::launch_periodic_post(d, g->is3D, st->U, (float*)tail, nullptr, nullptr, px, py, 0, s);
-    if (int rc = fnx_post_projection(g, st, stream)) return rc;
-    fnx::launch_periodic_post(d, g->is3D, st->U, (float*)tail, ubc ? st->UBC : nullptr, ubc ? st->UBCInvMask : nullptr, px, py, 1, s);
-    HIP_OK(hipGetLastError());
-    return FNX_OK;
-  } else {
-    if (stick) {                                // simulate.py:129-133: setWallBcsStick, then the second setConstVals
-      if (int rc = stick_pass()) return rc;
-      if (int rc = fnx_set_const_vals(g, st->U, st->UBC, st->UBCInvMask, rho, st->densityBC, st->densityBCInvMask, stream)) return rc;
+    case StepProjection::NET_STICK:            // simulate.py:129-133: setWallBcsStick, then the second setConstVals
+      if (int rc = stick_then_bcs()) return rc;
+      [[fallthrough]];
+    case StepProjection::NET_FUSED: {
+      // simulate.py:136-142: p, U = net(cat(p, U, flags, density)) -- the net only reads U and flags (model.py:104-126),
+      // so the concatenation is not materialised: U is projected in place.
+      const int mode = fnx::net_mode(prm->precision_mode);
+      if (mode < 0) return fail(FNX_EINVAL, "simulate_step: unknown precision_mode %d", prm->precision_mode);
+      // without flags_stick the tail of the net's forward and the step's last setConstVals are one pass (fluidnet_core)
+      if (int rc = fnx::fluidnet_core(g, st->net, st->flags, prm->normalize_threshold, mode, st->p, st->U, L.tail, stream,
+                                      plan.projection == StepProjection::NET_FUSED ? st : nullptr)) return rc;
+      break;
     }
-    // simulate.py:136-142: p, U = net(cat(p, U, flags, density)) -- the net only reads U and flags (model.py:104-126),
-    // so the concatenation is not materialised: U is projected in place.
-    if (tail_bytes < fnx::fluidnet_ws_bytes(d, g->is3D)) return fail(FNX_EWORKSPACE, "simulate_step: workspace too small for the CNN");
-    const int mode = fnx::net_mode(prm->precision_mode);
-    if (mode < 0) return fail(FNX_EINVAL, "simulate_step: unknown precision_mode %d", prm->precision_mode);
-    // without flags_stick the tail of the net's forward and the step's last setConstVals are one pass (fluidnet_core)
-    if (int rc = fnx::fluidnet_core(g, st->net, st->flags, prm->normalize_threshold, mode, st->p, st->U, tail, stream,
-                                    stick ? nullptr : st)) return rc;
-    if (!stick) { HIP_OK(hipGetLastError()); return FNX_OK; }
-    if (int rc = stick_pass()) return rc;                                       // simulate.py:165-166
   }
-  fnx_set_const_vals(g, st->U, st->UBC, st->UBCInvMask, rho, st->densityBC, st->densityBCInvMask, stream);
+  switch (plan.tail) {                         // simulate.py:154-168
+    case StepTail::POST:
+      if (int rc = fnx_post_projection(g, st, stream)) return rc;
+      break;
+    case StepTail::POST_PERIODIC: {
+      // simulate.py:157-164: the patches read the field as it was before setWallBcs; their source row / column (border cells,
+      // which velocityUpdate leaves alone) is saved ahead of the in-place pass.  The solve is through with the tail.
+      const fnx::BcPtrs bc = fnx::bc_ptrs(st);
+      fnx::launch_periodic_post(d, g->is3D, st->U, (float*)L.tail, nullptr, nullptr, plan.stage.px, plan.stage.py, 0, s);
+      if (int rc = fnx_post_projection(g, st, stream)) return rc;
+      fnx::launch_periodic_post(d, g->is3D, st->U, (float*)L.tail, bc.UBC, bc.UBCInvMask, plan.stage.px, plan.stage.py, 1, s);
+      break;
+    }
+    case StepTail::STICK_BCS:                  // simulate.py:165-168
+      if (int rc = stick_then_bcs()) return rc;
+      break;
+    case StepTail::NONE:
+      break;
+  }
   HIP_OK(hipGetLastError());
   return FNX_OK;
 }

@@ -1811,10 +1811,26 @@ void launch_gather_input(const GridDims& g, int nc, const float* input, float* U
   gather_input_kernel<<<bgrid(g.DHW, g.B), 256, 0, s>>>((size_t)g.DHW, nc, input, U, flags);
 }
 
-size_t fluidnet_ws_bytes(const GridDims& g, bool is3d) {
+// The scratch of FluidNet.forward behind its flags copy, in this order, each region rounded up to 256 bytes: the divergence (the fused
+// step keeps the net's p there), the net's input, scale_std's partial sums, the per-sample scales, the net's own workspace.
+// base == nullptr: the size only.
+struct FluidnetWs { float* div; float* x; double* partial; float* scale; void* msws; size_t bytes; };
+static FluidnetWs fluidnet_ws_layout(const GridDims& g, bool is3d, void* base) {
   const size_t full = (size_t)g.B * g.DHW;
-  return multiscale_ws_bytes(g, is3d) + al256(full * 4) /*flags*/ + al256(full * 4) /*div, or the net's p before the fused tail*/ + al256(full * 2 * 4) /*x*/ +
-         al256(scale_std_scratch_bytes(g.B)) + al256(sizeof(float) * g.B);
+  size_t off = 0;
+  auto take = [&](size_t bytes) { void* r = base ? (char*)base + off : nullptr; off += al256(bytes); return r; };
+  FluidnetWs w{};
+  w.div = (float*)take(full * 4);
+  w.x = (float*)take(full * 2 * 4);
+  w.partial = (double*)take(scale_std_scratch_bytes(g.B));
+  w.scale = (float*)take(sizeof(float) * g.B);
+  w.msws = take(multiscale_ws_bytes(g, is3d));
+  w.bytes = off;
+  return w;
+}
+
+size_t fluidnet_ws_bytes(const GridDims& g, bool is3d) {
+  return al256((size_t)g.B * g.DHW * 4) /*flags*/ + fluidnet_ws_layout(g, is3d, nullptr).bytes;
 }
 
 }  // namespace fnx
@@ -1836,14 +1852,10 @@ int fluidnet_core(const FnxGrid* g, const void* packed, const float* flags, floa
   const GridDims d = make_dims(g->B, g->D, g->H, g->W, g->z_offset, g->D_global);
   hipStream_t s = (hipStream_t)stream;
   const int nc = g->is3D ? 3 : 2;
-  const size_t full = (size_t)g->B * d.DHW;
-  char* w = (char*)ws;
-  auto take = [&](size_t bytes) { void* r = w; w += (bytes + 255) & ~(size_t)255; return r; };
-  float* div = (float*)take(full * 4);
-  float* x = (float*)take(full * 2 * 4);
-  double* partial = (double*)take(scale_std_scratch_bytes(g->B));
-  float* scale = (float*)take(sizeof(float) * g->B);
-  void* msws = w;
+  const FluidnetWs w = fluidnet_ws_layout(d, g->is3D, ws);
+  float *div = w.div, *x = w.x, *scale = w.scale;
+  double* partial = w.partial;
+  void* msws = w.msws;
   if (bcs) {
     // The fused step (fnx_simulate_step, convnet, no flags_stick): three launches around the net instead of eight, the same
     // arithmetic per value.  The divergence goes straight into the net's input, U is not rewritten before the net, and
@@ -1858,11 +1870,9 @@ int fluidnet_core(const FnxGrid* g, const void* packed, const float* flags, floa
     }
     float* pnet = div;                                                           // (the divergence buffer is free here)
     multiscale_forward(d, g->is3D, packed, x, pnet, precision_mode, msws, s);    // model.py:174-175
-    const bool ubc = bcs->UBC && bcs->UBCInvMask, rbc = bcs->densityBC && bcs->densityBCInvMask;
     ProfScope ps(FNX_PROF_STAGE, s);
-    launch_post_projection(d, g->is3D, pnet, U, bcs->density, flags, ubc ? bcs->UBC : nullptr, ubc ? bcs->UBCInvMask : nullptr,
-                           rbc ? bcs->densityBC : nullptr, rbc ? bcs->densityBCInvMask : nullptr, s, bcs->bc_class,
-                           bcs->density_bc_applied != 0, scale, p_out);          // model.py:213-226, simulate.py:168
+    launch_post_projection(d, g->is3D, pnet, U, bcs->density, flags, bc_ptrs(bcs), s, bcs->density_bc_applied != 0, scale,
+                           p_out);                                               // model.py:213-226, simulate.py:168
     return fnx::launch_status(g->is3D);
   }
   if (int rc = fnx_velocity_divergence(g, U, flags, div, stream)) return rc;     // model.py:125-126
@@ -1883,14 +1893,10 @@ int fluidnet_pressure(const FnxGrid* g, const void* packed, const float* flags, 
   const GridDims d = make_dims(g->B, g->D, g->H, g->W, g->z_offset, g->D_global);
   hipStream_t s = (hipStream_t)stream;
   const int nc = g->is3D ? 3 : 2;
-  const size_t full = (size_t)g->B * d.DHW;
-  char* w = (char*)ws;
-  auto take = [&](size_t bytes) { void* r = w; w += (bytes + 255) & ~(size_t)255; return r; };
-  take(full * 4);                                                                // (fluidnet_core's layout: its divergence buffer)
-  float* x = (float*)take(full * 2 * 4);
-  double* partial = (double*)take(scale_std_scratch_bytes(g->B));
-  float* scale = (float*)take(sizeof(float) * g->B);
-  void* msws = w;
+  const FluidnetWs w = fluidnet_ws_layout(d, g->is3D, ws);                      // (its divergence buffer is not used here)
+  float *x = w.x, *scale = w.scale;
+  double* partial = w.partial;
+  void* msws = w.msws;
   launch_scale_std(d, nc, U, thr, partial, scale, s);                            // model.py:129-144
   launch_pack_div(d, g->is3D, U, flags, scale, x, s);                            // model.py:125-126, :146-168
   multiscale_forward(d, g->is3D, packed, x, p_out, precision_mode, msws, s);     // model.py:174-175

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include "fnx_device.h"
 #include "fnx_jacobi_plan.h"
+#include "fnx_step_plan.h"
 
 namespace fnx {
 
@@ -70,16 +71,31 @@ void launch_velocity_update_bwd(const GridDims& g, bool is3d, const float* gout,
                                 hipStream_t s);
 
 // fused step stages (fnx_step.hip)
-void launch_pre_projection(const GridDims& g, bool is3d, bool quirks, const float* U_adv, const float* rho_adv,
-                           const float* flags, const float* UBC, const float* UBCInvMask, const float* rhoBC,
-                           const float* rhoBCInvMask, float* U, float* rho, float* div, bool buoyancy, float sx,
-                           float sy, float sz, float rho_star, bool wall_bcs, hipStream_t s,
-                           const unsigned char* cls = nullptr, const float* gravity = nullptr, bool second_bcs = true,
-                           int div_k_end = 0, bool first_bcs = true);
-// first_bcs = false leaves out the setConstVals of simulate.py:96 (U_adv is a field that has been through it already);
-// gravity: 3 host floats (gravity * dt) or null; second_bcs = false leaves out the setConstVals of simulate.py:133; 3D with `div`:
-// the divergence of the staged field is written for the planes [g.K0, div_k_end) of the staged range (the staged value of a cell's
-// +1 neighbours is re-derived in the same pass; their advected inputs must be valid)
+// The BC arrays of a state as the stages take them: a pair counts only with both of its halves (bc_ptrs); cls: the optional class map
+struct BcPtrs { const float *UBC, *UBCInvMask, *rhoBC, *rhoBCInvMask; const unsigned char* cls; };
+inline BcPtrs bc_ptrs(const FnxState* st) {
+  const bool ubc = st->UBC && st->UBCInvMask, rbc = st->densityBC && st->densityBCInvMask;
+  return BcPtrs{ubc ? st->UBC : nullptr, ubc ? st->UBCInvMask : nullptr, rbc ? st->densityBC : nullptr, rbc ? st->densityBCInvMask : nullptr,
+                st->bc_class};
+}
+// The stage between the advection and the projection: U_adv, rho_adv (may be null) -> U, rho and, with `div`, the divergence of the
+// staged field (the staged value of a cell's +1 neighbours is re-derived in the same pass; their advected inputs must be valid)
+struct StageIO {
+  const float *U_adv, *rho_adv, *flags;
+  BcPtrs bc;
+  float *U, *rho, *div;
+};
+struct StageOps {
+  bool quirks;
+  bool first_bcs;              // false leaves out the setConstVals of simulate.py:96 (U_adv is a field that has been through it already)
+  bool buoy; float s[3];       // strengths gravity * dt
+  float rho_star;
+  bool grav; float g[3];       // forces gravity * dt
+  bool wall;
+  bool second_bcs;             // false leaves out the setConstVals of simulate.py:133
+  int div_k_end;               // 3D with div: the divergence is written for the planes [g.K0, div_k_end) of the staged range
+};
+void launch_pre_projection(const GridDims& g, bool is3d, const StageIO& io, const StageOps& ops, hipStream_t s);
 // periodic patches of the Jacobi branch (simulate.py:121-128, :157-164); `save`: periodic_save_bytes(g), mode 0 = save the
 // source row / column before the post-projection pass, 1 = write the destinations after it
 void launch_periodic_pre(const GridDims& g, bool is3d, const float* U_adv, const float* UBC, const float* UBCInvMask, float* U,
@@ -87,14 +103,11 @@ void launch_periodic_pre(const GridDims& g, bool is3d, const float* U_adv, const
 size_t periodic_save_bytes(const GridDims& g);
 void launch_periodic_post(const GridDims& g, bool is3d, float* U, float* save, const float* UBC, const float* UBCInvMask,
                           bool px, bool py, int mode, hipStream_t s);
-void launch_post_projection(const GridDims& g, bool is3d, const float* p, float* U, float* rho, const float* flags,
-                            const float* UBC, const float* UBCInvMask, const float* rhoBC, const float* rhoBCInvMask,
-                            hipStream_t s, const unsigned char* cls = nullptr, bool rho_bc_applied = false,
-                            const float* scale = nullptr, float* p_scaled = nullptr);
+void launch_post_projection(const GridDims& g, bool is3d, const float* p, float* U, float* rho, const float* flags, const BcPtrs& bc,
+                            hipStream_t s, bool rho_bc_applied = false, const float* scale = nullptr, float* p_scaled = nullptr);
 // scale (B device floats) / p_scaled: the tail of FluidNet.forward in the same pass (u = U / s into the update, u * s and
 // p_scaled = p * s out of it); p_scaled must not alias p (a cell reads p of its -1 neighbours)
-void launch_bc_classify(const GridDims& g, bool is3d, const float* UBC, const float* UBCInvMask, const float* rhoBC,
-                        const float* rhoBCInvMask, unsigned char* cls, hipStream_t s);
+void launch_bc_classify(const GridDims& g, bool is3d, const BcPtrs& bc, unsigned char* cls, hipStream_t s);
 
 // vorticity confinement (fnx_vorticity.hip): U_out = U_in + the confinement force of U_in scaled by amp; whole grids only (no
 // compute window, no z-slab view); U_out must not alias U_in

@@ -901,9 +901,7 @@ static int slab_step_body(FnxSlab* s, const FnxStepParams* prm, const FnxState* 
     // velocityUpdate on U / s, un-normalise, setWallBcs, the step's last setConstVals: one pass over the owned planes
     GridDims dw = dl;
     if (world > 1) { dw.K0 = lo; dw.KN = s->owned; }
-    const bool ubc = st->UBC && st->UBCInvMask, rbc = st->densityBC && st->densityBCInvMask;
-    fnx::launch_post_projection(dw, true, pn, st->U, st->density, st->flags, ubc ? st->UBC : nullptr, ubc ? st->UBCInvMask : nullptr,
-                                rbc ? st->densityBC : nullptr, rbc ? st->densityBCInvMask : nullptr, stream, state.bc_class, true, W.scale, st->p);
+    fnx::launch_post_projection(dw, true, pn, st->U, st->density, st->flags, fnx::bc_ptrs(&state), stream, true, W.scale, st->p);
     SLAB_HIP(hipGetLastError());
     return FNX_OK;
   }

@@ -427,61 +427,47 @@ inline dim3 cell_grid(const GridDims& g) { return dim3((g.W + BX - 1) / BX, (g.H
 
 namespace fnx {
 
-void launch_pre_projection(const GridDims& g, bool is3d, bool quirks, const float* U_adv, const float* rho_adv,
-                           const float* flags, const float* UBC, const float* UBCInvMask, const float* rhoBC,
-                           const float* rhoBCInvMask, float* U, float* rho, float* div, bool buoyancy, float sx,
-                           float sy, float sz, float rho_star, bool wall_bcs, hipStream_t s, const unsigned char* cls,
-                           const float* gravity, bool second_bcs, int div_k_end, bool first_bcs) {
-  StepPtrs P{U_adv, rho_adv, flags, UBC, UBCInvMask, rhoBC, rhoBCInvMask, U, rho, div, cls,
-             gravity ? 1 : 0, gravity ? gravity[0] : 0.f, gravity ? gravity[1] : 0.f, gravity ? gravity[2] : 0.f, second_bcs ? 1 : 0};
-  const dim3 grid = cell_grid(g), block(BX, BY);
-  if (!first_bcs) {
-    // the staged input has its buoyancy and gravity behind it (the caller passes neither; QUIRKS only concerns the buoyancy)
-    const int kd = div ? div_k_end : 0;
-    if (!is3d) {
-      if (wall_bcs) stage2d_div_kernel<true, false><<<grid, block, 0, s>>>(g, P, 0, 0.f, 0.f, rho_star);
-      else stage2d_div_kernel<false, false><<<grid, block, 0, s>>>(g, P, 0, 0.f, 0.f, rho_star);
-    } else if (div) {
-      if (wall_bcs) stage3d_kernel<false, true, true, false><<<grid, block, 0, s>>>(g, P, 0, 0.f, 0.f, 0.f, rho_star, kd);
-      else stage3d_kernel<false, false, true, false><<<grid, block, 0, s>>>(g, P, 0, 0.f, 0.f, 0.f, rho_star, kd);
-    } else {
-      if (wall_bcs) stage3d_kernel<false, true, false, false><<<grid, block, 0, s>>>(g, P, 0, 0.f, 0.f, 0.f, rho_star, kd);
-      else stage3d_kernel<false, false, false, false><<<grid, block, 0, s>>>(g, P, 0, 0.f, 0.f, 0.f, rho_star, kd);
-    }
-    return;
-  }
+namespace {
+// The instance of the stage kernel for a launch: 2D (WALL, BC1), 3D (QUIRKS, WALL, DIV, BC1).  Without the first setConstVals the input
+// has its buoyancy behind it, which is all QUIRKS concerns: those instances are the QUIRKS = false ones.
+using Stage2d = void (*)(GridDims, StepPtrs, int, float, float, float);
+using Stage3d = void (*)(GridDims, StepPtrs, int, float, float, float, float, int);
+struct StageKernel { Stage2d k2; Stage3d k3; };
+template <bool Q, bool BC1> Stage3d stage3d_of(bool wall, bool div) {
+  return wall ? (div ? stage3d_kernel<Q, true, true, BC1> : stage3d_kernel<Q, true, false, BC1>)
+              : (div ? stage3d_kernel<Q, false, true, BC1> : stage3d_kernel<Q, false, false, BC1>);
+}
+StageKernel stage_kernel(bool is3d, const StageOps& o, bool div) {
   if (!is3d) {
-    if (wall_bcs) stage2d_div_kernel<true><<<grid, block, 0, s>>>(g, P, buoyancy, sx, sy, rho_star);
-    else stage2d_div_kernel<false><<<grid, block, 0, s>>>(g, P, buoyancy, sx, sy, rho_star);
-    return;
+    return {o.first_bcs ? (o.wall ? stage2d_div_kernel<true, true> : stage2d_div_kernel<false, true>)
+                        : (o.wall ? stage2d_div_kernel<true, false> : stage2d_div_kernel<false, false>), nullptr};
   }
-  // 3D: `div` non-null: the fused form, divergence for the planes below div_k_end (the caller stages one plane more than it wants
-  // divergences of where there is one); null: staging only
-  const int kdiv = div ? div_k_end : 0;
-#define STAGE3D(Q, W_, D_) stage3d_kernel<Q, W_, D_><<<grid, block, 0, s>>>(g, P, buoyancy, sx, sy, sz, rho_star, kdiv)
-  if (div) {
-    if (quirks) { if (wall_bcs) STAGE3D(true, true, true); else STAGE3D(true, false, true); }
-    else        { if (wall_bcs) STAGE3D(false, true, true); else STAGE3D(false, false, true); }
-  } else {
-    if (quirks) { if (wall_bcs) STAGE3D(true, true, false); else STAGE3D(true, false, false); }
-    else        { if (wall_bcs) STAGE3D(false, true, false); else STAGE3D(false, false, false); }
-  }
-#undef STAGE3D
+  return {nullptr, !o.first_bcs ? stage3d_of<false, false>(o.wall, div) : o.quirks ? stage3d_of<true, true>(o.wall, div) : stage3d_of<false, true>(o.wall, div)};
+}
+}  // namespace
+
+void launch_pre_projection(const GridDims& g, bool is3d, const StageIO& io, const StageOps& o, hipStream_t s) {
+  const StepPtrs P{io.U_adv, io.rho_adv, io.flags, io.bc.UBC, io.bc.UBCInvMask, io.bc.rhoBC, io.bc.rhoBCInvMask, io.U, io.rho, io.div, io.bc.cls,
+                   o.grav ? 1 : 0, o.g[0], o.g[1], o.g[2], o.second_bcs ? 1 : 0};
+  const dim3 grid = cell_grid(g), block(BX, BY);
+  const StageKernel k = stage_kernel(is3d, o, io.div != nullptr);
+  auto launch = [&](auto kernel, auto... rest) { kernel<<<grid, block, 0, s>>>(g, P, o.buoy ? 1 : 0, o.s[0], o.s[1], rest...); };
+  // 3D with `div`: the fused form, divergence for the planes below div_k_end (the caller stages one plane more than it wants divergences
+  // of where there is one); without: staging only
+  if (is3d) launch(k.k3, o.s[2], o.rho_star, io.div ? o.div_k_end : 0);
+  else launch(k.k2, o.rho_star);
 }
 
-void launch_post_projection(const GridDims& g, bool is3d, const float* p, float* U, float* rho, const float* flags,
-                            const float* UBC, const float* UBCInvMask, const float* rhoBC, const float* rhoBCInvMask,
-                            hipStream_t s, const unsigned char* cls, bool rho_bc_applied, const float* scale, float* p_scaled) {
+void launch_post_projection(const GridDims& g, bool is3d, const float* p, float* U, float* rho, const float* flags, const BcPtrs& bc,
+                            hipStream_t s, bool rho_bc_applied, const float* scale, float* p_scaled) {
   const dim3 grid = cell_grid(g), block(BX, BY);
-  const int rd = (cls && rho_bc_applied) ? 1 : 0;
+  const int rd = (bc.cls && rho_bc_applied) ? 1 : 0;
   // (the scaled form is its own instantiation: as a run-time branch it cost the Jacobi step's pass 124 -> 163 us at 512x512x64)
-  if (scale && p_scaled) {
-    if (is3d) post_projection_kernel<true, true><<<grid, block, 0, s>>>(g, p, U, rho, flags, UBC, UBCInvMask, rhoBC, rhoBCInvMask, cls, rd, scale, p_scaled);
-    else post_projection_kernel<false, true><<<grid, block, 0, s>>>(g, p, U, rho, flags, UBC, UBCInvMask, rhoBC, rhoBCInvMask, cls, rd, scale, p_scaled);
-  } else {
-    if (is3d) post_projection_kernel<true, false><<<grid, block, 0, s>>>(g, p, U, rho, flags, UBC, UBCInvMask, rhoBC, rhoBCInvMask, cls, rd, nullptr, nullptr);
-    else post_projection_kernel<false, false><<<grid, block, 0, s>>>(g, p, U, rho, flags, UBC, UBCInvMask, rhoBC, rhoBCInvMask, cls, rd, nullptr, nullptr);
-  }
+  const bool scaled = scale && p_scaled;
+  auto k = scaled ? (is3d ? post_projection_kernel<true, true> : post_projection_kernel<false, true>)
+                  : (is3d ? post_projection_kernel<true, false> : post_projection_kernel<false, false>);
+  k<<<grid, block, 0, s>>>(g, p, U, rho, flags, bc.UBC, bc.UBCInvMask, bc.rhoBC, bc.rhoBCInvMask, bc.cls, rd, scaled ? scale : nullptr,
+                           scaled ? p_scaled : nullptr);
 }
 
 void launch_periodic_pre(const GridDims& g, bool is3d, const float* U_adv, const float* UBC, const float* UBCInvMask, float* U,
@@ -498,12 +484,11 @@ void launch_periodic_post(const GridDims& g, bool is3d, float* U, float* save, c
   periodic_post_kernel<<<grid, 256, 0, s>>>(g, is3d ? 3 : 2, U, save, UBC, UBCInvMask, px, py, mode);
 }
 
-void launch_bc_classify(const GridDims& g, bool is3d, const float* UBC, const float* UBCInvMask, const float* rhoBC,
-                        const float* rhoBCInvMask, unsigned char* cls, hipStream_t s) {
+void launch_bc_classify(const GridDims& g, bool is3d, const BcPtrs& bc, unsigned char* cls, hipStream_t s) {
   const size_t n = (size_t)g.B * g.DHW;
   size_t blocks = (n + 255) / 256;
   if (blocks > 8192) blocks = 8192;
-  bc_classify_kernel<<<(unsigned)blocks, 256, 0, s>>>(n, (size_t)g.DHW, is3d ? 3 : 2, UBC, UBCInvMask, rhoBC, rhoBCInvMask, cls);
+  bc_classify_kernel<<<(unsigned)blocks, 256, 0, s>>>(n, (size_t)g.DHW, is3d ? 3 : 2, bc.UBC, bc.UBCInvMask, bc.rhoBC, bc.rhoBCInvMask, cls);
 }
 
 }  // namespace fnx
