@@ -2,7 +2,8 @@
 """The reference's `pytorch/plume.py` main loop on this backend -- what a driver looks like after the switch.
 
     python examples/plume.py [--res 128] [--iters 200] [--out-iter 50] [--method jacobi|pcg|convnet|hybrid] [--weights CKPT]
-                             [--pcg-warm] [--vorticity AMP] [--depth N] [--weights3d CKPT] [--render] [--folder out] [--restart]
+                             [--pcg-warm] [--vorticity AMP] [--depth N] [--weights3d CKPT] [--render] [--dyes N] [--folder out]
+                             [--restart]
 
 Same structure as the reference driver (plume.py:66-178 setup, :231-424 loop): build the batch, `createPlumeBCs`, optional
 restart from `<folder>/restart.pth`, echo the configuration as YAML, then `simulate()` per iteration and, every `out-iter`
@@ -12,7 +13,9 @@ writes ({'state_dict', 'mconf', ...}), loaded the way the reference driver loads
 `--depth N` (N > 1) runs the 3D plume on a N x res x res grid (jacobi, pcg and --vorticity as in 2D); there `--method convnet` takes
 `--weights3d CKPT`, a checkpoint of `examples/train.py --depth N` (the 3D net; a 2D checkpoint given by --weights is refused).  `--render` adds volume renderings of the density (output.save_render: from the front, lit from above, and from the side)
 to every output event.  `--method hybrid` takes the same checkpoints as convnet and projects with the converged solve started from the
-net's pressure; `--pcg-warm` starts the 'pcg' solve from the previous step's pressure (mconf['pcgWarmStart'])."""
+net's pressure; `--dyes N` (1..3) carries N passive dyes along (batch_dict['scalars'], fluid.advectScalars: all of them through one pair
+of line traces): the inlet is cut into N equal sectors along x and dye n enters through sector n at concentration 1, so the output
+event's scalars_<it>.png shows in red, green and blue where each sector's fluid goes; `--pcg-warm` starts the 'pcg' solve from the previous step's pressure (mconf['pcgWarmStart'])."""
 import argparse
 import os
 import sys
@@ -41,6 +44,8 @@ def parser():
                     help="checkpoint of examples/train.py --depth N (needed by --method convnet and hybrid with --depth > 1)")
     ap.add_argument("--depth", type=int, default=1, metavar="N", help="cells along z; 1 (default) is the 2D plume, N > 1 the 3D one")
     ap.add_argument("--render", action="store_true", help="write volume renderings (render_<view>_<it>.png) with every output event")
+    ap.add_argument("--dyes", type=int, default=None, metavar="N",
+                    help="carry N passive dyes (1..3), one per sector of the inlet along x (batch_dict['scalars']); default: none")
     ap.add_argument("--folder", default="plume_out")
     ap.add_argument("--restart", action="store_true")
     return ap
@@ -52,6 +57,8 @@ def parse_args(argv=None):
     uses_net = a.method in ("convnet", "hybrid")
     if a.pcg_warm and a.method != "pcg":
         ap.error("--pcg-warm is only read by --method pcg")
+    if a.dyes is not None and not 1 <= a.dyes <= 3:
+        ap.error("--dyes must be 1, 2 or 3 (the channels of scalars_<it>.png)")
     if a.depth < 1 or a.depth == 2:
         ap.error("--depth must be 1 (2D) or at least 3")
     if a.depth > 1:
@@ -69,6 +76,22 @@ def parse_args(argv=None):
     if uses_net != (a.weights is not None):
         ap.error(f"--method {a.method if uses_net else 'convnet'} needs --weights CKPT, and --weights is only read by --method convnet and hybrid")
     return a
+
+
+def add_dyes(batch_dict, n):
+    """n dyes on a batch createPlumeBCs has been through: scalars = 0, and channel c enters at concentration 1 through sector c of
+    the inlet (n equal sectors along x of the cells where densityBC is set), under the density's mask"""
+    dbc, mask = batch_dict["densityBC"], batch_dict["densityBCInvMask"]
+    inlet = dbc[0, 0] != 0                                                # (D, H, W)
+    xs = torch.nonzero(inlet.any(0).any(0)).flatten()
+    x0, width = int(xs.min()), int(xs.max()) - int(xs.min()) + 1
+    sector = ((torch.arange(dbc.size(4), device=dbc.device) - x0) * n).div(width, rounding_mode="floor")   # (W,)
+    bc = torch.zeros((1, n) + tuple(dbc.shape[2:]), dtype=dbc.dtype, device=dbc.device)
+    for c in range(n):
+        bc[0, c] = (inlet & (sector == c)).to(dbc.dtype)
+    batch_dict["scalars"] = torch.zeros_like(bc)
+    batch_dict["scalarsBC"] = bc
+    batch_dict["scalarsBCInvMask"] = mask.expand_as(bc).contiguous()
 
 
 def main(argv=None):
@@ -109,6 +132,8 @@ def main(argv=None):
         assert os.path.isfile(restart_file), "Restart file does not exists."
         batch_dict, it = load_restart(restart_file, cuda)
         print("Restarting from checkpoint at it = " + str(it))
+    if a.dyes and "scalars" not in batch_dict:
+        add_dyes(batch_dict, a.dyes)
     output.echo_config(os.path.join(a.folder, "plumeConfig.yaml"), simConf)      # plume.py:176-178
     while it < a.iters:                                   # plume.py:231-424
         simulate(simConf, batch_dict, net, a.method)

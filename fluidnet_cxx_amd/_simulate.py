@@ -32,6 +32,21 @@ sim_method 'hybrid' is 'pcg' started from the net's pressure: p0, _ = net(cat(p,
 net's velocity is discarded), then solveLinearSystemPCG(..., p0=p0) to pcgTol / pcgIter -- the net's speed-up with a checked residual.
 mconf['vorticityConfinementAmp'] > 0 (no reference key either) adds fluid.addVorticityConfinement with that amplitude after
 addGravity and before setWallBcs, for every method; whole grids only (a compute window or z-slab `geom` raises).
+batch_dict['scalars'] (no reference key; (B,C,D,H,W) fp32, C >= 1): passive scalars carried along with the step -- a second smoke
+source, a dye, a temperature to look at.  They do not act on the flow.  At the top of the call, while U is still the old velocity (the
+one the density is advected by), on the fused and the operator path alike:
+  s = fluid.advectScalars(dt, scalars, U, flags) with the step's maccormackStrength and sampleOutsideFluid -- all channels through one
+      pair of line traces, each with the bits advectScalar gives the density;
+  mconf['correctScalar']: every channel gets the density's correction with the divergence of the old U;
+  'scalarsBC' and 'scalarsBCInvMask' present ((B,C,D,H,W)): s = s * scalarsBCInvMask + scalarsBC, two roundings, once.  The density
+      gets its setConstVals three times a step; for masks of 0 / 1 with scalarsBC == 0 wherever the mask is 1 -- what the drivers
+      build -- one application gives the same bits as three (x*1 + 0 and x*0 + bc are fixed points of a second and a third one);
+  batch_dict['scalars'] = s.
+A channel that starts as a copy of the density with the density's BC arrays stays the density, bit for bit.  No 'density' key is needed,
+and output_div=True runs the stage too.  The stage enqueues only, so a step with it stays capturable in a HIP graph; it is out of place,
+so such a graph reads the tensor the key held at capture time and writes the one it holds afterwards (copy one into the other between
+replays).  Whole single
+domains only: with a compute window or z-slab `geom` and the key present the call raises.
 `geom` (an `ext.Geom`, 3D only) selects the reference-quirk mode / a z-slab view for this call; it is per call, the
 extension keeps no state.
 """
@@ -138,6 +153,25 @@ def release_workspaces():
     _AUTO.clear()
 
 
+def _is_view(geom):
+    return geom is not None and (geom.k_begin != 0 or geom.k_end != 0 or geom.z_offset != 0 or geom.D_global != 0)
+
+
+def _scalars_stage(mconf, batch_dict, dt, U, flags, geom):
+    """the passive scalars of batch_dict['scalars'] by the old U (module docstring)"""
+    if _is_view(geom):
+        raise ValueError("simulate(): batch_dict['scalars'] is single-domain only (no compute window or z-slab view through geom)")
+    s = fluid.advectScalars(dt, batch_dict["scalars"], U, flags, method="maccormackFluidNet", boundary_width=1,
+                            sample_outside_fluid=mconf["sampleOutsideFluid"], maccormack_strength=mconf["maccormackStrength"], geom=geom)
+    if mconf.get("correctScalar", False):
+        div = fluid.velocityDivergence(U, flags, geom=geom)
+        for c in range(s.size(1)):                              # (the operator takes one field; a channel view is copied in and out)
+            fluid.correctScalar(dt, s[:, c:c + 1], div, flags)
+    if "scalarsBC" in batch_dict and "scalarsBCInvMask" in batch_dict:
+        s = s * batch_dict["scalarsBCInvMask"] + batch_dict["scalarsBC"]
+    batch_dict["scalars"] = s
+
+
 def simulate(mconf, batch_dict, net, sim_method, output_div=False, fused=True, workspace=None, static_flags=None,
              geom=None):
     assert sim_method in ("convnet", "jacobi", "pcg", "hybrid"), "Simulation method not supported. Choose convnet, jacobi, pcg or hybrid."
@@ -156,6 +190,8 @@ def simulate(mconf, batch_dict, net, sim_method, output_div=False, fused=True, w
     has_density = "density" in batch_dict
 
     is3D = U.size(1) == 3
+    if "scalars" in batch_dict:                                 # before anything writes U: the scalars go by the old velocity
+        _scalars_stage(mconf, batch_dict, dt, U, flags, geom)
     # the optional stages (viscosity, gravityScale, correctScalar, the periodic patches, flags_stick) are branches of the
     # native step (FnxStepParams / FnxState); what stays on the operator path: output_div (a training-time early return),
     # the stages the reference only has in 2D asked for in 3D (they raise there, as the operators do), and

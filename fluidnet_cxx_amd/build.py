@@ -21,6 +21,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 HIP_UNITS = {
     "fnx_stencils.hip": ["-ffp-contract=off"],
     "fnx_advect.hip": ["-ffp-contract=off", "-Rpass-analysis=kernel-resource-usage"],
+    "fnx_scalars.hip": ["-ffp-contract=off", "-Rpass-analysis=kernel-resource-usage"],
     "fnx_jacobi.hip": ["-ffp-contract=off"],
     "fnx_pcg.hip": ["-Rpass-analysis=kernel-resource-usage"],
     "fnx_step.hip": ["-ffp-contract=off"],
@@ -46,6 +47,9 @@ SCRATCH_FREE = {
                         "advect3d_bwd_vel_tile_kernel"],
                        "fnx_advect_march.h: the 3D advection marches run at 2-3 waves per SIMD with every VGPR in use; a reload from "
                        "scratch is an s_waitcnt vmcnt(0) that also waits for the plane in flight and the stores"),
+    "fnx_scalars.hip": (["advect_scalars_fwd_kernel", "advect_scalars_box_kernel", "advect_scalars_bwd_kernel"],
+                        "one thread per cell with a chunk of four channels' interpolation corners in registers; scratch there would mean "
+                        "a per-channel array was indexed at run time, or the line trace's state was pushed out by the chunk"),
     "fnx_pcg.hip": (["pcg_guess_kernel"],
                     "a streaming kernel like pcg_dir_apply_kernel: a cell's stencil, seven loads and three fp64 partial sums; scratch there "
                     "would mean the partial sums or the stencil were turned into arrays in memory"),

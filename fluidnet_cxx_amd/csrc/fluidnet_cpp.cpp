@@ -118,6 +118,35 @@ Tensor advect_scalar(float dt, Tensor src, Tensor U, Tensor flags, const std::st
   return dst;
 }
 
+// passive scalars (fnx_advect_scalars): src (B, C, D, H, W), C >= 1, all channels through one pair of line traces; returns a new tensor.
+// `workspace`: a uint8 tensor of at least advect_scalars_workspace_bytes, or None (then it comes from the caching allocator).
+Tensor advect_scalars(float dt, Tensor src, Tensor U, Tensor flags, const std::string method, int bnd,
+                      const bool sample_outside_fluid, const float maccormack_strength, c10::optional<Tensor> workspace,
+                      const Geom* geom, c10::optional<Tensor> out) {
+  check_field(U, "U");
+  FnxGrid g = grid_of(flags, U.size(1) == 3, geom);
+  check_vel(U, g, "U"); check_field(src, "src");
+  TORCH_CHECK(src.size(1) >= 1, "src has no channel");
+  TORCH_CHECK(src.size(0) == g.B && src.size(2) == g.D && src.size(3) == g.H && src.size(4) == g.W, "Size mismatch");
+  const int C = (int)src.size(1);
+  c10::hip::HIPGuard guard(flags.get_device());
+  Tensor dst = out_or_like(out, src);
+  check_field(dst, "out");
+  TORCH_CHECK(dst.sizes() == src.sizes(), "Size mismatch");
+  Tensor ws;
+  if (workspace.has_value() && workspace->defined()) {
+    ws = *workspace;
+    TORCH_CHECK(ws.is_cuda() && ws.scalar_type() == at::kByte && ws.is_contiguous(), "workspace must be a contiguous uint8 GPU tensor");
+  } else {
+    const size_t bytes = fnx_advect_scalars_workspace_bytes(&g, C);
+    ws = at::empty({(int64_t)(bytes ? bytes : 1)}, src.options().dtype(at::kByte));
+  }
+  check_status(fnx_advect_scalars(&g, dt, C, src.data_ptr<float>(), U.data_ptr<float>(), flags.data_ptr<float>(), dst.data_ptr<float>(),
+                                  method_of(method), bnd, sample_outside_fluid, maccormack_strength, ws.data_ptr(), (size_t)ws.numel(),
+                                  cur_stream(src)));
+  return dst;
+}
+
 Tensor advect_vel(float dt, Tensor orig, Tensor U, Tensor flags, const std::string method, int bnd,
                   const float maccormack_strength, c10::optional<Tensor> out, const Geom* geom, const std::string& plan) {
   check_field(U, "U");
@@ -1076,6 +1105,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("advect_scalar", &advect_scalar, "Advect Scalar", py::arg("dt"), py::arg("src"), py::arg("U"), py::arg("flags"),
         py::arg("method"), py::arg("boundary_width"), py::arg("sample_outside_fluid"), py::arg("maccormack_strength"),
         py::arg("out") = py::none(), GEOM, py::arg("plan") = "auto", NoGil());
+  m.def("advect_scalars", &advect_scalars, "Advect C passive scalars through one pair of line traces", py::arg("dt"), py::arg("src"),
+        py::arg("U"), py::arg("flags"), py::arg("method"), py::arg("boundary_width"), py::arg("sample_outside_fluid"),
+        py::arg("maccormack_strength"), py::arg("workspace") = py::none(), GEOM, py::arg("out") = py::none(), NoGil());
+  m.def("advect_scalars_workspace_bytes", [](int B, int D, int H, int W, bool is3D, int channels) {
+          FnxGrid g{}; g.B = B; g.D = D; g.H = H; g.W = W; g.is3D = is3D ? 1 : 0;
+          return fnx_advect_scalars_workspace_bytes(&g, channels);
+        }, py::arg("B"), py::arg("D"), py::arg("H"), py::arg("W"), py::arg("is3D"), py::arg("channels"));
   m.def("advect_step", &advect_step, py::arg("dt"), py::arg("density"), py::arg("U"), py::arg("flags"),
         py::arg("sample_outside_fluid"), py::arg("maccormack_strength"), py::arg("out_density") = py::none(),
         py::arg("out_U") = py::none(), GEOM, py::arg("plan") = "auto", NoGil());

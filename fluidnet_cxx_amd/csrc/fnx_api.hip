@@ -313,6 +313,44 @@ int fnx_advect_step_plan(const FnxGrid* g, float dt, const float* density, const
   return advect_run("advect_step", g, fnx::ADVECT_BOTH, FNX_ADVECT_MACCORMACK, plan, a, ws, ws_bytes, stream);
 }
 
+// passive scalars (fnx_scalars.hip): every refusal comes before a pointer is read
+static int check_scalars_grid(const FnxGrid* g, int channels) {
+  if (int rc = check_grid(g)) return rc;
+  if (channels < 1) return fail(FNX_EINVAL, "advect_scalars: channels < 1 (%d)", channels);
+  if (is_view(g)) return fail(FNX_EINVAL, "advect_scalars: no compute window or z-slab view (single-domain only)");
+  if ((g->H + 3) / 4 > 65535) return fail(FNX_EINVAL, "advect_scalars: H/4 > 65535 not supported");
+  // the 3D clamp-bounds launch carries the channels in its grid's z extent
+  if (g->is3D && (long long)g->B * channels * fnx::advect_scalars_box_chunks(dims(g)) > 65535)
+    return fail(FNX_EINVAL, "advect_scalars: B*channels*ceil(D/16) > 65535 not supported");
+  return FNX_OK;
+}
+
+size_t fnx_advect_scalars_workspace_bytes(const FnxGrid* g, int channels) {
+  if (check_scalars_grid(g, channels) != FNX_OK) return 0;
+  return fnx::advect_scalars_workspace(dims(g), g->is3D != 0, channels, nullptr).bytes;
+}
+
+int fnx_advect_scalars(const FnxGrid* g, float dt, int channels, const float* src, const float* U, const float* flags, float* dst,
+                       int method, int bnd, int sample_outside, float strength, void* ws, size_t ws_bytes, void* stream) {
+  if (int rc = check_scalars_grid(g, channels)) return rc;
+  if (!src || !U || !flags || !dst) return fail(FNX_EINVAL, "advect_scalars: NULL tensor");
+  if (dst == src) return fail(FNX_EINVAL, "advect_scalars: dst must not alias src");
+  if (method != FNX_ADVECT_EULER && method != FNX_ADVECT_MACCORMACK) return fail(FNX_EMETHOD, "Advection method not supported");
+  if (bnd != 1) return fail(FNX_EINVAL, "advect_scalars: only boundary_width == 1 is supported (the reference's MAC sampling strips exactly one border cell)");
+  const bool mac = method == FNX_ADVECT_MACCORMACK;
+  fnx::AdvectScalarsWs w{};
+  if (mac) {                                             // Euler writes dst directly and takes no workspace
+    w = fnx::advect_scalars_workspace(dims(g), g->is3D != 0, channels, ws);
+    if (!ws || w.bytes > ws_bytes) return fail(FNX_EWORKSPACE, "advect_scalars: workspace too small (%zu < %zu)", ws ? ws_bytes : (size_t)0, w.bytes);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  fnx::ProfScope ps(FNX_PROF_ADVECT, s);
+  fnx::launch_advect_scalars(dims(g), g->is3D != 0, quirks(g), mac, sample_outside != 0, dt, strength * 0.5f, channels, src, U, flags, dst,
+                             w, s);
+  HIP_OK(hipGetLastError());
+  return FNX_OK;
+}
+
 int fnx_velocity_divergence(const FnxGrid* g, const float* U, const float* flags, float* div, void* stream) {
   if (int rc = check_grid(g)) return rc;
   if (!U || !flags || !div) return fail(FNX_EINVAL, "velocity_divergence: NULL tensor");

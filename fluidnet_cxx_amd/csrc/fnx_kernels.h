@@ -45,6 +45,17 @@ struct AdvectArgs {
 };
 void launch_advect(const AdvectPlan& p, const AdvectArgs& a, const AdvectWs& ws, hipStream_t s);
 
+// passive scalars (fnx_scalars.hip): `channels` fields (B, C, D, H, W) through one pair of line traces, one thread per cell, whole
+// single domains only.  Workspace of a MacCormack call: the C forward fields, the traced cell, in 3D the C clamp-bounds fields; each
+// rounded up to 256 bytes (base == nullptr: the size only).  Euler writes dst directly and takes none.
+struct AdvectScalarsWs { float* fwd; int* cell; float2* box; size_t bytes; };
+AdvectScalarsWs advect_scalars_workspace(const GridDims& g, bool is3d, int channels, void* base);
+// z chunks of the 3D clamp-bounds launch: its grid's z extent is B * channels * this
+inline int advect_scalars_box_chunks(const GridDims& g) { return (g.D + 15) / 16; }
+void launch_advect_scalars(const GridDims& g, bool is3d, bool quirks, bool maccormack, bool sample_outside, float dt, float half_s,
+                           int channels, const float* src, const float* U, const float* flags, float* dst, const AdvectScalarsWs& w,
+                           hipStream_t s);
+
 // stencils (fnx_stencils.hip)
 void launch_divergence(const GridDims& g, bool is3d, const float* U, const float* flags, float* div, hipStream_t s);
 void launch_velocity_update(const GridDims& g, bool is3d, const float* p, float* U, const float* flags, hipStream_t s);

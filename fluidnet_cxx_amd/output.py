@@ -45,7 +45,8 @@ def _centered_gradient(field):
 def vtk_cell_data(batch_dict, window=None):
     """The cell arrays of the reference's VTK dump (plume.py:331-408) for sample 0, as a dict of float32 numpy arrays
     shaped (nx, ny, nz) -- x first, as gridToVTK wants them: density, divergence, pressure, ux, uy[, uz], gradPx, gradPy[, gradPz],
-    gradRhox, gradRhoy[, gradRhoz].  Pressure and velocity are NaN inside obstacles.  `window` = (minX, maxX, minY, maxY)
+    gradRhox, gradRhoy[, gradRhoz] and, with batch_dict['scalars'] (B,C,D,H,W), scalar0 .. scalar{C-1}.  Pressure and velocity are NaN
+    inside obstacles.  `window` = (minX, maxX, minY, maxY)
     in cells (default: the whole domain)."""
     U, flags, p, rho = batch_dict["U"], batch_dict["flags"], batch_dict["p"], batch_dict["density"]
     is3d = U.size(1) == 3
@@ -69,6 +70,9 @@ def vtk_cell_data(batch_dict, window=None):
         out["u" + name] = host(vel[0, c], True)
         out["gradP" + name] = host(grad_p[0, c])
         out["gradRho" + name] = host(grad_rho[0, c])
+    if "scalars" in batch_dict:
+        for c in range(batch_dict["scalars"].size(1)):
+            out["scalar%d" % c] = host(batch_dict["scalars"][0, c])
     return out
 
 
@@ -248,13 +252,38 @@ def save_render(folder, it, batch_dict, views=(("-z", "-y"),), **kw):
             for view, light in views]
 
 
+def scalars_image(batch_dict, window=None, plane=None):
+    """batch_dict['scalars'] of sample 0 as (H,W,3) uint8: the first three channels as red, green and blue clipped to [0, 1] (missing
+    channels 0), obstacles grey, z plane `plane` (default: the middle one), row 0 at the bottom like `colorize`."""
+    s, flags = batch_dict["scalars"], batch_dict["flags"]
+    d, h, w = flags.shape[2:]
+    k = d // 2 if plane is None else plane
+    minX, maxX, minY, maxY = window if window is not None else (0, w, 0, h)
+    a = s[0, 0:3, k, minY:maxY, minX:maxX].float().cpu().numpy()
+    rgb = np.zeros((a.shape[1], a.shape[2], 3), np.float32)
+    rgb[:, :, :a.shape[0]] = np.moveaxis(np.clip(np.nan_to_num(a, nan=0.0), 0.0, 1.0), 0, -1)
+    img = (rgb * 255.0 + 0.5).astype(np.uint8)
+    obst = (flags[0, 0, k, minY:maxY, minX:maxX] == float(fluid.CellType.TypeObstacle)).cpu().numpy()
+    img[obst] = 128
+    return np.ascontiguousarray(img[::-1])
+
+
+def save_scalars_png(folder, it, batch_dict, window=None, plane=None):
+    """`<folder>/scalars_<it:05>.png`: `scalars_image`"""
+    return write_png(os.path.join(folder, "scalars_{0:05}.png".format(it)), scalars_image(batch_dict, window, plane))
+
+
 def save_state(folder, it, batch_dict, window=None, vtk=True, png=True, restart=True, render=None):
     """One output event of the driver loop (plume.py:238-424): PNG, VTK and the restart file.  `render`: (view, light) pairs for
-    `save_render` (default: no rendering, and the files and the returned list are what they were without the keyword)."""
+    `save_render` (default: no rendering, and the files and the returned list are what they were without the keyword).  With
+    batch_dict['scalars'] the PNG event also writes `scalars_<it:05>.png` (`scalars_image`) and the VTK file has scalar0..; without the
+    key, files and return value are what they were."""
     from .state_io import save_restart
     files = []
     if png:
         files.append(save_png(folder, it, batch_dict, window))
+        if "scalars" in batch_dict:
+            files.append(save_scalars_png(folder, it, batch_dict, window))
     if vtk:
         files.append(save_vtk(folder, it, batch_dict, window))
     if render:

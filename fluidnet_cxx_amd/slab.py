@@ -29,6 +29,12 @@ def _refuse_vorticity(mconf):
         raise ValueError("the z-slab drivers do not run vorticity confinement (mconf['vorticityConfinementAmp'] > 0 is single-domain only)")
 
 
+def _refuse_scalars(st):
+    # fnx_advect_scalars takes whole domains only (no compute window, no z-slab view)
+    if "scalars" in st:
+        raise ValueError("the z-slab drivers do not carry passive scalars (batch_dict['scalars'] is single-domain only)")
+
+
 class SlabLayout:
     """Index arithmetic of one rank's slab."""
 
@@ -791,6 +797,7 @@ class SlabSimulator:
 
     def step(self, st):
         import contextlib
+        _refuse_scalars(st)
         handle = None
 
         def on(stream):      # a request may name the stream it is served on (deep_beside: the edge stream posts and waits)
@@ -855,6 +862,7 @@ class NativeSlabSimulator:
         return self._drv
 
     def step(self, st):
+        _refuse_scalars(st)
         assert "density" in st, "the z-slab driver advects a density field (simulate() without one is single-domain only)"
         cfg = self.cfg
         gv = cfg["gravityVec"]

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define FNX_ABI_VERSION 27
+#define FNX_ABI_VERSION 28
 
 enum {
   FNX_OK = 0,
@@ -113,6 +113,18 @@ int fnx_advect_scalar_plan(const FnxGrid* g, float dt, const float* src, const f
 int fnx_advect_vel_plan(const FnxGrid* g, float dt, const float* orig, const float* U, const float* flags,
                         float* dst, int method, int bnd, float maccormack_strength, int plan,
                         void* ws, size_t ws_bytes, void* stream);
+
+/* Passive scalar transport (ABI 28; no reference counterpart): `channels` fields, src and dst (B, channels, D, H, W) contiguous, advected
+ * by U through ONE forward and ONE backward line trace -- the trace, the interpolation weights, the corners' fluid bits and the clamp
+ * neighbourhood's validity depend on U, flags and dt alone.  Channel c of dst has the bits fnx_advect_scalar gives for channel c alone
+ * (any plan), so a caller may mix the two freely.  One thread per cell; no atomics.  Whole single domains only: a compute window or a
+ * z-slab view is FNX_EINVAL ("single-domain only"); ref_quirks is honoured.  dst must not alias src; channels >= 1; bnd == 1.
+ * Workspace (MacCormack; Euler takes none): channels forward fields, one traced-cell field and, in 3D, channels clamp-bounds fields
+ * (8 bytes a cell); 3D also needs B * channels * ceil(D/16) <= 65535. */
+size_t fnx_advect_scalars_workspace_bytes(const FnxGrid* g, int channels);
+int fnx_advect_scalars(const FnxGrid* g, float dt, int channels, const float* src, const float* U, const float* flags,
+                       float* dst, int method, int bnd, int sample_outside_fluid, float maccormack_strength,
+                       void* ws, size_t ws_bytes, void* stream);
 
 /* velocityDivergence, lib/fluid/velocity_divergence.py:4-74 */
 int fnx_velocity_divergence(const FnxGrid* g, const float* U, const float* flags, float* div, void* stream);
