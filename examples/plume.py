@@ -2,8 +2,8 @@
 """The reference's `pytorch/plume.py` main loop on this backend -- what a driver looks like after the switch.
 
     python examples/plume.py [--res 128] [--iters 200] [--out-iter 50] [--method jacobi|pcg|convnet|hybrid] [--weights CKPT]
-                             [--pcg-warm] [--vorticity AMP] [--depth N] [--weights3d CKPT] [--render] [--dyes N] [--folder out]
-                             [--restart]
+                             [--pcg-warm] [--vorticity AMP] [--viscosity NU] [--depth N] [--weights3d CKPT] [--render] [--dyes N]
+                             [--folder out] [--restart]
 
 Same structure as the reference driver (plume.py:66-178 setup, :231-424 loop): build the batch, `createPlumeBCs`, optional
 restart from `<folder>/restart.pth`, echo the configuration as YAML, then `simulate()` per iteration and, every `out-iter`
@@ -15,7 +15,10 @@ writes ({'state_dict', 'mconf', ...}), loaded the way the reference driver loads
 to every output event.  `--method hybrid` takes the same checkpoints as convnet and projects with the converged solve started from the
 net's pressure; `--dyes N` (1..3) carries N passive dyes along (batch_dict['scalars'], fluid.advectScalars: all of them through one pair
 of line traces): the inlet is cut into N equal sectors along x and dye n enters through sector n at concentration 1, so the output
-event's scalars_<it>.png shows in red, green and blue where each sector's fluid goes; `--pcg-warm` starts the 'pcg' solve from the previous step's pressure (mconf['pcgWarmStart'])."""
+event's scalars_<it>.png shows in red, green and blue where each sector's fluid goes; `--pcg-warm` starts the 'pcg' solve from the previous step's pressure (mconf['pcgWarmStart']).
+`--viscosity NU` sets mconf['viscosity'] (the velocity advected is fluid.addViscosity of U) for any --depth; the explicit update is
+stable for NU * dt <= 1/4 in 2D and <= 1/6 in 3D (dt is 0.1 here).  The native step has no 3D viscous stage, so with --depth > 1 the
+viscous step runs operator by operator (simulate(..., fused=False))."""
 import argparse
 import os
 import sys
@@ -40,6 +43,9 @@ def parser():
                     help="--method pcg: start each solve from the previous step's pressure (mconf['pcgWarmStart'])")
     ap.add_argument("--vorticity", type=float, default=0.0, metavar="AMP",
                     help="vorticity confinement amplitude (mconf['vorticityConfinementAmp'], no reference key; 0 = off)")
+    ap.add_argument("--viscosity", type=float, default=0.0, metavar="NU",
+                    help="kinematic viscosity (mconf['viscosity'], 2D and 3D; 0 = off).  The explicit update is stable for "
+                         "NU * dt <= 1/6 in 3D and <= 1/4 in 2D (dt = 0.1); nothing checks it")
     ap.add_argument("--weights3d", default=None, metavar="CKPT",
                     help="checkpoint of examples/train.py --depth N (needed by --method convnet and hybrid with --depth > 1)")
     ap.add_argument("--depth", type=int, default=1, metavar="N", help="cells along z; 1 (default) is the 2D plume, N > 1 the 3D one")
@@ -57,6 +63,8 @@ def parse_args(argv=None):
     uses_net = a.method in ("convnet", "hybrid")
     if a.pcg_warm and a.method != "pcg":
         ap.error("--pcg-warm is only read by --method pcg")
+    if a.viscosity < 0:
+        ap.error("--viscosity must not be negative")
     if a.dyes is not None and not 1 <= a.dyes <= 3:
         ap.error("--dyes must be 1, 2 or 3 (the channels of scalars_<it>.png)")
     if a.depth < 1 or a.depth == 2:
@@ -105,6 +113,8 @@ def main(argv=None):
         simConf.update(pcgTol=1e-5, pcgIter=50, pcgWarmStart=bool(a.pcg_warm))
     if a.vorticity > 0:                                   # puts back the small-scale rotation the advection smooths away
         simConf.update(vorticityConfinementAmp=a.vorticity)
+    if a.viscosity > 0:                                   # simulate.py:66-69: the velocity advected is addViscosity(U)
+        simConf.update(viscosity=a.viscosity)
     net = None
     if a.method in ("convnet", "hybrid"):                 # plume.py:119-123
         state = torch.load(a.weights3d if a.depth > 1 else a.weights, map_location="cpu", weights_only=False)
@@ -136,7 +146,8 @@ def main(argv=None):
         add_dyes(batch_dict, a.dyes)
     output.echo_config(os.path.join(a.folder, "plumeConfig.yaml"), simConf)      # plume.py:176-178
     while it < a.iters:                                   # plume.py:231-424
-        simulate(simConf, batch_dict, net, a.method)
+        # (the native step has no 3D viscous stage: that one step runs operator by operator)
+        simulate(simConf, batch_dict, net, a.method, fused=not (a.depth > 1 and a.viscosity > 0))
         if it % a.out_iter == 0:
             print("It = " + str(it))
             output.save_state(a.folder, it, batch_dict, render=RENDER_VIEWS if a.render else None)

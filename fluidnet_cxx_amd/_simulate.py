@@ -32,6 +32,10 @@ sim_method 'hybrid' is 'pcg' started from the net's pressure: p0, _ = net(cat(p,
 net's velocity is discarded), then solveLinearSystemPCG(..., p0=p0) to pcgTol / pcgIter -- the net's speed-up with a checked residual.
 mconf['vorticityConfinementAmp'] > 0 (no reference key either) adds fluid.addVorticityConfinement with that amplitude after
 addGravity and before setWallBcs, for every method; whole grids only (a compute window or z-slab `geom` raises).
+mconf['viscosity'] > 0 and batch_dict['flags_stick'] with 'convnet' in 3D (the reference's 3D branches cannot run; default semantics of
+fluid.addViscosity / fluid.setWallBcsStick, so a `geom` with ref_quirks raises): the native step has no 3D viscous stage.  A 3D state
+with flags_stick takes the operator path by itself; a 3D state with viscosity runs with fused=False and raises with fused=True.
+Stable for viscosity * dt <= 1/4 (2D), 1/6 (3D).
 batch_dict['scalars'] (no reference key; (B,C,D,H,W) fp32, C >= 1): passive scalars carried along with the step -- a second smoke
 source, a dye, a temperature to look at.  They do not act on the flow.  At the top of the call, while U is still the old velocity (the
 one the density is advected by), on the fused and the operator path alike:
@@ -190,13 +194,21 @@ def simulate(mconf, batch_dict, net, sim_method, output_div=False, fused=True, w
     has_density = "density" in batch_dict
 
     is3D = U.size(1) == 3
+    if is3D and geom is not None and geom.ref_quirks and (viscosity > 0 or ("flags_stick" in batch_dict and sim_method == "convnet")):
+        # neither operator takes a geom: in 3D the reference has no form of them that quirks could reproduce (fnx_add_viscosity and
+        # fnx_set_wall_bcs_stick refuse FnxGrid.ref_quirks for the same reason)
+        raise RuntimeError("simulate(): viscosity and flags_stick have no 3D form with ref_quirks (the reference's 3D branches cannot run)")
+    # 3D viscosity: fluid.addViscosity takes 3D fields, so the operator path runs the viscous step; the native step has no 3D
+    # viscous stage (fnx_simulate_step refuses it), and a call that asks for the native step is told so before anything is written
+    if is3D and viscosity > 0 and fused and not output_div:
+        raise RuntimeError("simulate(): mconf['viscosity'] is 2D only in the native step; in 3D pass fused=False (the operator path)")
     if "scalars" in batch_dict:                                 # before anything writes U: the scalars go by the old velocity
         _scalars_stage(mconf, batch_dict, dt, U, flags, geom)
     # the optional stages (viscosity, gravityScale, correctScalar, the periodic patches, flags_stick) are branches of the
     # native step (FnxStepParams / FnxState); what stays on the operator path: output_div (a training-time early return),
-    # the stages the reference only has in 2D asked for in 3D (they raise there, as the operators do), and
+    # 3D states with flags_stick (the native step refuses them; fluid.setWallBcsStick takes 3D fields), and
     # no 'density' key but a density BC: the reference applies setConstVals to its zeros (simulate.py:82-97)
-    simple = (not output_div and not (is3D and (viscosity > 0 or "flags_stick" in batch_dict))
+    simple = (not output_div and not (is3D and "flags_stick" in batch_dict)
               and (has_density or not ("densityBC" in batch_dict and "densityBCInvMask" in batch_dict)))
     if fused and simple:
         periodic = 0

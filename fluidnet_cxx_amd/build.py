@@ -26,6 +26,7 @@ HIP_UNITS = {
     "fnx_pcg.hip": ["-Rpass-analysis=kernel-resource-usage"],
     "fnx_step.hip": ["-ffp-contract=off"],
     "fnx_vorticity.hip": ["-ffp-contract=off", "-Rpass-analysis=kernel-resource-usage"],
+    "fnx_viscous.hip": ["-ffp-contract=off", "-Rpass-analysis=kernel-resource-usage"],
     "fnx_scenes.hip": ["-ffp-contract=off", "-Rpass-analysis=kernel-resource-usage"],
     "fnx_render.hip": ["-ffp-contract=off", "-Rpass-analysis=kernel-resource-usage"],
     "fnx_api.hip": ["-ffp-contract=off"],
@@ -56,6 +57,9 @@ SCRATCH_FREE = {
     "fnx_vorticity.hip": (["vorticity_confinement_kernel"],
                           "its z-march keeps three planes of c and n, two of the curl and three of F_z in registers between the barriers; "
                           "a spill puts a scratch round trip into every step of the march"),
+    "fnx_viscous.hip": (["add_viscosity3d_kernel"],
+                        "its z-march keeps three planes of the three components and of flags, and the halo cell of two planes, in "
+                        "registers between the barriers; a spill puts a scratch round trip into every step of a bandwidth-bound march"),
     "fnx_scenes.hip": (["scene_obstacles_kernel", "scene_turbulence_kernel", "train_loss_kernel", "train_loss_finish_kernel"],
                        "they are streaming kernels with a handful of live values per thread in either dimension (the 3D turbulence "
                        "thread's nine potential values, the loss's fp64 partial sums); scratch there would mean the octave loop, the "

@@ -360,6 +360,7 @@ void correct_scalar_(double dt, Tensor src, Tensor div, Tensor flags) {
   wrote(src);
 }
 
+// viscosity.py:7-70, in place on U like the reference; 2D (B,2,1,H,W) or 3D (B,3,D,H,W), the 3D form in default semantics
 void add_viscosity_(double dt, Tensor U, Tensor flags, double viscosity) {
   check_field(U, "U");
   FnxGrid g = grid_of(flags, U.size(1) == 3, nullptr);
@@ -371,9 +372,12 @@ void add_viscosity_(double dt, Tensor U, Tensor flags, double viscosity) {
   wrote(U);
 }
 
-// set_wall_bcs_stick.py:5-157 (2D; in place on U like the reference)
+// set_wall_bcs_stick.py:5-157 (2D; in place on U like the reference).  This is the reference's entry point and keeps the reference's
+// reach: a 3D field is refused here as before, and the 3D operator (no reference counterpart) is set_wall_bcs_stick_out below
 void set_wall_bcs_stick_(Tensor U, Tensor flags, Tensor flags_stick) {
   check_field(U, "U");
+  TORCH_CHECK(U.size(1) != 3, "set_wall_bcs_stick_: 2D only (the reference's 3D branch cannot run, set_wall_bcs_stick.py:85-86; the 3D "
+                              "operator of this package is set_wall_bcs_stick_out)");
   FnxGrid g = grid_of(flags, U.size(1) == 3, nullptr);
   check_vel(U, g, "U");
   check_scalar(flags_stick, g, "flags_stick");
@@ -382,6 +386,31 @@ void set_wall_bcs_stick_(Tensor U, Tensor flags, Tensor flags_stick) {
   check_status(fnx_set_wall_bcs_stick(&g, old.data_ptr<float>(), U.data_ptr<float>(), flags.data_ptr<float>(),
                                       flags_stick.data_ptr<float>(), cur_stream(U)));
   wrote(U);
+}
+
+// The same two operators out of place, as the C ABI has them (no reference counterpart): U is only read and `out`, a tensor of U's
+// shape, is written and returned -- what a caller that owns both buffers uses to spare the copy above.  `out` must not be U.
+Tensor add_viscosity_out(double dt, Tensor U, Tensor flags, double viscosity, Tensor out) {
+  check_field(U, "U");
+  FnxGrid g = grid_of(flags, U.size(1) == 3, nullptr);
+  check_vel(U, g, "U"); check_vel(out, g, "out");
+  c10::hip::HIPGuard guard(flags.get_device());
+  check_status(fnx_add_viscosity(&g, (float)dt, U.data_ptr<float>(), out.data_ptr<float>(), flags.data_ptr<float>(),
+                                 (float)viscosity, cur_stream(U)));
+  wrote(out);
+  return out;
+}
+
+Tensor set_wall_bcs_stick_out(Tensor U, Tensor flags, Tensor flags_stick, Tensor out) {
+  check_field(U, "U");
+  FnxGrid g = grid_of(flags, U.size(1) == 3, nullptr);
+  check_vel(U, g, "U"); check_vel(out, g, "out");
+  check_scalar(flags_stick, g, "flags_stick");
+  c10::hip::HIPGuard guard(flags.get_device());
+  check_status(fnx_set_wall_bcs_stick(&g, U.data_ptr<float>(), out.data_ptr<float>(), flags.data_ptr<float>(),
+                                      flags_stick.data_ptr<float>(), cur_stream(U)));
+  wrote(out);
+  return out;
 }
 
 void set_wall_bcs_(Tensor U, Tensor flags, const Geom* geom) {
@@ -924,7 +953,7 @@ struct PySlab {
             c10::optional<Tensor> densityBC, c10::optional<Tensor> densityBCInvMask, double dt, double maccormack_strength,
             bool sample_outside_fluid, double buoyancy_scale, std::vector<double> gravity_vec, double operating_density,
             double p_tol, int jacobi_iter, Tensor workspace, c10::optional<Tensor> net, const std::string& precision_mode,
-            double normalize_threshold, const std::string& method) {
+            double normalize_threshold, const std::string& method, double viscosity) {
     check_field(U, "U");
     Geom none;
     FnxGrid g = grid_of(flags, true, &none);
@@ -944,6 +973,7 @@ struct PySlab {
     }
     TORCH_CHECK(method == "auto" || method == "jacobi" || method == "convnet" || method == "pcg", "unknown z-slab step method '", method, "'");
     if (method == "pcg") prm.method = 2;           // refused by fnx_slab_step (single-domain only)
+    prm.viscosity = (float)viscosity;              // mconf['viscosity'] > 0: refused by fnx_slab_step as well (single-domain only)
     c10::optional<Tensor> rho(density);
     FnxState st = make_state(g, p, U, flags, rho, UBC, UBCInvMask, densityBC, densityBCInvMask);
     if (cnn) st.net = net->data_ptr();
@@ -1143,6 +1173,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("albedo_smoke") = 1.0, py::arg("albedo_obstacle") = 0.5, py::arg("bnd") = 1, NoGil());
   m.def("set_wall_bcs_", &set_wall_bcs_, py::arg("U"), py::arg("flags"), GEOM, NoGil());
   m.def("set_wall_bcs_stick_", &set_wall_bcs_stick_, NoGil());
+  m.def("add_viscosity_out", &add_viscosity_out, "addViscosity of U into `out` (not U), returned (fnx_add_viscosity)", py::arg("dt"), py::arg("U"),
+        py::arg("flags"), py::arg("viscosity"), py::arg("out"), NoGil());
+  m.def("set_wall_bcs_stick_out", &set_wall_bcs_stick_out, "setWallBcsStick of U into `out` (not U), returned (fnx_set_wall_bcs_stick)",
+        py::arg("U"), py::arg("flags"), py::arg("flags_stick"), py::arg("out"), NoGil());
   m.def("set_const_vals_", &set_const_vals_, NoGil());
   m.def("flags_to_occupancy", &flags_to_occupancy, NoGil());
   m.def("max_abs", &max_abs, NoGil());
@@ -1258,7 +1292,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            py::arg("densityBC"), py::arg("densityBCInvMask"), py::arg("dt"), py::arg("maccormack_strength"),
            py::arg("sample_outside_fluid"), py::arg("buoyancy_scale"), py::arg("gravity_vec"), py::arg("operating_density"),
            py::arg("p_tol"), py::arg("jacobi_iter"), py::arg("workspace"), py::arg("net") = py::none(), py::arg("precision_mode") = "fp32",
-           py::arg("normalize_threshold") = 1e-5, py::arg("method") = "auto", NoGil());
+           py::arg("normalize_threshold") = 1e-5, py::arg("method") = "auto", py::arg("viscosity") = 0.0, NoGil());
   m.def("device_name", []() { const char* n = fnx_device_name(); return std::string(n ? n : ""); });
   m.def("trilinear_upsample_backward", &trilinear_upsample_backward, py::arg("grad_dst"), py::arg("size"), NoGil());
   m.def("multiscale_tape_layout", [](int64_t B, int64_t H, int64_t W) { return multiscale_tape_layout(false, B, 1, H, W); }, py::arg("B"),

@@ -676,11 +676,15 @@ int fnx_add_viscosity(const FnxGrid* g, float dt, const float* U_in, float* U_ou
                       void* stream) {
   if (int rc = check_grid(g)) return rc;
   if (!U_in || !U_out || !flags) return fail(FNX_EINVAL, "add_viscosity: NULL tensor");
-  if (g->is3D) return fail(FNX_EINVAL, "add_viscosity: 2D only (reference viscosity.py:5)");
+  if (quirks(g))
+    return fail(FNX_EINVAL, "add_viscosity: no 3D form with ref_quirks (the reference's 3D branch cannot run, viscosity.py never defines "
+                            "mask_fluid_k: there is nothing to reproduce)");
+  if (g->is3D && is_view(g)) return fail(FNX_EINVAL, "add_viscosity: no compute window or z-slab view (whole grids only)");
   if (U_in == U_out) return fail(FNX_EINVAL, "add_viscosity: U_out must not alias U_in");
   if (!(viscosity >= 0.f)) return fail(FNX_EINVAL, "add_viscosity: viscosity must be positive");
   const float coef = (float)((double)dt * (double)viscosity);
-  fnx::launch_add_viscosity(dims(g), U_in, U_out, flags, coef, (hipStream_t)stream);
+  if (g->is3D) fnx::launch_add_viscosity3d(dims(g), U_in, U_out, flags, coef, (hipStream_t)stream);
+  else fnx::launch_add_viscosity(dims(g), U_in, U_out, flags, coef, (hipStream_t)stream);
   HIP_OK(hipGetLastError());
   return FNX_OK;
 }
@@ -756,9 +760,12 @@ int fnx_set_wall_bcs_stick(const FnxGrid* g, const float* U_in, float* U_out, co
                            void* stream) {
   if (int rc = check_grid(g)) return rc;
   if (!U_in || !U_out || !flags || !flags_stick) return fail(FNX_EINVAL, "set_wall_bcs_stick: NULL tensor");
-  if (g->is3D || g->D != 1) return fail(FNX_EINVAL, "set_wall_bcs_stick: 2D only (the reference's 3D branch cannot run, set_wall_bcs_stick.py:85-86)");
+  if (quirks(g))
+    return fail(FNX_EINVAL, "set_wall_bcs_stick: no 3D form with ref_quirks (the reference's 3D branch cannot run, "
+                            "set_wall_bcs_stick.py:85-86: there is nothing to reproduce)");
   if (U_in == U_out) return fail(FNX_EINVAL, "set_wall_bcs_stick: U_out must not alias U_in");
-  fnx::launch_set_wall_bcs_stick(dims(g), U_in, U_out, flags, flags_stick, (hipStream_t)stream);
+  if (g->is3D) fnx::launch_set_wall_bcs_stick3d(dims(g), U_in, U_out, flags, flags_stick, (hipStream_t)stream);
+  else fnx::launch_set_wall_bcs_stick(dims(g), U_in, U_out, flags, flags_stick, (hipStream_t)stream);
   HIP_OK(hipGetLastError());
   return FNX_OK;
 }
@@ -949,6 +956,7 @@ int fnx_simulate_step(const FnxGrid* g, const FnxStepParams* prm, const FnxState
   const fnx::StepPlan plan = fnx::step_plan(prm, has_rho, st->flags_stick != nullptr, st->UBC || st->densityBC);
   if (prm->viscosity < 0.f) return fail(FNX_EINVAL, "Viscosity must be positive");
   if (prm->vorticity_confinement != prm->vorticity_confinement) return fail(FNX_EINVAL, "simulate_step: vorticity_confinement is NaN");
+  // (the operators themselves take 3D grids since ABI 29; the step has no 3D viscous stage: the message's "2D only" speaks of the step)
   if (plan.viscous && g->is3D) return fail(FNX_EINVAL, "simulate_step: viscosity is 2D only (reference viscosity.py:5)");
   if (plan.projection == StepProjection::NET_STICK && g->is3D) return fail(FNX_EINVAL, "simulate_step: flags_stick is 2D only (set_wall_bcs_stick.py:85-86)");
   hipStream_t s = (hipStream_t)stream;

@@ -81,6 +81,12 @@ void launch_divergence_bwd(const GridDims& g, bool is3d, const float* gdiv, cons
 void launch_velocity_update_bwd(const GridDims& g, bool is3d, const float* gout, const float* flags, float* gU, float* gp,
                                 hipStream_t s);
 
+// the viscous-flow operators in 3D (fnx_viscous.hip; default semantics only: the reference has no 3D form to reproduce).  Both are out
+// of place, Uout must not alias Uin.  addViscosity marches whole grids along z; setWallBcsStick honours a compute window and a z-slab view
+void launch_add_viscosity3d(const GridDims& g, const float* Uin, float* Uout, const float* flags, float coef, hipStream_t s);
+void launch_set_wall_bcs_stick3d(const GridDims& g, const float* Uin, float* Uout, const float* flags, const float* stick,
+                                 hipStream_t s);
+
 // fused step stages (fnx_step.hip)
 // The BC arrays of a state as the stages take them: a pair counts only with both of its halves (bc_ptrs); cls: the optional class map
 struct BcPtrs { const float *UBC, *UBCInvMask, *rhoBC, *rhoBCInvMask; const unsigned char* cls; };

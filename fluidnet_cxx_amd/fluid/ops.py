@@ -236,10 +236,13 @@ def addGravity(U, flags, gravity, dt, *, geom=None):
 
 
 def addViscosity(dt, U, flags, viscosity):
-    """lib/fluid/viscosity.py:7-70 -- in place on U (2D only, like the reference)."""
+    """lib/fluid/viscosity.py:7-70 -- in place on U.  One explicit step of the viscous term on the MAC faces whose two cells are
+    fluid: U += (dt * viscosity) * (sum of the 2 nd face neighbours - 2 nd U), other interior faces are zeroed, the border is kept.
+    2D gives the reference's bits (its fourth neighbour is (i-1, j-1)).  3D, where the reference's branch cannot run, is the same
+    rule with the axis as a variable (include/fluidnet_hip.h: fnx_add_viscosity; tests/viscous_model_nd.py states it).
+    The explicit update is stable for dt * viscosity <= 1 / (2 nd): 1/4 in 2D, 1/6 in 3D.  Nothing checks that, as in the reference."""
     _check5(U, flags)
     assert flags.size(1) == 1, "flags is not scalar"
-    assert U.size(1) == 2 and U.size(2) == 1, "addViscosity: ONLY IN 2D"
     ext.add_viscosity_(float(dt), U, flags, float(viscosity))
 
 
@@ -290,14 +293,20 @@ def setWallBcs(U, flags, *, geom=None):
 
 
 def setWallBcsStick(U, flags, flags_stick):
-    """lib/fluid/set_wall_bcs_stick.py:5-157 -- no-slip walls, in place on U (2D).  `flags_stick` is a copy of flags
+    """lib/fluid/set_wall_bcs_stick.py:5-157 -- no-slip walls, in place on U.  `flags_stick` is a copy of flags
     with the no-slip obstacle cells set to CellType.TypeStick (cylinder.py:76).  The reference function raises
-    NameError as shipped; this is its body with the three unbound names bound (include/fluidnet_hip.h)."""
+    NameError as shipped; in 2D this is its body with the three unbound names bound (include/fluidnet_hip.h).
+    In 3D, where the reference's branch cannot run, a stick cell's tangential components become minus the mean of its fluid
+    neighbours' across the transverse axes, and a component normal to a fluid/obstacle face stays 0 (fnx_set_wall_bcs_stick;
+    tests/viscous_model_nd.py states it)."""
     _check5(U, flags)
     assert flags.dim() == 5 and flags_stick.dim() == 5, "Dimension mismatch"
     assert flags.size(1) == 1, "flags is not a scalar"
     assert flags_stick.size(1) == 1, "flags is not a scalar"
     assert flags_stick.is_contiguous(), "Input is not contiguous"
+    if U.size(1) == 3:          # the extension's in-place entry point is the reference's, 2D; the 3D operator is out of place
+        U.copy_(ext.set_wall_bcs_stick_out(U, flags, flags_stick, torch.empty_like(U)))
+        return
     ext.set_wall_bcs_stick_(U, flags, flags_stick)
 
 

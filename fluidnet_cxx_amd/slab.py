@@ -873,7 +873,7 @@ class NativeSlabSimulator:
                               float(cfg.get("pTol", 0.0)), int(cfg["jacobiIter"]), self._ws,
                               self.net.packed_for(st["flags"].device) if self.method == "convnet" else None,
                               getattr(self.net, "precision_mode", "fp32") if self.method == "convnet" else "fp32",
-                              float(cfg.get("normalizeInputThreshold", 1e-5)))
+                              float(cfg.get("normalizeInputThreshold", 1e-5)), viscosity=float(cfg.get("viscosity", 0) or 0))
 
 
 def rccl_comm(rank, world, group=None):

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define FNX_ABI_VERSION 28
+#define FNX_ABI_VERSION 29
 
 enum {
   FNX_OK = 0,
@@ -254,8 +254,14 @@ int fnx_add_gravity(const FnxGrid* g, float* U, const float* flags, const float 
 /* correctScalar (in place on src), lib/fluid/cpp/advection.py:9-12: src += (dt * 0.5) * src * div on fluid cells. */
 int fnx_correct_scalar(const FnxGrid* g, float dt, float* src, const float* div, const float* flags, void* stream);
 
-/* addViscosity, lib/fluid/viscosity.py:7-70 (2D only, like the reference).  The reference updates U in place from
- * a fully evaluated right-hand side; here U_in is the old field and U_out (a distinct buffer) receives the result. */
+/* addViscosity, lib/fluid/viscosity.py:7-70.  The reference updates U in place from a fully evaluated right-hand side; here U_in
+ * is the old field and U_out (a distinct buffer) receives the result.  2D: the reference's bits (its fourth neighbour is (i-1, j-1)).
+ * 3D (ABI 29; the reference's 3D branch cannot run, so default semantics only: with FnxGrid.ref_quirks it is FNX_EINVAL): on an
+ * interior cell and component c, fp32, uncontracted, in this order,
+ *   s = u(x+e_x) + u(x+e_y) + u(x+e_z);  s += u(x-e_x);  s += u(x-e_y);  s += u(x-e_z);  s -= 6 u(x)
+ *   U_out = m * (u(x) + coef * s),  coef = (float)((double)dt * viscosity),  m = 1 if the cell and its -e_c neighbour are fluid, else 0
+ * and the one-cell border is copied.  Stable for coef <= 1/6 (1/4 in 2D); not checked, as the reference checks nothing.  3D takes whole
+ * grids only (no compute window, no z-slab view). */
 int fnx_add_viscosity(const FnxGrid* g, float dt, const float* U_in, float* U_out, const float* flags,
                       float viscosity, void* stream);
 
@@ -303,10 +309,18 @@ int fnx_render_volume(const FnxGrid* g, const float* density, const float* flags
 int fnx_set_wall_bcs(const FnxGrid* g, float* U, const float* flags, void* stream);
 
 /* setWallBcsStick, lib/fluid/set_wall_bcs_stick.py:5-157 (no-slip walls: `flags_stick` is a copy of flags with the
- * no-slip obstacle cells set to 128, cylinder.py:76).  2D only.  As shipped the reference function raises NameError
- * on three unbound names (:62 ff.); with them bound its 2D body runs, and that is what this reproduces bit for bit
+ * no-slip obstacle cells set to 128, cylinder.py:76).  As shipped the reference function raises NameError
+ * on three unbound names (:62 ff.); with them bound its 2D body runs, and that is what the 2D form reproduces bit for bit
  * (tests/golden/stick.npz).  The reference updates U in place from gathered copies; here U_in is the old field and
- * U_out (a distinct buffer) receives the result. */
+ * U_out (a distinct buffer) receives the result.
+ * 3D (ABI 29; the reference's 3D branch cannot run, :85-87, so default semantics only: with FnxGrid.ref_quirks it is FNX_EINVAL).
+ * Every value is a function of U_in:
+ *   slip value s_c(x): 0 on an obstacle cell; else 0 where the cell is fluid or stick, x_c > 0 and flags(x - e_c) is an obstacle; else U_in
+ *   on a stick cell, component c: the fluid neighbours y = x -+ e_a inside the domain, a != c ascending, low before high, contribute
+ *     s_c(y): t = -s_c(y_1), t = t - s_c(y_k), value t / (float)n (an IEEE division).  It is written unless x_c > 0 and
+ *     flags(x - e_c) is fluid (a wall face: the normal component keeps its slip value, 0 on an obstacle); n = 0 keeps the slip value
+ *   every other cell gets its slip value.
+ * A compute window and a z-slab view are honoured as fnx_set_wall_bcs honours them (plane 0 of the domain has no -e_z rule). */
 int fnx_set_wall_bcs_stick(const FnxGrid* g, const float* U_in, float* U_out, const float* flags,
                            const float* flags_stick, void* stream);
 
@@ -374,8 +388,10 @@ typedef struct FnxStepParams {
                                  steps; the PCG vectors (~26 B per cell) share the scratch tail with the advection and the CNN,
                                  whose needs are larger, so they add nothing there */
   /* Optional stages of lib/simulate.py (all off when zero; fnx_slab_step refuses them): */
-  float viscosity;            /* mconf['viscosity'] > 0 (2D only, like addViscosity): the velocity advected is
-                                 addViscosity(U.clone()), advected by U (simulate.py:66-69, :85-93) */
+  float viscosity;            /* mconf['viscosity'] > 0: the velocity advected is addViscosity(U.clone()), advected by U
+                                 (simulate.py:66-69, :85-93).  2D only in this step: fnx_add_viscosity takes 3D grids since
+                                 ABI 29, fnx_simulate_step still refuses a 3D grid with it (callers compose the 3D viscous step
+                                 from the operators) */
   float gravity_scale;        /* mconf['gravityScale'] > 0: addGravity(gravityVec * -gravityScale) after the buoyancy, only with
                                  a density (simulate.py:107-114) */
   int   correct_scalar;       /* mconf['correctScalar']: density += dt/2 * density * div(U) on fluid cells after its
@@ -404,8 +420,8 @@ typedef struct FnxState {
    * bytes) and apply t = x*1, t + 0 directly: same bits.  Only valid while the four BC arrays do not change. */
   const unsigned char* bc_class;
   /* Optional (B,1,1,H,W) copy of flags with the no-slip cells set to 128 ('flags_stick' in batch_dict, cylinder.py:76), or
-   * NULL.  Method 1 (convnet), 2D only: setWallBcsStick before the second setConstVals and after the net
-   * (simulate.py:129-130, :165-166).  Method 0 ignores it, as the reference does. */
+   * NULL.  Method 1 (convnet), 2D only in the step (fnx_set_wall_bcs_stick itself takes 3D grids since ABI 29): setWallBcsStick
+   * before the second setConstVals and after the net (simulate.py:129-130, :165-166).  Method 0 ignores it, as the reference does. */
   const float* flags_stick;
   /* Optional promise to fnx_post_projection (0 = none): `density` already went through setConstVals with these BC arrays
    * since it was last written -- fnx_pre_projection leaves it that way.  On a cell of bc_class whose density BC is the
