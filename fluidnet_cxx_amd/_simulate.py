@@ -6,6 +6,11 @@ batch_dict, same mconf keys).  Two execution modes:
               Python between kernels);
   fused=False: operator by operator through the `fluid.*` surface in the reference's order (what the
               parity tests use to compare stage by stage).
+fused=True still runs operator by operator where the native step has no form of the call: output_div=True, a 3D state with
+flags_stick, a density BC without a 'density' key, and mconf['viscosity'] > 0 with a (dt, viscosity) pair whose double product the two
+floats of FnxStepParams do not give (about a third of all pairs, dt = 0.1 with viscosity = 0.05 among them; the reference rounds the
+product once, viscosity.py:64).  `workspace` and `static_flags` are then not used.  The same bits, more launches: until FnxStepParams
+carries the product (an ABI change) such a viscous 2D run is slower than one with, say, viscosity = 0.02.
 The reference's own call -- `simulate(mconf, batch_dict, net, sim_method)`, four arguments (plume.py:237) -- gets the static
 path by itself: the layer keeps one step workspace per (device, grid shape) and looks at `(data_ptr, _version, shape, stride)` of
 `flags` and of the four BC arrays (torch bumps `_version` on every in-place write, and so do this package's own in-place
@@ -54,6 +59,8 @@ domains only: with a compute window or z-slab `geom` and the key present the cal
 `geom` (an `ext.Geom`, 3D only) selects the reference-quirk mode / a z-slab view for this call; it is per call, the
 extension keeps no state.
 """
+import ctypes
+
 import torch
 
 from . import fluid
@@ -157,6 +164,18 @@ def release_workspaces():
     _AUTO.clear()
 
 
+def _f32(x):
+    return ctypes.c_float(x).value
+
+
+def _step_has_the_viscous_coefficient(dt, viscosity):
+    """The reference multiplies dt and viscosity as Python floats and rounds the product once (viscosity.py:64; fluid.addViscosity
+    does the same).  FnxStepParams carries the two as floats and the native step multiplies those: for about a third of all pairs that
+    coefficient is an ulp off (dt = 0.1 with viscosity = 0.05; not with the 0.02 of the goldens).  Such a step runs operator by operator
+    -- the same kernels, the reference's bits."""
+    return _f32(_f32(dt) * _f32(viscosity)) == _f32(dt * viscosity)
+
+
 def _is_view(geom):
     return geom is not None and (geom.k_begin != 0 or geom.k_end != 0 or geom.z_offset != 0 or geom.D_global != 0)
 
@@ -206,10 +225,12 @@ def simulate(mconf, batch_dict, net, sim_method, output_div=False, fused=True, w
         _scalars_stage(mconf, batch_dict, dt, U, flags, geom)
     # the optional stages (viscosity, gravityScale, correctScalar, the periodic patches, flags_stick) are branches of the
     # native step (FnxStepParams / FnxState); what stays on the operator path: output_div (a training-time early return),
-    # 3D states with flags_stick (the native step refuses them; fluid.setWallBcsStick takes 3D fields), and
-    # no 'density' key but a density BC: the reference applies setConstVals to its zeros (simulate.py:82-97)
+    # 3D states with flags_stick (the native step refuses them; fluid.setWallBcsStick takes 3D fields),
+    # no 'density' key but a density BC: the reference applies setConstVals to its zeros (simulate.py:82-97), and
+    # a (dt, viscosity) pair whose product the step's two floats do not give (_step_has_the_viscous_coefficient)
     simple = (not output_div and not (is3D and "flags_stick" in batch_dict)
-              and (has_density or not ("densityBC" in batch_dict and "densityBCInvMask" in batch_dict)))
+              and (has_density or not ("densityBC" in batch_dict and "densityBCInvMask" in batch_dict))
+              and (viscosity == 0 or _step_has_the_viscous_coefficient(dt, viscosity)))
     if fused and simple:
         periodic = 0
         if "periodic-x" in mconf and "periodic-y" in mconf:                     # simulate.py:121, :157

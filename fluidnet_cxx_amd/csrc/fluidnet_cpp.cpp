@@ -360,6 +360,16 @@ void correct_scalar_(double dt, Tensor src, Tensor div, Tensor flags) {
   wrote(src);
 }
 
+// The reference multiplies dt and viscosity as Python floats (doubles) and the product meets the float tensor rounded once
+// (viscosity.py:64).  fnx_add_viscosity takes two floats and forms (float)((double)dt * viscosity): rounding either factor first moves
+// the coefficient by an ulp for about a third of all pairs.  So the product is formed here and handed over as dt, with a viscosity of 1 (the C
+// function's product is then exact).  A negative viscosity goes through as it is, for the C function's own refusal.
+struct ViscousArgs { float dt, viscosity; };
+static ViscousArgs viscous_args(double dt, double viscosity) {
+  if (!(viscosity >= 0)) return {(float)dt, (float)viscosity};
+  return {(float)(dt * viscosity), 1.f};
+}
+
 // viscosity.py:7-70, in place on U like the reference; 2D (B,2,1,H,W) or 3D (B,3,D,H,W), the 3D form in default semantics
 void add_viscosity_(double dt, Tensor U, Tensor flags, double viscosity) {
   check_field(U, "U");
@@ -367,8 +377,9 @@ void add_viscosity_(double dt, Tensor U, Tensor flags, double viscosity) {
   check_vel(U, g, "U");
   c10::hip::HIPGuard guard(flags.get_device());
   Tensor old = U.clone();
-  check_status(fnx_add_viscosity(&g, (float)dt, old.data_ptr<float>(), U.data_ptr<float>(), flags.data_ptr<float>(),
-                                 (float)viscosity, cur_stream(U)));
+  const ViscousArgs a = viscous_args(dt, viscosity);
+  check_status(fnx_add_viscosity(&g, a.dt, old.data_ptr<float>(), U.data_ptr<float>(), flags.data_ptr<float>(), a.viscosity,
+                                 cur_stream(U)));
   wrote(U);
 }
 
@@ -395,8 +406,9 @@ Tensor add_viscosity_out(double dt, Tensor U, Tensor flags, double viscosity, Te
   FnxGrid g = grid_of(flags, U.size(1) == 3, nullptr);
   check_vel(U, g, "U"); check_vel(out, g, "out");
   c10::hip::HIPGuard guard(flags.get_device());
-  check_status(fnx_add_viscosity(&g, (float)dt, U.data_ptr<float>(), out.data_ptr<float>(), flags.data_ptr<float>(),
-                                 (float)viscosity, cur_stream(U)));
+  const ViscousArgs a = viscous_args(dt, viscosity);
+  check_status(fnx_add_viscosity(&g, a.dt, U.data_ptr<float>(), out.data_ptr<float>(), flags.data_ptr<float>(), a.viscosity,
+                                 cur_stream(U)));
   wrote(out);
   return out;
 }

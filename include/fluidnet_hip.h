@@ -261,7 +261,10 @@ int fnx_correct_scalar(const FnxGrid* g, float dt, float* src, const float* div,
  *   s = u(x+e_x) + u(x+e_y) + u(x+e_z);  s += u(x-e_x);  s += u(x-e_y);  s += u(x-e_z);  s -= 6 u(x)
  *   U_out = m * (u(x) + coef * s),  coef = (float)((double)dt * viscosity),  m = 1 if the cell and its -e_c neighbour are fluid, else 0
  * and the one-cell border is copied.  Stable for coef <= 1/6 (1/4 in 2D); not checked, as the reference checks nothing.  3D takes whole
- * grids only (no compute window, no z-slab view). */
+ * grids only (no compute window, no z-slab view).
+ * The reference multiplies dt and viscosity as Python doubles and rounds the product once; two doubles rounded to float first give a
+ * coef that is an ulp off for about a third of all pairs (dt = 0.1 with viscosity = 0.05 is one).  A caller that holds the doubles
+ * gets the reference's coef by passing dt = (float)(dt * viscosity), viscosity = 1 (the Python layer does). */
 int fnx_add_viscosity(const FnxGrid* g, float dt, const float* U_in, float* U_out, const float* flags,
                       float viscosity, void* stream);
 

@@ -142,8 +142,8 @@ def add_viscosity(dt, U, flags, viscosity):
     g = _grid(flags, U.shape[1] == 3)
     flags, pf = _f(flags)
     U = np.array(U, dtype=np.float32, order="C", copy=True)
-    rc = lib().ora_add_viscosity(ctypes.byref(g), ctypes.c_float(dt), U.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), pf,
-                                 ctypes.c_float(viscosity))
+    rc = lib().ora_add_viscosity(ctypes.byref(g), ctypes.c_double(dt), U.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), pf,
+                                 ctypes.c_double(viscosity))
     assert rc == 0, "addViscosity is 2D only (reference viscosity.py:5)"
     return U
 

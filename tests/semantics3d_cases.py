@@ -20,11 +20,14 @@ import os
 import numpy as np
 
 import fluid_model_nd as M
+import hostile2d_cases as HC
 
 CAP = 1e-3
 JUMP = 1e-4
 GOLDEN_2D = ("ops_2d_a", "ops_2d_b", "ops_2d_c", "ops_2d_d")
 GOLDEN_3D = ("ops_3d_a", "ops_3d_b")
+# the reference on the geometries of hostile2d_cases.py (open sides, scattered cells, per-sample flags): hostile2d.npz / hostile2d_hi.npz
+HOSTILE_2D = tuple("hostile2d_" + n for n in HC.GOLDEN_STATES)
 #               B, D,  H,  W, max|U| dt, seed
 OWN = {"tile_lo": (1, 10, 11, 67, 0.6, 11),      # crosses an x tile at 64, a row tile at 8 and a z chunk at 8 planes
        "tile_hi": (1, 10, 11, 67, 3.1, 12),
@@ -97,7 +100,11 @@ def state(name):
                  rho=rng.random((B, 1, D, H, W)).astype(np.float32), p=rng.standard_normal((B, 1, D, H, W)).astype(np.float32),
                  dt=float(np.float32(cfl / np.abs(U).max())), gravity=[0.3, 0.25, -0.2], rho_star=0.05)
     else:
+        pre = ""
+        if name in HOSTILE_2D:
+            pre, name = name[len("hostile2d_"):] + "_", HC.golden_file(name)
         z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", name + ".npz"))
+        z = HC.Prefixed(z, pre)
         s = dict(flags=z["flags"], U=z["U"], orig=z["orig"], rho=z["rho"], p=z["p"], dt=float(z["dt"]),
                  gravity=z["gravity"].tolist(), rho_star=float(z["rho_star"]))
         s["golden"] = {k: z[k] for k in OPS if k in z.files}
@@ -239,13 +246,19 @@ FIGURE = {
     "tile_open": {"advect_scalar": 4.06e-06, "advect_vel": 3.86e-06, "add_buoyancy": 3.58e-08, "add_gravity": 5.18e-08, "set_wall_bcs": 0.00e+00, "divergence": 7.96e-08, "velocity_update": 6.65e-08, "step_p": 2.49e-06, "step_U": 2.67e-06, "step_density": 3.95e-06},
     "small_open": {"advect_scalar": 1.15e-06, "advect_vel": 5.99e-07, "add_buoyancy": 3.28e-08, "add_gravity": 2.04e-08, "set_wall_bcs": 0.00e+00, "divergence": 6.73e-08, "velocity_update": 5.29e-08, "step_p": 4.28e-07, "step_U": 4.58e-07, "step_density": 1.02e-06},
     "large_open": {"advect_scalar": 2.57e-06, "advect_vel": 1.47e-06, "add_buoyancy": 5.18e-08, "add_gravity": 4.31e-08, "set_wall_bcs": 0.00e+00, "divergence": 8.83e-08, "velocity_update": 6.07e-08, "step_p": 5.88e-07, "step_U": 1.17e-06, "step_density": 2.57e-06},
+    "hostile2d_open2_lo": {"advect_scalar": 1.37e-06, "advect_vel": 2.03e-06, "add_buoyancy": 3.05e-08, "add_gravity": 2.66e-08, "set_wall_bcs": 0.00e+00, "divergence": 5.74e-08, "velocity_update": 6.46e-08},
+    "hostile2d_open2_hi": {"advect_scalar": 2.54e-06, "advect_vel": 2.28e-06, "add_buoyancy": 3.86e-08, "add_gravity": 2.14e-08, "set_wall_bcs": 0.00e+00, "divergence": 9.55e-08, "velocity_update": 5.96e-08},
+    "hostile2d_open4_lo": {"advect_scalar": 1.37e-06, "advect_vel": 2.03e-06, "add_buoyancy": 3.05e-08, "add_gravity": 2.66e-08, "set_wall_bcs": 0.00e+00, "divergence": 5.74e-08, "velocity_update": 6.46e-08},
+    "hostile2d_open4_hi": {"advect_scalar": 2.56e-06, "advect_vel": 2.28e-06, "add_buoyancy": 3.86e-08, "add_gravity": 2.14e-08, "set_wall_bcs": 0.00e+00, "divergence": 9.55e-08, "velocity_update": 5.96e-08},
+    "hostile2d_salt_lo": {"advect_scalar": 1.37e-06, "advect_vel": 2.03e-06, "add_buoyancy": 3.05e-08, "add_gravity": 2.66e-08, "set_wall_bcs": 0.00e+00, "divergence": 5.74e-08, "velocity_update": 6.46e-08},
+    "hostile2d_salt_hi": {"advect_scalar": 2.46e-06, "advect_vel": 2.26e-06, "add_buoyancy": 3.86e-08, "add_gravity": 2.14e-08, "set_wall_bcs": 0.00e+00, "divergence": 9.55e-08, "velocity_update": 5.96e-08},
 }
 
 TOL = {n: {f: 4.0 * v for f, v in fam.items()} for n, fam in FIGURE.items()}
 
 
 def print_figures():
-    for n in GOLDEN_2D + GOLDEN_3D + tuple(OWN):
+    for n in GOLDEN_2D + GOLDEN_3D + tuple(OWN) + HOSTILE_2D:
         fam = {}
         for op in model_outputs(n):
             fam[family(op)] = max(fam.get(family(op), 0.0), figure(n, op))

@@ -100,7 +100,7 @@ def test_oracle_default_mode_vs_model_all_cells(oracle, name):
         C.check(out[op], name, op, "oracle vs model")
 
 
-@pytest.mark.parametrize("name", C.GOLDEN_2D + C.GOLDEN_3D + tuple(C.OWN))
+@pytest.mark.parametrize("name", C.GOLDEN_2D + C.GOLDEN_3D + tuple(C.OWN) + C.HOSTILE_2D)
 def test_model_precision_guard(name):
     """float32 model against float64 model: at most a quarter of the cap beyond tol"""
     m32 = C.model_outputs(name, np.float32)
@@ -112,7 +112,8 @@ def test_model_precision_guard(name):
 def test_states_reach_both_cases_of_the_line_trace(name):
     """what the comparisons above can vouch for: behind an all-obstacle border no ray ever leaves the domain (a unit step ends in the
     wall cell first), so only the states with open faces run the ray / border intersection (case 1); every state above
-    max|U| dt = 1 runs the obstacle back-off (case 2).  No golden has an open face: case 1 is pinned by the model alone."""
+    max|U| dt = 1 runs the obstacle back-off (case 2).  No 3D golden has an open face: in 3D case 1 is pinned by the model alone (in 2D
+    the goldens of hostile2d_cases.py have open sides, test_hostile2d_reference.py)."""
     s = C.state(name)
     M.TRACE_STATS.update(border=0, blocked=0)
     M.advect_scalar(s["dt"], s["rho"], s["U"], s["flags"], "eulerFluidNet", False, 0.6)

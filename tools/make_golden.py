@@ -11,7 +11,7 @@ Runs only in the build container (needs /root/reference, no GPU).  It
   3. runs every hot-path operator on seeded inputs and stores inputs + outputs as .npz.
 
 The fixtures are data only (inputs and expected outputs).  Usage:
-    python tools/make_golden.py [--only ops2d,ops3d,plume,sim,cnn,gen,stick,grid,dump,grad]
+    python tools/make_golden.py [--only ops2d,ops3d,plume,sim,cnn,gen,stick,grid,dump,grad,hostile2d]
 """
 import argparse
 import importlib.util
@@ -101,15 +101,20 @@ def t(x, torch):
     return torch.from_numpy(np.ascontiguousarray(x))
 
 
-def gen_ops(torch, lib, ext, name, B, D, H, W, sigma, dt, seed, empties=False, boxes=True, jac_iters=7):
+def gen_ops(torch, lib, ext, name, B, D, H, W, sigma, dt, seed, empties=False, boxes=True, jac_iters=7, given=None):
+    """every hot-path operator on one seeded state -> ops_<name>.npz.  With `given` (a dict of flags, U, rho, p, orig: the caller's
+    state, gen_hostile2d) nothing is drawn or written here and the arrays are returned."""
     fluid = lib.fluid
     rng = np.random.default_rng(seed)
     is3d = D > 1
     nc = 3 if is3d else 2
-    flags = make_flags(rng, B, D, H, W, boxes, empties)
-    U = (rng.standard_normal((B, nc, D, H, W)) * sigma).astype(np.float32)
-    rho = rng.random((B, 1, D, H, W)).astype(np.float32)
-    p = rng.standard_normal((B, 1, D, H, W)).astype(np.float32)
+    if given is None:
+        flags = make_flags(rng, B, D, H, W, boxes, empties)
+        U = (rng.standard_normal((B, nc, D, H, W)) * sigma).astype(np.float32)
+        rho = rng.random((B, 1, D, H, W)).astype(np.float32)
+        p = rng.standard_normal((B, 1, D, H, W)).astype(np.float32)
+    else:
+        flags, U, rho, p = (np.array(given[k], np.float32) for k in ("flags", "U", "rho", "p"))
     out = dict(flags=flags, U=U, rho=rho, p=p, dt=np.float32(dt), is3d=np.int32(is3d))
     tf, tU, trho, tp = t(flags, torch), t(U, torch), t(rho, torch), t(p, torch)
 
@@ -123,7 +128,7 @@ def gen_ops(torch, lib, ext, name, B, D, H, W, sigma, dt, seed, empties=False, b
         r = ext.advect_vel(float(dt), tU, tU, tf, meth, 1, 0.6)
         out[f"advect_vel_{meth}"] = r.numpy().copy()
     # advect a different field than the carrier
-    orig = (rng.standard_normal((B, nc, D, H, W))).astype(np.float32)
+    orig = (rng.standard_normal((B, nc, D, H, W))).astype(np.float32) if given is None else np.array(given["orig"], np.float32)
     out["orig"] = orig
     out["advect_vel_orig"] = ext.advect_vel(float(dt), t(orig, torch), tU, tf, "maccormackFluidNet", 1, 0.75).numpy().copy()
 
@@ -160,6 +165,8 @@ def gen_ops(torch, lib, ext, name, B, D, H, W, sigma, dt, seed, empties=False, b
         Uv = tU.clone(); fluid.addViscosity(float(dt), Uv, tf, 0.07); out["add_viscosity"] = Uv.numpy().copy()
         out["viscosity"] = np.float32(0.07)
     out["occupancy"] = fluid.flagsToOccupancy(tf).numpy().copy()
+    if given is not None:
+        return out
     np.savez_compressed(os.path.join(OUT, f"ops_{name}.npz"), **out)
     print(f"  wrote ops_{name}.npz")
 
@@ -356,29 +363,34 @@ def gen_grad(torch, lib, ext):
     """Gradients of the stencil operators the training graph differentiates through (model.py:190-227 and
     fluid_net_train.py:366: velocityUpdate -> setWallBcs -> velocityDivergence), from the reference's own autograd:
     loss = sum(w_div * div) + sum(w_U * U), d loss / d p and d loss / d U_in, 2D with obstacles and Empty cells."""
-    fluid = lib.fluid
     out = {}
     rng = np.random.default_rng(31)
     for tag, (B, H, W, empties) in (("a", (2, 20, 33, False)), ("b", (1, 24, 40, True))):
-        flags = make_flags(rng, B, 1, H, W, boxes=True, empties=empties)
-        U0 = rng.standard_normal((B, 2, 1, H, W)).astype(np.float32)
-        p0 = rng.standard_normal((B, 1, 1, H, W)).astype(np.float32)
-        wd = rng.standard_normal((B, 1, 1, H, W)).astype(np.float32)
-        wu = rng.standard_normal((B, 2, 1, H, W)).astype(np.float32)
-        tf = t(flags, torch)
-        tU0 = t(U0, torch).requires_grad_(True)
-        tp = t(p0, torch).requires_grad_(True)
-        U = tU0 * 1.0                                   # (the operators work in place: not on a leaf)
-        fluid.velocityUpdate(pressure=tp, U=U, flags=tf)
-        U = fluid.setWallBcs(U, tf)
-        div = fluid.velocityDivergence(U.contiguous(), tf)
-        loss = (div * t(wd, torch)).sum() + (U * t(wu, torch)).sum()
-        loss.backward()
-        out.update({f"{tag}_flags": flags, f"{tag}_U": U0, f"{tag}_p": p0, f"{tag}_wd": wd, f"{tag}_wu": wu,
-                    f"{tag}_U_out": U.detach().numpy().copy(), f"{tag}_div": div.detach().numpy().copy(),
-                    f"{tag}_grad_U": tU0.grad.numpy().copy(), f"{tag}_grad_p": tp.grad.numpy().copy()})
+        out.update(grad_case(torch, lib, rng, tag, make_flags(rng, B, 1, H, W, boxes=True, empties=empties)))
     np.savez_compressed(os.path.join(OUT, "grad.npz"), **out)
     print("  wrote grad.npz")
+
+
+def grad_case(torch, lib, rng, tag, flags):
+    """the arrays of gen_grad for one (B, 1, 1, H, W) flags array, keys prefixed with `tag`"""
+    fluid = lib.fluid
+    B, _, _, H, W = flags.shape
+    U0 = rng.standard_normal((B, 2, 1, H, W)).astype(np.float32)
+    p0 = rng.standard_normal((B, 1, 1, H, W)).astype(np.float32)
+    wd = rng.standard_normal((B, 1, 1, H, W)).astype(np.float32)
+    wu = rng.standard_normal((B, 2, 1, H, W)).astype(np.float32)
+    tf = t(flags, torch)
+    tU0 = t(U0, torch).requires_grad_(True)
+    tp = t(p0, torch).requires_grad_(True)
+    U = tU0 * 1.0                                   # (the operators work in place: not on a leaf)
+    fluid.velocityUpdate(pressure=tp, U=U, flags=tf)
+    U = fluid.setWallBcs(U, tf)
+    div = fluid.velocityDivergence(U.contiguous(), tf)
+    loss = (div * t(wd, torch)).sum() + (U * t(wu, torch)).sum()
+    loss.backward()
+    return {f"{tag}_flags": flags, f"{tag}_U": U0, f"{tag}_p": p0, f"{tag}_wd": wd, f"{tag}_wu": wu,
+            f"{tag}_U_out": U.detach().numpy().copy(), f"{tag}_div": div.detach().numpy().copy(),
+            f"{tag}_grad_U": tU0.grad.numpy().copy(), f"{tag}_grad_p": tp.grad.numpy().copy()}
 
 
 def stick_flags(flags):
@@ -396,6 +408,13 @@ def stick_flags(flags):
     return fs
 
 
+def bind_stick_names(lib):
+    fluid = lib.fluid
+    mod = sys.modules[fluid.setWallBcsStick.__module__]
+    ct = fluid.CellType
+    mod.TypeObstacle, mod.TypeFluid, mod.TypeStick = ct.TypeObstacle, ct.TypeFluid, ct.TypeStick
+
+
 def gen_stick(torch, lib, ext):
     """setWallBcsStick (set_wall_bcs_stick.py:5-157).  As shipped it raises NameError on the bare names TypeObstacle /
     TypeFluid / TypeStick (:62 ff.); the harness binds those three names in the module's namespace (no source edit) --
@@ -403,9 +422,7 @@ def gen_stick(torch, lib, ext):
     checks the lower neighbour twice, :131; the corner sums count cur and left twice, :146-152).  The 3D branch has
     further typos (:85-86) and no z handling in the no-slip part: 2D only."""
     fluid = lib.fluid
-    mod = sys.modules[fluid.setWallBcsStick.__module__]
-    ct = fluid.CellType
-    mod.TypeObstacle, mod.TypeFluid, mod.TypeStick = ct.TypeObstacle, ct.TypeFluid, ct.TypeStick
+    bind_stick_names(lib)
     out = {}
     for name, B, H, W, sigma, seed, empties in (("a", 2, 20, 33, 2.0, 11, False), ("b", 1, 24, 40, 5.0, 12, True)):
         rng = np.random.default_rng(seed)
@@ -435,9 +452,71 @@ def gen_stick(torch, lib, ext):
     print("  wrote stick.npz")
 
 
+def gen_hostile2d(torch, lib, ext):
+    """The 2D operators on the geometries of tests/hostile2d_cases.py (open sides with Fluid and Empty border cells, scattered
+    Obstacle / Empty cells, samples of a batch that differ) -> hostile2d.npz: per state everything gen_ops stores, setWallBcsStick
+    with scattered stick cells and the per-sample tolerance exit of the Jacobi solve; the arrays of gen_grad on the open4 and salt
+    flags (the cfl 6.2 states go to hostile2d_hi.npz: one file would exceed the largest fixture so far).  hostile2d_sim.npz: 4 steps of lib.simulate 'jacobi' on a 48^2 plume with an open top / all sides open and a fast random
+    start, plain and with F2_CFG (inputs, flags, state after steps 1 and 4)."""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import hostile2d_cases as HC
+    fluid = lib.fluid
+    bind_stick_names(lib)
+    out = {"lo": {}, "hi": {}}
+    B, H, W = HC.GOLDEN_SHAPE
+    for name in HC.GOLDEN_STATES:
+        s = HC.golden_state(name)
+        o = gen_ops(torch, lib, ext, f"hostile2d:{name}", B, 1, H, W, None, s["dt"], None, jac_iters=9, given=s)
+        tf, div = t(o["flags"], torch), t(o["divergence"], torch)
+        # tolerance exit, sample by sample (gen_ops: the reference's B > 1 solve mixes samples): between the residuals of sweeps 3 and 4
+        tols, ps = [], []
+        for b in range(B):
+            fb, db = tf[b:b + 1].contiguous(), div[b:b + 1].contiguous()
+            r3 = ext.solve_linear_system(fb, db, False, 0.0, 3, False)[1].item()
+            r4 = ext.solve_linear_system(fb, db, False, 0.0, 4, False)[1].item()
+            tols.append(0.5 * (r3 + r4))
+            ps.append(ext.solve_linear_system(fb, db, False, tols[-1], 50, False)[0])
+        o["jacobi_tol"] = np.array(tols, np.float32); o["jacobi_tol_p"] = torch.cat(ps, 0).numpy().copy()
+        fs = HC.stick_flags(o["flags"], HC.STICK_SEED)
+        tU = t(o["U"], torch).clone()
+        fluid.setWallBcsStick(tU, tf, t(fs, torch))
+        o["flags_stick"] = fs; o["set_wall_bcs_stick"] = tU.numpy().copy()
+        o["viscosity"] = np.float64(0.07)      # what gen_ops passed: the reference multiplies it with dt in double (viscosity.py:64)
+        # ... a pair whose product as two floats is an ulp off that double product rounded once
+        Uv = t(o["U"], torch).clone(); fluid.addViscosity(0.1, Uv, tf, 0.05); o["add_viscosity_dt0p1_nu0p05"] = Uv.numpy().copy()
+        out[name[-2:]].update({f"{name}_{k}": v for k, v in o.items()})
+    rng = np.random.default_rng(41)
+    for kind in ("open4", "salt"):
+        out["lo"].update(grad_case(torch, lib, rng, f"grad_{kind}", np.array(HC.golden_state(kind + "_lo")["flags"])))
+    for part, fname in (("lo", "hostile2d.npz"), ("hi", "hostile2d_hi.npz")):
+        np.savez_compressed(os.path.join(OUT, fname), **out[part])
+        print(f"  wrote {fname}", os.path.getsize(os.path.join(OUT, fname)), "bytes")
+
+    sim = {}
+    mconf0 = plume_mconf(torch)
+    with torch.no_grad():
+        for kind in HC.SIM_KINDS:
+            for cfgname, extra in (("plain", {}), ("f2", F2_CFG)):
+                bd = plume_setup(torch, lib, HC.SIM_RES)
+                bd["flags"] = t(HC.sim_flags(kind, bd["flags"].numpy()), torch)
+                U, rho = HC.sim_fields(tuple(bd["U"].shape), tuple(bd["density"].shape))
+                bd["U"], bd["density"] = t(U, torch), t(rho, torch)
+                if cfgname == "plain":
+                    for k in ("flags", "U", "density", "p", "UBC", "UBCInvMask", "densityBC", "densityBCInvMask"):
+                        sim[f"{kind}_in_{k}"] = bd[k].numpy().copy()
+                mconf = dict(mconf0); mconf.update(extra)
+                for it in range(1, 5):
+                    lib.simulate(mconf, bd, None, "jacobi")
+                    if it in (1, 4):
+                        for k in ("U", "density", "p"):
+                            sim[f"{kind}_{cfgname}_{k}_{it}"] = bd[k].numpy().copy()
+    np.savez_compressed(os.path.join(OUT, "hostile2d_sim.npz"), **sim)
+    print("  wrote hostile2d_sim.npz", os.path.getsize(os.path.join(OUT, "hostile2d_sim.npz")), "bytes")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", default="ops2d,ops3d,plume,sim,cnn,gen,stick,grid,dump,grad")
+    ap.add_argument("--only", default="ops2d,ops3d,plume,sim,cnn,gen,stick,grid,dump,grad,hostile2d")
     a = ap.parse_args()
     only = set(a.only.split(","))
     os.makedirs(OUT, exist_ok=True)
@@ -467,6 +546,8 @@ def main():
         gen_dump(torch, lib, ext)
     if "grad" in only:
         gen_grad(torch, lib, ext)
+    if "hostile2d" in only:
+        gen_hostile2d(torch, lib, ext)
 
 
 if __name__ == "__main__":
