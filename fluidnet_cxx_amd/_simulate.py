@@ -9,7 +9,9 @@ batch_dict, same mconf keys).  Two execution modes:
 fused=True still runs operator by operator where the native step has no form of the call: output_div=True, a 3D state with
 flags_stick, a density BC without a 'density' key, and mconf['viscosity'] > 0 with a (dt, viscosity) pair whose double product the two
 floats of FnxStepParams do not give (about a third of all pairs, dt = 0.1 with viscosity = 0.05 among them; the reference rounds the
-product once, viscosity.py:64).  `workspace` and `static_flags` are then not used.  The same bits, more launches: until FnxStepParams
+product once, viscosity.py:64), and 'convnet' or 'hybrid' with a net of the reference's 'FluidNet' bank model (mconf['model'] =
+'FluidNet', 2D: the native step takes the ScaleNet image only; both methods call net(...) on the operator path, which runs the bank
+kernels of fnx_banknet.hip).  `workspace` and `static_flags` are then not used.  The same bits, more launches: until FnxStepParams
 carries the product (an ABI change) such a viscous 2D run is slower than one with, say, viscosity = 0.02.
 The reference's own call -- `simulate(mconf, batch_dict, net, sim_method)`, four arguments (plume.py:237) -- gets the static
 path by itself: the layer keeps one step workspace per (device, grid shape) and looks at `(data_ptr, _version, shape, stride)` of
@@ -228,7 +230,9 @@ def simulate(mconf, batch_dict, net, sim_method, output_div=False, fused=True, w
     # 3D states with flags_stick (the native step refuses them; fluid.setWallBcsStick takes 3D fields),
     # no 'density' key but a density BC: the reference applies setConstVals to its zeros (simulate.py:82-97), and
     # a (dt, viscosity) pair whose product the step's two floats do not give (_step_has_the_viscous_coefficient)
+    # and a net of the reference's 'FluidNet' bank model: the native step takes the ScaleNet image only (FluidNet.is_bank)
     simple = (not output_div and not (is3D and "flags_stick" in batch_dict)
+              and not (uses_net and getattr(net, "is_bank", False))
               and (has_density or not ("densityBC" in batch_dict and "densityBCInvMask" in batch_dict))
               and (viscosity == 0 or _step_has_the_viscous_coefficient(dt, viscosity)))
     if fused and simple:

@@ -33,6 +33,7 @@ HIP_UNITS = {
     # (resource-usage remarks: build_lib checks the kernels of SCRATCH_FREE)
     "fnx_cnn.hip": ["-Rpass-analysis=kernel-resource-usage"],
     "fnx_cnn_train.hip": ["-Rpass-analysis=kernel-resource-usage"],
+    "fnx_banknet.hip": ["-Rpass-analysis=kernel-resource-usage"],
     "fnx_slab.hip": [],
     "fnx_peer.hip": [],
 }
@@ -44,6 +45,10 @@ SCRATCH_FREE = {
                           "the MFMA kernel's nine 32x32 accumulators (144 VGPRs) live across the whole pixel march at two workgroups per "
                           "CU; a spill puts scratch traffic between the MFMAs.  The plain kernel slices a 5x5x5 layer by dz so that its "
                           "25 fp64 accumulators stay in registers"),
+    "fnx_banknet.hip": (["banknet_level_kernel"],
+                        "a lane keeps the 36 MFMA weight operands of a bank convolution (and, at full resolution, the tail's 12) in "
+                        "registers for the whole tile, and the 6x6x2 input patch of a 4x4 pooling window while it recomputes conv1; a "
+                        "spill puts a scratch reload in front of every MFMA"),
     "fnx_advect.hip": (["advect3d_fwd_tile_kernel", "advect3d_bwd_tile_kernel", "advect3d_bwd_scalar_tile_kernel",
                         "advect3d_bwd_vel_tile_kernel"],
                        "fnx_advect_march.h: the 3D advection marches run at 2-3 waves per SIMD with every VGPR in use; a reload from "

@@ -11,6 +11,9 @@ Inference only.  `FluidNet` is constructed and loaded the way the reference driv
 
 Weights are torch-style state-dict entries (`multiScale.convN_4.encode.0.weight` ...).  They are repacked for the MFMA
 kernels lazily, on the first forward on a given device (and again after `load_state_dict` / `.to()`).
+
+mconf['model'] = 'FluidNet' selects the reference's other net (model.py:177-209), the 16-channel bank net of `conv1`, `convBank`,
+`conv2`, `conv3` and `convOut`: `BankNet` / `net.bank(x)`, 2D, fp32 modes (csrc/fnx_banknet.hip).
 """
 from collections import OrderedDict
 
@@ -18,21 +21,28 @@ import numpy as np
 import torch
 
 from ._ext import ext
-from .weights import make_scalenet_weights, scalenet_layers
+from .weights import banknet_layers, make_banknet_weights, make_scalenet_weights, scalenet_layers
 
 # Parameters of the reference FluidNet that its ScaleNet forward never reads (model.py:59-72: conv1, convBank, conv2,
 # conv3, convOut are only used by the 'FluidNet' variant).  A checkpoint of the reference carries them; load_state_dict
 # keeps them verbatim so that state_dict() round-trips.
 _UNUSED_PREFIXES = ("conv1.", "convBank.", "conv2.", "conv3.", "convOut.", "scale.")
+# The other way round for the bank model (mconf['model'] = 'FluidNet', model.py:177-209): its forward reads those five modules and never
+# the MultiScaleNet, whose parameters a reference checkpoint carries all the same.
+_BANK_UNUSED_PREFIXES = ("multiScale.", "scale.")
 
 
 def _layer_keys(ndim):
     return [L["name"] + sfx for L in scalenet_layers(2, ndim) for sfx in (".weight", ".bias")]
 
 
-def blob_from_state_dict(sd, ndim=2):
+def _bank_keys():
+    return [L["name"] + sfx for L in banknet_layers() for sfx in (".weight", ".bias")]
+
+
+def blob_from_state_dict(sd, ndim=2, keys=None):
     parts = []
-    for k in _layer_keys(ndim):
+    for k in (_layer_keys(ndim) if keys is None else keys):
         v = sd[k]
         v = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
         parts.append(np.ascontiguousarray(v, np.float32).ravel())
@@ -60,6 +70,19 @@ class MultiScaleNet:
         return ext.multiscale_forward(self.packed, x.contiguous(), self.precision_mode, list(trim) if trim is not None else [])
 
 
+class BankNet:
+    """x (B,2,H,W) -> (B,1,H,W): the 16-channel bank net of model.py:177-209 (fnx_banknet.hip).  H and W multiples of 4, fp32 modes."""
+
+    def __init__(self, state_dict, device="cuda", precision_mode="fp32"):
+        self.is3D = False
+        self.precision_mode = precision_mode
+        blob = torch.from_numpy(blob_from_state_dict(state_dict, keys=_bank_keys())).to(device)
+        self.packed = ext.banknet_pack(blob)
+
+    def __call__(self, x):
+        return ext.banknet_forward(self.packed, x.contiguous(), self.precision_mode)
+
+
 class FluidNet:
     """input_ (B,5|6,D,H,W) = [p, U, flags, density] -> (p, U)   (model.py:76-227)
 
@@ -67,10 +90,18 @@ class FluidNet:
     compatibility -- every Dropout layer is the identity in eval mode, which is the only mode here (simulate.py:140).
     Supports the shipped configuration: model='ScaleNet', inputChannels={'div'}, normalizeInput on 'UDiv'.
     A freshly constructed net holds deterministic random-init weights of the reference architecture
-    (weights.make_scalenet_weights(0)); `load_state_dict` replaces them."""
+    (weights.make_scalenet_weights(0)); `load_state_dict` replaces them.
+
+    model='FluidNet' (what the reference's trainConfig.yaml ships) is the 16-channel bank net of model.py:177-209, 2D and fp32 modes
+    only: a fresh net holds weights.make_banknet_weights(0), `load_state_dict` requires the twelve conv1 / convBank / conv2 / conv3 /
+    convOut tensors and keeps multiScale.* and scale.*, `net.bank(x)` is the net alone, and `packed_for` raises -- the native step,
+    the z-slab drivers and the trainers take the ScaleNet image only; `simulate()` runs such a net operator by operator."""
 
     def __init__(self, mconf, dropout=True):
-        assert mconf.get("model", "ScaleNet") == "ScaleNet", "only the ScaleNet variant is accelerated"
+        model = mconf.get("model", "ScaleNet")
+        assert model in ("ScaleNet", "FluidNet"), "mconf['model'] must be 'ScaleNet' or 'FluidNet' (the 16-channel bank net)"
+        self.is_bank = model == "FluidNet"
+        assert not (self.is_bank and mconf.get("is3D", False)), "the 'FluidNet' bank model is 2D only (the reference asserts it)"
         ic = mconf.get("inputChannels", {"div": True, "pDiv": False, "UDiv": False})
         assert ic.get("div", False) and not ic.get("pDiv", False) and not ic.get("UDiv", False), \
             "inputChannels must be {div} (convModel_mconf.pth)"
@@ -84,7 +115,10 @@ class FluidNet:
         self.precision_mode = str(mconf.get("precisionMode", "fp32"))
         self.training = False
         self._ndim = 3 if self.is3D else 2
-        self._params = OrderedDict((k, torch.from_numpy(v)) for k, v in make_scalenet_weights(0, ndim=self._ndim).items())
+        init = make_banknet_weights(0) if self.is_bank else make_scalenet_weights(0, ndim=self._ndim)
+        self._params = OrderedDict((k, torch.from_numpy(v)) for k, v in init.items())
+        self._want = _bank_keys() if self.is_bank else _layer_keys(self._ndim)
+        self._unused = _BANK_UNUSED_PREFIXES if self.is_bank else _UNUSED_PREFIXES
         self._extra = OrderedDict()          # the reference's unused parameters, kept for state_dict()
         self._device = None                  # set by cuda()/to(); else the device of the first input
         self._ms = None                      # MultiScaleNet packed for `_ms_device`
@@ -125,11 +159,11 @@ class FluidNet:
         return sd
 
     def load_state_dict(self, state_dict, strict=True):
-        """Like nn.Module.load_state_dict: every multiScale.* parameter must be present with the right shape; the
-        reference FluidNet's parameters that the ScaleNet forward never reads are accepted and kept."""
-        want = _layer_keys(self._ndim)
+        """Like nn.Module.load_state_dict: every multiScale.* parameter (bank model: each of the twelve bank tensors) must be present
+        with the right shape; the reference FluidNet's parameters that this model's forward never reads are accepted and kept."""
+        want = self._want
         missing = [k for k in want if k not in state_dict]
-        unexpected = [k for k in state_dict if k not in self._params and not k.startswith(_UNUSED_PREFIXES)]
+        unexpected = [k for k in state_dict if k not in self._params and not k.startswith(self._unused)]
         if missing or (strict and unexpected):
             msg = "Error(s) in loading state_dict for FluidNet:"
             if missing:
@@ -147,7 +181,7 @@ class FluidNet:
                                    f"{tuple(self._params[k].shape)}.")
             new[k] = v.contiguous().clone()
         self._params = new
-        self._extra = OrderedDict((k, v) for k, v in state_dict.items() if k.startswith(_UNUSED_PREFIXES))
+        self._extra = OrderedDict((k, v) for k, v in state_dict.items() if k.startswith(self._unused))
         self._ms = None                      # repacked on the next forward / to()
         if self._device is not None:
             self._ensure_packed(self._device)
@@ -158,12 +192,26 @@ class FluidNet:
         if device.type == "cuda" and device.index is None:
             device = torch.device("cuda", torch.cuda.current_device())
         if self._ms is None or self._ms_device != device:
-            self._ms = MultiScaleNet(self._params, device, self.is3D, self.precision_mode)
+            self._ms = (BankNet(self._params, device, self.precision_mode) if self.is_bank
+                        else MultiScaleNet(self._params, device, self.is3D, self.precision_mode))
             self._ms_device = device
         return self._ms
 
+    def _not_scalenet(self, what):
+        raise RuntimeError(f"FluidNet.{what}: this net is the 'FluidNet' bank model; the native step, the z-slab drivers and the trainers "
+                           "take the ScaleNet image only (net.bank(x) and net(input) run the bank kernels)")
+
     @property
     def multiScale(self):
+        if self.is_bank:
+            self._not_scalenet("multiScale")
+        return self._ensure_packed(self._device if self._device is not None else "cuda")
+
+    @property
+    def bank(self):
+        """The bank net alone, x (B,2,H,W) -> (B,1,H,W): the counterpart of `multiScale` for model='FluidNet'."""
+        if not self.is_bank:
+            raise RuntimeError("FluidNet.bank: this net is the ScaleNet model (net.multiScale(x))")
         return self._ensure_packed(self._device if self._device is not None else "cuda")
 
     @property
@@ -172,11 +220,14 @@ class FluidNet:
 
     def packed_for(self, device):
         """The packed weight blob on `device` (what fnx_simulate_step takes as FnxState.net)."""
+        if self.is_bank:
+            self._not_scalenet("packed_for")
         return self._ensure_packed(device).packed
 
     def __call__(self, input_):
         ms = self._ensure_packed(input_.device)
-        p, U = ext.fluidnet_forward(ms.packed, input_.contiguous(), self.threshold, self.precision_mode)
+        fwd = ext.fluidnet_bank_forward if self.is_bank else ext.fluidnet_forward
+        p, U = fwd(ms.packed, input_.contiguous(), self.threshold, self.precision_mode)
         return p, U
 
     forward = __call__

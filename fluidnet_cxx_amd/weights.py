@@ -35,6 +35,18 @@ def scalenet_layers(in_dims=2, ndim=2):
     return out
 
 
+def banknet_layers():
+    """Layer table of the reference's 16-channel bank net (lib/model.py:57-71, mconf['model'] = 'FluidNet'; 2D only), in the
+    order of its weight blob.  conv2 is applied twice in the forward (model.py:204-205); convBank's one pair serves all three
+    levels."""
+    t = [("conv1", 2, 16, 3), ("convBank.block.0", 16, 16, 3), ("convBank.block.2", 16, 16, 3), ("conv2", 16, 16, 1),
+         ("conv3", 16, 8, 1), ("convOut", 8, 1, 1)]
+    return [dict(name=n, cin=ci, cout=co, k=k, relu=n != "convOut") for n, ci, co, k in t]
+
+
+_BANKNET_STREAM0 = 1000      # hash_uniform streams 1000 .. 1011: ScaleNet's are 0 .. 33
+
+
 def _splitmix64(x):
     x = (x + np.uint64(0x9E3779B97F4A7C15)).astype(np.uint64)
     z = x
@@ -64,4 +76,16 @@ def make_scalenet_weights(seed=0, in_dims=2, ndim=2, gain=1.0):
         w[L["name"] + ".weight"] = (hash_uniform(nw, 2 * li, seed) * np.float32(bound)).reshape(
             (L["cout"], L["cin"]) + kshape)
         w[L["name"] + ".bias"] = hash_uniform(L["cout"], 2 * li + 1, seed) * np.float32(bound)
+    return w
+
+
+def make_banknet_weights(seed=0, gain=1.0):
+    """name -> np.float32 array for the twelve parameter tensors of the bank net (5361 floats), torch's default bound."""
+    w = {}
+    for li, L in enumerate(banknet_layers()):
+        fan_in = L["cin"] * L["k"] * L["k"]
+        bound = gain / np.sqrt(fan_in)
+        w[L["name"] + ".weight"] = (hash_uniform(L["cout"] * fan_in, _BANKNET_STREAM0 + 2 * li, seed) * np.float32(bound)).reshape(
+            (L["cout"], L["cin"], L["k"], L["k"]))
+        w[L["name"] + ".bias"] = hash_uniform(L["cout"], _BANKNET_STREAM0 + 2 * li + 1, seed) * np.float32(bound)
     return w

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define FNX_ABI_VERSION 29
+#define FNX_ABI_VERSION 30
 
 enum {
   FNX_OK = 0,
@@ -690,6 +690,32 @@ int fnx_multiscale_forward_crop(const FnxGrid* g, const void* packed, const floa
 /* input: (B,5|6,D,H,W) = [p, U, flags, density] -> p_out (B,1,..), U_out (B,2|3,..) */
 int fnx_fluidnet_forward(const FnxGrid* g, const void* packed, const float* input, float normalize_threshold,
                          float* p_out, float* U_out, int precision_mode, void* ws, size_t ws_bytes, void* stream);
+
+/* The reference's 16-channel "bank" net (ABI 30): lib/model.py:177-209, what mconf['model'] = 'FluidNet' selects -- 2D inference only.
+ *   a = relu(conv1(x)); t = (bank(a) + up2(bank(avgpool2(a)))) + up4(bank(avgpool4(a))); bank = relu(block.2(relu(block.0(.)))), one set
+ *   of weights for the three levels, zero padding at each level's own border, nearest upsampling;
+ *   p = convOut(relu(conv3(relu(conv2(relu(conv2(t)))))))                       (conv2 is applied twice, model.py:204-205)
+ * weights_blob: fnx_banknet_weight_floats() = 5361 floats, DEVICE pointer: conv1, convBank.block.0, convBank.block.2, conv2, conv3,
+ * convOut, for each the torch-layout weight (Cout,Cin,kh,kw) then bias.  fnx_banknet_pack repacks it into `packed`
+ * (fnx_banknet_packed_bytes()) in the operand order of v_mfma_f32_16x16x4_f32.
+ * Every entry point refuses, before it touches the device and each with its own fnx_last_error text: null arguments; a 3D grid (the
+ * reference asserts 2D); an unknown precision mode; the bf16 modes (every fp32 mode runs the one exact-fp32 kernel family); H or W that
+ * is no multiple of 4 (the reference's sum of the three levels raises there); a short workspace (FNX_EWORKSPACE).
+ * Three launches, no atomics, no host synchronisation (capturable); a sample's result does not depend on the rest of the batch.
+ * Workspace: fnx_banknet_ws_bytes(g, 0) for the net alone -- the two coarser banks' results, 20 bytes per full-resolution cell --
+ * and fnx_banknet_ws_bytes(g, 1) for the whole forward (0 for a grid without a workspace size). */
+size_t fnx_banknet_weight_floats(void);
+size_t fnx_banknet_packed_bytes(void);
+int fnx_banknet_pack(const float* weights_blob, void* packed, void* stream);
+size_t fnx_banknet_ws_bytes(const FnxGrid* g, int whole_forward);
+/* x: (B,2,H,W) [div/s, occupancy] -> p (B,1,H,W) */
+int fnx_banknet_forward(const FnxGrid* g, const void* packed, const float* x, float* p, int precision_mode, void* ws, size_t ws_bytes,
+                        void* stream);
+/* fnx_fluidnet_forward's contract with the bank net in the middle: input (B,5,1,H,W) = [p, U, flags, density] -> p_out (B,1,1,H,W),
+ * U_out (B,2,1,H,W); the launches around the net are fnx_fluidnet_forward's.  fnx_simulate_step, fnx_slab_step and FnxState.net take the
+ * ScaleNet image only. */
+int fnx_fluidnet_bank_forward(const FnxGrid* g, const void* packed, const float* input, float normalize_threshold, float* p_out,
+                              float* U_out, int precision_mode, void* ws, size_t ws_bytes, void* stream);
 
 /* Training of the 2D net (ABI 21): gradients of a scalar loss of p (or of FluidNet.forward's (p, U)) with respect to the 34 parameter
  * tensors, fp32 arithmetic only.  Every entry point checks, before it touches the device: a 2D grid (is3D = 0, D = 1) and a precision mode

@@ -1,0 +1,71 @@
+"""A float64 torch model of the reference's 16-channel bank net (lib/model.py:177-209, mconf['model'] = 'FluidNet'), written from
+the statement of the net and sharing no code with the kernels:
+
+    a  = relu(conv1(x))                                   2 -> 16, 3x3, zero padding 1
+    a1 = avgpool2(a); a2 = avgpool4(a)
+    bank(t) = relu(cB2(relu(cB0(t))))                     16 -> 16 -> 16, 3x3, zero padding 1 at that level's border, one set of weights
+    t  = (bank(a) + up2(bank(a1))) + up4(bank(a2))        nearest
+    t  = relu(conv2(t)); t = relu(conv2(t)); t = relu(conv3(t)); p = convOut(t)
+
+`drop` leaves one level (0: full, 1: half, 2: quarter resolution) out of the sum: the tests use it to show that every level reaches
+the output under the weights they use.  propagating_bank_weights are those weights: default-scale weights give an output that is its
+bias constant to within a few per cent, which would hide almost any error of the kernels.
+"""
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from fluidnet_cxx_amd.weights import banknet_layers, make_banknet_weights
+
+SHAPES = [(1, 4, 4), (2, 8, 12), (1, 16, 24), (3, 36, 68), (1, 132, 260)]     # (B, H, W)
+GOLDEN_SHAPES = SHAPES[:4]
+
+
+def propagating_bank_weights(seed=0):
+    """make_banknet_weights(seed) scaled to He-uniform: weights x sqrt(6) for a layer followed by ReLU, x sqrt(3) for convOut,
+    biases x 0.1 (as cnn_reference.propagating_weights).  float32, the same names and shapes."""
+    w = make_banknet_weights(seed)
+    for L in banknet_layers():
+        g = np.sqrt(6.0) if L["relu"] else np.sqrt(3.0)
+        w[L["name"] + ".weight"] = (w[L["name"] + ".weight"].astype(np.float64) * g).astype(np.float32)
+        w[L["name"] + ".bias"] = (w[L["name"] + ".bias"].astype(np.float64) * 0.1).astype(np.float32)
+    return w
+
+
+def bank_input(B, H, W, seed=0, boxes=False):
+    """x (B,2,H,W) float32 = [a normalised-divergence-like field in [-1, 1), occupancy]: a wall of one cell, and with `boxes` two
+    obstacle boxes inside; the first channel is zero in occupied cells, as the divergence is."""
+    from fluidnet_cxx_amd.weights import hash_uniform
+    x = np.zeros((B, 2, H, W), np.float32)
+    x[:, 0] = hash_uniform(B * H * W, 2000 + seed).reshape(B, H, W)
+    occ = np.zeros((H, W), np.float32)
+    occ[0], occ[-1], occ[:, 0], occ[:, -1] = 1, 1, 1, 1
+    if boxes:
+        occ[H // 4:H // 4 + 3, W // 3:W // 3 + 5] = 1
+        occ[H // 2:H // 2 + 4, 2 * W // 3:2 * W // 3 + 2] = 1
+    x[:, 1] = occ
+    x[:, 0] *= 1 - occ
+    return x
+
+
+def banknet_forward64(weights, x, drop=None):
+    """p (B,1,H,W) float64 of the net above for x (B,2,H,W); weights: name -> array or tensor."""
+    w = {k: torch.as_tensor(np.asarray(v), dtype=torch.float64) for k, v in weights.items()}
+    x = torch.as_tensor(np.asarray(x), dtype=torch.float64)
+    assert x.dim() == 4 and x.size(1) == 2 and x.size(2) % 4 == 0 and x.size(3) % 4 == 0
+
+    def conv(t, name, pad):
+        return F.conv2d(t, w[name + ".weight"], w[name + ".bias"], padding=pad)
+
+    def bank(t):
+        return F.relu(conv(F.relu(conv(t, "convBank.block.0", 1)), "convBank.block.2", 1))
+
+    a = F.relu(conv(x, "conv1", 1))
+    levels = [bank(a),
+              bank(F.avg_pool2d(a, 2)).repeat_interleave(2, 2).repeat_interleave(2, 3),
+              bank(F.avg_pool2d(a, 4)).repeat_interleave(4, 2).repeat_interleave(4, 3)]
+    t = sum(l for i, l in enumerate(levels) if i != drop)
+    t = F.relu(conv(t, "conv2", 0))
+    t = F.relu(conv(t, "conv2", 0))
+    t = F.relu(conv(t, "conv3", 0))
+    return conv(t, "convOut", 0)
