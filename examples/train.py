@@ -3,11 +3,14 @@
 Mantaflow data set, on scenes generated while training (fluidnet_cxx_amd/training.py; with --depth fluidnet_cxx_amd/training3d.py).
 
     python examples/train.py [--res 128] [--batch 64] [--iters 1000] [--seed 0] [--out convModel.pth] [--lr 5e-5] [--eval-every 50]
-                             [--no-long-term] [--resume CKPT] [--report FILE] [--depth N]
+                             [--no-long-term] [--resume CKPT] [--report FILE] [--depth N] [--model {ScaleNet,FluidNet}]
 
 Writes a checkpoint {'state_dict', 'optimizer', 'mconf', 'it', ...} that `FluidNet.load_state_dict` takes and
 `examples/plume.py --method convnet --weights` runs.  With --report the loss curve, the held-out ratio divL2(net's U) / divL2(U before
 the projection) and the number of Jacobi sweeps that reach the same held-out divL2 on the same scenes go to FILE as text.
+
+`--model FluidNet` trains the reference's 16-channel bank net (what its trainConfig.yaml ships; 2D, res a multiple of 4) instead of the
+ScaleNet; `examples/plume.py` picks the net from the checkpoint's mconf.
 
 `--depth N` (N >= 4) trains the 3D net on a N x res x res grid instead (the defaults become --res 64 --batch 4); its checkpoint goes to
 `examples/plume.py --depth N --method convnet --weights3d`.  The report then has no Jacobi line."""
@@ -35,7 +38,10 @@ def parse_args(argv=None):
     ap.add_argument("--resume", default=None, metavar="CKPT")
     ap.add_argument("--report", default=None, metavar="FILE")
     ap.add_argument("--depth", type=int, default=None, metavar="N", help="train the 3D net on N x res x res cells (N >= 4)")
+    ap.add_argument("--model", choices=("ScaleNet", "FluidNet"), default="ScaleNet", help="FluidNet: the 16-channel bank net (2D only)")
     a = ap.parse_args(argv)
+    if a.depth is not None and a.model != "ScaleNet":
+        ap.error("--model FluidNet is 2D only (the reference asserts it); --depth trains the 3D ScaleNet")
     if a.depth is not None and a.depth < 4:
         ap.error("--depth must be at least 4 (the net's three scales need 4 planes); without --depth the 2D net is trained")
     is3d = a.depth is not None
@@ -49,7 +55,7 @@ def main(argv=None):
     is3d = a.depth is not None
     if is3d:
         from fluidnet_cxx_amd.training3d import MCONF3D_DEFAULTS, evaluate3d, train3d
-    mconf = dict(MCONF3D_DEFAULTS if is3d else MCONF_DEFAULTS, lr=a.lr)
+    mconf = dict(MCONF3D_DEFAULTS if is3d else MCONF_DEFAULTS, lr=a.lr, model=a.model)
     if a.no_long_term:
         mconf["divLongTermLambda"] = 0.0
     tconf = dict(res=a.res, batch=a.batch, iters=a.iters, seed=a.seed, evalEvery=a.eval_every)
@@ -64,7 +70,7 @@ def main(argv=None):
     ev = (evaluate3d if is3d else evaluate)(run["net"], run["held_out"], lam)
     ratio = ev["divL2_out"] / ev["divL2_in"]
     sweeps = None if is3d else jacobi_sweeps_to_reach(run["held_out"], ev["divL2_out"])
-    lines = [f"examples/train.py{f' --depth {a.depth}' if is3d else ''} --res {a.res} --batch {a.batch} --iters {a.iters} --seed {a.seed} --lr {a.lr:g}"
+    lines = [f"examples/train.py{f' --depth {a.depth}' if is3d else ''} {'' if a.model == 'ScaleNet' else f' --model {a.model}'} --res {a.res} --batch {a.batch} --iters {a.iters} --seed {a.seed} --lr {a.lr:g}"
              f"{' --no-long-term' if a.no_long_term else ''}: {seconds:.1f} s wall ({seconds / max(a.iters, 1) * 1e3:.1f} ms per iteration, "
              "sampler, evaluation and checkpoint included)",
              f"held-out ({len(run['held_out'])} batches of another seed): loss {ev['loss']:.4e}, divL2 of the net's U {ev['divL2_out']:.4e}, "

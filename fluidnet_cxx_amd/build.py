@@ -34,6 +34,7 @@ HIP_UNITS = {
     "fnx_cnn.hip": ["-Rpass-analysis=kernel-resource-usage"],
     "fnx_cnn_train.hip": ["-Rpass-analysis=kernel-resource-usage"],
     "fnx_banknet.hip": ["-Rpass-analysis=kernel-resource-usage"],
+    "fnx_banknet_train.hip": ["-Rpass-analysis=kernel-resource-usage"],
     "fnx_slab.hip": [],
     "fnx_peer.hip": [],
 }
@@ -49,6 +50,11 @@ SCRATCH_FREE = {
                         "a lane keeps the 36 MFMA weight operands of a bank convolution (and, at full resolution, the tail's 12) in "
                         "registers for the whole tile, and the 6x6x2 input patch of a 4x4 pooling window while it recomputes conv1; a "
                         "spill puts a scratch reload in front of every MFMA"),
+    "fnx_banknet_train.hip": (["banknet_level_tape_kernel", "bank_tail_bwd_kernel", "bank_level_bwd_kernel", "bank_conv1_bwd_kernel"],
+                              "the level kernels keep a convolution's 36 MFMA weight operands and, in the backward, the 72 accumulator "
+                              "registers of the two weight gradients across the workgroup's tiles at two workgroups per CU; the tail "
+                              "and conv1 kernels keep their accumulators across the cell march; a spill puts scratch traffic between "
+                              "the MFMAs"),
     "fnx_advect.hip": (["advect3d_fwd_tile_kernel", "advect3d_bwd_tile_kernel", "advect3d_bwd_scalar_tile_kernel",
                         "advect3d_bwd_vel_tile_kernel"],
                        "fnx_advect_march.h: the 3D advection marches run at 2-3 waves per SIMD with every VGPR in use; a reload from "

@@ -802,6 +802,113 @@ Tensor fluidnet_backward(bool is3d, Tensor packed_t, Tensor flags, Tensor scale,
   return grad;
 }
 
+// ---- training of the bank net (fnx_banknet_train.hip): the bodies above with the bank entry points; a grid the C ABI refuses gets a
+// token tape and workspace, so that the C ABI's text is what is raised ----------------------------------------------------------------
+static size_t bank_tape_floats(const FnxGrid& g) { return fnx_banknet_tape_layout(&g, nullptr); }
+static void check_banknet_image_t(const Tensor& packed_t, const Tensor& like) {
+  TORCH_CHECK(packed_t.is_cuda() && packed_t.is_contiguous() && packed_t.get_device() == like.get_device() &&
+              (size_t)packed_t.nbytes() == fnx_banknet_packed_t_bytes(),
+              "packed_t must be the ", fnx_banknet_packed_t_bytes(), "-byte image from banknet_pack_t on the input's device (got ", packed_t.nbytes(),
+              " bytes)");
+}
+
+Tensor banknet_pack_t(Tensor blob) {
+  TORCH_CHECK(blob.is_cuda() && blob.scalar_type() == at::kFloat && blob.is_contiguous(), "weights blob must be a contiguous float32 GPU tensor");
+  TORCH_CHECK((size_t)blob.numel() == fnx_banknet_weight_floats(), "weights blob has ", blob.numel(), " floats, expected ",
+              fnx_banknet_weight_floats());
+  c10::hip::HIPGuard guard(blob.get_device());
+  Tensor packed = at::zeros({(int64_t)fnx_banknet_packed_t_bytes()}, blob.options().dtype(at::kByte));
+  check_status(fnx_banknet_pack_t(blob.data_ptr<float>(), packed.data_ptr(), cur_stream(blob)));
+  return packed;
+}
+
+// -> (name, offset, C, H, W) per tape entry
+std::vector<py::tuple> banknet_tape_layout(int64_t B, int64_t H, int64_t W) {
+  const FnxGrid g = make_grid(B, 1, H, W, false);
+  std::vector<FnxTapeEntry> e(fnx_banknet_tape_entries());
+  if (fnx_banknet_tape_layout(&g, e.data()) == 0) check_status(FNX_EINVAL);
+  std::vector<py::tuple> out;
+  for (const FnxTapeEntry& t : e) out.push_back(py::make_tuple(std::string(t.name), (int64_t)t.offset, t.C, t.H, t.W));
+  return out;
+}
+
+// x (B,2,H,W) -> p, tape
+std::vector<Tensor> banknet_forward_train(Tensor packed, Tensor x, const std::string& precision_mode) {
+  const FnxGrid g = grid_of_net_tensor(x, "x");
+  TORCH_CHECK(x.size(1) == 2, "x must have 2 channels");
+  check_banknet_image(packed);
+  c10::hip::HIPGuard guard(x.get_device());
+  std::vector<int64_t> osz = x.sizes().vec(); osz[1] = 1;
+  Tensor p = at::empty(osz, x.options());
+  const size_t floats = bank_tape_floats(g);
+  Tensor tape = at::empty({(int64_t)(floats ? floats : 1)}, x.options());
+  check_status(fnx_banknet_forward_train(&g, packed.data_ptr(), x.data_ptr<float>(), p.data_ptr<float>(), tape.data_ptr<float>(),
+                                         precision_of(precision_mode), cur_stream(x)));
+  return {p, tape};
+}
+
+// grad_p (B,1,H,W), the forward's tape and x -> the gradient in the blob's layout
+Tensor banknet_backward(Tensor packed_t, Tensor x, Tensor grad_p, Tensor tape, const std::string& precision_mode) {
+  const FnxGrid g = grid_of_net_tensor(grad_p, "grad_p");
+  grid_of_net_tensor(x, "x");
+  TORCH_CHECK(grad_p.size(1) == 1 && x.size(1) == 2 && x.dim() == grad_p.dim() && x.size(0) == grad_p.size(0) &&
+              x.size(x.dim() - 2) == grad_p.size(x.dim() - 2) && x.size(x.dim() - 1) == grad_p.size(x.dim() - 1),
+              "grad_p (1 channel) and x (2 channels) must share their grid");
+  check_banknet_image_t(packed_t, grad_p);
+  const size_t floats = bank_tape_floats(g);
+  check_tape(tape, floats);
+  c10::hip::HIPGuard guard(grad_p.get_device());
+  Tensor grad = at::empty({(int64_t)fnx_banknet_weight_floats()}, grad_p.options());
+  const size_t bytes = std::max<size_t>(floats ? fnx_banknet_backward_ws_bytes(&g) : 0, 256);
+  Tensor ws = at::empty({(int64_t)bytes}, grad_p.options().dtype(at::kByte));
+  check_status(fnx_banknet_backward(&g, packed_t.data_ptr(), x.data_ptr<float>(), grad_p.data_ptr<float>(), tape.data_ptr<float>(),
+                                    grad.data_ptr<float>(), precision_of(precision_mode), ws.data_ptr(), bytes, cur_stream(grad_p)));
+  return grad;
+}
+
+// input (B,5,1,H,W) = [p, U, flags, density] -> p, U, tape, s (B), flags (B,1,1,H,W)
+std::vector<Tensor> fluidnet_bank_forward_train(Tensor packed, Tensor input, double normalize_threshold, const std::string& precision_mode) {
+  check_field(input, "input");
+  TORCH_CHECK(input.size(1) == 5 || input.size(1) == 6, "input must have 5 (2D) or 6 (3D) channels [p, U, flags, density]");
+  const FnxGrid g = make_grid(input.size(0), input.size(2), input.size(3), input.size(4), input.size(1) == 6);
+  check_banknet_image(packed);
+  c10::hip::HIPGuard guard(input.get_device());
+  Tensor p = at::empty({g.B, 1, g.D, g.H, g.W}, input.options());
+  Tensor U = at::empty({g.B, g.is3D ? 3 : 2, g.D, g.H, g.W}, input.options());
+  Tensor flags = at::empty({g.B, 1, g.D, g.H, g.W}, input.options());
+  Tensor scale = at::empty({g.B}, input.options());
+  const size_t floats = bank_tape_floats(g);
+  const size_t bytes = std::max<size_t>(floats ? fnx_fluidnet_bank_train_ws_bytes(&g) : 0, 256);
+  Tensor tape = at::empty({(int64_t)(floats ? floats : 1)}, input.options());
+  Tensor ws = at::empty({(int64_t)bytes}, input.options().dtype(at::kByte));
+  check_status(fnx_fluidnet_bank_forward_train(&g, packed.data_ptr(), input.data_ptr<float>(), (float)normalize_threshold, p.data_ptr<float>(),
+                                               U.data_ptr<float>(), flags.data_ptr<float>(), scale.data_ptr<float>(), tape.data_ptr<float>(),
+                                               precision_of(precision_mode), ws.data_ptr(), bytes, cur_stream(input)));
+  return {p, U, tape, scale, flags};
+}
+
+// grad_p (B,1,1,H,W), grad_U (B,2,1,H,W), flags and scale of the forward -> the gradient in the blob's layout
+Tensor fluidnet_bank_backward(Tensor packed_t, Tensor flags, Tensor scale, Tensor grad_p, Tensor grad_U, Tensor tape,
+                              const std::string& precision_mode) {
+  check_field(grad_p, "grad_p"); check_field(grad_U, "grad_U"); check_field(flags, "flags");
+  TORCH_CHECK(grad_p.size(1) == 1 && grad_U.size(1) == 2 && flags.size(1) == 1, "grad_p and flags must have 1 channel, grad_U 2");
+  TORCH_CHECK(grad_U.size(0) == grad_p.size(0) && grad_U.size(2) == grad_p.size(2) && grad_U.size(3) == grad_p.size(3) &&
+              grad_U.size(4) == grad_p.size(4) && flags.sizes() == grad_p.sizes(), "grad_p, grad_U and flags must share their grid");
+  const FnxGrid g = make_grid(grad_p.size(0), grad_p.size(2), grad_p.size(3), grad_p.size(4), grad_p.size(2) > 1);
+  check_banknet_image_t(packed_t, grad_p);
+  TORCH_CHECK(scale.is_cuda() && scale.scalar_type() == at::kFloat && scale.is_contiguous() && scale.numel() == g.B, "scale must hold B floats on the GPU");
+  const size_t floats = bank_tape_floats(g);
+  check_tape(tape, floats);
+  c10::hip::HIPGuard guard(grad_p.get_device());
+  Tensor grad = at::empty({(int64_t)fnx_banknet_weight_floats()}, grad_p.options());
+  const size_t bytes = std::max<size_t>(floats ? fnx_fluidnet_bank_train_ws_bytes(&g) : 0, 256);
+  Tensor ws = at::empty({(int64_t)bytes}, grad_p.options().dtype(at::kByte));
+  check_status(fnx_fluidnet_bank_backward(&g, packed_t.data_ptr(), flags.data_ptr<float>(), scale.data_ptr<float>(), grad_p.data_ptr<float>(),
+                                          grad_U.data_ptr<float>(), tape.data_ptr<float>(), grad.data_ptr<float>(), precision_of(precision_mode),
+                                          ws.data_ptr(), bytes, cur_stream(grad_p)));
+  return grad;
+}
+
 // the grid of B scenes: 3D if it has more than one plane, whichever name was called
 static FnxGrid scene_grid(const Tensor& ids, int64_t D, int64_t H, int64_t W) {
   TORCH_CHECK(ids.is_cuda() && ids.scalar_type() == at::kInt && ids.dim() == 1 && ids.is_contiguous() && ids.numel() >= 1,
@@ -1257,6 +1364,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("banknet_forward", &banknet_forward, py::arg("packed"), py::arg("x"), py::arg("precision_mode") = "fp32", NoGil());
   m.def("fluidnet_bank_forward", &fluidnet_bank_forward, py::arg("packed"), py::arg("input"), py::arg("normalize_threshold"),
         py::arg("precision_mode") = "fp32", NoGil());
+  m.def("banknet_pack_t", &banknet_pack_t, py::arg("blob"), NoGil());
+  m.def("banknet_tape_layout", &banknet_tape_layout, py::arg("B"), py::arg("H"), py::arg("W"));
+  m.def("banknet_forward_train", &banknet_forward_train, py::arg("packed"), py::arg("x"), py::arg("precision_mode") = "fp32", NoGil());
+  m.def("banknet_backward", &banknet_backward, py::arg("packed_t"), py::arg("x"), py::arg("grad_p"), py::arg("tape"),
+        py::arg("precision_mode") = "fp32", NoGil());
+  m.def("fluidnet_bank_forward_train", &fluidnet_bank_forward_train, py::arg("packed"), py::arg("input"), py::arg("normalize_threshold"),
+        py::arg("precision_mode") = "fp32", NoGil());
+  m.def("fluidnet_bank_backward", &fluidnet_bank_backward, py::arg("packed_t"), py::arg("flags"), py::arg("scale"), py::arg("grad_p"),
+        py::arg("grad_U"), py::arg("tape"), py::arg("precision_mode") = "fp32", NoGil());
   m.def("simulate_step_", &simulate_step_, py::arg("p"), py::arg("U"), py::arg("flags"), py::arg("density"), py::arg("UBC"),
         py::arg("UBCInvMask"), py::arg("densityBC"), py::arg("densityBCInvMask"), py::arg("net"), py::arg("dt"),
         py::arg("maccormack_strength"), py::arg("sample_outside_fluid"), py::arg("buoyancy_scale"), py::arg("gravity_vec"),

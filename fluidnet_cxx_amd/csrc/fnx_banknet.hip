@@ -26,31 +26,10 @@
 // planes of a 32-lane group on disjoint banks.  D holds channels 4g .. 4g+3 of one cell in lane group g: register r of the result IS the
 // B operand of a following 1x1 layer whose A operand carries the weights of input channels 4g + r, which is how the tail is packed.
 // No atomics; a cell's value is a fixed-order sum that does not depend on the batch or on the tile it falls into.
-#include <hip/hip_runtime.h>
-#include "fnx_cnn.h"
-#include "fnx_kernels.h"
-#include "../../include/fluidnet_hip.h"
+#include "fnx_banknet_tile.h"
 
 namespace fnx {
 namespace {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-// the blob: conv1, convBank.block.0, convBank.block.2, conv2, conv3, convOut; each weight (Cout, Cin, k, k) then bias
-// (float offsets: conv1 0 / 288, block.0 304 / 2608, block.2 2624 / 4928, conv2 4944 / 5200, conv3 5216 / 5344, convOut 5352 / 5360)
-constexpr int BLOB_WB0 = 304, BLOB_WB2 = 2624, BLOB_W2 = 4944, BLOB_B2 = 5200, BLOB_W3 = 5216, BLOB_B3 = 5344, BLOB_WO = 5352, BLOB_BO = 5360,
-              BLOB_FLOATS = 5361;
-// the packed image (floats)
-constexpr int PK_W1 = 0;            // [cout 16][cin 2][3][3], the blob's own order
-constexpr int PK_B1 = 288;          // 16
-constexpr int PK_WB0 = 304;         // [tap 9][kc 4][lane 64] = W[cout = lane & 15][cin = 4 kc + (lane >> 4)][tap]
-constexpr int PK_BB0 = 2608;        // 16
-constexpr int PK_WB2 = 2624;
-constexpr int PK_BB2 = 4928;
-// the 1x1 tail, 272 floats per layer: [r 4][lane 64] = W[cout = lane & 15][cin = 4 (lane >> 4) + r], then 16 biases; rows and input
-// channels a layer does not have are zero (conv3: 8 rows; convOut: row 0, input channels 0..7)
-constexpr int PK_W2 = 4944;         // conv2 4944, conv3 5216, convOut 5488
-constexpr int PK_FLOATS = 5760;
 
 __global__ void banknet_pack_kernel(const float* __restrict__ blob, float* __restrict__ pk) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -83,207 +62,12 @@ __global__ void banknet_pack_kernel(const float* __restrict__ blob, float* __res
   pk[i] = v;
 }
 
-// The geometry of a level-R tile (floats).
-template <int R, int TH, int TW>
-struct BankTile {
-  static constexpr int P = TW + 4;                       // pitch of the planes: the tile and two halo cells on either side
-  static constexpr int ROWS = TH + 4;
-  static constexpr int NA = ROWS * P;                    // pooled cells
-  static constexpr int Q0 = (TH + 2) * P;                // flattened positions of cB0 (the tile + 1), of cB2 (the tile)
-  static constexpr int Q2 = TH * P;
-  static constexpr int G0 = (Q0 + 15) / 16, G2 = (Q2 + 15) / 16;
-  // a wave takes two groups at a time, so positions up to 16 (G0 + 1) are computed, and a position reads up to 2 P + 2 beyond itself
-  static constexpr int SMIN = 16 * (G0 + 1) + 2 * P + 2;
-  static constexpr int S = (SMIN + 15) / 32 * 32 + 16;   // >= SMIN, = 16 (mod 32)
-  static constexpr int XH = ROWS * R + 2, XW = P * R + 2;
-  static constexpr int XFLOATS = 2 * XH * XW;
-  static constexpr int BUF2 = 16 * S > XFLOATS ? 16 * S : XFLOATS;     // the x tile, then b0
-  static constexpr int LDS_FLOATS = 16 * S + BUF2;
-  static_assert(S >= SMIN && S % 32 == 16 && NA <= S, "plane stride");
-  static_assert(LDS_FLOATS * 4 <= 64 * 1024, "static LDS");
-};
-
-// One 3x3 bank convolution over `ngroups` groups of 16 flattened positions of the LDS planes at `src` (stride S, pitch P), two groups per
-// wave and step (two independent accumulators).  epi(q of this lane, the four channels 4 (lane >> 4) + r after bias, before ReLU).
-template <int P, int S, typename Epi>
-__device__ __forceinline__ void bank_conv(const float* __restrict__ wpk, const float* __restrict__ bias, const float* src, int ngroups,
-                                          int wave, int lane, Epi epi) {
-  float wa[36];
-#pragma unroll
-  for (int i = 0; i < 36; ++i) wa[i] = wpk[i * 64 + lane];
-  f32x4 b4;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) b4[r] = bias[4 * (lane >> 4) + r];
-  const float* sp = src + (lane >> 4) * S + (lane & 15);
-  for (int grp = 2 * wave; grp < ngroups; grp += 8) {
-    const float* s0 = sp + grp * 16;
-    f32x4 acc0 = b4, acc1 = b4;
-#pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-      for (int kc = 0; kc < 4; ++kc) {
-        const int off = kc * 4 * S + (t / 3) * P + (t % 3);
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[t * 4 + kc], s0[off], acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[t * 4 + kc], s0[off + 16], acc1, 0, 0, 0);
-      }
-    epi(grp * 16 + (lane & 15), acc0);
-    epi(grp * 16 + 16 + (lane & 15), acc1);
-  }
-}
-
 // x (B, 2, H, W).  R = 4, 2: out (B, 16, H/R, W/R).  R = 1: l2, l4 the coarser results, p (B, 1, H, W).  256 threads.
 template <int R, int TH, int TW>
 __global__ __launch_bounds__(256) void banknet_level_kernel(const float* __restrict__ pk, const float* __restrict__ x, int H, int W,
                                                             float* __restrict__ out, const float* __restrict__ l2,
                                                             const float* __restrict__ l4, float* __restrict__ p) {
-  using T = BankTile<R, TH, TW>;
-  constexpr int P = T::P, S = T::S;
-  __shared__ float lds[T::LDS_FLOATS];
-  float* const la = lds;                 // pooled relu(conv1): [16][S]
-  float* const lx = lds + 16 * S;        // x tile [2][XH][XW], then b0 [16][S]
-  float* const lb = lx;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int b = blockIdx.z;
-  const int HR = H / R, WR = W / R;
-  const int ty0 = blockIdx.y * TH, tx0 = blockIdx.x * TW;
-
-  // 1. the x tile
-  {
-    const int oy = (ty0 - 2) * R - 1, ox = (tx0 - 2) * R - 1;
-    const float* xb = x + (size_t)b * 2 * H * W;
-    for (int i = tid; i < T::XFLOATS; i += 256) {
-      const int c = i / (T::XH * T::XW), rem = i % (T::XH * T::XW);
-      const int gy = oy + rem / T::XW, gx = ox + rem % T::XW;
-      float v = 0.f;
-      if (gy >= 0 && gy < H && gx >= 0 && gx < W) v = xb[((size_t)c * H + gy) * W + gx];
-      lx[i] = v;
-    }
-  }
-  __syncthreads();
-
-  // 2. relu(conv1) pooled over R x R: wave w computes channels 4w .. 4w+3 of every pooled cell
-  {
-    float w1[4][18], b1[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      b1[c] = pk[PK_B1 + 4 * wave + c];
-#pragma unroll
-      for (int k = 0; k < 18; ++k) w1[c][k] = pk[PK_W1 + (4 * wave + c) * 18 + k];
-    }
-    for (int n = lane; n < T::NA; n += 64) {
-      const int y = n / P, xx = n % P;
-      const int ly = ty0 - 2 + y, lxx = tx0 - 2 + xx;
-      float pool[4] = {0.f, 0.f, 0.f, 0.f};
-      if (ly >= 0 && ly < HR && lxx >= 0 && lxx < WR) {
-        float in[2][R + 2][R + 2];
-#pragma unroll
-        for (int c = 0; c < 2; ++c)
-#pragma unroll
-          for (int dy = 0; dy < R + 2; ++dy)
-#pragma unroll
-            for (int dx = 0; dx < R + 2; ++dx) in[c][dy][dx] = lx[(c * T::XH + y * R + dy) * T::XW + xx * R + dx];
-#pragma unroll
-        for (int py = 0; py < R; ++py)
-#pragma unroll
-          for (int px = 0; px < R; ++px) {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-              float acc = b1[c];
-#pragma unroll
-              for (int ci = 0; ci < 2; ++ci)
-#pragma unroll
-                for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-                  for (int dx = 0; dx < 3; ++dx) acc = fmaf(w1[c][ci * 9 + dy * 3 + dx], in[ci][py + dy][px + dx], acc);
-              pool[c] += fmaxf(acc, 0.f);
-            }
-          }
-#pragma unroll
-        for (int c = 0; c < 4; ++c) pool[c] *= 1.f / (float)(R * R);
-      }
-#pragma unroll
-      for (int c = 0; c < 4; ++c) la[(4 * wave + c) * S + n] = pool[c];
-    }
-  }
-  __syncthreads();
-
-  // 3. cB0 on the tile + 1: position q = (y, x) of b0 is level cell (ty0 - 1 + y, tx0 - 1 + x)
-  bank_conv<P, S>(pk + PK_WB0, pk + PK_BB0, la, T::G0, wave, lane, [&](int q, f32x4 v) {
-    const int ly = ty0 - 1 + q / P, lxx = tx0 - 1 + q % P;
-    const bool in = ly >= 0 && ly < HR && lxx >= 0 && lxx < WR;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) lb[(4 * (lane >> 4) + r) * S + q] = in ? fmaxf(v[r], 0.f) : 0.f;
-  });
-  __syncthreads();
-
-  // 4. cB2 on the tile: position q = (y, x) is level cell (ty0 + y, tx0 + x)
-  if constexpr (R != 1) {
-    float* ob = out + (size_t)b * 16 * HR * WR;
-    bank_conv<P, S>(pk + PK_WB2, pk + PK_BB2, lb, T::G2, wave, lane, [&](int q, f32x4 v) {
-      const int y = q / P, xx = q % P;
-      const int ly = ty0 + y, lxx = tx0 + xx;
-      if (y < TH && xx < TW && ly < HR && lxx < WR) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) ob[((size_t)(4 * (lane >> 4) + r) * HR + ly) * WR + lxx] = fmaxf(v[r], 0.f);
-      }
-    });
-  } else {
-    float wt[3][4];
-    f32x4 bt[3];
-#pragma unroll
-    for (int l = 0; l < 3; ++l) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        wt[l][r] = pk[PK_W2 + l * 272 + r * 64 + lane];
-        bt[l][r] = pk[PK_W2 + l * 272 + 256 + 4 * (lane >> 4) + r];
-      }
-    }
-    const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4;
-    const float* l2b = l2 + (size_t)b * 16 * H2 * W2;
-    const float* l4b = l4 + (size_t)b * 16 * H4 * W4;
-    float* pb = p + (size_t)b * H * W;
-    bank_conv<P, S>(pk + PK_WB2, pk + PK_BB2, lb, T::G2, wave, lane, [&](int q, f32x4 v) {
-      const int y = q / P, xx = q % P;
-      const int ly = ty0 + y, lxx = tx0 + xx;
-      const bool valid = y < TH && xx < TW && ly < H && lxx < W;
-      const int cy = ly < H ? ly : H - 1, cx = lxx < W ? lxx : W - 1;     // (every lane runs the MFMAs; a lane without a cell reads a clamped one)
-      f32x4 t;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int ch = 4 * (lane >> 4) + r;
-        t[r] = (fmaxf(v[r], 0.f) + l2b[((size_t)ch * H2 + cy / 2) * W2 + cx / 2]) + l4b[((size_t)ch * H4 + cy / 4) * W4 + cx / 4];
-      }
-      // conv2, conv2 again, conv3, convOut: register r of a result is the B operand of input channels 4g + r
-#pragma unroll
-      for (int l = 0; l < 4; ++l) {
-        const int m = l == 0 ? 0 : l - 1;
-        f32x4 h = bt[m];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) h = __builtin_amdgcn_mfma_f32_16x16x4f32(wt[m][r], t[r], h, 0, 0, 0);
-        if (l < 3) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) t[r] = fmaxf(h[r], 0.f);
-        } else {
-          t = h;
-        }
-      }
-      if (valid && lane < 16) pb[(size_t)ly * W + lxx] = t[0];
-    });
-  }
-}
-
-constexpr int TILE_H = 8, TILE_W1 = 32, TILE_WC = 16;   // level 1: 8 x 32 cells; levels 2 and 4: 8 x 16
-
-inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
-struct BankWs { float* l2; float* l4; size_t bytes; };
-BankWs banknet_ws_layout(int B, int H, int W, void* base) {
-  BankWs w{};
-  const size_t n2 = al256((size_t)B * 16 * (H / 2) * (W / 2) * 4), n4 = al256((size_t)B * 16 * (H / 4) * (W / 4) * 4);
-  w.l2 = (float*)base;
-  w.l4 = base ? (float*)((char*)base + n2) : nullptr;
-  w.bytes = n2 + n4;
-  return w;
+  bank_level_tile<R, TH, TW, false>(pk, x, H, W, out, l2, l4, p, BankTapeOut{});
 }
 
 void banknet_forward(int B, int H, int W, const float* pk, const float* x, float* p, void* ws, hipStream_t s) {
@@ -313,33 +97,6 @@ BankFluidnetWs bank_fluidnet_ws_layout(int B, int H, int W, void* base) {
   return w;
 }
 
-int bank_status() {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? FNX_OK : set_error(FNX_EHIP, "HIP error in a bank-net launch: %s", hipGetErrorString(e));
-}
-
-// The checks the bank net's entry points share, before any device call, each refusal with its own text.
-int check_bank_call(const char* fn, const FnxGrid* g, bool args, int precision_mode, bool whole, size_t ws_bytes) {
-  if (!g || !args) return set_error(FNX_EINVAL, "%s: null argument", fn);
-  if (g->is3D || g->D != 1)
-    return set_error(FNX_EINVAL, "%s: the bank net ('FluidNet' model) is 2D only (is3D = %d, D = %d)", fn, g->is3D, g->D);
-  const int mode = net_mode(precision_mode);
-  if (mode < 0)
-    return set_error(FNX_EINVAL, "%s: unknown precision_mode %d (FNX_PRECISION_FP32, _FP32_DIRECT, _BF16X6, _BF16X3, _FP32_F4 or _FP32_F2)", fn,
-                     precision_mode);
-  if (mode == FNX_PRECISION_BF16X6 || mode == FNX_PRECISION_BF16X3)
-    return set_error(FNX_EINVAL, "%s: the bank net runs in fp32 arithmetic only (FNX_PRECISION_FP32, _FP32_F4, _FP32_F2 or _FP32_DIRECT), "
-                     "not in the bf16 modes (precision_mode %d)", fn, precision_mode);
-  if (g->B < 1 || g->B > 65535) return set_error(FNX_EINVAL, "%s: batch size %d is outside 1 .. 65535", fn, g->B);
-  if (g->H < 4 || g->H % 4) return set_error(FNX_EINVAL, "%s: H = %d must be a positive multiple of 4 (the three levels are added)", fn, g->H);
-  if (g->W < 4 || g->W % 4) return set_error(FNX_EINVAL, "%s: W = %d must be a positive multiple of 4 (the three levels are added)", fn, g->W);
-  if ((size_t)g->H * g->W >= ((size_t)1 << 27))
-    return set_error(FNX_EINVAL, "%s: H * W = %zu cells per sample is beyond the bank kernels' range", fn, (size_t)g->H * g->W);
-  const size_t want = whole ? bank_fluidnet_ws_layout(g->B, g->H, g->W, nullptr).bytes : banknet_ws_layout(g->B, g->H, g->W, nullptr).bytes;
-  if (ws_bytes < want) return set_error(FNX_EWORKSPACE, "%s: workspace of %zu bytes is too small (%zu needed)", fn, ws_bytes, want);
-  return FNX_OK;
-}
-
 }  // namespace
 }  // namespace fnx
 
@@ -361,14 +118,16 @@ size_t fnx_banknet_ws_bytes(const FnxGrid* g, int whole_forward) {
 
 int fnx_banknet_forward(const FnxGrid* g, const void* packed, const float* x, float* p, int precision_mode, void* ws, size_t ws_bytes,
                         void* stream) {
-  if (int rc = fnx::check_bank_call(__func__, g, packed && x && p && ws, precision_mode, false, ws_bytes)) return rc;
+  if (int rc = fnx::check_bank_call(__func__, g, packed && x && p && ws, precision_mode,
+                                      [](int B, int H, int W) { return fnx::banknet_ws_layout(B, H, W, nullptr).bytes; }, ws_bytes)) return rc;
   fnx::banknet_forward(g->B, g->H, g->W, (const float*)packed, x, p, ws, (hipStream_t)stream);
   return fnx::bank_status();
 }
 
 int fnx_fluidnet_bank_forward(const FnxGrid* g, const void* packed, const float* input, float thr, float* p_out, float* U_out,
                               int precision_mode, void* ws, size_t ws_bytes, void* stream) {
-  if (int rc = fnx::check_bank_call(__func__, g, packed && input && p_out && U_out && ws, precision_mode, true, ws_bytes)) return rc;
+  if (int rc = fnx::check_bank_call(__func__, g, packed && input && p_out && U_out && ws, precision_mode,
+                                      [](int B, int H, int W) { return fnx::bank_fluidnet_ws_layout(B, H, W, nullptr).bytes; }, ws_bytes)) return rc;
   const GridDims d = make_dims(g->B, 1, g->H, g->W, g->z_offset, g->D_global);
   hipStream_t s = (hipStream_t)stream;
   const fnx::BankFluidnetWs w = fnx::bank_fluidnet_ws_layout(g->B, g->H, g->W, ws);

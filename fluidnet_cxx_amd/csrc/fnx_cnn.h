@@ -128,6 +128,19 @@ namespace fnx {
 // precision_mode (FNX_PRECISION_*) as the CNN launchers dispatch on it: FNX_PRECISION_FP32_F4 names what FNX_PRECISION_FP32 runs and
 // becomes it; -1: no such mode.  The C ABI entry points map it once; everything below them takes the mapped value.
 int net_mode(int precision_mode);
+// FluidNet.forward for training around a taped net, whichever net it is (fnx_cnn_train.hip; the ScaleNet and the bank model call these):
+// the forward's scratch (the divergence, the net's input x, scale_std's partial sums), the backward's (the wall-masked scaled grad_U, the
+// update's grad_U and grad_p, g_net, then the net's own workspace at `net`), the launches of model.py:104-168 in front of the net, those
+// of :213-226 behind it, and  g_net = s grad_p + velocity_update_backward_p(s setWallBcs(grad_U)).  nc: 2 or 3 velocity components.
+struct FluidnetTrainFwdWs { float* div; float* x; double* partial; size_t bytes; };
+struct FluidnetTrainBwdWs { float *gU, *gU_in, *gp, *gnet; void* net; size_t bytes; };   // bytes: in front of `net`
+FluidnetTrainFwdWs fluidnet_train_fwd_ws(const FnxGrid* g, void* base);
+FluidnetTrainBwdWs fluidnet_train_bwd_ws(int nc, const FnxGrid* g, void* base);
+int fluidnet_train_pre(int nc, const FnxGrid* g, const float* input, float normalize_threshold, float* U_out, float* flags_out,
+                       float* scale_out, const FluidnetTrainFwdWs& w, void* stream);
+int fluidnet_train_post(int nc, const FnxGrid* g, float* p_out, float* U_out, const float* flags, const float* scale, void* stream);
+int fluidnet_train_gnet(int nc, const FnxGrid* g, const float* flags, const float* scale, const float* grad_p, const float* grad_U,
+                        const FluidnetTrainBwdWs& w, void* stream);
 // the net's un-normalised pressure alone (model.py:125-175, :221-222) for the hybrid projection: p_out = scale * net(div(U) / scale, occupancy);
 // U is read only.  ws: fluidnet_ws_bytes.
 int fluidnet_pressure(const FnxGrid* g, const void* packed, const float* flags, float thr, int precision_mode, float* p_out, const float* U,

@@ -590,6 +590,56 @@ void launch_scale_mul(size_t n1, int nc, int B, const float* scale, const float*
   scale_mul_kernel<<<dim3((unsigned)blocks, B), 256, 0, s>>>(n1, nc, scale, a, addend, out);
 }
 
+
+// FluidNet.forward around a taped net and the adjoint of what follows it (fnx_cnn.h): one statement for the ScaleNet and the bank model.
+FluidnetTrainFwdWs fluidnet_train_fwd_ws(const FnxGrid* g, void* base) {
+  const size_t full = (size_t)g->B * g->D * g->H * g->W;
+  char* w = (char*)base;
+  FluidnetTrainFwdWs f{};
+  f.div = (float*)w; w += al256(full * 4);
+  f.x = (float*)w; w += al256(full * 2 * 4);
+  f.partial = (double*)w; w += al256(scale_std_scratch_bytes(g->B));
+  f.bytes = (size_t)(w - (char*)base);
+  return f;
+}
+FluidnetTrainBwdWs fluidnet_train_bwd_ws(int nc, const FnxGrid* g, void* base) {
+  const size_t full = (size_t)g->B * g->D * g->H * g->W;
+  char* w = (char*)base;
+  FluidnetTrainBwdWs f{};
+  f.gU = (float*)w; w += al256(full * nc * 4);
+  f.gU_in = (float*)w; w += al256(full * nc * 4);
+  f.gp = (float*)w; w += al256(full * 4);
+  f.gnet = (float*)w; w += al256(full * 4);
+  f.net = w;
+  f.bytes = (size_t)(w - (char*)base);
+  return f;
+}
+int fluidnet_train_pre(int nc, const FnxGrid* g, const float* input, float normalize_threshold, float* U_out, float* flags_out,
+                       float* scale_out, const FluidnetTrainFwdWs& w, void* stream) {
+  const GridDims d = make_dims(g->B, g->D, g->H, g->W);
+  hipStream_t s = (hipStream_t)stream;
+  launch_gather_input(d, nc, input, U_out, flags_out, s);
+  if (int rc = fnx_velocity_divergence(g, U_out, flags_out, w.div, stream)) return rc;
+  launch_scale_std(d, nc, U_out, normalize_threshold, w.partial, scale_out, s);
+  launch_pack_input(d, nc, w.div, flags_out, scale_out, U_out, w.x, s);
+  return FNX_OK;
+}
+int fluidnet_train_post(int nc, const FnxGrid* g, float* p_out, float* U_out, const float* flags, const float* scale, void* stream) {
+  if (int rc = fnx_velocity_update(g, p_out, U_out, flags, stream)) return rc;
+  launch_unscale(make_dims(g->B, g->D, g->H, g->W), nc, scale, p_out, U_out, (hipStream_t)stream);
+  return fnx_set_wall_bcs(g, U_out, flags, stream);
+}
+int fluidnet_train_gnet(int nc, const FnxGrid* g, const float* flags, const float* scale, const float* grad_p, const float* grad_U,
+                        const FluidnetTrainBwdWs& w, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const size_t n1 = (size_t)g->D * g->H * g->W;
+  launch_scale_mul(n1, nc, g->B, scale, grad_U, nullptr, w.gU, s);
+  if (int rc = fnx_set_wall_bcs(g, w.gU, flags, stream)) return rc;
+  if (int rc = fnx_velocity_update_backward(g, w.gU, flags, w.gU_in, w.gp, stream)) return rc;
+  launch_scale_mul(n1, 1, g->B, scale, grad_p, w.gp, w.gnet, s);
+  return FNX_OK;
+}
+
 }  // namespace fnx
 
 // ---------------------------------------------------------------------------------------------------
@@ -695,9 +745,8 @@ int backward_call(const char* fn, bool is3d, const FnxGrid* g, const void* packe
 // nc: the velocity components, 2 or 3 (g is checked).
 // forward: div, x (2), std partials; backward: the wall-masked scaled grad_U (nc), grad_U of the update (nc), its grad_p, g_net
 size_t fluidnet_train_ws(int nc, const FnxGrid* g) {
-  const size_t full = (size_t)g->B * g->D * g->H * g->W;
-  const size_t fwd = al256(full * 4) + al256(full * 2 * 4) + al256(fnx::scale_std_scratch_bytes(g->B));
-  const size_t bwd = 2 * al256(full * nc * 4) + 2 * al256(full * 4) + fnx::multiscale_backward_ws_bytes(nc == 3, g->B, g->D, g->H, g->W);
+  const size_t fwd = fnx::fluidnet_train_fwd_ws(g, nullptr).bytes;
+  const size_t bwd = fnx::fluidnet_train_bwd_ws(nc, g, nullptr).bytes + fnx::multiscale_backward_ws_bytes(nc == 3, g->B, g->D, g->H, g->W);
   return fwd > bwd ? fwd : bwd;
 }
 
@@ -710,22 +759,11 @@ int fluidnet_forward_train_call(const char* fn, int nc, const FnxGrid* g, const 
     return rc;
   if (int rc = check_image(fn, is3d, packed_bytes, false)) return rc;
   if (ws_bytes < fluidnet_train_ws(nc, g)) return too_small(fn, ws_bytes);
-  const GridDims d = make_dims(g->B, g->D, g->H, g->W);
-  hipStream_t s = (hipStream_t)stream;
-  const size_t full = (size_t)g->B * d.DHW;
-  char* w = (char*)ws;
-  float* div = (float*)w; w += al256(full * 4);
-  float* x = (float*)w; w += al256(full * 2 * 4);
-  double* partial = (double*)w;
+  const fnx::FluidnetTrainFwdWs w = fnx::fluidnet_train_fwd_ws(g, ws);
   // fnx_fluidnet_forward's stages (model.py:104-227) around the taped net
-  fnx::launch_gather_input(d, nc, input, U_out, flags_out, s);
-  if (int rc = fnx_velocity_divergence(g, U_out, flags_out, div, stream)) return rc;
-  fnx::launch_scale_std(d, nc, U_out, normalize_threshold, partial, scale_out, s);
-  fnx::launch_pack_input(d, nc, div, flags_out, scale_out, U_out, x, s);
-  fnx::multiscale_forward_train(is3d, g->B, g->D, g->H, g->W, packed, x, p_out, tape, mode, s);
-  if (int rc = fnx_velocity_update(g, p_out, U_out, flags_out, stream)) return rc;
-  fnx::launch_unscale(d, nc, scale_out, p_out, U_out, s);
-  if (int rc = fnx_set_wall_bcs(g, U_out, flags_out, stream)) return rc;
+  if (int rc = fnx::fluidnet_train_pre(nc, g, input, normalize_threshold, U_out, flags_out, scale_out, w, stream)) return rc;
+  fnx::multiscale_forward_train(is3d, g->B, g->D, g->H, g->W, packed, w.x, p_out, tape, mode, (hipStream_t)stream);
+  if (int rc = fnx::fluidnet_train_post(nc, g, p_out, U_out, flags_out, scale_out, stream)) return rc;
   return train_status(is3d);
 }
 
@@ -738,19 +776,11 @@ int fluidnet_backward_call(const char* fn, int nc, const FnxGrid* g, const void*
     return rc;
   if (int rc = check_image(fn, is3d, packed_t_bytes, true)) return rc;
   if (ws_bytes < fluidnet_train_ws(nc, g)) return too_small(fn, ws_bytes);
-  hipStream_t s = (hipStream_t)stream;
-  const size_t n1 = (size_t)g->D * g->H * g->W, full = n1 * g->B;
-  char* w = (char*)ws;
-  float* gU = (float*)w; w += al256(full * nc * 4);
-  float* gU_in = (float*)w; w += al256(full * nc * 4);
-  float* gp = (float*)w; w += al256(full * 4);
-  float* gnet = (float*)w; w += al256(full * 4);
+  const fnx::FluidnetTrainBwdWs w = fnx::fluidnet_train_bwd_ws(nc, g, ws);
   // g_net = s g_p + velocity_update_backward_p(s setWallBcs(g_U)): the adjoints of model.py:226, :221-223 and :213-218 in reverse
-  fnx::launch_scale_mul(n1, nc, g->B, scale, grad_U, nullptr, gU, s);
-  if (int rc = fnx_set_wall_bcs(g, gU, flags, stream)) return rc;
-  if (int rc = fnx_velocity_update_backward(g, gU, flags, gU_in, gp, stream)) return rc;
-  fnx::launch_scale_mul(n1, 1, g->B, scale, grad_p, gp, gnet, s);
-  if (!fnx::multiscale_backward(is3d, g->B, g->D, g->H, g->W, packed_t, gnet, tape, grad_blob, mode, w, s)) return not_launched(fn, is3d);
+  if (int rc = fnx::fluidnet_train_gnet(nc, g, flags, scale, grad_p, grad_U, w, stream)) return rc;
+  if (!fnx::multiscale_backward(is3d, g->B, g->D, g->H, g->W, packed_t, w.gnet, tape, grad_blob, mode, w.net, (hipStream_t)stream))
+    return not_launched(fn, is3d);
   return train_status(is3d);
 }
 

@@ -95,7 +95,8 @@ class FluidNet:
     model='FluidNet' (what the reference's trainConfig.yaml ships) is the 16-channel bank net of model.py:177-209, 2D and fp32 modes
     only: a fresh net holds weights.make_banknet_weights(0), `load_state_dict` requires the twelve conv1 / convBank / conv2 / conv3 /
     convOut tensors and keeps multiScale.* and scale.*, `net.bank(x)` is the net alone, and `packed_for` raises -- the native step,
-    the z-slab drivers and the trainers take the ScaleNet image only; `simulate()` runs such a net operator by operator."""
+    the z-slab drivers and FluidNetTrain take the ScaleNet image only; `simulate()` runs such a net operator by operator, and
+    train.FluidNetBankTrain is its counterpart with a native backward pass."""
 
     def __init__(self, mconf, dropout=True):
         model = mconf.get("model", "ScaleNet")

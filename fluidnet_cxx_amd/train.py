@@ -6,7 +6,12 @@ reference, and torch.optim.* / zero_grad() work on it.  forward(input_) returns 
 backward is the native backward pass (fnx_fluidnet_backward); `net.multiScale(x)` is differentiable in the same way.  Under
 torch.no_grad() or .eval() both run the inference launches.  Gradients come from the kernels: torch only carries the tensors.
 
-Scope: the 2D ScaleNet configuration `FluidNet` accepts, precision modes fp32 / fp32_f4 / fp32_f2 / fp32_direct, gradients with respect to
+`FluidNetBankTrain(mconf, dropout=False)` is the same for the reference's 16-channel bank net (mconf['model'] = 'FluidNet',
+model.py:177-209; csrc/fnx_banknet_train.hip): the twelve parameters `conv1`, `convBank.block.0`, `convBank.block.2`, `conv2`, `conv3`,
+`convOut`, and `net.bank(x)` where the ScaleNet has `net.multiScale(x)`.  Both nets share the autograd functions; an `_Api` names the
+extension's entry points of each.
+
+Scope: the 2D configurations `FluidNet` accepts, precision modes fp32 / fp32_f4 / fp32_f2 / fp32_direct, gradients with respect to
 the parameters.  3D, the bf16 modes, dropout and a gradient with respect to input_ raise.
 """
 from collections import OrderedDict
@@ -14,8 +19,8 @@ from collections import OrderedDict
 import torch
 
 from ._ext import ext
-from .model import _UNUSED_PREFIXES
-from .weights import make_scalenet_weights, scalenet_layers
+from .model import _BANK_UNUSED_PREFIXES, _UNUSED_PREFIXES
+from .weights import banknet_layers, make_banknet_weights, make_scalenet_weights, scalenet_layers
 
 _TRAIN_MODES = ("fp32", "fp32_f4", "fp32_f2", "fp32_direct")
 
@@ -35,21 +40,44 @@ def _split(blob, shapes):
     return grads
 
 
-class _Api:
-    """what differs between the 2D and the 3D net: the extension's entry points and the number of velocity components (only the
-    dimension is state, so a module that holds one copies and pickles as before)"""
+# the bank net's entry points under the names the ScaleNet's have in _Api
+_BANK_NAMES = {"scalenet#_pack_t": "banknet_pack_t", "multiscale#_forward_train": "banknet_forward_train",
+               "multiscale#_backward": "banknet_backward", "fluidnet#_forward_train": "fluidnet_bank_forward_train",
+               "fluidnet#_backward": "fluidnet_bank_backward"}
 
-    def __init__(self, ndim):
-        self.ndim, self.nc = ndim, ndim
+
+class _Api:
+    """what differs between the 2D net, the 3D net and the 2D bank net: the extension's entry points and the number of velocity
+    components (only the dimension and the model are state, so a module that holds one copies and pickles as before)"""
+
+    bank = False                         # (a class default: an _Api pickled before the bank net existed has no such attribute)
+
+    def __init__(self, ndim, bank=False):
+        self.ndim, self.nc, self.bank = ndim, ndim, bank
 
     def _fn(self, name):
+        if self.bank:
+            return getattr(ext, _BANK_NAMES[name])
         return getattr(ext, name.replace("#", "" if self.ndim == 2 else "3d"))
 
     def pack(self, blob):
-        return ext.scalenet_pack(blob, self.ndim == 3), self._fn("scalenet#_pack_t")(blob)
+        fwd = ext.banknet_pack(blob) if self.bank else ext.scalenet_pack(blob, self.ndim == 3)
+        return fwd, self._fn("scalenet#_pack_t")(blob)
+
+    def net_forward(self, packed, x, mode):
+        """the inference launches of the net alone"""
+        return ext.banknet_forward(packed, x, mode) if self.bank else ext.multiscale_forward(packed, x, mode, [])
+
+    def fluidnet_forward(self, packed, input_, threshold, mode):
+        """the inference launches of FluidNet.forward"""
+        return (ext.fluidnet_bank_forward if self.bank else ext.fluidnet_forward)(packed, input_, threshold, mode)
+
+    def net_backward(self, packed_t, x, gp, tape, mode):
+        """(the bank net's backward reads the net's input again: conv1's weight gradient)"""
+        fn = self._fn("multiscale#_backward")
+        return fn(packed_t, x, gp, tape, mode) if self.bank else fn(packed_t, gp, tape, mode)
 
     multiscale_forward_train = property(lambda self: self._fn("multiscale#_forward_train"))
-    multiscale_backward = property(lambda self: self._fn("multiscale#_backward"))
     fluidnet_forward_train = property(lambda self: self._fn("fluidnet#_forward_train"))
     fluidnet_backward = property(lambda self: self._fn("fluidnet#_backward"))
 
@@ -62,11 +90,12 @@ class _MultiScaleFn(torch.autograd.Function):
         packed, ctx.packed_t = owner._packed(x.device)
         p, ctx.tape = owner._api.multiscale_forward_train(packed, x, owner.precision_mode)
         ctx.mode, ctx.shapes, ctx.api = owner.precision_mode, [q.shape for q in params], owner._api
+        ctx.x = x if ctx.api.bank else None
         return p
 
     @staticmethod
     def backward(ctx, gp):
-        blob = ctx.api.multiscale_backward(ctx.packed_t, gp.contiguous(), ctx.tape, ctx.mode)
+        blob = ctx.api.net_backward(ctx.packed_t, ctx.x, gp.contiguous(), ctx.tape, ctx.mode)
         return (None, None) + tuple(_split(blob, ctx.shapes))
 
 
@@ -102,6 +131,18 @@ class _Holder(torch.nn.Module):
     pass
 
 
+def _repack(owner, device):
+    """(packed, packed_t) of owner._ordered() on `device`, cached in owner._key / owner._images: repacked on the device whenever a
+    parameter was written (an optimiser step, load_state_dict, .to())"""
+    params = owner._ordered()
+    key = (str(device),) + tuple((p.data_ptr(), p._version) for p in params)
+    if key != owner._key:
+        blob = torch.cat([p.detach().reshape(-1) for p in params]).to(device=device, dtype=torch.float32).contiguous()
+        owner._images = owner._api.pack(blob)
+        owner._key = key
+    return owner._images
+
+
 class _MultiScaleTrain(torch.nn.Module):
     """x (B,2,H,W) -> p (B,1,H,W), or (B,2,D,H,W) -> (B,1,D,H,W) with ndim = 3   (multi_scale_net.py:118-127), differentiable with
     respect to the parameters"""
@@ -128,29 +169,34 @@ class _MultiScaleTrain(torch.nn.Module):
         return [named[L["name"].split(".", 1)[1] + sfx] for L in scalenet_layers(2, self._api.ndim) for sfx in (".weight", ".bias")]
 
     def _packed(self, device):
-        """(packed, packed_t) for the current parameter values on `device`: repacked on the device whenever a parameter was written
-        (an optimiser step, load_state_dict, .to())"""
-        params = self._ordered()
-        key = (str(device),) + tuple((p.data_ptr(), p._version) for p in params)
-        if key != self._key:
-            blob = torch.cat([p.detach().reshape(-1) for p in params]).to(device=device, dtype=torch.float32).contiguous()
-            self._images = self._api.pack(blob)
-            self._key = key
-        return self._images
+        """(packed, packed_t) for the current parameter values on `device`"""
+        return _repack(self, device)
 
     def forward(self, x):
         x = x.contiguous()
         if not (self.training and torch.is_grad_enabled()):
-            return ext.multiscale_forward(self._packed(x.device)[0], x, self.precision_mode, [])
+            return self._api.net_forward(self._packed(x.device)[0], x, self.precision_mode)
         _no_input_grad(x, "x")
         return _MultiScaleFn.apply(x, self, *self._ordered())
 
 
 class _FluidNetTrainBase(torch.nn.Module):
-    """What FluidNetTrain (2D) and FluidNetTrain3D share: everything but the dimension, which a subclass states in _NDIM, and its
-    check of mconf['is3D'] (_check_dim)."""
+    """What FluidNetTrain (2D), FluidNetTrain3D and FluidNetBankTrain share: everything but the dimension, which a subclass states in
+    _NDIM, its check of mconf['is3D'] (_check_dim), and the net in the middle (_check_model, _build_net, _ordered, _packed)."""
 
     _NDIM = 2
+    _UNUSED = _UNUSED_PREFIXES           # the reference's parameters this model's forward never reads, kept for state_dict()
+
+    def _check_model(self, mconf, name):
+        if mconf.get("model", "ScaleNet") != "ScaleNet":
+            raise ValueError(f"{name}: only the ScaleNet variant is accelerated")
+
+    def _build_net(self):
+        self.multiScale = _MultiScaleTrain(self.precision_mode, self._NDIM)
+        self._api = self.multiScale._api
+
+    def _ordered(self):
+        return self.multiScale._ordered()
 
     def _check_dim(self, mconf):
         raise NotImplementedError
@@ -161,8 +207,7 @@ class _FluidNetTrainBase(torch.nn.Module):
         if dropout:
             raise ValueError(f"{name}: dropout=True is not supported (the reference's drivers build the ScaleNet "
                              "path with dropout=False)")
-        if mconf.get("model", "ScaleNet") != "ScaleNet":
-            raise ValueError(f"{name}: only the ScaleNet variant is accelerated")
+        self._check_model(mconf, name)
         ic = mconf.get("inputChannels", {"div": True, "pDiv": False, "UDiv": False})
         if not (ic.get("div", False) and not ic.get("pDiv", False) and not ic.get("UDiv", False)):
             raise ValueError(f"{name}: inputChannels must be {{div}} (convModel_mconf.pth)")
@@ -177,8 +222,7 @@ class _FluidNetTrainBase(torch.nn.Module):
         self.is3D = self._NDIM == 3
         self.inDims = mconf.get("inputDim", self._NDIM)
         self.threshold = float(mconf.get("normalizeInputThreshold", 1e-5))
-        self.multiScale = _MultiScaleTrain(self.precision_mode, self._NDIM)
-        self._api = self.multiScale._api
+        self._build_net()
         self._extra = OrderedDict()          # the reference's unused parameters (conv1.* ...), kept for state_dict()
 
     def _packed(self, device):
@@ -207,8 +251,8 @@ class _FluidNetTrainBase(torch.nn.Module):
     def load_state_dict(self, state_dict, strict=True, **kwargs):
         """Like FluidNet.load_state_dict: every multiScale.* parameter must be present with the right shape; the reference FluidNet's
         parameters that the ScaleNet forward never reads are accepted and kept."""
-        extra = OrderedDict((k, v) for k, v in state_dict.items() if k.startswith(_UNUSED_PREFIXES))
-        own = OrderedDict((k, torch.as_tensor(v)) for k, v in state_dict.items() if not k.startswith(_UNUSED_PREFIXES))
+        extra = OrderedDict((k, v) for k, v in state_dict.items() if k.startswith(self._UNUSED))
+        own = OrderedDict((k, torch.as_tensor(v)) for k, v in state_dict.items() if not k.startswith(self._UNUSED))
         res = super().load_state_dict(own, strict=strict, **kwargs)
         self._extra = extra
         return res
@@ -216,10 +260,10 @@ class _FluidNetTrainBase(torch.nn.Module):
     def forward(self, input_):
         input_ = input_.contiguous()
         if not (self.training and torch.is_grad_enabled()):
-            p, U = ext.fluidnet_forward(self._packed(input_.device)[0], input_, self.threshold, self.precision_mode)
+            p, U = self._api.fluidnet_forward(self._packed(input_.device)[0], input_, self.threshold, self.precision_mode)
             return p, U
         _no_input_grad(input_, "input_")
-        return _FluidNetFn.apply(input_, self, *self.multiScale._ordered())
+        return _FluidNetFn.apply(input_, self, *self._ordered())
 
 
 class FluidNetTrain(_FluidNetTrainBase):
@@ -230,3 +274,61 @@ class FluidNetTrain(_FluidNetTrainBase):
     def _check_dim(self, mconf):
         if mconf.get("is3D", False):
             raise ValueError("fluidnet_cxx_amd.FluidNetTrain: training is 2D only (is3D=True; FluidNetTrain3D trains the 3D net)")
+
+
+class FluidNetBankTrain(_FluidNetTrainBase):
+    """FluidNetTrain for the reference's 16-channel bank net, mconf['model'] = 'FluidNet' (model.py:177-209): the twelve parameters
+    conv1, convBank.block.0, convBank.block.2, conv2, conv3, convOut (.weight / .bias), a fresh net holding
+    weights.make_banknet_weights(0).  load_state_dict requires the twelve tensors and keeps multiScale.* / scale.*, as FluidNet does for
+    this model; `net.bank(x)`, x (B,2,H,W) -> p (B,1,H,W), is the net alone, differentiable like forward().  2D, H and W multiples of 4."""
+
+    is_bank = True                       # simulate() runs such a net operator by operator
+    _UNUSED = _BANK_UNUSED_PREFIXES
+
+    def _check_model(self, mconf, name):
+        if mconf.get("model", "ScaleNet") != "FluidNet":
+            raise ValueError(f"{name}: mconf['model'] must be 'FluidNet', the 16-channel bank net (FluidNetTrain trains the ScaleNet)")
+
+    def _check_dim(self, mconf):
+        if mconf.get("is3D", False):
+            raise ValueError("fluidnet_cxx_amd.FluidNetBankTrain: the 'FluidNet' bank model is 2D only (the reference asserts it)")
+
+    def _build_net(self):
+        self._api = _Api(2, bank=True)
+        w = make_banknet_weights(0)
+        for L in banknet_layers():
+            parts = L["name"].split(".")                  # conv1  |  convBank, block, 0
+            mod = self
+            for part in parts[:-1]:
+                if not hasattr(mod, part):
+                    mod.add_module(part, _Holder())
+                mod = getattr(mod, part)
+            mod.add_module(parts[-1], _Conv(w[L["name"] + ".weight"], w[L["name"] + ".bias"]))
+        self._key = None
+        self._images = None
+
+    def _ordered(self):
+        """the twelve parameters in the blob's order (banknet_layers(): weight, bias per convolution)"""
+        named = dict(self.named_parameters())
+        return [named[L["name"] + sfx] for L in banknet_layers() for sfx in (".weight", ".bias")]
+
+    def _packed(self, device):
+        return _repack(self, device)
+
+    def _not_scalenet(self, what):
+        raise RuntimeError(f"FluidNetBankTrain.{what}: this net is the 'FluidNet' bank model; the native step and the z-slab drivers "
+                           "take the ScaleNet image only (net.bank(x) and net(input) run the bank kernels)")
+
+    @property
+    def packed(self):
+        self._not_scalenet("packed")
+
+    def packed_for(self, device):
+        self._not_scalenet("packed_for")
+
+    def bank(self, x):
+        x = x.contiguous()
+        if not (self.training and torch.is_grad_enabled()):
+            return self._api.net_forward(self._packed(x.device)[0], x, self.precision_mode)
+        _no_input_grad(x, "x")
+        return _MultiScaleFn.apply(x, self, *self._ordered())

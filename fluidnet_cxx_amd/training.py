@@ -7,7 +7,8 @@ random obstacles (fnx_scene_obstacles), a divergence-free turbulent velocity and
 step through the solver, and hands out (data, target) batches in the reference's layout: data (B,5,1,H,W) = [p of the previous step,
 U before the projection, flags, density], target (B,4,1,H,W) = [p, U, density] of the converged ('pcg') projection.  `fluidnet_loss` is
 the loss of fluid_net_train.py:276-285 with its gradient from one kernel (fnx_train_loss); `train` is run_epoch's body around
-`FluidNetTrain`, torch.optim.Adam and ReduceLROnPlateau with the reference's arguments.
+`FluidNetTrain` (or, with mconf['model'] = 'FluidNet', the 16-channel bank net's `FluidNetBankTrain`), torch.optim.Adam and
+ReduceLROnPlateau with the reference's arguments.
 
 torch carries the tensors (allocation, copies, concatenation, the optimiser); the arithmetic on fields is the extension's kernels.
 Every random choice comes from the counter-based hash of the scene kernels (include/fluidnet_hip.h), evaluated on the host for the
@@ -25,7 +26,7 @@ import torch
 from . import fluid
 from ._ext import ext
 from ._simulate import simulate
-from .train import FluidNetTrain
+from .train import FluidNetBankTrain, FluidNetTrain
 
 # the scene generator's parameters (FnxSceneParams): up to four discs / boxes whose centres lie within 0.3 min(H, W) of the grid centre
 # and whose radius / half extent is 0.03 .. 0.12 min(H, W) -- they never reach the border ring, and at least 70 % of the cells stay fluid
@@ -280,6 +281,8 @@ class SceneSampler(_SceneSamplerBase):
 
 _DIM = _Dim(2, FluidNetTrain, lambda mconf, B, dims, *rest: SceneSampler(mconf, B, dims[0], dims[1], *rest), fluidnet_loss,
             ext.train_loss)
+# the same with the reference's 16-channel bank net in the middle (mconf['model'] = 'FluidNet')
+_DIM_BANK = _Dim(2, FluidNetBankTrain, _DIM.sampler, fluidnet_loss, ext.train_loss)
 
 
 # ---- the trainer ----------------------------------------------------------------------------------------------------------------------
@@ -461,4 +464,4 @@ def train(mconf=None, tconf=None, device="cuda", out=None, resume=None, log=None
         raise ValueError("fluidnet_cxx_amd.training.train: training is 2D only (is3D=True)")
     _refuse_3d("train", tconf.get("D", 1))
     H, W = int(tconf.get("H", tconf["res"])), int(tconf.get("W", tconf["res"]))
-    return _train(_DIM, mconf, tconf, (H, W), device, out, resume, log)
+    return _train(_DIM_BANK if mconf.get("model", "ScaleNet") == "FluidNet" else _DIM, mconf, tconf, (H, W), device, out, resume, log)

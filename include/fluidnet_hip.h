@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define FNX_ABI_VERSION 30
+#define FNX_ABI_VERSION 31
 
 enum {
   FNX_OK = 0,
@@ -691,7 +691,8 @@ int fnx_multiscale_forward_crop(const FnxGrid* g, const void* packed, const floa
 int fnx_fluidnet_forward(const FnxGrid* g, const void* packed, const float* input, float normalize_threshold,
                          float* p_out, float* U_out, int precision_mode, void* ws, size_t ws_bytes, void* stream);
 
-/* The reference's 16-channel "bank" net (ABI 30): lib/model.py:177-209, what mconf['model'] = 'FluidNet' selects -- 2D inference only.
+/* The reference's 16-channel "bank" net (ABI 30): lib/model.py:177-209, what mconf['model'] = 'FluidNet' selects -- 2D; its training entry points
+ * (ABI 31) follow those of the 2D ScaleNet below.
  *   a = relu(conv1(x)); t = (bank(a) + up2(bank(avgpool2(a)))) + up4(bank(avgpool4(a))); bank = relu(block.2(relu(block.0(.)))), one set
  *   of weights for the three levels, zero padding at each level's own border, nearest upsampling;
  *   p = convOut(relu(conv3(relu(conv2(relu(conv2(t)))))))                       (conv2 is applied twice, model.py:204-205)
@@ -766,6 +767,49 @@ int fnx_fluidnet_forward_train(const FnxGrid* g, const void* packed, const float
 int fnx_fluidnet_backward(const FnxGrid* g, const void* packed_t, const float* flags, const float* scale, const float* grad_p,
                           const float* grad_U, const float* tape, float* grad_blob, int precision_mode, void* ws, size_t ws_bytes,
                           void* stream);
+
+/* Training of the bank net in 2D (ABI 31): gradients of a scalar loss of p (or of FluidNet.forward's (p, U)) with respect to the twelve
+ * parameter tensors of the 'FluidNet' model, exact fp32.  Every entry point refuses, before it touches the device and each with its own
+ * fnx_last_error text, what the inference entry points of ABI 30 refuse: null arguments; a 3D grid and an unknown precision mode (the text
+ * starts with the function's name); the bf16 modes; H or W that is no positive multiple of 4; a short workspace (FNX_EWORKSPACE).  No
+ * gradient with respect to the input, no dropout.  No atomics and no host synchronisation (capturable): every cross-workgroup sum goes
+ * through per-workgroup partial sums -- min(work items, 512) workgroups per launch, a function of (B, H, W) alone -- which one kernel adds
+ * in index order in fp64, so two calls on the same inputs give the same bits.  grad_p, x and the tape are not modified.
+ *
+ * The training forward computes fnx_banknet_forward's arithmetic (p is bit-identical to it in every fp32 mode) and writes every ReLU
+ * output, after its ReLU, into one caller-provided buffer, the tape, as contiguous (B,C,h,w) tensors: "a" = relu(conv1(x)); "h1", "b1" the
+ * outputs of convBank.block.0 / block.2 at full resolution, "h2", "b2" at half and "h4", "b4" at quarter resolution; "a2", "a4" the
+ * average-pooled a those two levels start from; "t" the sum of the three levels; "c2a", "c2b" the outputs of the first and the second
+ * conv2; "c3" (8 channels) of conv3; and "x" (2 channels), the net's input, which only fnx_fluidnet_bank_forward_train writes (it builds
+ * x itself).  fnx_banknet_tape_layout returns the tape's size in floats (0 on error) and, if `entries` is not NULL, fills
+ * fnx_banknet_tape_entries() of them in tape order; names and offsets are a function of (B, H, W) alone.
+ *
+ * packed_t (fnx_banknet_packed_t_bytes()): the transposed, tap-flipped bank weights in the A-operand order of v_mfma_f32_16x16x4_f32 and
+ * the transposed 1x1 weights; fnx_banknet_pack_t runs on the device.  Repack it, as `packed`, whenever the weights change.
+ *
+ * Backward: grad_p (B,1,H,W), the tape and x (B,2,H,W) -> grad_blob (fnx_banknet_weight_floats() floats) in the layout of weights_blob:
+ * per conv the weight gradient, then the bias gradient.  The derivative of a ReLU is (saved output > 0), torch's rule.  conv2's gradient
+ * is the sum over its two applications, a bank tensor's the sum over the three levels; the gradient reaches level 2 (4) as the sum of its
+ * 2x2 (4x4) children and comes back from the pooling as g_a1 + up2(g_a2) / 4 + up4(g_a4) / 16.  The input gradients of the 16 -> 16
+ * convolutions and every 16 x 16 weight gradient run on v_mfma_f32_16x16x4_f32; conv1's 288 weight gradients and the bias gradients are
+ * plain sums.  Workspace: fnx_banknet_backward_ws_bytes(g) (0 for a grid without a size). */
+int fnx_banknet_tape_entries(void);
+size_t fnx_banknet_tape_layout(const FnxGrid* g, FnxTapeEntry* entries);
+size_t fnx_banknet_packed_t_bytes(void);
+int fnx_banknet_pack_t(const float* weights_blob, void* packed_t, void* stream);
+size_t fnx_banknet_backward_ws_bytes(const FnxGrid* g);
+int fnx_banknet_forward_train(const FnxGrid* g, const void* packed, const float* x, float* p, float* tape, int precision_mode, void* stream);
+int fnx_banknet_backward(const FnxGrid* g, const void* packed_t, const float* x, const float* grad_p, const float* tape, float* grad_blob,
+                         int precision_mode, void* ws, size_t ws_bytes, void* stream);
+/* fnx_fluidnet_forward_train / fnx_fluidnet_backward's contract with the bank net in the middle, and their launches around the net:
+ * g_net = s grad_p + velocity_update_backward_p(s setWallBcs(grad_U)).  One workspace size for both. */
+size_t fnx_fluidnet_bank_train_ws_bytes(const FnxGrid* g);
+int fnx_fluidnet_bank_forward_train(const FnxGrid* g, const void* packed, const float* input, float normalize_threshold, float* p_out,
+                                    float* U_out, float* flags_out, float* scale_out, float* tape, int precision_mode, void* ws,
+                                    size_t ws_bytes, void* stream);
+int fnx_fluidnet_bank_backward(const FnxGrid* g, const void* packed_t, const float* flags, const float* scale, const float* grad_p,
+                               const float* grad_U, const float* tape, float* grad_blob, int precision_mode, void* ws, size_t ws_bytes,
+                               void* stream);
 
 /* Training of the 3D net (ABI 25): the same gradients for the Conv3d net, under names of their own next to the 2D entry points above,
  * which keep refusing 3D.  Every entry point checks, before it touches the device and each with its own fnx_last_error text: null
