@@ -13,7 +13,8 @@ writes ({'state_dict', 'mconf', ...}), loaded the way the reference driver loads
 The checkpoint's own mconf['model'] picks the net, so no option does: 'ScaleNet' is the MultiScale net on the native step, 'FluidNet'
 (what the reference's trainConfig.yaml ships) is its 16-channel bank net, 2D only, which simulate() runs operator by operator.
 `--depth N` (N > 1) runs the 3D plume on a N x res x res grid (jacobi, pcg and --vorticity as in 2D); there `--method convnet` takes
-`--weights3d CKPT`, a checkpoint of `examples/train.py --depth N` (the 3D net; a 2D checkpoint given by --weights is refused).  `--render` adds volume renderings of the density (output.save_render: from the front, lit from above, and from the side)
+`--weights3d CKPT`, a checkpoint of `examples/train.py --depth N` (the 3D net; a 2D checkpoint given by --weights is refused) or one whose
+mconf['model'] is 'FluidNet3D', the Conv3d bank net (N and res multiples of 4; simulate() runs it operator by operator).  `--render` adds volume renderings of the density (output.save_render: from the front, lit from above, and from the side)
 to every output event.  `--method hybrid` takes the same checkpoints as convnet and projects with the converged solve started from the
 net's pressure; `--dyes N` (1..3) carries N passive dyes along (batch_dict['scalars'], fluid.advectScalars: all of them through one pair
 of line traces): the inlet is cut into N equal sectors along x and dye n enters through sector n at concentration 1, so the output
@@ -122,6 +123,9 @@ def main(argv=None):
         state = torch.load(a.weights3d if a.depth > 1 else a.weights, map_location="cpu", weights_only=False)
         mconf = state["mconf"]
         assert bool(mconf.get("is3D", False)) == (a.depth > 1), "the checkpoint's net has another dimension than the grid"
+        if mconf.get("model", "ScaleNet") == "FluidNet3D" and (a.depth % 4 or a.res % 4):
+            sys.exit(f"plume.py: the checkpoint's net is the 'FluidNet3D' bank net, which adds three levels: --depth {a.depth} and --res {a.res} "
+                     "must be multiples of 4")
         net = FluidNet(mconf, dropout=False)
         net = net.cuda()
         net.load_state_dict(state["state_dict"])

@@ -21,7 +21,7 @@ def __getattr__(name):
         return getattr(importlib.import_module(".state_io", __name__), name)
     if name == "output":
         return importlib.import_module(".output", __name__)
-    if name in ("FluidNet", "MultiScaleNet", "BankNet"):
+    if name in ("FluidNet", "MultiScaleNet", "BankNet", "BankNet3D"):
         return getattr(importlib.import_module(".model", __name__), name)
     if name == "FluidNetTrain":
         return importlib.import_module(".train", __name__).FluidNetTrain

@@ -10,8 +10,8 @@ fused=True still runs operator by operator where the native step has no form of 
 flags_stick, a density BC without a 'density' key, and mconf['viscosity'] > 0 with a (dt, viscosity) pair whose double product the two
 floats of FnxStepParams do not give (about a third of all pairs, dt = 0.1 with viscosity = 0.05 among them; the reference rounds the
 product once, viscosity.py:64), and 'convnet' or 'hybrid' with a net of the reference's 'FluidNet' bank model (mconf['model'] =
-'FluidNet', 2D: the native step takes the ScaleNet image only; both methods call net(...) on the operator path, which runs the bank
-kernels of fnx_banknet.hip).  `workspace` and `static_flags` are then not used.  The same bits, more launches: until FnxStepParams
+'FluidNet', 2D, or 'FluidNet3D', its Conv3d counterpart: the native step takes the ScaleNet image only; both methods call net(...) on
+the operator path, which runs the bank kernels of fnx_banknet.hip / fnx_banknet3d.hip).  `workspace` and `static_flags` are then not used.  The same bits, more launches: until FnxStepParams
 carries the product (an ABI change) such a viscous 2D run is slower than one with, say, viscosity = 0.02.
 The reference's own call -- `simulate(mconf, batch_dict, net, sim_method)`, four arguments (plume.py:237) -- gets the static
 path by itself: the layer keeps one step workspace per (device, grid shape) and looks at `(data_ptr, _version, shape, stride)` of

@@ -35,6 +35,7 @@ HIP_UNITS = {
     "fnx_cnn_train.hip": ["-Rpass-analysis=kernel-resource-usage"],
     "fnx_banknet.hip": ["-Rpass-analysis=kernel-resource-usage"],
     "fnx_banknet_train.hip": ["-Rpass-analysis=kernel-resource-usage"],
+    "fnx_banknet3d.hip": ["-Rpass-analysis=kernel-resource-usage"],
     "fnx_slab.hip": [],
     "fnx_peer.hip": [],
 }
@@ -55,6 +56,11 @@ SCRATCH_FREE = {
                               "registers of the two weight gradients across the workgroup's tiles at two workgroups per CU; the tail "
                               "and conv1 kernels keep their accumulators across the cell march; a spill puts scratch traffic between "
                               "the MFMAs"),
+    "fnx_banknet3d.hip": (["bank3d_conv1_kernel", "bank3d_conv_kernel"],
+                          "a lane of the convolution keeps its 108 MFMA weight operands, the twelve values of the plane in flight and "
+                          "(full resolution) the tail's 24 in registers for the whole z-march at two waves a SIMD; a spill puts a scratch "
+                          "reload in front of every MFMA.  conv1 keeps the 32 accumulators of a pair of cells and reads its weights "
+                          "from LDS; scratch there would mean the 880 weights were hoisted into registers"),
     "fnx_advect.hip": (["advect3d_fwd_tile_kernel", "advect3d_bwd_tile_kernel", "advect3d_bwd_scalar_tile_kernel",
                         "advect3d_bwd_vel_tile_kernel"],
                        "fnx_advect_march.h: the 3D advection marches run at 2-3 waves per SIMD with every VGPR in use; a reload from "

@@ -633,6 +633,55 @@ std::vector<Tensor> fluidnet_bank_forward(Tensor packed, Tensor input, double no
   return {p, U};
 }
 
+// ---- the Conv3d bank net, mconf['model'] = 'FluidNet3D' (fnx_banknet3d.hip): 3D inference; the bodies above with the 3D entry points ----
+Tensor banknet3d_pack(Tensor blob) {
+  TORCH_CHECK(blob.is_cuda() && blob.scalar_type() == at::kFloat && blob.is_contiguous(), "weights blob must be a contiguous float32 GPU tensor");
+  TORCH_CHECK((size_t)blob.numel() == fnx_banknet3d_weight_floats(), "weights blob has ", blob.numel(), " floats, expected ",
+              fnx_banknet3d_weight_floats());
+  c10::hip::HIPGuard guard(blob.get_device());
+  Tensor packed = at::zeros({(int64_t)fnx_banknet3d_packed_bytes()}, blob.options().dtype(at::kByte));
+  check_status(fnx_banknet3d_pack(blob.data_ptr<float>(), packed.data_ptr(), cur_stream(blob)));
+  return packed;
+}
+
+static void check_banknet3d_image(const Tensor& packed) {
+  TORCH_CHECK(packed.is_cuda() && packed.is_contiguous() && (size_t)packed.nbytes() == fnx_banknet3d_packed_bytes(),
+              "packed must be the ", fnx_banknet3d_packed_bytes(), "-byte image from banknet3d_pack (got ", packed.nbytes(), " bytes)");
+}
+
+Tensor banknet3d_forward(Tensor packed, Tensor x, const std::string& precision_mode) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.is_contiguous(), "x must be a contiguous float32 GPU tensor");
+  TORCH_CHECK((x.dim() == 4 || x.dim() == 5) && x.size(1) == 2, "x must be (B,2,H,W) or (B,2,D,H,W)");
+  check_banknet3d_image(packed);
+  FnxGrid g{}; g.B = (int)x.size(0); g.D = x.dim() == 5 ? (int)x.size(2) : 1; g.H = (int)x.size(x.dim() - 2); g.W = (int)x.size(x.dim() - 1);
+  g.is3D = x.dim() == 5 && g.D > 1;
+  c10::hip::HIPGuard guard(x.get_device());
+  std::vector<int64_t> osz = x.sizes().vec(); osz[1] = 1;
+  Tensor p = at::empty(osz, x.options());
+  const size_t bytes = std::max<size_t>(fnx_banknet3d_ws_bytes(&g, 0), 256);
+  Tensor ws = at::empty({(int64_t)bytes}, x.options().dtype(at::kByte));
+  check_status(fnx_banknet3d_forward(&g, packed.data_ptr(), x.data_ptr<float>(), p.data_ptr<float>(), precision_of(precision_mode),
+                                     ws.data_ptr(), bytes, cur_stream(x)));
+  return p;
+}
+
+std::vector<Tensor> fluidnet_bank3d_forward(Tensor packed, Tensor input, double normalize_threshold, const std::string& precision_mode) {
+  check_field(input, "input");
+  TORCH_CHECK(input.size(1) == 5 || input.size(1) == 6, "input must have 5 (2D) or 6 (3D) channels [p, U, flags, density]");
+  check_banknet3d_image(packed);
+  const bool is3D = input.size(1) == 6;
+  FnxGrid g{}; g.B = (int)input.size(0); g.D = (int)input.size(2); g.H = (int)input.size(3); g.W = (int)input.size(4);
+  g.is3D = is3D;
+  c10::hip::HIPGuard guard(input.get_device());
+  Tensor p = at::empty({g.B, 1, g.D, g.H, g.W}, input.options());
+  Tensor U = at::empty({g.B, is3D ? 3 : 2, g.D, g.H, g.W}, input.options());
+  const size_t bytes = std::max<size_t>(fnx_banknet3d_ws_bytes(&g, 1), 256);
+  Tensor ws = at::empty({(int64_t)bytes}, input.options().dtype(at::kByte));
+  check_status(fnx_fluidnet_bank3d_forward(&g, packed.data_ptr(), input.data_ptr<float>(), (float)normalize_threshold, p.data_ptr<float>(),
+                                           U.data_ptr<float>(), precision_of(precision_mode), ws.data_ptr(), bytes, cur_stream(input)));
+  return {p, U};
+}
+
 // ---- training: the CNN's backward pass (fnx_cnn_train.hip), the scenes and the loss (fnx_scenes.hip) -------------------------------
 // Every operation is one body that takes the dimension; the module registers it under its 2D and its 3D name.  A body builds the grid
 // it is given, of either dimension, and the C ABI of its own dimension refuses the other ("2D only", "3D only") before it touches the
@@ -1363,6 +1412,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("banknet_pack", &banknet_pack, py::arg("blob"), NoGil());
   m.def("banknet_forward", &banknet_forward, py::arg("packed"), py::arg("x"), py::arg("precision_mode") = "fp32", NoGil());
   m.def("fluidnet_bank_forward", &fluidnet_bank_forward, py::arg("packed"), py::arg("input"), py::arg("normalize_threshold"),
+        py::arg("precision_mode") = "fp32", NoGil());
+  m.def("banknet3d_pack", &banknet3d_pack, py::arg("blob"), NoGil());
+  m.def("banknet3d_forward", &banknet3d_forward, py::arg("packed"), py::arg("x"), py::arg("precision_mode") = "fp32", NoGil());
+  m.def("fluidnet_bank3d_forward", &fluidnet_bank3d_forward, py::arg("packed"), py::arg("input"), py::arg("normalize_threshold"),
         py::arg("precision_mode") = "fp32", NoGil());
   m.def("banknet_pack_t", &banknet_pack_t, py::arg("blob"), NoGil());
   m.def("banknet_tape_layout", &banknet_tape_layout, py::arg("B"), py::arg("H"), py::arg("W"));

@@ -1,0 +1,484 @@
+// The Conv3d counterpart of the 16-channel bank net (mconf['model'] = 'FluidNet3D'; the reference's net of lib/model.py:177-209 with every
+// module replaced by its 3D sibling), inference forward, exact fp32.
+//
+//   a  = relu(conv1(x))                               2 -> 16, 3x3x3, zero padding at the full-resolution border
+//   a2 = avgpool3d(a, 2), a4 = avgpool3d(a, 4)
+//   bank(t) = relu(cB2(relu(cB0(t))))                 16 -> 16 -> 16, 3x3x3, zero padding at THAT level's border (z included), one set of weights
+//   t  = (bank(a) + up2(bank(a2))) + up4(bank(a4))    nearest: source index k / 2, i / 2, j / 2 and k / 4, i / 4, j / 4
+//   t  = relu(conv2(t)); t = relu(conv2(t)); t = relu(conv3(t)); p = convOut(t)      1x1x1: 16 -> 16 (twice), 16 -> 8, 8 -> 1
+//
+// Unlike the 2D net this one is bound by the matrix pipe (34 560 FLOP a voxel), so the layers stay separate and the activations go
+// through HBM (155 bytes of workspace a full-resolution cell).  Six launches:
+//   bank3d_conv1_kernel          x -> a, a2, a4.  VALU.  A workgroup owns 4 x 8 x 64 cells (z, y, x); a thread owns one 2x2x2 pooling window:
+//                                it computes the 16 channels of its eight cells (weights broadcast from LDS), writes them and their mean; the
+//                                eight window means of a 4x4x4 window are added through LDS in one fixed order.
+//   bank3d_conv_kernel<false>    Conv3d 16 -> 16 + bias + ReLU at one level: block.0 on a4, a2 and a, block.2 on the two coarser levels.
+//   bank3d_conv_kernel<true>     block.2 at full resolution with the epilogue of the 2D net's R = 1 kernel: ReLU, the two coarser results
+//                                added in the order above, the four 1x1x1 layers on the accumulator registers; only p is written.
+// The convolution is an implicit GEMM on v_mfma_f32_16x16x4_f32 that marches along z.  A workgroup of four waves owns a TH x TW tile of
+// (y, x) and a range of z.  LDS holds a ring of four input planes, 16 channels x (TH + 2) rows of pitch P = TW + 2, zero where the level's
+// domain ends (a zero ACTIVATION): while plane k is computed from the slots of k - 1, k and k + 1, plane k + 2 is on its way from HBM in
+// registers; it is written to the fourth slot after the MFMAs, and one barrier a plane separates the steps.  M = 16 output channels,
+// N = 16 consecutive positions q = y * P + x of the flattened plane (the two positions a row that wrap are computed and dropped), K = 4
+// input channels of one tap: 108 MFMAs per 16 cells, their 108 A operands in registers for the whole march, B one ds_read_b32 each from
+// planes whose stride S = 16 (mod 32) floats keeps the two channels of a 32-lane group on disjoint banks.  A wave owns two groups of 16
+// positions (two independent accumulator chains).  Operand maps as in fnx_banknet.hip.
+// No atomics.  A cell's value is one fixed-order sum (bias, then dz, dy, dx, the input channels four at a time) that depends neither on
+// the batch, nor on the tile, nor on how z was split.  The sample is grid z.  Every index into an activation tensor is 64-bit.
+#include "fnx_banknet_tile.h"
+
+namespace fnx {
+namespace {
+
+// the blob: conv1, convBank.block.0, convBank.block.2, conv2, conv3, convOut; each weight (Cout, Cin, 3|1, 3|1, 3|1) then bias
+constexpr int B3_W1 = 0, B3_B1 = 864, B3_WB0 = 880, B3_WB2 = 7808, B3_W2 = 14736, B3_B2 = 14992,
+              B3_W3 = 15008, B3_B3 = 15136, B3_WO = 15144, B3_BO = 15152, B3_FLOATS = 15153;
+// the packed image (floats)
+constexpr int P3_W1 = 0;             // [cin 2][tap 27][cout 16]: the 16 weights of one input value are 64 consecutive bytes
+constexpr int P3_B1 = 864;           // 16
+constexpr int P3_WB0 = 880;          // [tap 27][kc 4][lane 64] = W[cout = lane & 15][cin = 4 kc + (lane >> 4)][tap = 9 dz + 3 dy + dx]
+constexpr int P3_BB0 = 7792;         // 16
+constexpr int P3_WB2 = 7808;
+constexpr int P3_BB2 = 14720;
+constexpr int P3_W2 = 14736;         // the 1x1x1 tail in the 2D image's layout (fnx_banknet_tile.h: PK_W2), 3 x 272
+constexpr int P3_FLOATS = 15552;     // 62 208 bytes, a multiple of 256
+
+__global__ void bank3d_pack_kernel(const float* __restrict__ blob, float* __restrict__ pk) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= P3_FLOATS) return;
+  float v = 0.f;
+  if (i < P3_B1) {
+    const int cout = i & 15, k = i >> 4;                      // k = cin * 27 + tap, the blob's own order inside an output channel
+    v = blob[B3_W1 + cout * 54 + k];
+  } else if (i < P3_WB0) {
+    v = blob[B3_B1 + i - P3_B1];
+  } else if (i < P3_W2) {
+    const bool second = i >= P3_WB2;
+    const int j = i - (second ? P3_WB2 : P3_WB0);
+    const int src = second ? B3_WB2 : B3_WB0;
+    if (j < 6912) {
+      const int lane = j & 63, kc = (j >> 6) & 3, tap = j >> 8;
+      v = blob[src + ((lane & 15) * 16 + 4 * kc + (lane >> 4)) * 27 + tap];
+    } else {
+      v = blob[src + j];                                      // the bias follows the weight in both
+    }
+  } else {
+    const int layer = (i - P3_W2) / 272, j = (i - P3_W2) % 272;
+    const int cout_n = layer == 0 ? 16 : (layer == 1 ? 8 : 1), cin_n = layer == 2 ? 8 : 16;
+    const int wsrc = layer == 0 ? B3_W2 : (layer == 1 ? B3_W3 : B3_WO), bsrc = layer == 0 ? B3_B2 : (layer == 1 ? B3_B3 : B3_BO);
+    if (j < 256) {
+      const int lane = j & 63, r = j >> 6;
+      const int cout = lane & 15, cin = 4 * (lane >> 4) + r;
+      if (cout < cout_n && cin < cin_n) v = blob[wsrc + cout * cin_n + cin];
+    } else if (j - 256 < cout_n) {
+      v = blob[bsrc + j - 256];
+    }
+  }
+  pk[i] = v;
+}
+
+// ---- conv1 and the two poolings ---------------------------------------------------------------------------------------------------------
+constexpr int C1_TD = 4, C1_TH = 8, C1_TW = 64;                              // cells of a workgroup: multiples of 4, so no pooling window crosses
+constexpr int C1_XD = C1_TD + 2, C1_XH = C1_TH + 2, C1_XW = C1_TW + 2;       // the x tile with its halo
+constexpr int C1_XFLOATS = 2 * C1_XD * C1_XH * C1_XW;                        // 7 920
+constexpr int C1_WIN = (C1_TD / 2) * (C1_TH / 2) * (C1_TW / 2);              // 256 windows of 2x2x2 = 256 threads
+static_assert(C1_WIN == 256 && C1_XFLOATS >= 16 * C1_WIN, "the window means reuse the x tile's LDS");
+
+// x (B, 2, D, H, W) -> a (B, 16, D, H, W), a2 (B, 16, D/2, H/2, W/2), a4 (B, 16, D/4, H/4, W/4).  256 threads.
+// grid: (x tiles, y tiles * z tiles, B)
+__global__ __launch_bounds__(256) void bank3d_conv1_kernel(const float* __restrict__ pk, const float* __restrict__ x, int D, int H, int W,
+                                                           int tiles_y, float* __restrict__ a, float* __restrict__ a2,
+                                                           float* __restrict__ a4) {
+  __shared__ float lds[C1_XFLOATS];
+  __shared__ float lw[P3_WB0];                                  // conv1's weights and bias: every lane reads the same address (a broadcast)
+  const int tid = threadIdx.x;
+  const int b = blockIdx.z;
+  for (int i = tid; i < P3_WB0; i += 256) lw[i] = pk[i];
+  const int x0 = blockIdx.x * C1_TW, y0 = (blockIdx.y % tiles_y) * C1_TH, z0 = (blockIdx.y / tiles_y) * C1_TD;
+  const size_t HW = (size_t)H * W, DHW = (size_t)D * HW;
+  {
+    const float* xb = x + (size_t)b * 2 * DHW;
+    for (int i = tid; i < C1_XFLOATS; i += 256) {
+      const int xx = i % C1_XW, r = i / C1_XW;
+      const int yy = r % C1_XH, zz = (r / C1_XH) % C1_XD, c = r / (C1_XH * C1_XD);
+      const int gz = z0 - 1 + zz, gy = y0 - 1 + yy, gx = x0 - 1 + xx;
+      float v = 0.f;
+      if (gz >= 0 && gz < D && gy >= 0 && gy < H && gx >= 0 && gx < W) v = xb[(size_t)c * DHW + (size_t)gz * HW + (size_t)gy * W + gx];
+      lds[i] = v;
+    }
+  }
+  __syncthreads();
+  // this thread's window: cells (z0 + 2 wz + pz, y0 + 2 wy + py, x0 + 2 wx + px)
+  const int wx = tid & 31, wy = (tid >> 5) & 3, wz = tid >> 7;
+  const int cz = z0 + 2 * wz, cy = y0 + 2 * wy, cx = x0 + 2 * wx;
+  const bool inside = cz < D && cy < H && cx < W;              // D, H, W are even: a window is inside or outside as a whole
+  float pool[16];
+#pragma unroll
+  for (int c = 0; c < 16; ++c) pool[c] = 0.f;
+  if (inside) {
+    float* ab = a + (size_t)b * 16 * DHW;
+    for (int pz = 0; pz < 2; ++pz)
+      for (int py = 0; py < 2; ++py) {
+        __asm__ volatile("" ::: "memory");                        // the 880 weights are read again per pair of cells, not hoisted into registers
+        float acc[2][16];
+#pragma unroll
+        for (int c = 0; c < 16; ++c) acc[0][c] = acc[1][c] = lw[P3_B1 + c];
+        const float* lp = lds + ((2 * wz + pz) * C1_XH + 2 * wy + py) * C1_XW + 2 * wx;
+#pragma unroll
+        for (int ci = 0; ci < 2; ++ci)
+#pragma unroll
+          for (int dz = 0; dz < 3; ++dz)
+#pragma unroll
+            for (int dy = 0; dy < 3; ++dy) {
+              float in[4];
+#pragma unroll
+              for (int k = 0; k < 4; ++k) in[k] = lp[((ci * C1_XD + dz) * C1_XH + dy) * C1_XW + k];
+#pragma unroll
+              for (int dx = 0; dx < 3; ++dx) {
+                const float* wrow = lw + P3_W1 + (ci * 27 + dz * 9 + dy * 3 + dx) * 16;
+#pragma unroll
+                for (int c = 0; c < 16; ++c) {
+                  acc[0][c] = fmaf(wrow[c], in[dx], acc[0][c]);
+                  acc[1][c] = fmaf(wrow[c], in[dx + 1], acc[1][c]);
+                }
+              }
+            }
+        const size_t cell = (size_t)(cz + pz) * HW + (size_t)(cy + py) * W + cx;
+#pragma unroll
+        for (int c = 0; c < 16; ++c) {
+          const float v0 = fmaxf(acc[0][c], 0.f), v1 = fmaxf(acc[1][c], 0.f);
+          *reinterpret_cast<float2*>(ab + (size_t)c * DHW + cell) = make_float2(v0, v1);        // cx and W are even: 8-byte aligned
+          pool[c] += v0;                                                                        // the window's order: z, y, x
+          pool[c] += v1;
+        }
+      }
+    const int D2 = D / 2, H2 = H / 2, W2 = W / 2;
+    float* a2b = a2 + (size_t)b * 16 * D2 * H2 * W2;
+#pragma unroll
+    for (int c = 0; c < 16; ++c) {
+      pool[c] *= 0.125f;
+      a2b[(((size_t)c * D2 + cz / 2) * H2 + cy / 2) * W2 + cx / 2] = pool[c];
+    }
+  }
+  __syncthreads();                                             // every thread is done with the x tile
+#pragma unroll
+  for (int c = 0; c < 16; ++c) lds[c * C1_WIN + tid] = pool[c];
+  __syncthreads();
+  // the 4x4x4 windows: 1 x 2 x 16 of them and 16 channels = 512 values, two a thread; eight window means in the order z, y, x
+  const int D4 = D / 4, H4 = H / 4, W4 = W / 4;
+  float* a4b = a4 + (size_t)b * 16 * D4 * H4 * W4;
+  for (int i = tid; i < 16 * 32; i += 256) {
+    const int qx = i & 15, qy = (i >> 4) & 1, c = i >> 5;
+    if (z0 < D && y0 + 4 * qy < H && x0 + 4 * qx < W) {
+      float s = 0.f;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) s += lds[c * C1_WIN + (k >> 2) * 128 + (2 * qy + ((k >> 1) & 1)) * 32 + 2 * qx + (k & 1)];
+      a4b[(((size_t)c * D4 + z0 / 4) * H4 + y0 / 4 + qy) * W4 + x0 / 4 + qx] = s * 0.125f;
+    }
+  }
+}
+
+// ---- the 16 -> 16 convolution, marching along z -----------------------------------------------------------------------------------------
+constexpr int CV_TH = 4, CV_TW = 30;
+constexpr int CV_P = CV_TW + 2, CV_ROWS = CV_TH + 2;            // pitch 32
+constexpr int CV_NA = CV_ROWS * CV_P;                           // 192 cells of an input plane
+constexpr int CV_Q = CV_TH * CV_P, CV_G = CV_Q / 16;            // 128 flattened positions, 8 groups: two a wave
+constexpr int CV_SMIN = 16 * CV_G + 2 * CV_P + 2;               // a position reads up to 2 P + 2 beyond itself
+constexpr int CV_S = (CV_SMIN + 15) / 32 * 32 + 16;             // 208
+constexpr int CV_SLOT = 16 * CV_S;                              // floats of a ring slot
+constexpr int CV_LOADS = 16 * CV_NA / 256;                      // 12 values of a plane per thread
+static_assert(CV_G == 8 && CV_Q % 16 == 0 && CV_S >= CV_SMIN && CV_S % 32 == 16 && 4 * CV_SLOT * 4 <= 64 * 1024, "tile geometry");
+static_assert(16 * CV_NA % 256 == 0, "plane load");
+
+// in (B, 16, d, h, w) -> out = relu(conv(in) + bias) (B, 16, d, h, w); TAIL: l2, l4 the coarser banks' results, p (B, 1, d, h, w) instead.
+// grid: (x tiles, y tiles * z chunks, B); the workgroup computes planes [zc * chunk, min(d, (zc + 1) * chunk)).  256 threads.
+template <bool TAIL>
+__global__ __launch_bounds__(256) void bank3d_conv_kernel(const float* __restrict__ wpk, const float* __restrict__ bias,
+                                                          const float* __restrict__ tail, const float* __restrict__ in, int d, int h, int w,
+                                                          int tiles_y, int chunk, float* __restrict__ out, const float* __restrict__ l2,
+                                                          const float* __restrict__ l4, float* __restrict__ p) {
+  __shared__ float lds[4 * CV_SLOT];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int b = blockIdx.z;
+  const int x0 = blockIdx.x * CV_TW, y0 = (blockIdx.y % tiles_y) * CV_TH;
+  const int z0 = (blockIdx.y / tiles_y) * chunk, z1 = min(d, z0 + chunk);
+  const size_t hw = (size_t)h * w, dhw = (size_t)d * hw;
+  const float* inb = in + (size_t)b * 16 * dhw;
+
+  for (int i = tid; i < 4 * CV_SLOT; i += 256) lds[i] = 0.f;      // the pad of every plane, read by positions that are dropped
+
+  // what this thread loads of every plane: value j is channel ch, cell (y0 - 1 + row, x0 - 1 + col)
+  size_t goff[CV_LOADS];
+  int loff[CV_LOADS];
+  unsigned okmask = 0;
+#pragma unroll
+  for (int j = 0; j < CV_LOADS; ++j) {
+    const int i = tid + 256 * j;
+    const int ch = i / CV_NA, rem = i % CV_NA;
+    const int gy = y0 - 1 + rem / CV_P, gx = x0 - 1 + rem % CV_P;
+    const bool ok = gy >= 0 && gy < h && gx >= 0 && gx < w;
+    goff[j] = ok ? (size_t)ch * dhw + (size_t)gy * w + gx : 0;
+    loff[j] = ch * CV_S + rem;
+    if (ok) okmask |= 1u << j;
+  }
+  float pre[CV_LOADS];
+  auto fetch = [&](int z) {                                       // plane z of the level, zero outside its domain
+    const bool zin = z >= 0 && z < d;
+    const float* src = inb + (size_t)(zin ? z : 0) * hw;
+#pragma unroll
+    for (int j = 0; j < CV_LOADS; ++j) pre[j] = (zin && ((okmask >> j) & 1)) ? src[goff[j]] : 0.f;
+  };
+  auto stash = [&](int z) {                                       // into the slot of plane z: (z + 1) & 3  (z >= -1)
+    float* dst = lds + ((z + 1) & 3) * CV_SLOT;
+#pragma unroll
+    for (int j = 0; j < CV_LOADS; ++j) dst[loff[j]] = pre[j];
+  };
+
+  float wa[108];
+#pragma unroll
+  for (int i = 0; i < 108; ++i) wa[i] = wpk[i * 64 + lane];
+  f32x4 b4;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) b4[r] = bias[4 * (lane >> 4) + r];
+  float wt[3][4];
+  f32x4 bt[3];
+  if constexpr (TAIL) {
+#pragma unroll
+    for (int l = 0; l < 3; ++l)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        wt[l][r] = tail[l * 272 + r * 64 + lane];
+        bt[l][r] = tail[l * 272 + 256 + 4 * (lane >> 4) + r];
+      }
+  }
+
+  __syncthreads();                                                // the zeros are in place
+  for (int z = z0 - 1; z <= z0 + 1; ++z) {
+    fetch(z);
+    stash(z);
+  }
+  __syncthreads();
+
+  // this wave's two groups of positions; its lanes' cells
+  const int q0 = 32 * wave + (lane & 15), q1 = q0 + 16;
+  const int ry = q0 / CV_P;                                       // both groups lie in row `wave` (P = 32)
+  const int gy = y0 + ry, gx0 = x0 + q0 % CV_P, gx1 = x0 + q1 % CV_P;
+  const bool ok0 = gy < h && q0 % CV_P < CV_TW && gx0 < w, ok1 = gy < h && q1 % CV_P < CV_TW && gx1 < w;
+  const int lbase = (lane >> 4) * CV_S + q0;
+  const int g4 = 4 * (lane >> 4);
+
+  for (int z = z0; z < z1; ++z) {
+    if (z + 2 <= z1) fetch(z + 2);                                // in flight during the MFMAs (plane z1 + 1 is never read)
+    f32x4 acc0 = b4, acc1 = b4;
+#pragma unroll
+    for (int dz = 0; dz < 3; ++dz) {
+      const float* sp = lds + ((z + dz) & 3) * CV_SLOT + lbase;   // the slot of plane z - 1 + dz
+#pragma unroll
+      for (int t = 0; t < 9; ++t)
+#pragma unroll
+        for (int kc = 0; kc < 4; ++kc) {
+          const int off = kc * 4 * CV_S + (t / 3) * CV_P + (t % 3);
+          acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[(dz * 9 + t) * 4 + kc], sp[off], acc0, 0, 0, 0);
+          acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[(dz * 9 + t) * 4 + kc], sp[off + 16], acc1, 0, 0, 0);
+        }
+    }
+    if constexpr (!TAIL) {
+      float* ob = out + (size_t)b * 16 * dhw + (size_t)z * hw + (size_t)gy * w;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        if (ok0) ob[(size_t)(g4 + r) * dhw + gx0] = fmaxf(acc0[r], 0.f);
+        if (ok1) ob[(size_t)(g4 + r) * dhw + gx1] = fmaxf(acc1[r], 0.f);
+      }
+    } else {
+      const int d2 = d / 2, h2 = h / 2, w2 = w / 2, d4 = d / 4, h4 = h / 4, w4 = w / 4;
+      const float* l2b = l2 + (size_t)b * 16 * d2 * h2 * w2;
+      const float* l4b = l4 + (size_t)b * 16 * d4 * h4 * w4;
+      const int cy = gy < h ? gy : h - 1;                         // every lane runs the MFMAs; a lane without a cell reads a clamped one
+#pragma unroll
+      for (int half = 0; half < 2; ++half) {
+        const int gx = half ? gx1 : gx0;
+        const int cx = gx < w ? gx : w - 1;
+        const f32x4 v = half ? acc1 : acc0;
+        f32x4 t;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const size_t ch = g4 + r;
+          t[r] = (fmaxf(v[r], 0.f) + l2b[((ch * d2 + z / 2) * h2 + cy / 2) * w2 + cx / 2]) + l4b[((ch * d4 + z / 4) * h4 + cy / 4) * w4 + cx / 4];
+        }
+        // conv2, conv2 again, conv3, convOut: register r of a result is the B operand of input channels 4g + r
+#pragma unroll
+        for (int l = 0; l < 4; ++l) {
+          const int m = l == 0 ? 0 : l - 1;
+          f32x4 hh = bt[m];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) hh = __builtin_amdgcn_mfma_f32_16x16x4f32(wt[m][r], t[r], hh, 0, 0, 0);
+          if (l < 3) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) t[r] = fmaxf(hh[r], 0.f);
+          } else {
+            t = hh;
+          }
+        }
+        if ((half ? ok1 : ok0) && lane < 16) p[(size_t)b * dhw + (size_t)z * hw + (size_t)gy * w + gx] = t[0];
+      }
+    }
+    if (z + 2 <= z1) stash(z + 2);                                // the slot of plane z - 2, which no wave reads since the last barrier
+    __syncthreads();
+  }
+}
+
+// ---- the launch plan: a host function of (B, D, H, W) alone -----------------------------------------------------------------------------
+constexpr long long BANK3D_TARGET_GROUPS = 4096;
+struct Bank3dConvPlan { int tiles_x, tiles_y, chunk, chunks; };
+inline Bank3dConvPlan bank3d_conv_plan(int B, int d, int h, int w) {
+  Bank3dConvPlan pl{};
+  pl.tiles_x = (w + CV_TW - 1) / CV_TW;
+  pl.tiles_y = (h + CV_TH - 1) / CV_TH;
+  // split z until about 4096 workgroups are in flight (16 a CU), but keep at least four planes a chunk: a chunk loads two planes more
+  const long long tiles = (long long)B * pl.tiles_x * pl.tiles_y;
+  long long want = (BANK3D_TARGET_GROUPS + tiles - 1) / tiles;
+  const int most = d / 4 > 1 ? d / 4 : 1;
+  if (want > most) want = most;
+  if (want < 1) want = 1;
+  pl.chunk = (int)((d + want - 1) / want);
+  pl.chunks = (d + pl.chunk - 1) / pl.chunk;
+  return pl;
+}
+
+struct Bank3dWs { float *a, *h, *a2, *h2, *b2, *a4, *h4, *b4; size_t bytes; };
+inline Bank3dWs bank3d_ws_layout(int B, int D, int H, int W, void* base) {
+  const size_t n1 = (size_t)B * 16 * D * H * W * 4, n2 = n1 / 8, n4 = n1 / 64;      // bytes: 64 + 64 + 3 * 8 + 3 * 1 = 155 a cell
+  size_t off = 0;
+  auto take = [&](size_t bytes) { float* r = base ? (float*)((char*)base + off) : nullptr; off += al256(bytes); return r; };
+  Bank3dWs ws{};
+  ws.a = take(n1); ws.h = take(n1);
+  ws.a2 = take(n2); ws.h2 = take(n2); ws.b2 = take(n2);
+  ws.a4 = take(n4); ws.h4 = take(n4); ws.b4 = take(n4);
+  ws.bytes = off;
+  return ws;
+}
+
+void bank3d_forward(int B, int D, int H, int W, const float* pk, const float* x, float* p, void* wsp, hipStream_t s) {
+  const Bank3dWs ws = bank3d_ws_layout(B, D, H, W, wsp);
+  ProfScope ps(FNX_PROF_CONV_MFMA16, s);
+  {
+    const int ty = (H + C1_TH - 1) / C1_TH, tz = (D + C1_TD - 1) / C1_TD;
+    bank3d_conv1_kernel<<<dim3((unsigned)((W + C1_TW - 1) / C1_TW), (unsigned)(ty * tz), (unsigned)B), 256, 0, s>>>(pk, x, D, H, W, ty, ws.a,
+                                                                                                                  ws.a2, ws.a4);
+  }
+  auto conv = [&](int R, bool second, const float* in, float* out) {
+    const int d = D / R, h = H / R, w = W / R;
+    const Bank3dConvPlan pl = bank3d_conv_plan(B, d, h, w);
+    bank3d_conv_kernel<false><<<dim3((unsigned)pl.tiles_x, (unsigned)(pl.tiles_y * pl.chunks), (unsigned)B), 256, 0, s>>>(
+        pk + (second ? P3_WB2 : P3_WB0), pk + (second ? P3_BB2 : P3_BB0), nullptr, in, d, h, w, pl.tiles_y, pl.chunk, out, nullptr, nullptr,
+        nullptr);
+  };
+  conv(4, false, ws.a4, ws.h4);
+  conv(4, true, ws.h4, ws.b4);
+  conv(2, false, ws.a2, ws.h2);
+  conv(2, true, ws.h2, ws.b2);
+  conv(1, false, ws.a, ws.h);
+  const Bank3dConvPlan pl = bank3d_conv_plan(B, D, H, W);
+  bank3d_conv_kernel<true><<<dim3((unsigned)pl.tiles_x, (unsigned)(pl.tiles_y * pl.chunks), (unsigned)B), 256, 0, s>>>(
+      pk + P3_WB2, pk + P3_BB2, pk + P3_W2, ws.h, D, H, W, pl.tiles_y, pl.chunk, nullptr, ws.b2, ws.b4, p);
+}
+
+// The scratch of the whole forward: the flags copy, the divergence, the net's input, scale_std's partial sums, the per-sample scales, the
+// net's own workspace; each rounded up to 256 bytes.
+struct Bank3dFluidnetWs { float* flags; float* div; float* x; double* partial; float* scale; void* net; size_t bytes; };
+Bank3dFluidnetWs bank3d_fluidnet_ws_layout(int B, int D, int H, int W, void* base) {
+  const size_t full = (size_t)B * D * H * W;
+  size_t off = 0;
+  auto take = [&](size_t bytes) { void* r = base ? (char*)base + off : nullptr; off += al256(bytes); return r; };
+  Bank3dFluidnetWs w{};
+  w.flags = (float*)take(full * 4);
+  w.div = (float*)take(full * 4);
+  w.x = (float*)take(full * 2 * 4);
+  w.partial = (double*)take(scale_std_scratch_bytes(B));
+  w.scale = (float*)take(sizeof(float) * B);
+  w.net = take(bank3d_ws_layout(B, D, H, W, nullptr).bytes);
+  w.bytes = off;
+  return w;
+}
+
+// The checks the entry points share, before any device call, each refusal with its own text.
+int check_bank3d_call(const char* fn, const FnxGrid* g, bool args, int precision_mode, bool whole, size_t ws_bytes) {
+  if (!g || !args) return set_error(FNX_EINVAL, "%s: null argument", fn);
+  if (!g->is3D || g->D < 4)
+    return set_error(FNX_EINVAL, "%s: the Conv3d bank net ('FluidNet3D' model) is 3D only (is3D = %d, D = %d)", fn, g->is3D, g->D);
+  const int mode = net_mode(precision_mode);
+  if (mode < 0)
+    return set_error(FNX_EINVAL, "%s: unknown precision_mode %d (FNX_PRECISION_FP32, _FP32_DIRECT, _BF16X6, _BF16X3, _FP32_F4 or _FP32_F2)", fn,
+                     precision_mode);
+  if (mode == FNX_PRECISION_BF16X6 || mode == FNX_PRECISION_BF16X3)
+    return set_error(FNX_EINVAL, "%s: the bank net runs in fp32 arithmetic only (FNX_PRECISION_FP32, _FP32_F4, _FP32_F2 or _FP32_DIRECT), "
+                     "not in the bf16 modes (precision_mode %d)", fn, precision_mode);
+  if (g->B < 1 || g->B > 65535) return set_error(FNX_EINVAL, "%s: batch size %d is outside 1 .. 65535", fn, g->B);
+  if (g->D % 4) return set_error(FNX_EINVAL, "%s: D = %d must be a positive multiple of 4 (the three levels are added)", fn, g->D);
+  if (g->H < 4 || g->H % 4) return set_error(FNX_EINVAL, "%s: H = %d must be a positive multiple of 4 (the three levels are added)", fn, g->H);
+  if (g->W < 4 || g->W % 4) return set_error(FNX_EINVAL, "%s: W = %d must be a positive multiple of 4 (the three levels are added)", fn, g->W);
+  const size_t cells = (size_t)g->D * g->H * g->W;
+  if (cells >= ((size_t)1 << 31) || (size_t)(g->D / 4) * (g->H / 4) > 65535)      // grid y: (y tiles) x (z tiles or chunks)
+    return set_error(FNX_EINVAL, "%s: D * H * W = %zu cells per sample (D = %d, H = %d) is beyond the bank kernels' launch range", fn, cells,
+                     g->D, g->H);
+  const size_t want = whole ? bank3d_fluidnet_ws_layout(g->B, g->D, g->H, g->W, nullptr).bytes
+                            : bank3d_ws_layout(g->B, g->D, g->H, g->W, nullptr).bytes;
+  if (ws_bytes < want) return set_error(FNX_EWORKSPACE, "%s: workspace of %zu bytes is too small (%zu needed)", fn, ws_bytes, want);
+  return FNX_OK;
+}
+
+}  // namespace
+}  // namespace fnx
+
+extern "C" {
+
+size_t fnx_banknet3d_weight_floats(void) { return fnx::B3_FLOATS; }
+size_t fnx_banknet3d_packed_bytes(void) { return (size_t)fnx::P3_FLOATS * sizeof(float); }
+
+int fnx_banknet3d_pack(const float* weights_blob, void* packed, void* stream) {
+  if (!weights_blob || !packed) return fnx::set_error(FNX_EINVAL, "%s: null argument", __func__);
+  fnx::bank3d_pack_kernel<<<(fnx::P3_FLOATS + 255) / 256, 256, 0, (hipStream_t)stream>>>(weights_blob, (float*)packed);
+  return fnx::bank_status();
+}
+
+size_t fnx_banknet3d_ws_bytes(const FnxGrid* g, int whole_forward) {
+  if (!g || g->B < 1 || g->D < 4 || g->H < 4 || g->W < 4) return 0;
+  return whole_forward ? fnx::bank3d_fluidnet_ws_layout(g->B, g->D, g->H, g->W, nullptr).bytes
+                       : fnx::bank3d_ws_layout(g->B, g->D, g->H, g->W, nullptr).bytes;
+}
+
+int fnx_banknet3d_launch_plan(const FnxGrid* g, int level, int plan[6]) {
+  if (!g || !plan || (level != 1 && level != 2 && level != 4) || g->B < 1 || g->D < 4 || g->H < 4 || g->W < 4 || g->D % 4 || g->H % 4 || g->W % 4)
+    return fnx::set_error(FNX_EINVAL, "%s: a grid with D, H and W positive multiples of 4 and a level of 1, 2 or 4", __func__);
+  const fnx::Bank3dConvPlan pl = fnx::bank3d_conv_plan(g->B, g->D / level, g->H / level, g->W / level);
+  plan[0] = pl.tiles_x; plan[1] = pl.tiles_y; plan[2] = pl.chunks; plan[3] = pl.chunk; plan[4] = fnx::CV_TH; plan[5] = fnx::CV_TW;
+  return FNX_OK;
+}
+
+int fnx_banknet3d_forward(const FnxGrid* g, const void* packed, const float* x, float* p, int precision_mode, void* ws, size_t ws_bytes,
+                          void* stream) {
+  if (int rc = fnx::check_bank3d_call(__func__, g, packed && x && p && ws, precision_mode, false, ws_bytes)) return rc;
+  fnx::bank3d_forward(g->B, g->D, g->H, g->W, (const float*)packed, x, p, ws, (hipStream_t)stream);
+  return fnx::bank_status();
+}
+
+int fnx_fluidnet_bank3d_forward(const FnxGrid* g, const void* packed, const float* input, float thr, float* p_out, float* U_out,
+                                int precision_mode, void* ws, size_t ws_bytes, void* stream) {
+  if (int rc = fnx::check_bank3d_call(__func__, g, packed && input && p_out && U_out && ws, precision_mode, true, ws_bytes)) return rc;
+  const GridDims d = make_dims(g->B, g->D, g->H, g->W, g->z_offset, g->D_global);
+  hipStream_t s = (hipStream_t)stream;
+  const fnx::Bank3dFluidnetWs w = fnx::bank3d_fluidnet_ws_layout(g->B, g->D, g->H, g->W, ws);
+  // FluidNet.forward around the net, with the launches of fnx_fluidnet_bank_forward on three velocity components
+  fnx::launch_gather_input(d, 3, input, U_out, w.flags, s);
+  if (int rc = fnx_velocity_divergence(g, U_out, w.flags, w.div, stream)) return rc;
+  fnx::launch_scale_std(d, 3, U_out, thr, w.partial, w.scale, s);
+  fnx::launch_pack_input(d, 3, w.div, w.flags, w.scale, U_out, w.x, s);
+  fnx::bank3d_forward(g->B, g->D, g->H, g->W, (const float*)packed, w.x, p_out, w.net, s);
+  if (int rc = fnx_velocity_update(g, p_out, U_out, w.flags, stream)) return rc;
+  fnx::launch_unscale(d, 3, w.scale, p_out, U_out, s);
+  if (int rc = fnx_set_wall_bcs(g, U_out, w.flags, stream)) return rc;
+  return fnx::bank_status();
+}
+
+}  // extern "C"

@@ -13,7 +13,8 @@ Weights are torch-style state-dict entries (`multiScale.convN_4.encode.0.weight`
 kernels lazily, on the first forward on a given device (and again after `load_state_dict` / `.to()`).
 
 mconf['model'] = 'FluidNet' selects the reference's other net (model.py:177-209), the 16-channel bank net of `conv1`, `convBank`,
-`conv2`, `conv3` and `convOut`: `BankNet` / `net.bank(x)`, 2D, fp32 modes (csrc/fnx_banknet.hip).
+`conv2`, `conv3` and `convOut`: `BankNet` / `net.bank(x)`, 2D, fp32 modes (csrc/fnx_banknet.hip).  mconf['model'] = 'FluidNet3D' (with
+is3D) is that net with every module replaced by its 3D sibling, this project's own definition: `BankNet3D` (csrc/fnx_banknet3d.hip).
 """
 from collections import OrderedDict
 
@@ -21,7 +22,7 @@ import numpy as np
 import torch
 
 from ._ext import ext
-from .weights import banknet_layers, make_banknet_weights, make_scalenet_weights, scalenet_layers
+from .weights import banknet_layers, make_banknet3d_weights, make_banknet_weights, make_scalenet_weights, scalenet_layers
 
 # Parameters of the reference FluidNet that its ScaleNet forward never reads (model.py:59-72: conv1, convBank, conv2,
 # conv3, convOut are only used by the 'FluidNet' variant).  A checkpoint of the reference carries them; load_state_dict
@@ -83,6 +84,20 @@ class BankNet:
         return ext.banknet_forward(self.packed, x.contiguous(), self.precision_mode)
 
 
+class BankNet3D:
+    """x (B,2,D,H,W) -> (B,1,D,H,W): the Conv3d counterpart of BankNet, mconf['model'] = 'FluidNet3D' (fnx_banknet3d.hip).  D, H and W
+    multiples of 4, fp32 modes."""
+
+    def __init__(self, state_dict, device="cuda", precision_mode="fp32"):
+        self.is3D = True
+        self.precision_mode = precision_mode
+        blob = torch.from_numpy(blob_from_state_dict(state_dict, keys=_bank_keys())).to(device)
+        self.packed = ext.banknet3d_pack(blob)
+
+    def __call__(self, x):
+        return ext.banknet3d_forward(self.packed, x.contiguous(), self.precision_mode)
+
+
 class FluidNet:
     """input_ (B,5|6,D,H,W) = [p, U, flags, density] -> (p, U)   (model.py:76-227)
 
@@ -96,13 +111,21 @@ class FluidNet:
     only: a fresh net holds weights.make_banknet_weights(0), `load_state_dict` requires the twelve conv1 / convBank / conv2 / conv3 /
     convOut tensors and keeps multiScale.* and scale.*, `net.bank(x)` is the net alone, and `packed_for` raises -- the native step,
     the z-slab drivers and FluidNetTrain take the ScaleNet image only; `simulate()` runs such a net operator by operator, and
-    train.FluidNetBankTrain is its counterpart with a native backward pass."""
+    train.FluidNetBankTrain is its counterpart with a native backward pass.
+
+    model='FluidNet3D' (with is3D=True; not a reference model, which is 2D only) is the same net with every module replaced by its 3D
+    sibling: a fresh net holds weights.make_banknet3d_weights(0), the twelve tensors have 5-D weights, `net.bank(x)` takes
+    (B,2,D,H,W) with D, H and W multiples of 4, and everything else is as for 'FluidNet'.  Inference only: no trainer takes it."""
 
     def __init__(self, mconf, dropout=True):
         model = mconf.get("model", "ScaleNet")
-        assert model in ("ScaleNet", "FluidNet"), "mconf['model'] must be 'ScaleNet' or 'FluidNet' (the 16-channel bank net)"
-        self.is_bank = model == "FluidNet"
-        assert not (self.is_bank and mconf.get("is3D", False)), "the 'FluidNet' bank model is 2D only (the reference asserts it)"
+        assert model in ("ScaleNet", "FluidNet", "FluidNet3D"), \
+            "mconf['model'] must be 'ScaleNet' or 'FluidNet' (the 16-channel bank net) or 'FluidNet3D' (its Conv3d counterpart)"
+        self.is_bank3d = model == "FluidNet3D"
+        self.is_bank = model in ("FluidNet", "FluidNet3D")       # simulate() runs such a net operator by operator
+        assert not (model == "FluidNet" and mconf.get("is3D", False)), \
+            "the 'FluidNet' bank model is 2D only (the reference asserts it); its Conv3d counterpart is model='FluidNet3D'"
+        assert not (self.is_bank3d and not mconf.get("is3D", False)), "the 'FluidNet3D' bank model is 3D only (is3D=True); 'FluidNet' is the 2D net"
         ic = mconf.get("inputChannels", {"div": True, "pDiv": False, "UDiv": False})
         assert ic.get("div", False) and not ic.get("pDiv", False) and not ic.get("UDiv", False), \
             "inputChannels must be {div} (convModel_mconf.pth)"
@@ -116,7 +139,8 @@ class FluidNet:
         self.precision_mode = str(mconf.get("precisionMode", "fp32"))
         self.training = False
         self._ndim = 3 if self.is3D else 2
-        init = make_banknet_weights(0) if self.is_bank else make_scalenet_weights(0, ndim=self._ndim)
+        init = (make_banknet3d_weights(0) if self.is_bank3d else make_banknet_weights(0) if self.is_bank
+                else make_scalenet_weights(0, ndim=self._ndim))
         self._params = OrderedDict((k, torch.from_numpy(v)) for k, v in init.items())
         self._want = _bank_keys() if self.is_bank else _layer_keys(self._ndim)
         self._unused = _BANK_UNUSED_PREFIXES if self.is_bank else _UNUSED_PREFIXES
@@ -193,13 +217,14 @@ class FluidNet:
         if device.type == "cuda" and device.index is None:
             device = torch.device("cuda", torch.cuda.current_device())
         if self._ms is None or self._ms_device != device:
-            self._ms = (BankNet(self._params, device, self.precision_mode) if self.is_bank
+            self._ms = (BankNet3D(self._params, device, self.precision_mode) if self.is_bank3d
+                        else BankNet(self._params, device, self.precision_mode) if self.is_bank
                         else MultiScaleNet(self._params, device, self.is3D, self.precision_mode))
             self._ms_device = device
         return self._ms
 
     def _not_scalenet(self, what):
-        raise RuntimeError(f"FluidNet.{what}: this net is the 'FluidNet' bank model; the native step, the z-slab drivers and the trainers "
+        raise RuntimeError(f"FluidNet.{what}: this net is the '{self.mconf.get('model')}' bank model; the native step, the z-slab drivers and the trainers "
                            "take the ScaleNet image only (net.bank(x) and net(input) run the bank kernels)")
 
     @property
@@ -210,7 +235,7 @@ class FluidNet:
 
     @property
     def bank(self):
-        """The bank net alone, x (B,2,H,W) -> (B,1,H,W): the counterpart of `multiScale` for model='FluidNet'."""
+        """The bank net alone, x (B,2,H,W) -> (B,1,H,W) ('FluidNet3D': (B,2,D,H,W) -> (B,1,D,H,W)): the counterpart of `multiScale`."""
         if not self.is_bank:
             raise RuntimeError("FluidNet.bank: this net is the ScaleNet model (net.multiScale(x))")
         return self._ensure_packed(self._device if self._device is not None else "cuda")
@@ -227,7 +252,7 @@ class FluidNet:
 
     def __call__(self, input_):
         ms = self._ensure_packed(input_.device)
-        fwd = ext.fluidnet_bank_forward if self.is_bank else ext.fluidnet_forward
+        fwd = ext.fluidnet_bank3d_forward if self.is_bank3d else ext.fluidnet_bank_forward if self.is_bank else ext.fluidnet_forward
         p, U = fwd(ms.packed, input_.contiguous(), self.threshold, self.precision_mode)
         return p, U
 

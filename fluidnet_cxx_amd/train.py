@@ -180,6 +180,12 @@ class _MultiScaleTrain(torch.nn.Module):
         return _MultiScaleFn.apply(x, self, *self._ordered())
 
 
+def _refuse_bank3d(mconf, name):
+    if mconf.get("model", "ScaleNet") == "FluidNet3D":
+        raise ValueError(f"{name}: training the 'FluidNet3D' model is not built (the Conv3d bank net has an inference forward only, "
+                         "FluidNet(mconf); the trainers take the ScaleNet and the 2D 'FluidNet' bank net)")
+
+
 class _FluidNetTrainBase(torch.nn.Module):
     """What FluidNetTrain (2D), FluidNetTrain3D and FluidNetBankTrain share: everything but the dimension, which a subclass states in
     _NDIM, its check of mconf['is3D'] (_check_dim), and the net in the middle (_check_model, _build_net, _ordered, _packed)."""
@@ -188,6 +194,7 @@ class _FluidNetTrainBase(torch.nn.Module):
     _UNUSED = _UNUSED_PREFIXES           # the reference's parameters this model's forward never reads, kept for state_dict()
 
     def _check_model(self, mconf, name):
+        _refuse_bank3d(mconf, name)
         if mconf.get("model", "ScaleNet") != "ScaleNet":
             raise ValueError(f"{name}: only the ScaleNet variant is accelerated")
 
@@ -286,6 +293,7 @@ class FluidNetBankTrain(_FluidNetTrainBase):
     _UNUSED = _BANK_UNUSED_PREFIXES
 
     def _check_model(self, mconf, name):
+        _refuse_bank3d(mconf, name)
         if mconf.get("model", "ScaleNet") != "FluidNet":
             raise ValueError(f"{name}: mconf['model'] must be 'FluidNet', the 16-channel bank net (FluidNetTrain trains the ScaleNet)")
 

@@ -92,4 +92,7 @@ def train3d(mconf=None, tconf=None, device="cuda", out=None, resume=None, log=No
     tconf = dict(TCONF3D_DEFAULTS, **(tconf or {}))
     D, H, W = (int(tconf.get(k, tconf["res"])) for k in ("D", "H", "W"))
     _refuse_2d("train3d", mconf, D)
+    if mconf.get("model", "ScaleNet") == "FluidNet3D":
+        raise ValueError("train3d: training the 'FluidNet3D' model is not built (the Conv3d bank net has an inference forward only); "
+                         "train3d trains the 3D ScaleNet")
     return _train(_DIM3, mconf, tconf, (D, H, W), device, out, resume, log)

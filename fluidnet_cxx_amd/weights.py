@@ -45,6 +45,13 @@ def banknet_layers():
 
 
 _BANKNET_STREAM0 = 1000      # hash_uniform streams 1000 .. 1011: ScaleNet's are 0 .. 33
+_BANKNET3D_STREAM0 = 1100    # the Conv3d bank net: 1100 .. 1111
+
+
+def banknet3d_layers():
+    """Layer table of the Conv3d counterpart of the bank net (mconf['model'] = 'FluidNet3D'): banknet_layers() with every module
+    replaced by its 3D sibling -- the same names, channels and kernel extents, 5-D weights, 15153 floats."""
+    return banknet_layers()
 
 
 def _splitmix64(x):
@@ -88,4 +95,16 @@ def make_banknet_weights(seed=0, gain=1.0):
         w[L["name"] + ".weight"] = (hash_uniform(L["cout"] * fan_in, _BANKNET_STREAM0 + 2 * li, seed) * np.float32(bound)).reshape(
             (L["cout"], L["cin"], L["k"], L["k"]))
         w[L["name"] + ".bias"] = hash_uniform(L["cout"], _BANKNET_STREAM0 + 2 * li + 1, seed) * np.float32(bound)
+    return w
+
+
+def make_banknet3d_weights(seed=0, gain=1.0):
+    """name -> np.float32 array for the twelve parameter tensors of the Conv3d bank net (15153 floats), torch's default bound."""
+    w = {}
+    for li, L in enumerate(banknet3d_layers()):
+        fan_in = L["cin"] * L["k"] ** 3
+        bound = gain / np.sqrt(fan_in)
+        w[L["name"] + ".weight"] = (hash_uniform(L["cout"] * fan_in, _BANKNET3D_STREAM0 + 2 * li, seed) * np.float32(bound)).reshape(
+            (L["cout"], L["cin"], L["k"], L["k"], L["k"]))
+        w[L["name"] + ".bias"] = hash_uniform(L["cout"], _BANKNET3D_STREAM0 + 2 * li + 1, seed) * np.float32(bound)
     return w

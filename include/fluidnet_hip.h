@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define FNX_ABI_VERSION 31
+#define FNX_ABI_VERSION 32
 
 enum {
   FNX_OK = 0,
@@ -717,6 +717,38 @@ int fnx_banknet_forward(const FnxGrid* g, const void* packed, const float* x, fl
  * ScaleNet image only. */
 int fnx_fluidnet_bank_forward(const FnxGrid* g, const void* packed, const float* input, float normalize_threshold, float* p_out,
                               float* U_out, int precision_mode, void* ws, size_t ws_bytes, void* stream);
+
+/* The Conv3d counterpart of the bank net (ABI 32): mconf['model'] = 'FluidNet3D', this project's own definition (the reference's net is 2D
+ * only) -- every module of the net above replaced by its 3D sibling: Conv3d 3x3x3 with zero padding 1 at each level's own border (z
+ * included), avgpool3d by 2 and 4, nearest upsampling in z, y and x, the same order of additions, the 1x1x1 tail with conv2 applied twice.
+ * weights_blob: fnx_banknet3d_weight_floats() = 15153 floats, DEVICE pointer, the six layers in the order above, for each the torch-layout
+ * weight (Cout,Cin,kd,kh,kw) then bias.  fnx_banknet3d_pack repacks it into `packed` (fnx_banknet3d_packed_bytes()).
+ * Every entry point refuses, before it touches the device and each with its own fnx_last_error text that starts with the function's
+ * name: null arguments; a grid that is not 3D (is3D == 0 or D < 4: "3D only"); an unknown precision mode; the bf16 modes ("fp32 arithmetic
+ * only"; every fp32 mode runs the one exact-fp32 kernel family); D, H or W that is no positive multiple of 4 (the axis and its value are
+ * named); a short workspace (FNX_EWORKSPACE).  'FluidNet' with a 3D grid stays refused by the 2D entry points above.
+ * Six launches (conv1 with both poolings; block.0 and block.2 on the quarter and the half level; block.0 at full resolution; block.2 at
+ * full resolution with the sum of the levels and the tail), no atomics, no host synchronisation (capturable); a sample's result depends
+ * neither on the rest of the batch nor on how the launch plan splits z.
+ * Workspace: fnx_banknet3d_ws_bytes(g, 0) for the net alone -- relu(conv1) and block.0's output at full resolution and three 16-channel
+ * tensors at each coarser level, 64 + 64 + 3 * 8 + 3 * 1 = 155 bytes per full-resolution cell -- and fnx_banknet3d_ws_bytes(g, 1) for
+ * the whole forward (0 for a grid without a workspace size).
+ * fnx_banknet3d_launch_plan: how the 16 -> 16 convolution kernel is launched at level 1, 2 or 4 of the grid, a function of (B, D, H, W)
+ * alone: plan = {x tiles, y tiles, z chunks, planes per chunk, tile height, tile width}; tile (i, j) owns rows [i * height, ..) and
+ * columns [j * width, ..), chunk c the planes [c * planes, min(d, (c + 1) * planes)) of the level. */
+size_t fnx_banknet3d_weight_floats(void);
+size_t fnx_banknet3d_packed_bytes(void);
+int fnx_banknet3d_pack(const float* weights_blob, void* packed, void* stream);
+size_t fnx_banknet3d_ws_bytes(const FnxGrid* g, int whole_forward);
+int fnx_banknet3d_launch_plan(const FnxGrid* g, int level, int plan[6]);
+/* x: (B,2,D,H,W) [div/s, occupancy] -> p (B,1,D,H,W) */
+int fnx_banknet3d_forward(const FnxGrid* g, const void* packed, const float* x, float* p, int precision_mode, void* ws, size_t ws_bytes,
+                          void* stream);
+/* fnx_fluidnet_forward's contract with this net in the middle: input (B,6,D,H,W) = [p, U, flags, density] -> p_out (B,1,D,H,W),
+ * U_out (B,3,D,H,W); the launches around the net are fnx_fluidnet_bank_forward's on three velocity components.  fnx_simulate_step,
+ * fnx_slab_step and FnxState.net take the ScaleNet image only. */
+int fnx_fluidnet_bank3d_forward(const FnxGrid* g, const void* packed, const float* input, float normalize_threshold, float* p_out,
+                                float* U_out, int precision_mode, void* ws, size_t ws_bytes, void* stream);
 
 /* Training of the 2D net (ABI 21): gradients of a scalar loss of p (or of FluidNet.forward's (p, U)) with respect to the 34 parameter
  * tensors, fp32 arithmetic only.  Every entry point checks, before it touches the device: a 2D grid (is3D = 0, D = 1) and a precision mode
