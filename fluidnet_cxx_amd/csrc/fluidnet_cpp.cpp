@@ -566,119 +566,72 @@ Tensor multiscale_forward(Tensor packed, Tensor x, const std::string& precision_
   return p;
 }
 
-std::vector<Tensor> fluidnet_forward(Tensor packed, Tensor input, double normalize_threshold, const std::string& precision_mode) {
-  check_field(input, "input");
-  const bool is3D = input.size(1) == 6;
-  TORCH_CHECK(input.size(1) == 5 || input.size(1) == 6, "input must have 5 (2D) or 6 (3D) channels [p, U, flags, density]");
-  FnxGrid g{}; g.B = (int)input.size(0); g.D = (int)input.size(2); g.H = (int)input.size(3); g.W = (int)input.size(4);
-  g.is3D = is3D; g.ref_quirks = 0; g.z_offset = 0; g.D_global = 0;
-  c10::hip::HIPGuard guard(input.get_device());
-  Tensor p = at::empty({g.B, 1, g.D, g.H, g.W}, input.options());
-  Tensor U = at::empty({g.B, is3D ? 3 : 2, g.D, g.H, g.W}, input.options());
-  const size_t bytes = fnx_workspace_bytes(&g, FNX_OP_FLUIDNET);
-  Tensor ws = at::empty({(int64_t)bytes}, input.options().dtype(at::kByte));
-  check_status(fnx_fluidnet_forward(&g, packed.data_ptr(), input.data_ptr<float>(), (float)normalize_threshold,
-                                    p.data_ptr<float>(), U.data_ptr<float>(), precision_of(precision_mode), ws.data_ptr(), bytes,
-                                    cur_stream(input)));
-  return {p, U};
-}
+// ---- the 16-channel bank nets: mconf['model'] = 'FluidNet' (fnx_banknet.hip, 2D) and 'FluidNet3D' (fnx_banknet3d.hip), inference ----
+// Every operation is one body that takes the net's C entry points; the module registers it under its 2D and its 3D name.
+// A grid the C ABI refuses (the other dimension, a size that is no multiple of 4, a bf16 mode) gets a token workspace, so that the C
+// ABI's text is what is raised.
+struct BankApi {
+  const char* pack_name;
+  size_t (*weight_floats)(void);
+  size_t (*packed_bytes)(void);
+  int (*pack)(const float*, void*, void*);
+  size_t (*ws_bytes)(const FnxGrid*, int);
+  int (*forward)(const FnxGrid*, const void*, const float*, float*, int, void*, size_t, void*);
+  int (*whole_forward)(const FnxGrid*, const void*, const float*, float, float*, float*, int, void*, size_t, void*);
+};
+static const BankApi BANK2D = {"banknet_pack", fnx_banknet_weight_floats, fnx_banknet_packed_bytes, fnx_banknet_pack, fnx_banknet_ws_bytes,
+                               fnx_banknet_forward, fnx_fluidnet_bank_forward};
+static const BankApi BANK3D = {"banknet3d_pack", fnx_banknet3d_weight_floats, fnx_banknet3d_packed_bytes, fnx_banknet3d_pack,
+                               fnx_banknet3d_ws_bytes, fnx_banknet3d_forward, fnx_fluidnet_bank3d_forward};
 
-// ---- the 16-channel bank net, mconf['model'] = 'FluidNet' (fnx_banknet.hip): 2D inference ------------------------------------------
-// A grid the C ABI refuses (3D, H or W no multiple of 4, a bf16 mode) gets a token workspace, so that the C ABI's text is what is raised.
-Tensor banknet_pack(Tensor blob) {
+static Tensor bank_pack(const BankApi* net, Tensor blob) {
   TORCH_CHECK(blob.is_cuda() && blob.scalar_type() == at::kFloat && blob.is_contiguous(), "weights blob must be a contiguous float32 GPU tensor");
-  TORCH_CHECK((size_t)blob.numel() == fnx_banknet_weight_floats(), "weights blob has ", blob.numel(), " floats, expected ",
-              fnx_banknet_weight_floats());
+  TORCH_CHECK((size_t)blob.numel() == net->weight_floats(), "weights blob has ", blob.numel(), " floats, expected ", net->weight_floats());
   c10::hip::HIPGuard guard(blob.get_device());
-  Tensor packed = at::zeros({(int64_t)fnx_banknet_packed_bytes()}, blob.options().dtype(at::kByte));
-  check_status(fnx_banknet_pack(blob.data_ptr<float>(), packed.data_ptr(), cur_stream(blob)));
+  Tensor packed = at::zeros({(int64_t)net->packed_bytes()}, blob.options().dtype(at::kByte));
+  check_status(net->pack(blob.data_ptr<float>(), packed.data_ptr(), cur_stream(blob)));
   return packed;
 }
 
-static void check_banknet_image(const Tensor& packed) {
-  TORCH_CHECK(packed.is_cuda() && packed.is_contiguous() && (size_t)packed.nbytes() == fnx_banknet_packed_bytes(),
-              "packed must be the ", fnx_banknet_packed_bytes(), "-byte image from banknet_pack (got ", packed.nbytes(), " bytes)");
+static void check_bank_image(const BankApi* net, const Tensor& packed) {
+  TORCH_CHECK(packed.is_cuda() && packed.is_contiguous() && (size_t)packed.nbytes() == net->packed_bytes(),
+              "packed must be the ", net->packed_bytes(), "-byte image from ", net->pack_name, " (got ", packed.nbytes(), " bytes)");
 }
+static void check_banknet_image(const Tensor& packed) { check_bank_image(&BANK2D, packed); }
 
-Tensor banknet_forward(Tensor packed, Tensor x, const std::string& precision_mode) {
+static Tensor bank_forward(const BankApi* net, Tensor packed, Tensor x, const std::string& precision_mode) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.is_contiguous(), "x must be a contiguous float32 GPU tensor");
   TORCH_CHECK((x.dim() == 4 || x.dim() == 5) && x.size(1) == 2, "x must be (B,2,H,W) or (B,2,D,H,W)");
-  check_banknet_image(packed);
+  check_bank_image(net, packed);
   FnxGrid g{}; g.B = (int)x.size(0); g.D = x.dim() == 5 ? (int)x.size(2) : 1; g.H = (int)x.size(x.dim() - 2); g.W = (int)x.size(x.dim() - 1);
   g.is3D = g.D > 1;
   c10::hip::HIPGuard guard(x.get_device());
   std::vector<int64_t> osz = x.sizes().vec(); osz[1] = 1;
   Tensor p = at::empty(osz, x.options());
-  const size_t bytes = std::max<size_t>(fnx_banknet_ws_bytes(&g, 0), 256);
+  const size_t bytes = std::max<size_t>(net->ws_bytes(&g, 0), 256);
   Tensor ws = at::empty({(int64_t)bytes}, x.options().dtype(at::kByte));
-  check_status(fnx_banknet_forward(&g, packed.data_ptr(), x.data_ptr<float>(), p.data_ptr<float>(), precision_of(precision_mode),
-                                   ws.data_ptr(), bytes, cur_stream(x)));
+  check_status(net->forward(&g, packed.data_ptr(), x.data_ptr<float>(), p.data_ptr<float>(), precision_of(precision_mode), ws.data_ptr(), bytes,
+                           cur_stream(x)));
   return p;
 }
 
-std::vector<Tensor> fluidnet_bank_forward(Tensor packed, Tensor input, double normalize_threshold, const std::string& precision_mode) {
+// FluidNet.forward of any model.  net == nullptr: the ScaleNet, whose image has no size of its own to check
+static std::vector<Tensor> whole_forward(const BankApi* net, Tensor packed, Tensor input, double normalize_threshold,
+                                         const std::string& precision_mode) {
   check_field(input, "input");
   TORCH_CHECK(input.size(1) == 5 || input.size(1) == 6, "input must have 5 (2D) or 6 (3D) channels [p, U, flags, density]");
-  check_banknet_image(packed);
+  if (net) check_bank_image(net, packed);
   const bool is3D = input.size(1) == 6;
   FnxGrid g{}; g.B = (int)input.size(0); g.D = (int)input.size(2); g.H = (int)input.size(3); g.W = (int)input.size(4);
   g.is3D = is3D;
   c10::hip::HIPGuard guard(input.get_device());
   Tensor p = at::empty({g.B, 1, g.D, g.H, g.W}, input.options());
   Tensor U = at::empty({g.B, is3D ? 3 : 2, g.D, g.H, g.W}, input.options());
-  const size_t bytes = std::max<size_t>(fnx_banknet_ws_bytes(&g, 1), 256);
+  const size_t bytes = net ? std::max<size_t>(net->ws_bytes(&g, 1), 256) : fnx_workspace_bytes(&g, FNX_OP_FLUIDNET);
   Tensor ws = at::empty({(int64_t)bytes}, input.options().dtype(at::kByte));
-  check_status(fnx_fluidnet_bank_forward(&g, packed.data_ptr(), input.data_ptr<float>(), (float)normalize_threshold, p.data_ptr<float>(),
-                                         U.data_ptr<float>(), precision_of(precision_mode), ws.data_ptr(), bytes, cur_stream(input)));
-  return {p, U};
-}
-
-// ---- the Conv3d bank net, mconf['model'] = 'FluidNet3D' (fnx_banknet3d.hip): 3D inference; the bodies above with the 3D entry points ----
-Tensor banknet3d_pack(Tensor blob) {
-  TORCH_CHECK(blob.is_cuda() && blob.scalar_type() == at::kFloat && blob.is_contiguous(), "weights blob must be a contiguous float32 GPU tensor");
-  TORCH_CHECK((size_t)blob.numel() == fnx_banknet3d_weight_floats(), "weights blob has ", blob.numel(), " floats, expected ",
-              fnx_banknet3d_weight_floats());
-  c10::hip::HIPGuard guard(blob.get_device());
-  Tensor packed = at::zeros({(int64_t)fnx_banknet3d_packed_bytes()}, blob.options().dtype(at::kByte));
-  check_status(fnx_banknet3d_pack(blob.data_ptr<float>(), packed.data_ptr(), cur_stream(blob)));
-  return packed;
-}
-
-static void check_banknet3d_image(const Tensor& packed) {
-  TORCH_CHECK(packed.is_cuda() && packed.is_contiguous() && (size_t)packed.nbytes() == fnx_banknet3d_packed_bytes(),
-              "packed must be the ", fnx_banknet3d_packed_bytes(), "-byte image from banknet3d_pack (got ", packed.nbytes(), " bytes)");
-}
-
-Tensor banknet3d_forward(Tensor packed, Tensor x, const std::string& precision_mode) {
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.is_contiguous(), "x must be a contiguous float32 GPU tensor");
-  TORCH_CHECK((x.dim() == 4 || x.dim() == 5) && x.size(1) == 2, "x must be (B,2,H,W) or (B,2,D,H,W)");
-  check_banknet3d_image(packed);
-  FnxGrid g{}; g.B = (int)x.size(0); g.D = x.dim() == 5 ? (int)x.size(2) : 1; g.H = (int)x.size(x.dim() - 2); g.W = (int)x.size(x.dim() - 1);
-  g.is3D = x.dim() == 5 && g.D > 1;
-  c10::hip::HIPGuard guard(x.get_device());
-  std::vector<int64_t> osz = x.sizes().vec(); osz[1] = 1;
-  Tensor p = at::empty(osz, x.options());
-  const size_t bytes = std::max<size_t>(fnx_banknet3d_ws_bytes(&g, 0), 256);
-  Tensor ws = at::empty({(int64_t)bytes}, x.options().dtype(at::kByte));
-  check_status(fnx_banknet3d_forward(&g, packed.data_ptr(), x.data_ptr<float>(), p.data_ptr<float>(), precision_of(precision_mode),
-                                     ws.data_ptr(), bytes, cur_stream(x)));
-  return p;
-}
-
-std::vector<Tensor> fluidnet_bank3d_forward(Tensor packed, Tensor input, double normalize_threshold, const std::string& precision_mode) {
-  check_field(input, "input");
-  TORCH_CHECK(input.size(1) == 5 || input.size(1) == 6, "input must have 5 (2D) or 6 (3D) channels [p, U, flags, density]");
-  check_banknet3d_image(packed);
-  const bool is3D = input.size(1) == 6;
-  FnxGrid g{}; g.B = (int)input.size(0); g.D = (int)input.size(2); g.H = (int)input.size(3); g.W = (int)input.size(4);
-  g.is3D = is3D;
-  c10::hip::HIPGuard guard(input.get_device());
-  Tensor p = at::empty({g.B, 1, g.D, g.H, g.W}, input.options());
-  Tensor U = at::empty({g.B, is3D ? 3 : 2, g.D, g.H, g.W}, input.options());
-  const size_t bytes = std::max<size_t>(fnx_banknet3d_ws_bytes(&g, 1), 256);
-  Tensor ws = at::empty({(int64_t)bytes}, input.options().dtype(at::kByte));
-  check_status(fnx_fluidnet_bank3d_forward(&g, packed.data_ptr(), input.data_ptr<float>(), (float)normalize_threshold, p.data_ptr<float>(),
-                                           U.data_ptr<float>(), precision_of(precision_mode), ws.data_ptr(), bytes, cur_stream(input)));
+  check_status((net ? net->whole_forward : fnx_fluidnet_forward)(&g, packed.data_ptr(), input.data_ptr<float>(), (float)normalize_threshold,
+                                                                 p.data_ptr<float>(), U.data_ptr<float>(), precision_of(precision_mode),
+                                                                 ws.data_ptr(), bytes, cur_stream(input)));
   return {p, U};
 }
 
@@ -1325,10 +1278,11 @@ int64_t step_workspace_bytes(int B, int D, int H, int W, bool is3D) {
 
 }  // namespace
 
-// a training operation's one body with its dimension bound: what the module registers under the operation's 2D and 3D name
-template <class R, class... A>
-static auto in_dim(bool is3d, R (*body)(bool, A...)) {
-  return [=](A... a) { return body(is3d, std::forward<A>(a)...); };
+// an operation's one body with its dimension (training) or its net's entry points (the bank nets) bound: what the module registers under
+// the operation's 2D and 3D name
+template <class T, class R, class... A>
+static auto in_dim(T which, R (*body)(T, A...)) {
+  return [=](A... a) { return body(which, std::forward<A>(a)...); };
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1407,15 +1361,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("scalenet_pack", &scalenet_pack, NoGil());
   m.def("multiscale_forward", &multiscale_forward, py::arg("packed"), py::arg("x"), py::arg("precision_mode") = "fp32",
         py::arg("trim") = std::vector<int64_t>(), NoGil());
-  m.def("fluidnet_forward", &fluidnet_forward, py::arg("packed"), py::arg("input"), py::arg("normalize_threshold"),
+  m.def("fluidnet_forward", in_dim((const BankApi*)nullptr, &whole_forward), py::arg("packed"), py::arg("input"),
+        py::arg("normalize_threshold"), py::arg("precision_mode") = "fp32", NoGil());
+  m.def("banknet_pack", in_dim(&BANK2D, &bank_pack), py::arg("blob"), NoGil());
+  m.def("banknet_forward", in_dim(&BANK2D, &bank_forward), py::arg("packed"), py::arg("x"), py::arg("precision_mode") = "fp32", NoGil());
+  m.def("fluidnet_bank_forward", in_dim(&BANK2D, &whole_forward), py::arg("packed"), py::arg("input"), py::arg("normalize_threshold"),
         py::arg("precision_mode") = "fp32", NoGil());
-  m.def("banknet_pack", &banknet_pack, py::arg("blob"), NoGil());
-  m.def("banknet_forward", &banknet_forward, py::arg("packed"), py::arg("x"), py::arg("precision_mode") = "fp32", NoGil());
-  m.def("fluidnet_bank_forward", &fluidnet_bank_forward, py::arg("packed"), py::arg("input"), py::arg("normalize_threshold"),
-        py::arg("precision_mode") = "fp32", NoGil());
-  m.def("banknet3d_pack", &banknet3d_pack, py::arg("blob"), NoGil());
-  m.def("banknet3d_forward", &banknet3d_forward, py::arg("packed"), py::arg("x"), py::arg("precision_mode") = "fp32", NoGil());
-  m.def("fluidnet_bank3d_forward", &fluidnet_bank3d_forward, py::arg("packed"), py::arg("input"), py::arg("normalize_threshold"),
+  m.def("banknet3d_pack", in_dim(&BANK3D, &bank_pack), py::arg("blob"), NoGil());
+  m.def("banknet3d_forward", in_dim(&BANK3D, &bank_forward), py::arg("packed"), py::arg("x"), py::arg("precision_mode") = "fp32", NoGil());
+  m.def("fluidnet_bank3d_forward", in_dim(&BANK3D, &whole_forward), py::arg("packed"), py::arg("input"), py::arg("normalize_threshold"),
         py::arg("precision_mode") = "fp32", NoGil());
   m.def("banknet_pack_t", &banknet_pack_t, py::arg("blob"), NoGil());
   m.def("banknet_tape_layout", &banknet_tape_layout, py::arg("B"), py::arg("H"), py::arg("W"));

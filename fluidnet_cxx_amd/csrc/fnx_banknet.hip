@@ -39,25 +39,9 @@ __global__ void banknet_pack_kernel(const float* __restrict__ blob, float* __res
     v = blob[i];                                              // conv1 and its bias
   } else if (i < PK_W2) {
     const bool second = i >= PK_WB2;
-    const int j = i - (second ? PK_WB2 : PK_WB0);
-    const int src = second ? BLOB_WB2 : BLOB_WB0;
-    if (j < 2304) {
-      const int lane = j & 63, kc = (j >> 6) & 3, tap = j >> 8;
-      v = blob[src + ((lane & 15) * 16 + 4 * kc + (lane >> 4)) * 9 + tap];
-    } else {
-      v = blob[src + j];                                      // the bias follows the weight in both
-    }
+    v = bank_pack_conv16(blob, second ? BLOB_WB2 : BLOB_WB0, 9, i - (second ? PK_WB2 : PK_WB0));
   } else {
-    const int layer = (i - PK_W2) / 272, j = (i - PK_W2) % 272;
-    const int cout_n = layer == 0 ? 16 : (layer == 1 ? 8 : 1), cin_n = layer == 2 ? 8 : 16;
-    const int wsrc = layer == 0 ? BLOB_W2 : (layer == 1 ? BLOB_W3 : BLOB_WO), bsrc = layer == 0 ? BLOB_B2 : (layer == 1 ? BLOB_B3 : BLOB_BO);
-    if (j < 256) {
-      const int lane = j & 63, r = j >> 6;
-      const int cout = lane & 15, cin = 4 * (lane >> 4) + r;
-      if (cout < cout_n && cin < cin_n) v = blob[wsrc + cout * cin_n + cin];
-    } else if (j - 256 < cout_n) {
-      v = blob[bsrc + j - 256];
-    }
+    v = bank_pack_tail(blob, BLOB_W2, i - PK_W2);
   }
   pk[i] = v;
 }
@@ -79,23 +63,9 @@ void banknet_forward(int B, int H, int W, const float* pk, const float* x, float
   banknet_level_kernel<1, TILE_H, TILE_W1><<<grid(1, TILE_W1), 256, 0, s>>>(pk, x, H, W, nullptr, w.l2, w.l4, p);
 }
 
-// The scratch of the whole forward: the flags copy, the divergence, the net's input, scale_std's partial sums, the per-sample scales, the
-// net's own workspace; each rounded up to 256 bytes.
-struct BankFluidnetWs { float* flags; float* div; float* x; double* partial; float* scale; void* net; size_t bytes; };
-BankFluidnetWs bank_fluidnet_ws_layout(int B, int H, int W, void* base) {
-  const size_t full = (size_t)B * H * W;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { void* r = base ? (char*)base + off : nullptr; off += al256(bytes); return r; };
-  BankFluidnetWs w{};
-  w.flags = (float*)take(full * 4);
-  w.div = (float*)take(full * 4);
-  w.x = (float*)take(full * 2 * 4);
-  w.partial = (double*)take(scale_std_scratch_bytes(B));
-  w.scale = (float*)take(sizeof(float) * B);
-  w.net = take(banknet_ws_layout(B, H, W, nullptr).bytes);
-  w.bytes = off;
-  return w;
-}
+// the workspace of the net alone and of the whole forward (the flags copy, fnx_cnn.h's FluidnetWs with the net's at its end)
+size_t bank_net_ws(const FnxGrid* g) { return banknet_ws_layout(g->B, g->H, g->W, nullptr).bytes; }
+size_t bank_whole_ws(const FnxGrid* g) { return fluidnet_whole_ws_bytes(g->B, (size_t)g->H * g->W, bank_net_ws(g)); }
 
 }  // namespace
 }  // namespace fnx
@@ -113,33 +83,28 @@ int fnx_banknet_pack(const float* weights_blob, void* packed, void* stream) {
 
 size_t fnx_banknet_ws_bytes(const FnxGrid* g, int whole_forward) {
   if (!g || g->B < 1 || g->H < 4 || g->W < 4) return 0;
-  return whole_forward ? fnx::bank_fluidnet_ws_layout(g->B, g->H, g->W, nullptr).bytes : fnx::banknet_ws_layout(g->B, g->H, g->W, nullptr).bytes;
+  return whole_forward ? fnx::bank_whole_ws(g) : fnx::bank_net_ws(g);
 }
 
 int fnx_banknet_forward(const FnxGrid* g, const void* packed, const float* x, float* p, int precision_mode, void* ws, size_t ws_bytes,
                         void* stream) {
-  if (int rc = fnx::check_bank_call(__func__, g, packed && x && p && ws, precision_mode,
-                                      [](int B, int H, int W) { return fnx::banknet_ws_layout(B, H, W, nullptr).bytes; }, ws_bytes)) return rc;
+  if (int rc = fnx::check_bank_call(__func__, 2, g, packed && x && p && ws, precision_mode, fnx::bank_net_ws, ws_bytes)) return rc;
   fnx::banknet_forward(g->B, g->H, g->W, (const float*)packed, x, p, ws, (hipStream_t)stream);
   return fnx::bank_status();
 }
 
+// FluidNet.forward (lib/model.py:104-226) around the net, as fnx_fluidnet_forward runs it around the ScaleNet
 int fnx_fluidnet_bank_forward(const FnxGrid* g, const void* packed, const float* input, float thr, float* p_out, float* U_out,
                               int precision_mode, void* ws, size_t ws_bytes, void* stream) {
-  if (int rc = fnx::check_bank_call(__func__, g, packed && input && p_out && U_out && ws, precision_mode,
-                                      [](int B, int H, int W) { return fnx::bank_fluidnet_ws_layout(B, H, W, nullptr).bytes; }, ws_bytes)) return rc;
-  const GridDims d = make_dims(g->B, 1, g->H, g->W, g->z_offset, g->D_global);
-  hipStream_t s = (hipStream_t)stream;
-  const fnx::BankFluidnetWs w = fnx::bank_fluidnet_ws_layout(g->B, g->H, g->W, ws);
-  // FluidNet.forward around the net, with the launches of fnx_fluidnet_forward (lib/model.py:104-226)
-  fnx::launch_gather_input(d, 2, input, U_out, w.flags, s);                               // :104-119
-  if (int rc = fnx_velocity_divergence(g, U_out, w.flags, w.div, stream)) return rc;      // :125-126
-  fnx::launch_scale_std(d, 2, U_out, thr, w.partial, w.scale, s);                         // :129-144
-  fnx::launch_pack_input(d, 2, w.div, w.flags, w.scale, U_out, w.x, s);                   // :146-168
-  fnx::banknet_forward(g->B, g->H, g->W, (const float*)packed, w.x, p_out, w.net, s);     // :179-209
-  if (int rc = fnx_velocity_update(g, p_out, U_out, w.flags, stream)) return rc;          // :213-218
-  fnx::launch_unscale(d, 2, w.scale, p_out, U_out, s);                                    // :221-223
-  if (int rc = fnx_set_wall_bcs(g, U_out, w.flags, stream)) return rc;                    // :226
+  if (int rc = fnx::check_bank_call(__func__, 2, g, packed && input && p_out && U_out && ws, precision_mode, fnx::bank_whole_ws, ws_bytes))
+    return rc;
+  const size_t cells = (size_t)g->H * g->W;
+  float* flags = (float*)ws;
+  const fnx::FluidnetWs w = fnx::fluidnet_ws_layout(g->B, cells, fnx::bank_net_ws(g), (char*)ws + fnx::fluidnet_flags_bytes(g->B, cells));
+  fnx::fluidnet_split(g, input, U_out, flags, stream);
+  if (int rc = fnx::fluidnet_pre(g, thr, U_out, flags, w.scale, w, stream)) return rc;
+  fnx::banknet_forward(g->B, g->H, g->W, (const float*)packed, w.x, p_out, w.net, (hipStream_t)stream);     // :179-209
+  if (int rc = fnx::fluidnet_post(g, p_out, U_out, flags, w.scale, stream)) return rc;
   return fnx::bank_status();
 }
 

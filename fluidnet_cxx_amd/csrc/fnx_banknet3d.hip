@@ -31,8 +31,9 @@ namespace fnx {
 namespace {
 
 // the blob: conv1, convBank.block.0, convBank.block.2, conv2, conv3, convOut; each weight (Cout, Cin, 3|1, 3|1, 3|1) then bias
-constexpr int B3_W1 = 0, B3_B1 = 864, B3_WB0 = 880, B3_WB2 = 7808, B3_W2 = 14736, B3_B2 = 14992,
-              B3_W3 = 15008, B3_B3 = 15136, B3_WO = 15144, B3_BO = 15152, B3_FLOATS = 15153;
+// (the 1x1x1 layers behind conv2's weight as in the 2D blob: fnx_banknet_tile.h, bank_pack_tail)
+constexpr int B3_W1 = 0, B3_B1 = 864, B3_WB0 = 880, B3_WB2 = 7808, B3_W2 = 14736, B3_FLOATS = B3_W2 + BLOB_FLOATS - BLOB_W2;
+static_assert(B3_FLOATS == 15153, "the 3D blob");
 // the packed image (floats)
 constexpr int P3_W1 = 0;             // [cin 2][tap 27][cout 16]: the 16 weights of one input value are 64 consecutive bytes
 constexpr int P3_B1 = 864;           // 16
@@ -54,25 +55,9 @@ __global__ void bank3d_pack_kernel(const float* __restrict__ blob, float* __rest
     v = blob[B3_B1 + i - P3_B1];
   } else if (i < P3_W2) {
     const bool second = i >= P3_WB2;
-    const int j = i - (second ? P3_WB2 : P3_WB0);
-    const int src = second ? B3_WB2 : B3_WB0;
-    if (j < 6912) {
-      const int lane = j & 63, kc = (j >> 6) & 3, tap = j >> 8;
-      v = blob[src + ((lane & 15) * 16 + 4 * kc + (lane >> 4)) * 27 + tap];
-    } else {
-      v = blob[src + j];                                      // the bias follows the weight in both
-    }
+    v = bank_pack_conv16(blob, second ? B3_WB2 : B3_WB0, 27, i - (second ? P3_WB2 : P3_WB0));
   } else {
-    const int layer = (i - P3_W2) / 272, j = (i - P3_W2) % 272;
-    const int cout_n = layer == 0 ? 16 : (layer == 1 ? 8 : 1), cin_n = layer == 2 ? 8 : 16;
-    const int wsrc = layer == 0 ? B3_W2 : (layer == 1 ? B3_W3 : B3_WO), bsrc = layer == 0 ? B3_B2 : (layer == 1 ? B3_B3 : B3_BO);
-    if (j < 256) {
-      const int lane = j & 63, r = j >> 6;
-      const int cout = lane & 15, cin = 4 * (lane >> 4) + r;
-      if (cout < cout_n && cin < cin_n) v = blob[wsrc + cout * cin_n + cin];
-    } else if (j - 256 < cout_n) {
-      v = blob[bsrc + j - 256];
-    }
+    v = bank_pack_tail(blob, B3_W2, i - P3_W2);
   }
   pk[i] = v;
 }
@@ -384,49 +369,9 @@ void bank3d_forward(int B, int D, int H, int W, const float* pk, const float* x,
       pk + P3_WB2, pk + P3_BB2, pk + P3_W2, ws.h, D, H, W, pl.tiles_y, pl.chunk, nullptr, ws.b2, ws.b4, p);
 }
 
-// The scratch of the whole forward: the flags copy, the divergence, the net's input, scale_std's partial sums, the per-sample scales, the
-// net's own workspace; each rounded up to 256 bytes.
-struct Bank3dFluidnetWs { float* flags; float* div; float* x; double* partial; float* scale; void* net; size_t bytes; };
-Bank3dFluidnetWs bank3d_fluidnet_ws_layout(int B, int D, int H, int W, void* base) {
-  const size_t full = (size_t)B * D * H * W;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { void* r = base ? (char*)base + off : nullptr; off += al256(bytes); return r; };
-  Bank3dFluidnetWs w{};
-  w.flags = (float*)take(full * 4);
-  w.div = (float*)take(full * 4);
-  w.x = (float*)take(full * 2 * 4);
-  w.partial = (double*)take(scale_std_scratch_bytes(B));
-  w.scale = (float*)take(sizeof(float) * B);
-  w.net = take(bank3d_ws_layout(B, D, H, W, nullptr).bytes);
-  w.bytes = off;
-  return w;
-}
-
-// The checks the entry points share, before any device call, each refusal with its own text.
-int check_bank3d_call(const char* fn, const FnxGrid* g, bool args, int precision_mode, bool whole, size_t ws_bytes) {
-  if (!g || !args) return set_error(FNX_EINVAL, "%s: null argument", fn);
-  if (!g->is3D || g->D < 4)
-    return set_error(FNX_EINVAL, "%s: the Conv3d bank net ('FluidNet3D' model) is 3D only (is3D = %d, D = %d)", fn, g->is3D, g->D);
-  const int mode = net_mode(precision_mode);
-  if (mode < 0)
-    return set_error(FNX_EINVAL, "%s: unknown precision_mode %d (FNX_PRECISION_FP32, _FP32_DIRECT, _BF16X6, _BF16X3, _FP32_F4 or _FP32_F2)", fn,
-                     precision_mode);
-  if (mode == FNX_PRECISION_BF16X6 || mode == FNX_PRECISION_BF16X3)
-    return set_error(FNX_EINVAL, "%s: the bank net runs in fp32 arithmetic only (FNX_PRECISION_FP32, _FP32_F4, _FP32_F2 or _FP32_DIRECT), "
-                     "not in the bf16 modes (precision_mode %d)", fn, precision_mode);
-  if (g->B < 1 || g->B > 65535) return set_error(FNX_EINVAL, "%s: batch size %d is outside 1 .. 65535", fn, g->B);
-  if (g->D % 4) return set_error(FNX_EINVAL, "%s: D = %d must be a positive multiple of 4 (the three levels are added)", fn, g->D);
-  if (g->H < 4 || g->H % 4) return set_error(FNX_EINVAL, "%s: H = %d must be a positive multiple of 4 (the three levels are added)", fn, g->H);
-  if (g->W < 4 || g->W % 4) return set_error(FNX_EINVAL, "%s: W = %d must be a positive multiple of 4 (the three levels are added)", fn, g->W);
-  const size_t cells = (size_t)g->D * g->H * g->W;
-  if (cells >= ((size_t)1 << 31) || (size_t)(g->D / 4) * (g->H / 4) > 65535)      // grid y: (y tiles) x (z tiles or chunks)
-    return set_error(FNX_EINVAL, "%s: D * H * W = %zu cells per sample (D = %d, H = %d) is beyond the bank kernels' launch range", fn, cells,
-                     g->D, g->H);
-  const size_t want = whole ? bank3d_fluidnet_ws_layout(g->B, g->D, g->H, g->W, nullptr).bytes
-                            : bank3d_ws_layout(g->B, g->D, g->H, g->W, nullptr).bytes;
-  if (ws_bytes < want) return set_error(FNX_EWORKSPACE, "%s: workspace of %zu bytes is too small (%zu needed)", fn, ws_bytes, want);
-  return FNX_OK;
-}
+// the workspace of the net alone and of the whole forward (the flags copy, fnx_cnn.h's FluidnetWs with the net's at its end)
+size_t bank3d_net_ws(const FnxGrid* g) { return bank3d_ws_layout(g->B, g->D, g->H, g->W, nullptr).bytes; }
+size_t bank3d_whole_ws(const FnxGrid* g) { return fluidnet_whole_ws_bytes(g->B, (size_t)g->D * g->H * g->W, bank3d_net_ws(g)); }
 
 }  // namespace
 }  // namespace fnx
@@ -444,8 +389,7 @@ int fnx_banknet3d_pack(const float* weights_blob, void* packed, void* stream) {
 
 size_t fnx_banknet3d_ws_bytes(const FnxGrid* g, int whole_forward) {
   if (!g || g->B < 1 || g->D < 4 || g->H < 4 || g->W < 4) return 0;
-  return whole_forward ? fnx::bank3d_fluidnet_ws_layout(g->B, g->D, g->H, g->W, nullptr).bytes
-                       : fnx::bank3d_ws_layout(g->B, g->D, g->H, g->W, nullptr).bytes;
+  return whole_forward ? fnx::bank3d_whole_ws(g) : fnx::bank3d_net_ws(g);
 }
 
 int fnx_banknet3d_launch_plan(const FnxGrid* g, int level, int plan[6]) {
@@ -458,26 +402,23 @@ int fnx_banknet3d_launch_plan(const FnxGrid* g, int level, int plan[6]) {
 
 int fnx_banknet3d_forward(const FnxGrid* g, const void* packed, const float* x, float* p, int precision_mode, void* ws, size_t ws_bytes,
                           void* stream) {
-  if (int rc = fnx::check_bank3d_call(__func__, g, packed && x && p && ws, precision_mode, false, ws_bytes)) return rc;
+  if (int rc = fnx::check_bank_call(__func__, 3, g, packed && x && p && ws, precision_mode, fnx::bank3d_net_ws, ws_bytes)) return rc;
   fnx::bank3d_forward(g->B, g->D, g->H, g->W, (const float*)packed, x, p, ws, (hipStream_t)stream);
   return fnx::bank_status();
 }
 
+// FluidNet.forward around the net, as fnx_fluidnet_bank_forward, on three velocity components
 int fnx_fluidnet_bank3d_forward(const FnxGrid* g, const void* packed, const float* input, float thr, float* p_out, float* U_out,
                                 int precision_mode, void* ws, size_t ws_bytes, void* stream) {
-  if (int rc = fnx::check_bank3d_call(__func__, g, packed && input && p_out && U_out && ws, precision_mode, true, ws_bytes)) return rc;
-  const GridDims d = make_dims(g->B, g->D, g->H, g->W, g->z_offset, g->D_global);
-  hipStream_t s = (hipStream_t)stream;
-  const fnx::Bank3dFluidnetWs w = fnx::bank3d_fluidnet_ws_layout(g->B, g->D, g->H, g->W, ws);
-  // FluidNet.forward around the net, with the launches of fnx_fluidnet_bank_forward on three velocity components
-  fnx::launch_gather_input(d, 3, input, U_out, w.flags, s);
-  if (int rc = fnx_velocity_divergence(g, U_out, w.flags, w.div, stream)) return rc;
-  fnx::launch_scale_std(d, 3, U_out, thr, w.partial, w.scale, s);
-  fnx::launch_pack_input(d, 3, w.div, w.flags, w.scale, U_out, w.x, s);
-  fnx::bank3d_forward(g->B, g->D, g->H, g->W, (const float*)packed, w.x, p_out, w.net, s);
-  if (int rc = fnx_velocity_update(g, p_out, U_out, w.flags, stream)) return rc;
-  fnx::launch_unscale(d, 3, w.scale, p_out, U_out, s);
-  if (int rc = fnx_set_wall_bcs(g, U_out, w.flags, stream)) return rc;
+  if (int rc = fnx::check_bank_call(__func__, 3, g, packed && input && p_out && U_out && ws, precision_mode, fnx::bank3d_whole_ws, ws_bytes))
+    return rc;
+  const size_t cells = (size_t)g->D * g->H * g->W;
+  float* flags = (float*)ws;
+  const fnx::FluidnetWs w = fnx::fluidnet_ws_layout(g->B, cells, fnx::bank3d_net_ws(g), (char*)ws + fnx::fluidnet_flags_bytes(g->B, cells));
+  fnx::fluidnet_split(g, input, U_out, flags, stream);
+  if (int rc = fnx::fluidnet_pre(g, thr, U_out, flags, w.scale, w, stream)) return rc;
+  fnx::bank3d_forward(g->B, g->D, g->H, g->W, (const float*)packed, w.x, p_out, w.net, (hipStream_t)stream);
+  if (int rc = fnx::fluidnet_post(g, p_out, U_out, flags, w.scale, stream)) return rc;
   return fnx::bank_status();
 }
 

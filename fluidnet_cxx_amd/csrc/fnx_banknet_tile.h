@@ -1,6 +1,7 @@
-// What the two units of the 16-channel bank net share (fnx_banknet.hip: inference; fnx_banknet_train.hip: tape forward and backward):
-// the blob's and the packed image's offsets, the geometry of a level tile, the 3x3 bank convolution on v_mfma_f32_16x16x4_f32, the body
-// of a level kernel (with a compile-time switch that also writes the tape) and the checks every entry point makes before the device.
+// What the units of the 16-channel bank net share (fnx_banknet.hip: 2D inference; fnx_banknet_train.hip: 2D tape forward and backward;
+// fnx_banknet3d.hip: 3D inference).  All three: the pieces of the weight packing and the checks every entry point makes before the
+// device.  The 2D units: the blob's and the packed image's offsets, the geometry of a level tile, the 3x3 bank convolution on
+// v_mfma_f32_16x16x4_f32 and the body of a level kernel (with a compile-time switch that also writes the tape).
 // The layout of the kernels and of the MFMA operands is described at the top of fnx_banknet.hip.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -78,6 +79,38 @@ __device__ __forceinline__ void bank_conv(const float* __restrict__ wpk, const f
     epi(grp * 16 + 16 + (lane & 15), acc1);
   }
 }
+
+// What the 2D and the 3D pack kernel share.  Float j of a 16 -> 16 convolution's image, [tap][kc 4][lane 64] =
+// W[cout = lane & 15][cin = 4 kc + (lane >> 4)][tap] then the 16 biases, from the blob's (16, 16, taps) weight at w, whose bias follows it.
+__device__ __forceinline__ float bank_pack_conv16(const float* __restrict__ blob, int w, int taps, int j) {
+  float v;
+  if (j < 256 * taps) {
+    const int lane = j & 63, kc = (j >> 6) & 3, tap = j >> 8;
+    v = blob[w + ((lane & 15) * 16 + 4 * kc + (lane >> 4)) * taps + tap];
+  } else {
+    v = blob[w + j];
+  }
+  return v;
+}
+// Float j of the tail's image (3 x 272, see PK_W2) from the blob with conv2's weight at w2: the 1x1 layers have one tap in either
+// dimension, so conv2, conv3 and convOut follow it at the same distances in both blobs.
+__device__ __forceinline__ float bank_pack_tail(const float* __restrict__ blob, int w2, int j) {
+  const int layer = j / 272;                              // conv2, conv3, convOut
+  j %= 272;
+  const int cout_n = layer == 0 ? 16 : (layer == 1 ? 8 : 1), cin_n = layer == 2 ? 8 : 16;
+  const int wsrc = w2 + (layer == 0 ? 0 : (layer == 1 ? 272 : 408)), bsrc = w2 + (layer == 0 ? 256 : (layer == 1 ? 400 : 416));
+  float v = 0.f;
+  if (j < 256) {
+    const int lane = j & 63, r = j >> 6;
+    const int cout = lane & 15, cin = 4 * (lane >> 4) + r;
+    if (cout < cout_n && cin < cin_n) v = blob[wsrc + cout * cin_n + cin];
+  } else if (j - 256 < cout_n) {
+    v = blob[bsrc + j - 256];
+  }
+  return v;
+}
+static_assert(BLOB_B2 - BLOB_W2 == 256 && BLOB_W3 - BLOB_W2 == 272 && BLOB_B3 - BLOB_W2 == 400 && BLOB_WO - BLOB_W2 == 408 &&
+              BLOB_BO - BLOB_W2 == 416, "bank_pack_tail's table");
 
 // Where a taping level launch writes (contiguous (B,C,h,w) tensors of the level it runs at; see fnx_banknet_tape_layout): the pooled
 // relu(conv1) it recomputes, the output of block.0 and of block.2 after their ReLUs and, at full resolution, the sum of the three levels
@@ -268,7 +301,6 @@ __device__ __forceinline__ void bank_level_tile(const float* __restrict__ pk, co
   }
 }
 
-inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 struct BankWs { float* l2; float* l4; size_t bytes; };
 inline BankWs banknet_ws_layout(int B, int H, int W, void* base) {
   BankWs w{};
@@ -284,13 +316,21 @@ inline int bank_status() {
   return e == hipSuccess ? FNX_OK : set_error(FNX_EHIP, "HIP error in a bank-net launch: %s", hipGetErrorString(e));
 }
 
-// The checks the bank net's entry points share, before any device call, each refusal with its own text.  want(B, H, W): the workspace
-// the entry point needs for a grid that passed the checks in front of it.
-template <typename Want>
-int check_bank_call(const char* fn, const FnxGrid* g, bool args, int precision_mode, Want want_of, size_t ws_bytes) {
+// The checks the entry points of the bank nets share, before any device call, each refusal with its own text.  ndim: 2 (the 'FluidNet'
+// model) or 3 ('FluidNet3D').  want_of(g): the workspace the entry point needs for a grid that passed the checks in front of it
+// (nullptr: none).
+inline int check_bank_call(const char* fn, int ndim, const FnxGrid* g, bool args, int precision_mode, size_t (*want_of)(const FnxGrid*),
+                           size_t ws_bytes) {
   if (!g || !args) return set_error(FNX_EINVAL, "%s: null argument", fn);
-  if (g->is3D || g->D != 1)
-    return set_error(FNX_EINVAL, "%s: the bank net ('FluidNet' model) is 2D only (is3D = %d, D = %d)", fn, g->is3D, g->D);
+  // what depends on the dimension: the kind of grid, D, and the range the kernels launch on (3D: grid y is (y tiles) x (z tiles or chunks))
+  const bool is3 = ndim == 3;
+  const size_t cells = (size_t)g->D * g->H * g->W;
+  const bool kind_ok = is3 ? g->is3D && g->D >= 4 : !g->is3D && g->D == 1;
+  const bool d_ok = !is3 || g->D % 4 == 0;
+  const bool range_ok = is3 ? cells < ((size_t)1 << 31) && (size_t)(g->D / 4) * (g->H / 4) <= 65535 : cells < ((size_t)1 << 27);
+  if (!kind_ok)
+    return is3 ? set_error(FNX_EINVAL, "%s: the Conv3d bank net ('FluidNet3D' model) is 3D only (is3D = %d, D = %d)", fn, g->is3D, g->D)
+               : set_error(FNX_EINVAL, "%s: the bank net ('FluidNet' model) is 2D only (is3D = %d, D = %d)", fn, g->is3D, g->D);
   const int mode = net_mode(precision_mode);
   if (mode < 0)
     return set_error(FNX_EINVAL, "%s: unknown precision_mode %d (FNX_PRECISION_FP32, _FP32_DIRECT, _BF16X6, _BF16X3, _FP32_F4 or _FP32_F2)", fn,
@@ -299,11 +339,14 @@ int check_bank_call(const char* fn, const FnxGrid* g, bool args, int precision_m
     return set_error(FNX_EINVAL, "%s: the bank net runs in fp32 arithmetic only (FNX_PRECISION_FP32, _FP32_F4, _FP32_F2 or _FP32_DIRECT), "
                      "not in the bf16 modes (precision_mode %d)", fn, precision_mode);
   if (g->B < 1 || g->B > 65535) return set_error(FNX_EINVAL, "%s: batch size %d is outside 1 .. 65535", fn, g->B);
+  if (!d_ok) return set_error(FNX_EINVAL, "%s: D = %d must be a positive multiple of 4 (the three levels are added)", fn, g->D);
   if (g->H < 4 || g->H % 4) return set_error(FNX_EINVAL, "%s: H = %d must be a positive multiple of 4 (the three levels are added)", fn, g->H);
   if (g->W < 4 || g->W % 4) return set_error(FNX_EINVAL, "%s: W = %d must be a positive multiple of 4 (the three levels are added)", fn, g->W);
-  if ((size_t)g->H * g->W >= ((size_t)1 << 27))
-    return set_error(FNX_EINVAL, "%s: H * W = %zu cells per sample is beyond the bank kernels' range", fn, (size_t)g->H * g->W);
-  const size_t want = want_of(g->B, g->H, g->W);
+  if (!range_ok)
+    return is3 ? set_error(FNX_EINVAL, "%s: D * H * W = %zu cells per sample (D = %d, H = %d) is beyond the bank kernels' launch range", fn,
+                           cells, g->D, g->H)
+               : set_error(FNX_EINVAL, "%s: H * W = %zu cells per sample is beyond the bank kernels' range", fn, cells);
+  const size_t want = want_of ? want_of(g) : 0;
   if (ws_bytes < want) return set_error(FNX_EWORKSPACE, "%s: workspace of %zu bytes is too small (%zu needed)", fn, ws_bytes, want);
   return FNX_OK;
 }

@@ -500,11 +500,11 @@ void banknet_backward(int B, int H, int W, const float* pt, const float* x, cons
 
 // FluidNet.forward for training with the bank net in the middle: one workspace size for the forward and the backward
 size_t bank_train_ws_bytes(const FnxGrid* g) {
-  const size_t fwd = fluidnet_train_fwd_ws(g, nullptr).bytes;
+  const size_t fwd = fluidnet_ws_layout(g->B, (size_t)g->H * g->W, 0, nullptr).head;
   const size_t bwd = fluidnet_train_bwd_ws(2, g, nullptr).bytes + bank_bwd_plan(g->B, g->H, g->W, nullptr).bytes;
   return fwd > bwd ? fwd : bwd;
 }
-const auto NO_WS = [](int, int, int) { return (size_t)0; };
+size_t bank_bwd_ws_bytes(const FnxGrid* g) { return bank_bwd_plan(g->B, g->H, g->W, nullptr).bytes; }
 
 }  // namespace
 }  // namespace fnx
@@ -536,19 +536,19 @@ int fnx_banknet_pack_t(const float* weights_blob, void* packed_t, void* stream) 
 
 size_t fnx_banknet_backward_ws_bytes(const FnxGrid* g) {
   if (!g || g->is3D || g->D != 1 || g->B < 1 || g->H < 4 || g->W < 4) return 0;
-  return fnx::bank_bwd_plan(g->B, g->H, g->W, nullptr).bytes;
+  return fnx::bank_bwd_ws_bytes(g);
 }
 
 int fnx_banknet_forward_train(const FnxGrid* g, const void* packed, const float* x, float* p, float* tape, int precision_mode, void* stream) {
-  if (int rc = fnx::check_bank_call(__func__, g, packed && x && p && tape, precision_mode, fnx::NO_WS, 0)) return rc;
+  if (int rc = fnx::check_bank_call(__func__, 2, g, packed && x && p && tape, precision_mode, nullptr, 0)) return rc;
   fnx::banknet_forward_train(g->B, g->H, g->W, (const float*)packed, x, p, tape, (hipStream_t)stream);
   return fnx::bank_status();
 }
 
 int fnx_banknet_backward(const FnxGrid* g, const void* packed_t, const float* x, const float* grad_p, const float* tape, float* grad_blob,
                          int precision_mode, void* ws, size_t ws_bytes, void* stream) {
-  if (int rc = fnx::check_bank_call(__func__, g, packed_t && x && grad_p && tape && grad_blob && ws, precision_mode,
-                                    [](int B, int H, int W) { return fnx::bank_bwd_plan(B, H, W, nullptr).bytes; }, ws_bytes))
+  if (int rc = fnx::check_bank_call(__func__, 2, g, packed_t && x && grad_p && tape && grad_blob && ws, precision_mode, fnx::bank_bwd_ws_bytes,
+                                    ws_bytes))
     return rc;
   fnx::banknet_backward(g->B, g->H, g->W, (const float*)packed_t, x, grad_p, tape, grad_blob, ws, (hipStream_t)stream);
   return fnx::bank_status();
@@ -562,22 +562,23 @@ size_t fnx_fluidnet_bank_train_ws_bytes(const FnxGrid* g) {
 int fnx_fluidnet_bank_forward_train(const FnxGrid* g, const void* packed, const float* input, float normalize_threshold, float* p_out,
                                     float* U_out, float* flags_out, float* scale_out, float* tape, int precision_mode, void* ws,
                                     size_t ws_bytes, void* stream) {
-  if (int rc = fnx::check_bank_call(__func__, g, packed && input && p_out && U_out && flags_out && scale_out && tape && ws,
-                                    precision_mode, [g](int, int, int) { return fnx::bank_train_ws_bytes(g); }, ws_bytes))
+  if (int rc = fnx::check_bank_call(__func__, 2, g, packed && input && p_out && U_out && flags_out && scale_out && tape && ws,
+                                    precision_mode, fnx::bank_train_ws_bytes, ws_bytes))
     return rc;
-  fnx::FluidnetTrainFwdWs w = fnx::fluidnet_train_fwd_ws(g, ws);
+  fnx::FluidnetWs w = fnx::fluidnet_ws_layout(g->B, (size_t)g->H * g->W, 0, ws);        // (its head: the scales go to scale_out)
   w.x = tape + fnx::bank_tape_layout(g->B, g->H, g->W).e[fnx::TP_X].off;      // the backward reads the net's input again (conv1)
-  if (int rc = fnx::fluidnet_train_pre(2, g, input, normalize_threshold, U_out, flags_out, scale_out, w, stream)) return rc;
+  fnx::fluidnet_split(g, input, U_out, flags_out, stream);
+  if (int rc = fnx::fluidnet_pre(g, normalize_threshold, U_out, flags_out, scale_out, w, stream)) return rc;
   fnx::banknet_forward_train(g->B, g->H, g->W, (const float*)packed, w.x, p_out, tape, (hipStream_t)stream);
-  if (int rc = fnx::fluidnet_train_post(2, g, p_out, U_out, flags_out, scale_out, stream)) return rc;
+  if (int rc = fnx::fluidnet_post(g, p_out, U_out, flags_out, scale_out, stream)) return rc;
   return fnx::bank_status();
 }
 
 int fnx_fluidnet_bank_backward(const FnxGrid* g, const void* packed_t, const float* flags, const float* scale,
                                const float* grad_p, const float* grad_U, const float* tape, float* grad_blob, int precision_mode, void* ws,
                                size_t ws_bytes, void* stream) {
-  if (int rc = fnx::check_bank_call(__func__, g, packed_t && flags && scale && grad_p && grad_U && tape && grad_blob && ws, precision_mode,
-                                    [g](int, int, int) { return fnx::bank_train_ws_bytes(g); }, ws_bytes))
+  if (int rc = fnx::check_bank_call(__func__, 2, g, packed_t && flags && scale && grad_p && grad_U && tape && grad_blob && ws, precision_mode,
+                                    fnx::bank_train_ws_bytes, ws_bytes))
     return rc;
   const fnx::FluidnetTrainBwdWs w = fnx::fluidnet_train_bwd_ws(2, g, ws);
   if (int rc = fnx::fluidnet_train_gnet(2, g, flags, scale, grad_p, grad_U, w, stream)) return rc;

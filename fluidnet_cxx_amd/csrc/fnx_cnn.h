@@ -26,6 +26,7 @@ size_t scalenet_weight_floats(bool is3d);
 size_t scalenet_packed_bytes(bool is3d);
 void scalenet_pack(bool is3d, const float* blob, void* packed, hipStream_t s);
 
+inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 size_t multiscale_ws_bytes(const GridDims& g, bool is3d);
 size_t fluidnet_ws_bytes(const GridDims& g, bool is3d);
 
@@ -128,17 +129,26 @@ namespace fnx {
 // precision_mode (FNX_PRECISION_*) as the CNN launchers dispatch on it: FNX_PRECISION_FP32_F4 names what FNX_PRECISION_FP32 runs and
 // becomes it; -1: no such mode.  The C ABI entry points map it once; everything below them takes the mapped value.
 int net_mode(int precision_mode);
-// FluidNet.forward for training around a taped net, whichever net it is (fnx_cnn_train.hip; the ScaleNet and the bank model call these):
-// the forward's scratch (the divergence, the net's input x, scale_std's partial sums), the backward's (the wall-masked scaled grad_U, the
-// update's grad_U and grad_p, g_net, then the net's own workspace at `net`), the launches of model.py:104-168 in front of the net, those
-// of :213-226 behind it, and  g_net = s grad_p + velocity_update_backward_p(s setWallBcs(grad_U)).  nc: 2 or 3 velocity components.
-struct FluidnetTrainFwdWs { float* div; float* x; double* partial; size_t bytes; };
+// FluidNet.forward around a net, whichever net it is (the ScaleNet, the bank nets and the two trainers call these).
+// The scratch behind the flags copy, in this order, each region rounded up to 256 bytes: the divergence (the fused step keeps the net's p
+// there), the net's input, scale_std's partial sums, the per-sample scales, `net_bytes` for the net's own workspace.  cells: D * H * W.
+// base == nullptr: the sizes only.  head: the bytes in front of `scale`, all a training forward takes (its scales go to the caller).
+// A whole-forward entry point puts its contiguous (B,1,..) copy of the flags channel, fluidnet_flags_bytes, in front of it.
+struct FluidnetWs { float* div; float* x; double* partial; float* scale; void* net; size_t head, bytes; };
+FluidnetWs fluidnet_ws_layout(int B, size_t cells, size_t net_bytes, void* base);
+inline size_t fluidnet_flags_bytes(int B, size_t cells) { return al256((size_t)B * cells * 4); }
+inline size_t fluidnet_whole_ws_bytes(int B, size_t cells, size_t net_bytes) {
+  return fluidnet_flags_bytes(B, cells) + fluidnet_ws_layout(B, cells, net_bytes, nullptr).bytes;
+}
+// the channel split of model.py:104-119 (input -> U, flags), the launches of :125-168 in front of the net and those of :213-226 behind
+// it.  The velocity components, 2 or 3, follow from g->is3D.
+void fluidnet_split(const FnxGrid* g, const float* input, float* U, float* flags, void* stream);
+int fluidnet_pre(const FnxGrid* g, float thr, float* U, const float* flags, float* scale, const FluidnetWs& w, void* stream);
+int fluidnet_post(const FnxGrid* g, float* p, float* U, const float* flags, const float* scale, void* stream);
+// The backward's scratch (the wall-masked scaled grad_U, the update's grad_U and grad_p, g_net, then the net's own workspace at `net`) and
+// g_net = s grad_p + velocity_update_backward_p(s setWallBcs(grad_U)) (fnx_cnn_train.hip).  nc: 2 or 3 velocity components.
 struct FluidnetTrainBwdWs { float *gU, *gU_in, *gp, *gnet; void* net; size_t bytes; };   // bytes: in front of `net`
-FluidnetTrainFwdWs fluidnet_train_fwd_ws(const FnxGrid* g, void* base);
 FluidnetTrainBwdWs fluidnet_train_bwd_ws(int nc, const FnxGrid* g, void* base);
-int fluidnet_train_pre(int nc, const FnxGrid* g, const float* input, float normalize_threshold, float* U_out, float* flags_out,
-                       float* scale_out, const FluidnetTrainFwdWs& w, void* stream);
-int fluidnet_train_post(int nc, const FnxGrid* g, float* p_out, float* U_out, const float* flags, const float* scale, void* stream);
 int fluidnet_train_gnet(int nc, const FnxGrid* g, const float* flags, const float* scale, const float* grad_p, const float* grad_U,
                         const FluidnetTrainBwdWs& w, void* stream);
 // the net's un-normalised pressure alone (model.py:125-175, :221-222) for the hybrid projection: p_out = scale * net(div(U) / scale, occupancy);

@@ -22,7 +22,6 @@ inline int launch_status(bool is3d) {
 
 namespace {
 
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 constexpr int co_tile(int cout) { return cout >= 16 ? 16 : cout; }
 constexpr int pad_to(int v, int m) { return (v + m - 1) / m * m; }
 
@@ -1811,26 +1810,23 @@ void launch_gather_input(const GridDims& g, int nc, const float* input, float* U
   gather_input_kernel<<<bgrid(g.DHW, g.B), 256, 0, s>>>((size_t)g.DHW, nc, input, U, flags);
 }
 
-// The scratch of FluidNet.forward behind its flags copy, in this order, each region rounded up to 256 bytes: the divergence (the fused
-// step keeps the net's p there), the net's input, scale_std's partial sums, the per-sample scales, the net's own workspace.
-// base == nullptr: the size only.
-struct FluidnetWs { float* div; float* x; double* partial; float* scale; void* msws; size_t bytes; };
-static FluidnetWs fluidnet_ws_layout(const GridDims& g, bool is3d, void* base) {
-  const size_t full = (size_t)g.B * g.DHW;
+FluidnetWs fluidnet_ws_layout(int B, size_t cells, size_t net_bytes, void* base) {
+  const size_t full = (size_t)B * cells;
   size_t off = 0;
   auto take = [&](size_t bytes) { void* r = base ? (char*)base + off : nullptr; off += al256(bytes); return r; };
   FluidnetWs w{};
   w.div = (float*)take(full * 4);
   w.x = (float*)take(full * 2 * 4);
-  w.partial = (double*)take(scale_std_scratch_bytes(g.B));
-  w.scale = (float*)take(sizeof(float) * g.B);
-  w.msws = take(multiscale_ws_bytes(g, is3d));
+  w.partial = (double*)take(scale_std_scratch_bytes(B));
+  w.head = off;
+  w.scale = (float*)take(sizeof(float) * B);
+  w.net = take(net_bytes);
   w.bytes = off;
   return w;
 }
 
 size_t fluidnet_ws_bytes(const GridDims& g, bool is3d) {
-  return al256((size_t)g.B * g.DHW * 4) /*flags*/ + fluidnet_ws_layout(g, is3d, nullptr).bytes;
+  return fluidnet_whole_ws_bytes(g.B, g.DHW, multiscale_ws_bytes(g, is3d));
 }
 
 }  // namespace fnx
@@ -1847,15 +1843,33 @@ int net_mode(int precision_mode) {
 // FluidNet.forward after the channel split (model.py:120-227), U in place: U holds UDiv on entry and the
 // projected velocity on exit.  ws needs fluidnet_ws_bytes() minus the flags copy.
 namespace fnx {
+void fluidnet_split(const FnxGrid* g, const float* input, float* U, float* flags, void* stream) {
+  launch_gather_input(make_dims(g->B, g->D, g->H, g->W), g->is3D ? 3 : 2, input, U, flags, (hipStream_t)stream);   // model.py:104-119
+}
+int fluidnet_pre(const FnxGrid* g, float thr, float* U, const float* flags, float* scale, const FluidnetWs& w, void* stream) {
+  const GridDims d = make_dims(g->B, g->D, g->H, g->W);          // (the launchers below read B and DHW alone)
+  hipStream_t s = (hipStream_t)stream;
+  const int nc = g->is3D ? 3 : 2;
+  if (int rc = fnx_velocity_divergence(g, U, flags, w.div, stream)) return rc;   // model.py:125-126
+  launch_scale_std(d, nc, U, thr, w.partial, scale, s);                          // model.py:129-144
+  launch_pack_input(d, nc, w.div, flags, scale, U, w.x, s);                      // model.py:146-168
+  return FNX_OK;
+}
+int fluidnet_post(const FnxGrid* g, float* p, float* U, const float* flags, const float* scale, void* stream) {
+  if (int rc = fnx_velocity_update(g, p, U, flags, stream)) return rc;           // model.py:213-218
+  launch_unscale(make_dims(g->B, g->D, g->H, g->W), g->is3D ? 3 : 2, scale, p, U, (hipStream_t)stream);   // model.py:221-223
+  return fnx_set_wall_bcs(g, U, flags, stream);                                  // model.py:226
+}
+
 int fluidnet_core(const FnxGrid* g, const void* packed, const float* flags, float thr, int precision_mode, float* p_out, float* U,
                   void* ws, void* stream, const FnxState* bcs) {
   const GridDims d = make_dims(g->B, g->D, g->H, g->W, g->z_offset, g->D_global);
   hipStream_t s = (hipStream_t)stream;
   const int nc = g->is3D ? 3 : 2;
-  const FluidnetWs w = fluidnet_ws_layout(d, g->is3D, ws);
+  const FluidnetWs w = fluidnet_ws_layout(d.B, d.DHW, multiscale_ws_bytes(d, g->is3D), ws);
   float *div = w.div, *x = w.x, *scale = w.scale;
   double* partial = w.partial;
-  void* msws = w.msws;
+  void* msws = w.net;
   if (bcs) {
     // The fused step (fnx_simulate_step, convnet, no flags_stick): three launches around the net instead of eight, the same
     // arithmetic per value.  The divergence goes straight into the net's input, U is not rewritten before the net, and
@@ -1875,13 +1889,9 @@ int fluidnet_core(const FnxGrid* g, const void* packed, const float* flags, floa
                            p_out);                                               // model.py:213-226, simulate.py:168
     return fnx::launch_status(g->is3D);
   }
-  if (int rc = fnx_velocity_divergence(g, U, flags, div, stream)) return rc;     // model.py:125-126
-  launch_scale_std(d, nc, U, thr, partial, scale, s);                            // model.py:129-144
-  launch_pack_input(d, nc, div, flags, scale, U, x, s);                          // model.py:146-168
+  if (int rc = fluidnet_pre(g, thr, U, flags, scale, w, stream)) return rc;
   multiscale_forward(d, g->is3D, packed, x, p_out, precision_mode, msws, s);     // model.py:174-175
-  if (int rc = fnx_velocity_update(g, p_out, U, flags, stream)) return rc;       // model.py:213-218
-  launch_unscale(d, nc, scale, p_out, U, s);                                     // model.py:221-223
-  if (int rc = fnx_set_wall_bcs(g, U, flags, stream)) return rc;                 // model.py:226
+  if (int rc = fluidnet_post(g, p_out, U, flags, scale, stream)) return rc;
   return fnx::launch_status(g->is3D);
 }
 
@@ -1893,10 +1903,10 @@ int fluidnet_pressure(const FnxGrid* g, const void* packed, const float* flags, 
   const GridDims d = make_dims(g->B, g->D, g->H, g->W, g->z_offset, g->D_global);
   hipStream_t s = (hipStream_t)stream;
   const int nc = g->is3D ? 3 : 2;
-  const FluidnetWs w = fluidnet_ws_layout(d, g->is3D, ws);                      // (its divergence buffer is not used here)
+  const FluidnetWs w = fluidnet_ws_layout(d.B, d.DHW, multiscale_ws_bytes(d, g->is3D), ws);   // (its divergence buffer is not used here)
   float *x = w.x, *scale = w.scale;
   double* partial = w.partial;
-  void* msws = w.msws;
+  void* msws = w.net;
   launch_scale_std(d, nc, U, thr, partial, scale, s);                            // model.py:129-144
   launch_pack_div(d, g->is3D, U, flags, scale, x, s);                            // model.py:125-126, :146-168
   multiscale_forward(d, g->is3D, packed, x, p_out, precision_mode, msws, s);     // model.py:174-175
@@ -1964,14 +1974,9 @@ int fnx_fluidnet_forward(const FnxGrid* g, const void* packed, const float* inpu
                          float* U_out, int precision_mode, void* ws, size_t ws_bytes, void* stream) {
   int mode;
   if (int rc = check_net_call(__func__, g, packed && input && p_out && U_out && ws, precision_mode, &mode, true, ws_bytes)) return rc;
-  const GridDims d = make_dims(g->B, g->D, g->H, g->W, g->z_offset, g->D_global);
-  hipStream_t s = (hipStream_t)stream;
-  const int nc = g->is3D ? 3 : 2;
-  const size_t full = (size_t)g->B * d.DHW;
   float* flags = (float*)ws;                       // contiguous (B,1,..) copy of the flags channel
-  void* rest = (char*)ws + ((full * 4 + 255) & ~(size_t)255);
-  // model.py:104-119: split the channels
-  fnx::launch_gather_input(d, nc, input, U_out, flags, s);
+  void* rest = (char*)ws + fnx::fluidnet_flags_bytes(g->B, (size_t)g->D * g->H * g->W);
+  fnx::fluidnet_split(g, input, U_out, flags, stream);
   return fnx::fluidnet_core(g, packed, flags, thr, mode, p_out, U_out, rest, stream);
 }
 

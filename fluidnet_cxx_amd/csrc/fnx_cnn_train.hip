@@ -24,7 +24,6 @@ namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 inline size_t al64(size_t x) { return (x + 63) & ~(size_t)63; }
 inline bool is_mfma(const ConvLayer& L) { return L.k == 3 && L.cin % 16 == 0 && L.cout % 32 == 0; }   // Family::MFMA, also transposed
 
@@ -591,17 +590,7 @@ void launch_scale_mul(size_t n1, int nc, int B, const float* scale, const float*
 }
 
 
-// FluidNet.forward around a taped net and the adjoint of what follows it (fnx_cnn.h): one statement for the ScaleNet and the bank model.
-FluidnetTrainFwdWs fluidnet_train_fwd_ws(const FnxGrid* g, void* base) {
-  const size_t full = (size_t)g->B * g->D * g->H * g->W;
-  char* w = (char*)base;
-  FluidnetTrainFwdWs f{};
-  f.div = (float*)w; w += al256(full * 4);
-  f.x = (float*)w; w += al256(full * 2 * 4);
-  f.partial = (double*)w; w += al256(scale_std_scratch_bytes(g->B));
-  f.bytes = (size_t)(w - (char*)base);
-  return f;
-}
+// The adjoint of what follows a taped net in FluidNet.forward (fnx_cnn.h): one statement for the ScaleNet and the bank model.
 FluidnetTrainBwdWs fluidnet_train_bwd_ws(int nc, const FnxGrid* g, void* base) {
   const size_t full = (size_t)g->B * g->D * g->H * g->W;
   char* w = (char*)base;
@@ -613,21 +602,6 @@ FluidnetTrainBwdWs fluidnet_train_bwd_ws(int nc, const FnxGrid* g, void* base) {
   f.net = w;
   f.bytes = (size_t)(w - (char*)base);
   return f;
-}
-int fluidnet_train_pre(int nc, const FnxGrid* g, const float* input, float normalize_threshold, float* U_out, float* flags_out,
-                       float* scale_out, const FluidnetTrainFwdWs& w, void* stream) {
-  const GridDims d = make_dims(g->B, g->D, g->H, g->W);
-  hipStream_t s = (hipStream_t)stream;
-  launch_gather_input(d, nc, input, U_out, flags_out, s);
-  if (int rc = fnx_velocity_divergence(g, U_out, flags_out, w.div, stream)) return rc;
-  launch_scale_std(d, nc, U_out, normalize_threshold, w.partial, scale_out, s);
-  launch_pack_input(d, nc, w.div, flags_out, scale_out, U_out, w.x, s);
-  return FNX_OK;
-}
-int fluidnet_train_post(int nc, const FnxGrid* g, float* p_out, float* U_out, const float* flags, const float* scale, void* stream) {
-  if (int rc = fnx_velocity_update(g, p_out, U_out, flags, stream)) return rc;
-  launch_unscale(make_dims(g->B, g->D, g->H, g->W), nc, scale, p_out, U_out, (hipStream_t)stream);
-  return fnx_set_wall_bcs(g, U_out, flags, stream);
 }
 int fluidnet_train_gnet(int nc, const FnxGrid* g, const float* flags, const float* scale, const float* grad_p, const float* grad_U,
                         const FluidnetTrainBwdWs& w, void* stream) {
@@ -705,7 +679,6 @@ int check_image(const char* fn, bool is3d, size_t bytes, bool transposed) {
                         transposed ? "fnx_scalenet3d_pack_t" : "fnx_scalenet_pack(is3D = 1)",
                         bytes == (transposed ? fwd : bwd) ? " (packed and packed3d_t are swapped)" : "");
 }
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 int train_status(bool is3d) {
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? FNX_OK : fnx::set_error(FNX_EHIP, "HIP error in a %sCNN training launch: %s", is3d ? "3D " : "", hipGetErrorString(e));
@@ -745,7 +718,7 @@ int backward_call(const char* fn, bool is3d, const FnxGrid* g, const void* packe
 // nc: the velocity components, 2 or 3 (g is checked).
 // forward: div, x (2), std partials; backward: the wall-masked scaled grad_U (nc), grad_U of the update (nc), its grad_p, g_net
 size_t fluidnet_train_ws(int nc, const FnxGrid* g) {
-  const size_t fwd = fnx::fluidnet_train_fwd_ws(g, nullptr).bytes;
+  const size_t fwd = fnx::fluidnet_ws_layout(g->B, (size_t)g->D * g->H * g->W, 0, nullptr).head;
   const size_t bwd = fnx::fluidnet_train_bwd_ws(nc, g, nullptr).bytes + fnx::multiscale_backward_ws_bytes(nc == 3, g->B, g->D, g->H, g->W);
   return fwd > bwd ? fwd : bwd;
 }
@@ -759,11 +732,12 @@ int fluidnet_forward_train_call(const char* fn, int nc, const FnxGrid* g, const 
     return rc;
   if (int rc = check_image(fn, is3d, packed_bytes, false)) return rc;
   if (ws_bytes < fluidnet_train_ws(nc, g)) return too_small(fn, ws_bytes);
-  const fnx::FluidnetTrainFwdWs w = fnx::fluidnet_train_fwd_ws(g, ws);
+  const fnx::FluidnetWs w = fnx::fluidnet_ws_layout(g->B, (size_t)g->D * g->H * g->W, 0, ws);      // (its head: the scales go to scale_out)
   // fnx_fluidnet_forward's stages (model.py:104-227) around the taped net
-  if (int rc = fnx::fluidnet_train_pre(nc, g, input, normalize_threshold, U_out, flags_out, scale_out, w, stream)) return rc;
+  fnx::fluidnet_split(g, input, U_out, flags_out, stream);
+  if (int rc = fnx::fluidnet_pre(g, normalize_threshold, U_out, flags_out, scale_out, w, stream)) return rc;
   fnx::multiscale_forward_train(is3d, g->B, g->D, g->H, g->W, packed, w.x, p_out, tape, mode, (hipStream_t)stream);
-  if (int rc = fnx::fluidnet_train_post(nc, g, p_out, U_out, flags_out, scale_out, stream)) return rc;
+  if (int rc = fnx::fluidnet_post(g, p_out, U_out, flags_out, scale_out, stream)) return rc;
   return train_status(is3d);
 }
 

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from ._ext import ext
-from .weights import banknet_layers, make_banknet3d_weights, make_banknet_weights, make_scalenet_weights, scalenet_layers
+from .weights import banknet_layers, make_banknet_weights, make_scalenet_weights, scalenet_layers
 
 # Parameters of the reference FluidNet that its ScaleNet forward never reads (model.py:59-72: conv1, convBank, conv2,
 # conv3, convOut are only used by the 'FluidNet' variant).  A checkpoint of the reference carries them; load_state_dict
@@ -72,30 +72,33 @@ class MultiScaleNet:
 
 
 class BankNet:
-    """x (B,2,H,W) -> (B,1,H,W): the 16-channel bank net of model.py:177-209 (fnx_banknet.hip).  H and W multiples of 4, fp32 modes."""
+    """x (B,2,H,W) -> (B,1,H,W): the 16-channel bank net of model.py:177-209 (fnx_banknet.hip).  H and W multiples of 4, fp32 modes.
+    is3D: its Conv3d counterpart, x (B,2,D,H,W) -> (B,1,D,H,W) with D a multiple of 4 as well (fnx_banknet3d.hip)."""
 
-    def __init__(self, state_dict, device="cuda", precision_mode="fp32"):
-        self.is3D = False
+    def __init__(self, state_dict, device="cuda", precision_mode="fp32", is3D=False):
+        self.is3D = bool(is3D)
         self.precision_mode = precision_mode
         blob = torch.from_numpy(blob_from_state_dict(state_dict, keys=_bank_keys())).to(device)
-        self.packed = ext.banknet_pack(blob)
+        self.packed = (ext.banknet3d_pack if self.is3D else ext.banknet_pack)(blob)
 
     def __call__(self, x):
-        return ext.banknet_forward(self.packed, x.contiguous(), self.precision_mode)
+        return (ext.banknet3d_forward if self.is3D else ext.banknet_forward)(self.packed, x.contiguous(), self.precision_mode)
 
 
-class BankNet3D:
-    """x (B,2,D,H,W) -> (B,1,D,H,W): the Conv3d counterpart of BankNet, mconf['model'] = 'FluidNet3D' (fnx_banknet3d.hip).  D, H and W
-    multiples of 4, fp32 modes."""
+class BankNet3D(BankNet):
+    """The Conv3d bank net, mconf['model'] = 'FluidNet3D': BankNet with is3D."""
 
-    def __init__(self, state_dict, device="cuda", precision_mode="fp32"):
-        self.is3D = True
-        self.precision_mode = precision_mode
-        blob = torch.from_numpy(blob_from_state_dict(state_dict, keys=_bank_keys())).to(device)
-        self.packed = ext.banknet3d_pack(blob)
+    def __init__(self, state_dict, device="cuda", precision_mode="fp32", is3D=True):
+        super().__init__(state_dict, device, precision_mode, is3D)
 
-    def __call__(self, x):
-        return ext.banknet3d_forward(self.packed, x.contiguous(), self.precision_mode)
+
+# what differs between the three models of mconf['model']: a fresh net's weights (seed, ndim), the net alone (state_dict, device,
+# precision_mode, is3D) and ext's FluidNet.forward around it
+_MODELS = {
+    "ScaleNet": dict(weights=make_scalenet_weights, net=MultiScaleNet, forward="fluidnet_forward"),
+    "FluidNet": dict(weights=make_banknet_weights, net=BankNet, forward="fluidnet_bank_forward"),
+    "FluidNet3D": dict(weights=make_banknet_weights, net=BankNet3D, forward="fluidnet_bank3d_forward"),
+}
 
 
 class FluidNet:
@@ -139,8 +142,8 @@ class FluidNet:
         self.precision_mode = str(mconf.get("precisionMode", "fp32"))
         self.training = False
         self._ndim = 3 if self.is3D else 2
-        init = (make_banknet3d_weights(0) if self.is_bank3d else make_banknet_weights(0) if self.is_bank
-                else make_scalenet_weights(0, ndim=self._ndim))
+        self._model = _MODELS[model]         # (only names and classes: a FluidNet copies and pickles)
+        init = self._model["weights"](0, ndim=self._ndim)
         self._params = OrderedDict((k, torch.from_numpy(v)) for k, v in init.items())
         self._want = _bank_keys() if self.is_bank else _layer_keys(self._ndim)
         self._unused = _BANK_UNUSED_PREFIXES if self.is_bank else _UNUSED_PREFIXES
@@ -217,9 +220,7 @@ class FluidNet:
         if device.type == "cuda" and device.index is None:
             device = torch.device("cuda", torch.cuda.current_device())
         if self._ms is None or self._ms_device != device:
-            self._ms = (BankNet3D(self._params, device, self.precision_mode) if self.is_bank3d
-                        else BankNet(self._params, device, self.precision_mode) if self.is_bank
-                        else MultiScaleNet(self._params, device, self.is3D, self.precision_mode))
+            self._ms = self._model["net"](self._params, device, precision_mode=self.precision_mode, is3D=self.is3D)
             self._ms_device = device
         return self._ms
 
@@ -252,8 +253,7 @@ class FluidNet:
 
     def __call__(self, input_):
         ms = self._ensure_packed(input_.device)
-        fwd = ext.fluidnet_bank3d_forward if self.is_bank3d else ext.fluidnet_bank_forward if self.is_bank else ext.fluidnet_forward
-        p, U = fwd(ms.packed, input_.contiguous(), self.threshold, self.precision_mode)
+        p, U = getattr(ext, self._model["forward"])(ms.packed, input_.contiguous(), self.threshold, self.precision_mode)
         return p, U
 
     forward = __call__

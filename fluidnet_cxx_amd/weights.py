@@ -44,14 +44,10 @@ def banknet_layers():
     return [dict(name=n, cin=ci, cout=co, k=k, relu=n != "convOut") for n, ci, co, k in t]
 
 
+banknet3d_layers = banknet_layers     # the Conv3d bank net ('FluidNet3D'): the same names, channels and kernel extents, 5-D weights
+
 _BANKNET_STREAM0 = 1000      # hash_uniform streams 1000 .. 1011: ScaleNet's are 0 .. 33
 _BANKNET3D_STREAM0 = 1100    # the Conv3d bank net: 1100 .. 1111
-
-
-def banknet3d_layers():
-    """Layer table of the Conv3d counterpart of the bank net (mconf['model'] = 'FluidNet3D'): banknet_layers() with every module
-    replaced by its 3D sibling -- the same names, channels and kernel extents, 5-D weights, 15153 floats."""
-    return banknet_layers()
 
 
 def _splitmix64(x):
@@ -86,25 +82,19 @@ def make_scalenet_weights(seed=0, in_dims=2, ndim=2, gain=1.0):
     return w
 
 
-def make_banknet_weights(seed=0, gain=1.0):
-    """name -> np.float32 array for the twelve parameter tensors of the bank net (5361 floats), torch's default bound."""
+def make_banknet_weights(seed=0, gain=1.0, ndim=2):
+    """name -> np.float32 array for the twelve parameter tensors of the bank net (ndim 2: 5361 floats; 3, the Conv3d net: 15153),
+    torch's default bound."""
     w = {}
     for li, L in enumerate(banknet_layers()):
-        fan_in = L["cin"] * L["k"] * L["k"]
+        kshape = (L["k"],) * ndim
+        fan_in = L["cin"] * L["k"] ** ndim
         bound = gain / np.sqrt(fan_in)
-        w[L["name"] + ".weight"] = (hash_uniform(L["cout"] * fan_in, _BANKNET_STREAM0 + 2 * li, seed) * np.float32(bound)).reshape(
-            (L["cout"], L["cin"], L["k"], L["k"]))
-        w[L["name"] + ".bias"] = hash_uniform(L["cout"], _BANKNET_STREAM0 + 2 * li + 1, seed) * np.float32(bound)
+        stream = (_BANKNET3D_STREAM0 if ndim == 3 else _BANKNET_STREAM0) + 2 * li
+        w[L["name"] + ".weight"] = (hash_uniform(L["cout"] * fan_in, stream, seed) * np.float32(bound)).reshape((L["cout"], L["cin"]) + kshape)
+        w[L["name"] + ".bias"] = hash_uniform(L["cout"], stream + 1, seed) * np.float32(bound)
     return w
 
 
 def make_banknet3d_weights(seed=0, gain=1.0):
-    """name -> np.float32 array for the twelve parameter tensors of the Conv3d bank net (15153 floats), torch's default bound."""
-    w = {}
-    for li, L in enumerate(banknet3d_layers()):
-        fan_in = L["cin"] * L["k"] ** 3
-        bound = gain / np.sqrt(fan_in)
-        w[L["name"] + ".weight"] = (hash_uniform(L["cout"] * fan_in, _BANKNET3D_STREAM0 + 2 * li, seed) * np.float32(bound)).reshape(
-            (L["cout"], L["cin"], L["k"], L["k"], L["k"]))
-        w[L["name"] + ".bias"] = hash_uniform(L["cout"], _BANKNET3D_STREAM0 + 2 * li + 1, seed) * np.float32(bound)
-    return w
+    return make_banknet_weights(seed, gain, ndim=3)

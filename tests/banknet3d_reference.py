@@ -23,23 +23,15 @@ tiles of (y, x), z split into chunks of at least four planes while fewer than 40
 tests/test_banknet3d_host.py checks on the plan itself that tiles and chunks cover every one of these grids (and larger ones) once.
 """
 import numpy as np
-import torch
-import torch.nn.functional as F
 
-from fluidnet_cxx_amd.weights import banknet3d_layers, hash_uniform, make_banknet3d_weights
+from banknet_reference import banknet_forward64, propagating_bank_weights
+from fluidnet_cxx_amd.weights import hash_uniform
 
 SHAPES3D = [(1, 4, 4, 4), (2, 8, 12, 20), (1, 12, 20, 36), (2, 4, 36, 68), (1, 20, 12, 132)]     # (B, D, H, W)
 
 
 def propagating_bank3d_weights(seed=0):
-    """make_banknet3d_weights(seed) scaled to He-uniform: weights x sqrt(6) for a layer followed by ReLU, x sqrt(3) for convOut,
-    biases x 0.1 (as banknet_reference.propagating_bank_weights).  float32, the same names and shapes."""
-    w = make_banknet3d_weights(seed)
-    for L in banknet3d_layers():
-        g = np.sqrt(6.0) if L["relu"] else np.sqrt(3.0)
-        w[L["name"] + ".weight"] = (w[L["name"] + ".weight"].astype(np.float64) * g).astype(np.float32)
-        w[L["name"] + ".bias"] = (w[L["name"] + ".bias"].astype(np.float64) * 0.1).astype(np.float32)
-    return w
+    return propagating_bank_weights(seed, ndim=3)
 
 
 def bank3d_input(B, D, H, W, boxes=True, seed=0):
@@ -59,27 +51,6 @@ def bank3d_input(B, D, H, W, boxes=True, seed=0):
 
 
 def banknet3d_forward64(weights, x, drop=None):
-    """p (B,1,D,H,W) float64 of the net above for x (B,2,D,H,W); weights: name -> array or tensor."""
-    w = {k: torch.as_tensor(np.asarray(v), dtype=torch.float64) for k, v in weights.items()}
-    x = torch.as_tensor(np.asarray(x), dtype=torch.float64)
-    assert x.dim() == 5 and x.size(1) == 2 and all(x.size(i) % 4 == 0 for i in (2, 3, 4))
-
-    def conv(t, name, pad):
-        return F.conv3d(t, w[name + ".weight"], w[name + ".bias"], padding=pad)
-
-    def bank(t):
-        return F.relu(conv(F.relu(conv(t, "convBank.block.0", 1)), "convBank.block.2", 1))
-
-    def up(t, r):
-        return t.repeat_interleave(r, 2).repeat_interleave(r, 3).repeat_interleave(r, 4)
-
-    a = F.relu(conv(x, "conv1", 1))
-    levels = [bank(a), up(bank(F.avg_pool3d(a, 2)), 2), up(bank(F.avg_pool3d(a, 4)), 4)]
-    t = None
-    for i, l in enumerate(levels):
-        if i != drop:
-            t = l if t is None else t + l
-    t = F.relu(conv(t, "conv2", 0))
-    t = F.relu(conv(t, "conv2", 0))
-    t = F.relu(conv(t, "conv3", 0))
-    return conv(t, "convOut", 0)
+    """p (B,1,D,H,W) float64 of the net above for x (B,2,D,H,W): banknet_reference's one statement of the net, on five dimensions"""
+    assert np.ndim(x) == 5
+    return banknet_forward64(weights, x, drop)

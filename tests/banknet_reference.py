@@ -21,10 +21,10 @@ SHAPES = [(1, 4, 4), (2, 8, 12), (1, 16, 24), (3, 36, 68), (1, 132, 260)]     # 
 GOLDEN_SHAPES = SHAPES[:4]
 
 
-def propagating_bank_weights(seed=0):
-    """make_banknet_weights(seed) scaled to He-uniform: weights x sqrt(6) for a layer followed by ReLU, x sqrt(3) for convOut,
-    biases x 0.1 (as cnn_reference.propagating_weights).  float32, the same names and shapes."""
-    w = make_banknet_weights(seed)
+def propagating_bank_weights(seed=0, ndim=2):
+    """make_banknet_weights(seed, ndim=ndim) scaled to He-uniform: weights x sqrt(6) for a layer followed by ReLU, x sqrt(3) for
+    convOut, biases x 0.1 (as cnn_reference.propagating_weights).  float32, the same names and shapes."""
+    w = make_banknet_weights(seed, ndim=ndim)
     for L in banknet_layers():
         g = np.sqrt(6.0) if L["relu"] else np.sqrt(3.0)
         w[L["name"] + ".weight"] = (w[L["name"] + ".weight"].astype(np.float64) * g).astype(np.float32)
@@ -49,22 +49,31 @@ def bank_input(B, H, W, seed=0, boxes=False):
 
 
 def banknet_forward64(weights, x, drop=None):
-    """p (B,1,H,W) float64 of the net above for x (B,2,H,W); weights: name -> array or tensor."""
+    """p float64 of the net above for x (B,2,H,W), or of its Conv3d counterpart (tests/banknet3d_reference.py) for x (B,2,D,H,W);
+    weights: name -> array or tensor."""
     w = {k: torch.as_tensor(np.asarray(v), dtype=torch.float64) for k, v in weights.items()}
     x = torch.as_tensor(np.asarray(x), dtype=torch.float64)
-    assert x.dim() == 4 and x.size(1) == 2 and x.size(2) % 4 == 0 and x.size(3) % 4 == 0
+    axes = tuple(range(2, x.dim()))
+    assert x.dim() in (4, 5) and x.size(1) == 2 and all(x.size(i) % 4 == 0 for i in axes)
+    convnd, pool = (F.conv2d, F.avg_pool2d) if x.dim() == 4 else (F.conv3d, F.avg_pool3d)
 
     def conv(t, name, pad):
-        return F.conv2d(t, w[name + ".weight"], w[name + ".bias"], padding=pad)
+        return convnd(t, w[name + ".weight"], w[name + ".bias"], padding=pad)
 
     def bank(t):
         return F.relu(conv(F.relu(conv(t, "convBank.block.0", 1)), "convBank.block.2", 1))
 
+    def up(t, r):
+        for i in axes:
+            t = t.repeat_interleave(r, i)
+        return t
+
     a = F.relu(conv(x, "conv1", 1))
-    levels = [bank(a),
-              bank(F.avg_pool2d(a, 2)).repeat_interleave(2, 2).repeat_interleave(2, 3),
-              bank(F.avg_pool2d(a, 4)).repeat_interleave(4, 2).repeat_interleave(4, 3)]
-    t = sum(l for i, l in enumerate(levels) if i != drop)
+    levels = [bank(a), up(bank(pool(a, 2)), 2), up(bank(pool(a, 4)), 4)]
+    t = None
+    for i, l in enumerate(levels):          # (full + half) + quarter
+        if i != drop:
+            t = l if t is None else t + l
     t = F.relu(conv(t, "conv2", 0))
     t = F.relu(conv(t, "conv2", 0))
     t = F.relu(conv(t, "conv3", 0))
