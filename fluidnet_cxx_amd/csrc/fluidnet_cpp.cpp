@@ -1273,7 +1273,7 @@ void post_projection_(Tensor p, Tensor U, Tensor flags, c10::optional<Tensor> de
 
 int64_t step_workspace_bytes(int B, int D, int H, int W, bool is3D) {
   FnxGrid g{B, D, H, W, is3D ? 1 : 0, 0, 0, 0};
-  return (int64_t)fnx_workspace_bytes(&g, FNX_OP_STEP);
+  return (int64_t)fnx_workspace_bytes(&g, FNX_OP_STEP_STATIC);   // (3D: with room for the stage word map; FNX_OP_STEP's size is still accepted)
 }
 
 }  // namespace

@@ -94,6 +94,11 @@ fnx::StepLayout carve_step(const FnxGrid* g, void* ws) {
   return fnx::step_layout(ncell(g), g->is3D ? 3 : 2, g->is3D != 0, ws_mask(g), ws_pcg_kept(g), tail_need, ws);
 }
 size_t ws_step(const FnxGrid* g) { return carve_step(g, nullptr).bytes; }
+// the step's workspace with, in 3D, room for the stage word map behind it (fnx_step_plan.h)
+size_t ws_step_static(const FnxGrid* g) {
+  const fnx::StepLayout L = carve_step(g, nullptr);
+  return g->is3D ? fnx::stage_word_offset(L) + al(fnx::stage_word_bytes(ncell(g), true)) : L.bytes;
+}
 
 }  // namespace
 
@@ -237,6 +242,7 @@ size_t fnx_workspace_bytes(const FnxGrid* g, int op) {
     case FNX_OP_STEP: return ws_step(g);
     case FNX_OP_FLUIDNET: return fnx::fluidnet_ws_bytes(dims(g), g->is3D);
     case FNX_OP_ADVECT_STEP: return ws_advect(g, fnx::ADVECT_BOTH);
+    case FNX_OP_STEP_STATIC: return ws_step_static(g);
   }
   fail(FNX_EINVAL, "unknown op %d", op);
   return 0;
@@ -863,8 +869,9 @@ int fnx_velocity_update_backward(const FnxGrid* g, const float* grad_U_out, cons
 // cell re-derives the staged component of its +1 neighbours), unless the periodic patches have to go between the stages and the
 // divergence: then staging, patches, a divergence pass.  With the confinement, which reads the field three cells around a cell and so
 // cannot join the radius-1 recompute, the stage is cut in three around it.
+// word: the step's stage word map (3D, with st->bc_class), or nullptr
 static int pre_projection(const FnxGrid* g, const fnx::StagePlan& sp, const FnxState* st, const float* U_adv, const float* rho_adv,
-                          float* div, void* stream) {
+                          float* div, void* stream, const unsigned* word = nullptr) {
   // a cell reads the advected fields of its +1 / -1 neighbours while other threads write theirs: no in-place use
   if (U_adv == st->U || (rho_adv && rho_adv == st->density)) return fail(FNX_EINVAL, "pre_projection: the advected fields must not alias the state");
   if (sp.confine && is_view(g))
@@ -872,7 +879,7 @@ static int pre_projection(const FnxGrid* g, const fnx::StagePlan& sp, const FnxS
   hipStream_t s = (hipStream_t)stream;
   fnx::ProfScope ps(FNX_PROF_STAGE, s);
   const GridDims d = dims(g);
-  const fnx::BcPtrs bc = fnx::bc_ptrs(st);
+  const fnx::BcPtrs bc = fnx::bc_ptrs(st, word);
   // the uncut stage: every operation of the plan, the divergence in the same pass unless the patches come between
   const fnx::StageIO io{U_adv, rho_adv, st->flags, bc, st->U, st->density, sp.periodic ? nullptr : div};
   const fnx::StageOps all{quirks(g), true, sp.buoy, {sp.s[0], sp.s[1], sp.s[2]}, sp.rho_star, sp.grav, {sp.g[0], sp.g[1], sp.g[2]},
@@ -916,15 +923,17 @@ int fnx_pre_projection(const FnxGrid* g, const FnxStepParams* prm, const FnxStat
   return pre_projection(g, fnx::stage_plan(prm, rho_adv != nullptr, st->flags_stick != nullptr), st, U_adv, rho_adv, div, stream);
 }
 
-int fnx_post_projection(const FnxGrid* g, const FnxState* st, void* stream) {
+static int post_projection(const FnxGrid* g, const FnxState* st, void* stream, const unsigned* word) {
   if (int rc = check_grid(g)) return rc;
   if (!st || !st->U || !st->flags || !st->p) return fail(FNX_EINVAL, "post_projection: NULL state");
   fnx::ProfScope ps(FNX_PROF_STAGE, (hipStream_t)stream);
-  fnx::launch_post_projection(dims(g), g->is3D, st->p, st->U, st->density, st->flags, fnx::bc_ptrs(st), (hipStream_t)stream,
+  fnx::launch_post_projection(dims(g), g->is3D, st->p, st->U, st->density, st->flags, fnx::bc_ptrs(st, word), (hipStream_t)stream,
                               st->density_bc_applied != 0);
   HIP_OK(hipGetLastError());
   return FNX_OK;
 }
+
+int fnx_post_projection(const FnxGrid* g, const FnxState* st, void* stream) { return post_projection(g, st, stream, nullptr); }
 
 int fnx_bc_classify(const FnxGrid* g, const FnxState* st, unsigned char* bc_class, void* stream) {
   if (int rc = check_grid(g)) return rc;
@@ -937,7 +946,7 @@ int fnx_bc_classify(const FnxGrid* g, const FnxState* st, unsigned char* bc_clas
 // One whole step: the argument checks, the workspace (carve_step), the plan (fnx::step_plan), then the sequence the plan names.
 int fnx_simulate_step(const FnxGrid* g, const FnxStepParams* prm, const FnxState* st, void* ws, size_t ws_bytes,
                       void* stream) {
-  using fnx::StepAdvect; using fnx::StepClassMap; using fnx::StepProjection; using fnx::StepTail;
+  using fnx::StepAdvect; using fnx::StepClassMap; using fnx::StepProjection; using fnx::StepStageWord; using fnx::StepTail;
   if (int rc = check_grid(g)) return rc;
   if (!prm || !st || !st->p || !st->U || !st->flags) return fail(FNX_EINVAL, "simulate_step: NULL state");
   if (prm->method < 0 || prm->method > 4) return fail(FNX_EINVAL, "Simulation method not supported. Choose convnet, jacobi, pcg or hybrid.");
@@ -989,8 +998,15 @@ int fnx_simulate_step(const FnxGrid* g, const FnxStepParams* prm, const FnxState
   stc.bc_class = plan.class_map == StepClassMap::NONE ? nullptr : L.cls;
   stc.density_bc_applied = 1;                  // by the pre-projection stage below, with these BC arrays
   st = &stc;
+  // static flags as well, 3D, and a workspace of FNX_OP_STEP_STATIC's size: the stage and the tail go by the stage word map behind the layout
+  const StepStageWord sw = fnx::stage_word_plan(prm, g->is3D != 0, plan.class_map, L, ncell(g), ws_bytes);
+  unsigned* word = sw == StepStageWord::NONE ? nullptr : (unsigned*)((char*)ws + fnx::stage_word_offset(L));
+  if (sw == StepStageWord::BUILD) {
+    fnx::ProfScope ps(FNX_PROF_STAGE, s);
+    fnx::launch_stage_word(d, st->flags, L.cls, word, s);
+  }
   // simulate.py:96-133 (+ :144 divergence) in one pass: BCs, buoyancy, gravity, wall BCs (+ periodic patches), BCs, -div
-  if (int rc = pre_projection(g, plan.stage, st, L.U2, has_rho ? L.rho2 : nullptr, plan.solve ? L.div : nullptr, stream)) return rc;
+  if (int rc = pre_projection(g, plan.stage, st, L.U2, has_rho ? L.rho2 : nullptr, plan.solve ? L.div : nullptr, stream, word)) return rc;
 
   // setWallBcsStick is out of place: st->U -> U2 (free since the staging pass) and back; then the setConstVals behind it
   auto stick_then_bcs = [&]() -> int {
@@ -1031,14 +1047,14 @@ int fnx_simulate_step(const FnxGrid* g, const FnxStepParams* prm, const FnxState
   }
   switch (plan.tail) {                         // simulate.py:154-168
     case StepTail::POST:
-      if (int rc = fnx_post_projection(g, st, stream)) return rc;
+      if (int rc = post_projection(g, st, stream, word)) return rc;
       break;
     case StepTail::POST_PERIODIC: {
       // simulate.py:157-164: the patches read the field as it was before setWallBcs; their source row / column (border cells,
       // which velocityUpdate leaves alone) is saved ahead of the in-place pass.  The solve is through with the tail.
       const fnx::BcPtrs bc = fnx::bc_ptrs(st);
       fnx::launch_periodic_post(d, g->is3D, st->U, (float*)L.tail, nullptr, nullptr, plan.stage.px, plan.stage.py, 0, s);
-      if (int rc = fnx_post_projection(g, st, stream)) return rc;
+      if (int rc = post_projection(g, st, stream, word)) return rc;
       fnx::launch_periodic_post(d, g->is3D, st->U, (float*)L.tail, bc.UBC, bc.UBCInvMask, plan.stage.px, plan.stage.py, 1, s);
       break;
     }

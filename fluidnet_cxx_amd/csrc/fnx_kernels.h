@@ -89,11 +89,13 @@ void launch_set_wall_bcs_stick3d(const GridDims& g, const float* Uin, float* Uou
 
 // fused step stages (fnx_step.hip)
 // The BC arrays of a state as the stages take them: a pair counts only with both of its halves (bc_ptrs); cls: the optional class map
-struct BcPtrs { const float *UBC, *UBCInvMask, *rhoBC, *rhoBCInvMask; const unsigned char* cls; };
-inline BcPtrs bc_ptrs(const FnxState* st) {
+// word: the optional stage word map of a 3D array (fnx_stage_word.h; needs cls): the 3D stage and the unscaled 3D post-projection pass then
+// read it instead of flags and cls.  Only fnx_simulate_step has one (the map lives in its workspace).
+struct BcPtrs { const float *UBC, *UBCInvMask, *rhoBC, *rhoBCInvMask; const unsigned char* cls; const unsigned* word; };
+inline BcPtrs bc_ptrs(const FnxState* st, const unsigned* word = nullptr) {
   const bool ubc = st->UBC && st->UBCInvMask, rbc = st->densityBC && st->densityBCInvMask;
   return BcPtrs{ubc ? st->UBC : nullptr, ubc ? st->UBCInvMask : nullptr, rbc ? st->densityBC : nullptr, rbc ? st->densityBCInvMask : nullptr,
-                st->bc_class};
+                st->bc_class, st->bc_class ? word : nullptr};
 }
 // The stage between the advection and the projection: U_adv, rho_adv (may be null) -> U, rho and, with `div`, the divergence of the
 // staged field (the staged value of a cell's +1 neighbours is re-derived in the same pass; their advected inputs must be valid)
@@ -125,6 +127,8 @@ void launch_post_projection(const GridDims& g, bool is3d, const float* p, float*
 // scale (B device floats) / p_scaled: the tail of FluidNet.forward in the same pass (u = U / s into the update, u * s and
 // p_scaled = p * s out of it); p_scaled must not alias p (a cell reads p of its -1 neighbours)
 void launch_bc_classify(const GridDims& g, bool is3d, const BcPtrs& bc, unsigned char* cls, hipStream_t s);
+// the stage word of every cell of a 3D array (all D planes, whatever the compute window) from flags and the class map
+void launch_stage_word(const GridDims& g, const float* flags, const unsigned char* cls, unsigned* word, hipStream_t s);
 
 // vorticity confinement (fnx_vorticity.hip): U_out = U_in + the confinement force of U_in scaled by amp; whole grids only (no
 // compute window, no z-slab view); U_out must not alias U_in

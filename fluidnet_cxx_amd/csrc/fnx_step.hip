@@ -15,8 +15,13 @@
 // (simulate.py:133).
 #include "fnx_device.h"
 #include "fnx_kernels.h"
+#include "fnx_stage_word.h"
+
+#include <type_traits>
 
 namespace {
+
+using fnx::FlagConst;
 
 constexpr int BX = 64, BY = 4;
 
@@ -27,14 +32,18 @@ struct StepPtrs {
   const float* rhoBC; const float* rhoBCInvMask;     // may be null
   float* U; float* rho; float* div;
   const unsigned char* cls;                          // optional BC class map (bit 0: velocity BCs are x*1+0, bit 1: density)
+  const unsigned* word;                              // 3D, WORD instances: the stage word map (fnx_stage_word.h) instead of flags and cls
   int grav; float gx, gy, gz;                        // addGravity after the buoyancy (simulate.py:107-114); strengths = gravity * dt
   int bc2;                                           // 0: leave out the second setConstVals (simulate.py:133) -- the caller runs
                                                      // setWallBcsStick between the two (simulate.py:129-133)
 };
 
 // addGravity's condition for one component of a non-border cell (source_terms.py:122-219; add_gravity_kernel)
-__device__ __forceinline__ bool gravity_applies(float fc, float fm) {
-  return (fc == FNX_FLUID || fc == FNX_EMPTY) && (fm == FNX_FLUID || (fm == FNX_EMPTY && fc == FNX_FLUID));
+// (F: a flag value or, in the kernels that go by the stage word, its code -- FlagConst<F> of fnx_stage_word.h is what it is compared with)
+template <class F>
+__device__ __forceinline__ bool gravity_applies(F fc, F fm) {
+  using K = FlagConst<F>;
+  return (fc == K::fluid || fc == K::empty) && (fm == K::fluid || (fm == K::empty && fc == K::fluid));
 }
 
 // The stage sequence of component `a` of one 3D cell: u its advected value, (um, uc) its velocity-BC entry, fc / fm the flags of
@@ -43,21 +52,22 @@ __device__ __forceinline__ bool gravity_applies(float fc, float fm) {
 // BC1 = false leaves out the first setConstVals (simulate.py:96): the input is a field that has been through it already -- the second
 // launch of a stage cut in two around the vorticity confinement (fnx_pre_projection).  The default instantiations are the kernels
 // of the uncut stage, unchanged.
-template <bool QUIRKS, bool WALL, bool BC1 = true>
-__device__ __forceinline__ float stage_eval3d(int a, float v, bool ubc, float um, float uc, float fc, float fm, bool border, bool buoy,
+template <bool QUIRKS, bool WALL, bool BC1 = true, class F>
+__device__ __forceinline__ float stage_eval3d(int a, float v, bool ubc, float um, float uc, F fc, F fm, bool border, bool buoy,
                                               float r0, float r1, bool rbc, float rm0, float rc0, float rm1, float rc1, float s_a,
                                               float rho_star, bool grav, float g_a, bool bc2, int kg, int k) {
+  using K = FlagConst<F>;
   if (ubc && BC1) { const float t = v * um; v = t + uc; }                                         // simulate.py:96
-  if (buoy && !border && fc == FNX_FLUID && fm == FNX_FLUID) {                              // source_terms.py
+  if (buoy && !border && fc == K::fluid && fm == K::fluid) {                                // source_terms.py
     float q0 = r0, q1 = r1;
     if (rbc) { float t = q0 * rm0; q0 = t + rc0; t = q1 * rm1; q1 = t + rc1; }
     if (a == 2 && QUIRKS) v = v + s_a * (0.5f * (q0 + (kg <= 1 ? 0.f : q1)));
     else v = v + s_a * ((0.5f * (q0 + q1)) - rho_star);
   }
   if (grav && !border && gravity_applies(fc, fm)) v = v + g_a;                             // source_terms.py:122-219
-  if (WALL && (fc == FNX_FLUID || fc == FNX_OBST)) {                                        // set_wall_bcs.py:45-84
+  if (WALL && (fc == K::fluid || fc == K::obst)) {                                          // set_wall_bcs.py:45-84
     if (!(a == 2 && (kg == 0 || k == 0))) {
-      if (fm == FNX_OBST || (fc == FNX_OBST && fm == FNX_FLUID)) v = 0.f;
+      if (fm == K::obst || (fc == K::obst && fm == K::fluid)) v = 0.f;
     }
   }
   if (ubc && bc2) { const float t = v * um; v = t + uc; }                                  // simulate.py:133
@@ -75,9 +85,14 @@ __device__ __forceinline__ float stage_eval3d(int a, float v, bool ubc, float um
 // neighbouring thread loads as its own -- instead of a second pass reading the staged field back (round 1 measured the fused
 // form slower, 0.67 against 0.59 ms at 256^3: that was the branchy kernel with 54 dependent loads; in the straight-line form
 // the divergence pass's 75 us at 512x512x64 become ~15).
-template <bool QUIRKS, bool WALL, bool DIV, bool BC1 = true>
+// WORD: the flags of the cell and of its six neighbours, and the class bits `ident` is made of, come out of the cell's stage word (one
+// load instead of seven flag values and seven class bytes; P.flags and P.cls are not read).  The predicates are integer tests on the
+// 2-bit flag codes; every float operation of the stage sequence is the same, on the same operands, in the same order.
+template <bool QUIRKS, bool WALL, bool DIV, bool BC1 = true, bool WORD = false>
 __global__ __launch_bounds__(BX* BY) void stage3d_kernel(GridDims g, StepPtrs P, int buoy, float sx, float sy, float sz,
                                                          float rho_star, int kdiv) {
+  using F = std::conditional_t<WORD, unsigned, float>;           // a flag: its code or its value
+  using K = FlagConst<F>;
   const int i = blockIdx.x * BX + threadIdx.x, j = blockIdx.y * BY + threadIdx.y;
   const int bk = blockIdx.z;
   const int b = bk / g.KN, k = g.K0 + (bk - b * g.KN);
@@ -88,7 +103,11 @@ __global__ __launch_bounds__(BX* BY) void stage3d_kernel(GridDims g, StepPtrs P,
   const int offp[3] = { i + 1 < g.W ? 1 : 0, j + 1 < g.H ? g.W : 0, k + 1 < g.D ? g.HW : 0 };   // +1 neighbours (DIV); 0 where there is none: never used
   const bool has_rho = P.rho_adv != nullptr, ubc = P.UBC != nullptr, rbc = P.rhoBC != nullptr;
   bool ident = false;
-  if (P.cls) {
+  unsigned w = 0u;
+  if constexpr (WORD) {
+    w = P.word[os];
+    ident = __builtin_amdgcn_ballot_w64(!fnx::stage_word_ident(w, want_div)) == 0;
+  } else if (P.cls) {
     bool mine = P.cls[os] == 3;
 #pragma unroll
     for (int a = 0; a < 3; ++a) mine = mine & ((P.cls[os - off[a]] & 2) != 0);
@@ -99,19 +118,26 @@ __global__ __launch_bounds__(BX* BY) void stage3d_kernel(GridDims g, StepPtrs P,
     ident = __builtin_amdgcn_ballot_w64(!mine) == 0;
   }
   // ---- loads
-  const float fc = P.flags[os];
-  float fm[3], u[3], r1[3] = { 0.f, 0.f, 0.f }, r0 = 0.f;
+  F fc, fm[3], fp[3] = { F(0), F(0), F(0) };
+  if constexpr (WORD) fc = fnx::stage_word_cell(w); else fc = P.flags[os];
+  float u[3], r1[3] = { 0.f, 0.f, 0.f }, r0 = 0.f;
 #pragma unroll
-  for (int a = 0; a < 3; ++a) { fm[a] = P.flags[os - off[a]]; u[a] = P.U_adv[((size_t)b * 3 + a) * g.DHW + o]; }
+  for (int a = 0; a < 3; ++a) {
+    if constexpr (WORD) fm[a] = fnx::stage_word_minus(w, a); else fm[a] = P.flags[os - off[a]];
+    u[a] = P.U_adv[((size_t)b * 3 + a) * g.DHW + o];
+  }
   if (has_rho) {
     r0 = P.rho_adv[os];
 #pragma unroll
     for (int a = 0; a < 3; ++a) r1[a] = P.rho_adv[os - off[a]];
   }
-  float fp[3] = { 0.f, 0.f, 0.f }, up[3] = { 0.f, 0.f, 0.f }, rp[3] = { 0.f, 0.f, 0.f };
+  float up[3] = { 0.f, 0.f, 0.f }, rp[3] = { 0.f, 0.f, 0.f };
   if (want_div) {
 #pragma unroll
-    for (int a = 0; a < 3; ++a) { fp[a] = P.flags[os + offp[a]]; up[a] = P.U_adv[((size_t)b * 3 + a) * g.DHW + o + offp[a]]; }
+    for (int a = 0; a < 3; ++a) {
+      if constexpr (WORD) fp[a] = fnx::stage_word_plus(w, a); else fp[a] = P.flags[os + offp[a]];
+      up[a] = P.U_adv[((size_t)b * 3 + a) * g.DHW + o + offp[a]];
+    }
     if (has_rho) {
 #pragma unroll
       for (int a = 0; a < 3; ++a) rp[a] = P.rho_adv[os + offp[a]];
@@ -170,7 +196,7 @@ __global__ __launch_bounds__(BX* BY) void stage3d_kernel(GridDims g, StepPtrs P,
       d = ((un[0] - vp[0]) + un[1]) - vp[1];
       d = d + (un[2] - vp[2]);
     }
-    if (fc == FNX_OBST) d = 0.f;
+    if (fc == K::obst) d = 0.f;
     P.div[os] = d;
   }
 }
@@ -263,7 +289,8 @@ __global__ __launch_bounds__(BX* BY) void stage2d_div_kernel(GridDims g, StepPtr
 // With `scale` (the convnet branch: model.py:213-226 then simulate.py:168) the same pass is the tail of FluidNet.forward: U holds
 // the unnormalised velocity and p the net's output for U / s, so u = U / s goes into the update, the updated u and the pressure are
 // multiplied by s again (p_scaled receives p * s), then wall BCs and BCs -- the operators' own arithmetic in their own order.
-template <bool IS3D, bool SCALE>
+// WORD (3D): flags of the cell and of its -1 neighbours and the cell's class come out of the stage word; `flags` and `cls` are not read.
+template <bool IS3D, bool SCALE, bool WORD = false>
 __global__ __launch_bounds__(BX* BY) void post_projection_kernel(GridDims g, const float* __restrict__ p,
                                                                  float* __restrict__ U, float* __restrict__ rho,
                                                                  const float* __restrict__ flags,
@@ -272,7 +299,11 @@ __global__ __launch_bounds__(BX* BY) void post_projection_kernel(GridDims g, con
                                                                  const float* __restrict__ rhoBC,
                                                                  const float* __restrict__ rhoBCInvMask,
                                                                  const unsigned char* __restrict__ cls, int rho_done,
-                                                                 const float* __restrict__ scale, float* __restrict__ p_scaled) {
+                                                                 const float* __restrict__ scale, float* __restrict__ p_scaled,
+                                                                 const unsigned* __restrict__ word) {
+  static_assert(IS3D || !WORD, "the stage word is 3D only");
+  using F = std::conditional_t<WORD, unsigned, float>;           // a flag: its code or its value
+  using K = FlagConst<F>;
   const int i = blockIdx.x * BX + threadIdx.x, j = blockIdx.y * BY + threadIdx.y;
   const int bk = blockIdx.z;
   const int b = IS3D ? bk / g.KN : bk, k = IS3D ? g.K0 + (bk - b * g.KN) : 0;
@@ -282,11 +313,17 @@ __global__ __launch_bounds__(BX* BY) void post_projection_kernel(GridDims g, con
   // Straight-line like stage3d_kernel: every load is issued up front with an address that is valid for every lane (a missing -1
   // neighbour reads the cell itself; BC entries are loaded for the whole wave when any lane needs them) and the conditions become
   // selects.  (Nested in the conditions they were a chain of load -> wait -> branch round trips: 30 waits for 20 loads.)
-  const float fc = flags[os], P = p[os];
-  const unsigned cl = cls ? cls[os] : 0u;
+  const float P = p[os];
+  unsigned sw = 0u;
+  if constexpr (WORD) sw = word[os];
+  F fc;
+  unsigned cl;
+  if constexpr (WORD) { fc = fnx::stage_word_cell(sw); cl = fnx::stage_word_class(sw); }
+  else { fc = flags[os]; cl = cls ? cls[os] : 0u; }
   const bool border = is_border<IS3D>(g, i, j, k);
   const float sc = SCALE ? scale[b] : 1.f;
-  float fm[NC], Pm[NC], u[NC], bm[NC], bc[NC];
+  F fm[NC];
+  float Pm[NC], u[NC], bm[NC], bc[NC];
   size_t ou[NC];
   const bool need_u = UBC != nullptr && !(cl & 1);
   const bool load_u = __builtin_amdgcn_ballot_w64(need_u) != 0;
@@ -299,7 +336,8 @@ __global__ __launch_bounds__(BX* BY) void post_projection_kernel(GridDims g, con
     const int off = a == 0 ? 1 : (a == 1 ? g.W : g.HW);
     const int idx = a == 0 ? i : (a == 1 ? j : k);
     const int offs = idx > 0 ? off : 0;                    // (idx == 0 is a border cell: fm counts as fc, Pm is not used)
-    fm[a] = flags[os - offs];
+    if constexpr (WORD) fm[a] = fnx::stage_word_minus(sw, a);
+    else fm[a] = flags[os - offs];
     Pm[a] = p[os - offs];
     u[a] = U[ou[a]];
     bm[a] = 1.f; bc[a] = 0.f;
@@ -317,12 +355,12 @@ __global__ __launch_bounds__(BX* BY) void post_projection_kernel(GridDims g, con
     float v = u[a];
     if (SCALE) v = v / sc;                                 // model.py:129-168: the net saw U / s
     {     // velocity_update.py:47-149 (border cells keep their value)
-      const float m_ff = (fc == FNX_FLUID && fm[a] == FNX_FLUID) ? 1.f : 0.f;
+      const float m_ff = (fc == K::fluid && fm[a] == K::fluid) ? 1.f : 0.f;
       float w;
       if (!IS3D) {
-        const float m_fe = (fc == FNX_FLUID && fm[a] == FNX_EMPTY) ? 1.f : 0.f;
-        const float m_ef = (fc == FNX_EMPTY && fm[a] == FNX_FLUID) ? 1.f : 0.f;
-        const float m_nf = (fc == FNX_EMPTY && fm[a] == FNX_EMPTY) ? 1.f : 0.f;
+        const float m_fe = (fc == K::fluid && fm[a] == K::empty) ? 1.f : 0.f;
+        const float m_ef = (fc == K::empty && fm[a] == K::fluid) ? 1.f : 0.f;
+        const float m_nf = (fc == K::empty && fm[a] == K::empty) ? 1.f : 0.f;
         w = ((m_ff * (v - (P - Pm[a])) + m_fe * (v - P)) + m_ef * (v + Pm[a])) + m_nf * 0.f;
       } else {
         w = m_ff * (v - (P - Pm[a]));
@@ -332,7 +370,7 @@ __global__ __launch_bounds__(BX* BY) void post_projection_kernel(GridDims g, con
     if (SCALE) v = v * sc;                                 // model.py:221-223
     {
       const bool zface = a == 2 && (k + g.zoff == 0 || k == 0);
-      const bool wall = (fc == FNX_FLUID || fc == FNX_OBST) && !zface && (fm[a] == FNX_OBST || (fc == FNX_OBST && fm[a] == FNX_FLUID));
+      const bool wall = (fc == K::fluid || fc == K::obst) && !zface && (fm[a] == K::obst || (fc == K::obst && fm[a] == K::fluid));
       v = wall ? 0.f : v;
     }
     if (UBC) {
@@ -368,6 +406,17 @@ __global__ __launch_bounds__(256) void bc_classify_kernel(size_t n, size_t dhw, 
     if (rhoBC && rhoBCInvMask) c |= ((rhoBCInvMask[q] == 1.f) & (__float_as_uint(rhoBC[q]) == 0u)) ? 2u : 0u;
     cls[q] = (unsigned char)c;
   }
+}
+
+// The stage word of every cell of a 3D array (fnx_stage_word.h), from `flags` and the class map: one thread per cell, every plane of the
+// array whatever the compute window (a window's cells read the words of no other cell, but the map is kept for later calls).
+__global__ __launch_bounds__(BX* BY) void stage_word_kernel(GridDims g, const float* __restrict__ flags,
+                                                            const unsigned char* __restrict__ cls, unsigned* __restrict__ word) {
+  const int i = blockIdx.x * BX + threadIdx.x, j = blockIdx.y * BY + threadIdx.y;
+  const int bk = blockIdx.z, b = bk / g.D, k = bk - b * g.D;
+  if (i >= g.W || j >= g.H) return;
+  const size_t base = (size_t)b * g.DHW;
+  word[base + (size_t)k * g.HW + j * g.W + i] = fnx::stage_word_at(flags + base, cls + base, g.W, g.H, g.D, i, j, k);
 }
 
 // The periodic patches of the Jacobi branch (simulate.py:121-128 before the projection, :157-164 after it):
@@ -433,24 +482,31 @@ namespace {
 using Stage2d = void (*)(GridDims, StepPtrs, int, float, float, float);
 using Stage3d = void (*)(GridDims, StepPtrs, int, float, float, float, float, int);
 struct StageKernel { Stage2d k2; Stage3d k3; };
-template <bool Q, bool BC1> Stage3d stage3d_of(bool wall, bool div) {
-  return wall ? (div ? stage3d_kernel<Q, true, true, BC1> : stage3d_kernel<Q, true, false, BC1>)
-              : (div ? stage3d_kernel<Q, false, true, BC1> : stage3d_kernel<Q, false, false, BC1>);
+template <bool Q, bool BC1, bool WORD> Stage3d stage3d_of(bool wall, bool div) {
+  return wall ? (div ? stage3d_kernel<Q, true, true, BC1, WORD> : stage3d_kernel<Q, true, false, BC1, WORD>)
+              : (div ? stage3d_kernel<Q, false, true, BC1, WORD> : stage3d_kernel<Q, false, false, BC1, WORD>);
 }
-StageKernel stage_kernel(bool is3d, const StageOps& o, bool div) {
+template <bool WORD> Stage3d stage3d_of(const StageOps& o, bool div) {
+  return !o.first_bcs ? stage3d_of<false, false, WORD>(o.wall, div)
+         : o.quirks   ? stage3d_of<true, true, WORD>(o.wall, div)
+                      : stage3d_of<false, true, WORD>(o.wall, div);
+}
+// word: the launch has a stage word map (3D): each of the eight 3D instances has its WORD twin
+StageKernel stage_kernel(bool is3d, const StageOps& o, bool div, bool word) {
   if (!is3d) {
     return {o.first_bcs ? (o.wall ? stage2d_div_kernel<true, true> : stage2d_div_kernel<false, true>)
                         : (o.wall ? stage2d_div_kernel<true, false> : stage2d_div_kernel<false, false>), nullptr};
   }
-  return {nullptr, !o.first_bcs ? stage3d_of<false, false>(o.wall, div) : o.quirks ? stage3d_of<true, true>(o.wall, div) : stage3d_of<false, true>(o.wall, div)};
+  return {nullptr, word ? stage3d_of<true>(o, div) : stage3d_of<false>(o, div)};
 }
 }  // namespace
 
 void launch_pre_projection(const GridDims& g, bool is3d, const StageIO& io, const StageOps& o, hipStream_t s) {
+  const unsigned* word = is3d ? io.bc.word : nullptr;
   const StepPtrs P{io.U_adv, io.rho_adv, io.flags, io.bc.UBC, io.bc.UBCInvMask, io.bc.rhoBC, io.bc.rhoBCInvMask, io.U, io.rho, io.div, io.bc.cls,
-                   o.grav ? 1 : 0, o.g[0], o.g[1], o.g[2], o.second_bcs ? 1 : 0};
+                   word, o.grav ? 1 : 0, o.g[0], o.g[1], o.g[2], o.second_bcs ? 1 : 0};
   const dim3 grid = cell_grid(g), block(BX, BY);
-  const StageKernel k = stage_kernel(is3d, o, io.div != nullptr);
+  const StageKernel k = stage_kernel(is3d, o, io.div != nullptr, word != nullptr);
   auto launch = [&](auto kernel, auto... rest) { kernel<<<grid, block, 0, s>>>(g, P, o.buoy ? 1 : 0, o.s[0], o.s[1], rest...); };
   // 3D with `div`: the fused form, divergence for the planes below div_k_end (the caller stages one plane more than it wants divergences
   // of where there is one); without: staging only
@@ -464,10 +520,13 @@ void launch_post_projection(const GridDims& g, bool is3d, const float* p, float*
   const int rd = (bc.cls && rho_bc_applied) ? 1 : 0;
   // (the scaled form is its own instantiation: as a run-time branch it cost the Jacobi step's pass 124 -> 163 us at 512x512x64)
   const bool scaled = scale && p_scaled;
+  // (the stage word serves the step's own 3D tail; the convnet's scaled tail stays on flags and the class map)
+  const unsigned* word = is3d && !scaled ? bc.word : nullptr;
   auto k = scaled ? (is3d ? post_projection_kernel<true, true> : post_projection_kernel<false, true>)
-                  : (is3d ? post_projection_kernel<true, false> : post_projection_kernel<false, false>);
+                  : (is3d ? (word ? post_projection_kernel<true, false, true> : post_projection_kernel<true, false>)
+                          : post_projection_kernel<false, false>);
   k<<<grid, block, 0, s>>>(g, p, U, rho, flags, bc.UBC, bc.UBCInvMask, bc.rhoBC, bc.rhoBCInvMask, bc.cls, rd, scaled ? scale : nullptr,
-                           scaled ? p_scaled : nullptr);
+                           scaled ? p_scaled : nullptr, word);
 }
 
 void launch_periodic_pre(const GridDims& g, bool is3d, const float* U_adv, const float* UBC, const float* UBCInvMask, float* U,
@@ -489,6 +548,11 @@ void launch_bc_classify(const GridDims& g, bool is3d, const BcPtrs& bc, unsigned
   size_t blocks = (n + 255) / 256;
   if (blocks > 8192) blocks = 8192;
   bc_classify_kernel<<<(unsigned)blocks, 256, 0, s>>>(n, (size_t)g.DHW, is3d ? 3 : 2, bc.UBC, bc.UBCInvMask, bc.rhoBC, bc.rhoBCInvMask, cls);
+}
+
+void launch_stage_word(const GridDims& g, const float* flags, const unsigned char* cls, unsigned* word, hipStream_t s) {
+  const dim3 grid((g.W + BX - 1) / BX, (g.H + BY - 1) / BY, g.B * g.D);
+  stage_word_kernel<<<grid, dim3(BX, BY), 0, s>>>(g, flags, cls, word);
 }
 
 }  // namespace fnx

@@ -13,6 +13,7 @@ namespace fnx {
 // In this order, each region rounded up to 256 bytes: the advected density and velocity, the divergence, the 3D Jacobi neighbour mask,
 // the BC class map and the PCG hierarchy (these three are kept between steps), in 2D the viscous velocity that is advected
 // (FnxStepParams.viscosity), then the tail that the advection, the solve, the net and the periodic patches use one after the other.
+// (Behind all of it, where the caller's workspace has FNX_OP_STEP_STATIC's size: the 3D stage word map, see stage_word_plan below.)
 struct StepLayout {
   float *rho2, *U2, *div;
   unsigned char *mask, *cls;      // mask: 3D only
@@ -122,6 +123,20 @@ inline StepPlan step_plan(const FnxStepParams* prm, bool has_rho, bool has_stick
          : p.projection == StepProjection::NET_STICK ? StepTail::STICK_BCS
          : p.stage.periodic ? StepTail::POST_PERIODIC : StepTail::POST;
   return p;
+}
+
+// ---- the 3D stage word map (fnx_stage_word.h) -----------------------------------------------------------------------------------------
+// One uint32 per cell behind the layout's last byte, for callers whose workspace has FNX_OP_STEP_STATIC's size: 3D steps that go by the
+// class map then stage and finish on the word.  It depends on `flags` as well as on the BC arrays, so it is trusted only when the caller
+// says both that the flags are unchanged (bit 0) and that the class map -- with which it is built -- was there already (bit 2).
+enum class StepStageWord { NONE, BUILD, REUSE };
+inline size_t stage_word_offset(const StepLayout& L) { return (L.bytes + 255) & ~(size_t)255; }
+inline size_t stage_word_bytes(size_t cells, bool is3d) { return is3d ? cells * 4 : 0; }
+// ws_bytes: what the caller's workspace holds
+inline StepStageWord stage_word_plan(const FnxStepParams* prm, bool is3d, StepClassMap class_map, const StepLayout& L, size_t cells,
+                                     size_t ws_bytes) {
+  if (!is3d || class_map == StepClassMap::NONE || ws_bytes < stage_word_offset(L) + stage_word_bytes(cells, true)) return StepStageWord::NONE;
+  return (prm->static_flags & 5) == 5 ? StepStageWord::REUSE : StepStageWord::BUILD;
 }
 
 }  // namespace fnx

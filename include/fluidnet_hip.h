@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define FNX_ABI_VERSION 32
+#define FNX_ABI_VERSION 33
 
 enum {
   FNX_OK = 0,
@@ -67,7 +67,11 @@ typedef struct FnxGrid {
 
 /* Workspace sizing. */
 enum { FNX_OP_ADVECT_SCALAR = 0, FNX_OP_ADVECT_VEL = 1, FNX_OP_JACOBI = 2, FNX_OP_STEP = 3, FNX_OP_FLUIDNET = 4,
-       FNX_OP_ADVECT_STEP = 5 };
+       FNX_OP_ADVECT_STEP = 5,
+       FNX_OP_STEP_STATIC = 6   /* ABI 33: FNX_OP_STEP plus, in 3D, 4 bytes per cell for the stage word map that fnx_simulate_step keeps
+                                   behind the step's layout when flags and BC arrays are promised static (FnxStepParams.static_flags).
+                                   FNX_OP_STEP stays what it was and stays enough for every call; in 2D the two are equal */
+};
 size_t fnx_workspace_bytes(const FnxGrid* g, int op);
 
 const char* fnx_last_error(void);
@@ -386,6 +390,13 @@ typedef struct FnxStepParams {
                                  bit 3 (method 2): the PCG multigrid hierarchy in this workspace was built by an earlier call for
                                         these flags AND this FnxGrid.ref_quirks (the hierarchy depends on both) -- reused only
                                         together with bit 0.
+                                 ABI 33, 3D with bit 1 and a workspace of at least fnx_workspace_bytes(FNX_OP_STEP_STATIC) bytes:
+                                 the stage before the projection and the pass after it (methods 0, 2, 3, 4) read one uint32 per cell,
+                                 kept behind the step's layout, instead of seven `flags` values and seven class bytes: the flag
+                                 codes and class bits of the cell and its six neighbours.  It is built in every call that does
+                                 not set both bit 0 and bit 2 (it depends on the flags and on the BC arrays), and the results are
+                                 bit for bit those of the smaller workspace.  The promises speak of the previous call with the
+                                 same `ws` AND the same `ws_bytes`.
                                  The step workspace (fnx_workspace_bytes FNX_OP_STEP) holds that hierarchy for every method:
                                  ~2 bytes per cell + 16 bytes per coarse cell (~4.3 B per cell in 3D, ~2.7 in 2D), kept between
                                  steps; the PCG vectors (~26 B per cell) share the scratch tail with the advection and the CNN,

@@ -12,7 +12,10 @@ cases, in 2D and in 3D where the stage exists there: methods 0 to 4 (untrained p
 density, with and without BC arrays, static_flags 0 then 15 on a second call, periodic 3, 5 and 7, viscosity, flags_stick, vorticity
 confinement, gravity_scale, correct_scalar, the reference's 3D quirks; then fnx_pre_projection on a plane range with the divergence (with
 and without wall BCs, with the quirks) and on the whole grid with the confinement, each followed by fnx_post_projection.  Together the
-cases launch each of the sixteen stage-kernel instances.  Every input comes from a seeded generator on the host."""
+cases launch each of the sixteen stage-kernel instances.  The workspace is FNX_OP_STEP_STATIC's where the library has that op (a build
+from before it: FNX_OP_STEP's), so in 3D the calls that go by the class map also build the stage word map (stage_word_kernel) and run the
+WORD twins of the stage and post-projection kernels; the class-map grid adds a second call that promises the BC arrays but not the flags
+(static_flags 6: the word is built again, the class map is not).  Every input comes from a seeded generator on the host."""
 import argparse
 import csv
 import ctypes
@@ -200,11 +203,12 @@ def run(lib, digest):
     import torch
     for shape, sparse in (((2, 1, 40, 70), False), ((1, 9, 20, 66), False), ((2, 6, 21, 66), True)):
         F = Fields(lib, shape, sparse_bc=sparse)
-        cases = step_cases(F.is3d) if not sparse else [(f"class_map_method{m}", dict(method=m), {}, (2, 15), {}) for m in range(5)]
+        cases = step_cases(F.is3d) if not sparse else ([(f"class_map_method{m}", dict(method=m), {}, (2, 15), {}) for m in range(5)] +
+                                                       [("class_map_flags_not_promised", dict(method=0), {}, (2, 6), {})])
         for name, prm_kw, st_kw, static, grid_kw in cases:
             g, prm = F.grid(**grid_kw), params(**prm_kw)
             t, st = F.fresh(net=prm.method in (1, 3), **st_kw)
-            ws_bytes = lib.fnx_workspace_bytes(ctypes.byref(g), 3)
+            ws_bytes = lib.fnx_workspace_bytes(ctypes.byref(g), 6) or lib.fnx_workspace_bytes(ctypes.byref(g), 3)   # FNX_OP_STEP_STATIC, _STEP
             ws = torch.zeros(ws_bytes, dtype=torch.uint8, device=F.dev)
             # a second call only where it differs from the first (its promises) or where the bits of two steps are wanted
             for flags in static if digest or static[1] != static[0] else static[:1]:
