@@ -3,7 +3,7 @@
 Mantaflow data set, on scenes generated while training (fluidnet_cxx_amd/training.py; with --depth fluidnet_cxx_amd/training3d.py).
 
     python examples/train.py [--res 128] [--batch 64] [--iters 1000] [--seed 0] [--out convModel.pth] [--lr 5e-5] [--eval-every 50]
-                             [--no-long-term] [--resume CKPT] [--report FILE] [--depth N] [--model {ScaleNet,FluidNet}]
+                             [--no-long-term] [--resume CKPT] [--report FILE] [--depth N] [--model {ScaleNet,FluidNet,FluidNet3D}]
 
 Writes a checkpoint {'state_dict', 'optimizer', 'mconf', 'it', ...} that `FluidNet.load_state_dict` takes and
 `examples/plume.py --method convnet --weights` runs.  With --report the loss curve, the held-out ratio divL2(net's U) / divL2(U before
@@ -13,7 +13,8 @@ the projection) and the number of Jacobi sweeps that reach the same held-out div
 ScaleNet; `examples/plume.py` picks the net from the checkpoint's mconf.
 
 `--depth N` (N >= 4) trains the 3D net on a N x res x res grid instead (the defaults become --res 64 --batch 4); its checkpoint goes to
-`examples/plume.py --depth N --method convnet --weights3d`.  The report then has no Jacobi line."""
+`examples/plume.py --depth N --method convnet --weights3d`.  The report then has no Jacobi line.  `--depth N --model FluidNet3D` trains the
+Conv3d 16-channel bank net there (N and res multiples of 4); the checkpoint's mconf carries the model, so the same plume command runs it."""
 import argparse
 import os
 import sys
@@ -38,10 +39,14 @@ def parse_args(argv=None):
     ap.add_argument("--resume", default=None, metavar="CKPT")
     ap.add_argument("--report", default=None, metavar="FILE")
     ap.add_argument("--depth", type=int, default=None, metavar="N", help="train the 3D net on N x res x res cells (N >= 4)")
-    ap.add_argument("--model", choices=("ScaleNet", "FluidNet"), default="ScaleNet", help="FluidNet: the 16-channel bank net (2D only)")
+    ap.add_argument("--model", choices=("ScaleNet", "FluidNet", "FluidNet3D"), default="ScaleNet",
+                    help="FluidNet: the 16-channel bank net (2D only); FluidNet3D: its Conv3d counterpart (with --depth)")
     a = ap.parse_args(argv)
-    if a.depth is not None and a.model != "ScaleNet":
-        ap.error("--model FluidNet is 2D only (the reference asserts it); --depth trains the 3D ScaleNet")
+    if a.depth is not None and a.model == "FluidNet":
+        ap.error("--model FluidNet is 2D only (the reference asserts it); --depth trains the 3D ScaleNet, or the Conv3d bank net with "
+                 "--model FluidNet3D")
+    if a.depth is None and a.model == "FluidNet3D":
+        ap.error("--model FluidNet3D is 3D only: give --depth N (without --depth, --model FluidNet trains the 2D bank net)")
     if a.depth is not None and a.depth < 4:
         ap.error("--depth must be at least 4 (the net's three scales need 4 planes); without --depth the 2D net is trained")
     is3d = a.depth is not None
@@ -54,14 +59,15 @@ def main(argv=None):
     a = parse_args(argv)
     is3d = a.depth is not None
     if is3d:
-        from fluidnet_cxx_amd.training3d import MCONF3D_DEFAULTS, evaluate3d, train3d
+        from fluidnet_cxx_amd.training3d import MCONF3D_DEFAULTS, evaluate3d, train3d, train_bank3d
     mconf = dict(MCONF3D_DEFAULTS if is3d else MCONF_DEFAULTS, lr=a.lr, model=a.model)
     if a.no_long_term:
         mconf["divLongTermLambda"] = 0.0
     tconf = dict(res=a.res, batch=a.batch, iters=a.iters, seed=a.seed, evalEvery=a.eval_every)
     t0 = time.time()
     if is3d:
-        run = train3d(mconf, dict(tconf, D=a.depth), torch.device("cuda"), out=a.out, resume=a.resume, log=print)
+        run = (train_bank3d if a.model == "FluidNet3D" else train3d)(mconf, dict(tconf, D=a.depth), torch.device("cuda"), out=a.out,
+                                                                     resume=a.resume, log=print)
     else:
         run = train(mconf, tconf, torch.device("cuda"), out=a.out, resume=a.resume, log=print)
     torch.cuda.synchronize()

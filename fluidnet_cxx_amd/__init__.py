@@ -4,6 +4,7 @@
     from fluidnet_cxx_amd import FluidNetTrain                 # the same net with a native backward pass (2D)
     from fluidnet_cxx_amd import FluidNetBankTrain             # ... for the 16-channel bank net, mconf['model'] = 'FluidNet' (2D)
     from fluidnet_cxx_amd import FluidNetTrain3D               # ... and its Conv3d counterpart (3D grids)
+    from fluidnet_cxx_amd import FluidNetBankTrain3D           # ... and the Conv3d bank net, mconf['model'] = 'FluidNet3D'
     from fluidnet_cxx_amd.training import train, SceneSampler  # the training loop on scenes generated on the device (2D)
     from fluidnet_cxx_amd.training3d import train3d, SceneSampler3D   # ... and in 3D
 
@@ -27,6 +28,8 @@ def __getattr__(name):
         return importlib.import_module(".train", __name__).FluidNetTrain
     if name == "FluidNetBankTrain":
         return importlib.import_module(".train", __name__).FluidNetBankTrain
+    if name == "FluidNetBankTrain3D":
+        return importlib.import_module(".train", __name__).FluidNetBankTrain3D
     if name == "FluidNetTrain3D":
         return importlib.import_module(".train3d", __name__).FluidNetTrain3D
     raise AttributeError(name)

@@ -578,11 +578,32 @@ struct BankApi {
   size_t (*ws_bytes)(const FnxGrid*, int);
   int (*forward)(const FnxGrid*, const void*, const float*, float*, int, void*, size_t, void*);
   int (*whole_forward)(const FnxGrid*, const void*, const float*, float, float*, float*, int, void*, size_t, void*);
+  // training (fnx_banknet_train.hip, fnx_banknet3d_train.hip)
+  const char* pack_t_name;
+  size_t (*packed_t_bytes)(void);
+  int (*pack_t)(const float*, void*, void*);
+  size_t (*tape_floats)(const FnxGrid&);
+  size_t (*backward_ws_bytes)(const FnxGrid*);
+  int (*forward_train)(const FnxGrid*, const void*, const float*, float*, float*, int, void*);
+  int (*backward)(const FnxGrid*, const void*, const float*, const float*, const float*, float*, int, void*, size_t, void*);
+  size_t (*train_ws_bytes)(const FnxGrid*);
+  int (*whole_forward_train)(const FnxGrid*, const void*, const float*, float, float*, float*, float*, float*, float*, int, void*, size_t,
+                             void*);
+  int (*whole_backward)(const FnxGrid*, const void*, const float*, const float*, const float*, const float*, const float*, float*, int, void*,
+                        size_t, void*);
 };
+static size_t bank2d_tape_floats(const FnxGrid& g) { return fnx_banknet_tape_layout(&g, nullptr); }
+static size_t bank3d_tape_floats(const FnxGrid& g) { return fnx_banknet3d_tape_layout(&g, nullptr); }
 static const BankApi BANK2D = {"banknet_pack", fnx_banknet_weight_floats, fnx_banknet_packed_bytes, fnx_banknet_pack, fnx_banknet_ws_bytes,
-                               fnx_banknet_forward, fnx_fluidnet_bank_forward};
+                               fnx_banknet_forward, fnx_fluidnet_bank_forward,
+                               "banknet_pack_t", fnx_banknet_packed_t_bytes, fnx_banknet_pack_t, bank2d_tape_floats,
+                               fnx_banknet_backward_ws_bytes, fnx_banknet_forward_train, fnx_banknet_backward,
+                               fnx_fluidnet_bank_train_ws_bytes, fnx_fluidnet_bank_forward_train, fnx_fluidnet_bank_backward};
 static const BankApi BANK3D = {"banknet3d_pack", fnx_banknet3d_weight_floats, fnx_banknet3d_packed_bytes, fnx_banknet3d_pack,
-                               fnx_banknet3d_ws_bytes, fnx_banknet3d_forward, fnx_fluidnet_bank3d_forward};
+                               fnx_banknet3d_ws_bytes, fnx_banknet3d_forward, fnx_fluidnet_bank3d_forward,
+                               "banknet3d_pack_t", fnx_banknet3d_packed_t_bytes, fnx_banknet3d_pack_t, bank3d_tape_floats,
+                               fnx_banknet3d_backward_ws_bytes, fnx_banknet3d_forward_train, fnx_banknet3d_backward,
+                               fnx_fluidnet_bank3d_train_ws_bytes, fnx_fluidnet_bank3d_forward_train, fnx_fluidnet_bank3d_backward};
 
 static Tensor bank_pack(const BankApi* net, Tensor blob) {
   TORCH_CHECK(blob.is_cuda() && blob.scalar_type() == at::kFloat && blob.is_contiguous(), "weights blob must be a contiguous float32 GPU tensor");
@@ -597,7 +618,6 @@ static void check_bank_image(const BankApi* net, const Tensor& packed) {
   TORCH_CHECK(packed.is_cuda() && packed.is_contiguous() && (size_t)packed.nbytes() == net->packed_bytes(),
               "packed must be the ", net->packed_bytes(), "-byte image from ", net->pack_name, " (got ", packed.nbytes(), " bytes)");
 }
-static void check_banknet_image(const Tensor& packed) { check_bank_image(&BANK2D, packed); }
 
 static Tensor bank_forward(const BankApi* net, Tensor packed, Tensor x, const std::string& precision_mode) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.is_contiguous(), "x must be a contiguous float32 GPU tensor");
@@ -804,23 +824,21 @@ Tensor fluidnet_backward(bool is3d, Tensor packed_t, Tensor flags, Tensor scale,
   return grad;
 }
 
-// ---- training of the bank net (fnx_banknet_train.hip): the bodies above with the bank entry points; a grid the C ABI refuses gets a
-// token tape and workspace, so that the C ABI's text is what is raised ----------------------------------------------------------------
-static size_t bank_tape_floats(const FnxGrid& g) { return fnx_banknet_tape_layout(&g, nullptr); }
-static void check_banknet_image_t(const Tensor& packed_t, const Tensor& like) {
+// ---- training of the bank nets (fnx_banknet_train.hip, fnx_banknet3d_train.hip): the bodies above with the net's entry points; a grid the
+// C ABI refuses gets a token tape and workspace, so that the C ABI's text is what is raised ---------------------------------------------
+static void check_bank_image_t(const BankApi* net, const Tensor& packed_t, const Tensor& like) {
   TORCH_CHECK(packed_t.is_cuda() && packed_t.is_contiguous() && packed_t.get_device() == like.get_device() &&
-              (size_t)packed_t.nbytes() == fnx_banknet_packed_t_bytes(),
-              "packed_t must be the ", fnx_banknet_packed_t_bytes(), "-byte image from banknet_pack_t on the input's device (got ", packed_t.nbytes(),
-              " bytes)");
+              (size_t)packed_t.nbytes() == net->packed_t_bytes(),
+              "packed_t must be the ", net->packed_t_bytes(), "-byte image from ", net->pack_t_name, " on the input's device (got ",
+              packed_t.nbytes(), " bytes)");
 }
 
-Tensor banknet_pack_t(Tensor blob) {
+static Tensor bank_pack_t(const BankApi* net, Tensor blob) {
   TORCH_CHECK(blob.is_cuda() && blob.scalar_type() == at::kFloat && blob.is_contiguous(), "weights blob must be a contiguous float32 GPU tensor");
-  TORCH_CHECK((size_t)blob.numel() == fnx_banknet_weight_floats(), "weights blob has ", blob.numel(), " floats, expected ",
-              fnx_banknet_weight_floats());
+  TORCH_CHECK((size_t)blob.numel() == net->weight_floats(), "weights blob has ", blob.numel(), " floats, expected ", net->weight_floats());
   c10::hip::HIPGuard guard(blob.get_device());
-  Tensor packed = at::zeros({(int64_t)fnx_banknet_packed_t_bytes()}, blob.options().dtype(at::kByte));
-  check_status(fnx_banknet_pack_t(blob.data_ptr<float>(), packed.data_ptr(), cur_stream(blob)));
+  Tensor packed = at::zeros({(int64_t)net->packed_t_bytes()}, blob.options().dtype(at::kByte));
+  check_status(net->pack_t(blob.data_ptr<float>(), packed.data_ptr(), cur_stream(blob)));
   return packed;
 }
 
@@ -833,81 +851,93 @@ std::vector<py::tuple> banknet_tape_layout(int64_t B, int64_t H, int64_t W) {
   for (const FnxTapeEntry& t : e) out.push_back(py::make_tuple(std::string(t.name), (int64_t)t.offset, t.C, t.H, t.W));
   return out;
 }
+// -> (name, offset, C, D, H, W) per tape entry
+std::vector<py::tuple> banknet3d_tape_layout(int64_t B, int64_t D, int64_t H, int64_t W) {
+  const FnxGrid g = make_grid(B, D, H, W, true);
+  std::vector<FnxTapeEntry3D> e(fnx_banknet3d_tape_entries());
+  if (fnx_banknet3d_tape_layout(&g, e.data()) == 0) check_status(FNX_EINVAL);
+  std::vector<py::tuple> out;
+  for (const FnxTapeEntry3D& t : e) out.push_back(py::make_tuple(std::string(t.name), (int64_t)t.offset, t.C, t.D, t.H, t.W));
+  return out;
+}
 
-// x (B,2,H,W) -> p, tape
-std::vector<Tensor> banknet_forward_train(Tensor packed, Tensor x, const std::string& precision_mode) {
+// x (B,2,[D,]H,W) -> p, tape
+static std::vector<Tensor> bank_forward_train(const BankApi* net, Tensor packed, Tensor x, const std::string& precision_mode) {
   const FnxGrid g = grid_of_net_tensor(x, "x");
   TORCH_CHECK(x.size(1) == 2, "x must have 2 channels");
-  check_banknet_image(packed);
+  check_bank_image(net, packed);
   c10::hip::HIPGuard guard(x.get_device());
   std::vector<int64_t> osz = x.sizes().vec(); osz[1] = 1;
   Tensor p = at::empty(osz, x.options());
-  const size_t floats = bank_tape_floats(g);
+  const size_t floats = net->tape_floats(g);
   Tensor tape = at::empty({(int64_t)(floats ? floats : 1)}, x.options());
-  check_status(fnx_banknet_forward_train(&g, packed.data_ptr(), x.data_ptr<float>(), p.data_ptr<float>(), tape.data_ptr<float>(),
-                                         precision_of(precision_mode), cur_stream(x)));
+  check_status(net->forward_train(&g, packed.data_ptr(), x.data_ptr<float>(), p.data_ptr<float>(), tape.data_ptr<float>(),
+                                  precision_of(precision_mode), cur_stream(x)));
   return {p, tape};
 }
 
-// grad_p (B,1,H,W), the forward's tape and x -> the gradient in the blob's layout
-Tensor banknet_backward(Tensor packed_t, Tensor x, Tensor grad_p, Tensor tape, const std::string& precision_mode) {
+// grad_p (B,1,[D,]H,W), the forward's tape and x -> the gradient in the blob's layout
+static Tensor bank_backward(const BankApi* net, Tensor packed_t, Tensor x, Tensor grad_p, Tensor tape, const std::string& precision_mode) {
   const FnxGrid g = grid_of_net_tensor(grad_p, "grad_p");
   grid_of_net_tensor(x, "x");
   TORCH_CHECK(grad_p.size(1) == 1 && x.size(1) == 2 && x.dim() == grad_p.dim() && x.size(0) == grad_p.size(0) &&
-              x.size(x.dim() - 2) == grad_p.size(x.dim() - 2) && x.size(x.dim() - 1) == grad_p.size(x.dim() - 1),
+              x.numel() == 2 * grad_p.numel() && x.size(x.dim() - 2) == grad_p.size(x.dim() - 2) &&
+              x.size(x.dim() - 1) == grad_p.size(x.dim() - 1),
               "grad_p (1 channel) and x (2 channels) must share their grid");
-  check_banknet_image_t(packed_t, grad_p);
-  const size_t floats = bank_tape_floats(g);
+  check_bank_image_t(net, packed_t, grad_p);
+  const size_t floats = net->tape_floats(g);
   check_tape(tape, floats);
   c10::hip::HIPGuard guard(grad_p.get_device());
-  Tensor grad = at::empty({(int64_t)fnx_banknet_weight_floats()}, grad_p.options());
-  const size_t bytes = std::max<size_t>(floats ? fnx_banknet_backward_ws_bytes(&g) : 0, 256);
+  Tensor grad = at::empty({(int64_t)net->weight_floats()}, grad_p.options());
+  const size_t bytes = std::max<size_t>(floats ? net->backward_ws_bytes(&g) : 0, 256);
   Tensor ws = at::empty({(int64_t)bytes}, grad_p.options().dtype(at::kByte));
-  check_status(fnx_banknet_backward(&g, packed_t.data_ptr(), x.data_ptr<float>(), grad_p.data_ptr<float>(), tape.data_ptr<float>(),
-                                    grad.data_ptr<float>(), precision_of(precision_mode), ws.data_ptr(), bytes, cur_stream(grad_p)));
+  check_status(net->backward(&g, packed_t.data_ptr(), x.data_ptr<float>(), grad_p.data_ptr<float>(), tape.data_ptr<float>(),
+                             grad.data_ptr<float>(), precision_of(precision_mode), ws.data_ptr(), bytes, cur_stream(grad_p)));
   return grad;
 }
 
-// input (B,5,1,H,W) = [p, U, flags, density] -> p, U, tape, s (B), flags (B,1,1,H,W)
-std::vector<Tensor> fluidnet_bank_forward_train(Tensor packed, Tensor input, double normalize_threshold, const std::string& precision_mode) {
+// input (B,5|6,D,H,W) = [p, U, flags, density] -> p, U, tape, s (B), flags (B,1,D,H,W)
+static std::vector<Tensor> bank_whole_forward_train(const BankApi* net, Tensor packed, Tensor input, double normalize_threshold,
+                                                    const std::string& precision_mode) {
   check_field(input, "input");
   TORCH_CHECK(input.size(1) == 5 || input.size(1) == 6, "input must have 5 (2D) or 6 (3D) channels [p, U, flags, density]");
   const FnxGrid g = make_grid(input.size(0), input.size(2), input.size(3), input.size(4), input.size(1) == 6);
-  check_banknet_image(packed);
+  check_bank_image(net, packed);
   c10::hip::HIPGuard guard(input.get_device());
   Tensor p = at::empty({g.B, 1, g.D, g.H, g.W}, input.options());
   Tensor U = at::empty({g.B, g.is3D ? 3 : 2, g.D, g.H, g.W}, input.options());
   Tensor flags = at::empty({g.B, 1, g.D, g.H, g.W}, input.options());
   Tensor scale = at::empty({g.B}, input.options());
-  const size_t floats = bank_tape_floats(g);
-  const size_t bytes = std::max<size_t>(floats ? fnx_fluidnet_bank_train_ws_bytes(&g) : 0, 256);
+  const size_t floats = net->tape_floats(g);
+  const size_t bytes = std::max<size_t>(floats ? net->train_ws_bytes(&g) : 0, 256);
   Tensor tape = at::empty({(int64_t)(floats ? floats : 1)}, input.options());
   Tensor ws = at::empty({(int64_t)bytes}, input.options().dtype(at::kByte));
-  check_status(fnx_fluidnet_bank_forward_train(&g, packed.data_ptr(), input.data_ptr<float>(), (float)normalize_threshold, p.data_ptr<float>(),
-                                               U.data_ptr<float>(), flags.data_ptr<float>(), scale.data_ptr<float>(), tape.data_ptr<float>(),
-                                               precision_of(precision_mode), ws.data_ptr(), bytes, cur_stream(input)));
+  check_status(net->whole_forward_train(&g, packed.data_ptr(), input.data_ptr<float>(), (float)normalize_threshold, p.data_ptr<float>(),
+                                        U.data_ptr<float>(), flags.data_ptr<float>(), scale.data_ptr<float>(), tape.data_ptr<float>(),
+                                        precision_of(precision_mode), ws.data_ptr(), bytes, cur_stream(input)));
   return {p, U, tape, scale, flags};
 }
 
-// grad_p (B,1,1,H,W), grad_U (B,2,1,H,W), flags and scale of the forward -> the gradient in the blob's layout
-Tensor fluidnet_bank_backward(Tensor packed_t, Tensor flags, Tensor scale, Tensor grad_p, Tensor grad_U, Tensor tape,
-                              const std::string& precision_mode) {
+// grad_p (B,1,D,H,W), grad_U (B,2|3,D,H,W), flags and scale of the forward -> the gradient in the blob's layout
+static Tensor bank_whole_backward(const BankApi* net, Tensor packed_t, Tensor flags, Tensor scale, Tensor grad_p, Tensor grad_U, Tensor tape,
+                                  const std::string& precision_mode) {
   check_field(grad_p, "grad_p"); check_field(grad_U, "grad_U"); check_field(flags, "flags");
-  TORCH_CHECK(grad_p.size(1) == 1 && grad_U.size(1) == 2 && flags.size(1) == 1, "grad_p and flags must have 1 channel, grad_U 2");
+  const int64_t nc = net == &BANK3D ? 3 : 2;
+  TORCH_CHECK(grad_p.size(1) == 1 && grad_U.size(1) == nc && flags.size(1) == 1, "grad_p and flags must have 1 channel, grad_U ", nc);
   TORCH_CHECK(grad_U.size(0) == grad_p.size(0) && grad_U.size(2) == grad_p.size(2) && grad_U.size(3) == grad_p.size(3) &&
               grad_U.size(4) == grad_p.size(4) && flags.sizes() == grad_p.sizes(), "grad_p, grad_U and flags must share their grid");
   const FnxGrid g = make_grid(grad_p.size(0), grad_p.size(2), grad_p.size(3), grad_p.size(4), grad_p.size(2) > 1);
-  check_banknet_image_t(packed_t, grad_p);
+  check_bank_image_t(net, packed_t, grad_p);
   TORCH_CHECK(scale.is_cuda() && scale.scalar_type() == at::kFloat && scale.is_contiguous() && scale.numel() == g.B, "scale must hold B floats on the GPU");
-  const size_t floats = bank_tape_floats(g);
+  const size_t floats = net->tape_floats(g);
   check_tape(tape, floats);
   c10::hip::HIPGuard guard(grad_p.get_device());
-  Tensor grad = at::empty({(int64_t)fnx_banknet_weight_floats()}, grad_p.options());
-  const size_t bytes = std::max<size_t>(floats ? fnx_fluidnet_bank_train_ws_bytes(&g) : 0, 256);
+  Tensor grad = at::empty({(int64_t)net->weight_floats()}, grad_p.options());
+  const size_t bytes = std::max<size_t>(floats ? net->train_ws_bytes(&g) : 0, 256);
   Tensor ws = at::empty({(int64_t)bytes}, grad_p.options().dtype(at::kByte));
-  check_status(fnx_fluidnet_bank_backward(&g, packed_t.data_ptr(), flags.data_ptr<float>(), scale.data_ptr<float>(), grad_p.data_ptr<float>(),
-                                          grad_U.data_ptr<float>(), tape.data_ptr<float>(), grad.data_ptr<float>(), precision_of(precision_mode),
-                                          ws.data_ptr(), bytes, cur_stream(grad_p)));
+  check_status(net->whole_backward(&g, packed_t.data_ptr(), flags.data_ptr<float>(), scale.data_ptr<float>(), grad_p.data_ptr<float>(),
+                                   grad_U.data_ptr<float>(), tape.data_ptr<float>(), grad.data_ptr<float>(), precision_of(precision_mode),
+                                   ws.data_ptr(), bytes, cur_stream(grad_p)));
   return grad;
 }
 
@@ -1371,15 +1401,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("banknet3d_forward", in_dim(&BANK3D, &bank_forward), py::arg("packed"), py::arg("x"), py::arg("precision_mode") = "fp32", NoGil());
   m.def("fluidnet_bank3d_forward", in_dim(&BANK3D, &whole_forward), py::arg("packed"), py::arg("input"), py::arg("normalize_threshold"),
         py::arg("precision_mode") = "fp32", NoGil());
-  m.def("banknet_pack_t", &banknet_pack_t, py::arg("blob"), NoGil());
   m.def("banknet_tape_layout", &banknet_tape_layout, py::arg("B"), py::arg("H"), py::arg("W"));
-  m.def("banknet_forward_train", &banknet_forward_train, py::arg("packed"), py::arg("x"), py::arg("precision_mode") = "fp32", NoGil());
-  m.def("banknet_backward", &banknet_backward, py::arg("packed_t"), py::arg("x"), py::arg("grad_p"), py::arg("tape"),
-        py::arg("precision_mode") = "fp32", NoGil());
-  m.def("fluidnet_bank_forward_train", &fluidnet_bank_forward_train, py::arg("packed"), py::arg("input"), py::arg("normalize_threshold"),
-        py::arg("precision_mode") = "fp32", NoGil());
-  m.def("fluidnet_bank_backward", &fluidnet_bank_backward, py::arg("packed_t"), py::arg("flags"), py::arg("scale"), py::arg("grad_p"),
-        py::arg("grad_U"), py::arg("tape"), py::arg("precision_mode") = "fp32", NoGil());
+  m.def("banknet3d_tape_layout", &banknet3d_tape_layout, py::arg("B"), py::arg("D"), py::arg("H"), py::arg("W"));
+  for (const BankApi* net : {&BANK2D, &BANK3D}) {
+    const std::string n3 = net == &BANK3D ? "3d" : "";
+    m.def(("banknet" + n3 + "_pack_t").c_str(), in_dim(net, &bank_pack_t), py::arg("blob"), NoGil());
+    m.def(("banknet" + n3 + "_forward_train").c_str(), in_dim(net, &bank_forward_train), py::arg("packed"), py::arg("x"),
+          py::arg("precision_mode") = "fp32", NoGil());
+    m.def(("banknet" + n3 + "_backward").c_str(), in_dim(net, &bank_backward), py::arg("packed_t"), py::arg("x"), py::arg("grad_p"),
+          py::arg("tape"), py::arg("precision_mode") = "fp32", NoGil());
+    m.def(("fluidnet_bank" + n3 + "_forward_train").c_str(), in_dim(net, &bank_whole_forward_train), py::arg("packed"), py::arg("input"),
+          py::arg("normalize_threshold"), py::arg("precision_mode") = "fp32", NoGil());
+    m.def(("fluidnet_bank" + n3 + "_backward").c_str(), in_dim(net, &bank_whole_backward), py::arg("packed_t"), py::arg("flags"),
+          py::arg("scale"), py::arg("grad_p"), py::arg("grad_U"), py::arg("tape"), py::arg("precision_mode") = "fp32", NoGil());
+  }
   m.def("simulate_step_", &simulate_step_, py::arg("p"), py::arg("U"), py::arg("flags"), py::arg("density"), py::arg("UBC"),
         py::arg("UBCInvMask"), py::arg("densityBC"), py::arg("densityBCInvMask"), py::arg("net"), py::arg("dt"),
         py::arg("maccormack_strength"), py::arg("sample_outside_fluid"), py::arg("buoyancy_scale"), py::arg("gravity_vec"),

@@ -1,5 +1,5 @@
 // What the units of the 16-channel bank net share (fnx_banknet.hip: 2D inference; fnx_banknet_train.hip: 2D tape forward and backward;
-// fnx_banknet3d.hip: 3D inference).  All three: the pieces of the weight packing and the checks every entry point makes before the
+// fnx_banknet3d.hip: 3D inference; fnx_banknet3d_train.hip: 3D tape forward and backward, through fnx_banknet3d_tile.h).  All of them: the pieces of the weight packing and the checks every entry point makes before the
 // device.  The 2D units: the blob's and the packed image's offsets, the geometry of a level tile, the 3x3 bank convolution on
 // v_mfma_f32_16x16x4_f32 and the body of a level kernel (with a compile-time switch that also writes the tape).
 // The layout of the kernels and of the MFMA operands is described at the top of fnx_banknet.hip.

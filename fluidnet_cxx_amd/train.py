@@ -11,8 +11,11 @@ model.py:177-209; csrc/fnx_banknet_train.hip): the twelve parameters `conv1`, `c
 `convOut`, and `net.bank(x)` where the ScaleNet has `net.multiScale(x)`.  Both nets share the autograd functions; an `_Api` names the
 extension's entry points of each.
 
+`FluidNetBankTrain3D` is that for the Conv3d bank net (mconf['model'] = 'FluidNet3D'; csrc/fnx_banknet3d_train.hip).
+
 Scope: the 2D configurations `FluidNet` accepts, precision modes fp32 / fp32_f4 / fp32_f2 / fp32_direct, gradients with respect to
-the parameters.  3D, the bf16 modes, dropout and a gradient with respect to input_ raise.
+the parameters.  3D (but for FluidNetBankTrain3D and train3d.FluidNetTrain3D), the bf16 modes, dropout and a gradient with respect to
+input_ raise.
 """
 from collections import OrderedDict
 
@@ -40,14 +43,15 @@ def _split(blob, shapes):
     return grads
 
 
-# the bank net's entry points under the names the ScaleNet's have in _Api
-_BANK_NAMES = {"scalenet#_pack_t": "banknet_pack_t", "multiscale#_forward_train": "banknet_forward_train",
-               "multiscale#_backward": "banknet_backward", "fluidnet#_forward_train": "fluidnet_bank_forward_train",
-               "fluidnet#_backward": "fluidnet_bank_backward"}
+# the bank nets' entry points under the names the ScaleNet's have in _Api ('#': nothing in 2D, '3d' in 3D, for either net)
+_BANK_NAMES = {"scalenet#_pack_t": "banknet#_pack_t", "multiscale#_forward_train": "banknet#_forward_train",
+               "multiscale#_backward": "banknet#_backward", "fluidnet#_forward_train": "fluidnet_bank#_forward_train",
+               "fluidnet#_backward": "fluidnet_bank#_backward", "pack": "banknet#_pack", "net_forward": "banknet#_forward",
+               "fluidnet_forward": "fluidnet_bank#_forward"}
 
 
 class _Api:
-    """what differs between the 2D net, the 3D net and the 2D bank net: the extension's entry points and the number of velocity
+    """what differs between the 2D net, the 3D net and the two bank nets: the extension's entry points and the number of velocity
     components (only the dimension and the model are state, so a module that holds one copies and pickles as before)"""
 
     bank = False                         # (a class default: an _Api pickled before the bank net existed has no such attribute)
@@ -57,20 +61,20 @@ class _Api:
 
     def _fn(self, name):
         if self.bank:
-            return getattr(ext, _BANK_NAMES[name])
+            name = _BANK_NAMES[name]
         return getattr(ext, name.replace("#", "" if self.ndim == 2 else "3d"))
 
     def pack(self, blob):
-        fwd = ext.banknet_pack(blob) if self.bank else ext.scalenet_pack(blob, self.ndim == 3)
+        fwd = self._fn("pack")(blob) if self.bank else ext.scalenet_pack(blob, self.ndim == 3)
         return fwd, self._fn("scalenet#_pack_t")(blob)
 
     def net_forward(self, packed, x, mode):
         """the inference launches of the net alone"""
-        return ext.banknet_forward(packed, x, mode) if self.bank else ext.multiscale_forward(packed, x, mode, [])
+        return self._fn("net_forward")(packed, x, mode) if self.bank else ext.multiscale_forward(packed, x, mode, [])
 
     def fluidnet_forward(self, packed, input_, threshold, mode):
         """the inference launches of FluidNet.forward"""
-        return (ext.fluidnet_bank_forward if self.bank else ext.fluidnet_forward)(packed, input_, threshold, mode)
+        return (self._fn("fluidnet_forward") if self.bank else ext.fluidnet_forward)(packed, input_, threshold, mode)
 
     def net_backward(self, packed_t, x, gp, tape, mode):
         """(the bank net's backward reads the net's input again: conv1's weight gradient)"""
@@ -182,12 +186,12 @@ class _MultiScaleTrain(torch.nn.Module):
 
 def _refuse_bank3d(mconf, name):
     if mconf.get("model", "ScaleNet") == "FluidNet3D":
-        raise ValueError(f"{name}: training the 'FluidNet3D' model is not built (the Conv3d bank net has an inference forward only, "
-                         "FluidNet(mconf); the trainers take the ScaleNet and the 2D 'FluidNet' bank net)")
+        raise ValueError(f"{name}: training the 'FluidNet3D' model is not built into this class or trainer: FluidNetBankTrain3D(mconf) "
+                         "is the Conv3d bank net's training module and training3d.train_bank3d its trainer")
 
 
 class _FluidNetTrainBase(torch.nn.Module):
-    """What FluidNetTrain (2D), FluidNetTrain3D and FluidNetBankTrain share: everything but the dimension, which a subclass states in
+    """What FluidNetTrain (2D), FluidNetTrain3D, FluidNetBankTrain and FluidNetBankTrain3D share: everything but the dimension, which a subclass states in
     _NDIM, its check of mconf['is3D'] (_check_dim), and the net in the middle (_check_model, _build_net, _ordered, _packed)."""
 
     _NDIM = 2
@@ -302,8 +306,8 @@ class FluidNetBankTrain(_FluidNetTrainBase):
             raise ValueError("fluidnet_cxx_amd.FluidNetBankTrain: the 'FluidNet' bank model is 2D only (the reference asserts it)")
 
     def _build_net(self):
-        self._api = _Api(2, bank=True)
-        w = make_banknet_weights(0)
+        self._api = _Api(self._NDIM, bank=True)
+        w = make_banknet_weights(0, ndim=self._NDIM)
         for L in banknet_layers():
             parts = L["name"].split(".")                  # conv1  |  convBank, block, 0
             mod = self
@@ -324,7 +328,7 @@ class FluidNetBankTrain(_FluidNetTrainBase):
         return _repack(self, device)
 
     def _not_scalenet(self, what):
-        raise RuntimeError(f"FluidNetBankTrain.{what}: this net is the 'FluidNet' bank model; the native step and the z-slab drivers "
+        raise RuntimeError(f"{type(self).__name__}.{what}: this net is the 'FluidNet' bank model; the native step and the z-slab drivers "
                            "take the ScaleNet image only (net.bank(x) and net(input) run the bank kernels)")
 
     @property
@@ -340,3 +344,20 @@ class FluidNetBankTrain(_FluidNetTrainBase):
             return self._api.net_forward(self._packed(x.device)[0], x, self.precision_mode)
         _no_input_grad(x, "x")
         return _MultiScaleFn.apply(x, self, *self._ordered())
+
+
+class FluidNetBankTrain3D(FluidNetBankTrain):
+    """FluidNetBankTrain for the Conv3d bank net, mconf['model'] = 'FluidNet3D' with is3D (csrc/fnx_banknet3d_train.hip): the same twelve
+    parameter names with 5-D weights, a fresh net holding weights.make_banknet_weights(0, ndim=3); input_ (B,6,D,H,W) -> (p, U) and
+    `net.bank(x)`, x (B,2,D,H,W) -> p (B,1,D,H,W).  D, H and W multiples of 4.  Its checkpoints load into FluidNet(mconf) and back."""
+
+    _NDIM = 3
+
+    def _check_model(self, mconf, name):
+        if mconf.get("model", "ScaleNet") != "FluidNet3D":
+            raise ValueError(f"{name}: mconf['model'] must be 'FluidNet3D', the Conv3d 16-channel bank net (FluidNetTrain3D trains the "
+                             "3D ScaleNet, FluidNetBankTrain the 2D 'FluidNet' bank net)")
+
+    def _check_dim(self, mconf):
+        if not mconf.get("is3D", False):
+            raise ValueError("fluidnet_cxx_amd.FluidNetBankTrain3D: the 'FluidNet3D' model is 3D only (is3D=False)")

@@ -1,6 +1,6 @@
 """Training of the 3D pressure net, end to end on the device: the 3D counterpart of fluidnet_cxx_amd/training.py.
 
-    from fluidnet_cxx_amd.training3d import train3d, SceneSampler3D, fluidnet_loss3d
+    from fluidnet_cxx_amd.training3d import train3d, train_bank3d, SceneSampler3D, fluidnet_loss3d
 
 The reference has no 3D training at all (its FluidNet is Conv2d only), so nothing here follows a reference file: the loop is the 2D one
 (fluidnet_cxx_amd/training.py holds the bodies both share, in private bases) around `FluidNetTrain3D`, with scenes from fnx_scene_obstacles3d /
@@ -15,6 +15,7 @@ fluidnet_cxx_amd.training trains the 2D net.
 import torch
 
 from ._ext import ext
+from .train import FluidNetBankTrain3D
 from .train3d import FluidNetTrain3D
 from .training import MCONF_DEFAULTS, TCONF_DEFAULTS, _Dim, _SceneSamplerBase, _evaluate, _loss_fn, _train
 
@@ -77,6 +78,8 @@ class SceneSampler3D(_SceneSamplerBase):
 
 _DIM3 = _Dim(3, FluidNetTrain3D, lambda mconf, B, dims, *rest: SceneSampler3D(mconf, B, dims[0], dims[1], dims[2], *rest), fluidnet_loss3d,
              ext.train_loss3d)
+# the same with the Conv3d 16-channel bank net in the middle (mconf['model'] = 'FluidNet3D')
+_DIM3_BANK = _Dim(3, FluidNetBankTrain3D, _DIM3.sampler, fluidnet_loss3d, ext.train_loss3d)
 
 
 def evaluate3d(net, batches, lambdas):
@@ -93,6 +96,16 @@ def train3d(mconf=None, tconf=None, device="cuda", out=None, resume=None, log=No
     D, H, W = (int(tconf.get(k, tconf["res"])) for k in ("D", "H", "W"))
     _refuse_2d("train3d", mconf, D)
     if mconf.get("model", "ScaleNet") == "FluidNet3D":
-        raise ValueError("train3d: training the 'FluidNet3D' model is not built (the Conv3d bank net has an inference forward only); "
-                         "train3d trains the 3D ScaleNet")
+        raise ValueError("train3d: training the 'FluidNet3D' model is not built into train3d, which trains the 3D ScaleNet; "
+                         "train_bank3d trains the Conv3d bank net")
     return _train(_DIM3, mconf, tconf, (D, H, W), device, out, resume, log)
+
+
+def train_bank3d(mconf=None, tconf=None, device="cuda", out=None, resume=None, log=None):
+    """train3d for the Conv3d bank net: mconf['model'] is 'FluidNet3D' (set if absent), the net FluidNetBankTrain3D, D, H and W multiples
+    of 4.  The checkpoint's mconf carries the model name, so FluidNet(ck["mconf"]) loads ck["state_dict"]."""
+    mconf = dict(MCONF3D_DEFAULTS, **dict({"model": "FluidNet3D"}, **(mconf or {})))
+    tconf = dict(TCONF3D_DEFAULTS, **(tconf or {}))
+    D, H, W = (int(tconf.get(k, tconf["res"])) for k in ("D", "H", "W"))
+    _refuse_2d("train_bank3d", mconf, D)
+    return _train(_DIM3_BANK, mconf, tconf, (D, H, W), device, out, resume, log)

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define FNX_ABI_VERSION 33
+#define FNX_ABI_VERSION 34
 
 enum {
   FNX_OK = 0,
@@ -874,6 +874,68 @@ typedef struct FnxTapeEntry3D {
   int C, D, H, W;
 } FnxTapeEntry3D;
 size_t fnx_multiscale3d_tape_layout(const FnxGrid* g, FnxTapeEntry3D* entries);
+
+/* Training of the Conv3d bank net (ABI 34): the 3D siblings of the ABI-31 block above for the 'FluidNet3D' model, with the same contracts.
+ * Gradients of a scalar loss of p (or of FluidNet.forward's (p, U)) with respect to the twelve parameter tensors, exact fp32.  Every entry
+ * point refuses, before it touches the device and each with its own fnx_last_error text, what fnx_banknet3d_forward refuses: null
+ * arguments; a 2D grid ("3D only"); the bf16 modes; an unknown precision mode; D, H or W that is no positive multiple of 4; a short
+ * workspace (FNX_EWORKSPACE).  No gradient with respect to the input, no dropout.  No atomics and no host synchronisation (capturable):
+ * every cross-workgroup sum goes through per-workgroup partial sums which one kernel adds in index order in fp64, so two calls on the
+ * same inputs give the same bits.  grad_p, x and the tape are not modified.
+ *
+ * The tape holds the 2D bank tape's fourteen entries, in its order and under its names, as contiguous (B,C,d,h,w) tensors: "a", "h1",
+ * "b1", "t", "c2a", "c2b" (16 channels) and "c3" (8) at full resolution, "a2", "h2", "b2" at D/2 H/2 W/2, "a4", "h4", "b4" at D/4 H/4 W/4, and
+ * "x" (2 channels), which only fnx_fluidnet_bank3d_forward_train writes: 106 + 48 / 8 + 48 / 64 = 112.75 floats a full-resolution voxel
+ * (451 bytes), offsets rounded to 64 floats.  fnx_banknet3d_tape_layout returns the tape's size in floats (0 on error) and, if `entries`
+ * is not NULL, fills fnx_banknet3d_tape_entries() of them; names and offsets are a function of (B, D, H, W) alone.  p of the training
+ * forward is bit-identical to fnx_banknet3d_forward's in every fp32 mode; the training forward needs no workspace.
+ *
+ * packed_t (fnx_banknet3d_packed_t_bytes()): the transposed, tap-flipped bank weights in the A-operand order of the forward's convolution
+ * kernel, 16 zeros as their bias, and the transposed 1x1x1 weights; fnx_banknet3d_pack_t runs on the device.  Repack it, as `packed`,
+ * whenever the weights change.
+ *
+ * Backward: grad_p (B,1,D,H,W), the tape and x (B,2,D,H,W) -> grad_blob (fnx_banknet3d_weight_floats() floats) in the layout of
+ * weights_blob.  The derivative of a ReLU is (saved output > 0).  conv2's gradient is the sum over its two applications, a bank tensor's
+ * the sum over the three levels (added in the order quarter, half, full); the gradient reaches level 2 (4) as the sum of its 2x2x2
+ * (4x4x4) children and comes back from the pooling as g_a1 + up2(g_a2) / 8 + up4(g_a4) / 64.  The input gradients of the 16 -> 16
+ * convolutions run through the forward's z-marching kernel body on packed_t; every 16 x 16 weight gradient runs on
+ * v_mfma_f32_16x16x4_f32 with the cells as K; conv1's 864 weight gradients and the bias gradients are plain sums.  Workspace:
+ * fnx_banknet3d_backward_ws_bytes(g) (0 for a grid without a size): 146 bytes a full-resolution voxel and the partial sums.
+ *
+ * fnx_banknet3d_backward_plan: the fnx_banknet3d_backward_launches() launches of the backward that leave partial sums, in launch order:
+ * the tail, the two weight gradients (block.2, block.0) of the quarter, the half and the full level, and conv1.  A launch takes
+ * min(items, cap) workgroups, with item i on workgroup i mod workgroups, and workgroup s writes partial_floats floats at
+ * partial_offset + 4 * s * partial_floats bytes of the workspace.  dims: a weight gradient's items are (sample, y tile, x tile, z chunk)
+ * = B x dims[1] x dims[0] x dims[2] of tiles WG 4 x 36 cells and dims[3] planes a chunk; the tail's and conv1's are units of dims[1]
+ * flattened cells, dims[0] a sample.  A function of (B, D, H, W) alone. */
+typedef struct FnxBankBwdLaunch {
+  char name[16];
+  int level;               /* 1, 2 or 4 */
+  long long items;
+  int workgroups, cap;
+  int partial_floats;
+  size_t partial_offset;   /* bytes from the start of the backward's workspace */
+  int dims[4];
+} FnxBankBwdLaunch;
+int fnx_banknet3d_tape_entries(void);
+size_t fnx_banknet3d_tape_layout(const FnxGrid* g, FnxTapeEntry3D* entries);
+size_t fnx_banknet3d_packed_t_bytes(void);
+int fnx_banknet3d_pack_t(const float* weights_blob, void* packed_t, void* stream);
+size_t fnx_banknet3d_backward_ws_bytes(const FnxGrid* g);
+int fnx_banknet3d_backward_launches(void);
+int fnx_banknet3d_backward_plan(const FnxGrid* g, FnxBankBwdLaunch* launches);
+int fnx_banknet3d_forward_train(const FnxGrid* g, const void* packed, const float* x, float* p, float* tape, int precision_mode, void* stream);
+int fnx_banknet3d_backward(const FnxGrid* g, const void* packed_t, const float* x, const float* grad_p, const float* tape, float* grad_blob,
+                           int precision_mode, void* ws, size_t ws_bytes, void* stream);
+/* fnx_fluidnet_bank_forward_train / fnx_fluidnet_bank_backward's contract on a (B,6,D,H,W) input with the Conv3d bank net in the middle:
+ * (p, U) have fnx_fluidnet_bank3d_forward's bits.  One workspace size for both. */
+size_t fnx_fluidnet_bank3d_train_ws_bytes(const FnxGrid* g);
+int fnx_fluidnet_bank3d_forward_train(const FnxGrid* g, const void* packed, const float* input, float normalize_threshold, float* p_out,
+                                      float* U_out, float* flags_out, float* scale_out, float* tape, int precision_mode, void* ws,
+                                      size_t ws_bytes, void* stream);
+int fnx_fluidnet_bank3d_backward(const FnxGrid* g, const void* packed_t, const float* flags, const float* scale, const float* grad_p,
+                                 const float* grad_U, const float* tape, float* grad_blob, int precision_mode, void* ws, size_t ws_bytes,
+                                 void* stream);
 /* The adjoint of the net's trilinear resampling (align_corners = False, sample positions in float32) of one channel on its own, as
  * the backward applies it at the two tower joints: grad_dst (B,1,Do,Ho,Wo) -> grad_src (B,1,Di,Hi,Wi), every source voxel the sum of
  * its destinations in a fixed x, y, z order.  Exposed so that a test can hold it against the transposed interpolation matrices. */
