@@ -1,8 +1,11 @@
 // The C ABI on its own: a C++ host with nothing but the HIP runtime and include/fluidnet_hip.h -- no torch, no Python -- runs
-// the 128 x 128 plume (configs[0]: Jacobi-28) for `steps` time steps through fnx_simulate_step and prints FNV-1a hashes of
+// the 128 x 128 plume (configs[0]: Jacobi-28) for `steps` time steps through fnx_simulate_step_net and prints FNV-1a hashes of
 // the resulting fields.  tests/test_abi.py builds and runs it on the GPU box and compares the hashes with the Python path.
 //   hipcc --offload-arch=gfx950 -O2 -I include examples/cabi_plume.cpp -L fluidnet_cxx_amd -lfluidnet_hip \
 //         -Wl,-rpath,$PWD/fluidnet_cxx_amd -o examples/cabi_plume.bin && examples/cabi_plume.bin 20
+// With a third argument, a file of fnx_banknet_weight_floats() raw float32 (the 'FluidNet' bank net's six layers in torch order, weight
+// then bias), the projection is the net's instead: `cabi_plume.bin 20 128 bank.f32` packs the file with fnx_banknet_pack and runs the
+// 'convnet' step through fnx_simulate_step_net(..., FNX_NET_BANK, ...); res must then be a multiple of 4.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -64,12 +67,26 @@ int main(int argc, char** argv) {
   prm.operating_density = 0.f; prm.p_tol = 0.f; prm.jacobi_iter = 28; prm.method = 0;
   FnxState st = {};
   st.p = p; st.U = U; st.density = rho; st.flags = flags; st.UBC = dUBC; st.UBCInvMask = dUBCm; st.densityBC = drBC; st.densityBCInvMask = drBCm;
+  int net_kind = FNX_NET_SCALENET;                               // (method 0 does not look at it)
+  if (argc > 3) {
+    // the bank net's weights from a file, packed on the device: the 'convnet' step with that net in the middle
+    std::vector<float> blob(fnx_banknet_weight_floats());
+    FILE* f = fopen(argv[3], "rb");
+    if (!f || fread(blob.data(), 4, blob.size(), f) != blob.size()) { fprintf(stderr, "%s: %zu float32 expected\n", argv[3], blob.size()); return 1; }
+    fclose(f);
+    float* dblob; void* packed;
+    CHECK_HIP(hipMalloc(&dblob, blob.size() * 4)); CHECK_HIP(hipMalloc(&packed, fnx_banknet_packed_bytes()));
+    CHECK_HIP(hipMemcpy(dblob, blob.data(), blob.size() * 4, hipMemcpyHostToDevice));
+    CHECK_FNX(fnx_banknet_pack(dblob, packed, s));
+    st.net = packed; net_kind = FNX_NET_BANK;
+    prm.method = 1; prm.normalize_threshold = 1e-5f; prm.precision_mode = FNX_PRECISION_FP32;
+  }
   hipEvent_t e0, e1;
   CHECK_HIP(hipEventCreate(&e0)); CHECK_HIP(hipEventCreate(&e1));
   CHECK_HIP(hipEventRecord(e0, s));
   for (int it = 0; it < steps; ++it) {
     prm.static_flags = it == 0 ? 0 : (it == 1 ? 3 : 7);          // flags and BC arrays never change here
-    CHECK_FNX(fnx_simulate_step(&g, &prm, &st, ws, ws_bytes, s));
+    CHECK_FNX(fnx_simulate_step_net(&g, &prm, &st, net_kind, ws, ws_bytes, s));
   }
   CHECK_HIP(hipEventRecord(e1, s));
   CHECK_HIP(hipStreamSynchronize(s));

@@ -11,7 +11,7 @@ iterations, the PNG panels, the VTK cell data and the restart file.  Only the im
 driver: `lib` -> `fluidnet_cxx_amd`.  `--method convnet --weights CKPT` projects with a trained net: CKPT is what examples/train.py
 writes ({'state_dict', 'mconf', ...}), loaded the way the reference driver loads convModel_lastEpoch_best.pth (plume.py:119-123).
 The checkpoint's own mconf['model'] picks the net, so no option does: 'ScaleNet' is the MultiScale net on the native step, 'FluidNet'
-(what the reference's trainConfig.yaml ships) is its 16-channel bank net, 2D only, which simulate() runs operator by operator.
+(what the reference's trainConfig.yaml ships) is its 16-channel bank net, 2D only; simulate() runs either in the native step.
 `--depth N` (N > 1) runs the 3D plume on a N x res x res grid (jacobi, pcg and --vorticity as in 2D); there `--method convnet` takes
 `--weights3d CKPT`, a checkpoint of `examples/train.py --depth N` (the 3D net; a 2D checkpoint given by --weights is refused) or one whose
 mconf['model'] is 'FluidNet3D', the Conv3d bank net (N and res multiples of 4; simulate() runs it operator by operator).  `--render` adds volume renderings of the density (output.save_render: from the front, lit from above, and from the side)

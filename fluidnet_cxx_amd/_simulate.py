@@ -9,10 +9,16 @@ batch_dict, same mconf keys).  Two execution modes:
 fused=True still runs operator by operator where the native step has no form of the call: output_div=True, a 3D state with
 flags_stick, a density BC without a 'density' key, and mconf['viscosity'] > 0 with a (dt, viscosity) pair whose double product the two
 floats of FnxStepParams do not give (about a third of all pairs, dt = 0.1 with viscosity = 0.05 among them; the reference rounds the
-product once, viscosity.py:64), and 'convnet' or 'hybrid' with a net of the reference's 'FluidNet' bank model (mconf['model'] =
-'FluidNet', 2D, or 'FluidNet3D', its Conv3d counterpart: the native step takes the ScaleNet image only; both methods call net(...) on
-the operator path, which runs the bank kernels of fnx_banknet.hip / fnx_banknet3d.hip).  `workspace` and `static_flags` are then not used.  The same bits, more launches: until FnxStepParams
+product once, viscosity.py:64).  `workspace` and `static_flags` are then not used.  The same bits, more launches: until FnxStepParams
 carries the product (an ABI change) such a viscous 2D run is slower than one with, say, viscosity = 0.02.
+The net of 'convnet' and 'hybrid' in 2D is whichever model the net is: the layer asks `net.step_net(device)` for (kind, image) --
+'scalenet', or 'bank' for the reference's 'FluidNet' bank model (mconf['model'] = 'FluidNet') -- and the native step runs that net
+between the same launches (fnx_simulate_step_net): the static path, an explicit workspace and a HIP-graph capture work
+with the bank net as with the ScaleNet, with the bits of the operator path.  A net without `step_net` is asked for
+`packed_for(device)`, a ScaleNet image.  The training nets (train.FluidNetTrain, FluidNetBankTrain) hand out an image of their current
+parameters; the native step records nothing for autograd, whatever the net's mode.  A net of the Conv3d bank model
+(mconf['model'] = 'FluidNet3D') still runs operator by operator, whatever `fused`, `workspace` or `static_flags` say: both methods call
+net(...), which runs the bank kernels of fnx_banknet3d.hip (the native step does not take that net yet).
 The reference's own call -- `simulate(mconf, batch_dict, net, sim_method)`, four arguments (plume.py:237) -- gets the static
 path by itself: the layer keeps one step workspace per (device, grid shape) and looks at `(data_ptr, _version, shape, stride)` of
 `flags` and of the four BC arrays (torch bumps `_version` on every in-place write, and so do this package's own in-place
@@ -230,9 +236,9 @@ def simulate(mconf, batch_dict, net, sim_method, output_div=False, fused=True, w
     # 3D states with flags_stick (the native step refuses them; fluid.setWallBcsStick takes 3D fields),
     # no 'density' key but a density BC: the reference applies setConstVals to its zeros (simulate.py:82-97), and
     # a (dt, viscosity) pair whose product the step's two floats do not give (_step_has_the_viscous_coefficient)
-    # and a net of the reference's 'FluidNet' bank model: the native step takes the ScaleNet image only (FluidNet.is_bank)
+    # and a net of the Conv3d bank model: the native step takes the ScaleNet and the 2D bank net (FluidNet.step_net)
     simple = (not output_div and not (is3D and "flags_stick" in batch_dict)
-              and not (uses_net and getattr(net, "is_bank", False))
+              and not (uses_net and is3D and getattr(net, "is_bank", False))
               and (has_density or not ("densityBC" in batch_dict and "densityBCInvMask" in batch_dict))
               and (viscosity == 0 or _step_has_the_viscous_coefficient(dt, viscosity)))
     if fused and simple:
@@ -243,7 +249,10 @@ def simulate(mconf, batch_dict, net, sim_method, output_div=False, fused=True, w
         # gravityVec is only read when buoyancy is applied (simulate.py:99-105)
         gvec = _gravity(mconf, 1.0)[0] if want_gvec else [0.0, 0.0, 0.0]
         density = batch_dict["density"] if has_density else None
-        packed = net.packed_for(U.device) if uses_net else None
+        # the net by its kind: ScaleNet or the 2D bank net ('bank'); a net without step_net hands out a ScaleNet image
+        net_kind, packed = "scalenet", None
+        if uses_net:
+            net_kind, packed = net.step_net(U.device) if hasattr(net, "step_net") else ("scalenet", net.packed_for(U.device))
         auto = None
         if workspace is None and static_flags is None and flags.is_cuda and geom is None:
             # the reference's four-argument call: the layer's own workspace, static inputs detected (module docstring)
@@ -263,7 +272,8 @@ def simulate(mconf, batch_dict, net, sim_method, output_div=False, fused=True, w
                            bool(mconf.get("correctScalar", False)) and has_density, periodic,
                            batch_dict.get("flags_stick") if sim_method == "convnet" else None,
                            pcg_tol=float(mconf.get("pcgTol", 1e-5)), pcg_iter=int(mconf.get("pcgIter", 50)),
-                           vorticity_confinement=float(vorticityAmp) if vorticityAmp > 0 else 0.0, pcg_warm=pcg_warm)
+                           vorticity_confinement=float(vorticityAmp) if vorticityAmp > 0 else 0.0, pcg_warm=pcg_warm,
+                           net_kind=net_kind)
         if auto is not None and uses_pcg:
             auto.built_hierarchy(flags)
         if not has_density:

@@ -1044,7 +1044,7 @@ void simulate_step_(Tensor p, Tensor U, Tensor flags, c10::optional<Tensor> dens
                     const std::string method, double normalize_threshold, c10::optional<Tensor> workspace,
                     int static_flags, const Geom* geom, const std::string& precision_mode, double viscosity,
                     double gravity_scale, bool correct_scalar, int periodic, c10::optional<Tensor> flags_stick, double pcg_tol,
-                    int pcg_iter, double vorticity_confinement, bool pcg_warm) {
+                    int pcg_iter, double vorticity_confinement, bool pcg_warm, const std::string& net_kind) {
   check_field(U, "U");
   FnxGrid g = grid_of(flags, U.size(1) == 3, geom);
   check_vel(U, g, "U"); check_scalar(p, g, "p");
@@ -1064,6 +1064,17 @@ void simulate_step_(Tensor p, Tensor U, Tensor flags, c10::optional<Tensor> dens
   prm.vorticity_confinement = (float)vorticity_confinement;
   FnxState st = make_state(g, p, U, flags, density, UBC, UBCInvMask, densityBC, densityBCInvMask);
   st.net = (net.has_value() && net->defined()) ? net->data_ptr() : nullptr;
+  // the image against its kind, by size (the three packers' images differ in it), as bank_forward checks its own
+  TORCH_CHECK(net_kind == "scalenet" || net_kind == "bank" || net_kind == "bank3d", "net_kind: 'scalenet', 'bank' or 'bank3d' (got '", net_kind, "')");
+  const int kind = net_kind == "bank" ? FNX_NET_BANK : (net_kind == "bank3d" ? FNX_NET_BANK3D : FNX_NET_SCALENET);   // (bank3d: refused by the C ABI)
+  if (st.net && (prm.method == 1 || prm.method == 3)) {
+    if (kind == FNX_NET_SCALENET) {
+      TORCH_CHECK(net->is_cuda() && net->is_contiguous() && (size_t)net->nbytes() == fnx_scalenet_packed_bytes(g.is3D),
+                  "net must be the ", fnx_scalenet_packed_bytes(g.is3D), "-byte image from scalenet_pack (got ", net->nbytes(), " bytes)");
+    } else {
+      check_bank_image(kind == FNX_NET_BANK ? &BANK2D : &BANK3D, *net);
+    }
+  }
   st.flags_stick = opt_field(g, flags_stick, false, "flags_stick");
   c10::hip::HIPGuard guard(flags.get_device());
   const size_t bytes = fnx_workspace_bytes(&g, FNX_OP_STEP);
@@ -1073,7 +1084,7 @@ void simulate_step_(Tensor p, Tensor U, Tensor flags, c10::optional<Tensor> dens
   else ws = at::empty({(int64_t)bytes}, flags.options().dtype(at::kByte));
   // the mask lives in the workspace: only a caller-owned workspace carries it from one step to the next
   prm.static_flags = given ? static_flags : 0;      // (promises about the previous step need a caller-owned workspace)
-  check_status(fnx_simulate_step(&g, &prm, &st, ws.data_ptr(), (size_t)ws.numel() * ws.element_size(), cur_stream(U)));
+  check_status(fnx_simulate_step_net(&g, &prm, &st, kind, ws.data_ptr(), (size_t)ws.numel() * ws.element_size(), cur_stream(U)));
   wrote(p); wrote(U); wrote(density);
 }
 
@@ -1422,7 +1433,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("normalize_threshold"), py::arg("workspace") = py::none(), py::arg("static_flags") = 0, GEOM,
         py::arg("precision_mode") = "fp32", py::arg("viscosity") = 0.0, py::arg("gravity_scale") = 0.0,
         py::arg("correct_scalar") = false, py::arg("periodic") = 0, py::arg("flags_stick") = py::none(), py::arg("pcg_tol") = 1e-5,
-        py::arg("pcg_iter") = 50, py::arg("vorticity_confinement") = 0.0, py::arg("pcg_warm") = false, NoGil());
+        py::arg("pcg_iter") = 50, py::arg("vorticity_confinement") = 0.0, py::arg("pcg_warm") = false, py::arg("net_kind") = "scalenet",
+        NoGil());
   m.def("step_workspace_bytes", &step_workspace_bytes);
   m.def("jacobi_sweeps_", &jacobi_sweeps_, py::arg("flags"), py::arg("div"), py::arg("p"), py::arg("is3D"), py::arg("nsweeps"),
         py::arg("workspace") = py::none(), py::arg("reuse_mask") = false, GEOM, py::arg("from_zero") = false, NoGil());

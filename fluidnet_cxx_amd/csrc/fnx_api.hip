@@ -943,13 +943,36 @@ int fnx_bc_classify(const FnxGrid* g, const FnxState* st, unsigned char* bc_clas
   return FNX_OK;
 }
 
-// One whole step: the argument checks, the workspace (carve_step), the plan (fnx::step_plan), then the sequence the plan names.
 int fnx_simulate_step(const FnxGrid* g, const FnxStepParams* prm, const FnxState* st, void* ws, size_t ws_bytes,
                       void* stream) {
+  return fnx_simulate_step_net(g, prm, st, FNX_NET_SCALENET, ws, ws_bytes, stream);
+}
+
+// What the bank net (FNX_NET_BANK) in methods 1 and 3 adds to the step's refusals, before the first launch and in the bank unit's own
+// words (check_bank_call): the kind against the grid's dimension, the precision mode, the axes, a view.  The Conv3d bank net has a kind
+// of its own, which the step does not take yet.
+static int check_step_net(const char* fn, const FnxGrid* g, const FnxStepParams* prm, int net_kind) {
+  if (net_kind == FNX_NET_SCALENET) return FNX_OK;
+  if (net_kind == FNX_NET_BANK3D)
+    return fail(FNX_EINVAL, "%s: FNX_NET_BANK3D is not built into the step (the Conv3d bank net runs through fnx_fluidnet_bank3d_forward, "
+                            "around the operators)", fn);
+  if (net_kind != FNX_NET_BANK)
+    return fail(FNX_EINVAL, "%s: unknown net_kind %d (FNX_NET_SCALENET, FNX_NET_BANK or FNX_NET_BANK3D)", fn, net_kind);
+  if (int rc = fnx::check_bank_grid(fn, g, prm->precision_mode)) return rc;
+  if (is_view(g)) return fail(FNX_EINVAL, "%s: the bank nets take no compute window or z-slab view (single domain only)", fn);
+  return FNX_OK;
+}
+
+// One whole step: the argument checks, the workspace (carve_step), the plan (fnx::step_plan), then the sequence the plan names.
+// net_kind: the net of methods 1 and 3 (the other methods do not look at it).
+int fnx_simulate_step_net(const FnxGrid* g, const FnxStepParams* prm, const FnxState* st, int net_kind, void* ws, size_t ws_bytes,
+                          void* stream) {
   using fnx::StepAdvect; using fnx::StepClassMap; using fnx::StepProjection; using fnx::StepStageWord; using fnx::StepTail;
   if (int rc = check_grid(g)) return rc;
   if (!prm || !st || !st->p || !st->U || !st->flags) return fail(FNX_EINVAL, "simulate_step: NULL state");
   if (prm->method < 0 || prm->method > 4) return fail(FNX_EINVAL, "Simulation method not supported. Choose convnet, jacobi, pcg or hybrid.");
+  if (prm->method != 1 && prm->method != 3) net_kind = FNX_NET_SCALENET;      // no net: the kind is not looked at
+  if (int rc = check_step_net(__func__, g, prm, net_kind)) return rc;
   const bool pcg = prm->method >= 2;                 // 2: cold, 3 ('hybrid'): from the net's pressure, 4: from st->p as it stands
   if (pcg && prm->pcg_iter < 1) return fail(FNX_EINVAL, "At least 1 iteration of the solver is needed (pcg_iter < 1)");
   if (pcg && is_view(g))
@@ -961,6 +984,10 @@ int fnx_simulate_step(const FnxGrid* g, const FnxStepParams* prm, const FnxState
   if (prm->method == 3 && fnx::net_mode(prm->precision_mode) < 0) return fail(FNX_EINVAL, "simulate_step: unknown precision_mode %d", prm->precision_mode);
   const fnx::StepLayout L = carve_step(g, ws);
   if (!ws || ws_bytes < L.bytes) return fail(FNX_EWORKSPACE, "simulate_step: workspace too small (%zu < %zu)", ws_bytes, L.bytes);
+  // a bank net's scratch comes out of the tail as the ScaleNet's does; the tail is sized for the ScaleNet (carve_step) and is not grown
+  if (net_kind != FNX_NET_SCALENET && fnx::fluidnet_core_ws_bytes(g, net_kind) > L.tail_bytes)
+    return fail(FNX_EWORKSPACE, "%s: the step workspace's scratch tail is too small for the bank net (%zu < %zu)", __func__, L.tail_bytes,
+                fnx::fluidnet_core_ws_bytes(g, net_kind));
   const bool has_rho = st->density != nullptr;
   const fnx::StepPlan plan = fnx::step_plan(prm, has_rho, st->flags_stick != nullptr, st->UBC || st->densityBC);
   if (prm->viscosity < 0.f) return fail(FNX_EINVAL, "Viscosity must be positive");
@@ -1024,7 +1051,7 @@ int fnx_simulate_step(const FnxGrid* g, const FnxStepParams* prm, const FnxState
       if (plan.projection == StepProjection::PCG_FROM_NET) {
         // the guess: the net's un-normalised pressure of this U, written into st->p.  The net's scratch and the solve's share the
         // tail: the net has finished (same stream) before the solve's first launch, and all the solve takes from it is st->p
-        if (int rc = fnx::fluidnet_pressure(g, st->net, st->flags, prm->normalize_threshold, fnx::net_mode(prm->precision_mode), st->p, st->U,
+        if (int rc = fnx::fluidnet_pressure(g, st->net, net_kind, st->flags, prm->normalize_threshold, fnx::net_mode(prm->precision_mode), st->p, st->U,
                                             L.tail, stream)) return rc;
       }
       const float* p0 = plan.projection == StepProjection::PCG_COLD ? nullptr : st->p;
@@ -1040,7 +1067,7 @@ int fnx_simulate_step(const FnxGrid* g, const FnxStepParams* prm, const FnxState
       const int mode = fnx::net_mode(prm->precision_mode);
       if (mode < 0) return fail(FNX_EINVAL, "simulate_step: unknown precision_mode %d", prm->precision_mode);
       // without flags_stick the tail of the net's forward and the step's last setConstVals are one pass (fluidnet_core)
-      if (int rc = fnx::fluidnet_core(g, st->net, st->flags, prm->normalize_threshold, mode, st->p, st->U, L.tail, stream,
+      if (int rc = fnx::fluidnet_core(g, st->net, net_kind, st->flags, prm->normalize_threshold, mode, st->p, st->U, L.tail, stream,
                                       plan.projection == StepProjection::NET_FUSED ? st : nullptr)) return rc;
       break;
     }

@@ -68,6 +68,15 @@ size_t bank_net_ws(const FnxGrid* g) { return banknet_ws_layout(g->B, g->H, g->W
 size_t bank_whole_ws(const FnxGrid* g) { return fluidnet_whole_ws_bytes(g->B, (size_t)g->H * g->W, bank_net_ws(g)); }
 
 }  // namespace
+
+// the net as fnx_cnn.hip's fluidnet_core runs it in the native step (fnx_cnn.h)
+size_t bank_net_ws_bytes(const FnxGrid* g) { return bank_net_ws(g); }
+void bank_net_forward(const FnxGrid* g, const void* packed, const float* x, float* p, void* ws, hipStream_t s) {
+  banknet_forward(g->B, g->H, g->W, (const float*)packed, x, p, ws, s);
+}
+int check_bank_grid(const char* fn, const FnxGrid* g, int precision_mode) {
+  return check_bank_call(fn, 2, g, true, precision_mode, nullptr, 0);
+}
 }  // namespace fnx
 
 extern "C" {

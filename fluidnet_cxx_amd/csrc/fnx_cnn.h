@@ -151,12 +151,20 @@ struct FluidnetTrainBwdWs { float *gU, *gU_in, *gp, *gnet; void* net; size_t byt
 FluidnetTrainBwdWs fluidnet_train_bwd_ws(int nc, const FnxGrid* g, void* base);
 int fluidnet_train_gnet(int nc, const FnxGrid* g, const float* flags, const float* scale, const float* grad_p, const float* grad_U,
                         const FluidnetTrainBwdWs& w, void* stream);
+// The net in the middle, by its kind (FNX_NET_SCALENET or FNX_NET_BANK, the 2D bank net; FNX_NET_BANK3D is not built into the step):
+// `packed` is the image of that kind.  The bank unit exports its net for it (fnx_banknet.hip): the workspace of the net alone, its
+// launches, and check_bank_call's refusals of a grid or a precision mode under the caller's name (no argument or workspace check).
+size_t bank_net_ws_bytes(const FnxGrid* g);
+void bank_net_forward(const FnxGrid* g, const void* packed, const float* x, float* p, void* ws, hipStream_t s);
+int check_bank_grid(const char* fn, const FnxGrid* g, int precision_mode);
+// what fluidnet_core and fluidnet_pressure take at `ws` for a net of this kind: fluidnet_ws_layout with the net's own workspace
+size_t fluidnet_core_ws_bytes(const FnxGrid* g, int net_kind);
 // the net's un-normalised pressure alone (model.py:125-175, :221-222) for the hybrid projection: p_out = scale * net(div(U) / scale, occupancy);
-// U is read only.  ws: fluidnet_ws_bytes.
-int fluidnet_pressure(const FnxGrid* g, const void* packed, const float* flags, float thr, int precision_mode, float* p_out, const float* U,
-                      void* ws, void* stream);
+// U is read only.  ws: fluidnet_core_ws_bytes.
+int fluidnet_pressure(const FnxGrid* g, const void* packed, int net_kind, const float* flags, float thr, int precision_mode, float* p_out,
+                      const float* U, void* ws, void* stream);
 // bcs != nullptr: the fused step's form -- the last setConstVals of the step (simulate.py:168) is part of the pass behind the
 // net (bcs supplies density, the BC arrays, bc_class and density_bc_applied; p_out must not be the workspace)
-int fluidnet_core(const FnxGrid* g, const void* packed, const float* flags, float thr, int precision_mode, float* p_out, float* U,
-                  void* ws, void* stream, const FnxState* bcs = nullptr);
+int fluidnet_core(const FnxGrid* g, const void* packed, int net_kind, const float* flags, float thr, int precision_mode, float* p_out,
+                  float* U, void* ws, void* stream, const FnxState* bcs = nullptr);
 }

@@ -1861,12 +1861,26 @@ int fluidnet_post(const FnxGrid* g, float* p, float* U, const float* flags, cons
   return fnx_set_wall_bcs(g, U, flags, stream);                                  // model.py:226
 }
 
-int fluidnet_core(const FnxGrid* g, const void* packed, const float* flags, float thr, int precision_mode, float* p_out, float* U,
-                  void* ws, void* stream, const FnxState* bcs) {
+// the workspace of the net alone, and its launches: x (B,2,..) -> p (B,1,..)
+static size_t net_ws_bytes(const FnxGrid* g, const GridDims& d, int net_kind) {
+  return net_kind == FNX_NET_BANK ? bank_net_ws_bytes(g) : multiscale_ws_bytes(d, g->is3D);
+}
+static void net_forward(const FnxGrid* g, const GridDims& d, const void* packed, int net_kind, const float* x, float* p, int precision_mode,
+                        void* ws, hipStream_t s) {
+  if (net_kind == FNX_NET_BANK) bank_net_forward(g, packed, x, p, ws, s);                    // model.py:179-209
+  else multiscale_forward(d, g->is3D, packed, x, p, precision_mode, ws, s);                  // model.py:174-175
+}
+size_t fluidnet_core_ws_bytes(const FnxGrid* g, int net_kind) {
+  const GridDims d = make_dims(g->B, g->D, g->H, g->W, g->z_offset, g->D_global);
+  return fluidnet_ws_layout(d.B, d.DHW, net_ws_bytes(g, d, net_kind), nullptr).bytes;
+}
+
+int fluidnet_core(const FnxGrid* g, const void* packed, int net_kind, const float* flags, float thr, int precision_mode, float* p_out,
+                  float* U, void* ws, void* stream, const FnxState* bcs) {
   const GridDims d = make_dims(g->B, g->D, g->H, g->W, g->z_offset, g->D_global);
   hipStream_t s = (hipStream_t)stream;
   const int nc = g->is3D ? 3 : 2;
-  const FluidnetWs w = fluidnet_ws_layout(d.B, d.DHW, multiscale_ws_bytes(d, g->is3D), ws);
+  const FluidnetWs w = fluidnet_ws_layout(d.B, d.DHW, net_ws_bytes(g, d, net_kind), ws);
   float *div = w.div, *x = w.x, *scale = w.scale;
   double* partial = w.partial;
   void* msws = w.net;
@@ -1883,14 +1897,14 @@ int fluidnet_core(const FnxGrid* g, const void* packed, const float* flags, floa
       else pack_div_kernel<false><<<grid, 256, 0, s>>>(d, U, flags, scale, x);
     }
     float* pnet = div;                                                           // (the divergence buffer is free here)
-    multiscale_forward(d, g->is3D, packed, x, pnet, precision_mode, msws, s);    // model.py:174-175
+    net_forward(g, d, packed, net_kind, x, pnet, precision_mode, msws, s);
     ProfScope ps(FNX_PROF_STAGE, s);
     launch_post_projection(d, g->is3D, pnet, U, bcs->density, flags, bc_ptrs(bcs), s, bcs->density_bc_applied != 0, scale,
                            p_out);                                               // model.py:213-226, simulate.py:168
     return fnx::launch_status(g->is3D);
   }
   if (int rc = fluidnet_pre(g, thr, U, flags, scale, w, stream)) return rc;
-  multiscale_forward(d, g->is3D, packed, x, p_out, precision_mode, msws, s);     // model.py:174-175
+  net_forward(g, d, packed, net_kind, x, p_out, precision_mode, msws, s);
   if (int rc = fluidnet_post(g, p_out, U, flags, scale, stream)) return rc;
   return fnx::launch_status(g->is3D);
 }
@@ -1898,18 +1912,18 @@ int fluidnet_core(const FnxGrid* g, const void* packed, const float* flags, floa
 // The hybrid projection's guess (fnx_simulate_step, method 3): the launches of the fused step in front of the net, the net straight
 // into p_out, and the multiply launch_unscale applies to p (nc = 0: no velocity is touched).  The same arithmetic per value as
 // fluidnet_core, so p_out holds the bits fnx_fluidnet_forward returns as p for this U.
-int fluidnet_pressure(const FnxGrid* g, const void* packed, const float* flags, float thr, int precision_mode, float* p_out, const float* U,
-                      void* ws, void* stream) {
+int fluidnet_pressure(const FnxGrid* g, const void* packed, int net_kind, const float* flags, float thr, int precision_mode, float* p_out,
+                      const float* U, void* ws, void* stream) {
   const GridDims d = make_dims(g->B, g->D, g->H, g->W, g->z_offset, g->D_global);
   hipStream_t s = (hipStream_t)stream;
   const int nc = g->is3D ? 3 : 2;
-  const FluidnetWs w = fluidnet_ws_layout(d.B, d.DHW, multiscale_ws_bytes(d, g->is3D), ws);   // (its divergence buffer is not used here)
+  const FluidnetWs w = fluidnet_ws_layout(d.B, d.DHW, net_ws_bytes(g, d, net_kind), ws);   // (its divergence buffer is not used here)
   float *x = w.x, *scale = w.scale;
   double* partial = w.partial;
   void* msws = w.net;
   launch_scale_std(d, nc, U, thr, partial, scale, s);                            // model.py:129-144
   launch_pack_div(d, g->is3D, U, flags, scale, x, s);                            // model.py:125-126, :146-168
-  multiscale_forward(d, g->is3D, packed, x, p_out, precision_mode, msws, s);     // model.py:174-175
+  net_forward(g, d, packed, net_kind, x, p_out, precision_mode, msws, s);
   launch_unscale(d, 0, scale, p_out, nullptr, s);                                // model.py:221-222
   return fnx::launch_status(g->is3D);
 }
@@ -1977,7 +1991,7 @@ int fnx_fluidnet_forward(const FnxGrid* g, const void* packed, const float* inpu
   float* flags = (float*)ws;                       // contiguous (B,1,..) copy of the flags channel
   void* rest = (char*)ws + fnx::fluidnet_flags_bytes(g->B, (size_t)g->D * g->H * g->W);
   fnx::fluidnet_split(g, input, U_out, flags, stream);
-  return fnx::fluidnet_core(g, packed, flags, thr, mode, p_out, U_out, rest, stream);
+  return fnx::fluidnet_core(g, packed, FNX_NET_SCALENET, flags, thr, mode, p_out, U_out, rest, stream);
 }
 
 }  // extern "C"

@@ -112,9 +112,10 @@ class FluidNet:
 
     model='FluidNet' (what the reference's trainConfig.yaml ships) is the 16-channel bank net of model.py:177-209, 2D and fp32 modes
     only: a fresh net holds weights.make_banknet_weights(0), `load_state_dict` requires the twelve conv1 / convBank / conv2 / conv3 /
-    convOut tensors and keeps multiScale.* and scale.*, `net.bank(x)` is the net alone, and `packed_for` raises -- the native step,
-    the z-slab drivers and FluidNetTrain take the ScaleNet image only; `simulate()` runs such a net operator by operator, and
-    train.FluidNetBankTrain is its counterpart with a native backward pass.
+    convOut tensors and keeps multiScale.* and scale.*, `net.bank(x)` is the net alone, and `packed_for` raises -- the z-slab
+    drivers and FluidNetTrain take the ScaleNet image only; `simulate()` runs such a net in the native step through `step_net`
+    (fnx_simulate_step_net; 2D: the 'FluidNet3D' model below stays on the operator path), and train.FluidNetBankTrain is its
+    counterpart with a native backward pass.
 
     model='FluidNet3D' (with is3D=True; not a reference model, which is 2D only) is the same net with every module replaced by its 3D
     sibling: a fresh net holds weights.make_banknet3d_weights(0), the twelve tensors have 5-D weights, `net.bank(x)` takes
@@ -125,7 +126,7 @@ class FluidNet:
         assert model in ("ScaleNet", "FluidNet", "FluidNet3D"), \
             "mconf['model'] must be 'ScaleNet' or 'FluidNet' (the 16-channel bank net) or 'FluidNet3D' (its Conv3d counterpart)"
         self.is_bank3d = model == "FluidNet3D"
-        self.is_bank = model in ("FluidNet", "FluidNet3D")       # simulate() runs such a net operator by operator
+        self.is_bank = model in ("FluidNet", "FluidNet3D")       # step_net() names the kind of image the native step gets
         assert not (model == "FluidNet" and mconf.get("is3D", False)), \
             "the 'FluidNet' bank model is 2D only (the reference asserts it); its Conv3d counterpart is model='FluidNet3D'"
         assert not (self.is_bank3d and not mconf.get("is3D", False)), "the 'FluidNet3D' bank model is 3D only (is3D=True); 'FluidNet' is the 2D net"
@@ -225,8 +226,9 @@ class FluidNet:
         return self._ms
 
     def _not_scalenet(self, what):
-        raise RuntimeError(f"FluidNet.{what}: this net is the '{self.mconf.get('model')}' bank model; the native step, the z-slab drivers and the trainers "
-                           "take the ScaleNet image only (net.bank(x) and net(input) run the bank kernels)")
+        raise RuntimeError(f"FluidNet.{what}: this net is the '{self.mconf.get('model')}' bank model; the z-slab drivers and the trainers "
+                           "take the ScaleNet image only (net.step_net(device) is what the native step takes; net.bank(x) and net(input) run the bank "
+                           "kernels)")
 
     @property
     def multiScale(self):
@@ -250,6 +252,17 @@ class FluidNet:
         if self.is_bank:
             self._not_scalenet("packed_for")
         return self._ensure_packed(device).packed
+
+    def step_net(self, device):
+        """(kind, packed) for the native step (ext.simulate_step_'s net_kind and net, fnx_simulate_step_net): 'scalenet' or 'bank' and
+        the image of that kind on `device`.  What simulate() asks a net for; `packed_for` stays the ScaleNet image alone.  The
+        'FluidNet3D' model raises: the native step does not take the Conv3d bank net, simulate() runs it operator by operator."""
+        if not self.is_bank:
+            return "scalenet", self.packed_for(device)
+        if self.is_bank3d:
+            raise RuntimeError("FluidNet.step_net: this net is the 'FluidNet3D' bank model, which the native step does not take "
+                               "(simulate() runs it operator by operator; net.bank(x) and net(input) run the bank kernels)")
+        return "bank", self._ensure_packed(device).packed
 
     def __call__(self, input_):
         ms = self._ensure_packed(input_.device)

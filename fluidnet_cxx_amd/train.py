@@ -248,6 +248,14 @@ class _FluidNetTrainBase(torch.nn.Module):
         z-slab driver ask a net for it, as they ask FluidNet."""
         return self._packed(device)[0]
 
+    def step_net(self, device):
+        """(kind, packed) for the native step, as FluidNet.step_net: the image of the CURRENT parameter values (_repack looks at every
+        parameter's _version, so an optimiser step or load_state_dict is followed by a new image)."""
+        if self._api.bank and self._NDIM == 3:
+            raise RuntimeError(f"{type(self).__name__}.step_net: this net is the 'FluidNet3D' bank model, which the native step does not "
+                               "take (simulate() runs it operator by operator)")
+        return ("bank" if self._api.bank else "scalenet"), self._packed(device)[0]
+
     def state_dict(self, *args, destination=None, prefix="", keep_vars=False):
         if args:                                  # the deprecated positional form (destination, prefix, keep_vars)
             destination = args[0]
@@ -293,7 +301,7 @@ class FluidNetBankTrain(_FluidNetTrainBase):
     weights.make_banknet_weights(0).  load_state_dict requires the twelve tensors and keeps multiScale.* / scale.*, as FluidNet does for
     this model; `net.bank(x)`, x (B,2,H,W) -> p (B,1,H,W), is the net alone, differentiable like forward().  2D, H and W multiples of 4."""
 
-    is_bank = True                       # simulate() runs such a net operator by operator
+    is_bank = True                       # step_net() hands the native step a bank image
     _UNUSED = _BANK_UNUSED_PREFIXES
 
     def _check_model(self, mconf, name):
@@ -328,8 +336,8 @@ class FluidNetBankTrain(_FluidNetTrainBase):
         return _repack(self, device)
 
     def _not_scalenet(self, what):
-        raise RuntimeError(f"{type(self).__name__}.{what}: this net is the 'FluidNet' bank model; the native step and the z-slab drivers "
-                           "take the ScaleNet image only (net.bank(x) and net(input) run the bank kernels)")
+        raise RuntimeError(f"{type(self).__name__}.{what}: this net is the 'FluidNet' bank model; the z-slab drivers take the ScaleNet image only "
+                           "(net.step_net(device) is what the native step takes; net.bank(x) and net(input) run the bank kernels)")
 
     @property
     def packed(self):

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define FNX_ABI_VERSION 34
+#define FNX_ABI_VERSION 35
 
 enum {
   FNX_OK = 0,
@@ -378,7 +378,8 @@ typedef struct FnxStepParams {
                                  stands on entry (the previous step's pressure; p = 0 gives the cold solve).  static_flags bits 0
                                  and 3 mean for 3 and 4 what they mean for 2.  The net's scratch and the solve's vectors overlap
                                  in the workspace tail -- the net has finished before the solve starts and the solve takes only
-                                 st->p from it -- so fnx_workspace_bytes(FNX_OP_STEP) is what it was before ABI 27 */
+                                 st->p from it -- so fnx_workspace_bytes(FNX_OP_STEP) is what it was before ABI 27.
+                                 ABI 35: the net of methods 1 and 3 is the ScaleNet, or the 2D bank net through fnx_simulate_step_net */
   float normalize_threshold;  /* mconf['normalizeInputThreshold'] (convnet) */
   int   precision_mode;       /* convnet: FNX_PRECISION_FP32 (0, the default), _FP32_DIRECT, _BF16X6 or _BF16X3, see fnx_multiscale_forward */
   int   static_flags;         /* promises about the previous fnx_simulate_step on this workspace (no reference key; every
@@ -428,7 +429,8 @@ typedef struct FnxState {
   const float* flags;
   const float* UBC; const float* UBCInvMask;                 /* may be NULL */
   const float* densityBC; const float* densityBCInvMask;     /* may be NULL */
-  const void*  net;  /* packed ScaleNet weights from fnx_scalenet_pack (methods 1 and 3), else NULL */
+  const void*  net;  /* packed ScaleNet weights from fnx_scalenet_pack (methods 1 and 3), else NULL.  ABI 35, fnx_simulate_step_net: the
+                        image of its net_kind -- fnx_banknet_pack's for FNX_NET_BANK */
   /* Optional (B,1,D,H,W) bytes from fnx_bc_classify, or NULL: bit 0 = setConstVals is x*1+0 for every velocity component
    * of the cell, bit 1 = the same for the density.  The BC stages then skip the 8 BC loads of such a cell (32 of its 64-68
    * bytes) and apply t = x*1, t + 0 directly: same bits.  Only valid while the four BC arrays do not change. */
@@ -449,6 +451,23 @@ int fnx_bc_classify(const FnxGrid* g, const FnxState* st, unsigned char* bc_clas
 
 int fnx_simulate_step(const FnxGrid* g, const FnxStepParams* prm, const FnxState* st,
                       void* ws, size_t ws_bytes, void* stream);
+
+/* ABI 35: the step with the net of methods 1 and 3 named.  st->net is the image of that kind: fnx_scalenet_pack's (FNX_NET_SCALENET) or
+ * fnx_banknet_pack's (FNX_NET_BANK: the 'FluidNet' bank model, 2D).  fnx_simulate_step(...) is
+ * fnx_simulate_step_net(..., FNX_NET_SCALENET, ...); methods 0, 2 and 4 ignore net_kind as they ignore st->net.  With FNX_NET_BANK the
+ * launches around the net are the ScaleNet step's (the per-sample scale, the fused input pass, the fused pass behind the net; with
+ * flags_stick the unfused ones; method 3: the un-normalised pressure into st->p), only the net in the middle is fnx_banknet_forward's,
+ * and the results are bit for bit those of the operators composed by hand around fnx_fluidnet_bank_forward.  The net's workspace (20 B a
+ * cell, plus 12 B for its input and output) is carved from the step's scratch tail, which is sized for the ScaleNet's ~1 KB a cell:
+ * fnx_workspace_bytes(FNX_OP_STEP) and FNX_OP_STEP_STATIC are what they were, and a grid whose tail were too small is FNX_EWORKSPACE.
+ * Refused before the first launch, each text starting with "fnx_simulate_step_net:" (methods 1 and 3): an unknown net_kind; FNX_NET_BANK
+ * on a 3D grid ("2D only"); H or W that is no positive multiple of 4; the bf16 modes ("fp32 arithmetic only"); a compute window or
+ * z-slab view with FNX_NET_BANK; and FNX_NET_BANK3D, the kind of fnx_banknet3d_pack's image, which the step does not take yet ("not
+ * built into the step": the Conv3d bank net runs through fnx_fluidnet_bank3d_forward, around the operators).  fnx_slab_step takes the
+ * ScaleNet image only. */
+enum { FNX_NET_SCALENET = 0, FNX_NET_BANK = 1, FNX_NET_BANK3D = 2 };
+int fnx_simulate_step_net(const FnxGrid* g, const FnxStepParams* prm, const FnxState* st, int net_kind,
+                          void* ws, size_t ws_bytes, void* stream);
 
 /* The two fused stages of fnx_simulate_step, exposed for drivers that interleave their own work (halo exchange):
  *   pre : simulate.py:96-133 + :144  U_adv, rho_adv (advection outputs) -> st->U, st->density, div
@@ -724,8 +743,8 @@ size_t fnx_banknet_ws_bytes(const FnxGrid* g, int whole_forward);
 int fnx_banknet_forward(const FnxGrid* g, const void* packed, const float* x, float* p, int precision_mode, void* ws, size_t ws_bytes,
                         void* stream);
 /* fnx_fluidnet_forward's contract with the bank net in the middle: input (B,5,1,H,W) = [p, U, flags, density] -> p_out (B,1,1,H,W),
- * U_out (B,2,1,H,W); the launches around the net are fnx_fluidnet_forward's.  fnx_simulate_step, fnx_slab_step and FnxState.net take the
- * ScaleNet image only. */
+ * U_out (B,2,1,H,W); the launches around the net are fnx_fluidnet_forward's.  fnx_simulate_step and fnx_slab_step take the ScaleNet
+ * image only; fnx_simulate_step_net (ABI 35) takes this net's as FNX_NET_BANK. */
 int fnx_fluidnet_bank_forward(const FnxGrid* g, const void* packed, const float* input, float normalize_threshold, float* p_out,
                               float* U_out, int precision_mode, void* ws, size_t ws_bytes, void* stream);
 
@@ -756,8 +775,8 @@ int fnx_banknet3d_launch_plan(const FnxGrid* g, int level, int plan[6]);
 int fnx_banknet3d_forward(const FnxGrid* g, const void* packed, const float* x, float* p, int precision_mode, void* ws, size_t ws_bytes,
                           void* stream);
 /* fnx_fluidnet_forward's contract with this net in the middle: input (B,6,D,H,W) = [p, U, flags, density] -> p_out (B,1,D,H,W),
- * U_out (B,3,D,H,W); the launches around the net are fnx_fluidnet_bank_forward's on three velocity components.  fnx_simulate_step,
- * fnx_slab_step and FnxState.net take the ScaleNet image only. */
+ * U_out (B,3,D,H,W); the launches around the net are fnx_fluidnet_bank_forward's on three velocity components.  fnx_simulate_step
+ * and fnx_slab_step take the ScaleNet image only, and fnx_simulate_step_net (ABI 35) refuses this net's kind, FNX_NET_BANK3D. */
 int fnx_fluidnet_bank3d_forward(const FnxGrid* g, const void* packed, const float* input, float normalize_threshold, float* p_out,
                                 float* U_out, int precision_mode, void* ws, size_t ws_bytes, void* stream);
 
