@@ -62,8 +62,7 @@ SCRATCH_FREE = {
                           "(full resolution) the tail's 24 in registers for the whole z-march at two waves a SIMD; a spill puts a scratch "
                           "reload in front of every MFMA.  conv1 keeps the 32 accumulators of a pair of cells and reads its weights "
                           "from LDS; scratch there would mean the 880 weights were hoisted into registers"),
-    "fnx_banknet3d_train.hip": (["bank3d_tail_tape_kernel", "bank3d_tail_bwd_kernel", "bank3d_conv_bwd_kernel", "bank3d_wgrad_kernel",
-                                 "bank3d_conv1_bwd_kernel"],
+    "fnx_banknet3d_train.hip": (["bank3d_tail_tape_kernel", "bank3d_conv_bwd_kernel", "bank3d_wgrad_kernel", "bank3d_conv1_bwd_kernel"],
                                 "the convolution body keeps its 108 MFMA weight operands in registers for the whole z-march, and the "
                                 "weight-gradient kernel its 27 accumulators (108 registers) across all the items of a workgroup, both at "
                                 "two waves a SIMD; the tail and conv1 kernels keep their accumulators across the cell march; a spill puts "

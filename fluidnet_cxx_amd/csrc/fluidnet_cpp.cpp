@@ -700,18 +700,23 @@ Tensor scalenet_pack_t(bool is3d, Tensor blob) {
   return packed;
 }
 
-// -> (name, offset, C, H, W) per tape entry in 2D, (name, offset, C, D, H, W) in 3D
+// A tape layout of the C ABI -> (name, offset, C, H, W) per tape entry for FnxTapeEntry, (name, offset, C, D, H, W) for FnxTapeEntry3D
+template <typename Entry>
+static std::vector<py::tuple> tape_tuples(const FnxGrid& g, int n, size_t (*layout)(const FnxGrid*, Entry*)) {
+  std::vector<Entry> e(n);
+  if (layout(&g, e.data()) == 0) check_status(FNX_EINVAL);
+  std::vector<py::tuple> out;
+  for (const Entry& t : e) {
+    if constexpr (std::is_same_v<Entry, FnxTapeEntry3D>) out.push_back(py::make_tuple(std::string(t.name), (int64_t)t.offset, t.C, t.D, t.H, t.W));
+    else out.push_back(py::make_tuple(std::string(t.name), (int64_t)t.offset, t.C, t.H, t.W));
+  }
+  return out;
+}
+
 std::vector<py::tuple> multiscale_tape_layout(bool is3d, int64_t B, int64_t D, int64_t H, int64_t W) {
   const FnxGrid g = make_grid(B, D, H, W, is3d);
-  const size_t n = fnx_multiscale_tape_entries();
-  std::vector<FnxTapeEntry> e2(n);
-  std::vector<FnxTapeEntry3D> e3(n);
-  if ((is3d ? fnx_multiscale3d_tape_layout(&g, e3.data()) : fnx_multiscale_tape_layout(&g, e2.data())) == 0) check_status(FNX_EINVAL);
-  std::vector<py::tuple> out;
-  for (size_t q = 0; q < n; ++q)
-    out.push_back(is3d ? py::make_tuple(std::string(e3[q].name), (int64_t)e3[q].offset, e3[q].C, e3[q].D, e3[q].H, e3[q].W)
-                       : py::make_tuple(std::string(e2[q].name), (int64_t)e2[q].offset, e2[q].C, e2[q].H, e2[q].W));
-  return out;
+  return is3d ? tape_tuples(g, fnx_multiscale_tape_entries(), fnx_multiscale3d_tape_layout)
+              : tape_tuples(g, fnx_multiscale_tape_entries(), fnx_multiscale_tape_layout);
 }
 
 // gd (B,1,Do,Ho,Wo) -> gs (B,1,Di,Hi,Wi): fnx_trilinear_upsample_backward
@@ -844,21 +849,11 @@ static Tensor bank_pack_t(const BankApi* net, Tensor blob) {
 
 // -> (name, offset, C, H, W) per tape entry
 std::vector<py::tuple> banknet_tape_layout(int64_t B, int64_t H, int64_t W) {
-  const FnxGrid g = make_grid(B, 1, H, W, false);
-  std::vector<FnxTapeEntry> e(fnx_banknet_tape_entries());
-  if (fnx_banknet_tape_layout(&g, e.data()) == 0) check_status(FNX_EINVAL);
-  std::vector<py::tuple> out;
-  for (const FnxTapeEntry& t : e) out.push_back(py::make_tuple(std::string(t.name), (int64_t)t.offset, t.C, t.H, t.W));
-  return out;
+  return tape_tuples(make_grid(B, 1, H, W, false), fnx_banknet_tape_entries(), fnx_banknet_tape_layout);
 }
 // -> (name, offset, C, D, H, W) per tape entry
 std::vector<py::tuple> banknet3d_tape_layout(int64_t B, int64_t D, int64_t H, int64_t W) {
-  const FnxGrid g = make_grid(B, D, H, W, true);
-  std::vector<FnxTapeEntry3D> e(fnx_banknet3d_tape_entries());
-  if (fnx_banknet3d_tape_layout(&g, e.data()) == 0) check_status(FNX_EINVAL);
-  std::vector<py::tuple> out;
-  for (const FnxTapeEntry3D& t : e) out.push_back(py::make_tuple(std::string(t.name), (int64_t)t.offset, t.C, t.D, t.H, t.W));
-  return out;
+  return tape_tuples(make_grid(B, D, H, W, true), fnx_banknet3d_tape_entries(), fnx_banknet3d_tape_layout);
 }
 
 // x (B,2,[D,]H,W) -> p, tape

@@ -6,9 +6,9 @@
 //             of fnx_banknet3d_tile.h under its `tail + tape` epilogue, which also stores b1, t, c2a, c2b and c3 from the accumulator
 //             registers.  The same arithmetic in the same order, so p has the inference forward's bits.  No workspace.
 //   backward  fifteen launches, then one reduction:
-//     bank3d_tail_bwd_kernel     convOut, conv3 and conv2 twice over the flattened D H W cells of a sample, 16 cells a wave: the 3D sibling
-//                                of the 2D unit's bank_tail_bwd_kernel with this unit's packed_t offsets (see there for the operand maps).
-//                                g_t (B,16,D,H,W) goes to the workspace.
+//     bank_tail_backward         convOut, conv3 and conv2 twice over the flattened D H W cells of a sample, 16 cells a wave: the 2D
+//                                unit's bank_tail_bwd_kernel itself (see there for the operand maps), launched on the 1x1x1 block of
+//                                this unit's packed_t through fnx_banknet_train.h.  g_t (B,16,D,H,W) goes to the workspace.
 //     bank3d_pool_bwd_kernel     one streaming pass over g_t: g_b2 = (b2 > 0) x the sum of the 2x2x2 children, g_b4 = (b4 > 0) x the sum of
 //                                the 4x4x4 children (in the order z, y, x), and g_t becomes g_b1 = g_t (b1 > 0) in place.
 //     bank3d_conv_bwd_kernel     the forward's z-marching convolution body on the transposed, tap-flipped weights of packed_t with a zero
@@ -23,8 +23,7 @@
 // A launch with partial sums has min(work items, cap) workgroups and workgroup s takes the items s, s + n, ...: the split is a function of
 // (B, D, H, W) alone (fnx_banknet3d_backward_plan).  No atomics, no host synchronisation; grad_p, x and the tape are only read.  Every
 // index into an activation or gradient tensor is 64-bit.
-#include "fnx_banknet3d_tile.h"
-#include <stdio.h>
+#include "fnx_banknet_train.h"
 
 namespace fnx {
 // fnx_banknet3d.hip: conv1 (x -> a, a2, a4) and the five ReLU convolutions of the forward, into the eight tensors given
@@ -33,53 +32,9 @@ void bank3d_forward_front(int B, int D, int H, int W, const float* pk, const flo
 
 namespace {
 
-// ---- the tape: the 2D tape's entries (fnx_banknet_train.hip) as contiguous (B,C,d,h,w) tensors ----
-constexpr int N_BANK3D_TAPE = 14;
-enum { TP_A, TP_H1, TP_B1, TP_A2, TP_H2, TP_B2, TP_A4, TP_H4, TP_B4, TP_T, TP_C2A, TP_C2B, TP_C3, TP_X };
-struct Bank3dTapeEntry { const char* name; size_t off; int C, D, H, W; };
-struct Bank3dTapeLayout { Bank3dTapeEntry e[N_BANK3D_TAPE]; size_t floats; };
-inline size_t al64(size_t x) { return (x + 63) & ~(size_t)63; }
-Bank3dTapeLayout bank3d_tape_layout(int B, int D, int H, int W) {
-  static const char* const names[N_BANK3D_TAPE] = {"a", "h1", "b1", "a2", "h2", "b2", "a4", "h4", "b4", "t", "c2a", "c2b", "c3", "x"};
-  Bank3dTapeLayout T{};
-  size_t off = 0;
-  for (int n = 0; n < N_BANK3D_TAPE; ++n) {
-    const int R = n < TP_A2 || n >= TP_T ? 1 : (n < TP_A4 ? 2 : 4), C = n == TP_C3 ? 8 : (n == TP_X ? 2 : 16);
-    T.e[n] = Bank3dTapeEntry{names[n], off, C, D / R, H / R, W / R};
-    off = al64(off + (size_t)B * C * (D / R) * (H / R) * (W / R));
-  }
-  T.floats = off;
-  return T;
-}
-
-// ---- packed_t: what the backward reads of the weights (floats) ----
-constexpr int PT3_WB0T = 0;          // [tap 27][kc 4][lane 64] = W[cout = 4 kc + (lane >> 4)][cin = lane & 15][26 - tap]: the A operand of the
-constexpr int PT3_WB2T = 6912;       //   transposed, tap-flipped convolution in the forward kernel's order
-constexpr int PT3_ZERO = 13824;      // 16 zeros: its bias
-constexpr int PT3_W2T = 13840;       // [r 4][lane 64] = W[cout = 4 (lane >> 4) + r][cin = lane & 15]
-constexpr int PT3_W3T = 14096;       //   (conv3: zero for cout >= 8)
-constexpr int PT3_WO = 14352;        // 16: convOut's weight of input channel c, zero for c >= 8
-constexpr int PT3_FLOATS = 14368;
-
+// packed_t of the 3D net: fnx_banknet_train.h with 27 taps
 __global__ void bank3d_pack_t_kernel(const float* __restrict__ blob, float* __restrict__ pt) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= PT3_FLOATS) return;
-  // the 1x1x1 layers sit behind conv2's weight at the 2D blob's distances (fnx_banknet_tile.h)
-  constexpr int W3 = B3_W2 + BLOB_W3 - BLOB_W2, WO = B3_W2 + BLOB_WO - BLOB_W2;
-  float v = 0.f;
-  if (i < PT3_ZERO) {
-    const int j = i % 6912, src = i < PT3_WB2T ? B3_WB0 : B3_WB2;
-    const int lane = j & 63, kc = (j >> 6) & 3, tap = j >> 8;
-    v = blob[src + ((4 * kc + (lane >> 4)) * 16 + (lane & 15)) * 27 + 26 - tap];
-  } else if (i >= PT3_W2T && i < PT3_WO) {
-    const bool third = i >= PT3_W3T;
-    const int j = i - (third ? PT3_W3T : PT3_W2T), lane = j & 63, r = j >> 6;
-    const int cout = 4 * (lane >> 4) + r, cin = lane & 15;
-    if (!third || cout < 8) v = blob[(third ? W3 : B3_W2) + cout * 16 + cin];
-  } else if (i >= PT3_WO && i - PT3_WO < 8) {
-    v = blob[WO + i - PT3_WO];
-  }
-  pt[i] = v;
+  bank_pack_t(blob, pt, 27, B3_WB0, B3_WB2, B3_W2);
 }
 
 // ---- forward ----
@@ -91,7 +46,7 @@ __global__ __launch_bounds__(256, 2) void bank3d_tail_tape_kernel(const float* _
 }
 
 void bank3d_forward_train(int B, int D, int H, int W, const float* pk, const float* x, float* p, float* tape, hipStream_t s) {
-  const Bank3dTapeLayout T = bank3d_tape_layout(B, D, H, W);
+  const BankTapeLayout T = bank_tape_layout(3, B, D, H, W);
   auto at = [&](int n) { return tape + T.e[n].off; };
   ProfScope ps(FNX_PROF_CONV_MFMA16, s);
   bank3d_forward_front(B, D, H, W, pk, x, at(TP_A), at(TP_H1), at(TP_A2), at(TP_H2), at(TP_B2), at(TP_A4), at(TP_H4), at(TP_B4), s);
@@ -102,121 +57,10 @@ void bank3d_forward_train(int B, int D, int H, int W, const float* pk, const flo
 }
 
 // ---- backward ----
-constexpr int MAX_SPLIT3 = 512;            // workgroups of the tail's and conv1's launch: two per CU of the largest part, a constant
-constexpr int WG_SPLIT = 256;              // of a weight-gradient launch: one per CU
-// floats of a workgroup's partial sums
-constexpr int TAIL_P3 = 816;               // convOut [16][16] (row 0), conv3 [16][16] (rows 0..7), conv2 [16][16]; then their biases, 16 each
+constexpr int WG_SPLIT = 256;              // workgroups of a weight-gradient launch: one per CU (the tail's and conv1's: MAX_SPLIT)
+// floats of a workgroup's partial sums (the tail's: TAIL_P of fnx_banknet_train.h)
 constexpr int WG_P = 27 * 256 + 16;        // [tap 27][cout 16][cin 16], then the bias
 constexpr int C1_P3 = 880;                 // conv1 in the blob's own order: [16][2][27], then the bias
-
-// the 2D unit's bank_tail_bwd_kernel over N = D H W flattened cells of a sample (its text stays in its own unit: moving it into a shared
-// header changed that kernel's register count)
-__global__ __launch_bounds__(256) void bank3d_tail_bwd_kernel(const float* __restrict__ pt, const float* __restrict__ grad_p,
-                                                              const float* __restrict__ tt, const float* __restrict__ c2a,
-                                                              const float* __restrict__ c2b, const float* __restrict__ c3,
-                                                              float* __restrict__ g_t, float* __restrict__ partial, int N, int ups, int nunits) {
-  constexpr int TS = 16 * 17;                 // a 16 x 16 transpose tile, pitch 17
-  __shared__ float st[4 * 8 * TS];
-  const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, c = lane & 15;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  float* const sw = st + wave * 8 * TS;
-  float a2t[4], a3t[4], wo[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    a2t[r] = pt[PT3_W2T + r * 64 + lane];
-    a3t[r] = pt[PT3_W3T + r * 64 + lane];
-    wo[r] = pt[PT3_WO + 4 * g + r];
-  }
-  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-  f32x4 dO = zero4, d3 = zero4, d2 = zero4;
-  float bO = 0.f, b3 = 0.f, b2 = 0.f;
-  for (int u = blockIdx.x; u < nunits; u += gridDim.x) {
-    const int b = u / ups, n = (u - b * ups) * 64 + wave * 16 + c;
-    const bool valid = n < N;
-    const int nn = valid ? n : N - 1;
-    const float gp = valid ? grad_p[(size_t)b * N + nn] : 0.f;
-    const size_t o16 = ((size_t)b * 16 + 4 * g) * N + nn, o8 = ((size_t)b * 8 + 4 * (g & 1)) * N + nn;
-    f32x4 vc3, vc2b, vc2a, vt;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      vc3[r] = valid && g < 2 ? c3[o8 + (size_t)r * N] : 0.f;
-      vc2b[r] = valid ? c2b[o16 + (size_t)r * N] : 0.f;
-      vc2a[r] = valid ? c2a[o16 + (size_t)r * N] : 0.f;
-      vt[r] = valid ? tt[o16 + (size_t)r * N] : 0.f;
-    }
-    // the gradients of the pre-activations: register r of a lane is channel 4g + r of its cell
-    f32x4 gc3, gc2b = zero4, gc2a = zero4, gt = zero4;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) gc3[r] = vc3[r] > 0.f ? gp * wo[r] : 0.f;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) gc2b = __builtin_amdgcn_mfma_f32_16x16x4f32(a3t[r], gc3[r], gc2b, 0, 0, 0);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) gc2b[r] = vc2b[r] > 0.f ? gc2b[r] : 0.f;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) gc2a = __builtin_amdgcn_mfma_f32_16x16x4f32(a2t[r], gc2b[r], gc2a, 0, 0, 0);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) gc2a[r] = vc2a[r] > 0.f ? gc2a[r] : 0.f;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) gt = __builtin_amdgcn_mfma_f32_16x16x4f32(a2t[r], gc2a[r], gt, 0, 0, 0);
-    if (valid) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) g_t[o16 + (size_t)r * N] = gt[r];
-    }
-    // [channel][cell] tiles for the weight gradients: grad_p (row 0), g_c3, g_c2b, g_c2a; c3, c2b, c2a, t
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int at = (4 * g + r) * 17 + c;
-      sw[0 * TS + at] = (g == 0 && r == 0) ? gp : 0.f;
-      sw[1 * TS + at] = gc3[r];
-      sw[2 * TS + at] = gc2b[r];
-      sw[3 * TS + at] = gc2a[r];
-      sw[4 * TS + at] = vc3[r];
-      sw[5 * TS + at] = vc2b[r];
-      sw[6 * TS + at] = vc2a[r];
-      sw[7 * TS + at] = vt[r];
-    }
-    __syncthreads();
-    // lane: channel c of both operands, cell 4 step + g
-#pragma unroll
-    for (int step = 0; step < 4; ++step) {
-      const int at = c * 17 + 4 * step + g;
-      const float aO = sw[0 * TS + at], a3 = sw[1 * TS + at], a2b = sw[2 * TS + at], a2a = sw[3 * TS + at];
-      dO = __builtin_amdgcn_mfma_f32_16x16x4f32(aO, sw[4 * TS + at], dO, 0, 0, 0);
-      d3 = __builtin_amdgcn_mfma_f32_16x16x4f32(a3, sw[5 * TS + at], d3, 0, 0, 0);
-      d2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a2b, sw[6 * TS + at], d2, 0, 0, 0);     // the second application: (g at c2b, c2a)
-      d2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a2a, sw[7 * TS + at], d2, 0, 0, 0);     // the first: (g at c2a, t)
-      bO += aO;
-      b3 += a3;
-      b2 += a2b + a2a;
-    }
-  }
-  // the four waves in order: D register r is row 4g + r, column c; a bias sum is per (channel c, cell slot g)
-  __syncthreads();
-  float* const red = st;                      // [wave][768 + 192]
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    red[wave * 960 + 0 + (4 * g + r) * 16 + c] = dO[r];
-    red[wave * 960 + 256 + (4 * g + r) * 16 + c] = d3[r];
-    red[wave * 960 + 512 + (4 * g + r) * 16 + c] = d2[r];
-  }
-  red[wave * 960 + 768 + lane] = bO;
-  red[wave * 960 + 832 + lane] = b3;
-  red[wave * 960 + 896 + lane] = b2;
-  __syncthreads();
-  float* const po = partial + (size_t)blockIdx.x * TAIL_P3;
-  for (int q = tid; q < TAIL_P3; q += 256) {
-    float v = 0.f;
-    if (q < 768) {
-      v = (red[q] + red[960 + q]) + (red[1920 + q] + red[2880 + q]);
-    } else {
-      const int which = (q - 768) >> 4, ch = (q - 768) & 15;
-      for (int w = 0; w < 4; ++w)
-        for (int k = 0; k < 4; ++k) v += red[w * 960 + 768 + which * 64 + k * 16 + ch];
-    }
-    po[q] = v;
-  }
-}
 
 // One thread per (sample, channel, quarter-level cell): its 4 x 4 x 4 children of g_t, four consecutive x at a time.
 // gt (B,16,D,H,W) becomes g_b1 in place; gb2 (B,16,D/2,H/2,W/2), gb4 (B,16,D/4,H/4,W/4).
@@ -500,22 +344,15 @@ __global__ __launch_bounds__(256) void bank3d_reduce_kernel(Bank3dPartials P, fl
       for (int s = 0; s < ns.wg[l]; ++s) v += (double)src[(size_t)s * WG_P + at];
     }
   } else {
-    const int q2 = q - B3_W2 + BLOB_W2;                           // the tail at the 2D blob's distances
-    int at;
-    if (q2 < BLOB_B2) at = 512 + (q2 - BLOB_W2);
-    else if (q2 < BLOB_W3) at = 800 + (q2 - BLOB_B2);
-    else if (q2 < BLOB_B3) at = 256 + (q2 - BLOB_W3);
-    else if (q2 < BLOB_WO) at = 784 + (q2 - BLOB_B3);
-    else if (q2 < BLOB_BO) at = q2 - BLOB_WO;
-    else at = 768;
-    for (int s = 0; s < ns.tail; ++s) v += (double)P.tail[(size_t)s * TAIL_P3 + at];
+    const int at = bank_tail_partial_at(q - B3_W2 + BLOB_W2);      // the tail at the 2D blob's distances
+    for (int s = 0; s < ns.tail; ++s) v += (double)P.tail[(size_t)s * TAIL_P + at];
   }
   out[q] = (float)v;
 }
 
 // the backward's launch plan and workspace: a function of (B, D, H, W) alone
 struct Bank3dBwdPlan {
-  int ups, nunits;                 // units of 64 cells per sample, in all
+  BankUnits u;                     // the tail's and conv1's units of 64 cells
   Bank3dWgPlan wg[3];              // quarter, half, full
   Bank3dSplits ns;
   float *g1, *h1, *g2, *h2, *g4, *h4;        // per level: g_b, over which g_a is written, and g_h
@@ -525,20 +362,19 @@ struct Bank3dBwdPlan {
 Bank3dBwdPlan bank3d_bwd_plan(int B, int D, int H, int W, void* base) {
   Bank3dBwdPlan p{};
   const size_t N = (size_t)D * H * W;
-  p.ups = (int)((N + 63) / 64);
-  p.nunits = B * p.ups;                                           // < 2^31: B <= 65535 and N < 2^31 would not do; see bank3d_bwd_range_ok
+  p.u = bank_units(B, N);                                         // < 2^31: B <= 65535 and N < 2^31 would not do; see bank3d_bwd_range_ok
   for (int l = 0; l < 3; ++l) {
     const int R = 4 >> l;
     p.wg[l] = bank3d_wg_plan(B, D / R, H / R, W / R);
     p.ns.wg[l] = p.wg[l].groups;
   }
-  p.ns.tail = p.ns.c1 = p.nunits < MAX_SPLIT3 ? p.nunits : MAX_SPLIT3;
+  p.ns.tail = p.ns.c1 = p.u.split;
   size_t off = 0;
   auto take = [&](size_t floats) { float* r = base ? (float*)((char*)base + off) : nullptr; off += al256(floats * 4); return r; };
   p.g1 = take(B * 16 * N); p.h1 = take(B * 16 * N);               // 2 x (64 + 8 + 1) = 146 bytes a full-resolution cell
   p.g2 = take(B * 16 * (N / 8)); p.h2 = take(B * 16 * (N / 8));
   p.g4 = take(B * 16 * (N / 64)); p.h4 = take(B * 16 * (N / 64));
-  p.ptail = take((size_t)p.ns.tail * TAIL_P3);
+  p.ptail = take((size_t)p.ns.tail * TAIL_P);
   for (int l = 0; l < 3; ++l) {
     p.pw2[l] = take((size_t)p.ns.wg[l] * WG_P);
     p.pw0[l] = take((size_t)p.ns.wg[l] * WG_P);
@@ -554,12 +390,12 @@ inline bool bank3d_bwd_range_ok(const FnxGrid* g) {
 
 void bank3d_backward(int B, int D, int H, int W, const float* pt, const float* x, const float* grad_p, const float* tape, float* grad_blob,
                      void* ws, hipStream_t s) {
-  const Bank3dTapeLayout T = bank3d_tape_layout(B, D, H, W);
+  const BankTapeLayout T = bank_tape_layout(3, B, D, H, W);
   const Bank3dBwdPlan p = bank3d_bwd_plan(B, D, H, W, ws);
   auto at = [&](int n) { return tape + T.e[n].off; };
   ProfScope ps(FNX_PROF_CONV_MFMA16, s);
   const int N = D * H * W;
-  bank3d_tail_bwd_kernel<<<p.ns.tail, 256, 0, s>>>(pt, grad_p, at(TP_T), at(TP_C2A), at(TP_C2B), at(TP_C3), p.g1, p.ptail, N, p.ups, p.nunits);
+  bank_tail_backward(pt + PT3_W2T, grad_p, at(TP_T), at(TP_C2A), at(TP_C2B), at(TP_C3), p.g1, p.ptail, N, p.u.ups, p.u.nunits, p.ns.tail, s);
   {
     const size_t total = (size_t)B * 16 * (N / 64);
     bank3d_pool_bwd_kernel<<<(unsigned)((total + 255) / 256), 256, 0, s>>>(p.g1, at(TP_B1), at(TP_B2), at(TP_B4), p.g2, p.g4, D, H, W, total);
@@ -577,49 +413,31 @@ void bank3d_backward(int B, int D, int H, int W, const float* pt, const float* x
   level(0, 4, p.g4, p.h4, at(TP_H4), at(TP_A4));
   level(1, 2, p.g2, p.h2, at(TP_H2), at(TP_A2));
   level(2, 1, p.g1, p.h1, at(TP_H1), at(TP_A));
-  bank3d_conv1_bwd_kernel<<<dim3((unsigned)p.ns.c1, 2), 256, 0, s>>>(x, at(TP_A), p.g1, p.g2, p.g4, p.pc1, D, H, W, p.ups, p.nunits);
+  bank3d_conv1_bwd_kernel<<<dim3((unsigned)p.ns.c1, 2), 256, 0, s>>>(x, at(TP_A), p.g1, p.g2, p.g4, p.pc1, D, H, W, p.u.ups, p.u.nunits);
   Bank3dPartials P{};
   P.tail = p.ptail; P.c1 = p.pc1;
   for (int l = 0; l < 3; ++l) { P.w2[l] = p.pw2[l]; P.w0[l] = p.pw0[l]; }
   bank3d_reduce_kernel<<<(B3_FLOATS + 255) / 256, 256, 0, s>>>(P, grad_blob, p.ns);
 }
 
-// FluidNet.forward for training with the bank net in the middle: one workspace size for the forward and the backward
-size_t bank3d_train_ws_bytes(const FnxGrid* g) {
-  const size_t fwd = fluidnet_ws_layout(g->B, (size_t)g->D * g->H * g->W, 0, nullptr).head;
-  const size_t bwd = fluidnet_train_bwd_ws(3, g, nullptr).bytes + bank3d_bwd_plan(g->B, g->D, g->H, g->W, nullptr).bytes;
-  return fwd > bwd ? fwd : bwd;
-}
-size_t bank3d_bwd_ws_bytes(const FnxGrid* g) { return bank3d_bwd_plan(g->B, g->D, g->H, g->W, nullptr).bytes; }
+size_t bank3d_bwd_plan_bytes(int B, int D, int H, int W) { return bank3d_bwd_plan(B, D, H, W, nullptr).bytes; }
 
 bool bank3d_sized(const FnxGrid* g) { return g && g->is3D && g->B >= 1 && g->D >= 4 && g->H >= 4 && g->W >= 4; }
-
-// check_bank_call and, behind it, the backward's own range
-int check_bank3d_bwd_call(const char* fn, const FnxGrid* g, bool args, int precision_mode, size_t (*want_of)(const FnxGrid*), size_t ws_bytes) {
-  if (g && args && g->is3D && g->B >= 1 && g->D >= 4 && g->H >= 4 && g->W >= 4 && !bank3d_bwd_range_ok(g))
-    return set_error(FNX_EINVAL, "%s: B * D * H * W = %d * %zu cells is beyond the bank backward's launch range", fn, g->B,
-                     (size_t)g->D * g->H * g->W);
-  return check_bank_call(fn, 3, g, args, precision_mode, want_of, ws_bytes);
-}
+constexpr BankTrainDim DIM3 = {3, bank3d_sized, bank3d_bwd_range_ok, bank3d_forward_train, bank3d_backward, bank3d_bwd_plan_bytes};
 
 }  // namespace
 }  // namespace fnx
 
 extern "C" {
 
-int fnx_banknet3d_tape_entries(void) { return fnx::N_BANK3D_TAPE; }
+int fnx_banknet3d_tape_entries(void) { return fnx::N_BANK_TAPE; }
 
 size_t fnx_banknet3d_tape_layout(const FnxGrid* g, FnxTapeEntry3D* entries) {
   if (!fnx::bank3d_sized(g) || g->D % 4 || g->H % 4 || g->W % 4) {
     fnx::set_error(FNX_EINVAL, "%s: a 3D grid with D, H and W positive multiples of 4 is needed", __func__);
     return 0;
   }
-  const fnx::Bank3dTapeLayout T = fnx::bank3d_tape_layout(g->B, g->D, g->H, g->W);
-  for (int i = 0; entries && i < fnx::N_BANK3D_TAPE; ++i) {
-    snprintf(entries[i].name, sizeof(entries[i].name), "%s", T.e[i].name);
-    entries[i].offset = T.e[i].off; entries[i].C = T.e[i].C; entries[i].D = T.e[i].D; entries[i].H = T.e[i].H; entries[i].W = T.e[i].W;
-  }
-  return T.floats;
+  return fnx::bank_fill_tape(fnx::bank_tape_layout(3, g->B, g->D, g->H, g->W), nullptr, entries);
 }
 
 size_t fnx_banknet3d_packed_t_bytes(void) { return (size_t)fnx::PT3_FLOATS * sizeof(float); }
@@ -630,10 +448,7 @@ int fnx_banknet3d_pack_t(const float* weights_blob, void* packed_t, void* stream
   return fnx::bank_status();
 }
 
-size_t fnx_banknet3d_backward_ws_bytes(const FnxGrid* g) {
-  if (!fnx::bank3d_sized(g) || !fnx::bank3d_bwd_range_ok(g)) return 0;
-  return fnx::bank3d_bwd_ws_bytes(g);
-}
+size_t fnx_banknet3d_backward_ws_bytes(const FnxGrid* g) { return fnx::bank_size_query<fnx::DIM3>(g, fnx::bank_bwd_ws_bytes<fnx::DIM3>); }
 
 int fnx_banknet3d_backward_launches(void) { return 8; }
 
@@ -649,64 +464,40 @@ int fnx_banknet3d_backward_plan(const FnxGrid* g, FnxBankBwdLaunch* launches) {
     L.level = level; L.items = items; L.workgroups = groups; L.cap = cap; L.partial_floats = pf; L.partial_offset = off(at);
     L.dims[0] = d0; L.dims[1] = d1; L.dims[2] = d2; L.dims[3] = d3;
   };
-  put("tail", 1, p.nunits, p.ns.tail, fnx::MAX_SPLIT3, fnx::TAIL_P3, p.ptail, p.ups, 64, 0, 0);
+  put("tail", 1, p.u.nunits, p.ns.tail, fnx::MAX_SPLIT, fnx::TAIL_P, p.ptail, p.u.ups, 64, 0, 0);
   for (int l = 0; l < 3; ++l) {
     put("wgrad.2", 4 >> l, p.wg[l].items, p.wg[l].groups, fnx::WG_SPLIT, fnx::WG_P, p.pw2[l], p.wg[l].tiles_x, p.wg[l].tiles_y, p.wg[l].chunks,
         fnx::WG_CHUNK);
     put("wgrad.0", 4 >> l, p.wg[l].items, p.wg[l].groups, fnx::WG_SPLIT, fnx::WG_P, p.pw0[l], p.wg[l].tiles_x, p.wg[l].tiles_y, p.wg[l].chunks,
         fnx::WG_CHUNK);
   }
-  put("conv1", 1, p.nunits, p.ns.c1, fnx::MAX_SPLIT3, fnx::C1_P3, p.pc1, p.ups, 64, 0, 0);
+  put("conv1", 1, p.u.nunits, p.ns.c1, fnx::MAX_SPLIT, fnx::C1_P3, p.pc1, p.u.ups, 64, 0, 0);
   return FNX_OK;
 }
 
 int fnx_banknet3d_forward_train(const FnxGrid* g, const void* packed, const float* x, float* p, float* tape, int precision_mode, void* stream) {
-  if (int rc = fnx::check_bank_call(__func__, 3, g, packed && x && p && tape, precision_mode, nullptr, 0)) return rc;
-  fnx::bank3d_forward_train(g->B, g->D, g->H, g->W, (const float*)packed, x, p, tape, (hipStream_t)stream);
-  return fnx::bank_status();
+  return fnx::bank_forward_train<fnx::DIM3>(__func__, g, packed, x, p, tape, precision_mode, stream);
 }
 
 int fnx_banknet3d_backward(const FnxGrid* g, const void* packed_t, const float* x, const float* grad_p, const float* tape, float* grad_blob,
                            int precision_mode, void* ws, size_t ws_bytes, void* stream) {
-  if (int rc = fnx::check_bank3d_bwd_call(__func__, g, packed_t && x && grad_p && tape && grad_blob && ws, precision_mode,
-                                          fnx::bank3d_bwd_ws_bytes, ws_bytes))
-    return rc;
-  fnx::bank3d_backward(g->B, g->D, g->H, g->W, (const float*)packed_t, x, grad_p, tape, grad_blob, ws, (hipStream_t)stream);
-  return fnx::bank_status();
+  return fnx::bank_backward<fnx::DIM3>(__func__, g, packed_t, x, grad_p, tape, grad_blob, precision_mode, ws, ws_bytes, stream);
 }
 
-size_t fnx_fluidnet_bank3d_train_ws_bytes(const FnxGrid* g) {
-  if (!fnx::bank3d_sized(g) || !fnx::bank3d_bwd_range_ok(g)) return 0;
-  return fnx::bank3d_train_ws_bytes(g);
-}
+size_t fnx_fluidnet_bank3d_train_ws_bytes(const FnxGrid* g) { return fnx::bank_size_query<fnx::DIM3>(g, fnx::bank_train_ws_bytes<fnx::DIM3>); }
 
 int fnx_fluidnet_bank3d_forward_train(const FnxGrid* g, const void* packed, const float* input, float normalize_threshold, float* p_out,
                                       float* U_out, float* flags_out, float* scale_out, float* tape, int precision_mode, void* ws,
                                       size_t ws_bytes, void* stream) {
-  if (int rc = fnx::check_bank3d_bwd_call(__func__, g, packed && input && p_out && U_out && flags_out && scale_out && tape && ws,
-                                          precision_mode, fnx::bank3d_train_ws_bytes, ws_bytes))
-    return rc;
-  const size_t cells = (size_t)g->D * g->H * g->W;
-  fnx::FluidnetWs w = fnx::fluidnet_ws_layout(g->B, cells, 0, ws);                 // (its head: the scales go to scale_out)
-  w.x = tape + fnx::bank3d_tape_layout(g->B, g->D, g->H, g->W).e[fnx::TP_X].off;    // the backward reads the net's input again (conv1)
-  fnx::fluidnet_split(g, input, U_out, flags_out, stream);
-  if (int rc = fnx::fluidnet_pre(g, normalize_threshold, U_out, flags_out, scale_out, w, stream)) return rc;
-  fnx::bank3d_forward_train(g->B, g->D, g->H, g->W, (const float*)packed, w.x, p_out, tape, (hipStream_t)stream);
-  if (int rc = fnx::fluidnet_post(g, p_out, U_out, flags_out, scale_out, stream)) return rc;
-  return fnx::bank_status();
+  return fnx::fluidnet_bank_forward_train<fnx::DIM3>(__func__, g, packed, input, normalize_threshold, p_out, U_out, flags_out, scale_out, tape,
+                                                     precision_mode, ws, ws_bytes, stream);
 }
 
 int fnx_fluidnet_bank3d_backward(const FnxGrid* g, const void* packed_t, const float* flags, const float* scale, const float* grad_p,
                                  const float* grad_U, const float* tape, float* grad_blob, int precision_mode, void* ws, size_t ws_bytes,
                                  void* stream) {
-  if (int rc = fnx::check_bank3d_bwd_call(__func__, g, packed_t && flags && scale && grad_p && grad_U && tape && grad_blob && ws, precision_mode,
-                                          fnx::bank3d_train_ws_bytes, ws_bytes))
-    return rc;
-  const fnx::FluidnetTrainBwdWs w = fnx::fluidnet_train_bwd_ws(3, g, ws);
-  if (int rc = fnx::fluidnet_train_gnet(3, g, flags, scale, grad_p, grad_U, w, stream)) return rc;
-  const float* x = tape + fnx::bank3d_tape_layout(g->B, g->D, g->H, g->W).e[fnx::TP_X].off;
-  fnx::bank3d_backward(g->B, g->D, g->H, g->W, (const float*)packed_t, x, w.gnet, tape, grad_blob, w.net, (hipStream_t)stream);
-  return fnx::bank_status();
+  return fnx::fluidnet_bank_backward<fnx::DIM3>(__func__, g, packed_t, flags, scale, grad_p, grad_U, tape, grad_blob, precision_mode, ws,
+                                                ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -9,7 +9,9 @@
 //                                sits on the accumulator registers (lane group g holds channels 4g .. 4g+3 of a cell) and register r IS the
 //                                B operand of output channels 4g + r, the mirror of the forward's tail.  The weight gradients are
 //                                D[cout][cin] += A[cout][k] B[k][cin] with k = four cells; the operands go through a 16 x 16 transpose in
-//                                LDS.  conv2's accumulator takes both applications.  g_t (B,16,H,W) goes to the workspace.
+//                                LDS.  conv2's accumulator takes both applications.  g_t (B,16,H,W) goes to the workspace.  It indexes
+//                                flattened cells, so it is the 3D unit's tail backward as well: bank_tail_backward, at the end of
+//                                this file, launches it on the 1x1 block of either unit's packed_t (fnx_banknet_train.h).
 //     bank_level_bwd_kernel<R>   R = 1, 2, 4: the mirror of the forward's level kernel on a TH x TW tile of level-R cells.  g_b = g_t (R = 1)
 //                                or the sum of its R x R children (the adjoint of nearest upsampling), masked by b > 0, on the tile + 2;
 //                                g_h = convT(block.2) of it masked by h > 0 on the tile + 1; g_a = convT(block.0) of that on the tile,
@@ -25,58 +27,14 @@
 //                                order quarter, half, full) and writes grad_blob.
 // A launch has min(work items, 512) workgroups and workgroup s takes the items s, s + n, ...: the split is a function of (B, H, W) alone.
 // No atomics, no host synchronisation; grad_p, x and the tape are only read.
-#include "fnx_banknet_tile.h"
-#include <stdio.h>
+#include "fnx_banknet_train.h"
 
 namespace fnx {
 namespace {
 
-// ---- the tape: every ReLU output, contiguous (B,C,h,w) tensors; a2, a4 are the pooled relu(conv1) the coarser levels start from; x is
-// the net's input, which only fnx_fluidnet_bank_forward_train writes (it builds x itself; fnx_banknet_backward is given x) ----
-constexpr int N_BANK_TAPE = 14;
-enum { TP_A, TP_H1, TP_B1, TP_A2, TP_H2, TP_B2, TP_A4, TP_H4, TP_B4, TP_T, TP_C2A, TP_C2B, TP_C3, TP_X };
-struct BankTapeEntry { const char* name; size_t off; int C, H, W; };
-struct BankTapeLayout { BankTapeEntry e[N_BANK_TAPE]; size_t floats; };
-inline size_t al64(size_t x) { return (x + 63) & ~(size_t)63; }
-BankTapeLayout bank_tape_layout(int B, int H, int W) {
-  static const char* const names[N_BANK_TAPE] = {"a", "h1", "b1", "a2", "h2", "b2", "a4", "h4", "b4", "t", "c2a", "c2b", "c3", "x"};
-  BankTapeLayout T{};
-  size_t off = 0;
-  for (int n = 0; n < N_BANK_TAPE; ++n) {
-    const int R = n < TP_A2 || n >= TP_T ? 1 : (n < TP_A4 ? 2 : 4), C = n == TP_C3 ? 8 : (n == TP_X ? 2 : 16);
-    T.e[n] = BankTapeEntry{names[n], off, C, H / R, W / R};
-    off = al64(off + (size_t)B * C * (H / R) * (W / R));
-  }
-  T.floats = off;
-  return T;
-}
-
-// ---- packed_t: what the backward reads of the weights (floats) ----
-constexpr int PT_WB0T = 0;          // [tap 9][kc 4][lane 64] = W[cout = 4 kc + (lane >> 4)][cin = lane & 15][8 - tap]: bank_conv's A operand
-constexpr int PT_WB2T = 2304;       //   of the transposed, tap-flipped convolution
-constexpr int PT_ZERO = 4608;       // 16 zeros: its bias
-constexpr int PT_W2T = 4624;        // [r 4][lane 64] = W[cout = 4 (lane >> 4) + r][cin = lane & 15]
-constexpr int PT_W3T = 4880;        //   (conv3: zero for cout >= 8)
-constexpr int PT_WO = 5136;         // 16: convOut's weight of input channel c, zero for c >= 8
-constexpr int PT_FLOATS = 5152;
-
+// packed_t of the 2D net: fnx_banknet_train.h with nine taps
 __global__ void banknet_pack_t_kernel(const float* __restrict__ blob, float* __restrict__ pt) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= PT_FLOATS) return;
-  float v = 0.f;
-  if (i < PT_ZERO) {
-    const int j = i % 2304, src = i < PT_WB2T ? BLOB_WB0 : BLOB_WB2;
-    const int lane = j & 63, kc = (j >> 6) & 3, tap = j >> 8;
-    v = blob[src + ((4 * kc + (lane >> 4)) * 16 + (lane & 15)) * 9 + 8 - tap];
-  } else if (i >= PT_W2T && i < PT_WO) {
-    const bool third = i >= PT_W3T;
-    const int j = i - (third ? PT_W3T : PT_W2T), lane = j & 63, r = j >> 6;
-    const int cout = 4 * (lane >> 4) + r, cin = lane & 15;
-    if (!third || cout < 8) v = blob[(third ? BLOB_W3 : BLOB_W2) + cout * 16 + cin];
-  } else if (i >= PT_WO && i - PT_WO < 8) {
-    v = blob[BLOB_WO + i - PT_WO];
-  }
-  pt[i] = v;
+  bank_pack_t(blob, pt, 9, BLOB_WB0, BLOB_WB2, BLOB_W2);
 }
 
 // ---- forward ----
@@ -87,8 +45,8 @@ __global__ __launch_bounds__(256) void banknet_level_tape_kernel(const float* __
   bank_level_tile<R, TH, TW, true>(pk, x, H, W, out, l2, l4, p, tape);
 }
 
-void banknet_forward_train(int B, int H, int W, const float* pk, const float* x, float* p, float* tape, hipStream_t s) {
-  const BankTapeLayout T = bank_tape_layout(B, H, W);
+void banknet_forward_train(int B, int /*D = 1*/, int H, int W, const float* pk, const float* x, float* p, float* tape, hipStream_t s) {
+  const BankTapeLayout T = bank_tape_layout(2, B, 1, H, W);
   auto at = [&](int n) { return tape + T.e[n].off; };
   ProfScope ps(FNX_PROF_CONV_MFMA16, s);
   auto grid = [&](int R, int tw) { return dim3((unsigned)((W / R + tw - 1) / tw), (unsigned)((H / R + TILE_H - 1) / TILE_H), (unsigned)B); };
@@ -101,13 +59,9 @@ void banknet_forward_train(int B, int H, int W, const float* pk, const float* x,
 }
 
 // ---- backward ----
-constexpr int MAX_SPLIT = 512;            // workgroups of a backward launch: two per CU of the largest part, a constant
-// floats of a workgroup's partial sums
-constexpr int TAIL_P = 816;               // convOut [16][16] (row 0), conv3 [16][16] (rows 0..7), conv2 [16][16]; then their biases, 16 each
+// floats of a workgroup's partial sums (the tail's: TAIL_P of fnx_banknet_train.h)
 constexpr int LEV_P = 4640;               // block.2 [tap 9][cout 16][cin 16], block.0 the same; then their biases, 16 each
 constexpr int C1_P = 304;                 // conv1 in the blob's own order: [16][18], then the bias
-
-inline int split_of(long items) { return items < MAX_SPLIT ? (int)items : MAX_SPLIT; }
 
 __global__ __launch_bounds__(256) void bank_tail_bwd_kernel(const float* __restrict__ pt, const float* __restrict__ grad_p,
                                                             const float* __restrict__ tt, const float* __restrict__ c2a,
@@ -435,13 +389,7 @@ __global__ __launch_bounds__(256) void bank_reduce_kernel(const float* __restric
     for (int s = 0; s < ns.lev[1]; ++s) v += (double)plev2[(size_t)s * LEV_P + at];
     for (int s = 0; s < ns.lev[2]; ++s) v += (double)plev1[(size_t)s * LEV_P + at];
   } else {
-    int at;
-    if (q < BLOB_B2) at = 512 + (q - BLOB_W2);
-    else if (q < BLOB_W3) at = 800 + (q - BLOB_B2);
-    else if (q < BLOB_B3) at = 256 + (q - BLOB_W3);
-    else if (q < BLOB_WO) at = 784 + (q - BLOB_B3);
-    else if (q < BLOB_BO) at = q - BLOB_WO;
-    else at = 768;
+    const int at = bank_tail_partial_at(q);
     for (int s = 0; s < ns.tail; ++s) v += (double)ptail[(size_t)s * TAIL_P + at];
   }
   out[q] = (float)v;
@@ -449,7 +397,7 @@ __global__ __launch_bounds__(256) void bank_reduce_kernel(const float* __restric
 
 // the backward's launch plan and workspace: a function of (B, H, W) alone
 struct BankBwdPlan {
-  int ups, nunits;                 // units of 64 cells per sample, in all
+  BankUnits u;                     // the tail's and conv1's units of 64 cells
   int ntx[3], nty[3], ntiles[3];   // level tiles: quarter, half, full
   BankSplits ns;
   float *gt, *ga1, *ga2, *ga4, *ptail, *plev[3], *pc1;
@@ -458,8 +406,7 @@ struct BankBwdPlan {
 BankBwdPlan bank_bwd_plan(int B, int H, int W, void* base) {
   BankBwdPlan p{};
   const size_t HW = (size_t)H * W;
-  p.ups = (int)((HW + 63) / 64);
-  p.nunits = B * p.ups;
+  p.u = bank_units(B, HW);
   for (int l = 0; l < 3; ++l) {
     const int R = 4 >> l, tw = TILE_W1;
     p.ntx[l] = (W / R + tw - 1) / tw;
@@ -467,7 +414,7 @@ BankBwdPlan bank_bwd_plan(int B, int H, int W, void* base) {
     p.ntiles[l] = B * p.ntx[l] * p.nty[l];
     p.ns.lev[l] = split_of(p.ntiles[l]);
   }
-  p.ns.tail = p.ns.c1 = split_of(p.nunits);
+  p.ns.tail = p.ns.c1 = p.u.split;
   size_t off = 0;
   auto take = [&](size_t floats) { float* r = base ? (float*)((char*)base + off) : nullptr; off += al256(floats * 4); return r; };
   p.gt = take(B * 16 * HW);
@@ -480,33 +427,39 @@ BankBwdPlan bank_bwd_plan(int B, int H, int W, void* base) {
   p.bytes = off;
   return p;
 }
+size_t bank_bwd_plan_bytes(int B, int /*D = 1*/, int H, int W) { return bank_bwd_plan(B, H, W, nullptr).bytes; }
 
-void banknet_backward(int B, int H, int W, const float* pt, const float* x, const float* grad_p, const float* tape, float* grad_blob,
-                      void* ws, hipStream_t s) {
-  const BankTapeLayout T = bank_tape_layout(B, H, W);
+void banknet_backward(int B, int /*D = 1*/, int H, int W, const float* pt, const float* x, const float* grad_p, const float* tape,
+                      float* grad_blob, void* ws, hipStream_t s) {
+  const BankTapeLayout T = bank_tape_layout(2, B, 1, H, W);
   const BankBwdPlan p = bank_bwd_plan(B, H, W, ws);
   auto at = [&](int n) { return tape + T.e[n].off; };
   ProfScope ps(FNX_PROF_CONV_MFMA16, s);
-  bank_tail_bwd_kernel<<<p.ns.tail, 256, 0, s>>>(pt, grad_p, at(TP_T), at(TP_C2A), at(TP_C2B), at(TP_C3), p.gt, p.ptail, H * W, p.ups, p.nunits);
+  bank_tail_backward(pt + PT_W2T, grad_p, at(TP_T), at(TP_C2A), at(TP_C2B), at(TP_C3), p.gt, p.ptail, H * W, p.u.ups, p.u.nunits, p.ns.tail, s);
   bank_level_bwd_kernel<4, TILE_H, TILE_W1><<<p.ns.lev[0], 256, 0, s>>>(pt, p.gt, at(TP_B4), at(TP_H4), at(TP_A4), p.ga4, p.plev[0], H, W,
                                                                         p.ntx[0], p.nty[0], p.ntiles[0]);
   bank_level_bwd_kernel<2, TILE_H, TILE_W1><<<p.ns.lev[1], 256, 0, s>>>(pt, p.gt, at(TP_B2), at(TP_H2), at(TP_A2), p.ga2, p.plev[1], H, W,
                                                                         p.ntx[1], p.nty[1], p.ntiles[1]);
   bank_level_bwd_kernel<1, TILE_H, TILE_W1><<<p.ns.lev[2], 256, 0, s>>>(pt, p.gt, at(TP_B1), at(TP_H1), at(TP_A), p.ga1, p.plev[2], H, W,
                                                                         p.ntx[2], p.nty[2], p.ntiles[2]);
-  bank_conv1_bwd_kernel<<<p.ns.c1, 256, 0, s>>>(x, at(TP_A), p.ga1, p.ga2, p.ga4, p.pc1, H, W, p.ups, p.nunits);
+  bank_conv1_bwd_kernel<<<p.ns.c1, 256, 0, s>>>(x, at(TP_A), p.ga1, p.ga2, p.ga4, p.pc1, H, W, p.u.ups, p.u.nunits);
   bank_reduce_kernel<<<(BLOB_FLOATS + 255) / 256, 256, 0, s>>>(p.ptail, p.plev[0], p.plev[1], p.plev[2], p.pc1, grad_blob, p.ns);
 }
 
-// FluidNet.forward for training with the bank net in the middle: one workspace size for the forward and the backward
-size_t bank_train_ws_bytes(const FnxGrid* g) {
-  const size_t fwd = fluidnet_ws_layout(g->B, (size_t)g->H * g->W, 0, nullptr).head;
-  const size_t bwd = fluidnet_train_bwd_ws(2, g, nullptr).bytes + bank_bwd_plan(g->B, g->H, g->W, nullptr).bytes;
-  return fwd > bwd ? fwd : bwd;
-}
-size_t bank_bwd_ws_bytes(const FnxGrid* g) { return bank_bwd_plan(g->B, g->H, g->W, nullptr).bytes; }
+bool bank2d_sized(const FnxGrid* g) { return g && !g->is3D && g->D == 1 && g->B >= 1 && g->H >= 4 && g->W >= 4; }
+constexpr BankTrainDim DIM2 = {2, bank2d_sized, nullptr, banknet_forward_train, banknet_backward, bank_bwd_plan_bytes};
 
 }  // namespace
+
+// The kernel reads its three blocks at pt[PT_W2T + ...], pt[PT_W3T + ...] and pt[PT_WO + ...], so it is given tail_t - PT_W2T: the 2D
+// image's own start, or 9216 floats into the 3D image (never a pointer before the allocation).
+static_assert(PT3_W3T - PT3_W2T == PT_W3T - PT_W2T && PT3_WO - PT3_W2T == PT_WO - PT_W2T && PT3_W2T >= PT_W2T,
+              "the 1x1 block sits alike in both images of packed_t");
+void bank_tail_backward(const float* tail_t, const float* grad_p, const float* tt, const float* c2a, const float* c2b, const float* c3,
+                        float* g_t, float* partial, int N, int ups, int nunits, int split, hipStream_t s) {
+  bank_tail_bwd_kernel<<<split, 256, 0, s>>>(tail_t - PT_W2T, grad_p, tt, c2a, c2b, c3, g_t, partial, N, ups, nunits);
+}
+
 }  // namespace fnx
 
 extern "C" {
@@ -518,12 +471,7 @@ size_t fnx_banknet_tape_layout(const FnxGrid* g, FnxTapeEntry* entries) {
     fnx::set_error(FNX_EINVAL, "%s: a 2D grid with H and W positive multiples of 4 is needed", __func__);
     return 0;
   }
-  const fnx::BankTapeLayout T = fnx::bank_tape_layout(g->B, g->H, g->W);
-  for (int i = 0; entries && i < fnx::N_BANK_TAPE; ++i) {
-    snprintf(entries[i].name, sizeof(entries[i].name), "%s", T.e[i].name);
-    entries[i].offset = T.e[i].off; entries[i].C = T.e[i].C; entries[i].H = T.e[i].H; entries[i].W = T.e[i].W;
-  }
-  return T.floats;
+  return fnx::bank_fill_tape(fnx::bank_tape_layout(2, g->B, 1, g->H, g->W), entries, nullptr);
 }
 
 size_t fnx_banknet_packed_t_bytes(void) { return (size_t)fnx::PT_FLOATS * sizeof(float); }
@@ -534,57 +482,31 @@ int fnx_banknet_pack_t(const float* weights_blob, void* packed_t, void* stream) 
   return fnx::bank_status();
 }
 
-size_t fnx_banknet_backward_ws_bytes(const FnxGrid* g) {
-  if (!g || g->is3D || g->D != 1 || g->B < 1 || g->H < 4 || g->W < 4) return 0;
-  return fnx::bank_bwd_ws_bytes(g);
-}
+size_t fnx_banknet_backward_ws_bytes(const FnxGrid* g) { return fnx::bank_size_query<fnx::DIM2>(g, fnx::bank_bwd_ws_bytes<fnx::DIM2>); }
 
 int fnx_banknet_forward_train(const FnxGrid* g, const void* packed, const float* x, float* p, float* tape, int precision_mode, void* stream) {
-  if (int rc = fnx::check_bank_call(__func__, 2, g, packed && x && p && tape, precision_mode, nullptr, 0)) return rc;
-  fnx::banknet_forward_train(g->B, g->H, g->W, (const float*)packed, x, p, tape, (hipStream_t)stream);
-  return fnx::bank_status();
+  return fnx::bank_forward_train<fnx::DIM2>(__func__, g, packed, x, p, tape, precision_mode, stream);
 }
 
 int fnx_banknet_backward(const FnxGrid* g, const void* packed_t, const float* x, const float* grad_p, const float* tape, float* grad_blob,
                          int precision_mode, void* ws, size_t ws_bytes, void* stream) {
-  if (int rc = fnx::check_bank_call(__func__, 2, g, packed_t && x && grad_p && tape && grad_blob && ws, precision_mode, fnx::bank_bwd_ws_bytes,
-                                    ws_bytes))
-    return rc;
-  fnx::banknet_backward(g->B, g->H, g->W, (const float*)packed_t, x, grad_p, tape, grad_blob, ws, (hipStream_t)stream);
-  return fnx::bank_status();
+  return fnx::bank_backward<fnx::DIM2>(__func__, g, packed_t, x, grad_p, tape, grad_blob, precision_mode, ws, ws_bytes, stream);
 }
 
-size_t fnx_fluidnet_bank_train_ws_bytes(const FnxGrid* g) {
-  if (!g || g->is3D || g->D != 1 || g->B < 1 || g->H < 4 || g->W < 4) return 0;
-  return fnx::bank_train_ws_bytes(g);
-}
+size_t fnx_fluidnet_bank_train_ws_bytes(const FnxGrid* g) { return fnx::bank_size_query<fnx::DIM2>(g, fnx::bank_train_ws_bytes<fnx::DIM2>); }
 
 int fnx_fluidnet_bank_forward_train(const FnxGrid* g, const void* packed, const float* input, float normalize_threshold, float* p_out,
                                     float* U_out, float* flags_out, float* scale_out, float* tape, int precision_mode, void* ws,
                                     size_t ws_bytes, void* stream) {
-  if (int rc = fnx::check_bank_call(__func__, 2, g, packed && input && p_out && U_out && flags_out && scale_out && tape && ws,
-                                    precision_mode, fnx::bank_train_ws_bytes, ws_bytes))
-    return rc;
-  fnx::FluidnetWs w = fnx::fluidnet_ws_layout(g->B, (size_t)g->H * g->W, 0, ws);        // (its head: the scales go to scale_out)
-  w.x = tape + fnx::bank_tape_layout(g->B, g->H, g->W).e[fnx::TP_X].off;      // the backward reads the net's input again (conv1)
-  fnx::fluidnet_split(g, input, U_out, flags_out, stream);
-  if (int rc = fnx::fluidnet_pre(g, normalize_threshold, U_out, flags_out, scale_out, w, stream)) return rc;
-  fnx::banknet_forward_train(g->B, g->H, g->W, (const float*)packed, w.x, p_out, tape, (hipStream_t)stream);
-  if (int rc = fnx::fluidnet_post(g, p_out, U_out, flags_out, scale_out, stream)) return rc;
-  return fnx::bank_status();
+  return fnx::fluidnet_bank_forward_train<fnx::DIM2>(__func__, g, packed, input, normalize_threshold, p_out, U_out, flags_out, scale_out, tape,
+                                                     precision_mode, ws, ws_bytes, stream);
 }
 
 int fnx_fluidnet_bank_backward(const FnxGrid* g, const void* packed_t, const float* flags, const float* scale,
                                const float* grad_p, const float* grad_U, const float* tape, float* grad_blob, int precision_mode, void* ws,
                                size_t ws_bytes, void* stream) {
-  if (int rc = fnx::check_bank_call(__func__, 2, g, packed_t && flags && scale && grad_p && grad_U && tape && grad_blob && ws, precision_mode,
-                                    fnx::bank_train_ws_bytes, ws_bytes))
-    return rc;
-  const fnx::FluidnetTrainBwdWs w = fnx::fluidnet_train_bwd_ws(2, g, ws);
-  if (int rc = fnx::fluidnet_train_gnet(2, g, flags, scale, grad_p, grad_U, w, stream)) return rc;
-  const float* x = tape + fnx::bank_tape_layout(g->B, g->H, g->W).e[fnx::TP_X].off;
-  fnx::banknet_backward(g->B, g->H, g->W, (const float*)packed_t, x, w.gnet, tape, grad_blob, w.net, (hipStream_t)stream);
-  return fnx::bank_status();
+  return fnx::fluidnet_bank_backward<fnx::DIM2>(__func__, g, packed_t, flags, scale, grad_p, grad_U, tape, grad_blob, precision_mode, ws,
+                                                ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -217,15 +217,14 @@ def test_train3d_kernels_resources(tmp_path):
     a lane admit two, which is the occupancy the body is built for (two waves a SIMD); so both LDS and registers must admit two."""
     unit = "fnx_banknet3d_train.hip"
     kernels, _ = build.SCRATCH_FREE[unit]
-    assert set(kernels) == {"bank3d_tail_tape_kernel", "bank3d_tail_bwd_kernel", "bank3d_conv_bwd_kernel", "bank3d_wgrad_kernel",
-                            "bank3d_conv1_bwd_kernel"}
+    assert set(kernels) == {"bank3d_tail_tape_kernel", "bank3d_conv_bwd_kernel", "bank3d_wgrad_kernel", "bank3d_conv1_bwd_kernel"}
     assert "-Rpass-analysis=kernel-resource-usage" in build.HIP_UNITS[unit]
     cmd = ([build.HIPCC] + build.COMMON + build.HIP_UNITS[unit] +
            ["--cuda-device-only", "-c", os.path.join(build.CSRC, unit), "-o", str(tmp_path / "banknet3d_train.o")])
     p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert p.returncode == 0, p.stdout[-4000:]
-    want = {"bank3d_tail_tape_kernel": 1, "bank3d_tail_bwd_kernel": 1, "bank3d_pool_bwd_kernel": 1, "bank3d_conv_bwd_kernel": 2,
-            "bank3d_wgrad_kernel": 1, "bank3d_conv1_bwd_kernel": 1, "bank3d_reduce_kernel": 1, "bank3d_pack_t_kernel": 1}
+    want = {"bank3d_tail_tape_kernel": 1, "bank3d_pool_bwd_kernel": 1, "bank3d_conv_bwd_kernel": 2, "bank3d_wgrad_kernel": 1,
+            "bank3d_conv1_bwd_kernel": 1, "bank3d_reduce_kernel": 1, "bank3d_pack_t_kernel": 1}
     body = {"bank3d_tail_tape_kernel", "bank3d_conv_bwd_kernel"}
     for kernel, count in want.items():
         bad, seen = build._scratch_users(p.stdout, kernel)
