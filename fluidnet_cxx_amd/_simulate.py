@@ -24,8 +24,12 @@ path by itself: the layer keeps one step workspace per (device, grid shape) and 
 `flags` and of the four BC arrays (torch bumps `_version` on every in-place write, and so do this package's own in-place
 operators).  While they are the tensors of the previous call, unwritten, the step reuses what it derived from them (the 3D
 solver's obstacle mask; the 1-byte class map of the BC stages, built on the second such call); any change -- a new tensor, an
-in-place write, another shape -- drops back to deriving everything again for that call.  The cache holds a reference to those
-five tensors, so their addresses cannot be recycled while it trusts them.  What torch's counter does not see: writes through
+in-place write, another shape -- drops back to deriving everything again for that call.  The cache holds a reference to the
+five tensors of the previous call, so their addresses cannot be recycled while it trusts them; what it derived from EARLIER
+flags (the mask of a Jacobi call, the hierarchy of a PCG call, some calls back) it drops as soon as a call sees other flags --
+those tensors may be freed, and a new tensor at a freed one's address has its version and shape too -- so a swap back to them
+derives again.  Identities are recorded only after the native call has returned: a call that raises (a refused argument, an
+interrupt) leaves the cache with nothing, and the next call derives everything.  What torch's counter does not see: writes through
 `.data`, a numpy / dlpack alias or a raw pointer -- after one of those call `forget_static_inputs()` (or pass `static_flags=0`).
 `release_workspaces()` frees the cached workspaces (the CNN's is ~1 KB per cell; one per device, stream and grid shape, at most four).
 A call captured in a HIP graph bakes the bits of capture time into the graph: replays do not look at the tensors again (and a graph
@@ -100,7 +104,16 @@ def _ident(t):
 
 
 class _AutoStep:
-    """the step workspace of one grid shape + what it holds that was derived from flags / the BC arrays"""
+    """The step workspace of one grid shape + what it holds that was derived from flags / the BC arrays.
+
+    A step is `bits, after = begin(...)`, the native call with those bits, `commit(after)`.  begin() forgets everything, so between the
+    two the entry trusts nothing: a call that raises (a refusal, an interrupt) never reaches commit() and the next call sends 0 --
+    whatever the failed one was about to build may be half written.  Only commit() records identities.
+    An identity is trusted only while the entry holds its tensor (`held`: the five tensors of the previous call), because a freed
+    tensor's address, version and shape can all come back with other contents.  flags_id and bc_id are those tensors' own.  mask_id and
+    mg_id describe the flags a Jacobi / PCG call saw, which may be several calls back: they are dropped as soon as a call sees other
+    flags (they are None or flags_id, never the identity of a tensor the entry no longer holds).  Keeping those older flags alive
+    instead would pin a caller's freed tensors for the sake of one case, a swap back to them."""
 
     def __init__(self, nbytes, like):
         self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=like.device)
@@ -108,38 +121,40 @@ class _AutoStep:
 
     def forget(self):
         self.flags_id = self.bc_id = None     # identities at the previous call
-        self.mask_id = None                   # flags identity the kept 3D obstacle mask was built from
-        self.cls_id = None                    # BC identity the kept class map was built from
-        self.mg_id = None                     # flags identity the kept PCG hierarchy was built from (set after a successful call)
+        self.mask_id = None                   # flags identity the kept 3D obstacle mask was built from: None or flags_id
+        self.cls_id = None                    # BC identity the kept class map was built from: None or bc_id
+        self.mg_id = None                     # flags identity the kept PCG hierarchy was built from: None or flags_id
         self.held = None                      # the five tensors themselves: alive -> their addresses cannot be reused
 
-    def static_bits(self, batch_dict, flags, is3D, jacobi, pcg=False):
+    def begin(self, batch_dict, flags, is3D, jacobi, pcg=False):
+        """(static_flags of this call, what commit() records once it has returned); the entry itself is left with nothing"""
         fid = _ident(flags)
         bcs = [batch_dict.get(k) for k in _BC_KEYS]
         bid = None if any(_ident(t) is None for t in bcs) else tuple(_ident(t) for t in bcs)
+        same_flags = fid is not None and fid == self.flags_id
+        mask_id = self.mask_id if same_flags else None          # other flags: what was derived from earlier ones is dropped
+        mg_id = self.mg_id if same_flags else None
         bits = 0
-        if fid is not None and fid == self.flags_id and (not (is3D and jacobi) or self.mask_id == fid):
+        if same_flags and (not (is3D and jacobi) or mask_id == fid):
             bits |= 1                         # flags unchanged (and, where a mask is used, the kept one is theirs)
+        cls_id = None
         if bid is not None and bid == self.bc_id:
             bits |= 2                         # BC arrays unchanged since the previous call: go by the class map ...
             if self.cls_id == bid:
                 bits |= 4                     # ... which an earlier call already built
-            self.cls_id = bid
-        else:
-            self.cls_id = None
-        if pcg and (bits & 1) and self.mg_id == fid:
+            cls_id = bid
+        if pcg and (bits & 1) and mg_id == fid:
             bits |= 8                         # the kept hierarchy is that of these flags
         if pcg:
-            self.mg_id = None                 # until the call has succeeded (built_hierarchy)
+            mg_id = fid                       # this call leaves the hierarchy of these flags behind (built now, or reused)
         if is3D and jacobi:
-            self.mask_id = fid                # this call leaves the mask of these flags behind (built now, or reused)
-        self.flags_id, self.bc_id = fid, bid
-        self.held = (flags, bcs)
-        return bits
+            mask_id = fid                     # and this one the mask
+        self.forget()
+        return bits, (fid, bid, mask_id, cls_id, mg_id, (flags, bcs))
 
-    def built_hierarchy(self, flags):
-        """a 'pcg' step on this workspace has succeeded: it holds the multigrid hierarchy of these flags"""
-        self.mg_id = _ident(flags)
+    def commit(self, after):
+        """the call begin() gave the bits for has returned: the workspace holds what it built"""
+        self.flags_id, self.bc_id, self.mask_id, self.cls_id, self.mg_id, self.held = after
 
 
 def _auto_step(flags, is3D):
@@ -258,7 +273,8 @@ def simulate(mconf, batch_dict, net, sim_method, output_div=False, fused=True, w
             # the reference's four-argument call: the layer's own workspace, static inputs detected (module docstring)
             auto = _auto_step(flags, is3D)
             if auto is not None:
-                workspace, static_flags = auto.workspace, auto.static_bits(batch_dict, flags, is3D, sim_method == "jacobi", uses_pcg)
+                workspace = auto.workspace
+                static_flags, kept = auto.begin(batch_dict, flags, is3D, sim_method == "jacobi", uses_pcg)
         if static_flags is None:
             static_flags = 0
         ext.simulate_step_(p, U, flags, density, batch_dict.get("UBC"), batch_dict.get("UBCInvMask"),
@@ -274,8 +290,8 @@ def simulate(mconf, batch_dict, net, sim_method, output_div=False, fused=True, w
                            pcg_tol=float(mconf.get("pcgTol", 1e-5)), pcg_iter=int(mconf.get("pcgIter", 50)),
                            vorticity_confinement=float(vorticityAmp) if vorticityAmp > 0 else 0.0, pcg_warm=pcg_warm,
                            net_kind=net_kind)
-        if auto is not None and uses_pcg:
-            auto.built_hierarchy(flags)
+        if auto is not None:
+            auto.commit(kept)                                   # only a call that returned: one that raised has left `auto` forgotten
         if not has_density:
             batch_dict["density"] = torch.zeros_like(flags)     # simulate.py:82-83
         return

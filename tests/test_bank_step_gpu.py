@@ -5,15 +5,13 @@ path: the step refuses its kind.
 
 Small plumes with an obstacle box and inlet BCs: 2D B = 2, 36 x 68 (partial tiles in both axes), 3D B = 2, 12 x 24 x 36; the weights
 are those under which every level of the net reaches the output (propagating_bank_weights / propagating_bank3d_weights)."""
-import math
-
 import numpy as np
 import pytest
 import torch
 
 from banknet3d_reference import propagating_bank3d_weights
 from banknet_reference import propagating_bank_weights
-from util import PLUME_CFG, assert_bitexact, make_flags
+from util import PLUME_CFG, assert_bitexact, box_plume_state
 
 pytestmark = pytest.mark.gpu
 
@@ -52,39 +50,8 @@ def N(t):
 
 
 def plume(ndim, dev, stick=False):
-    """The plume of util.plume_state on the (B, D, H, W) grid of SHAPE[ndim]: an inlet over the four bottom rows (velocity and density
-    BCs), an obstacle box above it -- in another place in the second sample -- and smoke already in the domain, more of it in the second
-    sample.  stick: a 'flags_stick' copy of the flags with the first sample's box marked no-slip."""
-    B, D, H, W = SHAPE[ndim]
-    nc = 3 if D > 1 else 2
-    flags = make_flags(B, D, H, W, boxes=False)
-    zs = slice(None) if D == 1 else slice(D // 3, D // 3 + 4)
-    flags[0, 0, zs, H // 2:H // 2 + 4, W // 2 - 3:W // 2 + 4] = 2
-    flags[1, 0, zs, H // 3:H // 3 + 3, W // 3:W // 3 + 6] = 2
-    rad = math.floor(W * 0.145)
-    x = np.arange(W) - W // 2
-    r2 = (x * x)[None, None, :]
-    if D > 1:
-        z = np.arange(D) - D // 2
-        r2 = r2 + (z * z)[:, None, None]
-    inside = np.broadcast_to(r2 <= rad * rad, (D, 4, W))
-    U = np.zeros((B, nc, D, H, W), np.float32)
-    UBC = np.zeros_like(U); UBC[:, 1, :, 0:4] = inside * 2.0
-    UBCInvMask = np.ones_like(U); UBCInvMask[:, :, :, 0:4] = 0
-    rho = np.zeros((B, 1, D, H, W), np.float32)
-    dBC = np.zeros_like(rho); dBC[:, 0, :, 0:4] = inside * np.float32(0.1)
-    dMask = np.ones_like(rho); dMask[:, 0, :, 0:4] = ~inside
-    yy, xx = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
-    for b in range(B):
-        rho[b, 0] = (0.05 * (b + 1) * np.exp(-((yy - H / 3) ** 2 + (xx - W / 2 - 4 * b) ** 2) / 40.0)).astype(np.float32)[None]
-        U[b, 1] = (0.5 * np.exp(-((yy - H / 4) ** 2 + (xx - W / 2) ** 2) / 60.0)).astype(np.float32)[None]
-    rho[flags != 1] = 0
-    st = dict(p=np.zeros_like(rho), U=U, density=rho, flags=flags, UBC=UBC, UBCInvMask=UBCInvMask, densityBC=dBC, densityBCInvMask=dMask)
-    if stick:
-        fs = flags.copy()
-        fs[0, 0, zs, H // 2:H // 2 + 4, W // 2 - 3:W // 2 + 4] = 128
-        st["flags_stick"] = fs
-    return {k: torch.from_numpy(np.ascontiguousarray(v, np.float32)).to(dev) for k, v in st.items()}
+    """util.box_plume_state on the (B, D, H, W) grid of SHAPE[ndim], on the device"""
+    return {k: torch.from_numpy(v).to(dev) for k, v in box_plume_state(*SHAPE[ndim], stick=stick).items()}
 
 
 def run(cfg, bd, net, method, steps, **kw):
