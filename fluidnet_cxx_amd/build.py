@@ -32,6 +32,8 @@ HIP_UNITS = {
     "fnx_api.hip": ["-ffp-contract=off"],
     # (resource-usage remarks: build_lib checks the kernels of SCRATCH_FREE)
     "fnx_cnn.hip": ["-Rpass-analysis=kernel-resource-usage"],
+    # FluidNet.forward around a net: the flags of fnx_cnn.hip, which held it (its fp64 sums of squares contract)
+    "fnx_fluidnet.hip": ["-Rpass-analysis=kernel-resource-usage"],
     "fnx_cnn_train.hip": ["-Rpass-analysis=kernel-resource-usage"],
     "fnx_banknet.hip": ["-Rpass-analysis=kernel-resource-usage"],
     "fnx_banknet_train.hip": ["-Rpass-analysis=kernel-resource-usage"],

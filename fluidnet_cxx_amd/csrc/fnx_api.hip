@@ -5,7 +5,7 @@
 #include <string.h>
 
 #include "../../include/fluidnet_hip.h"
-#include "fnx_cnn.h"
+#include "fnx_fluidnet.h"
 #include "fnx_kernels.h"
 #include <algorithm>
 #include <atomic>

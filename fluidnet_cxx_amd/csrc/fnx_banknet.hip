@@ -63,13 +63,13 @@ void banknet_forward(int B, int H, int W, const float* pk, const float* x, float
   banknet_level_kernel<1, TILE_H, TILE_W1><<<grid(1, TILE_W1), 256, 0, s>>>(pk, x, H, W, nullptr, w.l2, w.l4, p);
 }
 
-// the workspace of the net alone and of the whole forward (the flags copy, fnx_cnn.h's FluidnetWs with the net's at its end)
+// the workspace of the net alone and of the whole forward (the flags copy, fnx_fluidnet.h's FluidnetWs with the net's at its end)
 size_t bank_net_ws(const FnxGrid* g) { return banknet_ws_layout(g->B, g->H, g->W, nullptr).bytes; }
 size_t bank_whole_ws(const FnxGrid* g) { return fluidnet_whole_ws_bytes(g->B, (size_t)g->H * g->W, bank_net_ws(g)); }
 
 }  // namespace
 
-// the net as fnx_cnn.hip's fluidnet_core runs it in the native step (fnx_cnn.h)
+// the net as fnx_fluidnet.hip's fluidnet_core runs it in the native step (fnx_fluidnet.h)
 size_t bank_net_ws_bytes(const FnxGrid* g) { return bank_net_ws(g); }
 void bank_net_forward(const FnxGrid* g, const void* packed, const float* x, float* p, void* ws, hipStream_t s) {
   banknet_forward(g->B, g->H, g->W, (const float*)packed, x, p, ws, s);

@@ -189,7 +189,7 @@ void bank3d_forward(int B, int D, int H, int W, const float* pk, const float* x,
       pk + P3_WB2, pk + P3_BB2, pk + P3_W2, ws.h, D, H, W, pl.tiles_y, pl.chunk, nullptr, ws.b2, ws.b4, p);
 }
 
-// the workspace of the net alone and of the whole forward (the flags copy, fnx_cnn.h's FluidnetWs with the net's at its end)
+// the workspace of the net alone and of the whole forward (the flags copy, fnx_fluidnet.h's FluidnetWs with the net's at its end)
 size_t bank3d_net_ws(const FnxGrid* g) { return bank3d_ws_layout(g->B, g->D, g->H, g->W, nullptr).bytes; }
 size_t bank3d_whole_ws(const FnxGrid* g) { return fluidnet_whole_ws_bytes(g->B, (size_t)g->D * g->H * g->W, bank3d_net_ws(g)); }
 

@@ -5,7 +5,7 @@
 // The layout of the kernels and of the MFMA operands is described at the top of fnx_banknet.hip.
 #pragma once
 #include <hip/hip_runtime.h>
-#include "fnx_cnn.h"
+#include "fnx_fluidnet.h"
 #include "fnx_kernels.h"
 #include "../../include/fluidnet_hip.h"
 

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include "fnx_device.h"
 
+struct FnxGrid;
 namespace fnx {
 
 struct ConvLayer { int cin, cout, k, relu; };
@@ -22,13 +23,79 @@ constexpr ConvLayer LAYERS[N_LAYERS] = {
 constexpr int layer_taps(const ConvLayer& L, bool is3d) { return L.k * L.k * (is3d ? L.k : 1); }
 constexpr size_t layer_weight_floats(const ConvLayer& L, bool is3d) { return (size_t)L.cout * L.cin * layer_taps(L, is3d); }
 
+// float offsets of the layers' weights and biases in the blob (and in the gradient blob): per layer the weight, then the bias
+struct BlobOff { size_t w[N_LAYERS], b[N_LAYERS], total; };
+constexpr BlobOff blob_offsets(bool is3d) {
+  BlobOff o{};
+  size_t off = 0;
+  for (int l = 0; l < N_LAYERS; ++l) {
+    o.w[l] = off; off += layer_weight_floats(LAYERS[l], is3d);
+    o.b[l] = off; off += LAYERS[l].cout;
+  }
+  o.total = off;
+  return o;
+}
+
+// Family::MFMA: the 3x3(x3) layers the matrix-core kernels take (the bf16 pieces, F(4x4), F(2x2) or the implicit GEMM by launch_conv's rule)
+constexpr bool is_mfma_layer(int cin, int cout, int k) { return k == 3 && cin % 16 == 0 && cout % 32 == 0; }
+// Where a layer's images sit, as float offsets into the packed buffer.  Every family has `taps` (its tap image) and `bias`; `end` is where the
+// next layer starts.  The images of one Family::MFMA weight at float offset `off` of a buffer are what scalenet_pack writes for such a
+// layer, for any weight tensor -- the backward's transposed, tap-flipped weights go through the forward's launchers.
+struct MfmaImages {
+  size_t taps;      // the family's tap image (MFMA: [taps][Cin][Cout], the implicit GEMM's A operand)
+  size_t wino2;     // MFMA: G g G^T as [dz][16][Cin][Cout] (read by the pack kernels only)
+  size_t wino3;     // MFMA: the same values stage-contiguous (conv3_wino3_kernel)
+  size_t wbf;       // wide: G g G^T cut into three bf16 pieces in conv3_wbf_kernel's operand layout (1.5x the fp32 image)
+  size_t wino4;     // wide: the nine taps in conv3_wino4_kernel's lane order ([Cin/4][Cout/64][9][4][4][16] per z tap)
+  size_t bias, end;
+  bool wide;        // MFMA with Cout % 64 == 0: also has the bf16 and F(4x4) images
+};
+constexpr size_t al64(size_t x) { return (x + 63) & ~(size_t)63; }
+constexpr MfmaImages mfma_images(bool is3d, int cin, int cout, size_t off) {
+  MfmaImages im{};
+  const size_t kd = is3d ? 3 : 1, nw = 9 * kd * cin * cout, nwino = 16 * kd * cin * cout;
+  im.wide = cout % 64 == 0;
+  im.taps = off; im.wino2 = off + nw; im.wino3 = im.wino2 + nwino;
+  off = im.wino3 + nwino;
+  if (im.wide) { im.wbf = off; im.wino4 = im.wbf + nwino * 3 / 2; off = im.wino4 + nw; }
+  im.bias = off;
+  im.end = al64(off + cout);
+  return im;
+}
+// w (Cout,Cin,(3,)3,3), bias (Cout) -> the images at base + im.*
+void pack_mfma_images(bool is3d, const float* w, const float* bias, int cin, int cout, float* base, const MfmaImages& im, hipStream_t s);
+// y = conv3x3(x3)(x, the packed weight) [+ ReLU] by launch_conv's mode rule; false: nothing launched (D * H * W beyond the MFMA kernels'
+// range)
+bool conv_mfma_images(bool is3d, const MfmaImages& im, const float* base, int cin, int cout, int relu, int mode, const float* x, float* y,
+                      int B, int D, int H, int W, hipStream_t s);
+// float offsets of layer l's tap image and bias in the packed buffer
+void packed_offsets(int l, bool is3d, size_t* taps, size_t* bias);
+
 size_t scalenet_weight_floats(bool is3d);
 size_t scalenet_packed_bytes(bool is3d);
 void scalenet_pack(bool is3d, const float* blob, void* packed, hipStream_t s);
 
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-size_t multiscale_ws_bytes(const GridDims& g, bool is3d);
-size_t fluidnet_ws_bytes(const GridDims& g, bool is3d);
+// The three towers' grids {D, H, W}: quarter, half and full resolution, the reference's int(n * 0.25) / int(n * 0.5) (D stays 1 in 2D,
+// which is D = 1: one plane in every tensor)
+struct Dims { int D, H, W; };
+inline size_t vol(Dims d) { return (size_t)d.D * d.H * d.W; }
+struct Towers { Dims q, h, f; };
+inline Towers tower_sizes(bool is3d, int D, int H, int W) {
+  return Towers{{is3d ? (int)(D * 0.25) : 1, (int)(H * 0.25), (int)(W * 0.25)}, {is3d ? (int)(D * 0.5) : 1, (int)(H * 0.5), (int)(W * 0.5)},
+                {D, H, W}};
+}
+
+// The inference workspace, in this order, each region rounded up to 256 bytes: two ping-pong activation buffers of 128 channels at full
+// resolution, then the small tower I/O.  base == nullptr: the sizes only.
+struct MultiscaleWs { float *bufA, *bufB, *in1, *in2, *xq, *c2, *c4; size_t bytes; };
+MultiscaleWs multiscale_ws_layout(const GridDims& g, bool is3d, void* base);
+inline size_t multiscale_ws_bytes(const GridDims& g, bool is3d) { return multiscale_ws_layout(g, is3d, nullptr).bytes; }
+
+// The forward itself (multi_scale_net.py:119-126): resize, quarter tower, resize, half tower, resize, full tower, the last 5x5(x5) layer
+// with the final 1x1(x1) in its epilogue -- 19 launches, and where their tensors live: the three tower inputs (xq, in2, in1), the output
+// of layer l = 0..14 and p, the output of layers 15 + 16.  trim: multiscale_forward_crop's (zeros: whole tensors).
+struct TowerWalk { const float* x; float* in[3]; float* out[15]; float* p; int trim[4]; };
+void tower_walk(bool is3d, int B, const Towers& t, const void* packed, int mode, const TowerWalk& w, hipStream_t s);
 
 // x (B,2,D,H,W) -> p (B,1,D,H,W)
 void multiscale_forward(const GridDims& g, bool is3d, const void* packed, const float* x, float* p, int precision_mode, void* ws,
@@ -37,26 +104,12 @@ void multiscale_forward(const GridDims& g, bool is3d, const void* packed, const 
 // multiples of 4; p receives g.D - trim[0] - trim[1] planes.  Workspace: multiscale_ws_bytes(g)
 void multiscale_forward_crop(const GridDims& g, bool is3d, const void* packed, const float* x, float* p, int precision_mode,
                              void* ws, hipStream_t s, const int trim[4]);
-
-// pieces of FluidNet.forward (lib/model.py:76-227)
-size_t scale_std_scratch_bytes(int B);      // `partial` of launch_scale_std (fixed-order fp64 partial sums, no atomics)
-void launch_scale_std(const GridDims& g, int nc, const float* U, float thr, double* partial,
-                      float* scale /*B*/, hipStream_t s);
-void launch_pack_input(const GridDims& g, int nc, const float* div, const float* flags, const float* scale, float* U,
-                       float* x, hipStream_t s);
-void launch_unscale(const GridDims& g, int nc, const float* scale, float* p, float* U, hipStream_t s);
-void launch_gather_input(const GridDims& g, int nc, const float* input, float* U, float* flags, hipStream_t s);
-
-// pieces of the CNN projection on a z-slab (fnx_slab_step with method 1; fnx_slab.hip)
-size_t window_sums_scratch_bytes(int B);                       // `partial` of launch_window_sums_encode
-// this rank's fp64 (sum, sumsq) of U over the planes [k0, k1) of every channel, as 3 floats per double in ITS slots of
-// red[nranks][B][2][3] (all other slots zero): a float all-reduce(sum) over the ranks then is an exact all-gather
-void launch_window_sums_encode(const GridDims& g, int nc, int k0, int k1, const float* U, int rank, int nranks, double* partial,
-                               float* red, hipStream_t s);
-// scale[b] = clamp(unbiased std over n elements, thr) from the gathered sums, added in rank order
-void launch_scale_from_sums(int nranks, int B, double n, float thr, const float* red, float* scale, hipStream_t s);
-// x[b,0] = div(U / scale[b]), x[b,1] = occupancy(flags) on the planes of g's compute window (U is not modified)
-void launch_pack_div(const GridDims& g, bool is3d, const float* U, const float* flags, const float* scale, float* x, hipStream_t s);
+// (every error return sets the thread's message: the Python layer raises fnx_last_error(), which would otherwise be an earlier call's text)
+int launch_status(bool is3d);
+// The checks the CNN entry points share, before any device call: null arguments (`args`), the precision mode (*mode: as the launchers
+// dispatch on it, net_mode), the net's smallest grid and the workspace, which must hold need(dims of g, g->is3D) bytes
+int check_net_call(const char* fn, const FnxGrid* g, bool args, int precision_mode, int* mode, size_t (*need)(const GridDims&, bool),
+                   size_t ws_bytes);
 
 
 // ---- training (fnx_cnn_train.hip: 2D and 3D, fp32 modes) --------------------------------------------------------------------------
@@ -72,29 +125,7 @@ __device__ __forceinline__ void src_index(int dst, int in, int out, int& i0, int
   l0 = 1.f - l1;
 }
 
-
-// what the training unit uses of the forward's launchers (fnx_cnn.hip).  These hooks, and tape_layout, multiscale_forward_train,
-// multiscale_backward and its workspace size below, take `is3d` and a grid {D, H, W}; 2D is D = 1 (one plane in every tensor).
-// layer l of the net from x into y, exactly the launch the inference forward makes (launch_conv)
-void conv_layer(int l, bool is3d, int mode, const float* packed, const float* x, float* y, int B, int D, int H, int W, hipStream_t s);
-// float offsets of layer l's tap image and bias in the packed buffer
-void packed_offsets(int l, bool is3d, size_t* taps, size_t* bias);
-// the net's tower sizes: q, h = {D, H, W} at quarter and half resolution, the reference's int(n * 0.25) / int(n * 0.5) (D stays 1 in 2D)
-void net_sizes(bool is3d, int D, int H, int W, int q[3], int h[3]);
-// the resampling of multi_scale_net.py:119-125: x0 (B,C0,D0,H0,W0) and, if C1 > 0, x1 (B,C1,D1,H1,W1) -> channels [0, C0 + C1) of
-// y (B,.,Do,Ho,Wo)
-void resize(const float* x0, int C0, int D0, int H0, int W0, const float* x1, int C1, int D1, int H1, int W1, float* y, int B, int Do,
-            int Ho, int Wo, hipStream_t s);
-// The images of one Family::MFMA weight (3x3(x3), Cin % 16 == 0, Cout % 32 == 0) at float offset `off` of a buffer: what scalenet_pack
-// writes for such a layer, for any weight tensor -- the backward's transposed, tap-flipped weights go through the forward's launchers.
-struct MfmaImages { size_t taps, wino2, wino3, wbf, wino4, bias, end; bool wide; };
-MfmaImages mfma_images(bool is3d, int cin, int cout, size_t off);
-// w (Cout,Cin,(3,)3,3), bias (Cout) -> the images at base + im.*
-void pack_mfma_images(bool is3d, const float* w, const float* bias, int cin, int cout, float* base, const MfmaImages& im, hipStream_t s);
-// y = conv3x3(x3)(x, the packed weight) [+ ReLU] by launch_conv's mode rule; false: nothing launched (D * H * W beyond the MFMA kernels'
-// range)
-bool conv_mfma_images(bool is3d, const MfmaImages& im, const float* base, int cin, int cout, int relu, int mode, const float* x, float* y,
-                      int B, int D, int H, int W, hipStream_t s);
+// tape_layout, multiscale_forward_train, multiscale_backward and its workspace size below take `is3d` and a grid {D, H, W}; 2D is D = 1.
 
 // One entry of the tape of the training forward: a (B,C,D,H,W) tensor at float offset `off`.  The layout is a function of the
 // dimension and (B,D,H,W) alone.
@@ -122,49 +153,3 @@ void launch_resize3d_adjoint(const float* gd, float* gs, int B, int Di, int Hi, 
 // g_net = scale[b] * grad_p + velocity_update_backward_p(scale[b] * setWallBcs(grad_U))   (the adjoint of model.py:213-226)
 void launch_scale_mul(size_t n1, int nc, int B, const float* scale, const float* a, const float* addend, float* out, hipStream_t s);
 }  // namespace fnx
-
-struct FnxGrid;
-struct FnxState;
-namespace fnx {
-// precision_mode (FNX_PRECISION_*) as the CNN launchers dispatch on it: FNX_PRECISION_FP32_F4 names what FNX_PRECISION_FP32 runs and
-// becomes it; -1: no such mode.  The C ABI entry points map it once; everything below them takes the mapped value.
-int net_mode(int precision_mode);
-// FluidNet.forward around a net, whichever net it is (the ScaleNet, the bank nets and the two trainers call these).
-// The scratch behind the flags copy, in this order, each region rounded up to 256 bytes: the divergence (the fused step keeps the net's p
-// there), the net's input, scale_std's partial sums, the per-sample scales, `net_bytes` for the net's own workspace.  cells: D * H * W.
-// base == nullptr: the sizes only.  head: the bytes in front of `scale`, all a training forward takes (its scales go to the caller).
-// A whole-forward entry point puts its contiguous (B,1,..) copy of the flags channel, fluidnet_flags_bytes, in front of it.
-struct FluidnetWs { float* div; float* x; double* partial; float* scale; void* net; size_t head, bytes; };
-FluidnetWs fluidnet_ws_layout(int B, size_t cells, size_t net_bytes, void* base);
-inline size_t fluidnet_flags_bytes(int B, size_t cells) { return al256((size_t)B * cells * 4); }
-inline size_t fluidnet_whole_ws_bytes(int B, size_t cells, size_t net_bytes) {
-  return fluidnet_flags_bytes(B, cells) + fluidnet_ws_layout(B, cells, net_bytes, nullptr).bytes;
-}
-// the channel split of model.py:104-119 (input -> U, flags), the launches of :125-168 in front of the net and those of :213-226 behind
-// it.  The velocity components, 2 or 3, follow from g->is3D.
-void fluidnet_split(const FnxGrid* g, const float* input, float* U, float* flags, void* stream);
-int fluidnet_pre(const FnxGrid* g, float thr, float* U, const float* flags, float* scale, const FluidnetWs& w, void* stream);
-int fluidnet_post(const FnxGrid* g, float* p, float* U, const float* flags, const float* scale, void* stream);
-// The backward's scratch (the wall-masked scaled grad_U, the update's grad_U and grad_p, g_net, then the net's own workspace at `net`) and
-// g_net = s grad_p + velocity_update_backward_p(s setWallBcs(grad_U)) (fnx_cnn_train.hip).  nc: 2 or 3 velocity components.
-struct FluidnetTrainBwdWs { float *gU, *gU_in, *gp, *gnet; void* net; size_t bytes; };   // bytes: in front of `net`
-FluidnetTrainBwdWs fluidnet_train_bwd_ws(int nc, const FnxGrid* g, void* base);
-int fluidnet_train_gnet(int nc, const FnxGrid* g, const float* flags, const float* scale, const float* grad_p, const float* grad_U,
-                        const FluidnetTrainBwdWs& w, void* stream);
-// The net in the middle, by its kind (FNX_NET_SCALENET or FNX_NET_BANK, the 2D bank net; FNX_NET_BANK3D is not built into the step):
-// `packed` is the image of that kind.  The bank unit exports its net for it (fnx_banknet.hip): the workspace of the net alone, its
-// launches, and check_bank_call's refusals of a grid or a precision mode under the caller's name (no argument or workspace check).
-size_t bank_net_ws_bytes(const FnxGrid* g);
-void bank_net_forward(const FnxGrid* g, const void* packed, const float* x, float* p, void* ws, hipStream_t s);
-int check_bank_grid(const char* fn, const FnxGrid* g, int precision_mode);
-// what fluidnet_core and fluidnet_pressure take at `ws` for a net of this kind: fluidnet_ws_layout with the net's own workspace
-size_t fluidnet_core_ws_bytes(const FnxGrid* g, int net_kind);
-// the net's un-normalised pressure alone (model.py:125-175, :221-222) for the hybrid projection: p_out = scale * net(div(U) / scale, occupancy);
-// U is read only.  ws: fluidnet_core_ws_bytes.
-int fluidnet_pressure(const FnxGrid* g, const void* packed, int net_kind, const float* flags, float thr, int precision_mode, float* p_out,
-                      const float* U, void* ws, void* stream);
-// bcs != nullptr: the fused step's form -- the last setConstVals of the step (simulate.py:168) is part of the pass behind the
-// net (bcs supplies density, the BC arrays, bc_class and density_bc_applied; p_out must not be the workspace)
-int fluidnet_core(const FnxGrid* g, const void* packed, int net_kind, const float* flags, float thr, int precision_mode, float* p_out,
-                  float* U, void* ws, void* stream, const FnxState* bcs = nullptr);
-}

@@ -16,6 +16,7 @@
 #include "fnx_cnn.h"
 #include <assert.h>
 #include <stdio.h>
+#include "fnx_fluidnet.h"
 #include "fnx_kernels.h"
 #include "../../include/fluidnet_hip.h"
 
@@ -24,27 +25,13 @@ namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-inline size_t al64(size_t x) { return (x + 63) & ~(size_t)63; }
-inline bool is_mfma(const ConvLayer& L) { return L.k == 3 && L.cin % 16 == 0 && L.cout % 32 == 0; }   // Family::MFMA, also transposed
-
-// float offsets of the layers' weights and biases in the blob (and in the gradient blob)
-struct BlobOff { size_t w[N_LAYERS], b[N_LAYERS], total; };
-inline BlobOff blob_offsets(bool is3d) {
-  BlobOff o{};
-  size_t off = 0;
-  for (int l = 0; l < N_LAYERS; ++l) {
-    o.w[l] = off; off += layer_weight_floats(LAYERS[l], is3d);
-    o.b[l] = off; off += LAYERS[l].cout;
-  }
-  o.total = off;
-  return o;
-}
+constexpr bool is_mfma(const ConvLayer& L) { return is_mfma_layer(L.cin, L.cout, L.k); }   // Family::MFMA, also transposed
 
 // packed_t: [blob | 128 zeros (the transposed convolutions' bias) | staging for one transposed weight | images per MFMA layer]
 constexpr size_t stage_floats(bool is3d) {              // the largest transposed 3x3(x3) weight of LAYERS
   size_t n = 0;
   for (int l = 0; l < N_LAYERS; ++l)
-    if (LAYERS[l].k == 3 && LAYERS[l].cin % 16 == 0 && LAYERS[l].cout % 32 == 0 && layer_weight_floats(LAYERS[l], is3d) > n)
+    if (is_mfma(LAYERS[l]) && layer_weight_floats(LAYERS[l], is3d) > n)
       n = layer_weight_floats(LAYERS[l], is3d);
   return n;
 }
@@ -75,9 +62,6 @@ __global__ void transpose_flip_kernel(const float* __restrict__ w, float* __rest
 __global__ void fill_zero_kernel(float* __restrict__ p, int n) {
   for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < n; q += gridDim.x * blockDim.x) p[q] = 0.f;
 }
-
-struct Dims { int D, H, W; };
-inline size_t vol(Dims d) { return (size_t)d.D * d.H * d.W; }
 
 // ---------------------------------------------------------------------------------------------------
 // Thin convolutions (the 8-channel tensor of the forward; the input gradients through the 32->1 3x3, 32->8 5x5, 8->1 1x1 layers and
@@ -392,14 +376,6 @@ inline int split_count(long outputs, long rows) {
   return n < 1 ? 1 : (int)n;
 }
 
-// the three towers' grids: quarter, half and full resolution (the reference's size rule, as the inference forward applies it)
-struct Towers { Dims q, h, f; };
-inline Towers tower_sizes(bool is3d, int D, int H, int W) {
-  int q[3], h[3];
-  net_sizes(is3d, D, H, W, q, h);
-  return Towers{{q[0], q[1], q[2]}, {h[0], h[1], h[2]}, {D, H, W}};
-}
-
 }  // namespace
 
 TapeLayout tape_layout(bool is3d, int B, int D, int H, int W) {
@@ -450,23 +426,12 @@ void multiscale_forward_train(bool is3d, int B, int D, int H, int W, const void*
                               hipStream_t s) {
   const TapeLayout T = tape_layout(is3d, B, D, H, W);
   const float* pk = (const float*)packed;
-  const Towers t = tower_sizes(is3d, D, H, W);
-  const Dims q = t.q, h = t.h, f = t.f;
   auto out = [&](int l) { return tape + T.e[tape_output_index(l)].off; };
-  auto in = [&](int tower) { return tape + T.e[tape_input_index(tower)].off; };
-  auto tower = [&](int tw, int l0, int n, Dims d) {
-    const float* cur = in(tw);
-    for (int l = l0; l < l0 + n; ++l) { conv_layer(l, is3d, mode, pk, cur, out(l), B, d.D, d.H, d.W, s); cur = out(l); }
-  };
-  // multi_scale_net.py:119-126
-  resize(x, 2, D, H, W, nullptr, 0, 1, 1, 1, in(0), B, q.D, q.H, q.W, s);
-  tower(0, 0, 4, q);
-  resize(x, 2, D, H, W, out(3), 1, q.D, q.H, q.W, in(1), B, h.D, h.H, h.W, s);
-  tower(1, 4, 6, h);
-  resize(x, 2, D, H, W, out(9), 1, h.D, h.H, h.W, in(2), B, D, H, W, s);
-  tower(2, 10, 5, f);
-  // the last 5x5(x5) layer with the final 1x1(x1) in its epilogue, as the inference forward runs it: p
-  conv_layer(15, is3d, mode, pk, out(14), p, B, D, H, W, s);
+  // the inference forward's launches (tower_walk) with every tensor in the tape and no crop
+  TowerWalk w{x, {}, {}, p, {0, 0, 0, 0}};
+  for (int tw = 0; tw < 3; ++tw) w.in[tw] = tape + T.e[tape_input_index(tw)].off;
+  for (int l = 0; l < 15; ++l) w.out[l] = out(l);
+  tower_walk(is3d, B, tower_sizes(is3d, D, H, W), packed, mode, w, s);
   // the 8-channel tensor that launch never writes, from the same packed weights ([dz][r][wx 0..5][Cin][dx * 8 + co], dx = 0: tap (dz, r, wx))
   size_t taps, bias;
   packed_offsets(15, is3d, &taps, &bias);

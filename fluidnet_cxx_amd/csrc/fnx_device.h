@@ -35,6 +35,9 @@ __host__ __device__ inline GridDims make_dims(int B, int D, int H, int W, int zo
   return d;
 }
 
+// the rounding of every region of the CNN and FluidNet.forward workspaces
+namespace fnx { constexpr size_t al256(size_t x) { return (x + 255) & ~(size_t)255; } }
+
 // compute units of the current device, asked once per device ordinal (256, the MI355X's, where the runtime cannot tell): what the
 // persistent and one-round launches size their grids by
 inline int cu_count() {

@@ -29,6 +29,7 @@
 #include "../../include/fluidnet_hip.h"
 #include "fnx_kernels.h"
 #include "fnx_cnn.h"
+#include "fnx_fluidnet.h"
 
 namespace {
 

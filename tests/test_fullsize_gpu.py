@@ -233,7 +233,7 @@ def test_long_simulation_stays_bit_identical(oracle, case):
 
 
 # ---- the convnet step (lib/simulate.py:131-143 + lib/model.py:118-227) against the oracle --------------------------------------
-# The fused convnet step is three launches around the net (fnx_cnn.hip: pack_div_kernel -- the divergence of U / s straight into
+# The fused convnet step is three launches around the net (fnx_fluidnet.hip: pack_div_kernel -- the divergence of U / s straight into
 # the net's input --, the net, post_projection_kernel<IS3D, SCALE=true> -- velocityUpdate, un-normalisation, setWallBcs, the step's
 # last setConstVals) behind the advection and staging launches.  Tolerances: the net's arithmetic is a tolerance statement
 # (1e-5 * |ref|max on p and U, like every CNN test); everything that does not pass through the net is bit for bit.

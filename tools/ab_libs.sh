@@ -12,7 +12,7 @@ V=variants
 if [ "$1" = build ]; then
   mkdir -p $V
   U=${UNIT:-fnx_cnn}
-  extra=""; [ $U != fnx_cnn ] && [ $U != fnx_slab ] && [ $U != fnx_peer ] && extra="-ffp-contract=off"    # (build.py's per-unit flags)
+  extra=""; [ $U != fnx_cnn ] && [ $U != fnx_fluidnet ] && [ $U != fnx_slab ] && [ $U != fnx_peer ] && extra="-ffp-contract=off"    # (build.py's per-unit flags)
   src=fluidnet_cxx_amd/csrc/$U.hip
   if [ $# -ge 3 ]; then git show $3:$src > fluidnet_cxx_amd/csrc/.ab_$2.hip; src=fluidnet_cxx_amd/csrc/.ab_$2.hip; fi
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -fno-fast-math -fno-slp-vectorize -Wno-unused-value $extra ${ABFLAGS:-} \

@@ -1,12 +1,15 @@
 #!/usr/bin/env python3
-"""One SHA-256 per tensor of the native training path (2D and 3D) on seeded inputs, to compare two builds bit for bit:
+"""One SHA-256 per tensor of the native training path and of the inference forward (2D and 3D) on seeded inputs, to compare two builds
+bit for bit:
 
     python tools/cnn_train_digest.py [TREE] [--out FILE]
 
 TREE is the checkout whose built package is imported (default: the one this file sits in).  Only extension functions are used, so any
 two trees that have them can be compared: run the tool once per tree, each in a process of its own, and compare the outputs line by line.
 Shapes: W not a multiple of 32, H not a multiple of 4, B > 1, more than one split, the plain and the MFMA weight-gradient kernels and
-the direct, F(2x2) and F(4x4) input-gradient launches."""
+the direct, F(2x2) and F(4x4) input-gradient launches.  Inference ("infer" lines): ext.multiscale_forward in all six precision modes on a
+grid where every launcher falls back and on one past the F(2x2) / F(4x4) / bf16 fill thresholds, ext.fluidnet_forward, and the forward on
+nested z-crops with and without trims."""
 import argparse
 import hashlib
 import os
@@ -19,6 +22,10 @@ MODES = ("fp32", "fp32_f2", "fp32_direct")
 CASES2D = [((2, 37, 53), MODES), ((3, 199, 215), MODES), ((2, 255, 508), MODES)]
 CASES3D = [((2, 6, 10, 37), MODES), ((1, 9, 14, 70), ("fp32",))]
 BIG3D = (2, 32, 64, 64)            # past the Winograd kernels' fill thresholds: backward at fp32 on an fp32_direct tape
+ALL_MODES = ("fp32", "fp32_direct", "bf16x6", "bf16x3", "fp32_f4", "fp32_f2")
+INFER2D = [((2, 37, 53), ALL_MODES), ((2, 255, 508), ALL_MODES)]
+INFER3D = [((2, 6, 10, 37), ALL_MODES), (BIG3D, ("fp32",))]
+CROP3D, CROP_TRIM = (1, 24, 12, 37), [8, 4, 4, 0]
 FLUID, OBST = 1.0, 2.0
 
 
@@ -113,6 +120,19 @@ def main():
         grad = (ext.fluidnet3d_backward if is3d else ext.fluidnet_backward)(packed_t, flags, scale, w_p, w_U, tape, "fp32")
         for name, t in (("p", p), ("U", U), ("tape", entries(tape, shape)), ("scale", scale), ("flags", flags), ("grad", grad)):
             emit(f"fluidnet{ndim}d {sid(shape)} fp32 {name}", t)
+        del p, U, tape, grad
+        # the inference forward: every precision mode where every launcher falls back and past the fill thresholds, the whole
+        # FluidNet.forward, and (3D) the forward on nested z-crops
+        for ishape, modes in INFER3D if is3d else INFER2D:
+            x, _ = inputs(ishape)
+            for mode in modes:
+                emit(f"infer {sid(ishape)} {mode} p", ext.multiscale_forward(packed, x, mode))
+        for name, t in zip(("p", "U"), ext.fluidnet_forward(packed, inp, 1e-5, "fp32")):
+            emit(f"infer fluidnet{ndim}d {sid(shape)} fp32 {name}", t)
+        if is3d:
+            x, _ = inputs(CROP3D)
+            for trim in (CROP_TRIM, [0, 0, 0, 0]):
+                emit(f"infer {sid(CROP3D)} fp32 trim {trim} p", ext.multiscale_forward(packed, x, "fp32", trim))
         torch.cuda.empty_cache()
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
