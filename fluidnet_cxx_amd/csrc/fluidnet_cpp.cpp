@@ -566,63 +566,125 @@ Tensor multiscale_forward(Tensor packed, Tensor x, const std::string& precision_
   return p;
 }
 
-// ---- the 16-channel bank nets: mconf['model'] = 'FluidNet' (fnx_banknet.hip, 2D) and 'FluidNet3D' (fnx_banknet3d.hip), inference ----
-// Every operation is one body that takes the net's C entry points; the module registers it under its 2D and its 3D name.
-// A grid the C ABI refuses (the other dimension, a size that is no multiple of 4, a bf16 mode) gets a token workspace, so that the C
-// ABI's text is what is raised.
-struct BankApi {
+// ---- the four pressure nets: the ScaleNet (fnx_cnn.hip, fnx_cnn_train.hip) and the 16-channel bank net, mconf['model'] = 'FluidNet' /
+// 'FluidNet3D' (fnx_banknet*.hip), each in 2D and 3D.  One table row per net holds its C entry points under one signature per operation,
+// and every operation is one body over a row; the module registers it under the row's names.  A body builds the grid it is given, of
+// either dimension, and a grid the net's C ABI refuses (the other dimension, a size it does not take, a bf16 mode in training) gets a
+// token tape and workspace, so that the C ABI's text is what is raised.
+struct NetApi {
+  bool bank;                       // the bank family: its backward takes x, its grids are 3D by their depth and not by the name called
+  int ndim;
+  const char *net_name, *whole_name;                   // "<net_name>_forward_train", "<whole_name>_backward", ...
   const char* pack_name;
   size_t (*weight_floats)(void);
   size_t (*packed_bytes)(void);
+  // inference of the bank nets (the ScaleNet's has one name for both dimensions: scalenet_pack, multiscale_forward, fluidnet_forward)
   int (*pack)(const float*, void*, void*);
   size_t (*ws_bytes)(const FnxGrid*, int);
   int (*forward)(const FnxGrid*, const void*, const float*, float*, int, void*, size_t, void*);
   int (*whole_forward)(const FnxGrid*, const void*, const float*, float, float*, float*, int, void*, size_t, void*);
-  // training (fnx_banknet_train.hip, fnx_banknet3d_train.hip)
-  const char* pack_t_name;
+  // training.  image_sized: the binding checks an image's size (the 3D ScaleNet's entry points take it and refuse a wrong one themselves)
+  const char *pack_t_name, *packed_t_what, *blob_note;
+  bool image_sized;
   size_t (*packed_t_bytes)(void);
   int (*pack_t)(const float*, void*, void*);
-  size_t (*tape_floats)(const FnxGrid&);
+  size_t (*tape_floats)(const FnxGrid*);
   size_t (*backward_ws_bytes)(const FnxGrid*);
-  int (*forward_train)(const FnxGrid*, const void*, const float*, float*, float*, int, void*);
-  int (*backward)(const FnxGrid*, const void*, const float*, const float*, const float*, float*, int, void*, size_t, void*);
+  int (*forward_train)(const FnxGrid*, const void*, size_t, const float*, float*, float*, int, void*);
+  int (*backward)(const FnxGrid*, const void*, size_t, const float*, const float*, const float*, float*, int, void*, size_t, void*);
+  int (*backward_plain)(const FnxGrid*, const void*, size_t, const float*, const float*, const float*, float*, int, void*, size_t, void*);
   size_t (*train_ws_bytes)(const FnxGrid*);
-  int (*whole_forward_train)(const FnxGrid*, const void*, const float*, float, float*, float*, float*, float*, float*, int, void*, size_t,
-                             void*);
-  int (*whole_backward)(const FnxGrid*, const void*, const float*, const float*, const float*, const float*, const float*, float*, int, void*,
-                        size_t, void*);
+  int (*whole_forward_train)(const FnxGrid*, const void*, size_t, const float*, float, float*, float*, float*, float*, float*, int, void*,
+                             size_t, void*);
+  int (*whole_backward)(const FnxGrid*, const void*, size_t, const float*, const float*, const float*, const float*, const float*, float*, int,
+                        void*, size_t, void*);
 };
-static size_t bank2d_tape_floats(const FnxGrid& g) { return fnx_banknet_tape_layout(&g, nullptr); }
-static size_t bank3d_tape_floats(const FnxGrid& g) { return fnx_banknet3d_tape_layout(&g, nullptr); }
-static const BankApi BANK2D = {"banknet_pack", fnx_banknet_weight_floats, fnx_banknet_packed_bytes, fnx_banknet_pack, fnx_banknet_ws_bytes,
-                               fnx_banknet_forward, fnx_fluidnet_bank_forward,
-                               "banknet_pack_t", fnx_banknet_packed_t_bytes, fnx_banknet_pack_t, bank2d_tape_floats,
-                               fnx_banknet_backward_ws_bytes, fnx_banknet_forward_train, fnx_banknet_backward,
-                               fnx_fluidnet_bank_train_ws_bytes, fnx_fluidnet_bank_forward_train, fnx_fluidnet_bank_backward};
-static const BankApi BANK3D = {"banknet3d_pack", fnx_banknet3d_weight_floats, fnx_banknet3d_packed_bytes, fnx_banknet3d_pack,
-                               fnx_banknet3d_ws_bytes, fnx_banknet3d_forward, fnx_fluidnet_bank3d_forward,
-                               "banknet3d_pack_t", fnx_banknet3d_packed_t_bytes, fnx_banknet3d_pack_t, bank3d_tape_floats,
-                               fnx_banknet3d_backward_ws_bytes, fnx_banknet3d_forward_train, fnx_banknet3d_backward,
-                               fnx_fluidnet_bank3d_train_ws_bytes, fnx_fluidnet_bank3d_forward_train, fnx_fluidnet_bank3d_backward};
+// A C entry point under the table's signature (g, image, image bytes, [x,] ...): one that takes no image size, no x, or neither
+template <auto F, class... A> static int no_size(const FnxGrid* g, const void* image, size_t, A... a) { return F(g, image, a...); }
+template <auto F, class... A> static int no_x(const FnxGrid* g, const void* image, size_t n, const float*, A... a) { return F(g, image, n, a...); }
+template <auto F, class... A> static int no_size_x(const FnxGrid* g, const void* image, size_t, const float*, A... a) { return F(g, image, a...); }
+template <auto F> static size_t floats_of(const FnxGrid* g) { return F(g, nullptr); }      // a tape layout's size query: 0 for a refused grid
+template <int IS3D> static size_t scalenet_floats(void) { return fnx_scalenet_weight_floats(IS3D); }
+template <int IS3D> static size_t scalenet_bytes(void) { return fnx_scalenet_packed_bytes(IS3D); }
+// The rows are positional, one numbered line per group of fields in the struct's order:
+//   1: bank, ndim, net_name, whole_name
+//   2: pack_name, weight_floats, packed_bytes
+//   3: pack, ws_bytes, forward, whole_forward
+//   4: pack_t_name, packed_t_what, blob_note, image_sized
+//   5: packed_t_bytes, pack_t, tape_floats, backward_ws_bytes
+//   6: forward_train, backward, backward_plain
+//   7: train_ws_bytes, whole_forward_train, whole_backward
+static const NetApi SCALE2D = {
+    /* 1 */ false, 2, "multiscale", "fluidnet",
+    /* 2 */ "scalenet_pack", scalenet_floats<0>, scalenet_bytes<0>,
+    /* 3 */ nullptr, nullptr, nullptr, nullptr,
+    /* 4 */ "scalenet_pack_t", "packed_t", "", true,
+    /* 5 */ fnx_scalenet_packed_t_bytes, fnx_scalenet_pack_t, floats_of<fnx_multiscale_tape_layout>, fnx_multiscale_backward_ws_bytes,
+    /* 6 */ no_size<fnx_multiscale_forward_train>, no_size_x<fnx_multiscale_backward>, no_size_x<fnx_multiscale_backward_plain>,
+    /* 7 */ fnx_fluidnet_train_ws_bytes, no_size<fnx_fluidnet_forward_train>, no_size<fnx_fluidnet_backward>};
+static const NetApi SCALE3D = {
+    /* 1 */ false, 3, "multiscale3d", "fluidnet3d",
+    /* 2 */ "scalenet_pack", scalenet_floats<1>, scalenet_bytes<1>,
+    /* 3 */ nullptr, nullptr, nullptr, nullptr,
+    /* 4 */ "scalenet3d_pack_t", "packed3d_t", " (the 3D net)", false,
+    /* 5 */ fnx_scalenet3d_packed_t_bytes, fnx_scalenet3d_pack_t, floats_of<fnx_multiscale3d_tape_layout>, fnx_multiscale3d_backward_ws_bytes,
+    /* 6 */ fnx_multiscale3d_forward_train, no_x<fnx_multiscale3d_backward>, no_x<fnx_multiscale3d_backward_plain>,
+    /* 7 */ fnx_fluidnet3d_train_ws_bytes, fnx_fluidnet3d_forward_train, fnx_fluidnet3d_backward};
+static const NetApi BANK2D = {
+    /* 1 */ true, 2, "banknet", "fluidnet_bank",
+    /* 2 */ "banknet_pack", fnx_banknet_weight_floats, fnx_banknet_packed_bytes,
+    /* 3 */ fnx_banknet_pack, fnx_banknet_ws_bytes, fnx_banknet_forward, fnx_fluidnet_bank_forward,
+    /* 4 */ "banknet_pack_t", "packed_t", "", true,
+    /* 5 */ fnx_banknet_packed_t_bytes, fnx_banknet_pack_t, floats_of<fnx_banknet_tape_layout>, fnx_banknet_backward_ws_bytes,
+    /* 6 */ no_size<fnx_banknet_forward_train>, no_size<fnx_banknet_backward>, nullptr,
+    /* 7 */ fnx_fluidnet_bank_train_ws_bytes, no_size<fnx_fluidnet_bank_forward_train>, no_size<fnx_fluidnet_bank_backward>};
+static const NetApi BANK3D = {
+    /* 1 */ true, 3, "banknet3d", "fluidnet_bank3d",
+    /* 2 */ "banknet3d_pack", fnx_banknet3d_weight_floats, fnx_banknet3d_packed_bytes,
+    /* 3 */ fnx_banknet3d_pack, fnx_banknet3d_ws_bytes, fnx_banknet3d_forward, fnx_fluidnet_bank3d_forward,
+    /* 4 */ "banknet3d_pack_t", "packed_t", "", true,
+    /* 5 */ fnx_banknet3d_packed_t_bytes, fnx_banknet3d_pack_t, floats_of<fnx_banknet3d_tape_layout>, fnx_banknet3d_backward_ws_bytes,
+    /* 6 */ no_size<fnx_banknet3d_forward_train>, no_size<fnx_banknet3d_backward>, nullptr,
+    /* 7 */ fnx_fluidnet_bank3d_train_ws_bytes, no_size<fnx_fluidnet_bank3d_forward_train>, no_size<fnx_fluidnet_bank3d_backward>};
+static const NetApi* const NETS[4] = {&SCALE2D, &SCALE3D, &BANK2D, &BANK3D};
 
-static Tensor bank_pack(const BankApi* net, Tensor blob) {
+// pack (transposed = false; the bank nets') or pack_t
+static Tensor net_pack(const NetApi* net, bool transposed, Tensor blob) {
   TORCH_CHECK(blob.is_cuda() && blob.scalar_type() == at::kFloat && blob.is_contiguous(), "weights blob must be a contiguous float32 GPU tensor");
-  TORCH_CHECK((size_t)blob.numel() == net->weight_floats(), "weights blob has ", blob.numel(), " floats, expected ", net->weight_floats());
+  TORCH_CHECK((size_t)blob.numel() == net->weight_floats(), "weights blob has ", blob.numel(), " floats, expected ", net->weight_floats(),
+              transposed ? net->blob_note : "");
   c10::hip::HIPGuard guard(blob.get_device());
-  Tensor packed = at::zeros({(int64_t)net->packed_bytes()}, blob.options().dtype(at::kByte));
-  check_status(net->pack(blob.data_ptr<float>(), packed.data_ptr(), cur_stream(blob)));
+  Tensor packed = at::zeros({(int64_t)(transposed ? net->packed_t_bytes : net->packed_bytes)()}, blob.options().dtype(at::kByte));
+  check_status((transposed ? net->pack_t : net->pack)(blob.data_ptr<float>(), packed.data_ptr(), cur_stream(blob)));
   return packed;
 }
 
-static void check_bank_image(const BankApi* net, const Tensor& packed) {
+// the forward image of a net's kind, by its size (the packers' images differ in it): inference of the bank nets, and the step's `net`
+static void check_forward_image(const NetApi* net, const Tensor& packed, const char* what) {
   TORCH_CHECK(packed.is_cuda() && packed.is_contiguous() && (size_t)packed.nbytes() == net->packed_bytes(),
-              "packed must be the ", net->packed_bytes(), "-byte image from ", net->pack_name, " (got ", packed.nbytes(), " bytes)");
+              what, " must be the ", net->packed_bytes(), "-byte image from ", net->pack_name, " (got ", packed.nbytes(), " bytes)");
+}
+// In training the forward's weight image and the backward's look alike and differ in size: a swapped pair must not reach the device.  The
+// ScaleNet's images are held to the input's device first, in words of their own; the bank nets' forward image is not held to it.
+static void check_train_image(const NetApi* net, const Tensor& t, bool transposed, const Tensor& like) {
+  // the bank nets' packed: the inference check, size and all, and no word about the device
+  if (!transposed && net->bank) return check_forward_image(net, t, "packed");
+  const char* what = transposed ? net->packed_t_what : "packed";
+  const bool placed = t.is_cuda() && t.is_contiguous() && t.get_device() == like.get_device();
+  // the ScaleNet's packed and packed_t, either dimension: the placement first, in words of its own
+  if (!net->bank) TORCH_CHECK(placed, what, " must be a contiguous weight image on the input's device");
+  // the 3D ScaleNet's two images: their size is the C ABI's to refuse
+  if (!net->image_sized) return;
+  // the size -- the 2D ScaleNet's two images (placed already) and the bank nets' packed_t, which says placement and size in one text
+  const size_t bytes = transposed ? net->packed_t_bytes() : net->packed_bytes();
+  TORCH_CHECK(placed && (size_t)t.nbytes() == bytes, what, " must be the ", bytes, "-byte image from ", transposed ? net->pack_t_name : net->pack_name,
+              net->bank ? " on the input's device" : "", " (got ", t.nbytes(), " bytes)");
 }
 
-static Tensor bank_forward(const BankApi* net, Tensor packed, Tensor x, const std::string& precision_mode) {
+static Tensor bank_forward(const NetApi* net, Tensor packed, Tensor x, const std::string& precision_mode) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.is_contiguous(), "x must be a contiguous float32 GPU tensor");
   TORCH_CHECK((x.dim() == 4 || x.dim() == 5) && x.size(1) == 2, "x must be (B,2,H,W) or (B,2,D,H,W)");
-  check_bank_image(net, packed);
+  check_forward_image(net, packed, "packed");
   FnxGrid g{}; g.B = (int)x.size(0); g.D = x.dim() == 5 ? (int)x.size(2) : 1; g.H = (int)x.size(x.dim() - 2); g.W = (int)x.size(x.dim() - 1);
   g.is3D = g.D > 1;
   c10::hip::HIPGuard guard(x.get_device());
@@ -635,12 +697,12 @@ static Tensor bank_forward(const BankApi* net, Tensor packed, Tensor x, const st
   return p;
 }
 
-// FluidNet.forward of any model.  net == nullptr: the ScaleNet, whose image has no size of its own to check
-static std::vector<Tensor> whole_forward(const BankApi* net, Tensor packed, Tensor input, double normalize_threshold,
+// FluidNet.forward of any model.  net == nullptr: the ScaleNet of either dimension, whose image has no size of its own to check
+static std::vector<Tensor> whole_forward(const NetApi* net, Tensor packed, Tensor input, double normalize_threshold,
                                          const std::string& precision_mode) {
   check_field(input, "input");
   TORCH_CHECK(input.size(1) == 5 || input.size(1) == 6, "input must have 5 (2D) or 6 (3D) channels [p, U, flags, density]");
-  if (net) check_bank_image(net, packed);
+  if (net) check_forward_image(net, packed, "packed");
   const bool is3D = input.size(1) == 6;
   FnxGrid g{}; g.B = (int)input.size(0); g.D = (int)input.size(2); g.H = (int)input.size(3); g.W = (int)input.size(4);
   g.is3D = is3D;
@@ -655,10 +717,7 @@ static std::vector<Tensor> whole_forward(const BankApi* net, Tensor packed, Tens
   return {p, U};
 }
 
-// ---- training: the CNN's backward pass (fnx_cnn_train.hip), the scenes and the loss (fnx_scenes.hip) -------------------------------
-// Every operation is one body that takes the dimension; the module registers it under its 2D and its 3D name.  A body builds the grid
-// it is given, of either dimension, and the C ABI of its own dimension refuses the other ("2D only", "3D only") before it touches the
-// device: a refused grid gets a token tape and workspace, so the C ABI's text is what is raised.
+// ---- training: the nets' backward passes, the scenes and the loss (fnx_scenes.hip) ---------------------------------------------------
 static FnxGrid make_grid(int64_t B, int64_t D, int64_t H, int64_t W, bool is3D) {
   FnxGrid g{}; g.B = (int)B; g.D = (int)D; g.H = (int)H; g.W = (int)W; g.is3D = is3D;
   return g;
@@ -670,34 +729,13 @@ static FnxGrid grid_of_net_tensor(const Tensor& x, const char* what) {
   const int64_t D = x.dim() == 5 ? x.size(2) : 1;
   return make_grid(x.size(0), D, x.size(x.dim() - 2), x.size(x.dim() - 1), D > 1);
 }
-// the size queries of a dimension: 0 for a grid it refuses
-static size_t tape_floats(bool is3d, const FnxGrid& g) {
-  return is3d ? fnx_multiscale3d_tape_layout(&g, nullptr) : fnx_multiscale_tape_layout(&g, nullptr);
-}
 static void check_tape(const Tensor& tape, size_t floats) {
   TORCH_CHECK(tape.is_cuda() && tape.scalar_type() == at::kFloat && tape.is_contiguous(), "tape must be a contiguous float32 GPU tensor");
   TORCH_CHECK(!floats || (size_t)tape.numel() == floats, "tape has ", tape.numel(), " floats, not the layout of this grid");
 }
-// The forward's weight image and the backward's look alike and differ in size: a swapped pair must not reach the device.  The 3D entry
-// points of the C ABI take the image's size and refuse a wrong one themselves; the 2D ones take no size, so it is checked here.
-static void check_image(bool is3d, const Tensor& t, bool transposed, const Tensor& like) {
-  const char* what = !transposed ? "packed" : is3d ? "packed3d_t" : "packed_t";
-  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.get_device() == like.get_device(), what, " must be a contiguous weight image on the input's device");
-  if (is3d) return;
-  const size_t bytes = transposed ? fnx_scalenet_packed_t_bytes() : fnx_scalenet_packed_bytes(0);
-  TORCH_CHECK((size_t)t.nbytes() == bytes, what, " must be the ", bytes, "-byte image from scalenet_pack", transposed ? "_t" : "", " (got ",
-              t.nbytes(), " bytes)");
-}
-
-Tensor scalenet_pack_t(bool is3d, Tensor blob) {
-  TORCH_CHECK(blob.is_cuda() && blob.scalar_type() == at::kFloat && blob.is_contiguous(), "weights blob must be a contiguous float32 GPU tensor");
-  TORCH_CHECK((size_t)blob.numel() == fnx_scalenet_weight_floats(is3d), "weights blob has ", blob.numel(), " floats, expected ",
-              fnx_scalenet_weight_floats(is3d), is3d ? " (the 3D net)" : "");
-  c10::hip::HIPGuard guard(blob.get_device());
-  const size_t bytes = is3d ? fnx_scalenet3d_packed_t_bytes() : fnx_scalenet_packed_t_bytes();
-  Tensor packed = at::zeros({(int64_t)bytes}, blob.options().dtype(at::kByte));
-  check_status((is3d ? fnx_scalenet3d_pack_t : fnx_scalenet_pack_t)(blob.data_ptr<float>(), packed.data_ptr(), cur_stream(blob)));
-  return packed;
+// a byte workspace of the net's size query for a grid whose tape has `floats` floats; a refused grid's token one is never read
+static Tensor train_ws(size_t floats, size_t (*bytes_of)(const FnxGrid*), const FnxGrid& g, const Tensor& like) {
+  return at::empty({(int64_t)std::max<size_t>(floats ? bytes_of(&g) : 0, 256)}, like.options().dtype(at::kByte));
 }
 
 // A tape layout of the C ABI -> (name, offset, C, H, W) per tape entry for FnxTapeEntry, (name, offset, C, D, H, W) for FnxTapeEntry3D
@@ -713,12 +751,6 @@ static std::vector<py::tuple> tape_tuples(const FnxGrid& g, int n, size_t (*layo
   return out;
 }
 
-std::vector<py::tuple> multiscale_tape_layout(bool is3d, int64_t B, int64_t D, int64_t H, int64_t W) {
-  const FnxGrid g = make_grid(B, D, H, W, is3d);
-  return is3d ? tape_tuples(g, fnx_multiscale_tape_entries(), fnx_multiscale3d_tape_layout)
-              : tape_tuples(g, fnx_multiscale_tape_entries(), fnx_multiscale_tape_layout);
-}
-
 // gd (B,1,Do,Ho,Wo) -> gs (B,1,Di,Hi,Wi): fnx_trilinear_upsample_backward
 Tensor trilinear_upsample_backward(Tensor gd, std::vector<int64_t> size) {
   TORCH_CHECK(gd.is_cuda() && gd.scalar_type() == at::kFloat && gd.is_contiguous() && gd.dim() == 5 && gd.size(1) == 1,
@@ -732,207 +764,96 @@ Tensor trilinear_upsample_backward(Tensor gd, std::vector<int64_t> size) {
 }
 
 // x (B,2,[D,]H,W) -> p, tape
-std::vector<Tensor> multiscale_forward_train(bool is3d, Tensor packed, Tensor x, const std::string& precision_mode) {
+static std::vector<Tensor> net_forward_train(const NetApi* net, Tensor packed, Tensor x, const std::string& precision_mode) {
   const FnxGrid g = grid_of_net_tensor(x, "x");
   TORCH_CHECK(x.size(1) == 2, "x must have 2 channels");
-  check_image(is3d, packed, false, x);
+  check_train_image(net, packed, false, x);
   c10::hip::HIPGuard guard(x.get_device());
   std::vector<int64_t> osz = x.sizes().vec(); osz[1] = 1;
   Tensor p = at::empty(osz, x.options());
-  const size_t floats = tape_floats(is3d, g);
+  const size_t floats = net->tape_floats(&g);
   Tensor tape = at::empty({(int64_t)(floats ? floats : 1)}, x.options());
-  const int mode = precision_of(precision_mode);
-  check_status(is3d ? fnx_multiscale3d_forward_train(&g, packed.data_ptr(), (size_t)packed.nbytes(), x.data_ptr<float>(), p.data_ptr<float>(),
-                                                     tape.data_ptr<float>(), mode, cur_stream(x))
-                    : fnx_multiscale_forward_train(&g, packed.data_ptr(), x.data_ptr<float>(), p.data_ptr<float>(), tape.data_ptr<float>(), mode,
-                                                   cur_stream(x)));
+  check_status(net->forward_train(&g, packed.data_ptr(), (size_t)packed.nbytes(), x.data_ptr<float>(), p.data_ptr<float>(),
+                                  tape.data_ptr<float>(), precision_of(precision_mode), cur_stream(x)));
   return {p, tape};
 }
 
-// plain: the plain weight-gradient kernel for every layer (fnx_multiscale*_backward_plain), a cross-check and not a training path
-static Tensor multiscale_backward_impl(bool is3d, bool plain, Tensor packed_t, Tensor grad_p, Tensor tape, const std::string& precision_mode) {
+// grad_p (B,1,[D,]H,W), the forward's tape and, for the bank nets, its x -> the gradient in the blob's layout.  plain: the ScaleNet's plain
+// weight-gradient kernel for every layer (fnx_multiscale*_backward_plain), a cross-check and not a training path
+static Tensor net_backward(const NetApi* net, bool plain, Tensor packed_t, const Tensor* x, Tensor grad_p, Tensor tape,
+                           const std::string& precision_mode) {
   const FnxGrid g = grid_of_net_tensor(grad_p, "grad_p");
-  check_image(is3d, packed_t, true, grad_p);
-  TORCH_CHECK(grad_p.size(1) == 1, "grad_p must have 1 channel");
-  const size_t floats = tape_floats(is3d, g);
+  if (x) {
+    grid_of_net_tensor(*x, "x");
+    TORCH_CHECK(grad_p.size(1) == 1 && x->size(1) == 2 && x->dim() == grad_p.dim() && x->size(0) == grad_p.size(0) &&
+                x->numel() == 2 * grad_p.numel() && x->size(x->dim() - 2) == grad_p.size(x->dim() - 2) &&
+                x->size(x->dim() - 1) == grad_p.size(x->dim() - 1),
+                "grad_p (1 channel) and x (2 channels) must share their grid");
+  }
+  check_train_image(net, packed_t, true, grad_p);
+  if (!x) TORCH_CHECK(grad_p.size(1) == 1, "grad_p must have 1 channel");
+  const size_t floats = net->tape_floats(&g);
   check_tape(tape, floats);
   c10::hip::HIPGuard guard(grad_p.get_device());
-  Tensor grad = at::empty({(int64_t)fnx_scalenet_weight_floats(is3d)}, grad_p.options());
-  const size_t bytes = !floats ? 1 : is3d ? fnx_multiscale3d_backward_ws_bytes(&g) : fnx_multiscale_backward_ws_bytes(&g);
-  Tensor ws = at::empty({(int64_t)bytes}, grad_p.options().dtype(at::kByte));
-  const int mode = precision_of(precision_mode);
-  check_status(is3d ? (plain ? fnx_multiscale3d_backward_plain : fnx_multiscale3d_backward)(
-                          &g, packed_t.data_ptr(), (size_t)packed_t.nbytes(), grad_p.data_ptr<float>(), tape.data_ptr<float>(),
-                          grad.data_ptr<float>(), mode, ws.data_ptr(), bytes, cur_stream(grad_p))
-                    : (plain ? fnx_multiscale_backward_plain : fnx_multiscale_backward)(
-                          &g, packed_t.data_ptr(), grad_p.data_ptr<float>(), tape.data_ptr<float>(), grad.data_ptr<float>(), mode, ws.data_ptr(),
-                          bytes, cur_stream(grad_p)));
+  Tensor grad = at::empty({(int64_t)net->weight_floats()}, grad_p.options());
+  Tensor ws = train_ws(floats, net->backward_ws_bytes, g, grad_p);
+  check_status((plain ? net->backward_plain : net->backward)(&g, packed_t.data_ptr(), (size_t)packed_t.nbytes(), x ? x->data_ptr<float>() : nullptr,
+                                                             grad_p.data_ptr<float>(), tape.data_ptr<float>(), grad.data_ptr<float>(),
+                                                             precision_of(precision_mode), ws.data_ptr(), (size_t)ws.nbytes(),
+                                                             cur_stream(grad_p)));
   return grad;
 }
-Tensor multiscale_backward(bool is3d, Tensor packed_t, Tensor grad_p, Tensor tape, const std::string& precision_mode) {
-  return multiscale_backward_impl(is3d, false, packed_t, grad_p, tape, precision_mode);
+static Tensor scalenet_backward(const NetApi* net, Tensor packed_t, Tensor grad_p, Tensor tape, const std::string& precision_mode) {
+  return net_backward(net, false, packed_t, nullptr, grad_p, tape, precision_mode);
 }
-Tensor multiscale_backward_plain(bool is3d, Tensor packed_t, Tensor grad_p, Tensor tape, const std::string& precision_mode) {
-  return multiscale_backward_impl(is3d, true, packed_t, grad_p, tape, precision_mode);
+static Tensor scalenet_backward_plain(const NetApi* net, Tensor packed_t, Tensor grad_p, Tensor tape, const std::string& precision_mode) {
+  return net_backward(net, true, packed_t, nullptr, grad_p, tape, precision_mode);
+}
+static Tensor bank_backward(const NetApi* net, Tensor packed_t, Tensor x, Tensor grad_p, Tensor tape, const std::string& precision_mode) {
+  return net_backward(net, false, packed_t, &x, grad_p, tape, precision_mode);
 }
 
 // input (B,5|6,D,H,W) = [p, U, flags, density] -> p, U, tape, s (B), flags (B,1,D,H,W)
-std::vector<Tensor> fluidnet_forward_train(bool is3d, Tensor packed, Tensor input, double normalize_threshold, const std::string& precision_mode) {
+static std::vector<Tensor> whole_forward_train(const NetApi* net, Tensor packed, Tensor input, double normalize_threshold,
+                                               const std::string& precision_mode) {
   check_field(input, "input");
   TORCH_CHECK(input.size(1) == 5 || input.size(1) == 6, "input must have 5 (2D) or 6 (3D) channels [p, U, flags, density]");
   const FnxGrid g = make_grid(input.size(0), input.size(2), input.size(3), input.size(4), input.size(1) == 6);
-  check_image(is3d, packed, false, input);
+  check_train_image(net, packed, false, input);
   c10::hip::HIPGuard guard(input.get_device());
   Tensor p = at::empty({g.B, 1, g.D, g.H, g.W}, input.options());
   Tensor U = at::empty({g.B, g.is3D ? 3 : 2, g.D, g.H, g.W}, input.options());
   Tensor flags = at::empty({g.B, 1, g.D, g.H, g.W}, input.options());
   Tensor scale = at::empty({g.B}, input.options());
-  const size_t floats = tape_floats(is3d, g);
-  const size_t bytes = !floats ? 1 : is3d ? fnx_fluidnet3d_train_ws_bytes(&g) : fnx_fluidnet_train_ws_bytes(&g);
+  const size_t floats = net->tape_floats(&g);
   Tensor tape = at::empty({(int64_t)(floats ? floats : 1)}, input.options());
-  Tensor ws = at::empty({(int64_t)bytes}, input.options().dtype(at::kByte));
-  const int mode = precision_of(precision_mode);
-  const float thr = (float)normalize_threshold;
-  check_status(is3d ? fnx_fluidnet3d_forward_train(&g, packed.data_ptr(), (size_t)packed.nbytes(), input.data_ptr<float>(), thr, p.data_ptr<float>(),
-                                                   U.data_ptr<float>(), flags.data_ptr<float>(), scale.data_ptr<float>(), tape.data_ptr<float>(),
-                                                   mode, ws.data_ptr(), bytes, cur_stream(input))
-                    : fnx_fluidnet_forward_train(&g, packed.data_ptr(), input.data_ptr<float>(), thr, p.data_ptr<float>(), U.data_ptr<float>(),
-                                                 flags.data_ptr<float>(), scale.data_ptr<float>(), tape.data_ptr<float>(), mode, ws.data_ptr(),
-                                                 bytes, cur_stream(input)));
+  Tensor ws = train_ws(floats, net->train_ws_bytes, g, input);
+  check_status(net->whole_forward_train(&g, packed.data_ptr(), (size_t)packed.nbytes(), input.data_ptr<float>(), (float)normalize_threshold,
+                                        p.data_ptr<float>(), U.data_ptr<float>(), flags.data_ptr<float>(), scale.data_ptr<float>(),
+                                        tape.data_ptr<float>(), precision_of(precision_mode), ws.data_ptr(), (size_t)ws.nbytes(),
+                                        cur_stream(input)));
   return {p, U, tape, scale, flags};
 }
 
 // grad_p (B,1,D,H,W), grad_U (B,2|3,D,H,W), flags (B,1,D,H,W) and scale (B) of the forward -> the gradient in the blob's layout
-Tensor fluidnet_backward(bool is3d, Tensor packed_t, Tensor flags, Tensor scale, Tensor grad_p, Tensor grad_U, Tensor tape,
-                         const std::string& precision_mode) {
+static Tensor whole_backward(const NetApi* net, Tensor packed_t, Tensor flags, Tensor scale, Tensor grad_p, Tensor grad_U, Tensor tape,
+                             const std::string& precision_mode) {
   check_field(grad_p, "grad_p"); check_field(grad_U, "grad_U"); check_field(flags, "flags");
-  TORCH_CHECK(grad_p.size(1) == 1 && grad_U.size(1) == (is3d ? 3 : 2) && flags.size(1) == 1, "grad_p and flags must have 1 channel, grad_U ",
-              is3d ? 3 : 2);
-  TORCH_CHECK(grad_U.size(0) == grad_p.size(0) && grad_U.size(2) == grad_p.size(2) && grad_U.size(3) == grad_p.size(3) &&
-              grad_U.size(4) == grad_p.size(4) && flags.sizes() == grad_p.sizes(), "grad_p, grad_U and flags must share their grid");
-  const FnxGrid g = make_grid(grad_p.size(0), grad_p.size(2), grad_p.size(3), grad_p.size(4), is3d);
-  check_image(is3d, packed_t, true, grad_p);
-  TORCH_CHECK(scale.is_cuda() && scale.scalar_type() == at::kFloat && scale.is_contiguous() && scale.numel() == g.B, "scale must hold B floats on the GPU");
-  const size_t floats = tape_floats(is3d, g);
-  check_tape(tape, floats);
-  c10::hip::HIPGuard guard(grad_p.get_device());
-  Tensor grad = at::empty({(int64_t)fnx_scalenet_weight_floats(is3d)}, grad_p.options());
-  const size_t bytes = !floats ? 1 : is3d ? fnx_fluidnet3d_train_ws_bytes(&g) : fnx_fluidnet_train_ws_bytes(&g);
-  Tensor ws = at::empty({(int64_t)bytes}, grad_p.options().dtype(at::kByte));
-  const int mode = precision_of(precision_mode);
-  check_status(is3d ? fnx_fluidnet3d_backward(&g, packed_t.data_ptr(), (size_t)packed_t.nbytes(), flags.data_ptr<float>(), scale.data_ptr<float>(),
-                                              grad_p.data_ptr<float>(), grad_U.data_ptr<float>(), tape.data_ptr<float>(), grad.data_ptr<float>(),
-                                              mode, ws.data_ptr(), bytes, cur_stream(grad_p))
-                    : fnx_fluidnet_backward(&g, packed_t.data_ptr(), flags.data_ptr<float>(), scale.data_ptr<float>(), grad_p.data_ptr<float>(),
-                                            grad_U.data_ptr<float>(), tape.data_ptr<float>(), grad.data_ptr<float>(), mode, ws.data_ptr(), bytes,
-                                            cur_stream(grad_p)));
-  return grad;
-}
-
-// ---- training of the bank nets (fnx_banknet_train.hip, fnx_banknet3d_train.hip): the bodies above with the net's entry points; a grid the
-// C ABI refuses gets a token tape and workspace, so that the C ABI's text is what is raised ---------------------------------------------
-static void check_bank_image_t(const BankApi* net, const Tensor& packed_t, const Tensor& like) {
-  TORCH_CHECK(packed_t.is_cuda() && packed_t.is_contiguous() && packed_t.get_device() == like.get_device() &&
-              (size_t)packed_t.nbytes() == net->packed_t_bytes(),
-              "packed_t must be the ", net->packed_t_bytes(), "-byte image from ", net->pack_t_name, " on the input's device (got ",
-              packed_t.nbytes(), " bytes)");
-}
-
-static Tensor bank_pack_t(const BankApi* net, Tensor blob) {
-  TORCH_CHECK(blob.is_cuda() && blob.scalar_type() == at::kFloat && blob.is_contiguous(), "weights blob must be a contiguous float32 GPU tensor");
-  TORCH_CHECK((size_t)blob.numel() == net->weight_floats(), "weights blob has ", blob.numel(), " floats, expected ", net->weight_floats());
-  c10::hip::HIPGuard guard(blob.get_device());
-  Tensor packed = at::zeros({(int64_t)net->packed_t_bytes()}, blob.options().dtype(at::kByte));
-  check_status(net->pack_t(blob.data_ptr<float>(), packed.data_ptr(), cur_stream(blob)));
-  return packed;
-}
-
-// -> (name, offset, C, H, W) per tape entry
-std::vector<py::tuple> banknet_tape_layout(int64_t B, int64_t H, int64_t W) {
-  return tape_tuples(make_grid(B, 1, H, W, false), fnx_banknet_tape_entries(), fnx_banknet_tape_layout);
-}
-// -> (name, offset, C, D, H, W) per tape entry
-std::vector<py::tuple> banknet3d_tape_layout(int64_t B, int64_t D, int64_t H, int64_t W) {
-  return tape_tuples(make_grid(B, D, H, W, true), fnx_banknet3d_tape_entries(), fnx_banknet3d_tape_layout);
-}
-
-// x (B,2,[D,]H,W) -> p, tape
-static std::vector<Tensor> bank_forward_train(const BankApi* net, Tensor packed, Tensor x, const std::string& precision_mode) {
-  const FnxGrid g = grid_of_net_tensor(x, "x");
-  TORCH_CHECK(x.size(1) == 2, "x must have 2 channels");
-  check_bank_image(net, packed);
-  c10::hip::HIPGuard guard(x.get_device());
-  std::vector<int64_t> osz = x.sizes().vec(); osz[1] = 1;
-  Tensor p = at::empty(osz, x.options());
-  const size_t floats = net->tape_floats(g);
-  Tensor tape = at::empty({(int64_t)(floats ? floats : 1)}, x.options());
-  check_status(net->forward_train(&g, packed.data_ptr(), x.data_ptr<float>(), p.data_ptr<float>(), tape.data_ptr<float>(),
-                                  precision_of(precision_mode), cur_stream(x)));
-  return {p, tape};
-}
-
-// grad_p (B,1,[D,]H,W), the forward's tape and x -> the gradient in the blob's layout
-static Tensor bank_backward(const BankApi* net, Tensor packed_t, Tensor x, Tensor grad_p, Tensor tape, const std::string& precision_mode) {
-  const FnxGrid g = grid_of_net_tensor(grad_p, "grad_p");
-  grid_of_net_tensor(x, "x");
-  TORCH_CHECK(grad_p.size(1) == 1 && x.size(1) == 2 && x.dim() == grad_p.dim() && x.size(0) == grad_p.size(0) &&
-              x.numel() == 2 * grad_p.numel() && x.size(x.dim() - 2) == grad_p.size(x.dim() - 2) &&
-              x.size(x.dim() - 1) == grad_p.size(x.dim() - 1),
-              "grad_p (1 channel) and x (2 channels) must share their grid");
-  check_bank_image_t(net, packed_t, grad_p);
-  const size_t floats = net->tape_floats(g);
-  check_tape(tape, floats);
-  c10::hip::HIPGuard guard(grad_p.get_device());
-  Tensor grad = at::empty({(int64_t)net->weight_floats()}, grad_p.options());
-  const size_t bytes = std::max<size_t>(floats ? net->backward_ws_bytes(&g) : 0, 256);
-  Tensor ws = at::empty({(int64_t)bytes}, grad_p.options().dtype(at::kByte));
-  check_status(net->backward(&g, packed_t.data_ptr(), x.data_ptr<float>(), grad_p.data_ptr<float>(), tape.data_ptr<float>(),
-                             grad.data_ptr<float>(), precision_of(precision_mode), ws.data_ptr(), bytes, cur_stream(grad_p)));
-  return grad;
-}
-
-// input (B,5|6,D,H,W) = [p, U, flags, density] -> p, U, tape, s (B), flags (B,1,D,H,W)
-static std::vector<Tensor> bank_whole_forward_train(const BankApi* net, Tensor packed, Tensor input, double normalize_threshold,
-                                                    const std::string& precision_mode) {
-  check_field(input, "input");
-  TORCH_CHECK(input.size(1) == 5 || input.size(1) == 6, "input must have 5 (2D) or 6 (3D) channels [p, U, flags, density]");
-  const FnxGrid g = make_grid(input.size(0), input.size(2), input.size(3), input.size(4), input.size(1) == 6);
-  check_bank_image(net, packed);
-  c10::hip::HIPGuard guard(input.get_device());
-  Tensor p = at::empty({g.B, 1, g.D, g.H, g.W}, input.options());
-  Tensor U = at::empty({g.B, g.is3D ? 3 : 2, g.D, g.H, g.W}, input.options());
-  Tensor flags = at::empty({g.B, 1, g.D, g.H, g.W}, input.options());
-  Tensor scale = at::empty({g.B}, input.options());
-  const size_t floats = net->tape_floats(g);
-  const size_t bytes = std::max<size_t>(floats ? net->train_ws_bytes(&g) : 0, 256);
-  Tensor tape = at::empty({(int64_t)(floats ? floats : 1)}, input.options());
-  Tensor ws = at::empty({(int64_t)bytes}, input.options().dtype(at::kByte));
-  check_status(net->whole_forward_train(&g, packed.data_ptr(), input.data_ptr<float>(), (float)normalize_threshold, p.data_ptr<float>(),
-                                        U.data_ptr<float>(), flags.data_ptr<float>(), scale.data_ptr<float>(), tape.data_ptr<float>(),
-                                        precision_of(precision_mode), ws.data_ptr(), bytes, cur_stream(input)));
-  return {p, U, tape, scale, flags};
-}
-
-// grad_p (B,1,D,H,W), grad_U (B,2|3,D,H,W), flags and scale of the forward -> the gradient in the blob's layout
-static Tensor bank_whole_backward(const BankApi* net, Tensor packed_t, Tensor flags, Tensor scale, Tensor grad_p, Tensor grad_U, Tensor tape,
-                                  const std::string& precision_mode) {
-  check_field(grad_p, "grad_p"); check_field(grad_U, "grad_U"); check_field(flags, "flags");
-  const int64_t nc = net == &BANK3D ? 3 : 2;
+  const int64_t nc = net->ndim;
   TORCH_CHECK(grad_p.size(1) == 1 && grad_U.size(1) == nc && flags.size(1) == 1, "grad_p and flags must have 1 channel, grad_U ", nc);
   TORCH_CHECK(grad_U.size(0) == grad_p.size(0) && grad_U.size(2) == grad_p.size(2) && grad_U.size(3) == grad_p.size(3) &&
               grad_U.size(4) == grad_p.size(4) && flags.sizes() == grad_p.sizes(), "grad_p, grad_U and flags must share their grid");
-  const FnxGrid g = make_grid(grad_p.size(0), grad_p.size(2), grad_p.size(3), grad_p.size(4), grad_p.size(2) > 1);
-  check_bank_image_t(net, packed_t, grad_p);
+  const FnxGrid g = make_grid(grad_p.size(0), grad_p.size(2), grad_p.size(3), grad_p.size(4), net->bank ? grad_p.size(2) > 1 : nc == 3);
+  check_train_image(net, packed_t, true, grad_p);
   TORCH_CHECK(scale.is_cuda() && scale.scalar_type() == at::kFloat && scale.is_contiguous() && scale.numel() == g.B, "scale must hold B floats on the GPU");
-  const size_t floats = net->tape_floats(g);
+  const size_t floats = net->tape_floats(&g);
   check_tape(tape, floats);
   c10::hip::HIPGuard guard(grad_p.get_device());
   Tensor grad = at::empty({(int64_t)net->weight_floats()}, grad_p.options());
-  const size_t bytes = std::max<size_t>(floats ? net->train_ws_bytes(&g) : 0, 256);
-  Tensor ws = at::empty({(int64_t)bytes}, grad_p.options().dtype(at::kByte));
-  check_status(net->whole_backward(&g, packed_t.data_ptr(), flags.data_ptr<float>(), scale.data_ptr<float>(), grad_p.data_ptr<float>(),
-                                   grad_U.data_ptr<float>(), tape.data_ptr<float>(), grad.data_ptr<float>(), precision_of(precision_mode),
-                                   ws.data_ptr(), bytes, cur_stream(grad_p)));
+  Tensor ws = train_ws(floats, net->train_ws_bytes, g, grad_p);
+  check_status(net->whole_backward(&g, packed_t.data_ptr(), (size_t)packed_t.nbytes(), flags.data_ptr<float>(), scale.data_ptr<float>(),
+                                   grad_p.data_ptr<float>(), grad_U.data_ptr<float>(), tape.data_ptr<float>(), grad.data_ptr<float>(),
+                                   precision_of(precision_mode), ws.data_ptr(), (size_t)ws.nbytes(), cur_stream(grad_p)));
   return grad;
 }
 
@@ -1059,16 +980,12 @@ void simulate_step_(Tensor p, Tensor U, Tensor flags, c10::optional<Tensor> dens
   prm.vorticity_confinement = (float)vorticity_confinement;
   FnxState st = make_state(g, p, U, flags, density, UBC, UBCInvMask, densityBC, densityBCInvMask);
   st.net = (net.has_value() && net->defined()) ? net->data_ptr() : nullptr;
-  // the image against its kind, by size (the three packers' images differ in it), as bank_forward checks its own
+  // the image against its kind, by size (the three packers' images differ in it), as bank_forward checks its own (the nets' table)
   TORCH_CHECK(net_kind == "scalenet" || net_kind == "bank" || net_kind == "bank3d", "net_kind: 'scalenet', 'bank' or 'bank3d' (got '", net_kind, "')");
   const int kind = net_kind == "bank" ? FNX_NET_BANK : (net_kind == "bank3d" ? FNX_NET_BANK3D : FNX_NET_SCALENET);   // (bank3d: refused by the C ABI)
   if (st.net && (prm.method == 1 || prm.method == 3)) {
-    if (kind == FNX_NET_SCALENET) {
-      TORCH_CHECK(net->is_cuda() && net->is_contiguous() && (size_t)net->nbytes() == fnx_scalenet_packed_bytes(g.is3D),
-                  "net must be the ", fnx_scalenet_packed_bytes(g.is3D), "-byte image from scalenet_pack (got ", net->nbytes(), " bytes)");
-    } else {
-      check_bank_image(kind == FNX_NET_BANK ? &BANK2D : &BANK3D, *net);
-    }
+    if (kind == FNX_NET_SCALENET) check_forward_image(g.is3D ? &SCALE3D : &SCALE2D, *net, "net");
+    else check_forward_image(kind == FNX_NET_BANK ? &BANK2D : &BANK3D, *net, "packed");
   }
   st.flags_stick = opt_field(g, flags_stick, false, "flags_stick");
   c10::hip::HIPGuard guard(flags.get_device());
@@ -1314,8 +1231,8 @@ int64_t step_workspace_bytes(int B, int D, int H, int W, bool is3D) {
 
 }  // namespace
 
-// an operation's one body with its dimension (training) or its net's entry points (the bank nets) bound: what the module registers under
-// the operation's 2D and 3D name
+// an operation's one body with its dimension (scenes, loss) or its net's table row bound: what the module registers under the operation's
+// names
 template <class T, class R, class... A>
 static auto in_dim(T which, R (*body)(T, A...)) {
   return [=](A... a) { return body(which, std::forward<A>(a)...); };
@@ -1397,29 +1314,40 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("scalenet_pack", &scalenet_pack, NoGil());
   m.def("multiscale_forward", &multiscale_forward, py::arg("packed"), py::arg("x"), py::arg("precision_mode") = "fp32",
         py::arg("trim") = std::vector<int64_t>(), NoGil());
-  m.def("fluidnet_forward", in_dim((const BankApi*)nullptr, &whole_forward), py::arg("packed"), py::arg("input"),
+  m.def("fluidnet_forward", in_dim((const NetApi*)nullptr, &whole_forward), py::arg("packed"), py::arg("input"),
         py::arg("normalize_threshold"), py::arg("precision_mode") = "fp32", NoGil());
-  m.def("banknet_pack", in_dim(&BANK2D, &bank_pack), py::arg("blob"), NoGil());
-  m.def("banknet_forward", in_dim(&BANK2D, &bank_forward), py::arg("packed"), py::arg("x"), py::arg("precision_mode") = "fp32", NoGil());
-  m.def("fluidnet_bank_forward", in_dim(&BANK2D, &whole_forward), py::arg("packed"), py::arg("input"), py::arg("normalize_threshold"),
-        py::arg("precision_mode") = "fp32", NoGil());
-  m.def("banknet3d_pack", in_dim(&BANK3D, &bank_pack), py::arg("blob"), NoGil());
-  m.def("banknet3d_forward", in_dim(&BANK3D, &bank_forward), py::arg("packed"), py::arg("x"), py::arg("precision_mode") = "fp32", NoGil());
-  m.def("fluidnet_bank3d_forward", in_dim(&BANK3D, &whole_forward), py::arg("packed"), py::arg("input"), py::arg("normalize_threshold"),
-        py::arg("precision_mode") = "fp32", NoGil());
-  m.def("banknet_tape_layout", &banknet_tape_layout, py::arg("B"), py::arg("H"), py::arg("W"));
-  m.def("banknet3d_tape_layout", &banknet3d_tape_layout, py::arg("B"), py::arg("D"), py::arg("H"), py::arg("W"));
-  for (const BankApi* net : {&BANK2D, &BANK3D}) {
-    const std::string n3 = net == &BANK3D ? "3d" : "";
-    m.def(("banknet" + n3 + "_pack_t").c_str(), in_dim(net, &bank_pack_t), py::arg("blob"), NoGil());
-    m.def(("banknet" + n3 + "_forward_train").c_str(), in_dim(net, &bank_forward_train), py::arg("packed"), py::arg("x"),
+  m.def("multiscale_tape_layout", [](int64_t B, int64_t H, int64_t W) {
+    return tape_tuples(make_grid(B, 1, H, W, false), fnx_multiscale_tape_entries(), fnx_multiscale_tape_layout); }, py::arg("B"), py::arg("H"), py::arg("W"));
+  m.def("multiscale3d_tape_layout", [](int64_t B, int64_t D, int64_t H, int64_t W) {
+    return tape_tuples(make_grid(B, D, H, W, true), fnx_multiscale_tape_entries(), fnx_multiscale3d_tape_layout); }, py::arg("B"), py::arg("D"), py::arg("H"), py::arg("W"));
+  m.def("banknet_tape_layout", [](int64_t B, int64_t H, int64_t W) {
+    return tape_tuples(make_grid(B, 1, H, W, false), fnx_banknet_tape_entries(), fnx_banknet_tape_layout); }, py::arg("B"), py::arg("H"), py::arg("W"));
+  m.def("banknet3d_tape_layout", [](int64_t B, int64_t D, int64_t H, int64_t W) {
+    return tape_tuples(make_grid(B, D, H, W, true), fnx_banknet3d_tape_entries(), fnx_banknet3d_tape_layout); }, py::arg("B"), py::arg("D"), py::arg("H"), py::arg("W"));
+  // the four nets' operations, under the row's names; what one family alone has: the bank nets' inference names and their backward's x,
+  // the ScaleNet's backward_plain
+  for (const NetApi* net : NETS) {
+    const std::string n = net->net_name, w = net->whole_name;
+    m.def(net->pack_t_name, [net](Tensor blob) { return net_pack(net, true, blob); }, py::arg("blob"), NoGil());
+    m.def((n + "_forward_train").c_str(), in_dim(net, &net_forward_train), py::arg("packed"), py::arg("x"), py::arg("precision_mode") = "fp32",
+          NoGil());
+    if (net->bank) {
+      m.def(net->pack_name, [net](Tensor blob) { return net_pack(net, false, blob); }, py::arg("blob"), NoGil());
+      m.def((n + "_forward").c_str(), in_dim(net, &bank_forward), py::arg("packed"), py::arg("x"), py::arg("precision_mode") = "fp32", NoGil());
+      m.def((w + "_forward").c_str(), in_dim(net, &whole_forward), py::arg("packed"), py::arg("input"), py::arg("normalize_threshold"),
+            py::arg("precision_mode") = "fp32", NoGil());
+      m.def((n + "_backward").c_str(), in_dim(net, &bank_backward), py::arg("packed_t"), py::arg("x"), py::arg("grad_p"), py::arg("tape"),
+            py::arg("precision_mode") = "fp32", NoGil());
+    } else {
+      m.def((n + "_backward").c_str(), in_dim(net, &scalenet_backward), py::arg("packed_t"), py::arg("grad_p"), py::arg("tape"),
+            py::arg("precision_mode") = "fp32", NoGil());
+      m.def((n + "_backward_plain").c_str(), in_dim(net, &scalenet_backward_plain), py::arg("packed_t"), py::arg("grad_p"), py::arg("tape"),
+            py::arg("precision_mode") = "fp32", NoGil());
+    }
+    m.def((w + "_forward_train").c_str(), in_dim(net, &whole_forward_train), py::arg("packed"), py::arg("input"), py::arg("normalize_threshold"),
           py::arg("precision_mode") = "fp32", NoGil());
-    m.def(("banknet" + n3 + "_backward").c_str(), in_dim(net, &bank_backward), py::arg("packed_t"), py::arg("x"), py::arg("grad_p"),
-          py::arg("tape"), py::arg("precision_mode") = "fp32", NoGil());
-    m.def(("fluidnet_bank" + n3 + "_forward_train").c_str(), in_dim(net, &bank_whole_forward_train), py::arg("packed"), py::arg("input"),
-          py::arg("normalize_threshold"), py::arg("precision_mode") = "fp32", NoGil());
-    m.def(("fluidnet_bank" + n3 + "_backward").c_str(), in_dim(net, &bank_whole_backward), py::arg("packed_t"), py::arg("flags"),
-          py::arg("scale"), py::arg("grad_p"), py::arg("grad_U"), py::arg("tape"), py::arg("precision_mode") = "fp32", NoGil());
+    m.def((w + "_backward").c_str(), in_dim(net, &whole_backward), py::arg("packed_t"), py::arg("flags"), py::arg("scale"), py::arg("grad_p"),
+          py::arg("grad_U"), py::arg("tape"), py::arg("precision_mode") = "fp32", NoGil());
   }
   m.def("simulate_step_", &simulate_step_, py::arg("p"), py::arg("U"), py::arg("flags"), py::arg("density"), py::arg("UBC"),
         py::arg("UBCInvMask"), py::arg("densityBC"), py::arg("densityBCInvMask"), py::arg("net"), py::arg("dt"),
@@ -1526,9 +1454,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            py::arg("normalize_threshold") = 1e-5, py::arg("method") = "auto", py::arg("viscosity") = 0.0, NoGil());
   m.def("device_name", []() { const char* n = fnx_device_name(); return std::string(n ? n : ""); });
   m.def("trilinear_upsample_backward", &trilinear_upsample_backward, py::arg("grad_dst"), py::arg("size"), NoGil());
-  m.def("multiscale_tape_layout", [](int64_t B, int64_t H, int64_t W) { return multiscale_tape_layout(false, B, 1, H, W); }, py::arg("B"),
-        py::arg("H"), py::arg("W"));
-  m.def("multiscale3d_tape_layout", in_dim(true, &multiscale_tape_layout), py::arg("B"), py::arg("D"), py::arg("H"), py::arg("W"));
   m.def("scene_obstacles",
         [](Tensor ids, int64_t H, int64_t W, int64_t seed, int n_min, int n_max, double centre_min, double centre_max, double size_min,
            double size_max, int64_t depth) {
@@ -1547,23 +1472,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("density_scale"), py::arg("with_density") = true, py::arg("depth") = 1, NoGil());
   m.def("scene_turbulence3d", in_dim(true, &scene_turbulence), py::arg("scene_ids"), py::arg("D"), py::arg("H"), py::arg("W"), py::arg("seed"),
         py::arg("octaves"), py::arg("wavelength"), py::arg("amplitude"), py::arg("density_scale"), py::arg("with_density") = true, NoGil());
-  // the operations whose two names differ in the dimension alone: "<net>_..." in 2D, "<net>3d_..." in 3D
-  for (const bool is3d : {false, true}) {
-    const std::string d = is3d ? "3d" : "";
-    m.def(("scalenet" + d + "_pack_t").c_str(), in_dim(is3d, &scalenet_pack_t), py::arg("blob"), NoGil());
-    m.def(("multiscale" + d + "_forward_train").c_str(), in_dim(is3d, &multiscale_forward_train), py::arg("packed"), py::arg("x"),
-          py::arg("precision_mode") = "fp32", NoGil());
-    m.def(("multiscale" + d + "_backward").c_str(), in_dim(is3d, &multiscale_backward), py::arg("packed_t"), py::arg("grad_p"), py::arg("tape"),
-          py::arg("precision_mode") = "fp32", NoGil());
-    m.def(("multiscale" + d + "_backward_plain").c_str(), in_dim(is3d, &multiscale_backward_plain), py::arg("packed_t"), py::arg("grad_p"),
-          py::arg("tape"), py::arg("precision_mode") = "fp32", NoGil());
-    m.def(("fluidnet" + d + "_forward_train").c_str(), in_dim(is3d, &fluidnet_forward_train), py::arg("packed"), py::arg("input"),
-          py::arg("normalize_threshold"), py::arg("precision_mode") = "fp32", NoGil());
-    m.def(("fluidnet" + d + "_backward").c_str(), in_dim(is3d, &fluidnet_backward), py::arg("packed_t"), py::arg("flags"), py::arg("scale"),
-          py::arg("grad_p"), py::arg("grad_U"), py::arg("tape"), py::arg("precision_mode") = "fp32", NoGil());
+  for (const bool is3d : {false, true})
     m.def(is3d ? "train_loss3d" : "train_loss", in_dim(is3d, &train_loss), py::arg("out_p"), py::arg("out_U"), py::arg("flags"),
           py::arg("target_p"), py::arg("lambdas"), py::arg("upstream") = py::none(), py::arg("terms") = true, NoGil());
-  }
   m.def("abi_version", &fnx_abi_version);
   m.def("profile_enable", [](bool on, bool runs) { fnx_profile_enable(on ? (runs ? 2 : 1) : 0); }, py::arg("on"), py::arg("runs") = false);
   m.def("roctx_enable", [](bool on) { check_status(fnx_roctx_enable(on ? 1 : 0)); });

@@ -12,16 +12,20 @@
 #include <dlfcn.h>
 
 namespace {
-
 thread_local char g_err[512] = "";
-
-int fail(int code, const char* fmt, ...) {
+}
+// the thread's message (fnx_last_error) and the code to return, for every unit (fnx_kernels.h)
+int fnx::set_error(int code, const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
   return code;
 }
+
+namespace {
+
+constexpr auto fail = fnx::set_error;      // (this unit's older name for it)
 
 #define HIP_OK(expr)                                                                      \
   do {                                                                                    \
@@ -101,16 +105,6 @@ size_t ws_step_static(const FnxGrid* g) {
 }
 
 }  // namespace
-
-namespace fnx {
-int set_error(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
-}  // namespace fnx
 
 // ---- event-pair profiler ----------------------------------------------------------------------------
 namespace fnx {

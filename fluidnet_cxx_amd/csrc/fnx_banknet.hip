@@ -69,10 +69,13 @@ size_t bank_whole_ws(const FnxGrid* g) { return fluidnet_whole_ws_bytes(g->B, (s
 
 }  // namespace
 
-// the net as fnx_fluidnet.hip's fluidnet_core runs it in the native step (fnx_fluidnet.h)
-size_t bank_net_ws_bytes(const FnxGrid* g) { return bank_net_ws(g); }
-void bank_net_forward(const FnxGrid* g, const void* packed, const float* x, float* p, void* ws, hipStream_t s) {
-  banknet_forward(g->B, g->H, g->W, (const float*)packed, x, p, ws, s);
+// the net as FluidNet.forward's wrapper runs it (fnx_fluidnet.h)
+const Net& banknet_net() {
+  static const Net net = {2, FNX_NET_BANK, bank_status, bank_net_ws,
+                          [](const FnxGrid* g, const void* packed, const float* x, float* p, int, void* ws, hipStream_t s) {
+                            banknet_forward(g->B, g->H, g->W, (const float*)packed, x, p, ws, s);               // model.py:179-209
+                          }};
+  return net;
 }
 int check_bank_grid(const char* fn, const FnxGrid* g, int precision_mode) {
   return check_bank_call(fn, 2, g, true, precision_mode, nullptr, 0);
@@ -107,14 +110,7 @@ int fnx_fluidnet_bank_forward(const FnxGrid* g, const void* packed, const float*
                               int precision_mode, void* ws, size_t ws_bytes, void* stream) {
   if (int rc = fnx::check_bank_call(__func__, 2, g, packed && input && p_out && U_out && ws, precision_mode, fnx::bank_whole_ws, ws_bytes))
     return rc;
-  const size_t cells = (size_t)g->H * g->W;
-  float* flags = (float*)ws;
-  const fnx::FluidnetWs w = fnx::fluidnet_ws_layout(g->B, cells, fnx::bank_net_ws(g), (char*)ws + fnx::fluidnet_flags_bytes(g->B, cells));
-  fnx::fluidnet_split(g, input, U_out, flags, stream);
-  if (int rc = fnx::fluidnet_pre(g, thr, U_out, flags, w.scale, w, stream)) return rc;
-  fnx::banknet_forward(g->B, g->H, g->W, (const float*)packed, w.x, p_out, w.net, (hipStream_t)stream);     // :179-209
-  if (int rc = fnx::fluidnet_post(g, p_out, U_out, flags, w.scale, stream)) return rc;
-  return fnx::bank_status();
+  return fnx::fluidnet_whole_forward(fnx::banknet_net(), g, packed, input, thr, p_out, U_out, precision_mode, ws, stream);
 }
 
 }  // extern "C"

@@ -195,6 +195,15 @@ size_t bank3d_whole_ws(const FnxGrid* g) { return fluidnet_whole_ws_bytes(g->B, 
 
 }  // namespace
 
+// the net as FluidNet.forward's wrapper runs it (fnx_fluidnet.h)
+const Net& banknet3d_net() {
+  static const Net net = {3, FNX_NET_BANK3D, bank_status, bank3d_net_ws,
+                          [](const FnxGrid* g, const void* packed, const float* x, float* p, int, void* ws, hipStream_t s) {
+                            bank3d_forward(g->B, g->D, g->H, g->W, (const float*)packed, x, p, ws, s);
+                          }};
+  return net;
+}
+
 void bank3d_forward_front(int B, int D, int H, int W, const float* pk, const float* x, float* a, float* h, float* a2, float* h2, float* b2,
                           float* a4, float* h4, float* b4, hipStream_t s) {
   bank3d_front(B, D, H, W, pk, x, Bank3dWs{a, h, a2, h2, b2, a4, h4, b4, 0}, s);
@@ -238,14 +247,7 @@ int fnx_fluidnet_bank3d_forward(const FnxGrid* g, const void* packed, const floa
                                 int precision_mode, void* ws, size_t ws_bytes, void* stream) {
   if (int rc = fnx::check_bank_call(__func__, 3, g, packed && input && p_out && U_out && ws, precision_mode, fnx::bank3d_whole_ws, ws_bytes))
     return rc;
-  const size_t cells = (size_t)g->D * g->H * g->W;
-  float* flags = (float*)ws;
-  const fnx::FluidnetWs w = fnx::fluidnet_ws_layout(g->B, cells, fnx::bank3d_net_ws(g), (char*)ws + fnx::fluidnet_flags_bytes(g->B, cells));
-  fnx::fluidnet_split(g, input, U_out, flags, stream);
-  if (int rc = fnx::fluidnet_pre(g, thr, U_out, flags, w.scale, w, stream)) return rc;
-  fnx::bank3d_forward(g->B, g->D, g->H, g->W, (const float*)packed, w.x, p_out, w.net, (hipStream_t)stream);
-  if (int rc = fnx::fluidnet_post(g, p_out, U_out, flags, w.scale, stream)) return rc;
-  return fnx::bank_status();
+  return fnx::fluidnet_whole_forward(fnx::banknet3d_net(), g, packed, input, thr, p_out, U_out, precision_mode, ws, stream);
 }
 
 }  // extern "C"

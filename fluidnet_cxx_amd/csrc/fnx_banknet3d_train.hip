@@ -45,7 +45,9 @@ __global__ __launch_bounds__(256, 2) void bank3d_tail_tape_kernel(const float* _
   bank3d_conv_body<EPI3_TAIL_TAPE>(wpk, bias, tail, in, d, h, w, tiles_y, chunk, nullptr, l2, l4, p, nullptr, tape);
 }
 
-void bank3d_forward_train(int B, int D, int H, int W, const float* pk, const float* x, float* p, float* tape, hipStream_t s) {
+void bank3d_forward_train(const FnxGrid* g, const void* packed, const float* x, float* p, float* tape, int /*mode*/, hipStream_t s) {
+  const int B = g->B, D = g->D, H = g->H, W = g->W;
+  const float* pk = (const float*)packed;
   const BankTapeLayout T = bank_tape_layout(3, B, D, H, W);
   auto at = [&](int n) { return tape + T.e[n].off; };
   ProfScope ps(FNX_PROF_CONV_MFMA16, s);
@@ -388,8 +390,10 @@ inline bool bank3d_bwd_range_ok(const FnxGrid* g) {
   return ((size_t)g->D * g->H * g->W + 63) / 64 * (size_t)g->B < ((size_t)1 << 31);
 }
 
-void bank3d_backward(int B, int D, int H, int W, const float* pt, const float* x, const float* grad_p, const float* tape, float* grad_blob,
-                     void* ws, hipStream_t s) {
+bool bank3d_backward(const FnxGrid* g, const void* packed_t, const float* x, const float* grad_p, const float* tape, float* grad_blob,
+                     int /*mode*/, void* ws, hipStream_t s) {
+  const int B = g->B, D = g->D, H = g->H, W = g->W;
+  const float* pt = (const float*)packed_t;
   const BankTapeLayout T = bank_tape_layout(3, B, D, H, W);
   const Bank3dBwdPlan p = bank3d_bwd_plan(B, D, H, W, ws);
   auto at = [&](int n) { return tape + T.e[n].off; };
@@ -418,12 +422,16 @@ void bank3d_backward(int B, int D, int H, int W, const float* pt, const float* x
   P.tail = p.ptail; P.c1 = p.pc1;
   for (int l = 0; l < 3; ++l) { P.w2[l] = p.pw2[l]; P.w0[l] = p.pw0[l]; }
   bank3d_reduce_kernel<<<(B3_FLOATS + 255) / 256, 256, 0, s>>>(P, grad_blob, p.ns);
+  return true;
 }
 
-size_t bank3d_bwd_plan_bytes(int B, int D, int H, int W) { return bank3d_bwd_plan(B, D, H, W, nullptr).bytes; }
+size_t bank3d_bwd_plan_bytes(const FnxGrid* g) { return bank3d_bwd_plan(g->B, g->D, g->H, g->W, nullptr).bytes; }
 
 bool bank3d_sized(const FnxGrid* g) { return g && g->is3D && g->B >= 1 && g->D >= 4 && g->H >= 4 && g->W >= 4; }
-constexpr BankTrainDim DIM3 = {3, bank3d_sized, bank3d_bwd_range_ok, bank3d_forward_train, bank3d_backward, bank3d_bwd_plan_bytes};
+// the net's record (fnx_fluidnet.h): its input is kept in the tape, the backward's conv1 reads it again
+size_t bank3d_tape_x(const FnxGrid* g) { return bank_tape_layout(3, g->B, g->D, g->H, g->W).e[TP_X].off; }
+constexpr NetTrain NET3 = {3, bank_status, bank3d_forward_train, bank3d_backward, bank3d_bwd_plan_bytes, bank3d_tape_x};
+constexpr BankTrainDim DIM3 = {NET3, bank3d_sized, bank3d_bwd_range_ok};
 
 }  // namespace
 }  // namespace fnx
@@ -448,7 +456,7 @@ int fnx_banknet3d_pack_t(const float* weights_blob, void* packed_t, void* stream
   return fnx::bank_status();
 }
 
-size_t fnx_banknet3d_backward_ws_bytes(const FnxGrid* g) { return fnx::bank_size_query<fnx::DIM3>(g, fnx::bank_bwd_ws_bytes<fnx::DIM3>); }
+size_t fnx_banknet3d_backward_ws_bytes(const FnxGrid* g) { return fnx::bank_size_query<fnx::DIM3>(g, fnx::bank_bwd_ws<fnx::DIM3>); }
 
 int fnx_banknet3d_backward_launches(void) { return 8; }
 
@@ -484,20 +492,20 @@ int fnx_banknet3d_backward(const FnxGrid* g, const void* packed_t, const float* 
   return fnx::bank_backward<fnx::DIM3>(__func__, g, packed_t, x, grad_p, tape, grad_blob, precision_mode, ws, ws_bytes, stream);
 }
 
-size_t fnx_fluidnet_bank3d_train_ws_bytes(const FnxGrid* g) { return fnx::bank_size_query<fnx::DIM3>(g, fnx::bank_train_ws_bytes<fnx::DIM3>); }
+size_t fnx_fluidnet_bank3d_train_ws_bytes(const FnxGrid* g) { return fnx::bank_size_query<fnx::DIM3>(g, fnx::bank_train_ws<fnx::DIM3>); }
 
 int fnx_fluidnet_bank3d_forward_train(const FnxGrid* g, const void* packed, const float* input, float normalize_threshold, float* p_out,
                                       float* U_out, float* flags_out, float* scale_out, float* tape, int precision_mode, void* ws,
                                       size_t ws_bytes, void* stream) {
-  return fnx::fluidnet_bank_forward_train<fnx::DIM3>(__func__, g, packed, input, normalize_threshold, p_out, U_out, flags_out, scale_out, tape,
-                                                     precision_mode, ws, ws_bytes, stream);
+  return fnx::bank_whole_forward_train<fnx::DIM3>(__func__, g, packed, input, normalize_threshold, p_out, U_out, flags_out, scale_out, tape,
+                                                  precision_mode, ws, ws_bytes, stream);
 }
 
 int fnx_fluidnet_bank3d_backward(const FnxGrid* g, const void* packed_t, const float* flags, const float* scale, const float* grad_p,
                                  const float* grad_U, const float* tape, float* grad_blob, int precision_mode, void* ws, size_t ws_bytes,
                                  void* stream) {
-  return fnx::fluidnet_bank_backward<fnx::DIM3>(__func__, g, packed_t, flags, scale, grad_p, grad_U, tape, grad_blob, precision_mode, ws,
-                                                ws_bytes, stream);
+  return fnx::bank_whole_backward<fnx::DIM3>(__func__, g, packed_t, flags, scale, grad_p, grad_U, tape, grad_blob, precision_mode, ws, ws_bytes,
+                                             stream);
 }
 
 }  // extern "C"

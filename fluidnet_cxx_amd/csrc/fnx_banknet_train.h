@@ -1,6 +1,6 @@
 // What the two training units of the 16-channel bank net share (fnx_banknet_train.hip: 2D; fnx_banknet3d_train.hip: 3D): the tape's
 // layout, the arithmetic of packed_t, the tail's partial sums and their place in the gradient blob, the launcher of the one tail
-// backward kernel, and the bodies of the training entry points over a per-dimension record.  The forward and backward launchers, the
+// backward kernel, and the checks of the training entry points over the net's record.  The forward and backward launchers, the
 // level parts of the launch plans and every kernel but the tail's differ by algorithm and stay in their units.
 #pragma once
 #include "fnx_banknet3d_tile.h"
@@ -110,35 +110,24 @@ __device__ __forceinline__ int bank_tail_partial_at(int q2) {
   return at;
 }
 
-// ---- the training entry points: one body each, over what a dimension's unit brings ----
+// ---- the training entry points: one body each, over the net's record (fnx_fluidnet.h's NetTrain) and the grids its unit answers for ----
 struct BankTrainDim {
-  int ndim;
+  const NetTrain& net;
   bool (*sized)(const FnxGrid*);           // the grids the size queries answer for (not null, the dimension's kind, at least 4 cells an axis)
   bool (*range_ok)(const FnxGrid*);        // the backward's own launch range behind check_bank_call's; nullptr: that one is all
-  void (*forward)(int B, int D, int H, int W, const float* pk, const float* x, float* p, float* tape, hipStream_t s);
-  void (*backward)(int B, int D, int H, int W, const float* pt, const float* x, const float* grad_p, const float* tape, float* grad_blob,
-                   void* ws, hipStream_t s);
-  size_t (*plan_bytes)(int B, int D, int H, int W);      // the backward's workspace
 };
 
+// check_bank_call's want_of is a plain function: the backward's workspace, and the one size of the whole training forward and backward
 template <const BankTrainDim& DIM>
-size_t bank_bwd_ws_bytes(const FnxGrid* g) { return DIM.plan_bytes(g->B, g->D, g->H, g->W); }
-// FluidNet.forward for training with the bank net in the middle: one workspace size for the forward and the backward
+size_t bank_bwd_ws(const FnxGrid* g) { return DIM.net.backward_ws_bytes(g); }
 template <const BankTrainDim& DIM>
-size_t bank_train_ws_bytes(const FnxGrid* g) {
-  const size_t fwd = fluidnet_ws_layout(g->B, (size_t)g->D * g->H * g->W, 0, nullptr).head;
-  const size_t bwd = fluidnet_train_bwd_ws(DIM.ndim, g, nullptr).bytes + bank_bwd_ws_bytes<DIM>(g);
-  return fwd > bwd ? fwd : bwd;
-}
+size_t bank_train_ws(const FnxGrid* g) { return fluidnet_train_ws_bytes(DIM.net, g); }
 // a size query: 0 for a grid outside `sized` or the backward's range
 template <const BankTrainDim& DIM>
 size_t bank_size_query(const FnxGrid* g, size_t (*bytes_of)(const FnxGrid*)) {
   if (!DIM.sized(g) || (DIM.range_ok && !DIM.range_ok(g))) return 0;
   return bytes_of(g);
 }
-// the net's input inside the tape
-template <const BankTrainDim& DIM>
-size_t bank_tape_x(const FnxGrid* g) { return bank_tape_layout(DIM.ndim, g->B, g->D, g->H, g->W).e[TP_X].off; }
 
 // check_bank_call and, behind it, the backward's own range
 template <const BankTrainDim& DIM>
@@ -146,55 +135,47 @@ int check_bank_bwd_call(const char* fn, const FnxGrid* g, bool args, int precisi
   if (DIM.range_ok && args && DIM.sized(g) && !DIM.range_ok(g))
     return set_error(FNX_EINVAL, "%s: B * D * H * W = %d * %zu cells is beyond the bank backward's launch range", fn, g->B,
                      (size_t)g->D * g->H * g->W);
-  return check_bank_call(fn, DIM.ndim, g, args, precision_mode, want_of, ws_bytes);
+  return check_bank_call(fn, DIM.net.ndim, g, args, precision_mode, want_of, ws_bytes);
 }
 
 template <const BankTrainDim& DIM>
 int bank_forward_train(const char* fn, const FnxGrid* g, const void* packed, const float* x, float* p, float* tape, int precision_mode,
                        void* stream) {
-  if (int rc = check_bank_call(fn, DIM.ndim, g, packed && x && p && tape, precision_mode, nullptr, 0)) return rc;
-  DIM.forward(g->B, g->D, g->H, g->W, (const float*)packed, x, p, tape, (hipStream_t)stream);
+  if (int rc = check_bank_call(fn, DIM.net.ndim, g, packed && x && p && tape, precision_mode, nullptr, 0)) return rc;
+  DIM.net.forward(g, packed, x, p, tape, precision_mode, (hipStream_t)stream);
   return bank_status();
 }
 
 template <const BankTrainDim& DIM>
 int bank_backward(const char* fn, const FnxGrid* g, const void* packed_t, const float* x, const float* grad_p, const float* tape,
                   float* grad_blob, int precision_mode, void* ws, size_t ws_bytes, void* stream) {
-  if (int rc = check_bank_bwd_call<DIM>(fn, g, packed_t && x && grad_p && tape && grad_blob && ws, precision_mode, bank_bwd_ws_bytes<DIM>,
-                                        ws_bytes))
+  if (int rc = check_bank_bwd_call<DIM>(fn, g, packed_t && x && grad_p && tape && grad_blob && ws, precision_mode, bank_bwd_ws<DIM>, ws_bytes))
     return rc;
-  DIM.backward(g->B, g->D, g->H, g->W, (const float*)packed_t, x, grad_p, tape, grad_blob, ws, (hipStream_t)stream);
+  DIM.net.backward(g, packed_t, x, grad_p, tape, grad_blob, precision_mode, ws, (hipStream_t)stream);
   return bank_status();
 }
 
+// FluidNet.forward for training with the bank net in the middle: the checks, then fnx_fluidnet.hip's bodies
 template <const BankTrainDim& DIM>
-int fluidnet_bank_forward_train(const char* fn, const FnxGrid* g, const void* packed, const float* input, float normalize_threshold,
-                                float* p_out, float* U_out, float* flags_out, float* scale_out, float* tape, int precision_mode, void* ws,
-                                size_t ws_bytes, void* stream) {
+int bank_whole_forward_train(const char* fn, const FnxGrid* g, const void* packed, const float* input, float normalize_threshold,
+                             float* p_out, float* U_out, float* flags_out, float* scale_out, float* tape, int precision_mode, void* ws,
+                             size_t ws_bytes, void* stream) {
   if (int rc = check_bank_bwd_call<DIM>(fn, g, packed && input && p_out && U_out && flags_out && scale_out && tape && ws, precision_mode,
-                                        bank_train_ws_bytes<DIM>, ws_bytes))
+                                        bank_train_ws<DIM>, ws_bytes))
     return rc;
-  FluidnetWs w = fluidnet_ws_layout(g->B, (size_t)g->D * g->H * g->W, 0, ws);      // (its head: the scales go to scale_out)
-  w.x = tape + bank_tape_x<DIM>(g);                                                // the backward reads the net's input again (conv1)
-  fluidnet_split(g, input, U_out, flags_out, stream);
-  if (int rc = fluidnet_pre(g, normalize_threshold, U_out, flags_out, scale_out, w, stream)) return rc;
-  DIM.forward(g->B, g->D, g->H, g->W, (const float*)packed, w.x, p_out, tape, (hipStream_t)stream);
-  if (int rc = fluidnet_post(g, p_out, U_out, flags_out, scale_out, stream)) return rc;
-  return bank_status();
+  return fluidnet_forward_train(DIM.net, g, packed, input, normalize_threshold, p_out, U_out, flags_out, scale_out, tape, precision_mode, ws,
+                                stream);
 }
 
 template <const BankTrainDim& DIM>
-int fluidnet_bank_backward(const char* fn, const FnxGrid* g, const void* packed_t, const float* flags, const float* scale,
-                           const float* grad_p, const float* grad_U, const float* tape, float* grad_blob, int precision_mode, void* ws,
-                           size_t ws_bytes, void* stream) {
+int bank_whole_backward(const char* fn, const FnxGrid* g, const void* packed_t, const float* flags, const float* scale, const float* grad_p,
+                        const float* grad_U, const float* tape, float* grad_blob, int precision_mode, void* ws, size_t ws_bytes,
+                        void* stream) {
   if (int rc = check_bank_bwd_call<DIM>(fn, g, packed_t && flags && scale && grad_p && grad_U && tape && grad_blob && ws, precision_mode,
-                                        bank_train_ws_bytes<DIM>, ws_bytes))
+                                        bank_train_ws<DIM>, ws_bytes))
     return rc;
-  const FluidnetTrainBwdWs w = fluidnet_train_bwd_ws(DIM.ndim, g, ws);
-  if (int rc = fluidnet_train_gnet(DIM.ndim, g, flags, scale, grad_p, grad_U, w, stream)) return rc;
-  DIM.backward(g->B, g->D, g->H, g->W, (const float*)packed_t, tape + bank_tape_x<DIM>(g), w.gnet, tape, grad_blob, w.net,
-               (hipStream_t)stream);
-  return bank_status();
+  bool launched;
+  return fluidnet_backward(DIM.net, g, packed_t, flags, scale, grad_p, grad_U, tape, grad_blob, precision_mode, ws, stream, &launched);
 }
 
 }  // namespace

@@ -45,7 +45,9 @@ __global__ __launch_bounds__(256) void banknet_level_tape_kernel(const float* __
   bank_level_tile<R, TH, TW, true>(pk, x, H, W, out, l2, l4, p, tape);
 }
 
-void banknet_forward_train(int B, int /*D = 1*/, int H, int W, const float* pk, const float* x, float* p, float* tape, hipStream_t s) {
+void banknet_forward_train(const FnxGrid* g, const void* packed, const float* x, float* p, float* tape, int /*mode*/, hipStream_t s) {
+  const int B = g->B, H = g->H, W = g->W;
+  const float* pk = (const float*)packed;
   const BankTapeLayout T = bank_tape_layout(2, B, 1, H, W);
   auto at = [&](int n) { return tape + T.e[n].off; };
   ProfScope ps(FNX_PROF_CONV_MFMA16, s);
@@ -427,10 +429,12 @@ BankBwdPlan bank_bwd_plan(int B, int H, int W, void* base) {
   p.bytes = off;
   return p;
 }
-size_t bank_bwd_plan_bytes(int B, int /*D = 1*/, int H, int W) { return bank_bwd_plan(B, H, W, nullptr).bytes; }
+size_t bank_bwd_plan_bytes(const FnxGrid* g) { return bank_bwd_plan(g->B, g->H, g->W, nullptr).bytes; }
 
-void banknet_backward(int B, int /*D = 1*/, int H, int W, const float* pt, const float* x, const float* grad_p, const float* tape,
-                      float* grad_blob, void* ws, hipStream_t s) {
+bool banknet_backward(const FnxGrid* g, const void* packed_t, const float* x, const float* grad_p, const float* tape, float* grad_blob,
+                      int /*mode*/, void* ws, hipStream_t s) {
+  const int B = g->B, H = g->H, W = g->W;
+  const float* pt = (const float*)packed_t;
   const BankTapeLayout T = bank_tape_layout(2, B, 1, H, W);
   const BankBwdPlan p = bank_bwd_plan(B, H, W, ws);
   auto at = [&](int n) { return tape + T.e[n].off; };
@@ -444,10 +448,14 @@ void banknet_backward(int B, int /*D = 1*/, int H, int W, const float* pt, const
                                                                         p.ntx[2], p.nty[2], p.ntiles[2]);
   bank_conv1_bwd_kernel<<<p.ns.c1, 256, 0, s>>>(x, at(TP_A), p.ga1, p.ga2, p.ga4, p.pc1, H, W, p.u.ups, p.u.nunits);
   bank_reduce_kernel<<<(BLOB_FLOATS + 255) / 256, 256, 0, s>>>(p.ptail, p.plev[0], p.plev[1], p.plev[2], p.pc1, grad_blob, p.ns);
+  return true;
 }
 
 bool bank2d_sized(const FnxGrid* g) { return g && !g->is3D && g->D == 1 && g->B >= 1 && g->H >= 4 && g->W >= 4; }
-constexpr BankTrainDim DIM2 = {2, bank2d_sized, nullptr, banknet_forward_train, banknet_backward, bank_bwd_plan_bytes};
+// the net's record (fnx_fluidnet.h): its input is kept in the tape, the backward's conv1 reads it again
+size_t bank_tape_x(const FnxGrid* g) { return bank_tape_layout(2, g->B, 1, g->H, g->W).e[TP_X].off; }
+constexpr NetTrain NET2 = {2, bank_status, banknet_forward_train, banknet_backward, bank_bwd_plan_bytes, bank_tape_x};
+constexpr BankTrainDim DIM2 = {NET2, bank2d_sized, nullptr};
 
 }  // namespace
 
@@ -482,7 +490,7 @@ int fnx_banknet_pack_t(const float* weights_blob, void* packed_t, void* stream) 
   return fnx::bank_status();
 }
 
-size_t fnx_banknet_backward_ws_bytes(const FnxGrid* g) { return fnx::bank_size_query<fnx::DIM2>(g, fnx::bank_bwd_ws_bytes<fnx::DIM2>); }
+size_t fnx_banknet_backward_ws_bytes(const FnxGrid* g) { return fnx::bank_size_query<fnx::DIM2>(g, fnx::bank_bwd_ws<fnx::DIM2>); }
 
 int fnx_banknet_forward_train(const FnxGrid* g, const void* packed, const float* x, float* p, float* tape, int precision_mode, void* stream) {
   return fnx::bank_forward_train<fnx::DIM2>(__func__, g, packed, x, p, tape, precision_mode, stream);
@@ -493,20 +501,20 @@ int fnx_banknet_backward(const FnxGrid* g, const void* packed_t, const float* x,
   return fnx::bank_backward<fnx::DIM2>(__func__, g, packed_t, x, grad_p, tape, grad_blob, precision_mode, ws, ws_bytes, stream);
 }
 
-size_t fnx_fluidnet_bank_train_ws_bytes(const FnxGrid* g) { return fnx::bank_size_query<fnx::DIM2>(g, fnx::bank_train_ws_bytes<fnx::DIM2>); }
+size_t fnx_fluidnet_bank_train_ws_bytes(const FnxGrid* g) { return fnx::bank_size_query<fnx::DIM2>(g, fnx::bank_train_ws<fnx::DIM2>); }
 
 int fnx_fluidnet_bank_forward_train(const FnxGrid* g, const void* packed, const float* input, float normalize_threshold, float* p_out,
                                     float* U_out, float* flags_out, float* scale_out, float* tape, int precision_mode, void* ws,
                                     size_t ws_bytes, void* stream) {
-  return fnx::fluidnet_bank_forward_train<fnx::DIM2>(__func__, g, packed, input, normalize_threshold, p_out, U_out, flags_out, scale_out, tape,
-                                                     precision_mode, ws, ws_bytes, stream);
+  return fnx::bank_whole_forward_train<fnx::DIM2>(__func__, g, packed, input, normalize_threshold, p_out, U_out, flags_out, scale_out, tape,
+                                                  precision_mode, ws, ws_bytes, stream);
 }
 
 int fnx_fluidnet_bank_backward(const FnxGrid* g, const void* packed_t, const float* flags, const float* scale,
                                const float* grad_p, const float* grad_U, const float* tape, float* grad_blob, int precision_mode, void* ws,
                                size_t ws_bytes, void* stream) {
-  return fnx::fluidnet_bank_backward<fnx::DIM2>(__func__, g, packed_t, flags, scale, grad_p, grad_U, tape, grad_blob, precision_mode, ws,
-                                                ws_bytes, stream);
+  return fnx::bank_whole_backward<fnx::DIM2>(__func__, g, packed_t, flags, scale, grad_p, grad_U, tape, grad_blob, precision_mode, ws, ws_bytes,
+                                             stream);
 }
 
 }  // extern "C"

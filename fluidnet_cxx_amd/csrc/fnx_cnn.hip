@@ -816,6 +816,18 @@ int check_net_call(const char* fn, const FnxGrid* g, bool args, int precision_mo
     return set_error(FNX_EWORKSPACE, "%s: workspace of %zu bytes is too small", fn, ws_bytes);
   return FNX_OK;
 }
+
+// the ScaleNet as FluidNet.forward's wrapper runs it (fnx_fluidnet.h): a grid's dims carry its z-slab view
+static GridDims dims_of(const FnxGrid* g) { return make_dims(g->B, g->D, g->H, g->W, g->z_offset, g->D_global); }
+static size_t scalenet_ws(const FnxGrid* g) { return multiscale_ws_bytes(dims_of(g), g->is3D); }
+static void scalenet_forward(const FnxGrid* g, const void* packed, const float* x, float* p, int mode, void* ws, hipStream_t s) {
+  multiscale_forward(dims_of(g), g->is3D, packed, x, p, mode, ws, s);
+}
+const Net& scalenet_net(bool is3d) {
+  static const Net nets[2] = {{2, FNX_NET_SCALENET, [] { return launch_status(false); }, scalenet_ws, scalenet_forward},
+                              {3, FNX_NET_SCALENET, [] { return launch_status(true); }, scalenet_ws, scalenet_forward}};
+  return nets[is3d];
+}
 }  // namespace fnx
 
 // ---------------------------------------------------------------------------------------------------

@@ -680,47 +680,43 @@ int backward_call(const char* fn, bool is3d, const FnxGrid* g, const void* packe
   return train_status(is3d);
 }
 
-// nc: the velocity components, 2 or 3 (g is checked).
-// forward: div, x (2), std partials; backward: the wall-masked scaled grad_U (nc), grad_U of the update (nc), its grad_p, g_net
-size_t fluidnet_train_ws(int nc, const FnxGrid* g) {
-  const size_t fwd = fnx::fluidnet_ws_layout(g->B, (size_t)g->D * g->H * g->W, 0, nullptr).head;
-  const size_t bwd = fnx::fluidnet_train_bwd_ws(nc, g, nullptr).bytes + fnx::multiscale_backward_ws_bytes(nc == 3, g->B, g->D, g->H, g->W);
-  return fwd > bwd ? fwd : bwd;
+// The two ScaleNets' records for FluidNet.forward's wrapper (fnx_fluidnet.h): x is rebuilt from the tape, so none is kept or read
+template <bool IS3D>
+constexpr fnx::NetTrain scalenet_train() {
+  return {IS3D ? 3 : 2, [] { return train_status(IS3D); },
+          [](const FnxGrid* g, const void* packed, const float* x, float* p, float* tape, int mode, hipStream_t s) {
+            fnx::multiscale_forward_train(IS3D, g->B, g->D, g->H, g->W, packed, x, p, tape, mode, s);
+          },
+          [](const FnxGrid* g, const void* packed_t, const float*, const float* grad_p, const float* tape, float* grad_blob, int mode, void* ws,
+             hipStream_t s) { return fnx::multiscale_backward(IS3D, g->B, g->D, g->H, g->W, packed_t, grad_p, tape, grad_blob, mode, ws, s); },
+          [](const FnxGrid* g) { return fnx::multiscale_backward_ws_bytes(IS3D, g->B, g->D, g->H, g->W); }, nullptr};
 }
+constexpr fnx::NetTrain NET_TRAIN[2] = {scalenet_train<false>(), scalenet_train<true>()};
 
-int fluidnet_forward_train_call(const char* fn, int nc, const FnxGrid* g, const void* packed, size_t packed_bytes, const float* input,
-                                float normalize_threshold, float* p_out, float* U_out, float* flags_out, float* scale_out, float* tape,
-                                int precision_mode, void* ws, size_t ws_bytes, void* stream) {
-  const bool is3d = nc == 3;
+// FluidNet.forward for training around the ScaleNet: this family's checks, then fnx_fluidnet.hip's bodies
+int whole_forward_train_call(const char* fn, bool is3d, const FnxGrid* g, const void* packed, size_t packed_bytes, const float* input,
+                             float normalize_threshold, float* p_out, float* U_out, float* flags_out, float* scale_out, float* tape,
+                             int precision_mode, void* ws, size_t ws_bytes, void* stream) {
   int mode;
   if (int rc = check_train_call(fn, is3d, g, packed && input && p_out && U_out && flags_out && scale_out && tape && ws, precision_mode, &mode))
     return rc;
   if (int rc = check_image(fn, is3d, packed_bytes, false)) return rc;
-  if (ws_bytes < fluidnet_train_ws(nc, g)) return too_small(fn, ws_bytes);
-  const fnx::FluidnetWs w = fnx::fluidnet_ws_layout(g->B, (size_t)g->D * g->H * g->W, 0, ws);      // (its head: the scales go to scale_out)
-  // fnx_fluidnet_forward's stages (model.py:104-227) around the taped net
-  fnx::fluidnet_split(g, input, U_out, flags_out, stream);
-  if (int rc = fnx::fluidnet_pre(g, normalize_threshold, U_out, flags_out, scale_out, w, stream)) return rc;
-  fnx::multiscale_forward_train(is3d, g->B, g->D, g->H, g->W, packed, w.x, p_out, tape, mode, (hipStream_t)stream);
-  if (int rc = fnx::fluidnet_post(g, p_out, U_out, flags_out, scale_out, stream)) return rc;
-  return train_status(is3d);
+  if (ws_bytes < fnx::fluidnet_train_ws_bytes(NET_TRAIN[is3d], g)) return too_small(fn, ws_bytes);
+  return fnx::fluidnet_forward_train(NET_TRAIN[is3d], g, packed, input, normalize_threshold, p_out, U_out, flags_out, scale_out, tape, mode, ws,
+                                     stream);
 }
 
-int fluidnet_backward_call(const char* fn, int nc, const FnxGrid* g, const void* packed_t, size_t packed_t_bytes, const float* flags,
-                           const float* scale, const float* grad_p, const float* grad_U, const float* tape, float* grad_blob,
-                           int precision_mode, void* ws, size_t ws_bytes, void* stream) {
-  const bool is3d = nc == 3;
+int whole_backward_call(const char* fn, bool is3d, const FnxGrid* g, const void* packed_t, size_t packed_t_bytes, const float* flags,
+                        const float* scale, const float* grad_p, const float* grad_U, const float* tape, float* grad_blob, int precision_mode,
+                        void* ws, size_t ws_bytes, void* stream) {
   int mode;
   if (int rc = check_train_call(fn, is3d, g, packed_t && flags && scale && grad_p && grad_U && tape && grad_blob && ws, precision_mode, &mode))
     return rc;
   if (int rc = check_image(fn, is3d, packed_t_bytes, true)) return rc;
-  if (ws_bytes < fluidnet_train_ws(nc, g)) return too_small(fn, ws_bytes);
-  const fnx::FluidnetTrainBwdWs w = fnx::fluidnet_train_bwd_ws(nc, g, ws);
-  // g_net = s g_p + velocity_update_backward_p(s setWallBcs(g_U)): the adjoints of model.py:226, :221-223 and :213-218 in reverse
-  if (int rc = fnx::fluidnet_train_gnet(nc, g, flags, scale, grad_p, grad_U, w, stream)) return rc;
-  if (!fnx::multiscale_backward(is3d, g->B, g->D, g->H, g->W, packed_t, w.gnet, tape, grad_blob, mode, w.net, (hipStream_t)stream))
-    return not_launched(fn, is3d);
-  return train_status(is3d);
+  if (ws_bytes < fnx::fluidnet_train_ws_bytes(NET_TRAIN[is3d], g)) return too_small(fn, ws_bytes);
+  bool launched;
+  const int rc = fnx::fluidnet_backward(NET_TRAIN[is3d], g, packed_t, flags, scale, grad_p, grad_U, tape, grad_blob, mode, ws, stream, &launched);
+  return launched ? rc : not_launched(fn, is3d);
 }
 
 // the tape layout of a checked grid into one of the two ABI structs (FnxTapeEntry has no D); either may be null
@@ -814,33 +810,33 @@ int fnx_multiscale3d_backward_plain(const FnxGrid* g, const void* packed_t, size
   return backward_call(__func__, true, g, packed_t, packed_t_bytes, grad_p, tape, grad_blob, precision_mode, false, ws, ws_bytes, stream);
 }
 
-size_t fnx_fluidnet_train_ws_bytes(const FnxGrid* g) { return grid2d_ok(__func__, g) ? fluidnet_train_ws(2, g) : 0; }
-size_t fnx_fluidnet3d_train_ws_bytes(const FnxGrid* g) { return grid3d_ok(__func__, g) ? fluidnet_train_ws(3, g) : 0; }
+size_t fnx_fluidnet_train_ws_bytes(const FnxGrid* g) { return grid2d_ok(__func__, g) ? fnx::fluidnet_train_ws_bytes(NET_TRAIN[0], g) : 0; }
+size_t fnx_fluidnet3d_train_ws_bytes(const FnxGrid* g) { return grid3d_ok(__func__, g) ? fnx::fluidnet_train_ws_bytes(NET_TRAIN[1], g) : 0; }
 
 int fnx_fluidnet_forward_train(const FnxGrid* g, const void* packed, const float* input, float normalize_threshold, float* p_out,
                                float* U_out, float* flags_out, float* scale_out, float* tape, int precision_mode, void* ws, size_t ws_bytes,
                                void* stream) {
-  return fluidnet_forward_train_call(__func__, 2, g, packed, 0, input, normalize_threshold, p_out, U_out, flags_out, scale_out, tape,
-                                     precision_mode, ws, ws_bytes, stream);
+  return whole_forward_train_call(__func__, false, g, packed, 0, input, normalize_threshold, p_out, U_out, flags_out, scale_out, tape,
+                                  precision_mode, ws, ws_bytes, stream);
 }
 int fnx_fluidnet3d_forward_train(const FnxGrid* g, const void* packed, size_t packed_bytes, const float* input, float normalize_threshold,
                                  float* p_out, float* U_out, float* flags_out, float* scale_out, float* tape, int precision_mode, void* ws,
                                  size_t ws_bytes, void* stream) {
-  return fluidnet_forward_train_call(__func__, 3, g, packed, packed_bytes, input, normalize_threshold, p_out, U_out, flags_out, scale_out,
-                                     tape, precision_mode, ws, ws_bytes, stream);
+  return whole_forward_train_call(__func__, true, g, packed, packed_bytes, input, normalize_threshold, p_out, U_out, flags_out, scale_out,
+                                  tape, precision_mode, ws, ws_bytes, stream);
 }
 
 int fnx_fluidnet_backward(const FnxGrid* g, const void* packed_t, const float* flags, const float* scale, const float* grad_p,
                           const float* grad_U, const float* tape, float* grad_blob, int precision_mode, void* ws, size_t ws_bytes,
                           void* stream) {
-  return fluidnet_backward_call(__func__, 2, g, packed_t, 0, flags, scale, grad_p, grad_U, tape, grad_blob, precision_mode, ws, ws_bytes,
-                                stream);
+  return whole_backward_call(__func__, false, g, packed_t, 0, flags, scale, grad_p, grad_U, tape, grad_blob, precision_mode, ws, ws_bytes,
+                             stream);
 }
 int fnx_fluidnet3d_backward(const FnxGrid* g, const void* packed_t, size_t packed_t_bytes, const float* flags, const float* scale,
                             const float* grad_p, const float* grad_U, const float* tape, float* grad_blob, int precision_mode, void* ws,
                             size_t ws_bytes, void* stream) {
-  return fluidnet_backward_call(__func__, 3, g, packed_t, packed_t_bytes, flags, scale, grad_p, grad_U, tape, grad_blob, precision_mode, ws,
-                                ws_bytes, stream);
+  return whole_backward_call(__func__, true, g, packed_t, packed_t_bytes, flags, scale, grad_p, grad_U, tape, grad_blob, precision_mode, ws,
+                             ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -54,11 +54,44 @@ struct FluidnetTrainBwdWs { float *gU, *gU_in, *gp, *gnet; void* net; size_t byt
 FluidnetTrainBwdWs fluidnet_train_bwd_ws(int nc, const FnxGrid* g, void* base);
 int fluidnet_train_gnet(int nc, const FnxGrid* g, const float* flags, const float* scale, const float* grad_p, const float* grad_U,
                         const FluidnetTrainBwdWs& w, void* stream);
-// The net in the middle, by its kind (FNX_NET_SCALENET or FNX_NET_BANK, the 2D bank net; FNX_NET_BANK3D is not built into the step):
-// `packed` is the image of that kind.  The bank unit exports its net for it (fnx_banknet.hip): the workspace of the net alone, its
-// launches, and check_bank_call's refusals of a grid or a precision mode under the caller's name (no argument or workspace check).
-size_t bank_net_ws_bytes(const FnxGrid* g);
-void bank_net_forward(const FnxGrid* g, const void* packed, const float* x, float* p, void* ws, hipStream_t s);
+// The net in the middle, x (B,2,..) -> p (B,1,..), as the wrapper sees it.  Each unit defines its net's records next to its launchers:
+// fnx_cnn.hip / fnx_cnn_train.hip the two ScaleNets, the four bank units theirs.  mode: net_mode's value (the bank nets have one
+// arithmetic and ignore it).  status: the unit's wording of a HIP error after its launches.
+struct Net {
+  int ndim, kind;                                            // 2 or 3; FNX_NET_*
+  int (*status)();
+  size_t (*ws_bytes)(const FnxGrid* g);                      // the workspace of the net alone
+  void (*forward)(const FnxGrid* g, const void* packed, const float* x, float* p, int mode, void* ws, hipStream_t s);
+};
+const Net& scalenet_net(bool is3d);   // fnx_cnn.hip
+const Net& banknet_net();             // fnx_banknet.hip
+const Net& banknet3d_net();           // fnx_banknet3d.hip
+// kind: FNX_NET_SCALENET (either dimension), FNX_NET_BANK (2D) or FNX_NET_BANK3D (3D), as the caller has checked it
+const Net& net_of(int kind, bool is3d);
+// The net for training: the forward that keeps every layer's input in `tape`, the backward (false: a convolution was not launched, which
+// the caller refuses; x: the net's input, for a net that reads it again) and the backward's workspace.  tape_x: the float offset inside
+// the tape at which the net wants its input kept by the whole forward; nullptr: it does not.
+struct NetTrain {
+  int ndim;
+  int (*status)();
+  void (*forward)(const FnxGrid* g, const void* packed, const float* x, float* p, float* tape, int mode, hipStream_t s);
+  bool (*backward)(const FnxGrid* g, const void* packed_t, const float* x, const float* grad_p, const float* tape, float* grad_blob, int mode,
+                   void* ws, hipStream_t s);
+  size_t (*backward_ws_bytes)(const FnxGrid* g);
+  size_t (*tape_x)(const FnxGrid* g);
+};
+// FluidNet.forward around a net, everything behind an entry point's checks.  ws: fluidnet_whole_ws_bytes with the net's own (whole
+// forward); fluidnet_train_ws_bytes, one size for the training forward and the backward.  fluidnet_backward: *launched = false where the
+// net's backward was not launched (nothing is reported then: the entry point words the refusal).
+int fluidnet_whole_forward(const Net& n, const FnxGrid* g, const void* packed, const float* input, float thr, float* p_out, float* U_out,
+                           int mode, void* ws, void* stream);
+size_t fluidnet_train_ws_bytes(const NetTrain& n, const FnxGrid* g);
+int fluidnet_forward_train(const NetTrain& n, const FnxGrid* g, const void* packed, const float* input, float thr, float* p_out, float* U_out,
+                           float* flags_out, float* scale_out, float* tape, int mode, void* ws, void* stream);
+int fluidnet_backward(const NetTrain& n, const FnxGrid* g, const void* packed_t, const float* flags, const float* scale, const float* grad_p,
+                      const float* grad_U, const float* tape, float* grad_blob, int mode, void* ws, void* stream, bool* launched);
+// the bank net's refusals of a grid or a precision mode under the caller's name, for the step (check_bank_call without an argument or
+// workspace check; fnx_banknet.hip)
 int check_bank_grid(const char* fn, const FnxGrid* g, int precision_mode);
 // what fluidnet_core and fluidnet_pressure take at `ws` for a net of this kind: fluidnet_ws_layout with the net's own workspace
 size_t fluidnet_core_ws_bytes(const FnxGrid* g, int net_kind);

@@ -1,7 +1,8 @@
 // FluidNet.forward (lib/model.py:76-227) around a pressure net for gfx950: the channel split, the _ScaleNet std, the net's input, the net
-// by its kind (the MultiScale net of fnx_cnn.hip or the bank net of fnx_banknet.hip), velocityUpdate and the un-normalisation -- as the
-// whole forward (fnx_fluidnet_forward), as the projection of the native step (fluidnet_core, fluidnet_pressure) and, on a z-slab, as the
-// per-rank sums of the std over the whole domain.  All three nets, both trainers, the step and the slab driver call it.
+// by its record (fnx_fluidnet.h: the MultiScale net of fnx_cnn.hip or a bank net of fnx_banknet*.hip), velocityUpdate and the
+// un-normalisation -- as the whole forward of every net (fluidnet_whole_forward), as the training forward and backward around a taped net,
+// as the projection of the native step (fluidnet_core, fluidnet_pressure) and, on a z-slab, as the per-rank sums of the std over the whole
+// domain.  All four nets, their trainers, the step and the slab driver call it.
 // Built like fnx_cnn.hip (tolerance-checked, may contract a * b + c: the fp64 sums of squares of the std kernels do).
 #include "fnx_fluidnet.h"
 #include "fnx_cnn.h"
@@ -254,8 +255,6 @@ int net_mode(int precision_mode) {
   return precision_mode == FNX_PRECISION_FP32_F4 ? FNX_PRECISION_FP32 : precision_mode;
 }
 
-// FluidNet.forward after the channel split (model.py:120-227), U in place: U holds UDiv on entry and the
-// projected velocity on exit.  ws needs fluidnet_ws_bytes() minus the flags copy.
 void fluidnet_split(const FnxGrid* g, const float* input, float* U, float* flags, void* stream) {
   launch_gather_input(make_dims(g->B, g->D, g->H, g->W), g->is3D ? 3 : 2, input, U, flags, (hipStream_t)stream);   // model.py:104-119
 }
@@ -274,45 +273,53 @@ int fluidnet_post(const FnxGrid* g, float* p, float* U, const float* flags, cons
   return fnx_set_wall_bcs(g, U, flags, stream);                                  // model.py:226
 }
 
-// the workspace of the net alone, and its launches: x (B,2,..) -> p (B,1,..)
-static size_t net_ws_bytes(const FnxGrid* g, const GridDims& d, int net_kind) {
-  return net_kind == FNX_NET_BANK ? bank_net_ws_bytes(g) : multiscale_ws_bytes(d, g->is3D);
-}
-static void net_forward(const FnxGrid* g, const GridDims& d, const void* packed, int net_kind, const float* x, float* p, int precision_mode,
-                        void* ws, hipStream_t s) {
-  if (net_kind == FNX_NET_BANK) bank_net_forward(g, packed, x, p, ws, s);                    // model.py:179-209
-  else multiscale_forward(d, g->is3D, packed, x, p, precision_mode, ws, s);                  // model.py:174-175
+// the net by its kind and the grid's dimension (fnx_fluidnet.h)
+const Net& net_of(int kind, bool is3d) {
+  return kind == FNX_NET_BANK ? banknet_net() : (kind == FNX_NET_BANK3D ? banknet3d_net() : scalenet_net(is3d));
 }
 size_t fluidnet_core_ws_bytes(const FnxGrid* g, int net_kind) {
-  const GridDims d = make_dims(g->B, g->D, g->H, g->W, g->z_offset, g->D_global);
-  return fluidnet_ws_layout(d.B, d.DHW, net_ws_bytes(g, d, net_kind), nullptr).bytes;
+  return fluidnet_ws_layout(g->B, (size_t)g->D * g->H * g->W, net_of(net_kind, g->is3D).ws_bytes(g), nullptr).bytes;
+}
+
+// FluidNet.forward behind the channel split (model.py:120-227), U in place: U holds UDiv on entry and the projected velocity on exit.
+// ws: fluidnet_ws_layout with the net's own workspace.  The caller reports the launch status.
+static int fluidnet_around(const Net& n, const FnxGrid* g, const void* packed, const float* flags, float thr, int mode, float* p_out, float* U,
+                           void* ws, void* stream) {
+  const FluidnetWs w = fluidnet_ws_layout(g->B, (size_t)g->D * g->H * g->W, n.ws_bytes(g), ws);
+  if (int rc = fluidnet_pre(g, thr, U, flags, w.scale, w, stream)) return rc;
+  n.forward(g, packed, w.x, p_out, mode, w.net, (hipStream_t)stream);              // model.py:174-175 or :179-209
+  return fluidnet_post(g, p_out, U, flags, w.scale, stream);
+}
+
+int fluidnet_whole_forward(const Net& n, const FnxGrid* g, const void* packed, const float* input, float thr, float* p_out, float* U_out,
+                           int mode, void* ws, void* stream) {
+  float* flags = (float*)ws;                       // contiguous (B,1,..) copy of the flags channel
+  void* rest = (char*)ws + fluidnet_flags_bytes(g->B, (size_t)g->D * g->H * g->W);
+  fluidnet_split(g, input, U_out, flags, stream);
+  if (int rc = fluidnet_around(n, g, packed, flags, thr, mode, p_out, U_out, rest, stream)) return rc;
+  return n.status();
 }
 
 int fluidnet_core(const FnxGrid* g, const void* packed, int net_kind, const float* flags, float thr, int precision_mode, float* p_out,
                   float* U, void* ws, void* stream, const FnxState* bcs) {
-  const GridDims d = make_dims(g->B, g->D, g->H, g->W, g->z_offset, g->D_global);
-  hipStream_t s = (hipStream_t)stream;
-  const int nc = g->is3D ? 3 : 2;
-  const FluidnetWs w = fluidnet_ws_layout(d.B, d.DHW, net_ws_bytes(g, d, net_kind), ws);
-  float *div = w.div, *x = w.x, *scale = w.scale;
-  double* partial = w.partial;
-  void* msws = w.net;
+  const Net& n = net_of(net_kind, g->is3D);
   if (bcs) {
     // The fused step (fnx_simulate_step, convnet, no flags_stick): three launches around the net instead of eight, the same
     // arithmetic per value.  The divergence goes straight into the net's input, U is not rewritten before the net, and
     // velocityUpdate, the un-normalisation, setWallBcs and the step's last setConstVals (simulate.py:168) are one pass.
-    launch_scale_std(d, nc, U, thr, partial, scale, s);                          // model.py:129-144
-    launch_pack_div(d, g->is3D, U, flags, scale, x, s);                          // model.py:125-126, :146-168
-    float* pnet = div;                                                           // (the divergence buffer is free here)
-    net_forward(g, d, packed, net_kind, x, pnet, precision_mode, msws, s);
+    const GridDims d = make_dims(g->B, g->D, g->H, g->W, g->z_offset, g->D_global);
+    hipStream_t s = (hipStream_t)stream;
+    const FluidnetWs w = fluidnet_ws_layout(d.B, d.DHW, n.ws_bytes(g), ws);
+    launch_scale_std(d, g->is3D ? 3 : 2, U, thr, w.partial, w.scale, s);         // model.py:129-144
+    launch_pack_div(d, g->is3D, U, flags, w.scale, w.x, s);                      // model.py:125-126, :146-168
+    float* pnet = w.div;                                                         // (the divergence buffer is free here)
+    n.forward(g, packed, w.x, pnet, precision_mode, w.net, s);
     ProfScope ps(FNX_PROF_STAGE, s);
-    launch_post_projection(d, g->is3D, pnet, U, bcs->density, flags, bc_ptrs(bcs), s, bcs->density_bc_applied != 0, scale,
+    launch_post_projection(d, g->is3D, pnet, U, bcs->density, flags, bc_ptrs(bcs), s, bcs->density_bc_applied != 0, w.scale,
                            p_out);                                               // model.py:213-226, simulate.py:168
     return fnx::launch_status(g->is3D);
   }
-  if (int rc = fluidnet_pre(g, thr, U, flags, scale, w, stream)) return rc;
-  net_forward(g, d, packed, net_kind, x, p_out, precision_mode, msws, s);
-  if (int rc = fluidnet_post(g, p_out, U, flags, scale, stream)) return rc;
+  if (int rc = fluidnet_around(n, g, packed, flags, thr, precision_mode, p_out, U, ws, stream)) return rc;
   return fnx::launch_status(g->is3D);
 }
 
@@ -321,18 +328,44 @@ int fluidnet_core(const FnxGrid* g, const void* packed, int net_kind, const floa
 // fluidnet_core, so p_out holds the bits fnx_fluidnet_forward returns as p for this U.
 int fluidnet_pressure(const FnxGrid* g, const void* packed, int net_kind, const float* flags, float thr, int precision_mode, float* p_out,
                       const float* U, void* ws, void* stream) {
+  const Net& n = net_of(net_kind, g->is3D);
   const GridDims d = make_dims(g->B, g->D, g->H, g->W, g->z_offset, g->D_global);
   hipStream_t s = (hipStream_t)stream;
-  const int nc = g->is3D ? 3 : 2;
-  const FluidnetWs w = fluidnet_ws_layout(d.B, d.DHW, net_ws_bytes(g, d, net_kind), ws);   // (its divergence buffer is not used here)
-  float *x = w.x, *scale = w.scale;
-  double* partial = w.partial;
-  void* msws = w.net;
-  launch_scale_std(d, nc, U, thr, partial, scale, s);                            // model.py:129-144
-  launch_pack_div(d, g->is3D, U, flags, scale, x, s);                            // model.py:125-126, :146-168
-  net_forward(g, d, packed, net_kind, x, p_out, precision_mode, msws, s);
-  launch_unscale(d, 0, scale, p_out, nullptr, s);                                // model.py:221-222
+  const FluidnetWs w = fluidnet_ws_layout(d.B, d.DHW, n.ws_bytes(g), ws);        // (its divergence buffer is not used here)
+  launch_scale_std(d, g->is3D ? 3 : 2, U, thr, w.partial, w.scale, s);           // model.py:129-144
+  launch_pack_div(d, g->is3D, U, flags, w.scale, w.x, s);                        // model.py:125-126, :146-168
+  n.forward(g, packed, w.x, p_out, precision_mode, w.net, s);
+  launch_unscale(d, 0, w.scale, p_out, nullptr, s);                              // model.py:221-222
   return fnx::launch_status(g->is3D);
+}
+
+// ---- training: the same stages around a taped net, and their adjoints in front of the net's backward ----
+size_t fluidnet_train_ws_bytes(const NetTrain& n, const FnxGrid* g) {
+  // forward: div, x (2), std partials; backward: the wall-masked scaled grad_U, grad_U of the update, its grad_p, g_net, the net's own
+  const size_t fwd = fluidnet_ws_layout(g->B, (size_t)g->D * g->H * g->W, 0, nullptr).head;
+  const size_t bwd = fluidnet_train_bwd_ws(n.ndim, g, nullptr).bytes + n.backward_ws_bytes(g);
+  return fwd > bwd ? fwd : bwd;
+}
+
+int fluidnet_forward_train(const NetTrain& n, const FnxGrid* g, const void* packed, const float* input, float thr, float* p_out, float* U_out,
+                           float* flags_out, float* scale_out, float* tape, int mode, void* ws, void* stream) {
+  FluidnetWs w = fluidnet_ws_layout(g->B, (size_t)g->D * g->H * g->W, 0, ws);      // (its head: the scales go to scale_out)
+  if (n.tape_x) w.x = tape + n.tape_x(g);                                          // the backward reads the net's input again
+  fluidnet_split(g, input, U_out, flags_out, stream);
+  if (int rc = fluidnet_pre(g, thr, U_out, flags_out, scale_out, w, stream)) return rc;
+  n.forward(g, packed, w.x, p_out, tape, mode, (hipStream_t)stream);
+  if (int rc = fluidnet_post(g, p_out, U_out, flags_out, scale_out, stream)) return rc;
+  return n.status();
+}
+
+int fluidnet_backward(const NetTrain& n, const FnxGrid* g, const void* packed_t, const float* flags, const float* scale, const float* grad_p,
+                      const float* grad_U, const float* tape, float* grad_blob, int mode, void* ws, void* stream, bool* launched) {
+  *launched = true;
+  const FluidnetTrainBwdWs w = fluidnet_train_bwd_ws(n.ndim, g, ws);
+  // g_net = s g_p + velocity_update_backward_p(s setWallBcs(g_U)): the adjoints of model.py:226, :221-223 and :213-218 in reverse
+  if (int rc = fluidnet_train_gnet(n.ndim, g, flags, scale, grad_p, grad_U, w, stream)) return rc;
+  *launched = n.backward(g, packed_t, n.tape_x ? tape + n.tape_x(g) : nullptr, w.gnet, tape, grad_blob, mode, w.net, (hipStream_t)stream);
+  return *launched ? n.status() : FNX_OK;
 }
 }  // namespace fnx
 
@@ -346,10 +379,7 @@ int fnx_fluidnet_forward(const FnxGrid* g, const void* packed, const float* inpu
   int mode;
   if (int rc = fnx::check_net_call(__func__, g, packed && input && p_out && U_out && ws, precision_mode, &mode, fnx::fluidnet_ws_bytes, ws_bytes))
     return rc;
-  float* flags = (float*)ws;                       // contiguous (B,1,..) copy of the flags channel
-  void* rest = (char*)ws + fnx::fluidnet_flags_bytes(g->B, (size_t)g->D * g->H * g->W);
-  fnx::fluidnet_split(g, input, U_out, flags, stream);
-  return fnx::fluidnet_core(g, packed, FNX_NET_SCALENET, flags, thr, mode, p_out, U_out, rest, stream);
+  return fnx::fluidnet_whole_forward(fnx::scalenet_net(g->is3D), g, packed, input, thr, p_out, U_out, mode, ws, stream);
 }
 
 }  // extern "C"

@@ -33,6 +33,28 @@ _UNUSED_PREFIXES = ("conv1.", "convBank.", "conv2.", "conv3.", "convOut.", "scal
 _BANK_UNUSED_PREFIXES = ("multiScale.", "scale.")
 
 
+# The four pressure nets' entry points in ext, by (bank, ndim): the one table of their names (train._Api, BankNet and FluidNet read it).
+# The first three operations are inference, where the ScaleNet has one name for both dimensions and an argument more (pack_args: is3D;
+# forward_args: no trim); the rest is training.  backward_x: the net's backward takes the net's input behind packed_t.
+_NET_OPS = ("pack", "forward", "whole_forward", "pack_t", "forward_train", "backward", "whole_forward_train", "whole_backward")
+
+
+def _net_row(names, pack_args=(), forward_args=(), backward_x=True):
+    return dict(zip(_NET_OPS, names.split()), pack_args=pack_args, forward_args=forward_args, backward_x=backward_x)
+
+
+NET_EXT = {
+    (False, 2): _net_row("scalenet_pack multiscale_forward fluidnet_forward scalenet_pack_t multiscale_forward_train multiscale_backward "
+                         "fluidnet_forward_train fluidnet_backward", (False,), ([],), False),
+    (False, 3): _net_row("scalenet_pack multiscale_forward fluidnet_forward scalenet3d_pack_t multiscale3d_forward_train multiscale3d_backward "
+                         "fluidnet3d_forward_train fluidnet3d_backward", (True,), ([],), False),
+    (True, 2): _net_row("banknet_pack banknet_forward fluidnet_bank_forward banknet_pack_t banknet_forward_train banknet_backward "
+                        "fluidnet_bank_forward_train fluidnet_bank_backward"),
+    (True, 3): _net_row("banknet3d_pack banknet3d_forward fluidnet_bank3d_forward banknet3d_pack_t banknet3d_forward_train banknet3d_backward "
+                        "fluidnet_bank3d_forward_train fluidnet_bank3d_backward"),
+}
+
+
 def _layer_keys(ndim):
     return [L["name"] + sfx for L in scalenet_layers(2, ndim) for sfx in (".weight", ".bias")]
 
@@ -79,10 +101,13 @@ class BankNet:
         self.is3D = bool(is3D)
         self.precision_mode = precision_mode
         blob = torch.from_numpy(blob_from_state_dict(state_dict, keys=_bank_keys())).to(device)
-        self.packed = (ext.banknet3d_pack if self.is3D else ext.banknet_pack)(blob)
+        self.packed = self._fn("pack")(blob)
+
+    def _fn(self, op):
+        return getattr(ext, NET_EXT[True, 3 if self.is3D else 2][op])
 
     def __call__(self, x):
-        return (ext.banknet3d_forward if self.is3D else ext.banknet_forward)(self.packed, x.contiguous(), self.precision_mode)
+        return self._fn("forward")(self.packed, x.contiguous(), self.precision_mode)
 
 
 class BankNet3D(BankNet):
@@ -92,12 +117,12 @@ class BankNet3D(BankNet):
         super().__init__(state_dict, device, precision_mode, is3D)
 
 
-# what differs between the three models of mconf['model']: a fresh net's weights (seed, ndim), the net alone (state_dict, device,
-# precision_mode, is3D) and ext's FluidNet.forward around it
+# what differs between the three models of mconf['model'] besides NET_EXT's names: a fresh net's weights (seed, ndim) and the net alone
+# (state_dict, device, precision_mode, is3D)
 _MODELS = {
-    "ScaleNet": dict(weights=make_scalenet_weights, net=MultiScaleNet, forward="fluidnet_forward"),
-    "FluidNet": dict(weights=make_banknet_weights, net=BankNet, forward="fluidnet_bank_forward"),
-    "FluidNet3D": dict(weights=make_banknet_weights, net=BankNet3D, forward="fluidnet_bank3d_forward"),
+    "ScaleNet": dict(weights=make_scalenet_weights, net=MultiScaleNet),
+    "FluidNet": dict(weights=make_banknet_weights, net=BankNet),
+    "FluidNet3D": dict(weights=make_banknet_weights, net=BankNet3D),
 }
 
 
@@ -266,7 +291,7 @@ class FluidNet:
 
     def __call__(self, input_):
         ms = self._ensure_packed(input_.device)
-        p, U = getattr(ext, self._model["forward"])(ms.packed, input_.contiguous(), self.threshold, self.precision_mode)
+        p, U = getattr(ext, NET_EXT[self.is_bank, self._ndim]["whole_forward"])(ms.packed, input_.contiguous(), self.threshold, self.precision_mode)
         return p, U
 
     forward = __call__

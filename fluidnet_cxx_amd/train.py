@@ -22,7 +22,7 @@ from collections import OrderedDict
 import torch
 
 from ._ext import ext
-from .model import _BANK_UNUSED_PREFIXES, _UNUSED_PREFIXES
+from .model import _BANK_UNUSED_PREFIXES, _UNUSED_PREFIXES, NET_EXT
 from .weights import banknet_layers, make_banknet_weights, make_scalenet_weights, scalenet_layers
 
 _TRAIN_MODES = ("fp32", "fp32_f4", "fp32_f2", "fp32_direct")
@@ -43,47 +43,37 @@ def _split(blob, shapes):
     return grads
 
 
-# the bank nets' entry points under the names the ScaleNet's have in _Api ('#': nothing in 2D, '3d' in 3D, for either net)
-_BANK_NAMES = {"scalenet#_pack_t": "banknet#_pack_t", "multiscale#_forward_train": "banknet#_forward_train",
-               "multiscale#_backward": "banknet#_backward", "fluidnet#_forward_train": "fluidnet_bank#_forward_train",
-               "fluidnet#_backward": "fluidnet_bank#_backward", "pack": "banknet#_pack", "net_forward": "banknet#_forward",
-               "fluidnet_forward": "fluidnet_bank#_forward"}
-
-
 class _Api:
-    """what differs between the 2D net, the 3D net and the two bank nets: the extension's entry points and the number of velocity
-    components (only the dimension and the model are state, so a module that holds one copies and pickles as before)"""
+    """what differs between the 2D net, the 3D net and the two bank nets: the extension's entry points (model.NET_EXT's row) and the
+    number of velocity components (only the dimension and the model are state, so a module that holds one copies and pickles as before)"""
 
     bank = False                         # (a class default: an _Api pickled before the bank net existed has no such attribute)
 
     def __init__(self, ndim, bank=False):
         self.ndim, self.nc, self.bank = ndim, ndim, bank
 
-    def _fn(self, name):
-        if self.bank:
-            name = _BANK_NAMES[name]
-        return getattr(ext, name.replace("#", "" if self.ndim == 2 else "3d"))
+    @property
+    def _row(self):
+        return NET_EXT[self.bank, self.ndim]
+
+    def _fn(self, op):
+        return getattr(ext, self._row[op])
 
     def pack(self, blob):
-        fwd = self._fn("pack")(blob) if self.bank else ext.scalenet_pack(blob, self.ndim == 3)
-        return fwd, self._fn("scalenet#_pack_t")(blob)
+        return self._fn("pack")(blob, *self._row["pack_args"]), self._fn("pack_t")(blob)
 
     def net_forward(self, packed, x, mode):
         """the inference launches of the net alone"""
-        return self._fn("net_forward")(packed, x, mode) if self.bank else ext.multiscale_forward(packed, x, mode, [])
-
-    def fluidnet_forward(self, packed, input_, threshold, mode):
-        """the inference launches of FluidNet.forward"""
-        return (self._fn("fluidnet_forward") if self.bank else ext.fluidnet_forward)(packed, input_, threshold, mode)
+        return self._fn("forward")(packed, x, mode, *self._row["forward_args"])
 
     def net_backward(self, packed_t, x, gp, tape, mode):
         """(the bank net's backward reads the net's input again: conv1's weight gradient)"""
-        fn = self._fn("multiscale#_backward")
-        return fn(packed_t, x, gp, tape, mode) if self.bank else fn(packed_t, gp, tape, mode)
+        return self._fn("backward")(packed_t, *((x,) if self._row["backward_x"] else ()), gp, tape, mode)
 
-    multiscale_forward_train = property(lambda self: self._fn("multiscale#_forward_train"))
-    fluidnet_forward_train = property(lambda self: self._fn("fluidnet#_forward_train"))
-    fluidnet_backward = property(lambda self: self._fn("fluidnet#_backward"))
+    fluidnet_forward = property(lambda self: self._fn("whole_forward"))          # the inference launches of FluidNet.forward
+    multiscale_forward_train = property(lambda self: self._fn("forward_train"))
+    fluidnet_forward_train = property(lambda self: self._fn("whole_forward_train"))
+    fluidnet_backward = property(lambda self: self._fn("whole_backward"))
 
 
 class _MultiScaleFn(torch.autograd.Function):
@@ -94,7 +84,7 @@ class _MultiScaleFn(torch.autograd.Function):
         packed, ctx.packed_t = owner._packed(x.device)
         p, ctx.tape = owner._api.multiscale_forward_train(packed, x, owner.precision_mode)
         ctx.mode, ctx.shapes, ctx.api = owner.precision_mode, [q.shape for q in params], owner._api
-        ctx.x = x if ctx.api.bank else None
+        ctx.x = x if ctx.api._row["backward_x"] else None
         return p
 
     @staticmethod

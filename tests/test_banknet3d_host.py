@@ -247,6 +247,10 @@ def test_refusals_before_any_launch():
         for m in ("FNX_PRECISION_FP32", "FNX_PRECISION_FP32_DIRECT", "FNX_PRECISION_FP32_F4", "FNX_PRECISION_FP32_F2"):
             assert call(FnxGrid(**ok), mode=modes[m], ws_bytes=0)[0] == EWORKSPACE
     assert lib.fnx_banknet3d_pack(None, a, None) == EINVAL and lib.fnx_last_error().decode() == "fnx_banknet3d_pack: null argument"
+    # the whole forward's workspace and its refusal word for word, as recorded before the three nets' whole forwards became one body
+    assert whole(FnxGrid(**ok), ws_bytes=541951) == (EWORKSPACE,
+                                                     "fnx_fluidnet_bank3d_forward: workspace of 541951 bytes is too small (541952 needed)")
+    assert lib.fnx_banknet3d_ws_bytes(ctypes.byref(FnxGrid(**ok)), 1) == 541952
 
 
 def test_launch_plan_covers_every_cell_once():

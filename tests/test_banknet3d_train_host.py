@@ -151,6 +151,10 @@ def test_refusals_before_any_launch(lib):
     g1, g2 = FnxGrid(**ok), FnxGrid(B=2, D=8, H=32, W=24, is3D=1)
     assert lib.fnx_fluidnet_bank3d_train_ws_bytes(ctypes.byref(g2)) > lib.fnx_fluidnet_bank3d_train_ws_bytes(ctypes.byref(g1)) > \
         lib.fnx_banknet3d_backward_ws_bytes(ctypes.byref(g1))
+    # the sizes themselves at two grids, as recorded before the four nets' training wrappers became one body
+    for shape, train_ws in (((2, 8, 12, 20), 2088448), ((1, 4, 4, 4), 186112)):
+        assert lib.fnx_fluidnet_bank3d_train_ws_bytes(ctypes.byref(FnxGrid(*shape, is3D=1))) == train_ws, shape
+    assert lib.fnx_banknet3d_backward_ws_bytes(ctypes.byref(FnxGrid(2, 8, 12, 20, is3D=1))) == 1965568
 
 
 PLAN_GRIDS = [(1, 4, 4, 4), (2, 8, 12, 20), (1, 12, 20, 36), (2, 4, 36, 68), (1, 20, 12, 132), (2, 32, 64, 64), (3, 16, 40, 72),

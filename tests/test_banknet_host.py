@@ -199,6 +199,9 @@ def test_refusals_before_any_launch():
         for m in ("FNX_PRECISION_FP32", "FNX_PRECISION_FP32_DIRECT", "FNX_PRECISION_FP32_F4", "FNX_PRECISION_FP32_F2"):
             assert call(FnxGrid(**ok), mode=modes[m], ws_bytes=0)[0] == EWORKSPACE
     assert lib.fnx_banknet_pack(None, a, None) == EINVAL and lib.fnx_last_error().decode() == "fnx_banknet_pack: null argument"
+    # the whole forward's workspace and its refusal word for word, as recorded before the three nets' whole forwards became one body
+    assert whole(FnxGrid(**ok), ws_bytes=30463) == (EWORKSPACE, "fnx_fluidnet_bank_forward: workspace of 30463 bytes is too small (30464 needed)")
+    assert lib.fnx_banknet_ws_bytes(ctypes.byref(FnxGrid(**ok)), 1) == 30464
 
 
 def test_bank_kernels_use_no_scratch(tmp_path):

@@ -128,6 +128,10 @@ def test_refusals_before_any_launch(lib):
     g1, g2 = FnxGrid(**ok), FnxGrid(B=2, D=1, H=32, W=24)
     assert lib.fnx_fluidnet_bank_train_ws_bytes(ctypes.byref(g2)) > lib.fnx_fluidnet_bank_train_ws_bytes(ctypes.byref(g1)) > \
         lib.fnx_banknet_backward_ws_bytes(ctypes.byref(g1))
+    # the sizes themselves at two grids, as recorded before the four nets' training wrappers became one body
+    for shape, train_ws in (((3, 1, 36, 68), 3068672), ((64, 1, 4, 4), 4026368)):
+        assert lib.fnx_fluidnet_bank_train_ws_bytes(ctypes.byref(FnxGrid(*shape))) == train_ws, shape
+    assert lib.fnx_banknet_backward_ws_bytes(ctypes.byref(FnxGrid(3, 1, 36, 68))) == 2892032
 
 
 def test_train_kernels_resources(tmp_path):

@@ -99,6 +99,32 @@ def test_the_surface_simulate_uses(built):
     assert net.precision_mode == "fp32_f2"
 
 
+def test_nets_copy_and_pickle_and_an_old_api_record_loads(built):
+    """FluidNet, FluidNetTrain and FluidNetBankTrain survive copy.deepcopy and a pickle round trip with their parameters and the entry
+    points they name (the tables of names live at module level, not on the instances), and an _Api pickled before the bank net existed,
+    whose state has no `bank`, still names the ScaleNet's entry points."""
+    import copy
+    import pickle
+    from fluidnet_cxx_amd import FluidNet, FluidNetBankTrain, FluidNetTrain, train
+    from fluidnet_cxx_amd._ext import ext
+    bank = dict(MCONF, model="FluidNet")
+    for cls, mconf, forward in ((FluidNet, MCONF, None), (FluidNet, bank, None), (FluidNetTrain, MCONF, ext.fluidnet_forward_train),
+                                (FluidNetBankTrain, bank, ext.fluidnet_bank_forward_train)):
+        net = cls(mconf)
+        for twin in (copy.deepcopy(net), pickle.loads(pickle.dumps(net))):
+            assert type(twin) is cls and twin.mconf == mconf
+            sd, want = twin.state_dict(), net.state_dict()
+            assert list(sd) == list(want) and all(torch.equal(sd[k], want[k]) for k in want)
+            if forward is not None:
+                assert (twin._api.ndim, twin._api.nc, twin._api.bank) == (2, 2, cls is FluidNetBankTrain)
+                assert twin._api.fluidnet_forward_train == forward
+    old = train._Api.__new__(train._Api)
+    old.__dict__.update(ndim=3, nc=3)                      # (the state of an _Api of the 3D trainer from before the bank net)
+    old = pickle.loads(pickle.dumps(old))
+    assert old.bank is False and "bank" not in old.__dict__
+    assert old.fluidnet_backward == ext.fluidnet3d_backward and old.multiscale_forward_train == ext.multiscale3d_forward_train
+
+
 def test_out_of_scope_configurations_raise(built):
     from fluidnet_cxx_amd import FluidNet, FluidNetTrain
     with pytest.raises(ValueError, match="2D only"):

@@ -6,7 +6,7 @@
 TREE is the checkout whose built package is imported (default: the one this file sits in).  Only extension functions are used, so any
 two trees that have them can be compared: run the tool once per tree, each in a process of its own, and compare the outputs line by line.
 Per dimension: packed_t; at every shape p, the tape's entries without the alignment gaps and the gradient blob; at one shape the
-FluidNet-level p, U, scale, flags, tape and gradient.  The weights are He-scaled, so that every level and every ReLU carries gradient.
+FluidNet-level p, U, scale, flags, tape and gradient, and the inference whole forward's p and U.  The weights are He-scaled, so that every level and every ReLU carries gradient.
 Shapes: 2D (1,4,4) has fewer than 64 cells, so the tail backward's masked lanes run; (3,36,68) is a batch with partial tiles;
 (2,132,260) has 1 074 units of 64 cells on 512 workgroups, so a workgroup takes several.  3D (1,4,4,4) and (2,4,36,68) are the smallest
 and a thin batch; (2,32,64,64) has 4 096 units, above the cap.  In 3D, D H W is always a multiple of 64 (each a multiple of 4), so the
@@ -78,6 +78,9 @@ def main():
         grad = fn("fluidnet_bank#_backward")(packed_t, flags, scale, w_p, w_U, tape, "fp32")
         for name, t in (("p", p), ("U", U), ("scale", scale), ("flags", flags), ("tape", entries(tape, shape)), ("grad", grad)):
             emit(f"fluidnet bank {ndim}d {sid(shape)} {name}", t)
+        # the inference whole forward on the same input (ext.fluidnet_bank_forward / fluidnet_bank3d_forward)
+        for name, t in zip(("p", "U"), fn("fluidnet_bank#_forward")(packed, inp, 1e-5, "fp32")):
+            emit(f"fluidnet bank {ndim}d {sid(shape)} infer {name}", t)
         torch.cuda.empty_cache()
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
