@@ -25,6 +25,7 @@ struct Geom {
   bool ref_quirks = false;          // 3D only: reproduce the reference's 3D defects bit-for-bit (FnxGrid.ref_quirks)
   int z_offset = 0, D_global = 0;   // z-slab view: the tensors hold planes [z_offset, z_offset + D) of a D_global-deep domain
   int k_begin = 0, k_end = 0;       // compute window: plane-parallel operators produce local planes [k_begin, k_end) only
+  int jacobi_x = 0;                 // tiling of the 3D two-sweep Jacobi march: 0 the plan's choice, 60 / 64 forced (A/B timing, tests; same bits)
 };
 
 void check_status(int rc) {
@@ -46,7 +47,8 @@ FnxGrid grid_of(const Tensor& flags, bool is3D, const Geom* geom) {
   FnxGrid g{};
   g.B = (int)flags.size(0); g.D = (int)flags.size(2); g.H = (int)flags.size(3); g.W = (int)flags.size(4);
   g.is3D = is3D ? 1 : 0;
-  g.ref_quirks = go.ref_quirks ? 1 : 0;
+  g.ref_quirks = (go.ref_quirks ? 1 : 0) |
+                 ((go.jacobi_x == 60 ? FNX_JACOBI3D_X_60 : go.jacobi_x == 64 ? FNX_JACOBI3D_X_64 : FNX_JACOBI3D_X_AUTO) << FNX_JACOBI3D_X_SHIFT);
   g.z_offset = is3D ? go.z_offset : 0; g.D_global = is3D ? go.D_global : 0;
   g.k_begin = is3D ? go.k_begin : 0; g.k_end = is3D ? go.k_end : 0;
   if (!is3D) TORCH_CHECK(g.D == 1, "2D velocity field but zdepth > 1");
@@ -1244,12 +1246,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   using NoGil = py::call_guard<py::gil_scoped_release>;
   const auto GEOM = py::arg("geom") = py::none();
   py::class_<Geom>(m, "Geom", "per-call 3D geometry options: ref_quirks, z-slab view (z_offset, D_global), compute window [k_begin, k_end)")
-      .def(py::init([](bool ref_quirks, int z_offset, int D_global, int k_begin, int k_end) {
+      .def(py::init([](bool ref_quirks, int z_offset, int D_global, int k_begin, int k_end, int jacobi_x) {
              Geom g; g.ref_quirks = ref_quirks; g.z_offset = z_offset; g.D_global = D_global; g.k_begin = k_begin; g.k_end = k_end;
+             g.jacobi_x = jacobi_x;
              return g;
            }),
            py::arg("ref_quirks") = false, py::arg("z_offset") = 0, py::arg("D_global") = 0, py::arg("k_begin") = 0,
-           py::arg("k_end") = 0)
+           py::arg("k_end") = 0, py::arg("jacobi_x") = 0)
+      .def_readwrite("jacobi_x", &Geom::jacobi_x)
       .def_readwrite("ref_quirks", &Geom::ref_quirks)
       .def_readwrite("z_offset", &Geom::z_offset)
       .def_readwrite("D_global", &Geom::D_global)

@@ -55,7 +55,8 @@ inline GridDims dims(const FnxGrid* g) {
   if (g->is3D && g->k_end > g->k_begin) { d.K0 = g->k_begin; d.KN = g->k_end - g->k_begin; }
   return d;
 }
-inline bool quirks(const FnxGrid* g) { return g->is3D && g->ref_quirks; }
+inline bool quirks(const FnxGrid* g) { return g->is3D && (g->ref_quirks & 1); }
+inline int jacobi3d_x(const FnxGrid* g) { return (g->ref_quirks >> FNX_JACOBI3D_X_SHIFT) & 3; }   // the forced tiling of the two-sweep march, if any
 inline size_t ncell(const FnxGrid* g) { return (size_t)g->B * g->D * g->H * g->W; }
 inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -390,7 +391,7 @@ static const float* run_jacobi_launches(const FnxGrid* g, const fnx::JacobiSched
     float* out = buf[(first + l) & 1];
     fnx::ProfScope ps(FNX_PROF_JACOBI, s);
     if (!g->is3D) fnx::launch_jacobi(d, flags, div, in, out, L.sweeps, in == nullptr, s);
-    else if (L.sweeps == 2) fnx::launch_jacobi3d_x2(d, mask, div, in, out, s, 0, 0, in == nullptr, -1, L.lay);
+    else if (L.sweeps == 2) fnx::launch_jacobi3d_x2(d, mask, div, in, out, s, 0, 0, in == nullptr, -1, L.lay, nullptr, jacobi3d_x(g));
     else fnx::launch_jacobi3d(d, mask, div, in, out, in == nullptr, s);
     in = out;
   }
@@ -516,7 +517,7 @@ int fnx_jacobi_pass_layout(const FnxGrid* g, const float* flags, const float* di
   JacobiWs W;
   if (int rc = jacobi_begin("jacobi_pass", g, flags, ws, ws_bytes, reuse_mask != 0, s, &W)) return rc;
   fnx::ProfScope ps(FNX_PROF_JACOBI, s);
-  if (nsweeps == 2) fnx::launch_jacobi3d_x2(d, W.mask, div, p_in, p_out, s, k_begin, k_end, from_zero, k_begin2, layout);
+  if (nsweeps == 2) fnx::launch_jacobi3d_x2(d, W.mask, div, p_in, p_out, s, k_begin, k_end, from_zero, k_begin2, layout, nullptr, jacobi3d_x(g));
   else {
     fnx::launch_jacobi3d(d, W.mask, div, p_in, p_out, from_zero, s, k_begin, k_end);
     if (k_begin2 >= 0) fnx::launch_jacobi3d(d, W.mask, div, p_in, p_out, from_zero, s, k_begin2, k_begin2 + (k_end - k_begin));

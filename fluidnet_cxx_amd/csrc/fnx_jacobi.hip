@@ -30,6 +30,14 @@ __device__ __forceinline__ float dpp_from_left(float v) {    // value held by la
 __device__ __forceinline__ float dpp_from_right(float v) {   // value held by lane+1 (0 into lane 63)
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x130, 0xf, 0xf, true));
 }
+// the same shifts for a wave whose x neighbours live in other waves: the lane without an in-wave source keeps `old` (lane 0 of
+// dpp_from_left_or, lane 63 of dpp_from_right_or), where the caller has put the neighbour wave's value -- no select
+__device__ __forceinline__ float dpp_from_left_or(float old, float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old), __builtin_bit_cast(int, v), 0x138, 0xf, 0xf, false));
+}
+__device__ __forceinline__ float dpp_from_right_or(float old, float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old), __builtin_bit_cast(int, v), 0x130, 0xf, 0xf, false));
+}
 __device__ __forceinline__ unsigned dpp_from_left_u(unsigned v) {
   return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, true);
 }
@@ -574,15 +582,35 @@ __device__ __forceinline__ BufRsrc make_rsrc(const void* p, unsigned bytes) {
 // block writes the planes its neighbours need next straight into their mapped mailboxes (peer-store communicator) as the march
 // finishes them: no transport launch copies them afterwards.  The extra store is issued by every step and dropped by the buffer range
 // check outside the mirrored planes (an offset below the range wraps around, one above it is out of range): no branch.
+//
+// X64 (whole-domain passes of grids up to 512 wide, not SPLIT, not MIR; fnx::jacobi3d_x64_ok, measured in docs/history/r34_jacobi_x64.md): NO x halo.  A workgroup is the
+// blockDim.y = ceil(W / 64) waves of one (row group, plane chunk); wave w owns the columns [64w, 64w + 64) and every lane produces
+// output, where the 60-column tiles recompute two columns a side (5 waves for a 256-wide row, the fifth with 16 useful columns).
+// The two x neighbours a wave lacks come from its neighbour waves through an LDS mailbox, double-buffered by step parity, one
+// s_barrier a step: after sweep 1 of step t lanes 0 and 63 publish their p^1(t) (rows j0 .. j0+3, the centres of the next step's
+// sweep 2) and p^0(t+1) (rows j0-1 .. j0+4, the centres of its sweep 1: that plane is the z neighbour this step has already waited
+// for); after the next step's barrier every wave reads its left neighbour's lane-63 values and its right neighbour's lane-0
+// values, which go in as the `old` operand of the DPP shifts.  At the domain's x walls the mailbox read is the wave's own: a
+// border cell is never 'cont'.  `nxt` stays the 60-column tile count, by which the "same" bits are laid out: a 64-column tile
+// takes the AND of the one or two 60-column tiles that cover its columns.  The arithmetic is the same operations on the same operands.
 struct MirrorArgs { float* out[2][2]; const unsigned* sel[2]; int k[2]; int n; unsigned long long bstride; unsigned long long* clock; };
-template <bool ZERO, bool SPLIT, int LAY, bool MIR = false>
-__global__ __launch_bounds__(64 * Z2NW, Z2WPS) void jacobi3d_march2_kernel(GridDims g, const unsigned* __restrict__ maskq,
+using fnx::X64_MAXW;
+constexpr int X64_BOX = 12;   // floats a mailbox side: p^1 rows 0..3, p^0 rows 4..9, 2 of padding (16-byte accesses)
+__device__ __forceinline__ void x64_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+template <bool ZERO, bool SPLIT, int LAY, bool MIR = false, bool X64 = false>
+__global__ __launch_bounds__(X64 ? 64 * X64_MAXW : 64 * Z2NW, Z2WPS) void jacobi3d_march2_kernel(GridDims g, const unsigned* __restrict__ maskq,
                                                                       const unsigned* __restrict__ msame,
                                                                       const float* __restrict__ div,
                                                                       const float* __restrict__ p_in,
                                                                       float* __restrict__ p_out, int nxt, int nyt,
                                                                       int zchunk, int kb, int ke, int kb2, MirrorArgs mir = MirrorArgs{}) {
   constexpr int R0 = Z2R + 4, R1 = Z2R + 2;
+  static_assert(!X64 || (!SPLIT && !MIR), "the 64-column tiles run whole-domain passes in one resident set");
+  float* box = nullptr;                                  // X64: [step parity][wave][0: lane 0's, 1: lane 63's][X64_BOX]
+  if constexpr (X64) {
+    __shared__ __attribute__((aligned(16))) float box_s[2 * X64_MAXW * 2 * X64_BOX];
+    box = box_s;
+  }
   const int lane = threadIdx.x;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.y);
   if (MIR && mir.clock && blockIdx.x == 0 && lane == 0) *mir.clock = wall_clock64();     // when the mirrored stores begin (FnxPlaneMirror.start_clock)
@@ -594,7 +622,7 @@ __global__ __launch_bounds__(64 * Z2NW, Z2WPS) void jacobi3d_march2_kernel(GridD
   // contiguous ranges instead.
   const int G = gridDim.x, np = ke - kb;
   const int gid = (blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3);
-  const int ntiles = nxt * nyt * g.B;
+  const int ntiles = (X64 ? 1 : nxt) * nyt * g.B;          // X64: a "tile" is a whole row group, its waves the workgroup's
   int L0, L1;
   int kbase = kb;                                        // kb2 >= 0: a second plane range [kb2, kb2 + np) in the same launch
   if (!SPLIT) {
@@ -621,10 +649,10 @@ __global__ __launch_bounds__(64 * Z2NW, Z2WPS) void jacobi3d_march2_kernel(GridD
   const int tile = L0 / np, pk = L0 - tile * np;
   const int seg = min(np - pk, L1 - L0);
   L0 = SPLIT ? L0 + seg : L1;
-  const int bx = tile % nxt, l1 = tile / nxt;
+  const int bx = X64 ? 0 : tile % nxt, l1 = X64 ? tile : tile / nxt;
   const int by = l1 % nyt, b = l1 / nyt;
-  const int x = bx * 60 - 2 + lane;
-  const int j0 = (by * Z2NW + w) * Z2R;
+  const int x = X64 ? w * 64 + lane : bx * 60 - 2 + lane;
+  const int j0 = X64 ? by * Z2R : (by * Z2NW + w) * Z2R;
   const int k_lo = kbase + pk, k_hi = k_lo + seg;           // output planes [k_lo, k_hi) of this segment
   const bool xin = (x >= 0) & (x < g.W);
   const int xc = x < 0 ? 0 : (x > g.W - 1 ? g.W - 1 : x);
@@ -678,9 +706,15 @@ __global__ __launch_bounds__(64 * Z2NW, Z2WPS) void jacobi3d_march2_kernel(GridD
   // "plane k's mask equals plane k-1's" bits of this tile (jacobi3d_masksame_kernel) for the planes the steps after the first load the
   // mask of, [k_lo + 1, k_hi + 1]: two words from a wave-uniform address, i.e. scalar loads; planes past them simply load
   const int skw = (g.D + 31) >> 5, sw0 = (k_lo + 1) >> 5;
-  const unsigned* srow = msame + (size_t)tile * skw;
-  const unsigned long long sbits = (unsigned long long)(sw0 < skw ? srow[sw0] : 0u) |
-                                   ((unsigned long long)(sw0 + 1 < skw ? srow[sw0 + 1] : 0u) << 32);
+  auto same_bits = [&](int tile60) {
+    const unsigned* srow = msame + (size_t)tile60 * skw;
+    return (unsigned long long)(sw0 < skw ? srow[sw0] : 0u) | ((unsigned long long)(sw0 + 1 < skw ? srow[sw0 + 1] : 0u) << 32);
+  };
+  unsigned long long sbits;
+  if constexpr (X64) {                                   // columns 64w .. 64w+63 (clamped) lie in the 60-column tiles c0 and c1 (= c0 or c0 + 1)
+    const int c0 = (w * 64) / 60, xe = w * 64 + 63 < g.W - 1 ? w * 64 + 63 : g.W - 1, c1 = xe / 60;
+    sbits = same_bits(tile * nxt + c0) & same_bits(tile * nxt + c1);
+  } else sbits = same_bits(tile);
   auto ldf = [&](const BufRsrc& r, unsigned cell) {
     return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, xoff, cell * 4u, 0));
   };
@@ -731,13 +765,29 @@ __global__ __launch_bounds__(64 * Z2NW, Z2WPS) void jacobi3d_march2_kernel(GridD
     for (int rr = 0; rr < R1; ++rr) AD[0][rr] = ldf(r_d, pc + rowb[rr + 1]);
     AM[0] = ldm(t);
   }
-  const bool lane_out = (lane >= 2) & (lane <= 61) & xin;
+  const bool lane_out = X64 ? xin : (lane >= 2) & (lane <= 61) & xin;
+  // X64: the mailboxes this wave writes (per step parity: + 2 * X64_MAXW * X64_BOX) and reads
+  const int wl = w > 0 ? w - 1 : 0, wr = X64 && w + 1 < (int)blockDim.y ? w + 1 : w;
+  float* box_w = X64 ? box + (w * 2 + (lane == 63 ? 1 : 0)) * X64_BOX : nullptr;
+  const float* box_l = X64 ? box + (wl * 2 + 1) * X64_BOX : nullptr;
+  const float* box_r = X64 ? box + (wr * 2 + 0) * X64_BOX : nullptr;
+  constexpr int BOXP = 2 * X64_MAXW * X64_BOX;
+  if constexpr (X64 && !ZERO) {                          // p^0 of the first step's plane: what a step publishes for the next one
+    if (lane == 0 || lane == 63) {
+      *(f32x4*)(box_w + BOXP + 4) = f32x4{P0[0][1], P0[0][2], P0[0][3], P0[0][4]};
+      *(f32x2v*)(box_w + BOXP + 8) = f32x2v{P0[0][5], P0[0][6]};
+    }
+  }
   int prev_sel = 2;
 
   // one sweep over N rows: centre rows C[0..N), y-neighbours from the same plane, z-neighbours B / F
-  auto sweep = [&](auto nn, auto off, int sel, const Mask3 M, const float* Cm1, const float* B, const float* F,
-                   const float* DV, float* out) __attribute__((always_inline)) {
+  // hx: the x neighbours of row r are EL[r] and ER[r], shifted by the caller (lanes 0 and 63 hold what the neighbour waves handed over)
+  auto sweep = [&](auto nn, auto off, auto hx, int sel, const Mask3 M, const float* Cm1, const float* B, const float* F,
+                   const float* DV, float* out, const float* EL, const float* ER) __attribute__((always_inline)) {
     constexpr int N = decltype(nn)::value, OFF = decltype(off)::value;      // row r is row slot OFF + r: slot 0 = lo, 1..4 = own bytes, 5 = hi
+    constexpr bool HX = decltype(hx)::value != 0;
+    auto left = [&](int r, float c) { return HX ? EL[r] : dpp_from_left(c); };
+    auto right = [&](int r, float c) { return HX ? ER[r] : dpp_from_right(c); };
     auto mword = [&](int r) { return (OFF + r) == 0 ? M.lo : ((OFF + r) == 5 ? M.hi : M.own); };
     auto mshift = [&](int r) { return ((OFF + r) == 0 || (OFF + r) == 5) ? 0 : 8 * (OFF + r - 1); };
     float xs[N];
@@ -746,21 +796,21 @@ __global__ __launch_bounds__(64 * Z2NW, Z2WPS) void jacobi3d_march2_kernel(GridD
 #pragma unroll
       for (int r = 0; r < N; ++r) {
         const float c = Cm1[r + 1];
-        out[r] = relax3<0>(mword(r), mshift(r), c, dpp_from_left(c), dpp_from_right(c), Cm1[r], Cm1[r + 2], B[r], F[r], DV[r], xs[r]);
+        out[r] = relax3<0>(mword(r), mshift(r), c, left(r, c), right(r, c), Cm1[r], Cm1[r + 2], B[r], F[r], DV[r], xs[r]);
         bad |= __builtin_amdgcn_classf(out[r], 0x90);
       }
     } else if (sel == 1) {
 #pragma unroll
       for (int r = 0; r < N; ++r) {
         const float c = Cm1[r + 1];
-        out[r] = relax3<1>(mword(r), mshift(r), c, dpp_from_left(c), dpp_from_right(c), Cm1[r], Cm1[r + 2], B[r], F[r], DV[r], xs[r]);
+        out[r] = relax3<1>(mword(r), mshift(r), c, left(r, c), right(r, c), Cm1[r], Cm1[r + 2], B[r], F[r], DV[r], xs[r]);
         bad |= __builtin_amdgcn_classf(out[r], 0x90);
       }
     } else {
 #pragma unroll
       for (int r = 0; r < N; ++r) {
         const float c = Cm1[r + 1];
-        out[r] = relax3<2>(mword(r), mshift(r), c, dpp_from_left(c), dpp_from_right(c), Cm1[r], Cm1[r + 2], B[r], F[r], DV[r], xs[r]);
+        out[r] = relax3<2>(mword(r), mshift(r), c, left(r, c), right(r, c), Cm1[r], Cm1[r + 2], B[r], F[r], DV[r], xs[r]);
         bad |= __builtin_amdgcn_classf(out[r], 0x90);
       }
     }
@@ -787,15 +837,44 @@ __global__ __launch_bounds__(64 * Z2NW, Z2WPS) void jacobi3d_march2_kernel(GridD
     const unsigned sq = (unsigned)(t + 1 - 32 * sw0);
     if (t >= k_lo && sq < 64u && ((sbits >> sq) & 1ull)) AM[SP] = AM[SC];
     else AM[SP] = ldm(t + 1);
+    // ---- X64: the edge columns the neighbour waves published in the step before (the prologue, for the first step)
+    float EL0[R1], ER0[R1], EL1[Z2R], ER1[Z2R];
+    if constexpr (X64) {
+      x64_barrier();
+      const float* bl = box_l + (BUF ^ 1) * BOXP; const float* br = box_r + (BUF ^ 1) * BOXP;
+      const f32x4 l1 = *(const f32x4*)bl, r1 = *(const f32x4*)br;
+      EL1[0] = l1.x; EL1[1] = l1.y; EL1[2] = l1.z; EL1[3] = l1.w; ER1[0] = r1.x; ER1[1] = r1.y; ER1[2] = r1.z; ER1[3] = r1.w;
+      if constexpr (!ZERO) {
+        const f32x4 la = *(const f32x4*)(bl + 4), ra = *(const f32x4*)(br + 4);
+        const f32x2v lb = *(const f32x2v*)(bl + 8), rb = *(const f32x2v*)(br + 8);
+        EL0[0] = la.x; EL0[1] = la.y; EL0[2] = la.z; EL0[3] = la.w; EL0[4] = lb.x; EL0[5] = lb.y;
+        ER0[0] = ra.x; ER0[1] = ra.y; ER0[2] = ra.z; ER0[3] = ra.w; ER0[4] = rb.x; ER0[5] = rb.y;
+        // the shifts are the same whatever the obstacle path: once, in place, before the sweep branches on it
+#pragma unroll
+        for (int r = 0; r < R1; ++r) { EL0[r] = dpp_from_left_or(EL0[r], P0[SC][r + 1]); ER0[r] = dpp_from_right_or(ER0[r], P0[SC][r + 1]); }
+      }
+#pragma unroll
+      for (int r = 0; r < Z2R; ++r) { EL1[r] = dpp_from_left_or(EL1[r], P1[SM][r + 1]); ER1[r] = dpp_from_right_or(ER1[r], P1[SM][r + 1]); }
+    }
     // ---- sweep 1 on plane t, rows j0-1 .. j0+4
     const unsigned ob = AM[SC].own | ((AM[SC].lo | AM[SC].hi) & 0xffu);
     // no cell of these rows has an obstacle neighbour (0) / only x neighbours (1) / any (2)
     const int sel1 = __builtin_amdgcn_ballot_w64((ob & 0x78787878u) != 0) != 0 ? 2 : (__builtin_amdgcn_ballot_w64((ob & 0x06060606u) != 0) != 0 ? 1 : 0);
-    sweep(IC<R1>{}, IC<0>{}, sel1, AM[SC], P0[SC], &P0[SM][1], &P0[SP][1], AD[SC], P1[SC]);
+    sweep(IC<R1>{}, IC<0>{}, IC<(X64 && !ZERO)>{}, sel1, AM[SC], P0[SC], &P0[SM][1], &P0[SP][1], AD[SC], P1[SC], EL0, ER0);
+    if constexpr (X64) {
+      if (lane == 0 || lane == 63) {
+        float* bw = box_w + BUF * BOXP;
+        *(f32x4*)bw = f32x4{P1[SC][1], P1[SC][2], P1[SC][3], P1[SC][4]};
+        if constexpr (!ZERO) {
+          *(f32x4*)(bw + 4) = f32x4{P0[SP][1], P0[SP][2], P0[SP][3], P0[SP][4]};
+          *(f32x2v*)(bw + 8) = f32x2v{P0[SP][5], P0[SP][6]};
+        }
+      }
+    }
     // ---- sweep 2 on plane t-1, rows j0 .. j0+3 (p^1 of planes t-2, t-1, t = slots SN, SM, SC)
     if (t - 1 >= k_lo) {
       float v[Z2R];
-      sweep(IC<Z2R>{}, IC<1>{}, prev_sel, AM[SM], P1[SM], &P1[SN][1], &P1[SC][1], &AD[SM][1], v);
+      sweep(IC<Z2R>{}, IC<1>{}, IC<X64>{}, prev_sel, AM[SM], P1[SM], &P1[SN][1], &P1[SC][1], &AD[SM][1], v, EL1, ER1);
       const unsigned ok = (unsigned)((t - 1 - k0) * g.HW + j0 * g.W) * 4u;
       // (MIR) the mirrored planes are [mk0, mk0 + mir.n): a wave-uniform test, not the buffer range check -- the scalar offset of a
       // buffer instruction is outside that check, and a plane below mk0 would wrap it around 2^32.  Inside the window the plane offset
@@ -938,6 +1017,9 @@ void launch_tiles(const GridDims& g, const float* flags, const float* div, const
 using March2 = void (*)(GridDims, const unsigned*, const unsigned*, const float*, const float*, float*, int, int, int, int, int, int, MirrorArgs);
 template <bool ZERO, int LAY>
 March2 march2(bool split) { return split ? jacobi3d_march2_kernel<ZERO, true, LAY> : jacobi3d_march2_kernel<ZERO, false, LAY>; }
+// ... and the six of its 64-column tiling
+template <bool ZERO, int LAY>
+March2 march2_x64() { return jacobi3d_march2_kernel<ZERO, false, LAY, false, true>; }
 
 }  // namespace
 
@@ -964,11 +1046,19 @@ void launch_jacobi3d_mask(const GridDims& g, bool quirks, const float* flags, co
 
 // two sweeps in one pass: p_in = p^n, p_out = p^{n+2}.  lay: bit 0 = p_in, bit 1 = p_out in the row-quad layout
 void launch_jacobi3d_x2(const GridDims& g, const JacobiMaskLayout& mask, const float* div, const float* p_in, float* p_out,
-                        hipStream_t s, int kb, int ke, bool from_zero, int kb2, int lay, const JacobiMirror* mirror) {
+                        hipStream_t s, int kb, int ke, bool from_zero, int kb2, int lay, const JacobiMirror* mirror, int x_request) {
   if (ke <= kb) { kb = 0; ke = g.D; kb2 = -1; }
   const int np = ke - kb;
-  const Jacobi3dX2Plan p = jacobi3d_x2_plan(g, np, kb2 >= 0, from_zero, lay, cu_count());
   const Jacobi3dTiles t = jacobi3d_tiles(g);
+  if (jacobi3d_x64_pick(g, np, kb2 >= 0, mirror != nullptr, x_request, cu_count())) {
+    const Jacobi3dX64Plan q = jacobi3d_x64_plan(g, np, from_zero, lay, cu_count());
+    March2 k;
+    if (from_zero) k = q.lay == 2 ? march2_x64<true, 2>() : march2_x64<true, 0>();
+    else k = q.lay == 0 ? march2_x64<false, 0>() : q.lay == 1 ? march2_x64<false, 1>() : q.lay == 2 ? march2_x64<false, 2>() : march2_x64<false, 3>();
+    k<<<dim3((unsigned)q.G), dim3(64, q.nw), 0, s>>>(g, mask.quads, mask.same, div, p_in, p_out, t.nxt, t.nyt, q.zchunk, kb, ke, -1, MirrorArgs{});
+    return;
+  }
+  const Jacobi3dX2Plan p = jacobi3d_x2_plan(g, np, kb2 >= 0, from_zero, lay, cu_count());
   const dim3 grid((unsigned)p.G), block(64, Z2NW);
   MirrorArgs m{};
   if (p.serial) mirror = nullptr;                          // (jacobi3d_mirror_ok refuses such a launch: nothing asks for it)

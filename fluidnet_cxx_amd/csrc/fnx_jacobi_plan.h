@@ -127,6 +127,57 @@ inline Jacobi3dX2Plan jacobi3d_x2_plan(const GridDims& g, int np, bool two_range
   }
   return p;
 }
+// ---- the 64-column tiling of the two-sweep march (the kernel's X64): a workgroup is the ceil(W / 64) waves of one (row group, plane
+// chunk), which hand each other their edge columns through LDS instead of recomputing a two-column halo a side.
+constexpr int X64_MAXW = 8;                // waves a workgroup: W <= 512 (wider rows keep the 60-column tiles)
+enum { JACOBI3D_X_AUTO = 0, JACOBI3D_X_60 = 1, JACOBI3D_X_64 = 2 };   // the request: FnxGrid.ref_quirks bits 8-9 force a tiling (A/B timing, tests)
+inline int jacobi3d_x64_waves(const GridDims& g) { return (g.W + 63) / 64; }
+// whole workgroups resident at once: a compute unit holds Z2WPS * 4 waves of the march, i.e. floor(16 / nw) workgroups of nw waves
+// (5 of 3 waves, not 16 / 3: measured at 192^3, where the 64 workgroups that did not fit cost the pass 10 %)
+inline long jacobi3d_x64_slots(int nw, int cus) { return (long)(Z2WPS * 4 / nw) * cus; }
+// can the 64-column kernel run this launch at all?  Whole-domain passes of one plane range without a mirror, H % 4 == 0, at most
+// X64_MAXW waves a row, and every row group with a workgroup in one resident set.
+inline bool jacobi3d_x64_ok(const GridDims& g, int np, bool two_ranges, bool mirror, int cus) {
+  if (two_ranges || mirror || np != g.D || g.H % 4 != 0 || !jacobi3d_quad_ok(g)) return false;
+  const int nw = jacobi3d_x64_waves(g);
+  if (nw > X64_MAXW || !jacobi3d_offsets_fit(g, np)) return false;
+  return (long)(g.H / 4) * g.B <= jacobi3d_x64_slots(nw, cus);
+}
+// its launch: `nw` waves a workgroup, G workgroups (a multiple of 8), each marching `zchunk` planes of one row group; the chunk
+// count is what one resident set holds of the (fewer) waves.  Call only where jacobi3d_x64_ok.
+struct Jacobi3dX64Plan { int nw, zchunk; long long G; int lay; };
+inline Jacobi3dX64Plan jacobi3d_x64_plan(const GridDims& g, int np, bool from_zero, int lay, int cus) {
+  constexpr int zmin = 2;
+  Jacobi3dX64Plan p{};
+  p.nw = jacobi3d_x64_waves(g);
+  p.lay = from_zero ? lay & 2 : lay;
+  const long groups = (long)(g.H / 4) * g.B;
+  int nzc = (int)(jacobi3d_x64_slots(p.nw, cus) / groups);
+  if (nzc < 1) nzc = 1;
+  p.zchunk = (np + nzc - 1) / nzc;
+  if (p.zchunk < zmin) p.zchunk = zmin;
+  p.G = groups * ((np + p.zchunk - 1) / p.zchunk);
+  p.G = ((p.G + 7) / 8) * 8;
+  return p;
+}
+// THE rule: which tiling a two-sweep launch runs with.  Every wave of either launch is resident and marches its chunk plus two
+// lead-in steps, so a pass costs (waves x steps) wave-steps at a rate the tiling sets.  The hand-over (a barrier a step, one more
+// VALU instruction per obstacle-free row update) lowers that rate by 13 to 19 % (docs/history/r34_jacobi_x64.md), so the 64-column
+// tiling is taken where it issues at least X64_MARGIN_PCT per cent fewer wave-steps -- 256^3: 4096 x 18 against 3840 x 24, 20 %;
+// 128 wide: about 29 % -- and its chunks are at least X64_MIN_CHUNK planes: shorter ones are lead-in and launch latency (a tie).
+constexpr int X64_MARGIN_PCT = 19, X64_MIN_CHUNK = 8;
+inline bool jacobi3d_x64_pick(const GridDims& g, int np, bool two_ranges, bool mirror, int request, int cus) {
+  if (request == JACOBI3D_X_60 || !jacobi3d_x64_ok(g, np, two_ranges, mirror, cus)) return false;
+  if (request == JACOBI3D_X_64) return true;
+  const Jacobi3dX2Plan a = jacobi3d_x2_plan(g, np, false, false, 0, cus);
+  if (a.split) return false;                               // (the 60-column tiles overflow the wave slots, e.g. 2048 x 512: unmeasured, left alone)
+  const Jacobi3dX64Plan b = jacobi3d_x64_plan(g, np, false, 0, cus);
+  if (b.zchunk < X64_MIN_CHUNK) return false;
+  const long long w60 = jacobi3d_tiles(g).ntiles * ((np + a.zchunk - 1) / a.zchunk) * (a.zchunk + 2);
+  const long long w64 = (long long)(g.H / 4) * g.B * ((np + b.zchunk - 1) / b.zchunk) * b.nw * (b.zchunk + 2);
+  return w64 * 100 <= w60 * (100 - X64_MARGIN_PCT);
+}
+
 // may a two-sweep launch of these plane ranges mirror its output (launch_jacobi3d_x2's `mirror`)?  One resident set of waves, both
 // arrays in the same layout, not the from-zero pass
 inline bool jacobi3d_mirror_ok(const GridDims& g, int np, bool two_ranges, bool from_zero, int lay, int cus) {

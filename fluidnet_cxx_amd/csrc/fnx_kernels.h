@@ -157,7 +157,7 @@ struct JacobiMirror { float* out[2][2]; const unsigned* sel[2]; int k[2]; int n;
 // plans (jacobi3d_x2_plan) and launches: once, or once per plane range when the two (kb2 >= 0: [kb2, kb2 + ke - kb)) do not fit together
 void launch_jacobi3d_x2(const GridDims& g, const JacobiMaskLayout& mask, const float* div, const float* p_in, float* p_out,
                         hipStream_t s, int kb = 0, int ke = 0, bool from_zero = false, int kb2 = -1, int lay = 0,
-                        const JacobiMirror* mirror = nullptr);
+                        const JacobiMirror* mirror = nullptr, int x_request = 0);   // x_request: JACOBI3D_X_* (fnx_jacobi_plan.h)
 // Reproducible residual (no atomics): per sample b the squared differences of a[b*per_sample + first + q] - b[...] (b == null:
 // zeros), q < count, summed in a fixed order in fp64 through `partials` (residual_scratch_bytes(B)); sumsq (B floats, may be
 // null) receives the sums, res (1 float, may be null) max_b sqrt(sum)

@@ -48,11 +48,16 @@ enum { FNX_TYPE_NONE = 0, FNX_TYPE_FLUID = 1, FNX_TYPE_OBSTACLE = 2, FNX_TYPE_EM
 /* Advection methods, cpp/advect_type.cpp:5-16 ("eulerFluidNet", "maccormackFluidNet") */
 enum { FNX_ADVECT_EULER = 0, FNX_ADVECT_MACCORMACK = 1 };
 
+enum { FNX_JACOBI3D_X_SHIFT = 8, FNX_JACOBI3D_X_AUTO = 0, FNX_JACOBI3D_X_60 = 1, FNX_JACOBI3D_X_64 = 2 };   /* FnxGrid.ref_quirks bits 8-9 */
+
 typedef struct FnxGrid {
   int B, D, H, W;   /* batch, depth (1 for 2D), height, width */
   int is3D;         /* 0: U has 2 channels and D must be 1; 1: U has 3 channels */
-  int ref_quirks;   /* 3D only: 1 reproduces the reference's 3D defects bit-for-bit,
-                       0 (default) gives the intended 3D semantics.  Ignored in 2D. */
+  int ref_quirks;   /* 3D only.  Bit 0: 1 reproduces the reference's 3D defects bit-for-bit,
+                       0 (default) gives the intended 3D semantics.  Ignored in 2D.
+                       Bits 8-9 (FNX_JACOBI3D_X_*  << FNX_JACOBI3D_X_SHIFT; A/B timing and tests, the results are the same bits):
+                       the column tiling of the 3D two-sweep Jacobi march -- 0 the plan's choice, 1 the 60-column tiles,
+                       2 the 64-column tiles wherever that kernel can run. */
   /* z-slab decomposition (3D, multi-GPU): the arrays hold planes [z_offset, z_offset + D) of a domain that is
      D_global planes deep; only the domain-border test uses them.  0 / 0 = a whole domain (the default). */
   int z_offset, D_global;
