@@ -70,12 +70,14 @@ SCRATCH_FREE = {
                                 "two waves a SIMD; the tail and conv1 kernels keep their accumulators across the cell march; a spill puts "
                                 "scratch traffic between the MFMAs"),
     "fnx_advect.hip": (["advect3d_fwd_tile_kernel", "advect3d_bwd_tile_kernel", "advect3d_bwd_scalar_tile_kernel",
-                        "advect3d_bwd_vel_tile_kernel"],
+                        "advect3d_bwd_vel_tile_kernel", "box_minmax_kernel"],
                        "fnx_advect_march.h: the 3D advection marches run at 2-3 waves per SIMD with every VGPR in use; a reload from "
-                       "scratch is an s_waitcnt vmcnt(0) that also waits for the plane in flight and the stores"),
-    "fnx_scalars.hip": (["advect_scalars_fwd_kernel", "advect_scalars_box_kernel", "advect_scalars_bwd_kernel"],
-                        "one thread per cell with a chunk of four channels' interpolation corners in registers; scratch there would mean "
-                        "a per-channel array was indexed at run time, or the line trace's state was pushed out by the chunk"),
+                       "scratch is an s_waitcnt vmcnt(0) that also waits for the plane in flight and the stores.  The clamp-bounds "
+                       "reduction keeps three xy-reduced planes of eight rows in registers along its z-march; scratch there would mean "
+                       "a row array was indexed at run time"),
+    "fnx_scalars.hip": (["advect_scalars_fwd_kernel", "advect_scalars_bwd_kernel"],
+                        "one thread per cell with one channel's eight interpolation corners in registers at a time; scratch there would "
+                        "mean the corner array was indexed at run time, or the line trace's state was pushed out by the channel loop"),
     "fnx_pcg.hip": (["pcg_guess_kernel"],
                     "a streaming kernel like pcg_dir_apply_kernel: a cell's stencil, seven loads and three fp64 partial sums; scratch there "
                     "would mean the partial sums or the stencil were turned into arrays in memory"),

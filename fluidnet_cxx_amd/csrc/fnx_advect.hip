@@ -8,26 +8,11 @@
 //
 // Bit-parity: see fnx_device.h.  Compiled with -ffp-contract=off.
 #include "../../include/fluidnet_hip.h"
+#include "fnx_cells.h"
 #include "fnx_device.h"
 #include "fnx_kernels.h"
 
 namespace {
-
-constexpr int BX = 64, BY = 4;
-
-struct CellId { int b, k, j, i; bool valid; };
-
-template <bool IS3D>
-__device__ __forceinline__ CellId cell_id(const GridDims& g) {
-  CellId c;
-  c.i = blockIdx.x * BX + threadIdx.x;
-  c.j = blockIdx.y * BY + threadIdx.y;
-  const int bk = blockIdx.z;
-  c.b = IS3D ? bk / g.KN : bk;
-  c.k = IS3D ? g.K0 + (bk - c.b * g.KN) : 0;
-  c.valid = (c.i < g.W) & (c.j < g.H);
-  return c;
-}
 
 // ---------------------------------------------------------------------------------------------------
 // Scalar: one semi-Lagrangian pass (SemiLagrangeEulerFluidNet[SavePos], fluids_init.cpp:12-133).
@@ -78,14 +63,17 @@ __global__ __launch_bounds__(BX* BY) void sl_scalar_kernel(GridDims g, float dt,
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Clamp bounds of MacCormackClampFluidNet (:154-263) as a field: for every cell c the min / max of src over the
-// 3x3(x3) box around c, taken over the cells that are inside the (local) domain and -- unless sample_outside_fluid --
-// fluid.  The backward kernel then fetches ONE 8-byte pair at the traced cell instead of walking 27 cells x 2 fields
-// per thread.  min/max are exact, commutative and NaN-ignoring (v_min_f32 / v_max_f32 order -0 < +0), so the
-// separable evaluation gives the same bits as the reference's 27-step fold; "no cell qualified" (the reference then
-// keeps the forward value) is encoded as mn = NaN.
+// 3D clamp bounds of MacCormackClampFluidNet (:154-263) as a field: for every cell c of the compute window the min / max
+// of src over the 3x3x3 box around c, taken over the cells that are inside the (local) domain and -- unless
+// sample_outside_fluid -- fluid.  The backward kernel then fetches ONE 8-byte pair at the traced cell instead of walking
+// 27 cells x 2 fields per thread.  min/max are exact, commutative and NaN-ignoring (v_min_f32 / v_max_f32 order -0 < +0),
+// so the separable evaluation gives the same bits as the reference's 27-step fold; "no cell qualified" (the reference
+// then keeps the forward value) is encoded as mn = NaN.
+// src and box are B * C plane stacks (bc = b * C + c) over B samples of flags: the density is C = 1, the passive scalars
+// (fnx_scalars.hip) bring their channels.
 // A wave covers 62 columns (lanes 0 / 63 are halo columns) x BOX_R rows and marches along z: per plane it reduces
-// rows j0-1..j0+BOX_R in x (DPP) and y, and keeps the reduced planes k-1, k, k+1 in registers.
+// rows j0-1..j0+BOX_R in x (DPP) and y, and keeps the reduced planes k-1, k, k+1 in registers.  (2D: the 9 cells are
+// walked in the backward kernels, cheaper than a separate pass.)
 // ---------------------------------------------------------------------------------------------------
 constexpr int BOX_R = 8, BOX_ZC = 16;
 
@@ -98,8 +86,8 @@ __device__ __forceinline__ float dppf_right(float v) {    // lane+1
 __device__ __forceinline__ unsigned dppu_left(unsigned v) { return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, true); }
 __device__ __forceinline__ unsigned dppu_right(unsigned v) { return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x130, 0xf, 0xf, true); }
 
-template <bool IS3D, bool SAMPLE_OUTSIDE>
-__global__ __launch_bounds__(256) void box_minmax_kernel(GridDims g, const float* __restrict__ src,
+template <bool SAMPLE_OUTSIDE>
+__global__ __launch_bounds__(256) void box_minmax_kernel(GridDims g, int C, const float* __restrict__ src,
                                                          const float* __restrict__ flags, float2* __restrict__ box,
                                                          int nzc) {
   const int lane = threadIdx.x;
@@ -107,22 +95,22 @@ __global__ __launch_bounds__(256) void box_minmax_kernel(GridDims g, const float
   const int x = blockIdx.x * 62 - 1 + lane;
   const int j0 = (blockIdx.y * 4 + w) * BOX_R;
   const int bz = blockIdx.z;
-  const int zc = bz % nzc, b = bz / nzc;
+  const int zc = bz % nzc, bc = bz / nzc;                 // bc: plane stack b * C + c of src and box
   const int k_lo = g.K0 + zc * BOX_ZC, k_hi = min(k_lo + BOX_ZC, g.K0 + g.KN);      // planes of the compute window
   if (j0 >= g.H) return;
   const bool xin = (x >= 0) & (x < g.W);
   const int xc = clampi(x, 0, g.W - 1);
-  const size_t base = (size_t)b * g.DHW;
+  const size_t base = (size_t)bc * g.DHW, fbase = (size_t)(bc / C) * g.DHW;
   // all loads of a plane are unconditional (clamped rows / planes) so they issue back to back; validity only gates `ok`
   auto plane = [&](int k, float* omn, float* omx, unsigned* oan) {
     float sv[BOX_R + 2], fv[BOX_R + 2];
     const bool kin = (k >= 0) & (k < g.D);                           // the reference's box is clipped to the grid
-    const size_t ok_ = base + (size_t)clampi(k, 0, g.D - 1) * g.HW + xc;
+    const size_t ok_ = (size_t)clampi(k, 0, g.D - 1) * g.HW + xc;
 #pragma unroll
     for (int rr = 0; rr < BOX_R + 2; ++rr) {
       const size_t o = ok_ + (size_t)clampi(j0 - 1 + rr, 0, g.H - 1) * g.W;
-      sv[rr] = src[o];
-      fv[rr] = SAMPLE_OUTSIDE ? FNX_FLUID : flags[o];
+      sv[rr] = src[base + o];
+      fv[rr] = SAMPLE_OUTSIDE ? FNX_FLUID : flags[fbase + o];
     }
     float rmn[BOX_R + 2], rmx[BOX_R + 2]; unsigned ran[BOX_R + 2];
 #pragma unroll
@@ -143,25 +131,18 @@ __global__ __launch_bounds__(256) void box_minmax_kernel(GridDims g, const float
     }
   };
   const bool lane_out = (lane >= 1) & (lane <= 62) & xin;
-  auto store = [&](int k, int r, float lo, float hi, bool any) {
-    if (lane_out && j0 + r < g.H)
-      box[base + (size_t)k * g.HW + (size_t)(j0 + r) * g.W + x] = make_float2(any ? lo : __builtin_nanf(""), hi);
-  };
   float mn[3][BOX_R], mx[3][BOX_R]; unsigned an[3][BOX_R];           // xy-reduced planes k-1, k, k+1
-  if (!IS3D) {
-    plane(0, mn[0], mx[0], an[0]);
-#pragma unroll
-    for (int r = 0; r < BOX_R; ++r) store(0, r, mn[0][r], mx[0][r], an[0][r] != 0);
-    return;
-  }
   plane(k_lo - 1, mn[0], mx[0], an[0]);
   plane(k_lo, mn[1], mx[1], an[1]);
   for (int k = k_lo; k < k_hi; ++k) {
     plane(k + 1, mn[2], mx[2], an[2]);
 #pragma unroll
-    for (int r = 0; r < BOX_R; ++r)
-      store(k, r, fminf(fminf(mn[0][r], mn[1][r]), mn[2][r]), fmaxf(fmaxf(mx[0][r], mx[1][r]), mx[2][r]),
-            (an[0][r] | an[1][r] | an[2][r]) != 0);
+    for (int r = 0; r < BOX_R; ++r) {
+      const bool any = (an[0][r] | an[1][r] | an[2][r]) != 0;
+      const float lo = fminf(fminf(mn[0][r], mn[1][r]), mn[2][r]), hi = fmaxf(fmaxf(mx[0][r], mx[1][r]), mx[2][r]);
+      if (lane_out && j0 + r < g.H)
+        box[base + (size_t)k * g.HW + (size_t)(j0 + r) * g.W + x] = make_float2(any ? lo : __builtin_nanf(""), hi);
+    }
 #pragma unroll
     for (int r = 0; r < BOX_R; ++r) {
       mn[0][r] = mn[1][r]; mx[0][r] = mx[1][r]; an[0][r] = an[1][r];
@@ -591,9 +572,7 @@ __global__ __launch_bounds__(BX* BY) void advect_bwd_kernel(GridDims g, float dt
 #include "fnx_advect_march.h"
 #include "fnx_advect_tile2d.h"
 
-inline dim3 cell_grid(const GridDims& g) { return dim3((g.W + BX - 1) / BX, (g.H + BY - 1) / BY, g.B * g.KN); }
-
-// the same grid with the compute window widened by `by` planes (clipped to the array)
+// the grid with the compute window widened by `by` planes (clipped to the array)
 inline GridDims widened(GridDims d, int by) {
   const int a = d.K0 - by < 0 ? 0 : d.K0 - by, b = d.K0 + d.KN + by > d.D ? d.D : d.K0 + d.KN + by;
   d.K0 = a; d.KN = b - a;
@@ -622,17 +601,13 @@ void tile_launch_geometry(const GridDims& g, int& ntx, int& nty, int& zchunk, un
 }
 
 // The one dispatch of run-time choices to template arguments: `k` is a generic lambda that receives IS3D, QUIRKS, SAMPLE_OUTSIDE
-// and WHAT as AIC<> constants
-template <class K> void with_flag(bool b, K k) { if (b) k(AIC<1>{}); else k(AIC<0>{}); }
+// and WHAT as IC<> constants (fnx_cells.h)
 template <class K> void with_what(int what, K k) {
-  if (what == fnx::ADVECT_BOTH) k(AIC<fnx::ADVECT_BOTH>{}); else if (what == fnx::ADVECT_RHO) k(AIC<fnx::ADVECT_RHO>{}); else k(AIC<fnx::ADVECT_VEL>{});
+  if (what == fnx::ADVECT_BOTH) k(IC<fnx::ADVECT_BOTH>{}); else if (what == fnx::ADVECT_RHO) k(IC<fnx::ADVECT_RHO>{}); else k(IC<fnx::ADVECT_VEL>{});
 }
 template <class K> void dispatch(const fnx::AdvectPlan& p, bool sample_outside, K k) {
-  with_flag(p.is3d, [&](auto is3d) {
-    with_flag(p.quirks, [&](auto quirks) {
-      if constexpr (decltype(is3d)::value || !decltype(quirks)::value)          // quirks mode exists in 3D only
-        with_flag(sample_outside, [&](auto outside) { with_what(p.what, [&](auto what) { k(is3d, quirks, outside, what); }); });
-    });
+  with_semantics(p.is3d, p.quirks, sample_outside, [&](auto is3d, auto quirks, auto outside) {
+    with_what(p.what, [&](auto what) { k(is3d, quirks, outside, what); });
   });
 }
 
@@ -695,6 +670,15 @@ AdvectWs advect_workspace(const GridDims& g, bool is3d, int what, void* base) {
   return w;
 }
 
+void launch_box_minmax(const GridDims& g, int channels, bool sample_outside, const float* src, const float* flags, float2* box,
+                       hipStream_t s) {
+  const int nzc = (g.KN + BOX_ZC - 1) / BOX_ZC;
+  const dim3 grid((g.W + 61) / 62, (g.H + 4 * BOX_R - 1) / (4 * BOX_R), g.B * channels * nzc);
+  with_flag(sample_outside, [&](auto outside) {
+    box_minmax_kernel<decltype(outside)::value><<<grid, dim3(64, 4), 0, s>>>(g, channels, src, flags, box, nzc);
+  });
+}
+
 // MacCormack: forward pass(es) on p.gfwd into the workspace, backward pass fused with the correction and the clamp on p.g into dst;
 // the density and the velocity of a pair both by the OLD U (simulate.py:75-93).  Euler: the forward pass into dst.
 void launch_advect(const AdvectPlan& p, const AdvectArgs& a, const AdvectWs& w, hipStream_t s) {
@@ -727,11 +711,8 @@ void launch_advect(const AdvectPlan& p, const AdvectArgs& a, const AdvectWs& w, 
       if (p.cells_pair) advect_fwd_kernel<IS3D, Q, SO><<<cell_grid(gf), block, 0, s>>>(gf, dt, a.rho, a.U, a.flags, rho_fwd, w.cell, U_fwd);
       if (!p.cells_pair && do_s) sl_scalar_kernel<IS3D, Q, SO><<<cell_grid(gf), block, 0, s>>>(gf, dt, a.rho, a.U, a.flags, rho_fwd, w.cell);
       if (!p.cells_pair && do_v) sl_mac_kernel<IS3D, Q><<<cell_grid(gf), block, 0, s>>>(gf, dt, a.orig, a.U, a.flags, U_fwd);
-      if (mac && do_s && p.is3d) {                       // the clamp bounds of the density step as a field
-        const int nzc = (gf.KN + BOX_ZC - 1) / BOX_ZC;
-        const dim3 grid((gf.W + 61) / 62, (gf.H + 4 * BOX_R - 1) / (4 * BOX_R), gf.B * nzc);
-        box_minmax_kernel<IS3D, SO><<<grid, dim3(64, 4), 0, s>>>(gf, a.rho, a.flags, w.box, nzc);
-      }
+      if constexpr (IS3D)                                // the clamp bounds of the density step as a field
+        if (mac && do_s) launch_box_minmax(gf, 1, SO, a.rho, a.flags, w.box, s);
     }
     if (!mac) return;
     // ---- backward, correction and clamp

@@ -50,7 +50,6 @@ typedef __attribute__((address_space(3))) void* ALds;
 __device__ __forceinline__ ABuf amake_rsrc(const void* p, unsigned bytes) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, (int)bytes, 0x00020000);
 }
-template <int N> struct AIC { static constexpr int value = N; };
 
 // lerp_setup (fnx_device.h) for a position whose base cell lands on {c-1, c} per axis, c = (i, j, kg) given as floats.
 // With p' = p - 0.5 >= 0:  s1 = p' - (float)(int)p' is exactly fract(p') (the subtraction is exact, and so is v_fract for a

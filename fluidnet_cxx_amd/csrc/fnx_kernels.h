@@ -44,6 +44,10 @@ struct AdvectArgs {
   float *rho_dst, *U_dst;
 };
 void launch_advect(const AdvectPlan& p, const AdvectArgs& a, const AdvectWs& ws, hipStream_t s);
+// the 3D clamp bounds of the planes [K0, K0 + KN) of `channels` fields per sample (src, box: B * channels plane stacks; flags: B), the
+// reduction both launch_advect (channels = 1) and launch_advect_scalars run; its grid's z extent is B * channels * ceil(KN / 16)
+void launch_box_minmax(const GridDims& g, int channels, bool sample_outside, const float* src, const float* flags, float2* box,
+                       hipStream_t s);
 
 // passive scalars (fnx_scalars.hip): `channels` fields (B, C, D, H, W) through one pair of line traces, one thread per cell, whole
 // single domains only.  Workspace of a MacCormack call: the C forward fields, the traced cell, in 3D the C clamp-bounds fields; each

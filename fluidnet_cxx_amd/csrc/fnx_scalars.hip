@@ -5,40 +5,23 @@
 // and dt alone.  Here a thread does that once per pass and pushes every channel through the same sample points.  The per-channel
 // arithmetic is, operand for operand and parenthesis for parenthesis, that of interpol / interpol_with_fluid (fnx_device.h) and of
 // sl_scalar_cell / sl_scalar_bwd_clamp_cell (fnx_advect.hip): every channel comes out with the bits fnx_advect_scalar gives for it
-// alone.  One thread per cell, x fastest; whole single domains only (the C ABI refuses compute windows and z-slab views).
+// alone.  One thread per cell, x fastest (fnx_cells.h); whole single domains only (the C ABI refuses compute windows and z-slab views).
 //
-// Channels go in compile-time chunks of CHUNK (a remainder chunk of 1..CHUNK-1 behind it): per-channel values live in arrays indexed by
-// unrolled loops only, and a chunk's corner loads are all written ahead of the first use.
+// Channels go one at a time.  Measured on a developed plume against compile-time chunks of 2 and 4 channels: a chunk of 4
+// holds 32 corner values and costs the 3D kernels half of their waves (106-133 VGPRs, 3-4 waves per SIMD, against 42-58 and 8), and the
+// line trace -- a chain of dependent flag loads -- lives on occupancy: one channel at a time was the fastest at every size but one
+// (128^3, C = 8: 2 was 4 % ahead).
 //
-// MacCormack is a forward launch, in 3D a launch that reduces every channel's clamp bounds to a field, and a backward launch.
+// MacCormack is a forward launch, in 3D a launch that reduces every channel's clamp bounds to a field (box_minmax_kernel of
+// fnx_advect.hip over the B * C plane stacks), and a backward launch.
 //
 // Bit-parity: see fnx_device.h.  Compiled with -ffp-contract=off.  No atomics.
 #include "../../include/fluidnet_hip.h"
+#include "fnx_cells.h"
 #include "fnx_device.h"
 #include "fnx_kernels.h"
 
 namespace {
-
-constexpr int BX = 64, BY = 4;
-// Channels per chunk.  Measured on a developed plume with 1, 2 and 4: a chunk of 4 holds 32 corner values and costs the
-// 3D kernels half of their waves (106-133 VGPRs, 3-4 waves per SIMD, against 42-58 and 8), and the line trace -- a chain of
-// dependent flag loads -- lives on occupancy: one channel at a time was the fastest at every size but one (128^3, C = 8: 2 was 4 %
-// ahead).  The chunk code below is written for any CHUNK <= 4.
-constexpr int CHUNK = 1;
-
-struct CellId { int b, k, j, i; bool valid; };
-
-template <bool IS3D>
-__device__ __forceinline__ CellId cell_id(const GridDims& g) {
-  CellId c;
-  c.i = blockIdx.x * BX + threadIdx.x;
-  c.j = blockIdx.y * BY + threadIdx.y;
-  const int bk = blockIdx.z;
-  c.b = IS3D ? bk / g.D : bk;
-  c.k = IS3D ? bk - c.b * g.D : 0;
-  c.valid = (c.i < g.W) & (c.j < g.H);
-  return c;
-}
 
 // What a sample at one traced position needs besides the field: weights, the offset of corner a and the corners' fluid bits
 // (bit 0..7 = a b c d e f g h of interpol_with_fluid: a = (x0,y0), b = (x0,y0+1), c = (x0+1,y0), d = (x0+1,y0+1), e..h one plane up)
@@ -114,23 +97,6 @@ __device__ __forceinline__ void trace(const GridDims& g, const Field& fu, const 
 // ---------------------------------------------------------------------------------------------------
 // Forward pass: border -> 0, non-fluid -> copy, fluid -> the sample at the traced position
 // ---------------------------------------------------------------------------------------------------
-template <bool IS3D, bool SAMPLE_OUTSIDE, int N>
-__device__ __forceinline__ void fwd_chunk(const GridDims& g, const float* __restrict__ s, float* __restrict__ d, int o, const Recipe& r,
-                                          bool border, bool fluid) {
-  float I[N][8], own[N];
-#pragma unroll
-  for (int n = 0; n < N; ++n) {
-    const float* sn = s + (size_t)n * g.DHW;
-    load_corners<IS3D>(g, sn + r.o, I[n]);
-    own[n] = sn[o];
-  }
-#pragma unroll
-  for (int n = 0; n < N; ++n) {
-    const float smp = sample<IS3D, SAMPLE_OUTSIDE>(r.L, r.fl, I[n]);
-    d[(size_t)n * g.DHW + o] = border ? 0.f : (fluid ? smp : own[n]);      // "don't advect solid geometry"
-  }
-}
-
 template <bool IS3D, bool QUIRKS, bool SAMPLE_OUTSIDE>
 __global__ __launch_bounds__(BX* BY) void advect_scalars_fwd_kernel(GridDims g, float dt, int C, const float* __restrict__ src,
                                                                     const float* __restrict__ U, const float* __restrict__ flags,
@@ -153,135 +119,47 @@ __global__ __launch_bounds__(BX* BY) void advect_scalars_fwd_kernel(GridDims g, 
   const Recipe r = make_recipe<IS3D, QUIRKS, SAMPLE_OUTSIDE>(g, ff, p);
   const float* s = src + (size_t)c.b * C * g.DHW;
   float* d = dst + (size_t)c.b * C * g.DHW;
-  int ch = 0;
-  for (; ch + CHUNK <= C; ch += CHUNK)
-    fwd_chunk<IS3D, SAMPLE_OUTSIDE, CHUNK>(g, s + (size_t)ch * g.DHW, d + (size_t)ch * g.DHW, o, r, border, fluid);
-  s += (size_t)ch * g.DHW; d += (size_t)ch * g.DHW;
-  const int rem = C - ch;                               // < CHUNK
-  if constexpr (CHUNK > 3) if (rem == 3) fwd_chunk<IS3D, SAMPLE_OUTSIDE, 3>(g, s, d, o, r, border, fluid);
-  if constexpr (CHUNK > 2) if (rem == 2) fwd_chunk<IS3D, SAMPLE_OUTSIDE, 2>(g, s, d, o, r, border, fluid);
-  if constexpr (CHUNK > 1) if (rem == 1) fwd_chunk<IS3D, SAMPLE_OUTSIDE, 1>(g, s, d, o, r, border, fluid);
-}
-
-// ---------------------------------------------------------------------------------------------------
-// 3D clamp bounds as a field per channel, the reduction of box_minmax_kernel (fnx_advect.hip) over the B * C planes stacks: for every
-// cell the min / max of its channel over the 3x3x3 box clipped to the grid, taken over the cells that are fluid (unless
-// sample_outside_fluid); "no cell qualified" is mn = NaN.  min / max are exact, commutative and NaN-ignoring, so the separable
-// evaluation gives the bits of the reference's 27-step fold.  A wave covers 62 columns (lanes 0 / 63 are halo columns) x BOX_R rows and
-// marches along z with the xy-reduced planes k-1, k, k+1 in registers.  The backward kernel then fetches ONE 8-byte pair per channel
-// at the traced cell: walking the 27 cells per channel there instead took 2152 against 1238 us for four channels at 256^3.
-// ---------------------------------------------------------------------------------------------------
-constexpr int BOX_R = 8, BOX_ZC = 16;
-
-__device__ __forceinline__ float dppf_left(float v) {     // lane-1 (0.0 into lane 0: a halo lane, never stored)
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x138, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float dppf_right(float v) {    // lane+1
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x130, 0xf, 0xf, true));
-}
-__device__ __forceinline__ unsigned dppu_left(unsigned v) { return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, true); }
-__device__ __forceinline__ unsigned dppu_right(unsigned v) { return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x130, 0xf, 0xf, true); }
-
-template <bool SAMPLE_OUTSIDE>
-__global__ __launch_bounds__(256) void advect_scalars_box_kernel(GridDims g, int C, const float* __restrict__ src,
-                                                                 const float* __restrict__ flags, float2* __restrict__ box, int nzc) {
-  const int lane = threadIdx.x;
-  const int w = __builtin_amdgcn_readfirstlane(threadIdx.y);
-  const int x = blockIdx.x * 62 - 1 + lane;
-  const int j0 = (blockIdx.y * 4 + w) * BOX_R;
-  const int bz = blockIdx.z;
-  const int zc = bz % nzc, bc = bz / nzc;                 // bc: plane stack b * C + c of src and box
-  const int k_lo = zc * BOX_ZC, k_hi = min(k_lo + BOX_ZC, g.D);
-  if (j0 >= g.H) return;
-  const bool xin = (x >= 0) & (x < g.W);
-  const int xc = clampi(x, 0, g.W - 1);
-  const size_t base = (size_t)bc * g.DHW, fbase = (size_t)(bc / C) * g.DHW;
-  // all loads of a plane are unconditional (clamped rows / planes) so they issue back to back; validity only gates `ok`
-  auto plane = [&](int k, float* omn, float* omx, unsigned* oan) {
-    float sv[BOX_R + 2], fv[BOX_R + 2];
-    const bool kin = (k >= 0) & (k < g.D);
-    const size_t ok_ = (size_t)clampi(k, 0, g.D - 1) * g.HW + xc;
-#pragma unroll
-    for (int rr = 0; rr < BOX_R + 2; ++rr) {
-      const size_t o = ok_ + (size_t)clampi(j0 - 1 + rr, 0, g.H - 1) * g.W;
-      sv[rr] = src[base + o];
-      fv[rr] = SAMPLE_OUTSIDE ? FNX_FLUID : flags[fbase + o];
-    }
-    float rmn[BOX_R + 2], rmx[BOX_R + 2]; unsigned ran[BOX_R + 2];
-#pragma unroll
-    for (int rr = 0; rr < BOX_R + 2; ++rr) {
-      const int j = j0 - 1 + rr;
-      const bool ok = xin & kin & (j >= 0) & (j < g.H) & (fv[rr] == FNX_FLUID);
-      const float vmn = ok ? sv[rr] : INFINITY, vmx = ok ? sv[rr] : -INFINITY;
-      const unsigned va = ok ? 1u : 0u;
-      rmn[rr] = fminf(fminf(dppf_left(vmn), vmn), dppf_right(vmn));
-      rmx[rr] = fmaxf(fmaxf(dppf_left(vmx), vmx), dppf_right(vmx));
-      ran[rr] = dppu_left(va) | va | dppu_right(va);
-    }
-#pragma unroll
-    for (int r = 0; r < BOX_R; ++r) {
-      omn[r] = fminf(fminf(rmn[r], rmn[r + 1]), rmn[r + 2]);
-      omx[r] = fmaxf(fmaxf(rmx[r], rmx[r + 1]), rmx[r + 2]);
-      oan[r] = ran[r] | ran[r + 1] | ran[r + 2];
-    }
-  };
-  const bool lane_out = (lane >= 1) & (lane <= 62) & xin;
-  float mn[3][BOX_R], mx[3][BOX_R]; unsigned an[3][BOX_R];           // xy-reduced planes k-1, k, k+1
-  plane(k_lo - 1, mn[0], mx[0], an[0]);
-  plane(k_lo, mn[1], mx[1], an[1]);
-  for (int k = k_lo; k < k_hi; ++k) {
-    plane(k + 1, mn[2], mx[2], an[2]);
-#pragma unroll
-    for (int r = 0; r < BOX_R; ++r) {
-      const bool any = (an[0][r] | an[1][r] | an[2][r]) != 0;
-      const float lo = fminf(fminf(mn[0][r], mn[1][r]), mn[2][r]), hi = fmaxf(fmaxf(mx[0][r], mx[1][r]), mx[2][r]);
-      if (lane_out && j0 + r < g.H)
-        box[base + (size_t)k * g.HW + (size_t)(j0 + r) * g.W + x] = make_float2(any ? lo : __builtin_nanf(""), hi);
-    }
-#pragma unroll
-    for (int r = 0; r < BOX_R; ++r) {
-      mn[0][r] = mn[1][r]; mx[0][r] = mx[1][r]; an[0][r] = an[1][r];
-      mn[1][r] = mn[2][r]; mx[1][r] = mx[2][r]; an[1][r] = an[2][r];
-    }
+  for (int ch = 0; ch < C; ++ch) {
+    const float* sc = s + (size_t)ch * g.DHW;
+    float I[8];
+    load_corners<IS3D>(g, sc + r.o, I);
+    const float own = sc[o];
+    const float smp = sample<IS3D, SAMPLE_OUTSIDE>(r.L, r.fl, I);
+    d[(size_t)ch * g.DHW + o] = border ? 0.f : (fluid ? smp : own);      // "don't advect solid geometry"
   }
 }
 
 // ---------------------------------------------------------------------------------------------------
 // Backward pass on fwd + MacCormackCorrect + MacCormackClampFluidNet (sl_scalar_bwd_clamp_cell).  The clamp neighbourhood is the
-// 3x3(x3) box around the traced cell of the forward pass.  3D: the channel's bounds are in `box` (above).  2D: which of the 9 cells
-// count (in the domain and, unless sample_outside_fluid, fluid) is one bit mask per thread, `m` (bit (dj+1)*3 + (di+1)); the channels
-// walk the box with clamped addresses in the reference's order.
+// 3x3(x3) box around the traced cell of the forward pass.  3D: the channel's bounds are in `box`, ONE 8-byte pair per channel at the
+// traced cell (walking the 27 cells per channel here instead took 2152 against 1238 us for four channels at 256^3).
+// 2D: which of the 9 cells count (in the domain and, unless sample_outside_fluid, fluid) is one bit mask per thread, `m` (bit
+// (dj+1)*3 + (di+1)); the channels walk the box with clamped addresses in the reference's order.
 // ---------------------------------------------------------------------------------------------------
 struct Box { int j0, i0; unsigned m; int cell; };        // 2D: j0, i0, m;  3D: cell = the offset of the traced cell in its plane stack
 
-template <bool IS3D, bool SAMPLE_OUTSIDE, int N>
-__device__ __forceinline__ void bwd_chunk(const GridDims& g, float half_s, const float* __restrict__ s, const float* __restrict__ fw,
-                                          const float2* __restrict__ box, float* __restrict__ d, int o, const Recipe& r, bool border,
-                                          bool fluid, const Box& bx) {
-  float I[N][8], own[N], f[N];
-  float2 bb[N];
-#pragma unroll
-  for (int n = 0; n < N; ++n) {
-    load_corners<IS3D>(g, fw + (size_t)n * g.DHW + r.o, I[n]);
-    own[n] = s[(size_t)n * g.DHW + o];
-    f[n] = fw[(size_t)n * g.DHW + o];
-    if (IS3D) bb[n] = box[(size_t)n * g.DHW + bx.cell];
-  }
-  float dd[N];
-#pragma unroll
-  for (int n = 0; n < N; ++n) {
-    const float bwd = border ? 0.f : sample<IS3D, SAMPLE_OUTSIDE>(r.L, r.fl, I[n]);
-    dd[n] = fluid ? f[n] + half_s * (own[n] - bwd) : f[n];          // applied on border cells too (reference :371)
-  }
+// one channel: s, fw, box, d are its plane stacks
+template <bool IS3D, bool SAMPLE_OUTSIDE>
+__device__ __forceinline__ void bwd_channel(const GridDims& g, float half_s, const float* __restrict__ s, const float* __restrict__ fw,
+                                            const float2* __restrict__ box, float* __restrict__ d, int o, const Recipe& r, bool border,
+                                            bool fluid, const Box& bx) {
+  float I[8];
+  load_corners<IS3D>(g, fw + r.o, I);
+  const float own = s[o], f = fw[o];
+  float2 bb;
+  // The bounds load goes out with the corner loads.  Left to itself hipcc sinks it under `!border` below, behind the sample's arithmetic:
+  // measured 5 to 7 % slower for C >= 2 at 128^3 and 256^3 (docs/history/r35_one_cell_idiom.md).  The empty asm pins it here.
+  if (IS3D) { bb = box[bx.cell]; asm volatile("" : "+v"(bb.x), "+v"(bb.y)); }
+  const float smp = sample<IS3D, SAMPLE_OUTSIDE>(r.L, r.fl, I);      // not under the select: the corner loads stay unconditional
+  const float bwd = border ? 0.f : smp;
+  float dd = fluid ? f + half_s * (own - bwd) : f;       // applied on border cells too (reference :371)
   if (!border) {
-    float mn[N], mx[N];
-    bool any[N];
+    float mn, mx;
+    bool any;
     if (IS3D) {
-#pragma unroll
-      for (int n = 0; n < N; ++n) { mn[n] = bb[n].x; mx[n] = bb[n].y; any[n] = !(mn[n] != mn[n]); }
+      mn = bb.x; mx = bb.y; any = !(mn != mn);
     } else {
-#pragma unroll
-      for (int n = 0; n < N; ++n) { mn[n] = INFINITY; mx[n] = -INFINITY; any[n] = bx.m != 0; }
+      mn = INFINITY; mx = -INFINITY; any = bx.m != 0;
 #pragma unroll
       for (int dj = -1; dj <= 1; ++dj) {
         const int jc = clampi(bx.j0 + dj, 0, g.H - 1);
@@ -289,20 +167,15 @@ __device__ __forceinline__ void bwd_chunk(const GridDims& g, float half_s, const
         for (int di = -1; di <= 1; ++di) {
           const int q = jc * g.W + clampi(bx.i0 + di, 0, g.W - 1);
           const bool ok = ((bx.m >> ((dj + 1) * 3 + (di + 1))) & 1u) != 0;
-#pragma unroll
-          for (int n = 0; n < N; ++n) {
-            const float v = s[(size_t)n * g.DHW + q];
-            mn[n] = ok ? fminf(mn[n], v) : mn[n];
-            mx[n] = ok ? fmaxf(mx[n], v) : mx[n];
-          }
+          const float v = s[q];
+          mn = ok ? fminf(mn, v) : mn;
+          mx = ok ? fmaxf(mx, v) : mx;
         }
       }
     }
-#pragma unroll
-    for (int n = 0; n < N; ++n) dd[n] = any[n] ? fmaxf(mn[n], fminf(mx[n], dd[n])) : f[n];        // no cell qualified: the forward value
+    dd = any ? fmaxf(mn, fminf(mx, dd)) : f;             // no cell qualified: the forward value
   }
-#pragma unroll
-  for (int n = 0; n < N; ++n) d[(size_t)n * g.DHW + o] = dd[n];
+  d[o] = dd;
 }
 
 template <bool IS3D, bool QUIRKS, bool SAMPLE_OUTSIDE>
@@ -350,22 +223,13 @@ __global__ __launch_bounds__(BX* BY) void advect_scalars_bwd_kernel(GridDims g, 
   const float* fw = fwd + (size_t)c.b * C * g.DHW;
   const float2* bp = IS3D ? box + (size_t)c.b * C * g.DHW : nullptr;
   float* d = dst + (size_t)c.b * C * g.DHW;
-  int ch = 0;
-  for (; ch + CHUNK <= C; ch += CHUNK)
-    bwd_chunk<IS3D, SAMPLE_OUTSIDE, CHUNK>(g, half_s, s + (size_t)ch * g.DHW, fw + (size_t)ch * g.DHW, bp + (size_t)ch * g.DHW,
-                                           d + (size_t)ch * g.DHW, o, r, border, fluid, bx);
-  s += (size_t)ch * g.DHW; fw += (size_t)ch * g.DHW; bp += (size_t)ch * g.DHW; d += (size_t)ch * g.DHW;
-  const int rem = C - ch;                               // < CHUNK
-  if constexpr (CHUNK > 3) if (rem == 3) bwd_chunk<IS3D, SAMPLE_OUTSIDE, 3>(g, half_s, s, fw, bp, d, o, r, border, fluid, bx);
-  if constexpr (CHUNK > 2) if (rem == 2) bwd_chunk<IS3D, SAMPLE_OUTSIDE, 2>(g, half_s, s, fw, bp, d, o, r, border, fluid, bx);
-  if constexpr (CHUNK > 1) if (rem == 1) bwd_chunk<IS3D, SAMPLE_OUTSIDE, 1>(g, half_s, s, fw, bp, d, o, r, border, fluid, bx);
+  for (int ch = 0; ch < C; ++ch) {
+    const size_t co = (size_t)ch * g.DHW;                // the channel's plane stack
+    bwd_channel<IS3D, SAMPLE_OUTSIDE>(g, half_s, s + co, fw + co, bp + co, d + co, o, r, border, fluid, bx);
+  }
 }
 
 inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// run-time choices -> template arguments (quirks mode exists in 3D only, the rule of fnx_advect.hip)
-template <int V> struct IC { static constexpr int value = V; };
-template <class K> void with_flag(bool b, K k) { if (b) k(IC<1>{}); else k(IC<0>{}); }
 
 }  // namespace
 
@@ -384,25 +248,16 @@ AdvectScalarsWs advect_scalars_workspace(const GridDims& g, bool is3d, int chann
 void launch_advect_scalars(const GridDims& g, bool is3d, bool quirks, bool maccormack, bool sample_outside, float dt, float half_s,
                            int channels, const float* src, const float* U, const float* flags, float* dst, const AdvectScalarsWs& w,
                            hipStream_t s) {
-  const dim3 block(BX, BY), grid((g.W + BX - 1) / BX, (g.H + BY - 1) / BY, g.B * g.D);
-  with_flag(is3d, [&](auto is3d_) {
-    with_flag(is3d && quirks, [&](auto quirks_) {
-      if constexpr (decltype(is3d_)::value || !decltype(quirks_)::value)
-        with_flag(sample_outside, [&](auto outside_) {
-          constexpr bool IS3D = decltype(is3d_)::value, Q = decltype(quirks_)::value, SO = decltype(outside_)::value;
-          if (!maccormack) {                             // Euler: the forward pass straight into dst
-            advect_scalars_fwd_kernel<IS3D, Q, SO><<<grid, block, 0, s>>>(g, dt, channels, src, U, flags, dst, nullptr);
-            return;
-          }
-          advect_scalars_fwd_kernel<IS3D, Q, SO><<<grid, block, 0, s>>>(g, dt, channels, src, U, flags, w.fwd, w.cell);
-          if constexpr (IS3D) {                          // the clamp bounds of every channel as a field
-            const int nzc = (g.D + BOX_ZC - 1) / BOX_ZC;
-            const dim3 bgrid((g.W + 61) / 62, (g.H + 4 * BOX_R - 1) / (4 * BOX_R), g.B * channels * nzc);
-            advect_scalars_box_kernel<SO><<<bgrid, dim3(64, 4), 0, s>>>(g, channels, src, flags, w.box, nzc);
-          }
-          advect_scalars_bwd_kernel<IS3D, Q, SO><<<grid, block, 0, s>>>(g, dt, half_s, channels, src, w.fwd, w.cell, U, flags, w.box, dst);
-        });
-    });
+  const dim3 block(BX, BY), grid = cell_grid(g);
+  with_semantics(is3d, quirks, sample_outside, [&](auto is3d_, auto quirks_, auto outside_) {
+    constexpr bool IS3D = decltype(is3d_)::value, Q = decltype(quirks_)::value, SO = decltype(outside_)::value;
+    if (!maccormack) {                                   // Euler: the forward pass straight into dst
+      advect_scalars_fwd_kernel<IS3D, Q, SO><<<grid, block, 0, s>>>(g, dt, channels, src, U, flags, dst, nullptr);
+      return;
+    }
+    advect_scalars_fwd_kernel<IS3D, Q, SO><<<grid, block, 0, s>>>(g, dt, channels, src, U, flags, w.fwd, w.cell);
+    if constexpr (IS3D) launch_box_minmax(g, channels, SO, src, flags, w.box, s);      // the clamp bounds of every channel as a field
+    advect_scalars_bwd_kernel<IS3D, Q, SO><<<grid, block, 0, s>>>(g, dt, half_s, channels, src, w.fwd, w.cell, U, flags, w.box, dst);
   });
 }
 

@@ -5,28 +5,11 @@
 // 64x4 blocks so each wave reads/writes 256 contiguous bytes per field row; the +-1 neighbours in x come
 // out of the same cache lines, the +-1 rows out of L1/L2.  The reference implements these as 29-92 ATen
 // ops each.
+#include "fnx_cells.h"
 #include "fnx_device.h"
 #include "fnx_kernels.h"
 
 namespace {
-
-constexpr int BX = 64, BY = 4;
-
-struct CellId { int b, k, j, i; bool valid; };
-
-template <bool IS3D>
-__device__ __forceinline__ CellId cell_id(const GridDims& g) {
-  CellId c;
-  c.i = blockIdx.x * BX + threadIdx.x;
-  c.j = blockIdx.y * BY + threadIdx.y;
-  const int bk = blockIdx.z;
-  c.b = IS3D ? bk / g.KN : bk;
-  c.k = IS3D ? g.K0 + (bk - c.b * g.KN) : 0;
-  c.valid = (c.i < g.W) & (c.j < g.H);
-  return c;
-}
-
-inline dim3 cell_grid(const GridDims& g) { return dim3((g.W + BX - 1) / BX, (g.H + BY - 1) / BY, g.B * g.KN); }
 
 // velocityDivergence, lib/fluid/velocity_divergence.py:46-74
 template <bool IS3D>

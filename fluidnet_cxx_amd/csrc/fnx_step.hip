@@ -13,6 +13,7 @@
 // stage sequence"): setConstVals (simulate.py:96), addBuoyancy on interior fluid cells whose -1 neighbour is fluid
 // (source_terms.py:47-116), setWallBcs (set_wall_bcs.py:45-84; skipped before the convnet, simulate.py:120), setConstVals
 // (simulate.py:133).
+#include "fnx_cells.h"
 #include "fnx_device.h"
 #include "fnx_kernels.h"
 #include "fnx_stage_word.h"
@@ -22,8 +23,6 @@
 namespace {
 
 using fnx::FlagConst;
-
-constexpr int BX = 64, BY = 4;
 
 struct StepPtrs {
   const float* U_adv; const float* rho_adv;          // advected fields (rho_adv may be null)
@@ -469,8 +468,6 @@ __global__ __launch_bounds__(256) void periodic_post_kernel(GridDims g, int nc, 
   if (UBC) { const float q = v * UBCInvMask[dst]; v = q + UBC[dst]; }
   U[dst] = v;
 }
-
-inline dim3 cell_grid(const GridDims& g) { return dim3((g.W + BX - 1) / BX, (g.H + BY - 1) / BY, g.B * g.KN); }
 
 }  // namespace
 

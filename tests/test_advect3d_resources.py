@@ -1,4 +1,4 @@
-"""The 3D advection tile kernels compile without scratch and without VGPR spills (CPU: hipcc cross-compiles for gfx950).  build_lib
+"""The 3D advection tile kernels and the 3D clamp-bounds reduction compile without scratch and without VGPR spills (CPU: hipcc cross-compiles for gfx950).  build_lib
 refuses such a build too; this test states it on its own and checks that the remark parser sees every guarded instantiation."""
 import os
 import subprocess
@@ -21,6 +21,8 @@ def test_advect3d_tile_kernels_use_no_scratch(tmp_path):
     # the instantiations a step launches: forward (density + velocity, both sample_outside modes) and the fused backward march
     assert build._scratch_users(p.stdout, "advect3d_fwd_tile_kernel")[1] == 6
     assert build._scratch_users(p.stdout, "advect3d_bwd_tile_kernel")[1] == 2
+    # the clamp-bounds reduction of the per-cell path and of the passive scalars (fnx_scalars.hip): both sample_outside modes
+    assert "box_minmax_kernel" in kernels and build._scratch_users(p.stdout, "box_minmax_kernel")[1] == 2
 
 
 def test_scratch_parser_flags_a_spill():

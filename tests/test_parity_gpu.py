@@ -1131,6 +1131,22 @@ def test_standalone_advection_tile_plan(fl, ext, dev, oracle, shape):
         assert_bitexact(N(fl.advectVelocity(0.13, tUn, tUn, tf, M, 1, 0.7, plan="tiles")), N(fl.advectVelocity(0.13, tUn, tUn, tf, M, 1, 0.7, plan="cells")), f"U, U sign {sign}")
 
 
+def test_cells_window_clamp_bounds_second_chunk(fl, ext, dev):
+    """The compute window of the block above on the per-cell kernels, deep enough for two z chunks of their clamp-bounds reduction:
+    planes [3, 23) of 26 widen to [1, 25), 24 planes, so the reduction's second 16-plane chunk starts at plane 17 from K0 = 1.  With
+    sigma 1.0 and dt 0.13, |U dt| <= 1 (5 sigma), what the widening by two planes covers."""
+    B, D, H, W, sigma = 1, 26, 12, 70, 1.0
+    s = random_state(B, D, H, W, sigma, seed=29, empties=True)
+    tf, tU, trho = T(s["flags"], dev), T(s["U"], dev), T(s["rho"], dev)
+    M = "maccormackFluidNet"
+    ro = torch.full_like(trho, 9.0)
+    ext.advect_scalar(0.13, trho, tU, tf, M, 1, False, 0.7, ro, ext.Geom(k_begin=3, k_end=23), "cells")
+    for plan in ("cells", "auto"):
+        whole = fl.advectScalar(0.13, trho, tU, tf, M, 1, False, 0.7, plan=plan)
+        assert_bitexact(N(ro)[:, :, 3:23], N(whole)[:, :, 3:23], f"window [3, 23) on cells vs the whole domain on {plan}")
+    assert (N(ro)[:, :, :3] == 9.0).all() and (N(ro)[:, :, 23:] == 9.0).all(), "planes outside the window are untouched"
+
+
 @pytest.mark.parametrize("D", [1, 10])
 def test_tile_trace_division_extremes(fl, ext, dev, oracle, D):
     """The tile kernels take the three quotients d_i / length of a line trace from ONE refined reciprocal (fnx_advect_march.h: adiv3);

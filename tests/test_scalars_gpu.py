@@ -13,8 +13,11 @@ from util import PLUME_CFG, assert_bitexact, plume_state, random_state
 pytestmark = pytest.mark.gpu
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MAC, EULER = "maccormackFluidNet", "eulerFluidNet"
-# (B, C, D, H, W): W = 70 crosses the 64-wide segment of the 3D tile kernels the comparator runs; C = 5 leaves a chunk remainder
-SHAPES = {"2d": (2, 5, 1, 20, 33), "3d": (2, 5, 9, 12, 70), "2d_c1": (2, 1, 1, 20, 33), "3d_c1": (2, 1, 9, 12, 70)}
+# (B, C, D, H, W): W = 70 crosses the 64-wide segment of the 3D tile kernels the comparator runs; C = 5: more channels than a sample has
+# velocity components.  3d_deep crosses every tile edge of the clamp-bounds reduction: D = 19 its 16-plane chunk, H = 35 its 32-row
+# workgroup, W = 70 its 62-column wave, and B = 2 x C = 3 tells a channel's plane stack from its sample's flags
+SHAPES = {"2d": (2, 5, 1, 20, 33), "3d": (2, 5, 9, 12, 70), "2d_c1": (2, 1, 1, 20, 33), "3d_c1": (2, 1, 9, 12, 70),
+          "3d_deep": (2, 3, 19, 35, 70)}
 
 
 @pytest.fixture(scope="module")
@@ -86,7 +89,7 @@ def test_channels_equal_advect_scalar_2d(dev, ext, oracle, name, method, so):
 @pytest.mark.parametrize("quirks", [0, 1])
 @pytest.mark.parametrize("so", [False, True])
 @pytest.mark.parametrize("method", [MAC, EULER])
-@pytest.mark.parametrize("name", ["3d", "3d_c1"])
+@pytest.mark.parametrize("name", ["3d", "3d_c1", "3d_deep"])
 def test_channels_equal_advect_scalar_3d(dev, ext, name, method, so, quirks):
     from fluidnet_cxx_amd import fluid
     c = _case(name)

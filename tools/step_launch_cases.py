@@ -4,7 +4,8 @@ to compare two builds launch by launch and bit by bit:
 
     rocprofv3 --kernel-trace --output-format csv -d OUT -o t -- python tools/step_launch_cases.py --lib A/libfluidnet_hip.so
     python tools/step_launch_cases.py --reduce OUT/.../t_kernel_trace.csv > a.txt     # the (kernel, grid, workgroup) launched, in order
-    python tools/step_launch_cases.py --lib A/libfluidnet_hip.so --digest > da.txt    # sha256 of p, U, density after two steps of each case
+    python tools/step_launch_cases.py --lib A/libfluidnet_hip.so --digest > da.txt    # sha256 of p, U, density after two steps of each case,
+                                                                                      # then of fnx_advect_scalars' output (scalars_digest)
 
 and the same for B: the reduced files must be identical, and the digests equal line for line.  The grids: 2D (2,1,40,70), 3D (1,9,20,66),
 and (2,6,21,66) with BC arrays that are the identity almost everywhere and the class map on (whole waves of identity cells, B > 1).  The
@@ -237,6 +238,26 @@ def run(lib, digest):
         print("x".join(map(str, shape)), "done", file=sys.stderr, flush=True)
 
 
+def scalars_digest(lib):
+    """fnx_advect_scalars on the shapes (B, C, D, H, W) of tests/test_scalars_gpu.py, MacCormack and Euler: sha256 of the output"""
+    import torch
+    lib.fnx_advect_scalars_workspace_bytes.restype = sz
+    lib.fnx_advect_scalars.argtypes = [ctypes.POINTER(FnxGrid), cf, ci, vp, vp, vp, vp, ci, ci, ci, cf, vp, sz, vp]
+    for B, C, D, H, W in ((2, 5, 1, 20, 33), (2, 5, 9, 12, 70), (2, 1, 1, 20, 33), (2, 1, 9, 12, 70), (2, 3, 19, 35, 70)):
+        F = Fields(lib, (B, D, H, W))
+        rng = np.random.default_rng(C + 11 * D)
+        t = {k: torch.from_numpy(v).to(F.dev) for k, v in dict(F.host, src=rng.random((B, C, D, H, W)).astype(np.float32),
+                                                               U=(rng.standard_normal(F.host["U"].shape) * 3).astype(np.float32)).items()}
+        g, out = F.grid(), torch.zeros((B, C, D, H, W), device=F.dev)
+        ws_bytes = lib.fnx_advect_scalars_workspace_bytes(ctypes.byref(g), C)
+        ws = torch.zeros(ws_bytes, dtype=torch.uint8, device=F.dev)
+        for method in (1, 0):
+            F.check(lib.fnx_advect_scalars(ctypes.byref(g), 1.0, C, t["src"].data_ptr(), t["U"].data_ptr(), t["flags"].data_ptr(),
+                                           out.data_ptr(), method, 1, 0, 0.6, ws.data_ptr(), ws_bytes, None), "fnx_advect_scalars")
+            torch.cuda.synchronize()
+            print("x".join(map(str, (B, C, D, H, W))), f"advect_scalars_method{method}", "out", sha(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lib", default=os.path.join(REPO, "fluidnet_cxx_amd", "libfluidnet_hip.so"))
@@ -245,7 +266,10 @@ def main():
     a = ap.parse_args()
     if a.reduce:
         return reduce(a.reduce)
-    run(load(a.lib), a.digest)
+    lib = load(a.lib)
+    run(lib, a.digest)
+    if a.digest:
+        scalars_digest(lib)
 
 
 if __name__ == "__main__":
