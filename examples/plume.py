@@ -3,7 +3,7 @@
 
     python examples/plume.py [--res 128] [--iters 200] [--out-iter 50] [--method jacobi|pcg|convnet|hybrid] [--weights CKPT]
                              [--pcg-warm] [--vorticity AMP] [--viscosity NU] [--depth N] [--weights3d CKPT] [--render] [--dyes N]
-                             [--folder out] [--restart]
+                             [--obstacle sphere|box|PATH.obj] [--folder out] [--restart]
 
 Same structure as the reference driver (plume.py:66-178 setup, :231-424 loop): build the batch, `createPlumeBCs`, optional
 restart from `<folder>/restart.pth`, echo the configuration as YAML, then `simulate()` per iteration and, every `out-iter`
@@ -21,7 +21,10 @@ of line traces): the inlet is cut into N equal sectors along x and dye n enters 
 event's scalars_<it>.png shows in red, green and blue where each sector's fluid goes; `--pcg-warm` starts the 'pcg' solve from the previous step's pressure (mconf['pcgWarmStart']).
 `--viscosity NU` sets mconf['viscosity'] (the velocity advected is fluid.addViscosity of U) for any --depth; the explicit update is
 stable for NU * dt <= 1/4 in 2D and <= 1/6 in 3D (dt is 0.1 here).  The native step has no 3D viscous stage, so with --depth > 1 the
-viscous step runs operator by operator (simulate(..., fused=False))."""
+viscous step runs operator by operator (simulate(..., fused=False)).
+`--obstacle sphere|box|PATH.obj` (with --depth N) puts a body into the 3D plume's way, centred at (res/2, 0.45 res, depth/2): a sphere of
+radius 0.12 res (fluid.createSphere), the cube of that half-width (fluid.createBox3D), or the closed triangle mesh of a Wavefront OBJ
+file scaled so that its longest side is 0.3 res (fluid.load_obj, fluid.voxelizeMesh) -- all written into flags on the device."""
 import argparse
 import os
 import sys
@@ -55,6 +58,8 @@ def parser():
     ap.add_argument("--render", action="store_true", help="write volume renderings (render_<view>_<it>.png) with every output event")
     ap.add_argument("--dyes", type=int, default=None, metavar="N",
                     help="carry N passive dyes (1..3), one per sector of the inlet along x (batch_dict['scalars']); default: none")
+    ap.add_argument("--obstacle", default=None, metavar="sphere|box|PATH.obj",
+                    help="a body in the 3D plume's way (needs --depth N): a sphere, a cube, or the closed mesh of an OBJ file")
     ap.add_argument("--folder", default="plume_out")
     ap.add_argument("--restart", action="store_true")
     return ap
@@ -72,6 +77,11 @@ def parse_args(argv=None):
         ap.error("--dyes must be 1, 2 or 3 (the channels of scalars_<it>.png)")
     if a.depth < 1 or a.depth == 2:
         ap.error("--depth must be 1 (2D) or at least 3")
+    if a.obstacle is not None:
+        if a.depth == 1:
+            ap.error("--obstacle places a 3D body: it needs --depth N (N > 1)")
+        if a.obstacle not in ("sphere", "box") and not a.obstacle.lower().endswith(".obj"):
+            ap.error("--obstacle must be 'sphere', 'box' or the path of a .obj file")
     if a.depth > 1:
         if a.weights is not None:
             ap.error("--weights with --depth > 1: no 3D weights can be trained here by the 2D trainer this checkpoint comes from; "
@@ -103,6 +113,24 @@ def add_dyes(batch_dict, n):
     batch_dict["scalars"] = torch.zeros_like(bc)
     batch_dict["scalarsBC"] = bc
     batch_dict["scalarsBCInvMask"] = mask.expand_as(bc).contiguous()
+
+
+def add_obstacle(batch_dict, what, res, depth):
+    """the body of --obstacle, centred at (res/2, 0.45 res, depth/2), written into batch_dict['flags'] on the device"""
+    cx, cy, cz, r = res / 2, 0.45 * res, depth / 2, 0.12 * res
+    if what == "sphere":
+        fluid.createSphere(batch_dict, cx, cy, cz, r)
+    elif what == "box":
+        fluid.createBox3D(batch_dict, cx - r, cx + r, cy - r, cy + r, cz - r, cz + r)
+    else:
+        v, f = fluid.load_obj(what)
+        if len(v) == 0 or len(f) == 0:
+            sys.exit(f"plume.py: {what} holds no vertices or no faces")
+        lo, hi = v.min(axis=0), v.max(axis=0)
+        v = (v - (lo + hi) / 2) * (0.3 * res / float((hi - lo).max())) + (cx, cy, cz)
+        dev = batch_dict["flags"].device
+        # check=True: an open or broken mesh raises here, before the first step (the one synchronisation of the setup)
+        fluid.voxelizeMesh(batch_dict, torch.from_numpy(v).float().to(dev), torch.from_numpy(f).to(dev))
 
 
 def main(argv=None):
@@ -142,6 +170,8 @@ def main(argv=None):
     fluid.emptyDomain(flags)
     batch_dict = dict(p=p, U=U, flags=flags, density=density)
     fluid.createPlumeBCs(batch_dict, 0.1, 2, 0.145)
+    if a.obstacle is not None:                            # (a restart brings its flags, body included)
+        add_obstacle(batch_dict, a.obstacle, a.res, a.depth)
     it = 0
     restart_file = os.path.join(a.folder, "restart.pth")
     if a.restart:                                         # plume.py:168-175

@@ -29,6 +29,7 @@ HIP_UNITS = {
     "fnx_viscous.hip": ["-ffp-contract=off", "-Rpass-analysis=kernel-resource-usage"],
     "fnx_scenes.hip": ["-ffp-contract=off", "-Rpass-analysis=kernel-resource-usage"],
     "fnx_render.hip": ["-ffp-contract=off", "-Rpass-analysis=kernel-resource-usage"],
+    "fnx_voxelize.hip": ["-ffp-contract=off", "-Rpass-analysis=kernel-resource-usage"],
     "fnx_api.hip": ["-ffp-contract=off"],
     # (resource-usage remarks: build_lib checks the kernels of SCRATCH_FREE)
     "fnx_cnn.hip": ["-Rpass-analysis=kernel-resource-usage"],
@@ -91,6 +92,9 @@ SCRATCH_FREE = {
                        "they are streaming kernels with a handful of live values per thread in either dimension (the 3D turbulence "
                        "thread's nine potential values, the loss's fp64 partial sums); scratch there would mean the octave loop, the "
                        "per-axis arrays or the partial sums were turned into arrays in memory"),
+    "fnx_voxelize.hip": (["geometry3d_kernel", "voxel_faces_kernel", "voxel_fill_kernel"],
+                         "a face lane holds nine snapped coordinates and the box of its rows, a fill lane one word and a carry; scratch "
+                         "there would mean the face record handed between lanes was turned into an array in memory"),
     "fnx_render.hip": (["render_march_kernel", "render_march_x_kernel"],
                        "a column's running light, transmittance and radiance live in registers for the whole march; scratch there "
                        "would put a memory round trip between every two cells of a serial chain"),

@@ -512,6 +512,58 @@ void create_box2d_(Tensor flags, double x0, double x1, double y0, double y1) {
   wrote(flags);
 }
 
+// 3D obstacles from geometry (no reference counterpart): any batch, sample -1 = every sample
+void create_sphere_(Tensor flags, double center_x, double center_y, double center_z, double radius, int64_t sample) {
+  FnxGrid g = grid_of(flags, flags.size(2) > 1, nullptr);
+  c10::hip::HIPGuard guard(flags.get_device());
+  check_status(fnx_create_sphere(&g, flags.data_ptr<float>(), center_x, center_y, center_z, radius, (int)sample, cur_stream(flags)));
+  wrote(flags);
+}
+
+void create_box3d_(Tensor flags, double x0, double x1, double y0, double y1, double z0, double z1, int64_t sample) {
+  FnxGrid g = grid_of(flags, flags.size(2) > 1, nullptr);
+  c10::hip::HIPGuard guard(flags.get_device());
+  check_status(fnx_create_box3d(&g, flags.data_ptr<float>(), (float)x0, (float)x1, (float)y0, (float)y1, (float)z0, (float)z1, (int)sample,
+                                cur_stream(flags)));
+  wrote(flags);
+}
+
+int64_t voxelize_mesh_ws_bytes(Tensor flags) {
+  FnxGrid g = grid_of(flags, flags.size(2) > 1, nullptr);
+  const size_t bytes = fnx_voxelize_mesh_ws_bytes(&g);
+  TORCH_CHECK(bytes > 0, fnx_last_error());
+  return (int64_t)bytes;
+}
+
+// returns the report {open rows, bad faces} as a device int32[2]; never synchronises.  workspace (optional): a device byte tensor of at
+// least voxelize_mesh_ws_bytes(flags) bytes to use instead of one from the caching allocator
+Tensor voxelize_mesh_(Tensor flags, Tensor vertices, Tensor faces, int64_t sample, c10::optional<Tensor> workspace) {
+  FnxGrid g = grid_of(flags, flags.size(2) > 1, nullptr);
+  TORCH_CHECK(vertices.is_cuda() && faces.is_cuda() && vertices.get_device() == flags.get_device() && faces.get_device() == flags.get_device(),
+              "vertices and faces must be on the device of flags");
+  TORCH_CHECK(vertices.scalar_type() == at::kFloat && vertices.dim() == 2 && vertices.size(1) == 3 && vertices.is_contiguous(),
+              "vertices must be a contiguous (V,3) float32 tensor");
+  TORCH_CHECK(faces.scalar_type() == at::kInt && faces.dim() == 2 && faces.size(1) == 3 && faces.is_contiguous(),
+              "faces must be a contiguous (F,3) int32 tensor");
+  TORCH_CHECK(vertices.size(0) < (1ll << 31) && faces.size(0) < (1ll << 31), "more than 2^31 vertices or faces");
+  c10::hip::HIPGuard guard(flags.get_device());
+  const size_t need = fnx_voxelize_mesh_ws_bytes(&g);
+  TORCH_CHECK(need > 0, fnx_last_error());
+  Tensor ws;
+  if (workspace.has_value() && workspace->defined()) {
+    ws = *workspace;
+    TORCH_CHECK(ws.is_cuda() && ws.get_device() == flags.get_device() && ws.scalar_type() == at::kByte && ws.is_contiguous(),
+                "workspace must be a contiguous uint8 tensor on the device of flags");
+  } else {
+    ws = at::empty({(int64_t)need}, flags.options().dtype(at::kByte));
+  }
+  Tensor report = at::empty({2}, flags.options().dtype(at::kInt));
+  check_status(fnx_voxelize_mesh(&g, flags.data_ptr<float>(), vertices.data_ptr<float>(), (int)vertices.size(0), faces.data_ptr<int>(),
+                                 (int)faces.size(0), (int)sample, report.data_ptr<int>(), ws.data_ptr(), (size_t)ws.numel(), cur_stream(flags)));
+  wrote(flags);
+  return report;
+}
+
 // lib/fluid/grid.py:7-32
 Tensor get_centered(Tensor U) {
   check_field(U, "U");
@@ -1314,6 +1366,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("velocity_update_backward", &velocity_update_backward, py::arg("grad_U_out"), py::arg("flags"), GEOM, NoGil());
   m.def("create_cylinder_", &create_cylinder_, NoGil());
   m.def("create_box2d_", &create_box2d_, NoGil());
+  m.def("create_sphere_", &create_sphere_, py::arg("flags"), py::arg("center_x"), py::arg("center_y"), py::arg("center_z"), py::arg("radius"),
+        py::arg("sample") = -1, NoGil());
+  m.def("create_box3d_", &create_box3d_, py::arg("flags"), py::arg("x0"), py::arg("x1"), py::arg("y0"), py::arg("y1"), py::arg("z0"),
+        py::arg("z1"), py::arg("sample") = -1, NoGil());
+  m.def("voxelize_mesh_ws_bytes", &voxelize_mesh_ws_bytes, NoGil());
+  m.def("voxelize_mesh_", &voxelize_mesh_, "mesh -> obstacle cells of flags; returns the device report {open rows, bad faces} (fnx_voxelize_mesh)",
+        py::arg("flags"), py::arg("vertices"), py::arg("faces"), py::arg("sample") = -1, py::arg("workspace") = py::none(), NoGil());
   m.def("get_centered", &get_centered, NoGil());
   m.def("scalenet_pack", &scalenet_pack, NoGil());
   m.def("multiscale_forward", &multiscale_forward, py::arg("packed"), py::arg("x"), py::arg("precision_mode") = "fp32",

@@ -827,6 +827,67 @@ int fnx_create_box2d(const FnxGrid* g, float* flags, float x0, float x1, float y
   return FNX_OK;
 }
 
+// 3D obstacles from geometry (fnx_voxelize.hip): whole 3D domains only, any batch; sample -1 = every sample
+static int check_geometry3d(const char* name, const FnxGrid* g, const float* flags, int sample) {
+  if (int rc = check_grid(g)) return rc;
+  if (!g->is3D) return fail(FNX_EINVAL, "%s: 3D grids only (a 2D obstacle is createCylinder's or createBox2D's)", name);
+  if (is_view(g)) return fail(FNX_EINVAL, "%s: whole domains only, not a compute window or a z-slab view", name);
+  if (!flags) return fail(FNX_EINVAL, "%s: NULL tensor", name);
+  if (sample < -1 || sample >= g->B) return fail(FNX_EINVAL, "%s: sample %d out of range for B=%d", name, sample, g->B);
+  return FNX_OK;
+}
+
+int fnx_create_sphere(const FnxGrid* g, float* flags, double center_x, double center_y, double center_z, double radius, int sample,
+                      void* stream) {
+  if (int rc = check_geometry3d("create_sphere", g, flags, sample)) return rc;
+  const float r2 = (float)(radius * radius);               // as fnx_create_cylinder
+  fnx::launch_create_sphere(dims(g), flags, sample < 0 ? 0 : sample, sample < 0 ? g->B : 1, (float)center_x, (float)center_y,
+                            (float)center_z, r2, (hipStream_t)stream);
+  HIP_OK(hipGetLastError());
+  return FNX_OK;
+}
+
+int fnx_create_box3d(const FnxGrid* g, float* flags, float x0, float x1, float y0, float y1, float z0, float z1, int sample,
+                     void* stream) {
+  if (int rc = check_geometry3d("create_box3d", g, flags, sample)) return rc;
+  fnx::launch_create_box3d(dims(g), flags, sample < 0 ? 0 : sample, sample < 0 ? g->B : 1, x0, x1, y0, y1, z0, z1, (hipStream_t)stream);
+  HIP_OK(hipGetLastError());
+  return FNX_OK;
+}
+
+static int check_voxelize_grid(const FnxGrid* g) {
+  if (int rc = check_grid(g)) return rc;
+  if (!g->is3D) return fail(FNX_EINVAL, "voxelize_mesh: 3D grids only");
+  if (is_view(g)) return fail(FNX_EINVAL, "voxelize_mesh: whole domains only, not a compute window or a z-slab view");
+  return FNX_OK;
+}
+
+size_t fnx_voxelize_mesh_ws_bytes(const FnxGrid* g) {
+  if (check_voxelize_grid(g) != FNX_OK) return 0;
+  return (fnx::voxel_words(dims(g)) + 2) * 4;
+}
+
+int fnx_voxelize_mesh(const FnxGrid* g, float* flags, const float* vertices, int n_vertices, const int* faces, int n_faces, int sample,
+                      int* report, void* ws, size_t ws_bytes, void* stream) {
+  if (int rc = check_voxelize_grid(g)) return rc;
+  if (n_vertices < 0 || n_faces < 0) return fail(FNX_EINVAL, "voxelize_mesh: n_vertices=%d n_faces=%d must not be negative", n_vertices, n_faces);
+  // (an empty array may have no address: a mesh without faces marks nothing, a mesh without vertices has bad faces only)
+  if (!flags || (!vertices && n_vertices > 0) || (!faces && n_faces > 0)) return fail(FNX_EINVAL, "voxelize_mesh: NULL tensor");
+  if (sample < -1 || sample >= g->B) return fail(FNX_EINVAL, "voxelize_mesh: sample %d out of range for B=%d", sample, g->B);
+  const GridDims d = dims(g);
+  const size_t words = fnx::voxel_words(d), need = (words + 2) * 4;
+  if (!ws || need > ws_bytes) return fail(FNX_EWORKSPACE, "voxelize_mesh: workspace too small (%zu < %zu)", ws ? ws_bytes : (size_t)0, need);
+  if (((size_t)ws & 3) != 0) return fail(FNX_EINVAL, "voxelize_mesh: the workspace must be 4-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  unsigned* bits = (unsigned*)ws;
+  int* counters = (int*)(bits + words);                    // {open rows, bad faces}
+  HIP_OK(hipMemsetAsync(ws, 0, need, s));
+  fnx::launch_voxelize_mesh(d, flags, sample < 0 ? 0 : sample, sample < 0 ? g->B : 1, vertices, n_vertices, faces, n_faces, bits, counters, s);
+  HIP_OK(hipGetLastError());
+  if (report) HIP_OK(hipMemcpyAsync(report, counters, 8, hipMemcpyDeviceToDevice, s));
+  return FNX_OK;
+}
+
 int fnx_get_centered(const FnxGrid* g, const float* U, float* centered, void* stream) {
   // a pure per-cell average: any block of a field is a valid input (the drivers pass interior blocks, plume.py:351), so
   // only the launch limits are checked, not the operators' minimum domain size

@@ -85,6 +85,17 @@ void launch_divergence_bwd(const GridDims& g, bool is3d, const float* gdiv, cons
 void launch_velocity_update_bwd(const GridDims& g, bool is3d, const float* gout, const float* flags, float* gU, float* gp,
                                 hipStream_t s);
 
+// 3D obstacles from geometry (fnx_voxelize.hip): whole 3D domains; the samples [b0, b0 + nb) are written.  The mesh voxeliser's
+// workspace is one toggle bit per (k, j, i0), i0 in 0..W, in 32-bit words by rows, then two counters (open rows, bad faces); the
+// caller zeroes all of it before the launch.
+inline int voxel_words_per_row(const GridDims& g) { return g.W / 32 + 1; }                       // ceil((W + 1) / 32)
+inline size_t voxel_words(const GridDims& g) { return (size_t)g.D * g.H * voxel_words_per_row(g); }
+void launch_create_sphere(const GridDims& g, float* flags, int b0, int nb, float cx, float cy, float cz, float r2, hipStream_t s);
+void launch_create_box3d(const GridDims& g, float* flags, int b0, int nb, float x0, float x1, float y0, float y1, float z0, float z1,
+                         hipStream_t s);
+void launch_voxelize_mesh(const GridDims& g, float* flags, int b0, int nb, const float* vertices, int n_vertices, const int* faces,
+                          int n_faces, unsigned* bits, int* counters, hipStream_t s);
+
 // the viscous-flow operators in 3D (fnx_viscous.hip; default semantics only: the reference has no 3D form to reproduce).  Both are out
 // of place, Uout must not alias Uin.  addViscosity marches whole grids along z; setWallBcsStick honours a compute window and a z-slab view
 void launch_add_viscosity3d(const GridDims& g, const float* Uin, float* Uout, const float* flags, float coef, hipStream_t s);

@@ -17,8 +17,9 @@ from .ops import (advectScalar, advectScalars, advectVelocity, correctScalar, so
                   velocityUpdate, addBuoyancy, addGravity, addViscosity, addVorticityConfinement, setWallBcs, setWallBcsStick, flagsToOccupancy, setConstVals,
                   getDx, getCentered, renderVolume)
 from .init_conditions import emptyDomain, createPlumeBCs, createRayleighTaylorBCs
-from .geometry_utils import createCylinder, createBox2D
+from .geometry_utils import createCylinder, createBox2D, createSphere, createBox3D, voxelizeMesh, load_obj
 
 __all__ = ["CellType", "Geom", "advectScalar", "advectScalars", "advectVelocity", "correctScalar", "solveLinearSystemJacobi", "solveLinearSystemPCG",
            "velocityDivergence", "velocityUpdate", "addBuoyancy", "addGravity", "addViscosity", "addVorticityConfinement", "setWallBcs", "setWallBcsStick", "flagsToOccupancy", "setConstVals",
-           "getDx", "getCentered", "renderVolume", "emptyDomain", "createPlumeBCs", "createRayleighTaylorBCs", "createCylinder", "createBox2D"]
+           "getDx", "getCentered", "renderVolume", "emptyDomain", "createPlumeBCs", "createRayleighTaylorBCs", "createCylinder", "createBox2D",
+           "createSphere", "createBox3D", "voxelizeMesh", "load_obj"]

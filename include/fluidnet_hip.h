@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define FNX_ABI_VERSION 35
+#define FNX_ABI_VERSION 36
 
 enum {
   FNX_OK = 0,
@@ -360,6 +360,28 @@ int fnx_create_cylinder(const FnxGrid* g, float* flags, double center_x, double 
  * reference's body cannot run (it tests Y against y1 twice and names an undefined mask, :59-62); this is the box its
  * docstring describes.  In place on flags. */
 int fnx_create_box2d(const FnxGrid* g, float* flags, float x0, float x1, float y0, float y1, void* stream);
+
+/* 3D obstacles from geometry (ABI 36; no reference counterpart).  Cell (i, j, k) sits at the point (x, y, z) = (i, j, k), as for
+ * fnx_create_cylinder.  Each call writes FNX_TYPE_OBSTACLE into the cells it finds inside, whatever they held, and touches no other
+ * cell.  flags is (B,1,D,H,W) with B >= 1; sample = -1 applies the shape to every sample, sample = b to that one alone.  3D only: a
+ * 2D grid, a compute window and a z-slab view are each refused, and every refusal comes before a pointer is read.
+ * Sphere: dx*dx + dy*dy + dz*dz <= r*r in fp32, summed in that order -- fnx_create_cylinder's arithmetic with a third term (the
+ * slice k == center_z is the cylinder's disc bit for bit).  Box: half open, x0 <= i < x1 and the same for y and z. */
+int fnx_create_sphere(const FnxGrid* g, float* flags, double center_x, double center_y, double center_z, double radius, int sample,
+                      void* stream);
+int fnx_create_box3d(const FnxGrid* g, float* flags, float x0, float x1, float y0, float y1, float z0, float z1, int sample,
+                     void* stream);
+/* Triangle-mesh voxeliser: marks the cells whose point lies inside the closed surface, by the even-odd rule along x (overlapping closed
+ * components cancel; for a union call once per component).  vertices: n_vertices x 3 float32 xyz, faces: n_faces x 3 int32, both on
+ * the device (an array of no elements may be NULL).  The exact rule (snap to 1/64 cell, integer cover test per row, fp64 crossing position) is stated in DESIGN.md 34 and
+ * tests/voxel_reference.py.  A face with an index outside [0, n_vertices), a NaN or Inf coordinate or a vertex farther than 2^14
+ * cells from the origin is skipped and counted; nothing is read out of bounds for any input.  report (device int[2], may be NULL)
+ * receives {open rows, bad faces}: a closed surface has no open row.  ws: fnx_voxelize_mesh_ws_bytes(g) bytes, 4-byte aligned --
+ * (D*H*ceil((W+1)/32) + 2) * 4, whatever the face count; the call zeroes it on `stream` itself, so it can be captured into a graph
+ * and replayed.  The toggles are integer XOR atomics: the result does not depend on their order. */
+size_t fnx_voxelize_mesh_ws_bytes(const FnxGrid* g);   /* 0 (and fnx_last_error) for a grid the voxeliser refuses */
+int fnx_voxelize_mesh(const FnxGrid* g, float* flags, const float* vertices, int n_vertices, const int* faces, int n_faces, int sample,
+                      int* report, void* ws, size_t ws_bytes, void* stream);
 /* getCentered, lib/fluid/grid.py:7-32: (B,2|3,D,H,W) MAC velocity -> (B,3,D,H,W) cell-centred velocity (the z channel
  * is 0 in 2D); what the drivers' field dumps plot (plume.py:243,336). */
 int fnx_get_centered(const FnxGrid* g, const float* U, float* centered, void* stream);
